@@ -77,7 +77,14 @@ def parse():
     ap.add_argument("--workload", default="S1", choices=["S1", "S2", "S1c"],
                     help="S1: every point seen by --views images (headline); S2: ragged view counts "
                          "min(views, 1 + Geom(0.2)), 10 %% of the points unseen (SURVEY.md 8(d))")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) to DIR/<name>.npy in "
+                         "float32, at most 64 MB in all: fused features, feature-map gradient (fixed seeded samples when "
+                         "larger than 24 MB) and the view pooling module's parameter gradients (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def make_scene(n_points, views, n_images, C, H, W, dtype, device, seed, workload="S1", upscale=1):
@@ -1151,6 +1158,45 @@ def emit(res, json_fd, detail_file=None):
     os.write(json_fd, (json.dumps(compact_line(res, os.path.basename(paths[0]) if paths else DETAIL_FILE)) + "\n").encode())
 
 
+DUMP_BUDGET_BYTES = 64 << 20     # --dump-outputs: all files together
+DUMP_SAMPLE_BYTES = 24 << 20     # per sampled array (fused features, feature-map gradient)
+DUMP_SEED = 20240601
+
+
+def dump_outputs(out_dir, fused, x, view_pool):
+    """--dump-outputs DIR: what the last timed step handed its caller, as float32 .npy files, so that two builds can be
+    compared output for output on identical inputs (the scene, the module weights and the upstream gradient are seeded).
+      fused.npy               rows of the fused features [N, 4 + C] (all rows if they fit DUMP_SAMPLE_BYTES, else a fixed
+                              seeded sample of rows in ascending order)
+      x_grad.npy              gradient of the feature maps, flattened in logical [B, C, H, W] order (all of it or a fixed
+                              seeded sample of elements in ascending order)
+      grad_<parameter>.npy    gradient of every parameter of the view pooling module (whole)
+    Returns {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    arrays = {}
+    n, cols = fused.shape
+    k = min(n, max(1, DUMP_SAMPLE_BYTES // (4 * cols)))
+    rows = torch.arange(n) if k == n else torch.randperm(n, generator=g)[:k].sort()[0]
+    arrays["fused"] = fused.detach()[rows.to(fused.device)].float()
+    if x.grad is not None:
+        gx = x.grad.detach().float().reshape(-1)
+        k = min(gx.numel(), DUMP_SAMPLE_BYTES // 4)
+        idx = torch.arange(gx.numel()) if k == gx.numel() else torch.randperm(gx.numel(), generator=g)[:k].sort()[0]
+        arrays["x_grad"] = gx[idx.to(gx.device)]
+    for name, p in view_pool.named_parameters():
+        if p.grad is not None:
+            arrays["grad_" + name.replace(".", "_")] = p.grad.detach().float()
+    arrays = {name: a.cpu().numpy() for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (> {DUMP_BUDGET_BYTES})")
+    import numpy as np
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def dry_run(args, world, rank, local_rank, json_fd):
     """Hidden `--dry-run` (tests/test_bench_launcher.py): everything bench.py does to become N ranks -- launcher,
     rendezvous, process group, rank / device census, the gradient bucket's all-reduce, max-over-ranks timing -- with
@@ -1301,6 +1347,10 @@ def main():
     alloc_in_region = {k: int(mem1.get(k, 0) - mem0.get(k, 0)) for k in
                        ("num_device_alloc", "num_device_free", "num_alloc_retries", "num_ooms")}
     timer, ops.TIMER = ops.TIMER, None
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # outside the timed region, before the secondary workloads release the scene
+        dumped = dump_outputs(args.dump_outputs, fused, scene["x"], mods[1])
     per_step_device_ms = [a.elapsed_time(b) for a, b in zip(marks[:-1], marks[1:])]
     per_step_host_ms = [(b - a) * 1e3 for a, b in zip(host[:-1], host[1:])]
     collective = None
@@ -1394,6 +1444,8 @@ def main():
             "fused_abs_mean": float(fused.float().abs().mean().item()),
         }
         res["step_algorithmic_GBps"] = res["step_algorithmic_GB"] / (ms_per_step * 1e-3)
+        if dumped is not None:
+            res["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if _LIVE_PMC["table"] is not None:
             res["pmc_live"] = {"calibration_on_copy_kernel": _LIVE_PMC["table"].get("_calibration"),
                                "hbm_bytes_per_launch": {t: (_pmc_lookup(_LIVE_PMC["table"], t) or {}).get("hbm_bytes")

@@ -19,6 +19,7 @@ as np.float64.  Candidate order (KDTree order in the reference) is an explicit i
 
 Usage:  PYTORCH_JIT=0 python oracle/gen_golden.py
 """
+import copy
 import os
 import sys
 import types
@@ -65,6 +66,30 @@ def randomize(module, gen):
 
 def state(module, prefix='sd/'):
     return {prefix + k: v.clone() for k, v in module.state_dict().items()}
+
+
+def f64_pass(module, x_main, x_mod, x_map, csr, w):
+    """The same reference module (a copy taken before its fp32 forward) on the same inputs, in float64: the arrays of
+    the companion file <name>_f64.npz (same key names as the fp32 file).  A float32 output carries the rounding of the
+    host's BLAS kernels (they differ between CPUs), amplified where terms cancel; the float64 outputs pin the maths
+    alone, on any host."""
+    m = module.double()
+    m.save_last = True
+    d = lambda v: v.detach().double().requires_grad_() if v is not None else None
+    x_main, x_mod, x_map = d(x_main), d(x_mod), d(x_map)
+    out = m(x_main, x_mod, x_map, csr)
+    ins = [x_mod, x_map] + ([x_main] if x_main is not None else [])
+    grads = torch.autograd.grad((out * w.double()).sum(), ins + list(m.parameters()), allow_unused=True)
+    res = {'out': out, 'grad_x_mod': grads[0], 'grad_x_map': grads[1]}
+    if x_main is not None:
+        res['grad_x_main'] = grads[2]
+    for k in ('C', 'A', 'G'):
+        if getattr(m, '_last_' + k, None) is not None:
+            res['last_' + k] = getattr(m, '_last_' + k)
+    for (n, p), g in zip(m.named_parameters(), grads[len(ins):]):
+        res['gp/' + n] = g if g is not None else torch.zeros_like(p)
+    res.update(state(m, prefix='sd_after/'))
+    return res
 
 
 def random_csr(n_groups, max_size, gen, p_empty=0.2):
@@ -122,6 +147,7 @@ def pool_case(name, cls, kwargs, N, max_views, C, F_map, F_main, gen, train):
     randomize(module, gen)
     module.train(train)
     sd = state(module)
+    twin = copy.deepcopy(module)
     x_mod = torch.randn(V, C, generator=gen, requires_grad=True)
     x_map = torch.rand(V, F_map, generator=gen, requires_grad=True)
     x_main = torch.randn(N, F_main, generator=gen, requires_grad=True) if F_main else None
@@ -145,6 +171,7 @@ def pool_case(name, cls, kwargs, N, max_views, C, F_map, F_main, gen, train):
     res.update(sd)
     res['kwargs'] = np.array(repr(kwargs))
     save(name, **res)
+    save(name + "_f64", **f64_pass(twin, x_main, x_mod, x_map, csr, w))
 
 
 def gen_pools():
@@ -213,6 +240,7 @@ def gen_pools_headline():
         randomize(module, gen)
         module.train(train)
         sd = state(module)
+        twin = copy.deepcopy(module)
         x_mod = torch.randn(V, 64, generator=gen).bfloat16().float().requires_grad_()
         x_map = torch.rand(V, 8, generator=gen)
         module.save_last = True
@@ -227,6 +255,7 @@ def gen_pools_headline():
         res.update(sd)
         res['kwargs'] = np.array(repr(kwargs))
         save(name, **res)
+        save(name + "_f64", **f64_pass(twin, None, x_mod, x_map, csr, w))
 
 
 def gen_pools_bilinear():

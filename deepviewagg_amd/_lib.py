@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # DVA_LIB_PATH: another build of the same sources (compile-time A/B variants, csrc/Makefile LIB= / EXTRA=) -- tools only
 LIB_PATH = os.environ.get("DVA_LIB_PATH") or os.path.join(_HERE, "csrc", "libdva_hip.so")
 
-DVA_F32, DVA_BF16 = 0, 1
+DVA_F32, DVA_BF16, DVA_F16 = 0, 1, 2
 DVA_SUM, DVA_MEAN, DVA_MAX, DVA_MIN = 0, 1, 2, 3
 REDUCE_CODE = {"sum": DVA_SUM, "add": DVA_SUM, "mean": DVA_MEAN, "max": DVA_MAX, "min": DVA_MIN}
 CAMERA_CODE = {
@@ -132,6 +132,8 @@ SIGNATURES = {
     "dva_chain_bwd_layer6_a2": (ctypes.c_int, [_vp] * 13 + [_i32, _i64, _i64, _vp]),
     "dva_chain_attn_fwd": (ctypes.c_int, [_vp] * 18 + [_i64, _i64, _i64, _i32, _i32, _i32, _f32, _vp]),
     "dva_chain_attn_bwd": (ctypes.c_int, [_vp] * 14 + [_i64, _i64, _i64, _i32, _i32, _i32, _f32, _vp]),
+    "dva_chain_attn_fwd_dt": (ctypes.c_int, [_vp] * 18 + [_i64, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _vp]),
+    "dva_chain_attn_bwd_dt": (ctypes.c_int, [_vp] * 14 + [_i64, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _vp]),
     "dva_chain_attn_bwd_f32": (ctypes.c_int, [_vp] * 14 + [_i64, _i64, _i64, _i32, _i32, _i32, _f32, _vp]),
     "dva_gather_segment_max_fwd": (ctypes.c_int, [_vp] * 5 + [_i64, _i64, _i64, _i32, _i32, _vp]),
     "dva_gather_segment_max_bwd": (ctypes.c_int, [_vp] * 8 + [_i64, _i64, _i64, _i32, _i32, _vp]),
@@ -286,7 +288,9 @@ def dtype_code(t):
         return DVA_F32
     if t.dtype == torch.bfloat16:
         return DVA_BF16
-    raise TypeError(f"deepviewagg_amd kernels take float32 or bfloat16 features, got {t.dtype}")
+    if t.dtype == torch.float16:
+        return DVA_F16
+    raise TypeError(f"deepviewagg_amd kernels take float32, bfloat16 or float16 features, got {t.dtype}")
 
 
 def require_device(*tensors):

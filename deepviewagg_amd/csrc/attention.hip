@@ -207,6 +207,14 @@ struct Vec16<bf16_t> {
   }
 };
 
+template <>
+struct Vec16<f16_t> {
+  static constexpr int N = 8;
+  typedef uint4 raw;
+  static __device__ __forceinline__ void unpack(const raw& r, float* f) { unpack_h8<f16_t>(r, f); }
+  static __device__ __forceinline__ raw pack(const float* f) { return pack_h8<f16_t>(f); }
+};
+
 struct TeamGeom {
   int lpr;      // lanes per view row (power of two, <= 64)
   int rows;     // view rows in flight per team (power of two)
@@ -1422,6 +1430,37 @@ static int rows_grad_impl(const void* gout, const float* att, const float* gate,
 
 using namespace dva;
 
+// T = the 2-byte dtype of grad_out; to_16: the rows come out in T (rounded once where they are summed), else fp32
+template <typename T>
+static void rows_grad_rec16_launch(const void* grad_out, const int32_t* perm, const int32_t* row_ptr,
+                                   const void* view_rec16, void* grad_rows, bool to_16, int64_t n_rows, int64_t n_views,
+                                   int C, int G, int slab, hipStream_t s) {
+  const int lpr = C / 8, lpr_s = slab / 8;
+  if (n_views <= 2 * n_rows && lpr < 64) {
+    // sparse plan (view-level identity gathers): a lane team per row
+    const int64_t waves = (n_rows + (64 / lpr) - 1) / (64 / lpr);
+    if (to_16)
+      hipLaunchKernelGGL((rows_grad_short_rec16_kernel<T, T>), dim3(grid_cap((waves + 3) / 4)), dim3(256), 0, s,
+                         (const T*)grad_out, perm, row_ptr, (const uint32_t*)view_rec16, (T*)grad_rows, n_rows, C, lpr,
+                         lpr / G);
+    else
+      hipLaunchKernelGGL((rows_grad_short_rec16_kernel<T>), dim3(grid_cap((waves + 3) / 4)), dim3(256), 0, s,
+                         (const T*)grad_out, perm, row_ptr, (const uint32_t*)view_rec16, (float*)grad_rows, n_rows, C,
+                         lpr, lpr / G);
+    return;
+  }
+  for (int c0 = 0; c0 < C; c0 += slab) {
+    if (to_16)
+      hipLaunchKernelGGL((rows_grad_team_kernel<T, true, T>), dim3(grid_cap((n_rows + 3) / 4)), dim3(256), 0, s,
+                         (const T*)grad_out, (const float*)nullptr, (const float*)nullptr, (const int32_t*)nullptr, perm,
+                         row_ptr, (const float*)view_rec16, 4, (T*)grad_rows, n_rows, C, G, lpr_s, lpr / G, c0);
+    else
+      hipLaunchKernelGGL((rows_grad_team_kernel<T, true>), dim3(grid_cap((n_rows + 3) / 4)), dim3(256), 0, s,
+                         (const T*)grad_out, (const float*)nullptr, (const float*)nullptr, (const int32_t*)nullptr, perm,
+                         row_ptr, (const float*)view_rec16, 4, (float*)grad_rows, n_rows, C, G, lpr_s, lpr / G, c0);
+  }
+}
+
 extern "C" {
 
 static int attention_fwd_entry(const void* val, const int32_t* row_idx, const float* compat,
@@ -1440,6 +1479,9 @@ static int attention_fwd_entry(const void* val, const int32_t* row_idx, const fl
                          n_views, C, G, scaling, eps, algo, (hipStream_t)stream);
   else if (dtype == DVA_BF16)
     rc = fwd_impl<bf16_t>(val, row_idx, compat, ptr, gate_w, gate_b, out, att, gate, amax, n_points,
+                          n_views, C, G, scaling, eps, algo, (hipStream_t)stream);
+  else if (dtype == DVA_F16)
+    rc = fwd_impl<f16_t>(val, row_idx, compat, ptr, gate_w, gate_b, out, att, gate, amax, n_points,
                           n_views, C, G, scaling, eps, algo, (hipStream_t)stream);
   else
     return DVA_ERR_INVALID;
@@ -1470,6 +1512,10 @@ static int attention_bwd_entry(const void* grad_out, const void* val, const int3
                          scaling, algo, (hipStream_t)stream);
   else if (dtype == DVA_BF16)
     rc = bwd_impl<bf16_t>(grad_out, val, row_idx, grad_rows, compat, att, gate, amax, ptr, gate_w,
+                          grad_val, grad_compat, grad_gate_wb, view_rec, rec_stride, n_points, n_views, C, G,
+                          scaling, algo, (hipStream_t)stream);
+  else if (dtype == DVA_F16)
+    rc = bwd_impl<f16_t>(grad_out, val, row_idx, grad_rows, compat, att, gate, amax, ptr, gate_w,
                           grad_val, grad_compat, grad_gate_wb, view_rec, rec_stride, n_points, n_views, C, G,
                           scaling, algo, (hipStream_t)stream);
   else
@@ -1527,12 +1573,12 @@ static int rows_grad_rec16_impl(const void* grad_out, const int32_t* perm, const
                                 const void* view_rec16, void* grad_rows, int32_t out_dtype, int64_t n_rows,
                                 int64_t n_views, int32_t C, int32_t G, int32_t dtype, void* stream) {
   if (n_rows < 0 || n_views < 0 || C <= 0 || G <= 0 || G > 4 || (G & (G - 1))) return DVA_ERR_INVALID;
-  if (out_dtype != DVA_F32 && out_dtype != DVA_BF16) return DVA_ERR_INVALID;
+  if (out_dtype != DVA_F32 && out_dtype != DVA_BF16 && out_dtype != DVA_F16) return DVA_ERR_INVALID;
   if (n_views > 0x7fffffffLL) return DVA_ERR_UNSUPPORTED;
   if (n_rows == 0) return DVA_OK;
   if (!row_ptr || !grad_rows) return DVA_ERR_INVALID;
   if (n_views > 0 && (!grad_out || !view_rec16)) return DVA_ERR_INVALID;     // perm NULL: records in plan order
-  if (dtype != DVA_BF16) return DVA_ERR_UNSUPPORTED;
+  if ((dtype != DVA_BF16 && dtype != DVA_F16) || (out_dtype != DVA_F32 && out_dtype != dtype)) return DVA_ERR_UNSUPPORTED;
   const int lpr = C / 8;
   if ((C % 8) || !is_pow2(lpr) || lpr > 64 || (C % G) || ((C / G) % 8) || ((uintptr_t)grad_out % 16) ||
       ((uintptr_t)grad_rows % 16))
@@ -1542,34 +1588,13 @@ static int rows_grad_rec16_impl(const void* grad_out, const int32_t* perm, const
   static const int slab_env = tune_int("DVA_ROWS_GRAD_SLAB", 0);
   int slab = slab_env;
   if (slab <= 0 || slab >= C || (slab % 8) || !is_pow2(slab / 8) || (C % slab)) slab = C;
-  const int lpr_s = slab / 8;
-  const bool to_bf16 = out_dtype == DVA_BF16;
-  if (n_views <= 2 * n_rows && lpr < 64) {
-    // sparse plan (view-level identity gathers): a lane team per row
-    const int64_t waves = (n_rows + (64 / lpr) - 1) / (64 / lpr);
-    if (to_bf16)
-      hipLaunchKernelGGL((rows_grad_short_rec16_kernel<bf16_t, bf16_t>), dim3(grid_cap((waves + 3) / 4)), dim3(256), 0,
-                         (hipStream_t)stream, (const bf16_t*)grad_out, perm, row_ptr, (const uint32_t*)view_rec16,
-                         (bf16_t*)grad_rows, n_rows, (int)C, lpr, lpr / G);
-    else
-      hipLaunchKernelGGL((rows_grad_short_rec16_kernel<bf16_t>), dim3(grid_cap((waves + 3) / 4)), dim3(256), 0,
-                         (hipStream_t)stream, (const bf16_t*)grad_out, perm, row_ptr, (const uint32_t*)view_rec16,
-                         (float*)grad_rows, n_rows, (int)C, lpr, lpr / G);
-    DVA_CHECK_LAUNCH();
-    return DVA_OK;
-  }
-  for (int c0 = 0; c0 < C; c0 += slab) {
-    if (to_bf16)
-      hipLaunchKernelGGL((rows_grad_team_kernel<bf16_t, true, bf16_t>), dim3(grid_cap((n_rows + 3) / 4)),
-                         dim3(256), 0, (hipStream_t)stream, (const bf16_t*)grad_out, (const float*)nullptr,
-                         (const float*)nullptr, (const int32_t*)nullptr, perm, row_ptr, (const float*)view_rec16, 4,
-                         (bf16_t*)grad_rows, n_rows, (int)C, (int)G, lpr_s, lpr / G, c0);
-    else
-      hipLaunchKernelGGL((rows_grad_team_kernel<bf16_t, true>), dim3(grid_cap((n_rows + 3) / 4)),
-                         dim3(256), 0, (hipStream_t)stream, (const bf16_t*)grad_out, (const float*)nullptr,
-                         (const float*)nullptr, (const int32_t*)nullptr, perm, row_ptr, (const float*)view_rec16, 4,
-                         (float*)grad_rows, n_rows, (int)C, (int)G, lpr_s, lpr / G, c0);
-  }
+  const bool to_16 = out_dtype != DVA_F32;
+  if (dtype == DVA_F16)
+    rows_grad_rec16_launch<f16_t>(grad_out, perm, row_ptr, view_rec16, grad_rows, to_16, n_rows, n_views, C, G, slab,
+                                  (hipStream_t)stream);
+  else
+    rows_grad_rec16_launch<bf16_t>(grad_out, perm, row_ptr, view_rec16, grad_rows, to_16, n_rows, n_views, C, G, slab,
+                                   (hipStream_t)stream);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -1607,6 +1632,9 @@ int dva_view_gather_rows_grad(const void* grad_out, const float* att, const floa
   else if (dtype == DVA_BF16)
     rc = rows_grad_impl<bf16_t>(grad_out, att, gate, view_point, perm, row_ptr, view_rec, rec_stride,
                                 grad_rows, n_rows, C, G, (hipStream_t)stream);
+  else if (dtype == DVA_F16)
+    rc = rows_grad_impl<f16_t>(grad_out, att, gate, view_point, perm, row_ptr, view_rec, rec_stride,
+                                grad_rows, n_rows, C, G, (hipStream_t)stream);
   else
     return DVA_ERR_INVALID;
   if (rc) return rc;
@@ -1617,6 +1645,7 @@ int dva_view_gather_rows_grad(const void* grad_out, const float* att, const floa
 int dva_anchor_rows_sum(const void* grad_out, const int32_t* perm, const int32_t* row_ptr, const float* weights,
                         float* S, int64_t n_anchors, int64_t n_views, int32_t C, int32_t dtype, void* stream) {
   if (n_anchors < 0 || n_views < 0 || C <= 0) return DVA_ERR_INVALID;
+  if (dtype == DVA_F16) return DVA_ERR_UNSUPPORTED;
   if (n_anchors == 0) return DVA_OK;
   if (!row_ptr || !S || (n_views > 0 && (!grad_out || !perm || !weights))) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
@@ -1678,6 +1707,8 @@ int dva_gather_rows_sum(const void* grad_out, const int32_t* perm, const int32_t
     rc = rows_sum_impl<float>(grad_out, perm, row_ptr, weights, atom_shift, grad_rows, n_rows, C, (hipStream_t)stream);
   else if (dtype == DVA_BF16)
     rc = rows_sum_impl<bf16_t>(grad_out, perm, row_ptr, weights, atom_shift, grad_rows, n_rows, C, (hipStream_t)stream);
+  else if (dtype == DVA_F16)
+    rc = rows_sum_impl<f16_t>(grad_out, perm, row_ptr, weights, atom_shift, grad_rows, n_rows, C, (hipStream_t)stream);
   else
     return DVA_ERR_INVALID;
   if (rc) return rc;

@@ -88,13 +88,26 @@ __device__ __forceinline__ f32x16 score_bwd(const uint4* s_ops, int lane, const 
 // score-layer weight gradient -- is the separate pass score_stats_kernel below: 253 VGPRs / 2 wavefronts per SIMD became
 // two kernels that each fit a register budget with twice the occupancy.
 // ------------------------------------------------------------------------------------------------
-// T = bf16_t (the chain path: 8 channels per 16-byte lane, 16-byte records with bf16 weights) or float (the fp32 path of
+// T = bf16_t / f16_t (the chain path: 8 channels per 16-byte lane, 16-byte records with bf16 weights) or float (the fp32 path of
 // ops.view_gather_attention: 4 channels per lane, 32-byte records {point | fp32 gate * attention per group | pad} as
 // dva_view_gather_rows_grad reads them).
 template <typename T>
 __device__ __forceinline__ float dotv(const u32x4& a, const u32x4& b);
 template <>
 __device__ __forceinline__ float dotv<bf16_t>(const u32x4& a, const u32x4& b) { return dot8(a, b); }
+// fp16: products and sums in fp32 (v_fma_mix_f32), not v_dot2c_f32_f16 -- under GradScaler the grad_out rows are scaled
+// by 2^16, and a product of two fp16 values must not overflow before it reaches the fp32 accumulator
+template <>
+__device__ __forceinline__ float dotv<f16_t>(const u32x4& a, const u32x4& b) {
+  const uint32_t aa[4] = {a.x, a.y, a.z, a.w}, bb[4] = {b.x, b.y, b.z, b.w};
+  float d = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    d = __builtin_fmaf(Pair16<f16_t>::lo(aa[i]), Pair16<f16_t>::lo(bb[i]), d);
+    d = __builtin_fmaf(Pair16<f16_t>::hi(aa[i]), Pair16<f16_t>::hi(bb[i]), d);
+  }
+  return d;
+}
 template <>
 __device__ __forceinline__ float dotv<float>(const u32x4& a, const u32x4& b) {
   return __builtin_fmaf(__uint_as_float(a.w), __uint_as_float(b.w),
@@ -1400,8 +1413,9 @@ static int chain_attn_bwd_impl(const int32_t* rec_pos, const float* scores, cons
                        const void* rows, const int32_t* row_idx, const int64_t* ptr, const float* gate_w,
                        const float* gate_b, const void* grad_out, const void* out, float* grad_scores, void* view_rec,
                        float* grad_gate_wb, int64_t n_points, int64_t n_views, int64_t n_rows, int32_t C, int32_t G,
-                       int32_t scaling, float eps, void* stream) {
-  if (n_views < 0 || n_points < 0) return DVA_ERR_INVALID;
+                       int32_t scaling, float eps, int32_t dtype, void* stream) {
+  if (n_views < 0 || n_points < 0 || (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16)) return DVA_ERR_INVALID;
+  if (dtype == DVA_F32) return DVA_ERR_UNSUPPORTED;      // dva_chain_attn_bwd_f32
   if (n_views == 0) return DVA_OK;
   if (!scores || !view_point || !tiles || !n_tiles || !rows || !row_idx || !ptr || !grad_out || !out ||
       !grad_scores || !view_rec || ((gate_w == nullptr) != (gate_b == nullptr)) || (gate_w && !grad_gate_wb))
@@ -1410,11 +1424,16 @@ static int chain_attn_bwd_impl(const int32_t* rec_pos, const float* scores, cons
     return DVA_ERR_UNSUPPORTED;
   const dim3 grid(chain_grid(C <= 64 ? 4 : 3)), block(256);
   hipStream_t s = (hipStream_t)stream;
-#define DVA_ATTN_BWD(LPR_, G_)                                                                                    \
-  hipLaunchKernelGGL((attn_bwd_kernel<bf16_t, LPR_, G_>), grid, block, 0, s, scores, view_point,                  \
-                     (const int2*)tiles, n_tiles, (const bf16_t*)rows, row_idx, ptr, gate_w, gate_b,              \
-                     (const bf16_t*)grad_out, (const bf16_t*)out, grad_scores, (uint32_t*)view_rec, grad_gate_wb, \
+#define DVA_ATTN_BWD_T(T_, LPR_, G_)                                                                              \
+  hipLaunchKernelGGL((attn_bwd_kernel<T_, LPR_, G_>), grid, block, 0, s, scores, view_point,                      \
+                     (const int2*)tiles, n_tiles, (const T_*)rows, row_idx, ptr, gate_w, gate_b,                  \
+                     (const T_*)grad_out, (const T_*)out, grad_scores, (uint32_t*)view_rec, grad_gate_wb,         \
                      scaling, eps, n_views, n_points, n_rows, rec_pos)
+#define DVA_ATTN_BWD(LPR_, G_)                                                                                    \
+  do {                                                                                                            \
+    if (dtype == DVA_F16) DVA_ATTN_BWD_T(f16_t, LPR_, G_);                                                        \
+    else DVA_ATTN_BWD_T(bf16_t, LPR_, G_);                                                                        \
+  } while (0)
   const int key = C * 8 + G;
   switch (key) {
     case 32 * 8 + 1: DVA_ATTN_BWD(4, 1); break;
@@ -1435,6 +1454,7 @@ static int chain_attn_bwd_impl(const int32_t* rec_pos, const float* scores, cons
     default: return DVA_ERR_UNSUPPORTED;
   }
 #undef DVA_ATTN_BWD
+#undef DVA_ATTN_BWD_T
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -1445,7 +1465,18 @@ int dva_chain_attn_bwd(const float* scores, const int32_t* view_point, const voi
                        float* grad_gate_wb, int64_t n_points, int64_t n_views, int64_t n_rows, int32_t C, int32_t G,
                        int32_t scaling, float eps, void* stream) {
   return chain_attn_bwd_impl(nullptr, scores, view_point, tiles, n_tiles, rows, row_idx, ptr, gate_w, gate_b, grad_out, out,
-                             grad_scores, view_rec, grad_gate_wb, n_points, n_views, n_rows, C, G, scaling, eps, stream);
+                             grad_scores, view_rec, grad_gate_wb, n_points, n_views, n_rows, C, G, scaling, eps, DVA_BF16,
+                             stream);
+}
+
+int dva_chain_attn_bwd_dt(const float* scores, const int32_t* view_point, const void* tiles, const int32_t* n_tiles,
+                          const void* rows, const int32_t* row_idx, const int64_t* ptr, const float* gate_w,
+                          const float* gate_b, const void* grad_out, const void* out, float* grad_scores, void* view_rec,
+                          float* grad_gate_wb, int64_t n_points, int64_t n_views, int64_t n_rows, int32_t C, int32_t G,
+                          int32_t scaling, float eps, int32_t dtype, void* stream) {
+  return chain_attn_bwd_impl(nullptr, scores, view_point, tiles, n_tiles, rows, row_idx, ptr, gate_w, gate_b, grad_out, out,
+                             grad_scores, view_rec, grad_gate_wb, n_points, n_views, n_rows, C, G, scaling, eps, dtype,
+                             stream);
 }
 
 int dva_chain_attn_bwd_planrec(const int32_t* rec_pos, const float* scores, const int32_t* view_point, const void* tiles,
@@ -1455,7 +1486,8 @@ int dva_chain_attn_bwd_planrec(const int32_t* rec_pos, const float* scores, cons
                                int64_t n_rows, int32_t C, int32_t G, int32_t scaling, float eps, void* stream) {
   if (!rec_pos && n_views > 0) return DVA_ERR_INVALID;
   return chain_attn_bwd_impl(rec_pos, scores, view_point, tiles, n_tiles, rows, row_idx, ptr, gate_w, gate_b, grad_out, out,
-                             grad_scores, view_rec, grad_gate_wb, n_points, n_views, n_rows, C, G, scaling, eps, stream);
+                             grad_scores, view_rec, grad_gate_wb, n_points, n_views, n_rows, C, G, scaling, eps, DVA_BF16,
+                             stream);
 }
 
 int dva_chain_attn_bwd_f32(const float* scores, const int32_t* view_point, const void* tiles, const int32_t* n_tiles,

@@ -641,14 +641,14 @@ __global__ __launch_bounds__(256, 3) void keys_kernel(
 // KEYS (round 4, QKVBimodalCSRPool): the last layer is the KEY layer (operand OP_WS prepared with G = 32, `bs` = its bias
 // [32]); the scores are the compatibilities scale * <key, query of the point> per group (queries `qp` fp32 [N][32] in
 // position order); the bf16 key rows go to `keys_out` when a backward follows (dQ needs them).
-template <int LPR, int G, int OCC, bool KEYS = false>
+template <int LPR, int G, int OCC, bool KEYS = false, typename TR = bf16_t>
 __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(
     const float* __restrict__ x_map, const int32_t* __restrict__ vp, const float* __restrict__ u,
     const int2* __restrict__ tiles, const int32_t* __restrict__ n_tiles_dev, const uint4* __restrict__ ops,
     const float* __restrict__ bn1, const float* __restrict__ bn2, const float* __restrict__ bn5,
-    const float* __restrict__ bn6, const float* __restrict__ bs, const bf16_t* __restrict__ rows,
+    const float* __restrict__ bn6, const float* __restrict__ bs, const TR* __restrict__ rows,
     const int32_t* __restrict__ row_idx, const int64_t* __restrict__ ptr, const float* __restrict__ gw,
-    const float* __restrict__ gb, bf16_t* __restrict__ out, float* __restrict__ scores_out, int scaling, float eps,
+    const float* __restrict__ gb, TR* __restrict__ out, float* __restrict__ scores_out, int scaling, float eps,
     int64_t V, int64_t N, int64_t R, const float* __restrict__ qp = nullptr, float qscale = 0.f,
     bf16_t* __restrict__ keys_out = nullptr) {
   constexpr int C = LPR * 8, ROWS = 64 / LPR, KV = 32 / ROWS;
@@ -840,8 +840,8 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(
       const uint32_t rw[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        acc[2 * i] = __builtin_fmaf(w, __uint_as_float(rw[i] << 16), acc[2 * i]);
-        acc[2 * i + 1] = __builtin_fmaf(w, __uint_as_float(rw[i] & 0xffff0000u), acc[2 * i + 1]);
+        acc[2 * i] = __builtin_fmaf(w, Pair16<TR>::lo(rw[i]), acc[2 * i]);
+        acc[2 * i + 1] = __builtin_fmaf(w, Pair16<TR>::hi(rw[i]), acc[2 * i + 1]);
       }
     };
     if (single) {
@@ -909,7 +909,7 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(
           run_acc[0] = frag == 3 ? 0.f : v1;
         }
         if (done)
-          __builtin_amdgcn_raw_buffer_store_b16((short)f2bf(v1 * sc), O,
+          __builtin_amdgcn_raw_buffer_store_b16((short)Pair16<TR>::one(v1 * sc), O,
                                                 (int)((uint32_t)vp0 * (uint32_t)(C * 2) + (uint32_t)(q * 8 + rs_ch) * 2u),
                                                 0, 0);
       } else {
@@ -926,8 +926,8 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(
           }
         }
         if (done) {
-          const u32x4 o = {pack_bf16x2(acc[0] * sc, acc[1] * sc), pack_bf16x2(acc[2] * sc, acc[3] * sc),
-                           pack_bf16x2(acc[4] * sc, acc[5] * sc), pack_bf16x2(acc[6] * sc, acc[7] * sc)};
+          const u32x4 o = {Pair16<TR>::pack(acc[0] * sc, acc[1] * sc), Pair16<TR>::pack(acc[2] * sc, acc[3] * sc),
+                           Pair16<TR>::pack(acc[4] * sc, acc[5] * sc), Pair16<TR>::pack(acc[6] * sc, acc[7] * sc)};
           st128(O, slot == 0 ? (uint32_t)vp0 * (uint32_t)(C * 2) + (uint32_t)q * 16u : OOB, o);
         }
       }
@@ -978,17 +978,17 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(
             for (int i = 0; i < 8; ++i) {
               const int v = 8 * ch + i;
               if (CPL == 1) {
-                av[0] = __builtin_fmaf(w8[i], __uint_as_float(rv[i] << 16), av[0]);
+                av[0] = __builtin_fmaf(w8[i], Pair16<TR>::lo(rv[i]), av[0]);
               } else {
-                av[0] = __builtin_fmaf(w8[i], __uint_as_float(rv[i] << 16), av[0]);
-                av[CPL - 1] = __builtin_fmaf(w8[i], __uint_as_float(rv[i] & 0xffff0000u), av[CPL - 1]);
+                av[0] = __builtin_fmaf(w8[i], Pair16<TR>::lo(rv[i]), av[0]);
+                av[CPL - 1] = __builtin_fmaf(w8[i], Pair16<TR>::hi(rv[i]), av[CPL - 1]);
               }
               if ((emx >> v) & 1u) {           // wave-uniform: view v ends its point
                 if (v < nv) {
                   const uint32_t pid = (uint32_t)__builtin_amdgcn_readlane(p.vpj, v);
                   const uint32_t oo = pid * (uint32_t)(C * 2) + (uint32_t)c0 * 2u;
-                  if (CPL == 1) __builtin_amdgcn_raw_buffer_store_b16((short)f2bf(av[0]), O, (int)oo, 0, 0);
-                  else st32(O, oo, pack_bf16x2(av[0], av[CPL - 1]));
+                  if (CPL == 1) __builtin_amdgcn_raw_buffer_store_b16((short)Pair16<TR>::one(av[0]), O, (int)oo, 0, 0);
+                  else st32(O, oo, Pair16<TR>::pack(av[0], av[CPL - 1]));
                 }
 #pragma unroll
                 for (int k2 = 0; k2 < CPL; ++k2) av[k2] = 0.f;
@@ -1024,8 +1024,8 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(
                   *reinterpret_cast<float4*>(mine + 4) = make_float4(acc[4], acc[5], acc[6], acc[7]);
                 } else if (ssk >= sv0) {
                   const float s1 = sc_t[tg * 32 + vt];
-                  const u32x4 o = {pack_bf16x2(acc[0] * s1, acc[1] * s1), pack_bf16x2(acc[2] * s1, acc[3] * s1),
-                                   pack_bf16x2(acc[4] * s1, acc[5] * s1), pack_bf16x2(acc[6] * s1, acc[7] * s1)};
+                  const u32x4 o = {Pair16<TR>::pack(acc[0] * s1, acc[1] * s1), Pair16<TR>::pack(acc[2] * s1, acc[3] * s1),
+                                   Pair16<TR>::pack(acc[4] * s1, acc[5] * s1), Pair16<TR>::pack(acc[6] * s1, acc[7] * s1)};
                   st128(O, (uint32_t)pid_t[vt] * (uint32_t)(C * 2) + (uint32_t)q * 16u, o);
                 } else {
                   // the point started in an earlier slot and ends here
@@ -1053,8 +1053,8 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(
             }
           }
           const float s1 = sc_t[tg * 32 + head_view];
-          const u32x4 o = {pack_bf16x2(hp[0] * s1, hp[1] * s1), pack_bf16x2(hp[2] * s1, hp[3] * s1),
-                           pack_bf16x2(hp[4] * s1, hp[5] * s1), pack_bf16x2(hp[6] * s1, hp[7] * s1)};
+          const u32x4 o = {Pair16<TR>::pack(hp[0] * s1, hp[1] * s1), Pair16<TR>::pack(hp[2] * s1, hp[3] * s1),
+                           Pair16<TR>::pack(hp[4] * s1, hp[5] * s1), Pair16<TR>::pack(hp[6] * s1, hp[7] * s1)};
           st128(O, (uint32_t)pid_t[head_view] * (uint32_t)(C * 2) + (uint32_t)q * 16u, o);
         }
     
@@ -1260,13 +1260,14 @@ int dva_chain_keys_compat(const float* x_map, const int32_t* view_point, const f
                          scale, n_views, n_points, stream);
 }
 
-int dva_chain_attn_fwd(const float* x_map, const int32_t* view_point, const float* u, const void* tiles,
-                       const int32_t* n_tiles, const void* ops, const float* bn1, const float* bn2,
-                       const float* bn5, const float* bn6, const float* score_bias, const void* rows,
-                       const int32_t* row_idx, const int64_t* ptr, const float* gate_w, const float* gate_b,
-                       void* out, float* scores_out, int64_t n_points, int64_t n_views, int64_t n_rows, int32_t C,
-                       int32_t G, int32_t scaling, float eps, void* stream) {
-  if (n_views < 0 || n_points < 0) return DVA_ERR_INVALID;
+int dva_chain_attn_fwd_dt(const float* x_map, const int32_t* view_point, const float* u, const void* tiles,
+                          const int32_t* n_tiles, const void* ops, const float* bn1, const float* bn2,
+                          const float* bn5, const float* bn6, const float* score_bias, const void* rows,
+                          const int32_t* row_idx, const int64_t* ptr, const float* gate_w, const float* gate_b,
+                          void* out, float* scores_out, int64_t n_points, int64_t n_views, int64_t n_rows, int32_t C,
+                          int32_t G, int32_t scaling, float eps, int32_t dtype, void* stream) {
+  if (n_views < 0 || n_points < 0 || (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16)) return DVA_ERR_INVALID;
+  if (dtype == DVA_F32) return DVA_ERR_UNSUPPORTED;
   if (n_views == 0) return DVA_OK;
   if (!x_map || !view_point || !u || !tiles || !n_tiles || !ops || !bn1 || !bn2 || !bn5 || !bn6 || !score_bias ||
       !rows || !row_idx || !ptr || !out || ((gate_w == nullptr) != (gate_b == nullptr)))
@@ -1278,11 +1279,16 @@ int dva_chain_attn_fwd(const float* x_map, const int32_t* view_point, const floa
   const bool dense = occ_env ? (occ_env == 4 && C <= 64) : (C <= 64 && n_views >= 24 * n_points);   // mostly one point per tile
   const dim3 grid(chain_grid(dense ? 4 : 3)), block(256);
   hipStream_t s = (hipStream_t)stream;
-#define DVA_ATTN_FWD_O(LPR_, G_, OCC_)                                                                          \
-  hipLaunchKernelGGL((attn_fwd_kernel<LPR_, G_, OCC_>), grid, block, 0, s, x_map, view_point, u,               \
+#define DVA_ATTN_FWD_T(LPR_, G_, OCC_, T_)                                                                      \
+  hipLaunchKernelGGL((attn_fwd_kernel<LPR_, G_, OCC_, false, T_>), grid, block, 0, s, x_map, view_point, u,    \
                      (const int2*)tiles, n_tiles, (const uint4*)ops, bn1, bn2, bn5, bn6, score_bias,            \
-                     (const bf16_t*)rows, row_idx, ptr, gate_w, gate_b, (bf16_t*)out, scores_out, scaling, eps, \
+                     (const T_*)rows, row_idx, ptr, gate_w, gate_b, (T_*)out, scores_out, scaling, eps,         \
                      n_views, n_points, n_rows)
+#define DVA_ATTN_FWD_O(LPR_, G_, OCC_)                                                                          \
+  do {                                                                                                          \
+    if (dtype == DVA_F16) DVA_ATTN_FWD_T(LPR_, G_, OCC_, f16_t);                                                \
+    else DVA_ATTN_FWD_T(LPR_, G_, OCC_, bf16_t);                                                                \
+  } while (0)
 #define DVA_ATTN_FWD(LPR_, G_)                                                                                  \
   do {                                                                                                          \
     if (LPR_ <= 8 && dense) DVA_ATTN_FWD_O(LPR_, G_, (LPR_ <= 8 ? 4 : 3));                                      \
@@ -1309,8 +1315,20 @@ int dva_chain_attn_fwd(const float* x_map, const int32_t* view_point, const floa
   }
 #undef DVA_ATTN_FWD
 #undef DVA_ATTN_FWD_O
+#undef DVA_ATTN_FWD_T
   DVA_CHECK_LAUNCH();
   return DVA_OK;
+}
+
+int dva_chain_attn_fwd(const float* x_map, const int32_t* view_point, const float* u, const void* tiles,
+                       const int32_t* n_tiles, const void* ops, const float* bn1, const float* bn2,
+                       const float* bn5, const float* bn6, const float* score_bias, const void* rows,
+                       const int32_t* row_idx, const int64_t* ptr, const float* gate_w, const float* gate_b,
+                       void* out, float* scores_out, int64_t n_points, int64_t n_views, int64_t n_rows, int32_t C,
+                       int32_t G, int32_t scaling, float eps, void* stream) {
+  return dva_chain_attn_fwd_dt(x_map, view_point, u, tiles, n_tiles, ops, bn1, bn2, bn5, bn6, score_bias, rows, row_idx,
+                               ptr, gate_w, gate_b, out, scores_out, n_points, n_views, n_rows, C, G, scaling, eps,
+                               DVA_BF16, stream);
 }
 
 // QKVBimodalCSRPool in ONE view kernel (round 4): the fused view kernel with the KEY layer as the chain's last layer (ops

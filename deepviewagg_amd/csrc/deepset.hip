@@ -741,6 +741,7 @@ int dva_deepset_fwd_first(const float* x_map, const float* Wa, const float* bn1,
                           void* a2_, double* stats, int64_t V, int32_t F, int32_t stats_only,
                           int32_t algo, int32_t act_dtype, void* stream) {
   const int bf = act_bf(act_dtype);
+  if (act_dtype == DVA_F16) return DVA_ERR_UNSUPPORTED;      // fp32 / bf16 activations only
   if (V < 0 || !stats || bf < 0) return DVA_ERR_INVALID;
   if (bf && algo == 1) return DVA_ERR_UNSUPPORTED;  // bf16 storage only in the MFMA generation
   float* a2 = (float*)a2_;
@@ -769,6 +770,7 @@ int dva_deepset_fwd_first(const float* x_map, const float* Wa, const float* bn1,
 int dva_deepset_segmax(const void* a, const float* bn, const int64_t* ptr, float* pooled,
                        int32_t* arg, int64_t N, int64_t n_views, int32_t act_dtype, void* stream) {
   const int bf = act_bf(act_dtype);
+  if (act_dtype == DVA_F16) return DVA_ERR_UNSUPPORTED;      // fp32 / bf16 activations only
   if (N < 0 || bf < 0) return DVA_ERR_INVALID;
   if (N == 0) return DVA_OK;
   if (!a || !bn || !ptr || !pooled || !arg) return DVA_ERR_INVALID;
@@ -801,6 +803,7 @@ int dva_deepset_fwd_layer(const void* a_in_, const float* bn_in, const float* W,
                           const int32_t* group_of_row, void* a_out_, double* stats, int64_t V,
                           int32_t algo, int32_t act_dtype, void* stream) {
   const int bf = act_bf(act_dtype);
+  if (act_dtype == DVA_F16) return DVA_ERR_UNSUPPORTED;      // fp32 / bf16 activations only
   if (V < 0 || !stats || bf < 0) return DVA_ERR_INVALID;
   if (bf && algo == 1) return DVA_ERR_UNSUPPORTED;
   const float* a_in = (const float*)a_in_;
@@ -830,6 +833,7 @@ int dva_deepset_fwd_score(const void* a_, const float* bn, const float* Ws, cons
                           float* compat, int64_t V, int32_t G, const float* bn_pre, const float* W_pre,
                           int32_t algo, int32_t act_dtype, void* stream) {
   const int bf = act_bf(act_dtype);
+  if (act_dtype == DVA_F16) return DVA_ERR_UNSUPPORTED;      // fp32 / bf16 activations only
   if (V < 0 || G <= 0 || G > 32 || bf < 0) return DVA_ERR_INVALID;
   if (bf && algo == 1) return DVA_ERR_UNSUPPORTED;
   if ((bn_pre == nullptr) != (W_pre == nullptr)) return DVA_ERR_INVALID;
@@ -855,6 +859,7 @@ int dva_deepset_bwd_score(const float* dcompat, const void* a_, const float* bn,
                           const float* bn_pre, const float* W_pre, int32_t algo, int32_t act_dtype,
                           void* stream) {
   const int bf = act_bf(act_dtype);
+  if (act_dtype == DVA_F16) return DVA_ERR_UNSUPPORTED;      // fp32 / bf16 activations only
   if (V < 0 || G <= 0 || bf < 0) return DVA_ERR_INVALID;
   if (bf && algo == 1) return DVA_ERR_UNSUPPORTED;
   if ((bn_pre == nullptr) != (W_pre == nullptr)) return DVA_ERR_INVALID;
@@ -886,6 +891,7 @@ int dva_deepset_bwd_layer(const void* dz_L_, const void* a_L_, const float* bn_L
                           int32_t prev_is_xmap, int32_t raw_out, int32_t algo, int32_t act_dtype,
                           void* stream) {
   const int bf = act_bf(act_dtype);
+  if (act_dtype == DVA_F16) return DVA_ERR_UNSUPPORTED;      // fp32 / bf16 activations only
   if (V < 0 || bf < 0) return DVA_ERR_INVALID;
   if (bf && algo == 1) return DVA_ERR_UNSUPPORTED;
   // fused first-layer gradient: bf16 storage, x_map input, batch-norm output, no per-point sum
@@ -926,6 +932,7 @@ int dva_deepset_bwd_max(const void* dcat_, const void* a2_, const float* bn2, co
                         const float* dpooled, const int32_t* group_of_row, void* dz2_, double* st,
                         int64_t V, int32_t algo, int32_t act_dtype, void* stream) {
   const int bf = act_bf(act_dtype);
+  if (act_dtype == DVA_F16) return DVA_ERR_UNSUPPORTED;      // fp32 / bf16 activations only
   if (V < 0 || bf < 0) return DVA_ERR_INVALID;
   if (bf && algo == 1) return DVA_ERR_UNSUPPORTED;
   const float *dcat = (const float*)dcat_, *a2 = (const float*)a2_;
@@ -947,6 +954,7 @@ int dva_deepset_bwd_first(const void* dz1, const float* x_map, const float* Wa, 
                           const float* sm1, float* dWa, int64_t V, int32_t F, int32_t act_dtype,
                           void* stream) {
   const int bf = act_bf(act_dtype);
+  if (act_dtype == DVA_F16) return DVA_ERR_UNSUPPORTED;      // fp32 / bf16 activations only
   if (V < 0 || bf < 0) return DVA_ERR_INVALID;
   if (F != 8) return DVA_ERR_UNSUPPORTED;
   if (V == 0) return DVA_OK;

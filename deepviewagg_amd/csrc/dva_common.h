@@ -38,6 +38,52 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
 }
 __device__ __forceinline__ bf16_t f2bf(float f) { return (bf16_t)(pack_bf16x2(f, 0.f) & 0xffffu); }
 
+// IEEE binary16 (DVA_F16, the storage type of torch.float16).  A type of its own, not a second uint16_t: the Elt<> /
+// Pair16<> / dotv<> specialisations must tell it from bf16_t.  float -> fp16 rounds to nearest even (v_cvt_f16_f32,
+// v_cvt_pk_f16_f32 in the default round mode; never v_cvt_pkrtz): overflow gives +-inf and NaN stays NaN, as in torch
+// -- GradScaler's overflow check depends on both.
+typedef _Float16 f16_t;
+typedef _Float16 dva_f16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t pack_f16x2(float lo, float hi) {
+  const dva_f32x2 v = {lo, hi};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, dva_f16x2));
+}
+
+// Two 16-bit elements of one 32-bit word (element 0 in the low half) <-> fp32, per 2-byte storage type.
+template <typename T>
+struct Pair16;
+template <>
+struct Pair16<bf16_t> {
+  static __device__ __forceinline__ float lo(uint32_t w) { return __uint_as_float(w << 16); }
+  static __device__ __forceinline__ float hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
+  static __device__ __forceinline__ uint32_t pack(float a, float b) { return pack_bf16x2(a, b); }
+  static __device__ __forceinline__ uint16_t one(float a) { return f2bf(a); }
+};
+template <>
+struct Pair16<f16_t> {
+  static __device__ __forceinline__ float lo(uint32_t w) {
+    return (float)__builtin_bit_cast(f16_t, (uint16_t)(w & 0xffffu));
+  }
+  static __device__ __forceinline__ float hi(uint32_t w) { return (float)__builtin_bit_cast(f16_t, (uint16_t)(w >> 16)); }
+  static __device__ __forceinline__ uint32_t pack(float a, float b) { return pack_f16x2(a, b); }
+  static __device__ __forceinline__ uint16_t one(float a) { return __builtin_bit_cast(uint16_t, (f16_t)a); }
+};
+// 8 elements of a 16-byte chunk <-> fp32
+template <typename T>
+__device__ __forceinline__ void unpack_h8(const uint4& r, float* f) {
+  const uint32_t w[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    f[2 * i] = Pair16<T>::lo(w[i]);
+    f[2 * i + 1] = Pair16<T>::hi(w[i]);
+  }
+}
+template <typename T>
+__device__ __forceinline__ uint4 pack_h8(const float* f) {
+  return make_uint4(Pair16<T>::pack(f[0], f[1]), Pair16<T>::pack(f[2], f[3]), Pair16<T>::pack(f[4], f[5]),
+                    Pair16<T>::pack(f[6], f[7]));
+}
+
 template <typename T>
 struct Elt;
 template <>
@@ -49,6 +95,11 @@ template <>
 struct Elt<bf16_t> {
   static __device__ __forceinline__ float ld(const bf16_t* p, int64_t i) { return bf2f(p[i]); }
   static __device__ __forceinline__ void st(bf16_t* p, int64_t i, float v) { p[i] = f2bf(v); }
+};
+template <>
+struct Elt<f16_t> {
+  static __device__ __forceinline__ float ld(const f16_t* p, int64_t i) { return (float)p[i]; }
+  static __device__ __forceinline__ void st(f16_t* p, int64_t i, float v) { p[i] = (f16_t)v; }
 };
 
 // expand_group_feat (pooling.py:737-755): the first (C mod G) groups own floor(C/G)+1 channels,

@@ -62,6 +62,7 @@ __global__ __launch_bounds__(256) void concat_cast_kernel(float* __restrict__ a,
 template <bool BWD>
 static int concat_cast(float* a, void* b, float* cat, int64_t N, int Ca, int Cb, int dtype, hipStream_t s) {
   if (N < 0 || Ca < 0 || Cb < 0 || (Ca & 3) || (Cb & 3) || Ca + Cb > 1024) return DVA_ERR_INVALID;
+  if (dtype == DVA_F16) return DVA_ERR_UNSUPPORTED;          // fp32 / bf16 x_mod only
   if (N == 0 || Ca + Cb == 0) return DVA_OK;
   if ((Ca && !a) || (Cb && !b) || !cat) return DVA_ERR_INVALID;
   if (dtype == DVA_BF16 && ((uintptr_t)b & 7)) return DVA_ERR_UNSUPPORTED;     // 8-byte moves of the bf16 groups

@@ -218,6 +218,13 @@ struct GVec<bf16_t> {
     return r;
   }
 };
+template <>
+struct GVec<f16_t> {
+  static constexpr int N = 8;
+  typedef uint4 raw;
+  static __device__ __forceinline__ void unpack(const raw& r, float* f) { unpack_h8<f16_t>(r, f); }
+  static __device__ __forceinline__ raw pack(const float* f) { return pack_h8<f16_t>(f); }
+};
 template <typename T>
 __global__ __launch_bounds__(256) void gather_bilinear_fwd_vec_kernel(
     const T* __restrict__ x, const PackedIdx* __restrict__ idx, const float* __restrict__ coords,
@@ -409,15 +416,15 @@ __global__ __launch_bounds__(256) void gather_segment_max_fwd_kernel(const T* __
     for (int64_t a = beg; a < end; ++a) {
       const uint4 raw = *reinterpret_cast<const uint4*>(rows + (int64_t)row_idx[a] * C + c0);
       float f[VEC];
-      if (sizeof(T) == 4) {
+      if constexpr (sizeof(T) == 4) {
         f[0] = __uint_as_float(raw.x); f[1] = __uint_as_float(raw.y);
         f[2] = __uint_as_float(raw.z); f[VEC - 1] = __uint_as_float(raw.w);
       } else {
         const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          f[(2 * e) % VEC] = __uint_as_float(w[e] << 16);
-          f[(2 * e + 1) % VEC] = __uint_as_float(w[e] & 0xffff0000u);
+          f[(2 * e) % VEC] = Pair16<T>::lo(w[e]);
+          f[(2 * e + 1) % VEC] = Pair16<T>::hi(w[e]);
         }
       }
 #pragma unroll
@@ -428,14 +435,14 @@ __global__ __launch_bounds__(256) void gather_segment_max_fwd_kernel(const T* __
         }
       }
     }
-    if (sizeof(T) == 4) {
+    if constexpr (sizeof(T) == 4) {
       *reinterpret_cast<float4*>(out + v * C + c0) = make_float4(acc[0], acc[1], acc[2], acc[VEC - 1]);
       *reinterpret_cast<uint2*>(arg + v * C + c0) =
           make_uint2(best[0] | ((uint32_t)best[1] << 16), best[2] | ((uint32_t)best[VEC - 1] << 16));
     } else {
       *reinterpret_cast<uint4*>(out + v * C + c0) =
-          make_uint4(pack_bf16x2(acc[0], acc[1]), pack_bf16x2(acc[2], acc[3]), pack_bf16x2(acc[4 % VEC], acc[5 % VEC]),
-                     pack_bf16x2(acc[6 % VEC], acc[7 % VEC]));
+          make_uint4(Pair16<T>::pack(acc[0], acc[1]), Pair16<T>::pack(acc[2], acc[3]),
+                     Pair16<T>::pack(acc[4 % VEC], acc[5 % VEC]), Pair16<T>::pack(acc[6 % VEC], acc[7 % VEC]));
       *reinterpret_cast<uint4*>(arg + v * C + c0) =
           make_uint4(best[0] | ((uint32_t)best[1] << 16), best[2] | ((uint32_t)best[3] << 16),
                      best[4 % VEC] | ((uint32_t)best[5 % VEC] << 16), best[6 % VEC] | ((uint32_t)best[7 % VEC] << 16));
@@ -461,7 +468,7 @@ __global__ __launch_bounds__(256) void gather_segment_max_bwd_kernel(const T* __
     float g[VEC];
     uint16_t k16[VEC];
     const uint4 raw = *reinterpret_cast<const uint4*>(gout + v * C + c0);
-    if (sizeof(T) == 4) {
+    if constexpr (sizeof(T) == 4) {
       g[0] = __uint_as_float(raw.x); g[1] = __uint_as_float(raw.y);
       g[2] = __uint_as_float(raw.z); g[VEC - 1] = __uint_as_float(raw.w);
       const uint2 a2 = *reinterpret_cast<const uint2*>(arg + v * C + c0);
@@ -472,8 +479,8 @@ __global__ __launch_bounds__(256) void gather_segment_max_bwd_kernel(const T* __
       const uint32_t aw[4] = {a4.x, a4.y, a4.z, a4.w};
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        g[(2 * e) % VEC] = __uint_as_float(w[e] << 16);
-        g[(2 * e + 1) % VEC] = __uint_as_float(w[e] & 0xffff0000u);
+        g[(2 * e) % VEC] = Pair16<T>::lo(w[e]);
+        g[(2 * e + 1) % VEC] = Pair16<T>::hi(w[e]);
         k16[(2 * e) % VEC] = (uint16_t)aw[e];
         k16[(2 * e + 1) % VEC] = (uint16_t)(aw[e] >> 16);
       }
@@ -524,7 +531,7 @@ __global__ __launch_bounds__(256) void gather_segment_max_plan_bwd_kernel(
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         graw[u] = *reinterpret_cast<const uint4*>(gout + v[u] * C + col);
-        if (sizeof(T) == 4) {
+        if constexpr (sizeof(T) == 4) {
           const uint2 a2 = *reinterpret_cast<const uint2*>(arg + v[u] * C + col);
           araw[u] = make_uint4(a2.x, a2.y, 0u, 0u);
         } else {
@@ -535,7 +542,7 @@ __global__ __launch_bounds__(256) void gather_segment_max_plan_bwd_kernel(
       for (int u = 0; u < U; ++u) {
         const uint32_t gw[4] = {graw[u].x, graw[u].y, graw[u].z, graw[u].w};
         const uint32_t aw[4] = {araw[u].x, araw[u].y, araw[u].z, araw[u].w};
-        if (sizeof(T) == 4) {
+        if constexpr (sizeof(T) == 4) {
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             const uint32_t ak = (aw[k >> 1] >> (16 * (k & 1))) & 0xffffu;
@@ -544,8 +551,8 @@ __global__ __launch_bounds__(256) void gather_segment_max_plan_bwd_kernel(
         } else {
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            acc[(2 * e) % VEC] += (aw[e] & 0xffffu) == koff[u] ? __uint_as_float(gw[e] << 16) : 0.f;
-            acc[(2 * e + 1) % VEC] += (aw[e] >> 16) == koff[u] ? __uint_as_float(gw[e] & 0xffff0000u) : 0.f;
+            acc[(2 * e) % VEC] += (aw[e] & 0xffffu) == koff[u] ? Pair16<T>::lo(gw[e]) : 0.f;
+            acc[(2 * e + 1) % VEC] += (aw[e] >> 16) == koff[u] ? Pair16<T>::hi(gw[e]) : 0.f;
           }
         }
       }
@@ -649,7 +656,7 @@ int dva_gather_row_index(const void* packed_idx, int64_t n_atoms, int32_t B, int
 
 static int check_map(int64_t n_atoms, int B, int H, int W, int C, int dtype) {
   if (n_atoms < 0 || B < 0 || H < 0 || W < 0 || C < 0) return DVA_ERR_INVALID;
-  if (dtype != DVA_F32 && dtype != DVA_BF16) return DVA_ERR_INVALID;
+  if (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16) return DVA_ERR_INVALID;
   if (H > 32767 || W > 32767) return DVA_ERR_UNSUPPORTED;
   return DVA_OK;
 }
@@ -694,6 +701,9 @@ int dva_gather_nearest_bwd(const void* grad_out, const void* packed_idx, float* 
   if (dtype == DVA_F32)
     hipLaunchKernelGGL((gather_nearest_bwd_kernel<float>), dim3(grid), dim3(256), 0, s,
                        (const float*)grad_out, idx, grad_x, n_atoms, H, W, C);
+  else if (dtype == DVA_F16)
+    hipLaunchKernelGGL((gather_nearest_bwd_kernel<f16_t>), dim3(grid), dim3(256), 0, s,
+                       (const f16_t*)grad_out, idx, grad_x, n_atoms, H, W, C);
   else
     hipLaunchKernelGGL((gather_nearest_bwd_kernel<bf16_t>), dim3(grid), dim3(256), 0, s,
                        (const bf16_t*)grad_out, idx, grad_x, n_atoms, H, W, C);
@@ -719,6 +729,9 @@ int dva_gather_bilinear_fwd(const void* x, const void* packed_idx, const float* 
     if (dtype == DVA_F32)
       hipLaunchKernelGGL((gather_bilinear_fwd_vec_kernel<float>), dim3(gridv), dim3(256), 0, s, (const float*)x, idx,
                          coords, (float*)out, n_atoms, H, W, C, lpr);
+    else if (dtype == DVA_F16)
+      hipLaunchKernelGGL((gather_bilinear_fwd_vec_kernel<f16_t>), dim3(gridv), dim3(256), 0, s, (const f16_t*)x, idx,
+                         coords, (f16_t*)out, n_atoms, H, W, C, lpr);
     else
       hipLaunchKernelGGL((gather_bilinear_fwd_vec_kernel<bf16_t>), dim3(gridv), dim3(256), 0, s, (const bf16_t*)x, idx,
                          coords, (bf16_t*)out, n_atoms, H, W, C, lpr);
@@ -729,6 +742,9 @@ int dva_gather_bilinear_fwd(const void* x, const void* packed_idx, const float* 
   if (dtype == DVA_F32)
     hipLaunchKernelGGL((gather_bilinear_fwd_kernel<float>), dim3(grid), dim3(256), 0, s,
                        (const float*)x, idx, coords, (float*)out, n_atoms, H, W, C);
+  else if (dtype == DVA_F16)
+    hipLaunchKernelGGL((gather_bilinear_fwd_kernel<f16_t>), dim3(grid), dim3(256), 0, s,
+                       (const f16_t*)x, idx, coords, (f16_t*)out, n_atoms, H, W, C);
   else
     hipLaunchKernelGGL((gather_bilinear_fwd_kernel<bf16_t>), dim3(grid), dim3(256), 0, s,
                        (const bf16_t*)x, idx, coords, (bf16_t*)out, n_atoms, H, W, C);
@@ -749,6 +765,9 @@ int dva_gather_bilinear_bwd(const void* grad_out, const void* packed_idx, const 
   if (dtype == DVA_F32)
     hipLaunchKernelGGL((gather_bilinear_bwd_kernel<float>), dim3(grid), dim3(256), 0, s,
                        (const float*)grad_out, idx, coords, grad_x, n_atoms, H, W, C);
+  else if (dtype == DVA_F16)
+    hipLaunchKernelGGL((gather_bilinear_bwd_kernel<f16_t>), dim3(grid), dim3(256), 0, s,
+                       (const f16_t*)grad_out, idx, coords, grad_x, n_atoms, H, W, C);
   else
     hipLaunchKernelGGL((gather_bilinear_bwd_kernel<bf16_t>), dim3(grid), dim3(256), 0, s,
                        (const bf16_t*)grad_out, idx, coords, grad_x, n_atoms, H, W, C);
@@ -822,7 +841,8 @@ int dva_anchor_combine(const float* S, float* grad_rows, int32_t B, int32_t H, i
 int dva_anchor_fixup(const void* grad, const int32_t* rows, const float* weights, const int32_t* anchors,
                      float* grad_rows, int64_t n_atoms, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype,
                      void* stream) {
-  if (n_atoms < 0 || C <= 0 || (dtype != DVA_F32 && dtype != DVA_BF16)) return DVA_ERR_INVALID;
+  if (n_atoms < 0 || C <= 0 || (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16)) return DVA_ERR_INVALID;
+  if (dtype == DVA_F16) return DVA_ERR_UNSUPPORTED;
   if (n_atoms == 0) return DVA_OK;
   if (!grad || !rows || !weights || !anchors || !grad_rows) return DVA_ERR_INVALID;
   const int32_t dummy = (int32_t)((int64_t)B * (H + 1) * (W + 1));
@@ -855,7 +875,7 @@ int dva_anchor_fixup_bn(const void* dy_a, const void* z_a, const float* bn_a, co
 
 int dva_gather_segment_max_fwd(const void* rows, const int32_t* row_idx, const int64_t* atom_ptr, void* out, void* arg,
                                int64_t n_views, int64_t n_atoms, int64_t n_rows, int32_t C, int32_t dtype, void* stream) {
-  if (n_views < 0 || n_atoms < 0 || n_rows < 0 || C < 0 || (dtype != DVA_F32 && dtype != DVA_BF16)) return DVA_ERR_INVALID;
+  if (n_views < 0 || n_atoms < 0 || n_rows < 0 || C < 0 || (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16)) return DVA_ERR_INVALID;
   if (n_views == 0 || C == 0) return DVA_OK;
   if (!rows || !atom_ptr || !out || !arg || (n_atoms > 0 && !row_idx)) return DVA_ERR_INVALID;
   const int vec = dtype == DVA_F32 ? 4 : 8;
@@ -865,6 +885,9 @@ int dva_gather_segment_max_fwd(const void* rows, const int32_t* row_idx, const i
   if (dtype == DVA_F32)
     hipLaunchKernelGGL((gather_segment_max_fwd_kernel<float>), dim3(grid_for(total)), dim3(256), 0, s, (const float*)rows,
                        row_idx, atom_ptr, (float*)out, (uint16_t*)arg, n_views, (int)C);
+  else if (dtype == DVA_F16)
+    hipLaunchKernelGGL((gather_segment_max_fwd_kernel<f16_t>), dim3(grid_for(total)), dim3(256), 0, s, (const f16_t*)rows,
+                       row_idx, atom_ptr, (f16_t*)out, (uint16_t*)arg, n_views, (int)C);
   else
     hipLaunchKernelGGL((gather_segment_max_fwd_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, s, (const bf16_t*)rows,
                        row_idx, atom_ptr, (bf16_t*)out, (uint16_t*)arg, n_views, (int)C);
@@ -875,7 +898,7 @@ int dva_gather_segment_max_fwd(const void* rows, const int32_t* row_idx, const i
 int dva_gather_segment_max_bwd(const void* grad_out, const void* arg, const int32_t* row_idx, const int64_t* atom_ptr,
                                const int32_t* perm, const int32_t* row_ptr, const int32_t* view_of_atom, float* grad_rows,
                                int64_t n_views, int64_t n_atoms, int64_t n_rows, int32_t C, int32_t dtype, void* stream) {
-  if (n_views < 0 || n_atoms < 0 || n_rows < 0 || C < 0 || (dtype != DVA_F32 && dtype != DVA_BF16)) return DVA_ERR_INVALID;
+  if (n_views < 0 || n_atoms < 0 || n_rows < 0 || C < 0 || (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16)) return DVA_ERR_INVALID;
   if (n_rows == 0 || C == 0) return DVA_OK;
   if (!grad_rows || !atom_ptr) return DVA_ERR_INVALID;
   const int vec = dtype == DVA_F32 ? 4 : 8;
@@ -895,6 +918,10 @@ int dva_gather_segment_max_bwd(const void* grad_out, const void* arg, const int3
       hipLaunchKernelGGL((gather_segment_max_plan_bwd_kernel<float>), dim3((int)blocks), dim3(256), 0, s,
                          (const float*)grad_out, (const uint16_t*)arg, atom_ptr, perm, row_ptr, view_of_atom, grad_rows,
                          n_rows, (int)C, lpr);
+    else if (dtype == DVA_F16)
+      hipLaunchKernelGGL((gather_segment_max_plan_bwd_kernel<f16_t>), dim3((int)blocks), dim3(256), 0, s,
+                         (const f16_t*)grad_out, (const uint16_t*)arg, atom_ptr, perm, row_ptr, view_of_atom, grad_rows,
+                         n_rows, (int)C, lpr);
     else
       hipLaunchKernelGGL((gather_segment_max_plan_bwd_kernel<bf16_t>), dim3((int)blocks), dim3(256), 0, s,
                          (const bf16_t*)grad_out, (const uint16_t*)arg, atom_ptr, perm, row_ptr, view_of_atom, grad_rows,
@@ -907,6 +934,9 @@ int dva_gather_segment_max_bwd(const void* grad_out, const void* arg, const int3
   const int64_t total = n_views * (C / vec);
   if (dtype == DVA_F32)
     hipLaunchKernelGGL((gather_segment_max_bwd_kernel<float>), dim3(grid_for(total)), dim3(256), 0, s, (const float*)grad_out,
+                       (const uint16_t*)arg, row_idx, atom_ptr, grad_rows, n_views, (int)C);
+  else if (dtype == DVA_F16)
+    hipLaunchKernelGGL((gather_segment_max_bwd_kernel<f16_t>), dim3(grid_for(total)), dim3(256), 0, s, (const f16_t*)grad_out,
                        (const uint16_t*)arg, row_idx, atom_ptr, grad_rows, n_views, (int)C);
   else
     hipLaunchKernelGGL((gather_segment_max_bwd_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, s, (const bf16_t*)grad_out,

@@ -389,10 +389,10 @@ __global__ __launch_bounds__(TILE / IPT) void scatter_kernel(const uint32_t* __r
 // consumed where they lie: per row its records in view order, the 128-byte grad_out row of each record's point
 // gathered U at a time.  Deterministic (a row is summed by one lane team in view order); the order differs from the
 // segmented reduction of attention.hip (which splits a row over 8 lane slots), so the two agree to fp32 rounding, not
-// bit for bit.  bf16 in, bf16 out, C in {32, 64}.
-template <int C, int BT>
-__global__ __launch_bounds__(1024) void bucket_rows_grad_kernel(const uint4* __restrict__ rec, const bf16_t* __restrict__ gout,
-                                                                bf16_t* __restrict__ grows, int64_t n_rows, int G,
+// bit for bit.  bf16 in, bf16 out or fp16 in, fp16 out (fp32 sums, one rounding), C in {32, 64}.
+template <int C, int BT, typename T>
+__global__ __launch_bounds__(1024) void bucket_rows_grad_kernel(const uint4* __restrict__ rec, const T* __restrict__ gout,
+                                                                T* __restrict__ grows, int64_t n_rows, int G,
                                                                 const int32_t* __restrict__ bucket_start,
                                                                 const int32_t* __restrict__ order) {
   // BT = records ranked + staged at a time (the kernel's own tile: the bucket is one contiguous, view-ordered range).
@@ -481,14 +481,14 @@ __global__ __launch_bounds__(1024) void bucket_rows_grad_kernel(const uint4* __r
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const uint4 r = raw[u];
-          acc[rr][0] = fmaf(__uint_as_float(r.x << 16), sc[u], acc[rr][0]);
-          acc[rr][1] = fmaf(__uint_as_float(r.x & 0xffff0000u), sc[u], acc[rr][1]);
-          acc[rr][2] = fmaf(__uint_as_float(r.y << 16), sc[u], acc[rr][2]);
-          acc[rr][3] = fmaf(__uint_as_float(r.y & 0xffff0000u), sc[u], acc[rr][3]);
-          acc[rr][4] = fmaf(__uint_as_float(r.z << 16), sc[u], acc[rr][4]);
-          acc[rr][5] = fmaf(__uint_as_float(r.z & 0xffff0000u), sc[u], acc[rr][5]);
-          acc[rr][6] = fmaf(__uint_as_float(r.w << 16), sc[u], acc[rr][6]);
-          acc[rr][7] = fmaf(__uint_as_float(r.w & 0xffff0000u), sc[u], acc[rr][7]);
+          acc[rr][0] = fmaf(Pair16<T>::lo(r.x), sc[u], acc[rr][0]);
+          acc[rr][1] = fmaf(Pair16<T>::hi(r.x), sc[u], acc[rr][1]);
+          acc[rr][2] = fmaf(Pair16<T>::lo(r.y), sc[u], acc[rr][2]);
+          acc[rr][3] = fmaf(Pair16<T>::hi(r.y), sc[u], acc[rr][3]);
+          acc[rr][4] = fmaf(Pair16<T>::lo(r.z), sc[u], acc[rr][4]);
+          acc[rr][5] = fmaf(Pair16<T>::hi(r.z), sc[u], acc[rr][5]);
+          acc[rr][6] = fmaf(Pair16<T>::lo(r.w), sc[u], acc[rr][6]);
+          acc[rr][7] = fmaf(Pair16<T>::hi(r.w), sc[u], acc[rr][7]);
         }
       }
     }
@@ -497,8 +497,8 @@ __global__ __launch_bounds__(1024) void bucket_rows_grad_kernel(const uint4* __r
   for (int rr = 0; rr < RPT; ++rr) {
     const int64_t r = (int64_t)b * BINS + grp + GROUPS * rr;
     if (r < n_rows) {
-      const uint4 o = {pack_bf16x2(acc[rr][0], acc[rr][1]), pack_bf16x2(acc[rr][2], acc[rr][3]),
-                       pack_bf16x2(acc[rr][4], acc[rr][5]), pack_bf16x2(acc[rr][6], acc[rr][7])};
+      const uint4 o = {Pair16<T>::pack(acc[rr][0], acc[rr][1]), Pair16<T>::pack(acc[rr][2], acc[rr][3]),
+                       Pair16<T>::pack(acc[rr][4], acc[rr][5]), Pair16<T>::pack(acc[rr][6], acc[rr][7])};
       *reinterpret_cast<uint4*>(grows + r * C + cl * 8) = o;
     }
   }
@@ -615,16 +615,16 @@ __global__ __launch_bounds__(1024) void bucket_rows_grad_f32_kernel(const uint4*
   }
 }
 
-template <int C>
-static void bucket_rows_grad(const uint4* rec, const bf16_t* gout, bf16_t* grows, int64_t n_rows, int G, int nb,
+template <int C, typename T>
+static void bucket_rows_grad(const uint4* rec, const T* gout, T* grows, int64_t n_rows, int G, int nb,
                              const int32_t* bstart, const int32_t* order, hipStream_t s) {
   static const int bt = tune_int("DVA_PLAN_BT", 8192);
   if (bt == 2048)
-    hipLaunchKernelGGL((bucket_rows_grad_kernel<C, 2048>), dim3(nb), dim3(1024), 0, s, rec, gout, grows, n_rows, G, bstart, order);
+    hipLaunchKernelGGL((bucket_rows_grad_kernel<C, 2048, T>), dim3(nb), dim3(1024), 0, s, rec, gout, grows, n_rows, G, bstart, order);
   else if (bt == 4096)
-    hipLaunchKernelGGL((bucket_rows_grad_kernel<C, 4096>), dim3(nb), dim3(1024), 0, s, rec, gout, grows, n_rows, G, bstart, order);
+    hipLaunchKernelGGL((bucket_rows_grad_kernel<C, 4096, T>), dim3(nb), dim3(1024), 0, s, rec, gout, grows, n_rows, G, bstart, order);
   else
-    hipLaunchKernelGGL((bucket_rows_grad_kernel<C, 8192>), dim3(nb), dim3(1024), 0, s, rec, gout, grows, n_rows, G, bstart, order);
+    hipLaunchKernelGGL((bucket_rows_grad_kernel<C, 8192, T>), dim3(nb), dim3(1024), 0, s, rec, gout, grows, n_rows, G, bstart, order);
 }
 
 }  // namespace ps
@@ -752,7 +752,8 @@ int dva_plan_split_rows_grad(const void* grad_out, const void* bucket_rec, int64
                              int32_t out_dtype, void* stream) {
   if (n_views < 0 || n_rows < 0 || C <= 0 || G <= 0) return DVA_ERR_INVALID;
   const bool f32 = dtype == DVA_F32 && out_dtype == DVA_F32;       // 32-byte records (dva_plan_split_sort_records32)
-  if (!ps::eligible(n_views, n_rows) || (!f32 && (dtype != DVA_BF16 || out_dtype != DVA_BF16)) ||
+  const bool f16 = dtype == DVA_F16 && out_dtype == DVA_F16;
+  if (!ps::eligible(n_views, n_rows) || (!f32 && !f16 && (dtype != DVA_BF16 || out_dtype != DVA_BF16)) ||
       (C != 32 && C != 64) || (G != 1 && G != 2 && G != 4) || ((C / (f32 ? 4 : 8)) % G) != 0)
     return DVA_ERR_UNSUPPORTED;
   if (!grad_out || !bucket_rec || !tables || !grad_rows) return DVA_ERR_INVALID;
@@ -772,7 +773,13 @@ int dva_plan_split_rows_grad(const void* grad_out, const void* bucket_rec, int64
     DVA_CHECK_LAUNCH();
     return DVA_OK;
   }
-  if (C == 64)
+  if (f16 && C == 64)
+    ps::bucket_rows_grad<64>((const uint4*)bucket_rec, (const f16_t*)grad_out, (f16_t*)grad_rows, n_rows, (int)G, nb,
+                             T.bstart, T.order, s);
+  else if (f16)
+    ps::bucket_rows_grad<32>((const uint4*)bucket_rec, (const f16_t*)grad_out, (f16_t*)grad_rows, n_rows, (int)G, nb,
+                             T.bstart, T.order, s);
+  else if (C == 64)
     ps::bucket_rows_grad<64>((const uint4*)bucket_rec, (const bf16_t*)grad_out, (bf16_t*)grad_rows, n_rows, (int)G, nb,
                              T.bstart, T.order, s);
   else

@@ -132,6 +132,12 @@ template <> struct RVec<bf16_t> {
                       pack_bf16x2(f[6], f[7]));
   }
 };
+template <> struct RVec<f16_t> {
+  static constexpr int N = 8;
+  typedef uint4 raw;
+  static __device__ __forceinline__ void unpack(const raw& r, float* f) { unpack_h8<f16_t>(r, f); }
+  static __device__ __forceinline__ raw pack(const float* f) { return pack_h8<f16_t>(f); }
+};
 
 // MODE 0: forward statistics (w y | w y^2); MODE 1: backward statistics (dz | dz a)
 template <typename T, int MODE>
@@ -312,7 +318,7 @@ extern "C" {
 int dva_rowbn_stats(const void* y, const int32_t* counts, double* sums, int64_t R, int32_t C,
                     int32_t dtype, void* stream) {
   if (R < 0 || C <= 0 || C > 4096 || !sums) return DVA_ERR_INVALID;
-  if (dtype != DVA_F32 && dtype != DVA_BF16) return DVA_ERR_INVALID;
+  if (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16) return DVA_ERR_INVALID;
   if (R == 0) return DVA_OK;
   if (!y) return DVA_ERR_INVALID;
   const dim3 block(64, 4);
@@ -324,6 +330,9 @@ int dva_rowbn_stats(const void* y, const int32_t* counts, double* sums, int64_t 
     if (dtype == DVA_F32)
       hipLaunchKernelGGL((rowbn_sums_vec_kernel<float, 0>), dim3((int)b), dim3(256), lds, (hipStream_t)stream,
                          (const float*)y, (const float*)nullptr, counts, (const float*)nullptr, sums, R, C, 0.f);
+    else if (dtype == DVA_F16)
+      hipLaunchKernelGGL((rowbn_sums_vec_kernel<f16_t, 0>), dim3((int)b), dim3(256), lds, (hipStream_t)stream,
+                         (const f16_t*)y, (const f16_t*)nullptr, counts, (const float*)nullptr, sums, R, C, 0.f);
     else
       hipLaunchKernelGGL((rowbn_sums_vec_kernel<bf16_t, 0>), dim3((int)b), dim3(256), lds, (hipStream_t)stream,
                          (const bf16_t*)y, (const bf16_t*)nullptr, counts, (const float*)nullptr, sums, R, C, 0.f);
@@ -333,6 +342,9 @@ int dva_rowbn_stats(const void* y, const int32_t* counts, double* sums, int64_t 
   if (dtype == DVA_F32)
     hipLaunchKernelGGL((rowbn_stats_kernel<float>), dim3(rows_grid(R)), block, lds, (hipStream_t)stream,
                        (const float*)y, counts, sums, R, C);
+  else if (dtype == DVA_F16)
+    hipLaunchKernelGGL((rowbn_stats_kernel<f16_t>), dim3(rows_grid(R)), block, lds, (hipStream_t)stream,
+                       (const f16_t*)y, counts, sums, R, C);
   else
     hipLaunchKernelGGL((rowbn_stats_kernel<bf16_t>), dim3(rows_grid(R)), block, lds, (hipStream_t)stream,
                        (const bf16_t*)y, counts, sums, R, C);
@@ -343,7 +355,7 @@ int dva_rowbn_stats(const void* y, const int32_t* counts, double* sums, int64_t 
 int dva_rowbn_apply(const void* y, const float* bn, void* out, int64_t R, int32_t C, float slope,
                     int32_t dtype, void* stream) {
   if (R < 0 || C <= 0) return DVA_ERR_INVALID;
-  if (dtype != DVA_F32 && dtype != DVA_BF16) return DVA_ERR_INVALID;
+  if (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16) return DVA_ERR_INVALID;
   if (R == 0) return DVA_OK;
   if (!y || !bn || !out) return DVA_ERR_INVALID;
   if (dtype == DVA_F32 ? rv_ok<float>(C, y, out, out) : rv_ok<bf16_t>(C, y, out, out)) {
@@ -352,6 +364,10 @@ int dva_rowbn_apply(const void* y, const float* bn, void* out, int64_t R, int32_
       hipLaunchKernelGGL((rowbn_apply_vec_kernel<float, 0>), vg, dim3(256), 0, (hipStream_t)stream, (const float*)y,
                          (const float*)nullptr, (const int32_t*)nullptr, bn, (const float*)nullptr, (float*)out, R,
                          C, slope);
+    else if (dtype == DVA_F16)
+      hipLaunchKernelGGL((rowbn_apply_vec_kernel<f16_t, 0>), vg, dim3(256), 0, (hipStream_t)stream,
+                         (const f16_t*)y, (const f16_t*)nullptr, (const int32_t*)nullptr, bn,
+                         (const float*)nullptr, (f16_t*)out, R, C, slope);
     else
       hipLaunchKernelGGL((rowbn_apply_vec_kernel<bf16_t, 0>), vg, dim3(256), 0, (hipStream_t)stream,
                          (const bf16_t*)y, (const bf16_t*)nullptr, (const int32_t*)nullptr, bn,
@@ -363,6 +379,9 @@ int dva_rowbn_apply(const void* y, const float* bn, void* out, int64_t R, int32_
   if (dtype == DVA_F32)
     hipLaunchKernelGGL((rowbn_apply_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream,
                        (const float*)y, bn, (float*)out, R, C, slope);
+  else if (dtype == DVA_F16)
+    hipLaunchKernelGGL((rowbn_apply_kernel<f16_t>), grid, dim3(256), 0, (hipStream_t)stream,
+                       (const f16_t*)y, bn, (f16_t*)out, R, C, slope);
   else
     hipLaunchKernelGGL((rowbn_apply_kernel<bf16_t>), grid, dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)y, bn, (bf16_t*)out, R, C, slope);
@@ -373,7 +392,7 @@ int dva_rowbn_apply(const void* y, const float* bn, void* out, int64_t R, int32_
 int dva_rowbn_bwd_stats(const void* grad_out, const void* y, const float* bn, double* sums, int64_t R,
                         int32_t C, float slope, int32_t dtype, void* stream) {
   if (R < 0 || C <= 0 || C > 4096 || !sums) return DVA_ERR_INVALID;
-  if (dtype != DVA_F32 && dtype != DVA_BF16) return DVA_ERR_INVALID;
+  if (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16) return DVA_ERR_INVALID;
   if (R == 0) return DVA_OK;
   if (!grad_out || !y || !bn) return DVA_ERR_INVALID;
   const dim3 block(64, 4);
@@ -385,6 +404,9 @@ int dva_rowbn_bwd_stats(const void* grad_out, const void* y, const float* bn, do
     if (dtype == DVA_F32)
       hipLaunchKernelGGL((rowbn_sums_vec_kernel<float, 1>), dim3((int)b), dim3(256), lds, (hipStream_t)stream,
                          (const float*)y, (const float*)grad_out, (const int32_t*)nullptr, bn, sums, R, C, slope);
+    else if (dtype == DVA_F16)
+      hipLaunchKernelGGL((rowbn_sums_vec_kernel<f16_t, 1>), dim3((int)b), dim3(256), lds, (hipStream_t)stream,
+                         (const f16_t*)y, (const f16_t*)grad_out, (const int32_t*)nullptr, bn, sums, R, C, slope);
     else
       hipLaunchKernelGGL((rowbn_sums_vec_kernel<bf16_t, 1>), dim3((int)b), dim3(256), lds, (hipStream_t)stream,
                          (const bf16_t*)y, (const bf16_t*)grad_out, (const int32_t*)nullptr, bn, sums, R, C, slope);
@@ -394,6 +416,10 @@ int dva_rowbn_bwd_stats(const void* grad_out, const void* y, const float* bn, do
   if (dtype == DVA_F32)
     hipLaunchKernelGGL((rowbn_bwd_stats_kernel<float>), dim3(rows_grid(R)), block, lds,
                        (hipStream_t)stream, (const float*)grad_out, (const float*)y, bn, sums, R, C, slope);
+  else if (dtype == DVA_F16)
+    hipLaunchKernelGGL((rowbn_bwd_stats_kernel<f16_t>), dim3(rows_grid(R)), block, lds,
+                       (hipStream_t)stream, (const f16_t*)grad_out, (const f16_t*)y, bn, sums, R, C,
+                       slope);
   else
     hipLaunchKernelGGL((rowbn_bwd_stats_kernel<bf16_t>), dim3(rows_grid(R)), block, lds,
                        (hipStream_t)stream, (const bf16_t*)grad_out, (const bf16_t*)y, bn, sums, R, C,
@@ -406,7 +432,7 @@ int dva_rowbn_bwd_apply(const void* grad_out, const void* y, const int32_t* coun
                         const float* sm, void* grad_y, int64_t R, int32_t C, float slope, int32_t dtype,
                         void* stream) {
   if (R < 0 || C <= 0) return DVA_ERR_INVALID;
-  if (dtype != DVA_F32 && dtype != DVA_BF16) return DVA_ERR_INVALID;
+  if (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16) return DVA_ERR_INVALID;
   if (R == 0) return DVA_OK;
   if (!grad_out || !y || !bn || !sm || !grad_y) return DVA_ERR_INVALID;
   if (dtype == DVA_F32 ? rv_ok<float>(C, y, grad_out, grad_y) : rv_ok<bf16_t>(C, y, grad_out, grad_y)) {
@@ -414,6 +440,9 @@ int dva_rowbn_bwd_apply(const void* grad_out, const void* y, const int32_t* coun
     if (dtype == DVA_F32)
       hipLaunchKernelGGL((rowbn_apply_vec_kernel<float, 1>), vg, dim3(256), 0, (hipStream_t)stream, (const float*)y,
                          (const float*)grad_out, counts, bn, sm, (float*)grad_y, R, C, slope);
+    else if (dtype == DVA_F16)
+      hipLaunchKernelGGL((rowbn_apply_vec_kernel<f16_t, 1>), vg, dim3(256), 0, (hipStream_t)stream,
+                         (const f16_t*)y, (const f16_t*)grad_out, counts, bn, sm, (f16_t*)grad_y, R, C, slope);
     else
       hipLaunchKernelGGL((rowbn_apply_vec_kernel<bf16_t, 1>), vg, dim3(256), 0, (hipStream_t)stream,
                          (const bf16_t*)y, (const bf16_t*)grad_out, counts, bn, sm, (bf16_t*)grad_y, R, C, slope);
@@ -424,6 +453,10 @@ int dva_rowbn_bwd_apply(const void* grad_out, const void* y, const int32_t* coun
   if (dtype == DVA_F32)
     hipLaunchKernelGGL((rowbn_bwd_apply_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream,
                        (const float*)grad_out, (const float*)y, counts, bn, sm, (float*)grad_y, R, C, slope);
+  else if (dtype == DVA_F16)
+    hipLaunchKernelGGL((rowbn_bwd_apply_kernel<f16_t>), grid, dim3(256), 0, (hipStream_t)stream,
+                       (const f16_t*)grad_out, (const f16_t*)y, counts, bn, sm, (f16_t*)grad_y, R, C,
+                       slope);
   else
     hipLaunchKernelGGL((rowbn_bwd_apply_kernel<bf16_t>), grid, dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)grad_out, (const bf16_t*)y, counts, bn, sm, (bf16_t*)grad_y, R, C,

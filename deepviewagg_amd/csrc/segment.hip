@@ -158,6 +158,12 @@ template <> struct SVec<bf16_t> {
                       pack_bf16x2(f[6], f[7]));
   }
 };
+template <> struct SVec<f16_t> {
+  static constexpr int N = 8;
+  typedef uint4 raw;
+  static __device__ __forceinline__ void unpack(const raw& r, float* f) { unpack_h8<f16_t>(r, f); }
+  static __device__ __forceinline__ raw pack(const float* f) { return pack_h8<f16_t>(f); }
+};
 
 template <typename T, int REDUCE>
 __global__ __launch_bounds__(256) void segment_csr_fwd_vec_kernel(const T* __restrict__ src,
@@ -312,7 +318,7 @@ using namespace dva;
 
 extern "C" {
 
-int dva_version(void) { return 306; }
+int dva_version(void) { return 307; }
 
 int dva_device_count(void) {
   int n = 0;
@@ -333,6 +339,8 @@ int dva_segment_csr_fwd(const void* src, const int64_t* ptr, void* out, int32_t*
     rc = launch_segment_fwd<float>(src, ptr, out, arg, n_groups, C, reduce, (hipStream_t)stream);
   else if (dtype == DVA_BF16)
     rc = launch_segment_fwd<bf16_t>(src, ptr, out, arg, n_groups, C, reduce, (hipStream_t)stream);
+  else if (dtype == DVA_F16)
+    rc = launch_segment_fwd<f16_t>(src, ptr, out, arg, n_groups, C, reduce, (hipStream_t)stream);
   else
     return DVA_ERR_INVALID;
   if (rc) return rc;
@@ -355,6 +363,9 @@ int dva_segment_csr_bwd(const void* grad_out, const int64_t* ptr, const int32_t*
   else if (dtype == DVA_BF16)
     rc = launch_segment_bwd<bf16_t>(grad_out, ptr, arg, grad_src, n_groups, C, reduce,
                                     (hipStream_t)stream);
+  else if (dtype == DVA_F16)
+    rc = launch_segment_bwd<f16_t>(grad_out, ptr, arg, grad_src, n_groups, C, reduce,
+                                    (hipStream_t)stream);
   else
     return DVA_ERR_INVALID;
   if (rc) return rc;
@@ -368,7 +379,7 @@ int dva_gather_csr(const void* src, const int64_t* ptr, void* out, int64_t n_gro
   if (n_groups == 0 || C == 0) return DVA_OK;
   // pure byte movement: with 16-byte aligned rows every thread copies 16 bytes of a group's row
   const int64_t row_bytes = (int64_t)C * (dtype == DVA_F32 ? 4 : 2);
-  if (dtype != DVA_F32 && dtype != DVA_BF16) return DVA_ERR_INVALID;
+  if (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16) return DVA_ERR_INVALID;
   if (row_bytes % 16 == 0 && ((uintptr_t)src % 16 == 0) && ((uintptr_t)out % 16 == 0)) {
     const int u = (int)(row_bytes / 16);
     hipLaunchKernelGGL((gather_csr_kernel<uint4>), dim3(grid_for(n_groups * (int64_t)u)), dim3(256), 0,
@@ -381,8 +392,8 @@ int dva_gather_csr(const void* src, const int64_t* ptr, void* out, int64_t n_gro
     hipLaunchKernelGGL((gather_csr_kernel<float>), dim3(grid), dim3(256), 0, (hipStream_t)stream,
                        (const float*)src, ptr, (float*)out, n_groups, C);
   else
-    hipLaunchKernelGGL((gather_csr_kernel<bf16_t>), dim3(grid), dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)src, ptr, (bf16_t*)out, n_groups, C);
+    hipLaunchKernelGGL((gather_csr_kernel<uint16_t>), dim3(grid), dim3(256), 0, (hipStream_t)stream,
+                       (const uint16_t*)src, ptr, (uint16_t*)out, n_groups, C);     // bf16 / fp16: 2-byte moves
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }

@@ -401,6 +401,7 @@ using namespace dva;
 extern "C" {
 
 int64_t dva_sparse_conv_workspace_bytes(int32_t K, int32_t Cin, int32_t Cout, int32_t dtype) {
+  if (dtype == DVA_F16) return DVA_ERR_UNSUPPORTED;          // fp32 / bf16 sparse convolution only
   if (K <= 0 || Cin <= 0 || Cout <= 0 || (dtype != DVA_F32 && dtype != DVA_BF16)) return DVA_ERR_INVALID;
   return (int64_t)K * pad_tile(Cin) * pad_out(Cout) * 2 * (dtype == DVA_F32 ? 2 : 1);
 }
@@ -410,6 +411,7 @@ int dva_sparse_conv_apply(const void* x, const int32_t* nbr, const float* W, con
                           int32_t dtype, void* workspace, int64_t workspace_bytes, void* stream) {
   if (n_src < 0 || n_dst < 0 || K <= 0 || Cin <= 0 || Cout <= 0 || (mode != 0 && mode != 1))
     return DVA_ERR_INVALID;
+  if (dtype == DVA_F16) return DVA_ERR_UNSUPPORTED;
   if (dtype != DVA_F32 && dtype != DVA_BF16) return DVA_ERR_INVALID;
   if (Cin % 16 != 0 || Cout % 16 != 0) return DVA_ERR_UNSUPPORTED;  // the host pads the channel counts
   if (n_src > 0x7fffffffLL || n_dst > 0x7fffffffLL / K) return DVA_ERR_UNSUPPORTED;
@@ -427,6 +429,7 @@ int dva_sparse_conv_apply(const void* x, const int32_t* nbr, const float* W, con
 int dva_sparse_conv_wgrad(const void* x, const int32_t* nbr, const void* grad_out, float* grad_W, int64_t n_src,
                           int64_t n_dst, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* stream) {
   if (n_src < 0 || n_dst < 0 || K <= 0 || Cin <= 0 || Cout <= 0) return DVA_ERR_INVALID;
+  if (dtype == DVA_F16) return DVA_ERR_UNSUPPORTED;
   if (dtype != DVA_F32 && dtype != DVA_BF16) return DVA_ERR_INVALID;
   if (Cin % 16 != 0 || Cout % 16 != 0) return DVA_ERR_UNSUPPORTED;
   if (n_src > 0x7fffffffLL || n_dst > 0x7fffffffLL / K) return DVA_ERR_UNSUPPORTED;

@@ -9,8 +9,10 @@ index and the row index; the only view-sized writes of a training step are the s
 16-byte view records of the rows gradient and one bf16 [V, 32] gradient row handed between two backward passes.
 Train-mode BatchNorm keeps one statistics pass per layer.
 
-Selected by ``pooling.GroupBimodalCSRPool`` inside ``torch.autocast(bfloat16)`` (or with ``FORCE = True``)
-when ``applicable`` holds; everything else takes the fp32 kernels of ``fused_deepset`` / ``ops``.
+Selected by ``pooling.GroupBimodalCSRPool`` inside ``torch.autocast(bfloat16)`` or ``torch.autocast(float16)`` (or with
+``FORCE = True``) when ``applicable`` holds; everything else takes the fp32 kernels of ``fused_deepset`` / ``ops``.
+Under float16 the value rows, the pooled output and the rows gradient are fp16; the score chain keeps its bf16
+operands (its [V, 32] gradient rows carry the GradScaler factor, which fp16 cannot hold).
 The per-point set branch (``mlp_set`` on N rows) runs on the same kind of kernels (``csrc/chain_set.hip``).
 """
 import os
@@ -21,7 +23,7 @@ from . import _lib, ops, fused_deepset
 from ._lib import check, ptr, require_device, stream_of
 from .fused_deepset import D, _bn_of, _bn_consts
 
-# None = auto (inside torch.autocast(bfloat16) only); True / False pin the choice (tests, bench A/B)
+# None = auto (inside torch.autocast(bfloat16 / float16) only); True / False pin the choice (tests, bench A/B)
 FORCE = None
 VIEWS_PER_CHUNK = 512       # tile-table construction granularity (one lane walks one chunk)
 OPS_BYTES = 18 * 64 * 16 + 7 * 64 * 32       # bf16 operand blocks + the fp32 copy of the forward operands
@@ -30,14 +32,17 @@ OPS_BYTES = 18 * 64 * 16 + 7 * 64 * 32       # bf16 operand blocks + the fp32 co
 def enabled():
     if FORCE is not None:
         return FORCE
-    return torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') == torch.bfloat16
+    return torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') in (torch.bfloat16, torch.float16)
+
+
+ROW_DTYPES = (torch.bfloat16, torch.float16)      # value-row dtypes of the view kernels (dva_chain_attn_fwd_dt)
 
 
 def applicable(module, x_mod, x_map, csr_idx=None):
     """Can ``module`` (a GroupBimodalCSRPool) pool ``x_mod`` (an ops.GatheredFeatures) on the chain?"""
     if not enabled() or module.use_mod or module.save_last:
         return False
-    if not isinstance(x_mod, ops.GatheredFeatures) or x_mod.rows.dtype != torch.bfloat16:
+    if not isinstance(x_mod, ops.GatheredFeatures) or x_mod.rows.dtype not in ROW_DTYPES:
         return False
     if not fused_deepset.applicable(module.E_map, module.E_score, x_map):        # incl. fp32 parameters / buffers
         return False
@@ -52,11 +57,11 @@ def applicable(module, x_mod, x_map, csr_idx=None):
     return V * 64 < (1 << 32) - 16 and R * C * 2 < (1 << 32) - 16 and N * max(C * 2, 128) < (1 << 32) - 16
 
 
-def pooled_output(csr_idx, N, C, dev):
-    """The bf16 [N, C] tensor the view kernel pools into: the rows of points WITHOUT views are cleared here (exact
-    zeros, pooling.py:870), the kernel writes every other row -- no fill of the whole tensor (round 5)."""
+def pooled_output(csr_idx, N, C, dev, dtype=torch.bfloat16):
+    """The [N, C] tensor (the value rows' dtype) the view kernel pools into: the rows of points WITHOUT views are
+    cleared here (exact zeros, pooling.py:870), the kernel writes every other row -- no fill of the whole tensor (round 5)."""
     lib = _lib.load()
-    out = torch.empty((N, C), dtype=torch.bfloat16, device=dev)
+    out = torch.empty((N, C), dtype=dtype, device=dev)
     check(lib.dva_zero_unseen_rows(ptr(csr_idx), ptr(out), N, C * 2, stream_of(out)), "dva_zero_unseen_rows")
     return out
 
@@ -271,17 +276,18 @@ class _ChainPool(torch.autograd.Function):
         need_bwd = any(ctx.needs_input_grad)
         S = chain_prologue(module, x_map, csr_idx, store_a2=CHAIN_A2 and need_bwd)
         # ---- the fused view kernel
-        out = pooled_output(csr_idx, N, C, dev)
+        out = pooled_output(csr_idx, N, C, dev, rows.dtype)
         # a backward will follow: the scores of every view stay (16 bytes per view) -- the attention backward starts from
         # them instead of evaluating the chain once more
         scores = torch.empty((V, 4), dtype=torch.float32, device=dev) if need_bwd else None
         # SURVEY.md 8(d) fused view-gather + attention: V (C s + F_map 4 + idx) + N (C s + ptr); idx = view->point
         # index + row index (4 + 4), per point the set-branch row (128) on top (+ 16 bytes per view of scores out in training)
         with ops._timed("chain_attn_fwd", V * (C * 2 + 32 + 8 + (16 if need_bwd else 0)) + N * (C * 2 + 128 + 8)):
-            check(lib.dva_chain_attn_fwd(ptr(x_map), ptr(S.vp), ptr(S.t_add), ptr(S.tiles), ptr(S.n_tiles), ptr(S.wops),
-                                         ptr(S.bn1), ptr(S.bn2), ptr(S.bn5), ptr(S.bn6), ptr(S.bs), ptr(rows),
-                                         ptr(row_idx), ptr(csr_idx), ptr(S.gw), ptr(S.gb), ptr(out), ptr(scores), N, V,
-                                         R, C, S.G, int(scaling), float(eps), st), "dva_chain_attn_fwd")
+            check(lib.dva_chain_attn_fwd_dt(ptr(x_map), ptr(S.vp), ptr(S.t_add), ptr(S.tiles), ptr(S.n_tiles),
+                                            ptr(S.wops), ptr(S.bn1), ptr(S.bn2), ptr(S.bn5), ptr(S.bn6), ptr(S.bs),
+                                            ptr(rows), ptr(row_idx), ptr(csr_idx), ptr(S.gw), ptr(S.gb), ptr(out),
+                                            ptr(scores), N, V, R, C, S.G, int(scaling), float(eps),
+                                            _lib.dtype_code(rows), st), "dva_chain_attn_fwd_dt")
         ctx.save_for_backward(rows, row_idx, x_map, csr_idx, S.vp, S.tiles, S.n_tiles, S.wops, S.t_add, S.zstar, S.arg,
                               S.mom, S.bn1, S.bn2, S.bn5, S.bn6, out, scores, S.bs, S.gw, S.gb, S.W1)
         ctx.plan = plan
@@ -340,8 +346,11 @@ def key_position_order(device):
 
 
 def keys_applicable(module, x_mod, x_map, csr_idx):
-    """Can ``module`` (a QKVBimodalCSRPool) take its keys from the recompute chain?"""
-    if not enabled() or module.use_mod_k or module.use_mod_q or module.save_last or module.debug:
+    """Can ``module`` (a QKVBimodalCSRPool) take its keys from the recompute chain?  bf16 autocast only: the key
+    kernels have no fp16 form (under float16 the compatibilities come from the generic path)."""
+    if not enabled() or (FORCE is None and torch.get_autocast_dtype('cuda') != torch.bfloat16):
+        return False
+    if module.use_mod_k or module.use_mod_q or module.save_last or module.debug:
         return False
     if not isinstance(x_mod, ops.GatheredFeatures) or x_mod.rows.dtype != torch.bfloat16:
         return False

@@ -213,7 +213,7 @@ def backward(ctx, gout):
     R, C = rows.shape
     G = qk[0] if qk is not None else module.E_score.weight.shape[0]
     st = stream_of(x_map)
-    gout = gout.contiguous().to(torch.bfloat16)
+    gout = gout.contiguous().to(rows.dtype)          # bf16, or fp16 under autocast(float16)
     S = SimpleNamespace(vp=vp, tiles=tiles, n_tiles=n_tiles, wops=wops, t_add=t_add, zstar=zstar, arg=arg, mom=mom,
                         bn1=bn1, bn2=bn2, bn5=bn5, bn6=bn6, W1=W1, G=G if qk is None else D, training=training,
                         a2=getattr(ctx, "a2", None))
@@ -228,7 +228,8 @@ def backward(ctx, gout):
     plan = None
     if ctx.needs_input_grad[0]:
         plan = ctx.plan if ctx.plan is not None else ops.row_plan(row_idx, R, with_counts=False)[0]
-    planrec = PLAN_ORDER_RECORDS and plan is not None and not isinstance(plan, ops.SplitPlan)
+    planrec = (PLAN_ORDER_RECORDS and plan is not None and not isinstance(plan, ops.SplitPlan)
+               and rows.dtype == torch.bfloat16)          # dva_chain_attn_bwd_planrec reads bf16 rows
     if planrec:
         # A/B (round 4): records written in plan order through the inverse of the plan permutation
         inv = torch.empty(V, dtype=torch.int32, device=dev)
@@ -241,9 +242,10 @@ def backward(ctx, gout):
                                                  ptr(dc), ptr(rec), ptr(gwb), N, V, R, C, G, scaling, eps, st),
                   "dva_chain_attn_bwd_planrec")
         else:
-            check(lib.dva_chain_attn_bwd(ptr(scores), ptr(vp), ptr(tiles), ptr(n_tiles), ptr(rows), ptr(row_idx),
-                                         ptr(csr_idx), ptr(gw), ptr(gb), ptr(gout), ptr(out), ptr(dc), ptr(rec),
-                                         ptr(gwb), N, V, R, C, G, scaling, eps, st), "dva_chain_attn_bwd")
+            check(lib.dva_chain_attn_bwd_dt(ptr(scores), ptr(vp), ptr(tiles), ptr(n_tiles), ptr(rows), ptr(row_idx),
+                                            ptr(csr_idx), ptr(gw), ptr(gb), ptr(gout), ptr(out), ptr(dc), ptr(rec),
+                                            ptr(gwb), N, V, R, C, G, scaling, eps, _lib.dtype_code(rows), st),
+                  "dva_chain_attn_bwd_dt")
     del scores
     # ---- rows gradient: segmented reduction over the row plan (deterministic, no atomics)
     grows = None
@@ -260,7 +262,7 @@ def backward(ctx, gout):
             with ops._timed("view_gather_rows_grad", V * (4 + 16 + C * 2) + R * (C * 2 + 4)):
                 check(lib.dva_view_gather_rows_grad_rec16_to(ptr(gout), None if planrec else ptr(perm), ptr(row_ptr),
                                                              ptr(rec), ptr(g), _lib.dtype_code(g), R, V, C, G,
-                                                             _lib.DVA_BF16, stream),
+                                                             _lib.dtype_code(gout), stream),
                       "dva_view_gather_rows_grad_rec16_to")
             return g
         if OVERLAP_ROWS_GRAD:

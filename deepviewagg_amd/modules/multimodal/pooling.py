@@ -91,7 +91,7 @@ def mlp_on_gathered_rows(mlp, rows, counts, n_views=None, first_linear_done=Fals
     for i, block in enumerate(mlp):
         lin, bn, act = block[0], block[1].batch_norm, block[2]
         slope = _leaky_slope(act)
-        if slope is None or x.dtype not in (torch.float32, torch.bfloat16):
+        if slope is None or x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
             if first_linear_done:
                 raise NotImplementedError("hoisted first Linear with an activation the row kernels do not cover")
             return _mlp_on_gathered_rows_torch(mlp, rows, counts)
@@ -119,7 +119,7 @@ def _hoisted_first_linear(mlp, x_mod):
     (E_mod(x_mod) as a [V, C_out] tensor, True), or (the materialised [V, C_in] gather, False) when it does not apply."""
     lin, bn, act = mlp[0][0], mlp[0][1].batch_norm, mlp[0][2]
     rows = x_mod.rows
-    ok = (x_mod.exact and lin.bias is None and rows.is_cuda and rows.dtype in (torch.float32, torch.bfloat16)
+    ok = (x_mod.exact and lin.bias is None and rows.is_cuda and rows.dtype in (torch.float32, torch.bfloat16, torch.float16)
           and all(_leaky_slope(b[2]) is not None for b in mlp))
     if not ok:
         return x_mod.materialize(), False
@@ -368,7 +368,7 @@ class GroupBimodalCSRPool(nn.Module, _SaveLast):
             # bf16 recompute chain: E_mod on the map rows, then ONE view kernel (DeepSetFeat scores, softmax,
             # row gather, weighted sum, gate) -- no [V, .] activation tensor at all (fused_chain.py)
             val_rows = mlp_on_gathered_rows(self.E_mod, x_mod.rows, x_mod.counts, x_mod.shape[0])
-            if val_rows.dtype == torch.bfloat16:
+            if val_rows.dtype in (torch.bfloat16, torch.float16):
                 return fused_chain.chain_pool(self, x_mod.with_rows(val_rows), x_map, csr_idx)
         fused_scores = (not self.use_mod and not self.save_last
                         and fused_deepset.applicable(self.E_map, self.E_score, x_map))

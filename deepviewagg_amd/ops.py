@@ -458,6 +458,10 @@ def gather_nearest(x, packed_idx):
 
 
 def _anchor_ok(C, dtype):
+    """The anchor route of the bilinear backward (dva_anchor_rows_sum / _fixup: fp32 and bf16 gradients only; an fp16
+    gradient takes dva_gather_rows_sum)."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        return False
     vec = 4 if dtype == torch.float32 else 8
     lpr = C // vec
     return C % vec == 0 and lpr > 0 and (lpr & (lpr - 1)) == 0 and lpr <= 64
@@ -634,10 +638,10 @@ SPLIT_PLAN_MIN_VIEWS = 1 << 20
 
 
 def split_plan_serves(dtype, C):
-    """Does a consumer of [R, C] value rows of this dtype take its rows gradient over a SplitPlan?  bf16: the 16-byte
-    records of the chain (any C: bucket kernel at C in {32, 64}, the two record passes otherwise); fp32: the 32-byte
+    """Does a consumer of [R, C] value rows of this dtype take its rows gradient over a SplitPlan?  bf16 / fp16: the
+    16-byte records of the chain (any C: bucket kernel at C in {32, 64}, the two record passes otherwise); fp32: the 32-byte
     records of the lean attention backward at C in {32, 64} (round 6).  Everything else wants the permutation."""
-    return dtype == torch.bfloat16 or (dtype == torch.float32 and C in (32, 64))
+    return dtype in (torch.bfloat16, torch.float16) or (dtype == torch.float32 and C in (32, 64))
 
 
 def _split_plan_pays(n_views, n_rows):
@@ -737,20 +741,21 @@ class SplitPlan:
         return g
 
     def rows_grad_fused(self, gout, rec, C, G, stream):
-        """bf16 [R, C] rows gradient from KEYED view-order records through pass A + the bucket kernel
+        """bf16 / fp16 [R, C] rows gradient (gout's dtype) from KEYED view-order records through pass A + the bucket kernel
         (``dva_plan_split_rows_grad``: no pass B, no plan-order records), or None where that kernel does not apply."""
         lib = _lib.load()
         V, R = self.row_idx.shape[0], self.n_rows
         # everything dva_plan_split_rows_grad refuses (DVA_ERR_UNSUPPORTED: dtype, C, G, 16-byte alignment of the
         # gradient rows; the records and the output are fresh allocations) is decided here, BEFORE pass A is launched
-        if (gout.dtype != torch.bfloat16 or C not in (32, 64) or G not in (1, 2, 4) or (C // 8) % G
+        if (gout.dtype not in (torch.bfloat16, torch.float16) or C not in (32, 64) or G not in (1, 2, 4) or (C // 8) % G
                 or gout.data_ptr() % 16 or not gout.is_contiguous()):
             return None
         brec = self.sort_records(rec, keyed=True, bucket_order=True)
-        g = torch.empty((R, C), dtype=torch.bfloat16, device=gout.device)
+        g = torch.empty((R, C), dtype=gout.dtype, device=gout.device)
+        code = dtype_code(gout)
         with _timed("view_gather_rows_grad", V * (16 + C * 2) + R * C * 2):
             check(lib.dva_plan_split_rows_grad(ptr(gout), ptr(brec), V, R, ptr(self.tables), self.tables.numel(), ptr(g),
-                                               C, G, _lib.DVA_BF16, _lib.DVA_BF16, stream), "dva_plan_split_rows_grad")
+                                               C, G, code, code, stream), "dva_plan_split_rows_grad")
         return g
 
 
@@ -782,7 +787,7 @@ def rows_grad_rec16(gout, plan, rec, R, C, G, out_dtype, stream):
     lib = _lib.load()
     V = rec.shape[0]
     if isinstance(plan, SplitPlan):
-        if SPLIT_FUSED and out_dtype == torch.bfloat16:
+        if SPLIT_FUSED and out_dtype == gout.dtype:
             fused = plan.rows_grad_fused(gout, rec, C, G, stream)
             if fused is not None:
                 return fused
@@ -793,7 +798,7 @@ def rows_grad_rec16(gout, plan, rec, R, C, G, out_dtype, stream):
     g = torch.empty((R, C), dtype=out_dtype, device=gout.device)
     with _timed("view_gather_rows_grad", V * ((4 if perm is not None else 0) + 16 + C * 2) + R * (C * 2 + 4)):
         check(lib.dva_view_gather_rows_grad_rec16_to(ptr(gout), ptr(perm), ptr(row_ptr), ptr(rec), ptr(g), dtype_code(g),
-                                                     R, V, C, G, _lib.DVA_BF16, stream),
+                                                     R, V, C, G, dtype_code(gout), stream),
               "dva_view_gather_rows_grad_rec16_to")
     return g
 
@@ -1008,7 +1013,7 @@ def gather_segment_max_applicable(x_mod, atom_ptr):
     # 16-byte alignment of the row base: a contiguous slice of a feature map with a storage offset that is not a
     # multiple of 16 bytes takes the materialised route instead of DVA_ERR_UNSUPPORTED; non-contiguous
     # rows are copied by the op (fresh, aligned allocation)
-    return (x_mod.rows.dtype in (torch.float32, torch.bfloat16) and C % (16 // es) == 0 and C > 0
+    return (x_mod.rows.dtype in (torch.float32, torch.bfloat16, torch.float16) and C % (16 // es) == 0 and C > 0
             and x_mod.rows.is_cuda and (not x_mod.rows.is_contiguous() or x_mod.rows.data_ptr() % 16 == 0)
             and _atoms_per_view_ok(atom_ptr))
 
@@ -1244,8 +1249,8 @@ class _ViewGatherAttention(torch.autograd.Function):
             g_w = gwb[:G].reshape(w_shape) if (has_gate and w_shape is not None) else None
             g_b = gwb[G:].reshape(b_shape) if (has_gate and b_shape is not None) else None
             return grows, None, gcompat, None, g_w, g_b, None, None, None
-        if (LEAN_ATTENTION_BWD and use_plan and ATTENTION_ALGO != 1 and rows.dtype == torch.bfloat16
-                and gout.dtype == torch.bfloat16 and out.dtype == torch.bfloat16 and G in (1, 2, 4)
+        if (LEAN_ATTENTION_BWD and use_plan and ATTENTION_ALGO != 1 and rows.dtype in (torch.bfloat16, torch.float16)
+                and gout.dtype == rows.dtype and out.dtype == rows.dtype and G in (1, 2, 4)
                 and C in (32, 64, 128, 256, 512) and V > 0 and V * 16 < (1 << 32) - 16
                 and max(R, N) * C * 2 < (1 << 32) - 16):
             # bf16 rows (round 4; QKVBimodalCSRPool on the chain, and every bf16 caller with <= 4 score groups): the
@@ -1262,12 +1267,13 @@ class _ViewGatherAttention(torch.autograd.Function):
             dc = torch.empty((V, 4), dtype=torch.float32, device=rows.device)
             rec = torch.empty((V, 4), dtype=torch.int32, device=rows.device)
             with _timed("view_gather_attention_bwd", V * (C * 2 + 16 + 8 + 16 + 16) + N * (C * 2 + 8)):
-                check(lib.dva_chain_attn_bwd(
+                check(lib.dva_chain_attn_bwd_dt(
                     ptr(sc4), ptr(vp), ptr(tiles), ptr(n_tiles), ptr(rows), ptr(row_idx), ptr(csr_idx),
                     ptr(gw) if has_gate else None, ptr(gb) if has_gate else None, ptr(gout), ptr(out), ptr(dc),
-                    ptr(rec), ptr(gwb), N, V, R, C, G, scaling, ctx.eps, stream_of(rows)), "dva_chain_attn_bwd")
+                    ptr(rec), ptr(gwb), N, V, R, C, G, scaling, ctx.eps, dtype_code(rows), stream_of(rows)),
+                      "dva_chain_attn_bwd_dt")
             plan = ctx.plan if ctx.plan is not None else row_plan(row_idx, R, with_counts=False)[0]
-            # bf16: rounded where it is summed
+            # bf16 / fp16: rounded where it is summed
             grows = rows_grad_rec16(gout, plan, rec, R, C, G, rows.dtype, stream_of(rows))
             g_w = gwb[:G].reshape(w_shape) if (has_gate and w_shape is not None) else None
             g_b = gwb[G:].reshape(b_shape) if (has_gate and b_shape is not None) else None
@@ -1585,9 +1591,10 @@ class _SparseConv(torch.autograd.Function):
 def sparse_conv(x, W, bias, nbr, nbr_t):
     """Sparse convolution over a kernel map pair (see ``voxel_kernel_map``): x [n_src, Cin] (fp32 or bf16),
     W fp32 [K, Cin, Cout], bias [Cout] or None -> [n_dst, Cout].  Under ``torch.autocast`` the features are
-    taken in the autocast dtype (the weights stay fp32 masters, rounded to bf16 inside the kernel)."""
+    taken in the autocast dtype (the weights stay fp32 masters, rounded to bf16 inside the kernel); the kernels have no fp16
+    form, so under autocast(float16) the 3D branch stays fp32 (the fusion concat already promotes to it)."""
     if torch.is_autocast_enabled() and x.is_cuda:
-        x = x.to(torch.get_autocast_gpu_dtype())
+        x = x.to(torch.bfloat16 if torch.get_autocast_dtype('cuda') == torch.bfloat16 else torch.float32)
     return _SparseConv.apply(x, W, bias, nbr, nbr_t)
 
 

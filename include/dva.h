@@ -12,7 +12,13 @@
  *
  * Layouts: feature maps are channels-last x[B][H][W][C]; row matrices are row-major [rows][C];
  * CSR pointers are int64 (reference: torch.LongTensor). dtype codes below select the element type
- * of "feature" buffers (void*): fp32 or bf16; scores / mapping features / statistics are fp32.
+ * of "feature" buffers (void*): fp32, bf16 or fp16; scores / mapping features / statistics are fp32.
+ * DVA_F16 (torch.float16, autocast(float16)) is accepted by: dva_segment_csr_fwd / _bwd, dva_gather_csr,
+ * dva_gather_nearest_fwd / _bwd, dva_gather_bilinear_fwd / _bwd, dva_gather_rows_sum, dva_gather_segment_max_fwd /
+ * _bwd, dva_view_attention_*, dva_view_gather_attention_*, dva_view_gather_rows_grad, dva_view_gather_rows_grad_rec16,
+ * dva_view_gather_rows_grad_rec16_to, dva_rowbn_*, dva_chain_attn_fwd_dt, dva_chain_attn_bwd_dt and
+ * dva_plan_split_rows_grad (dtype = out_dtype = DVA_F16).  Every other entry with a dtype argument returns
+ * DVA_ERR_UNSUPPORTED for it before launching anything.
  */
 #ifndef DVA_H_
 #define DVA_H_
@@ -31,6 +37,7 @@ extern "C" {
 
 #define DVA_F32 0
 #define DVA_BF16 1
+#define DVA_F16 2
 
 #define DVA_SUM 0
 #define DVA_MEAN 1
@@ -226,7 +233,8 @@ int dva_plan_split_sort_records(const int32_t* row_idx, const void* rec, int64_t
  * fp32 sums in its registers, ranks and stages the bucket's tiles in LDS like pass B and consumes the staged records where
  * they lie (the 16 bytes per view pass B writes and the rows gradient reads again never exist).  grad_rows [n_rows][C]
  * bf16, written; deterministic; a row is summed by one lane team in view order (dva_view_gather_rows_grad_rec16* splits
- * it over 8 lane slots: the two agree to fp32 rounding).  bf16 / bf16, C in {32, 64}, G in {1, 2, 4}; otherwise
+ * it over 8 lane slots: the two agree to fp32 rounding).  bf16 / bf16 or fp16 / fp16 (fp32 sums, one rounding), C in
+ * {32, 64}, G in {1, 2, 4}; otherwise
  * DVA_ERR_UNSUPPORTED (the caller runs pass B and dva_view_gather_rows_grad_rec16_to).
  * fp32 / fp32 (round 6; the reference's default arithmetic, models/base_model.py:244,381): bucket_rec = the 32-BYTE records
  * of dva_chain_attn_bwd_f32 in bucket order, from dva_plan_split_sort_records32 -- pass A on {point | 4 fp32 weights | 3 pad
@@ -255,7 +263,8 @@ int dva_view_gather_rows_grad(const void* grad_out, const float* att, const floa
 int dva_view_gather_rows_grad_rec16(const void* grad_out, const int32_t* perm, const int32_t* row_ptr,
                                     const void* view_rec16, float* grad_rows, int64_t n_rows, int64_t n_views,
                                     int32_t C, int32_t G, int32_t dtype, void* stream);
-/* The same with the output dtype chosen by the caller: out_dtype = DVA_F32 (as above) or DVA_BF16 -- the summed row is
+/* The same with the output dtype chosen by the caller: out_dtype = DVA_F32 (as above) or the 2-byte dtype of grad_out
+ * (DVA_BF16 / DVA_F16) -- the summed row is
  * rounded once where it is summed, for maps that are bf16 anyway (the gradient autograd hands on has the map's dtype:
  * core/multimodal/image.py:1262-1287 is an index_add in the map's dtype); no fp32 [n_rows, C] tensor, no conversion pass. */
 int dva_view_gather_rows_grad_rec16_to(const void* grad_out, const int32_t* perm, const int32_t* row_ptr,
@@ -542,6 +551,14 @@ int dva_chain_attn_fwd(const float* x_map, const int32_t* view_point, const floa
                        const int32_t* row_idx, const int64_t* ptr, const float* gate_w, const float* gate_b,
                        void* out, float* scores_out, int64_t n_points, int64_t n_views, int64_t n_rows, int32_t C,
                        int32_t G, int32_t scaling, float eps, void* stream);
+/* dva_chain_attn_fwd with the element type of rows and out as an argument: dtype DVA_BF16 (= dva_chain_attn_fwd) or
+ * DVA_F16 (autocast(float16): fp16 value rows, fp16 pooled features; the scores stay bf16-operand / fp32-accumulator). */
+int dva_chain_attn_fwd_dt(const float* x_map, const int32_t* view_point, const float* u, const void* tiles,
+                          const int32_t* n_tiles, const void* ops, const float* bn1, const float* bn2,
+                          const float* bn5, const float* bn6, const float* score_bias, const void* rows,
+                          const int32_t* row_idx, const int64_t* ptr, const float* gate_w, const float* gate_b,
+                          void* out, float* scores_out, int64_t n_points, int64_t n_views, int64_t n_rows, int32_t C,
+                          int32_t G, int32_t scaling, float eps, int32_t dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------ *
  * Recompute chain with a per-view E_mod: the fused path of the BILINEAR gather (interpolate=True;
@@ -669,6 +686,13 @@ int dva_chain_attn_bwd(const float* scores, const int32_t* view_point, const voi
                        const float* gate_b, const void* grad_out, const void* out, float* grad_scores, void* view_rec,
                        float* grad_gate_wb, int64_t n_points, int64_t n_views, int64_t n_rows, int32_t C, int32_t G,
                        int32_t scaling, float eps, void* stream);
+/* dva_chain_attn_bwd with the element type of rows / grad_out / out as an argument: DVA_BF16 (= dva_chain_attn_bwd) or
+ * DVA_F16.  The 16-byte view records keep their bf16 weights for both. */
+int dva_chain_attn_bwd_dt(const float* scores, const int32_t* view_point, const void* tiles, const int32_t* n_tiles,
+                          const void* rows, const int32_t* row_idx, const int64_t* ptr, const float* gate_w,
+                          const float* gate_b, const void* grad_out, const void* out, float* grad_scores, void* view_rec,
+                          float* grad_gate_wb, int64_t n_points, int64_t n_views, int64_t n_rows, int32_t C, int32_t G,
+                          int32_t scaling, float eps, int32_t dtype, void* stream);
 /* A/B variant of round 4 (profiles/r04*_rows_grad_planrec_ab.json): dva_chain_attn_bwd that writes the
  * 16-byte record of view v to slot rec_pos[v] -- its position in the row plan, rec_pos = dva_plan_inverse(perm) -- so that
  * dva_view_gather_rows_grad_rec16(perm = NULL) streams the records instead of gathering them. */

@@ -209,6 +209,9 @@ SIGNATURES = {
     "dva_knn_workspace_bytes": (ctypes.c_int64, [_i64]),
     "dva_knn": (ctypes.c_int, [_vp, _i64, _vp, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "dva_view_occlusion": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "dva_knn_query_workspace_bytes": (ctypes.c_int64, [_i64, _i64]),
+    "dva_knn_query": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "dva_pointwise_pca": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
     "dva_lex_workspace_bytes": (ctypes.c_int64, [_i64]),
     "dva_argsort_i64": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "dva_argunique_i64": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp]),

@@ -9,6 +9,10 @@
 // first neighbour.  Exactness: cells are visited in Chebyshev shells around the query's cell; after shell R
 // every unvisited point is farther than R*cell - slack, so the search stops as soon as the current k-th
 // distance is below that bound (slack absorbs the float rounding of the cell assignment).
+// dva_knn_query (PCAComputePointwise, reference core/data_transform/features.py:360-485) runs the same search for
+// the points of a separate query cloud, walked in the cell order of the search cloud's grid; the order is then
+// (d2, search index) alone, with no self-first rule.  The argument holds for queries outside the search cloud's
+// box as long as bbox covers both clouds.
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -79,12 +83,24 @@ __device__ __forceinline__ int cell_start(const uint64_t* __restrict__ tkeys, co
   }
 }
 
+// the query points of a separate query cloud, in the cell order of their keys: qpts[i] = (xyz, original index)
+__global__ __launch_bounds__(256) void knn_query_points_kernel(const float* __restrict__ xyz,
+                                                                const int32_t* __restrict__ perm, int64_t n,
+                                                                float4* __restrict__ qpts) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t o = perm[i];
+    qpts[i] = make_float4(xyz[3 * (int64_t)o], xyz[3 * (int64_t)o + 1], xyz[3 * (int64_t)o + 2], __int_as_float(o));
+  }
+}
+
+// qpts [nq] = the queries (x, y, z, query index) in cell order; pts / keys_sorted [n] = the search cloud.  dva_knn
+// passes its sorted cloud as both.
 template <int KCAP>
 __global__ __launch_bounds__(KNN_TPB) void knn_query_kernel(
-    const float4* __restrict__ pts, const uint64_t* __restrict__ keys_sorted, int64_t n,
-    const float* __restrict__ bbox, float cell, const uint64_t* __restrict__ tkeys,
-    const int32_t* __restrict__ tvals, uint32_t mask, int k, int max_shell, uint8_t* __restrict__ done,
-    int32_t* __restrict__ nbr, float* __restrict__ d2_out) {
+    const float4* __restrict__ qpts, int64_t nq, const float4* __restrict__ pts,
+    const uint64_t* __restrict__ keys_sorted, int64_t n, const float* __restrict__ bbox, float cell,
+    const uint64_t* __restrict__ tkeys, const int32_t* __restrict__ tvals, uint32_t mask, int k, int max_shell,
+    uint8_t* __restrict__ done, int32_t* __restrict__ nbr, float* __restrict__ d2_out) {
   __shared__ float s_d[KCAP][KNN_TPB];
   __shared__ int32_t s_i[KCAP][KNN_TPB];
   const int t = threadIdx.x;
@@ -94,8 +110,8 @@ __global__ __launch_bounds__(KNN_TPB) void knn_query_kernel(
   const int r_all = (int)(ext * inv_cell) + 2;          // shells that cover the whole cloud
   const int r_max = max_shell < r_all ? max_shell : r_all;
   // queries in sorted (cell) order: the threads of a wavefront walk the same few cells
-  for (int64_t qs = blockIdx.x * (int64_t)KNN_TPB + t; qs < n; qs += (int64_t)gridDim.x * KNN_TPB) {
-    const float4 q = pts[qs];
+  for (int64_t qs = blockIdx.x * (int64_t)KNN_TPB + t; qs < nq; qs += (int64_t)gridDim.x * KNN_TPB) {
+    const float4 q = qpts[qs];
     const int qi = __float_as_int(q.w);
     if (done && done[qi]) continue;      // finished on a finer grid
     const int cx = cell_of(q.x, bbox[0], inv_cell), cy = cell_of(q.y, bbox[1], inv_cell),
@@ -201,16 +217,23 @@ __global__ __launch_bounds__(256) void occlusion_kernel(const int32_t* __restric
 
 static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 struct KnnLayout {
-  size_t keys, ids, keys_sorted, perm, pts, tkeys, tvals, temp, temp_bytes, total;
+  size_t keys, ids, keys_sorted, perm, pts, tkeys, tvals, qkeys, qids, qkeys_sorted, qperm, qpts, temp, temp_bytes,
+      total;
   uint64_t cap;
 };
-static int knn_layout(int64_t n, KnnLayout* L) {
-  size_t tmp = 0;
+// n search points; nq > 0: a separate query cloud (dva_knn_query) with its own sort; the two sorts share the
+// temp storage
+static int knn_layout(int64_t n, KnnLayout* L, int64_t nq = 0) {
+  size_t tmp = 0, qtmp = 0;
   uint64_t* nk = nullptr;
   int32_t* nv = nullptr;
   if (rocprim::radix_sort_pairs(nullptr, tmp, nk, nk, nv, nv, (size_t)n, 0, 3 * CELL_BITS, (hipStream_t)0) !=
       hipSuccess)
     return DVA_ERR_LAUNCH;
+  if (nq > 0 && rocprim::radix_sort_pairs(nullptr, qtmp, nk, nk, nv, nv, (size_t)nq, 0, 3 * CELL_BITS,
+                                          (hipStream_t)0) != hipSuccess)
+    return DVA_ERR_LAUNCH;
+  if (qtmp > tmp) tmp = qtmp;
   uint64_t cap = 64;
   while (cap < 2 * (uint64_t)n) cap <<= 1;
   L->cap = cap;
@@ -222,6 +245,11 @@ static int knn_layout(int64_t n, KnnLayout* L) {
   L->pts = off;         off += al256((size_t)n * 16);
   L->tkeys = off;       off += al256(cap * 8);
   L->tvals = off;       off += al256(cap * 4);
+  L->qkeys = off;        off += al256((size_t)nq * 8);
+  L->qids = off;         off += al256((size_t)nq * 4);
+  L->qkeys_sorted = off; off += al256((size_t)nq * 8);
+  L->qperm = off;        off += al256((size_t)nq * 4);
+  L->qpts = off;         off += al256((size_t)nq * 16);
   L->temp = off;        L->temp_bytes = tmp; off += al256(tmp);
   L->total = off;
   return DVA_OK;
@@ -231,6 +259,20 @@ static inline int grid256(int64_t n) {
   if (b > 8192) b = 8192;
   if (b < 1) b = 1;
   return (int)b;
+}
+
+static void launch_knn_query(const float4* qpts, int64_t nq, const float4* pts, const uint64_t* keys_sorted,
+                             int64_t n, const float* bbox, float cell, const uint64_t* tkeys, const int32_t* tvals,
+                             uint32_t mask, int k, int max_shell, uint8_t* done, int32_t* neighbors, float* dist2,
+                             hipStream_t s) {
+  int64_t qb = (nq + KNN_TPB - 1) / KNN_TPB;
+  if (qb > 256 * 32) qb = 256 * 32;
+  if (k <= 64)
+    hipLaunchKernelGGL(knn_query_kernel<64>, dim3((int)qb), dim3(KNN_TPB), 0, s, qpts, nq, pts, keys_sorted, n, bbox,
+                       cell, tkeys, tvals, mask, k, max_shell, done, neighbors, dist2);
+  else
+    hipLaunchKernelGGL(knn_query_kernel<128>, dim3((int)qb), dim3(KNN_TPB), 0, s, qpts, nq, pts, keys_sorted, n, bbox,
+                       cell, tkeys, tvals, mask, k, max_shell, done, neighbors, dist2);
 }
 
 }  // namespace dva
@@ -277,14 +319,69 @@ int dva_knn(const float* xyz, int64_t n, const float* bbox, float cell, int32_t 
   if (hipMemsetAsync(tkeys, 0xff, L.cap * 8, s) != hipSuccess) return DVA_ERR_LAUNCH;
   hipLaunchKernelGGL(knn_cells_kernel, dim3(grid256(n)), dim3(256), 0, s, xyz, keys_sorted, perm, n, pts, tkeys,
                      tvals, (uint32_t)(L.cap - 1));
-  int64_t qb = (n + KNN_TPB - 1) / KNN_TPB;
-  if (qb > 256 * 32) qb = 256 * 32;
-  if (k <= 64)
-    hipLaunchKernelGGL(knn_query_kernel<64>, dim3((int)qb), dim3(KNN_TPB), 0, s, pts, keys_sorted, n, bbox, cell, tkeys,
-                       tvals, (uint32_t)(L.cap - 1), k, max_shell, done, neighbors, dist2);
-  else
-    hipLaunchKernelGGL(knn_query_kernel<128>, dim3((int)qb), dim3(KNN_TPB), 0, s, pts, keys_sorted, n, bbox, cell, tkeys,
-                       tvals, (uint32_t)(L.cap - 1), k, max_shell, done, neighbors, dist2);
+  launch_knn_query(pts, n, pts, keys_sorted, n, bbox, cell, tkeys, tvals, (uint32_t)(L.cap - 1), k, max_shell, done,
+                   neighbors, dist2, s);
+  DVA_CHECK_LAUNCH();
+  return DVA_OK;
+}
+
+int64_t dva_knn_query_workspace_bytes(int64_t n_query, int64_t n_search) {
+  if (n_query < 0 || n_search < 0) return DVA_ERR_INVALID;
+  if (n_query > 0x7fffffffLL || n_search > 0x3fffffffLL) return DVA_ERR_UNSUPPORTED;
+  if (n_query == 0 || n_search == 0) return 256;
+  KnnLayout L;
+  int rc = knn_layout(n_search, &L, n_query);
+  if (rc) return rc;
+  return (int64_t)L.total;
+}
+
+int dva_knn_query(const float* query_xyz, int64_t n_query, const float* search_xyz, int64_t n_search,
+                  const float* bbox, float cell, int32_t k, int32_t max_shell, uint8_t* done, int32_t* neighbors,
+                  float* dist2, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (n_query < 0 || n_search < 0 || k <= 0 || k > KNN_KMAX || n_search < k || !(cell > 0.f) || max_shell < 1)
+    return DVA_ERR_INVALID;
+  if (n_query > 0x7fffffffLL || n_search > 0x3fffffffLL) return DVA_ERR_UNSUPPORTED;
+  if (n_query == 0) return DVA_OK;
+  if (!query_xyz || !search_xyz || !bbox || !neighbors || !workspace) return DVA_ERR_INVALID;
+  KnnLayout L;
+  int rc = knn_layout(n_search, &L, n_query);
+  if (rc) return rc;
+  if ((int64_t)L.total > workspace_bytes) return DVA_ERR_INVALID;
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  uint64_t* keys = (uint64_t*)(ws + L.keys);
+  int32_t* ids = (int32_t*)(ws + L.ids);
+  uint64_t* keys_sorted = (uint64_t*)(ws + L.keys_sorted);
+  int32_t* perm = (int32_t*)(ws + L.perm);
+  float4* pts = (float4*)(ws + L.pts);
+  uint64_t* tkeys = (uint64_t*)(ws + L.tkeys);
+  int32_t* tvals = (int32_t*)(ws + L.tvals);
+  uint64_t* qkeys = (uint64_t*)(ws + L.qkeys);
+  int32_t* qids = (int32_t*)(ws + L.qids);
+  uint64_t* qkeys_sorted = (uint64_t*)(ws + L.qkeys_sorted);
+  int32_t* qperm = (int32_t*)(ws + L.qperm);
+  float4* qpts = (float4*)(ws + L.qpts);
+  const float inv_cell = 1.f / cell;
+  // the grid of the search cloud
+  hipLaunchKernelGGL(knn_keys_kernel, dim3(grid256(n_search)), dim3(256), 0, s, search_xyz, n_search, bbox, inv_cell,
+                     keys, ids);
+  size_t tmp = L.temp_bytes;
+  if (rocprim::radix_sort_pairs(ws + L.temp, tmp, keys, keys_sorted, ids, perm, (size_t)n_search, 0, 3 * CELL_BITS,
+                                s) != hipSuccess)
+    return DVA_ERR_LAUNCH;
+  if (hipMemsetAsync(tkeys, 0xff, L.cap * 8, s) != hipSuccess) return DVA_ERR_LAUNCH;
+  hipLaunchKernelGGL(knn_cells_kernel, dim3(grid256(n_search)), dim3(256), 0, s, search_xyz, keys_sorted, perm,
+                     n_search, pts, tkeys, tvals, (uint32_t)(L.cap - 1));
+  // the queries in the cell order of the same grid, so that the lanes of a wavefront walk the same cells
+  hipLaunchKernelGGL(knn_keys_kernel, dim3(grid256(n_query)), dim3(256), 0, s, query_xyz, n_query, bbox, inv_cell,
+                     qkeys, qids);
+  tmp = L.temp_bytes;
+  if (rocprim::radix_sort_pairs(ws + L.temp, tmp, qkeys, qkeys_sorted, qids, qperm, (size_t)n_query, 0, 3 * CELL_BITS,
+                                s) != hipSuccess)
+    return DVA_ERR_LAUNCH;
+  hipLaunchKernelGGL(knn_query_points_kernel, dim3(grid256(n_query)), dim3(256), 0, s, query_xyz, qperm, n_query, qpts);
+  launch_knn_query(qpts, n_query, pts, keys_sorted, n_search, bbox, cell, tkeys, tvals, (uint32_t)(L.cap - 1), k,
+                   max_shell, done, neighbors, dist2, s);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }

@@ -3,7 +3,8 @@
 The reference finds its modules by name at the dotted paths
 ``torch_points3d.modules.multimodal.{pooling,fusion}`` (ModalityFactory.get_module,
 models/base_architectures/unet.py:69-101), ``torch_points3d.core.multimodal.visibility``
-(MapImages, core/data_transform/multimodal/image.py:214-215) and imports the data classes from
+(MapImages, core/data_transform/multimodal/image.py:214-215), finds its pre-transforms
+(PCAComputePointwise, EigenFeatures) in ``torch_points3d.core.data_transform.features`` and imports the data classes from
 ``torch_points3d.core.multimodal.{csr,image}``.  ``install()`` either patches an importable
 ``torch_points3d`` in place (attribute by attribute) or, when the package is absent, registers alias
 modules under those dotted names in ``sys.modules``.
@@ -18,6 +19,7 @@ _ALIASES = {
     "torch_points3d.modules.multimodal.dropout": "deepviewagg_amd.modules.multimodal.dropout",
     "torch_points3d.modules.multimodal.modules": "deepviewagg_amd.modules.multimodal.modules",
     "torch_points3d.core.data_transform.multimodal.image": "deepviewagg_amd.core.data_transform.multimodal.image",
+    "torch_points3d.core.data_transform.features": "deepviewagg_amd.core.data_transform.features",
     "torch_points3d.core.multimodal.csr": "deepviewagg_amd.core.multimodal.csr",
     "torch_points3d.core.multimodal.image": "deepviewagg_amd.core.multimodal.image",
     "torch_points3d.core.multimodal.visibility": "deepviewagg_amd.core.multimodal.visibility",

@@ -1602,6 +1602,21 @@ def sparse_conv(x, W, bias, nbr, nbr_t):
 # neighbourhood-based mapping features (data_transform/multimodal/image.py:431-612)
 # ---------------------------------------------------------------------------------------------
 
+def _knn_default_cell(lo, hi, ext, n, k):
+    """Grid cell of the K-NN for n search points in the box [lo, hi] of largest extent ext."""
+    # a cell that holds a few points of a surface-like cloud: mean spacing x (k/4)^(1/3)
+    dims = (hi - lo) > 1e-6 * max(ext, 1e-30)
+    nd = int(dims.sum())
+    if nd in (1, 2):
+        # a PLANAR (or collinear) cloud -- BiasuttiVisibility searches image-plane points (x, y, 0): the volume rule
+        # would give a cell far below the point spacing (z extent clamped to 1e-6) and every query would be retried
+        # on coarser grids (4 - 6 full launches, ADVICE r5): mean spacing in the occupied dimensions x (k/4)^(1/nd)
+        area = float((hi - lo)[dims].prod())
+        return (area / n) ** (1 / nd) * max(1.0, (k / 4) ** (1 / nd))
+    vol = float((hi - lo).clamp(min=1e-6).prod())
+    return (vol / n) ** (1 / 3) * max(1.0, (k / 4) ** (1 / 3))
+
+
 def knn(xyz, k, cell=None):
     """Exact k nearest neighbours of every point among all points (itself first): ``(neighbors int32 [n, k],
     dist2 fp32 [n, k])``, ascending by (squared fp32 distance, index)."""
@@ -1621,18 +1636,7 @@ def knn(xyz, k, cell=None):
     bbox = torch.cat([lo, hi]).contiguous()
     ext = float((hi - lo).max())                   # host sync: this is a preprocessing transform
     if cell is None:
-        # a cell that holds a few points of a surface-like cloud: mean spacing x (k/4)^(1/3)
-        dims = (hi - lo) > 1e-6 * max(ext, 1e-30)
-        nd = int(dims.sum())
-        if nd in (1, 2):
-            # a PLANAR (or collinear) cloud -- BiasuttiVisibility searches image-plane points (x, y, 0): the volume rule
-            # would give a cell far below the point spacing (z extent clamped to 1e-6) and every query would be retried
-            # on coarser grids (4 - 6 full launches): mean spacing in the occupied dimensions x (k/4)^(1/nd)
-            area = float((hi - lo)[dims].prod())
-            cell = (area / n) ** (1 / nd) * max(1.0, (k / 4) ** (1 / nd))
-        else:
-            vol = float((hi - lo).clamp(min=1e-6).prod())
-            cell = (vol / n) ** (1 / 3) * max(1.0, (k / 4) ** (1 / 3))
+        cell = _knn_default_cell(lo, hi, ext, n, k)
     cell = max(float(cell), ext / (1 << 19), 1e-12)
     nbytes = lib.dva_knn_workspace_bytes(n)
     if nbytes < 0:
@@ -1651,6 +1655,82 @@ def knn(xyz, k, cell=None):
                 break
             cell *= 4.0
     return nbr, d2
+
+
+def knn_query(query, search, k, cell=None):
+    """Exact k nearest neighbours in ``search`` [m, 3] of every point of ``query`` [n, 3]: ``(neighbors int32 [n, k]
+    indexing ``search``, dist2 fp32 [n, k])``, ascending by (squared fp32 distance, search index).  The reference's
+    KeOps ``argKmin`` of PCAComputePointwise (core/data_transform/features.py:423-436).  With ``query`` the same
+    cloud as ``search`` this equals ``knn``.  ``cell`` defaults to the rule of ``knn`` on the search cloud's density;
+    queries may lie outside the search cloud's box."""
+    lib = _lib.load()
+    require_device(query, search)
+    query = query.float().contiguous()
+    search = search.float().contiguous()
+    assert query.dim() == 2 and query.shape[1] == 3 and search.dim() == 2 and search.shape[1] == 3
+    n, m = query.shape[0], search.shape[0]
+    if not 0 < k <= 128:
+        raise ValueError(f"ops.knn_query: k = {k} neighbours requested, the kernel keeps at most 128 candidates per "
+                         f"query (csrc/knn.hip)")
+    if m < k:
+        raise ValueError(f"ops.knn_query: k = {k} neighbours requested from a search cloud of {m} points")
+    nbr = torch.empty((n, k), dtype=torch.int32, device=query.device)
+    d2 = torch.empty((n, k), dtype=torch.float32, device=query.device)
+    if n == 0:
+        return nbr, d2
+    s_lo, s_hi = search.min(0).values, search.max(0).values
+    lo, hi = torch.minimum(s_lo, query.min(0).values), torch.maximum(s_hi, query.max(0).values)
+    bbox = torch.cat([lo, hi]).contiguous()        # the grid's origin and extent cover both clouds
+    ext = float((hi - lo).max())                   # host sync: this is a preprocessing transform
+    if cell is None:
+        cell = _knn_default_cell(s_lo, s_hi, float((s_hi - s_lo).max()), m, k)
+    cell = max(float(cell), ext / (1 << 19), 1e-12)
+    nbytes = lib.dva_knn_query_workspace_bytes(n, m)
+    if nbytes < 0:
+        raise _lib.DvaError("dva_knn_query_workspace_bytes", int(nbytes))
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=query.device)
+    done = torch.zeros(n, dtype=torch.uint8, device=query.device)
+    # the level loop of knn: queries not provably complete within 2 shells are retried on a 4x coarser grid
+    shells = 2
+    with _timed("knn_query", n * (12 + k * 8) + m * 12):
+        while True:
+            last = cell * shells >= ext + cell
+            check(lib.dva_knn_query(ptr(query), n, ptr(search), m, ptr(bbox), float(cell), int(k),
+                                    (1 << 30) if last else shells, ptr(done), ptr(nbr), ptr(d2), ptr(ws), int(nbytes),
+                                    stream_of(query)), "dva_knn_query")
+            if last:
+                break
+            cell *= 4.0
+    return nbr, d2
+
+
+def pointwise_pca(search, neighbors):
+    """PCA of the neighbourhood of every query point (the reference's ``batch_pca`` over ``search[neighbors]``,
+    core/data_transform/features.py:307-329): ``(eigenvalues fp32 [n, 3] ascending, eigenvectors fp32 [n, 9])``, the
+    eigenvectors as rows [v0 | v1 | v2] so that ``[:, :3]`` is the normal.  ``neighbors`` int [n, k] indexes ``search``
+    [m, 3].  A neighbourhood with NaN coordinates gets eigenvalues 1 and the identity; the sign of every eigenvector
+    makes its largest-magnitude component positive (include/dva.h)."""
+    lib = _lib.load()
+    require_device(search, neighbors)
+    search = search.float().contiguous()
+    assert search.dim() == 2 and search.shape[1] == 3 and neighbors.dim() == 2
+    n, k = neighbors.shape
+    m = search.shape[0]
+    if not 0 < k <= 128:
+        raise ValueError(f"ops.pointwise_pca: neighbourhoods of k = {k} points, the kernel takes 1 <= k <= 128")
+    if m < k:
+        raise ValueError(f"ops.pointwise_pca: neighbourhoods of k = {k} points in a cloud of {m} points")
+    evals = torch.empty((n, 3), dtype=torch.float32, device=search.device)
+    evecs = torch.empty((n, 9), dtype=torch.float32, device=search.device)
+    if n == 0:
+        return evals, evecs
+    if int(neighbors.min()) < 0 or int(neighbors.max()) >= m:      # host sync: a preprocessing transform
+        raise ValueError(f"ops.pointwise_pca: neighbour indices outside [0, {m})")
+    nbr = neighbors.to(torch.int32).contiguous()
+    with _timed("pointwise_pca", n * (k * 16 + 48)):
+        check(lib.dva_pointwise_pca(ptr(search), m, ptr(nbr), n, int(k), ptr(evals), ptr(evecs), stream_of(search)),
+              "dva_pointwise_pca")
+    return evals, evecs
 
 
 def view_occlusion(csr_idx, images, neighbors, k_list, n_images):

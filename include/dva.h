@@ -913,6 +913,28 @@ int64_t dva_knn_workspace_bytes(int64_t n);
 int dva_knn(const float* xyz, int64_t n, const float* bbox, float cell, int32_t k, int32_t max_shell,
             uint8_t* done, int32_t* neighbors, float* dist2, void* workspace, int64_t workspace_bytes,
             void* stream);
+/* The same search for the n_query points of a separate query cloud in the n_search points of a search cloud
+ * (PCAComputePointwise with use_full_pos, reference core/data_transform/features.py:360-485: KeOps argKmin of the
+ * query cloud against data.full_pos).  neighbors int32 [n_query, k] (k <= 128, n_search >= k) index the search
+ * cloud, dist2 fp32 [n_query, k] (nullable): ascending by (d2, search index) with d2 = ((dx*dx + dy*dy) + dz*dz) in
+ * fp32, ties to the lower index, no self-first rule.  bbox (device fp32[6]) must cover BOTH clouds (queries may lie
+ * outside the search cloud's box); the grid is built on the search cloud.  cell, max_shell and done (uint8 [n_query])
+ * as for dva_knn; exact for any cell.  n_query < 2^31, n_search < 2^30 (DVA_ERR_UNSUPPORTED beyond). */
+int64_t dva_knn_query_workspace_bytes(int64_t n_query, int64_t n_search);
+int dva_knn_query(const float* query_xyz, int64_t n_query, const float* search_xyz, int64_t n_search,
+                  const float* bbox, float cell, int32_t k, int32_t max_shell, uint8_t* done, int32_t* neighbors,
+                  float* dist2, void* workspace, int64_t workspace_bytes, void* stream);
+/* Per-point PCA of the k-point neighbourhoods neighbors int32 [n_query, k] (indices into search_xyz fp32
+ * [n_search, 3]; 1 <= k <= 128, n_search >= k): what the reference's batch_pca (core/data_transform/features.py:307-329)
+ * computes per point.  Mean of the neighbour positions, covariance of the centred positions / k (not k - 1),
+ * eigenvalues fp32 [n_query, 3] ascending with values below 0 set to 0, eigenvectors fp32 [n_query, 9] as three unit
+ * rows [v0 | v1 | v2] (evec.transpose(2, 1).flatten(1)): the first three values are the normal.  Sign convention: the
+ * fp32 component of largest magnitude of every eigenvector is positive (the first one of equal magnitudes).  A covariance
+ * with a NaN entry (NaN / inf coordinates) or a neighbour index outside [0, n_search) gives eigenvalues (1, 1, 1)
+ * and the identity (features.py:320-323); a zero covariance (all neighbours equal) gives 0 and the identity.
+ * Covariance accumulated in fp64, eigenproblem solved by fp64 cyclic Jacobi (csrc/pca.hip). */
+int dva_pointwise_pca(const float* search_xyz, int64_t n_search, const int32_t* neighbors, int64_t n_query,
+                      int32_t k, float* eigenvalues, float* eigenvectors, void* stream);
 /* out fp32 [n_views, n_k]: (1 + #{i < k_list[c] : neighbors[p(v), i] is seen by image(v)}) / (k_list[c] + 1)
  * (k_list ascending, last <= k).  view_point int32 [n_views] (dva_csr_expand), images int64 [n_views],
  * bits = scratch uint64 [n_points * ceil(n_images / 64)]. */

@@ -14,10 +14,15 @@ N > 1 is launched by the driver with torch.distributed.run (one rank per GPU, RC
 its own scene (tile) -> weak scaling (--strong: one 2^20-point scene cut into N slabs); the collectives are the
 all-reduce of the pooling module's parameter gradients and of a stand-in 112 MB fp32 bucket (--standin-mb: the rest of
 the model's gradients), both on a side stream under the backward.  Rank 0 prints ONE compact JSON line
-(< 4 KB; the driver keeps an 8 KB tail of stdout): the contract fields + `roofline` (dominant kernel),
-`roofline_view_gather_attention` (the fused kernel the north star names), `cpu_baseline` (C + OpenMP twin of the whole
-step), one ms figure per secondary workload and the top-8 kernels.  The full record (`workloads`, every kernel,
-`mapping_build`, `gather`, per-step arrays, notes) goes to `bench_detail.json` (`compact_line` / `emit`).
+(< 4 KB, so that an 8 KB tail of stdout holds it): the contract fields + `roofline` (dominant kernel),
+`roofline_view_gather_attention` (the fused kernel the north star names) and the top-8 kernels.  The full record (every
+kernel, per-step arrays, notes) goes to `bench_detail.json` (`compact_line` / `emit`).
+
+A plain run does only what that line needs: set-up, warm-up, the timed steps, --dump-outputs, the line.  --full adds
+every other measurement after the timed steps (each still switched off by its --no-* option): the rocprofv3 PMC child
+passes behind `roofline.traffic`, the HBM copy ceiling, the materialised gather + mapping build + K-NN (`gather`,
+`mapping_build`, `neighborhood_features`), the secondary workloads (`workloads`) and `cpu_baseline` (C + OpenMP twin of
+the whole step).
 """
 import argparse
 import json
@@ -43,6 +48,10 @@ def parse():
     ap.add_argument("--views", type=int, default=32)
     ap.add_argument("--channels", type=int, default=64)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also take every measurement beyond the headline: PMC traffic passes, "
+                         "copy ceiling, gather / mapping build / K-NN, secondary workloads, CPU baselines (see the "
+                         "--no-* options)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-log2-points", type=int, default=14)
     ap.add_argument("--no-mapping-build", action="store_true")
@@ -204,8 +213,10 @@ def live_pmc_passes(timeout_s=150):
     work = tempfile.mkdtemp(prefix="dva_pmc_", dir="/tmp")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["TMPDIR"] = "/tmp"
-    child = [sys.executable, os.path.abspath(__file__), "--no-cpu-baseline", "--no-mapping-build", "--no-secondary",
-             "--no-pmc", "--steps", "1", "--warmup", "1", "--detail-file", os.path.join(work, "child_detail.json")]
+    # --full for the copy ceiling: its kernel is the calibration of summarize_pmc
+    child = [sys.executable, os.path.abspath(__file__), "--full", "--no-cpu-baseline", "--no-mapping-build",
+             "--no-secondary", "--no-pmc", "--steps", "1", "--warmup", "1",
+             "--detail-file", os.path.join(work, "child_detail.json")]
     try:
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             out = os.path.join(work, f"pmc_{counter}")
@@ -1098,8 +1109,8 @@ def _workload_ms(w):
 
 
 def compact_line(res, detail_file=DETAIL_FILE):
-    """The ONE stdout line: the contract fields, the two roofline objects, cpu_baseline and one number per secondary
-    measurement.  Everything else (`workloads`, the full per-kernel table, per-step arrays, mapping build detail, prose
+    """The ONE stdout line: the contract fields, the two roofline objects and, after --full, cpu_baseline and one number
+    per secondary measurement.  Everything else (`workloads`, the full per-kernel table, per-step arrays, mapping build detail, prose
     notes) lives in `detail_file`.  tests/test_bench_line.py holds the size cap."""
     contract = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data")
@@ -1305,7 +1316,8 @@ def main():
     # per-kernel table: PROFILE_STEPS more UNTIMED steps with HIP events around every launch.  The timed region below
     # carries events only around the kernels its roofline objects report on (the dominant kernel found here and the fused
     # view kernel): a pair of events costs the stream ~6 us of bubble per launch -- 43 pairs = 0.27 ms of an 11.2 ms step
-    # in the rocprofv3 trace (profiles/r05b_S1_last_step.txt) -- which is measurement, not the path's work
+    # in the rocprofv3 trace (profiles/r05b_S1_last_step.txt) -- which is measurement, not the path's work.  A plain run
+    # (no --full) takes these steps too: they pick the two kernels the timed region carries events around
     ops.TIMER = ops.KernelTimer()
     for _ in range(PROFILE_STEPS):
         one_step()
@@ -1393,7 +1405,9 @@ def main():
         default_workload = (args.log2_points == 20 and args.dtype == "bf16" and args.workload == "S1"
                             and args.channels == 64 and args.views == 32 and not args.materialize
                             and not args.strong and not args.interpolate and args.out_channels is None)
-        if default_workload and world == 1 and not args.no_pmc:
+        if not args.full:
+            _LIVE_PMC["why"] = "run with --full only"
+        elif default_workload and world == 1 and not args.no_pmc:
             live_pmc_passes()
         traffic, traffic_why = pmc_traffic(name, default_workload)
         chain = "chain_attn_fwd" in kern
@@ -1457,10 +1471,11 @@ def main():
             res["exposed_ms"] = max(a + b for a, b in zip(collective["standin_exposed_ms"],
                                                           collective["pooling_bucket_exposed_ms"]))
             res["collective"] = collective
-        # practical ceiling next to the nominal one: the float4 copy kernel in this process
-        res["hbm_copy_GBps"] = copy_ceiling(device)
-        res["roofline"]["copy_ceiling"] = res["hbm_copy_GBps"]
-        res["roofline"]["frac_of_copy_ceiling"] = achieved / res["hbm_copy_GBps"]
+        if args.full:
+            # practical ceiling next to the nominal one: the float4 copy kernel in this process
+            res["hbm_copy_GBps"] = copy_ceiling(device)
+            res["roofline"]["copy_ceiling"] = res["hbm_copy_GBps"]
+            res["roofline"]["frac_of_copy_ceiling"] = achieved / res["hbm_copy_GBps"]
         # the kernel the north star's >= 70 % target names: the fused view-gather + attention forward
         tname = target_name
         tk = kern_timed.get(tname) or kern.get(tname)
@@ -1471,20 +1486,23 @@ def main():
             res["roofline_view_gather_attention"] = {
                 "bound": "hbm", "kernel": tname, "achieved": t_ach, "peak": HBM_PEAK_GBS,
                 "unit": "GB/s", "frac": t_ach / HBM_PEAK_GBS, "avg_launch_ms": t_ms, "launches": tk["launches"],
-                "algorithmic_bytes_per_launch": nb, "frac_of_copy_ceiling": t_ach / res["hbm_copy_GBps"],
+                "algorithmic_bytes_per_launch": nb,
                 "traffic": pmc_traffic(tname, default_workload)[0],
                 "note": "x_map + value rows in -> pooled features out in ONE kernel (DeepSetFeat scores, softmax, row "
                         "gather, weighted sum, gate); SURVEY.md 8(d) bytes V (C s + 32 + 8) + N (C s + 8), every "
                         "gathered row counted as an HBM read although the rows of this workload come out of a 33 MB "
                         "map (cache hierarchy); the kernel also reads 128 bytes per point (set-branch row)"}
-        if world == 1 and not args.no_mapping_build:
+            if res["hbm_copy_GBps"] is not None:
+                res["roofline_view_gather_attention"]["frac_of_copy_ceiling"] = t_ach / res["hbm_copy_GBps"]
+        # everything below is --full only: measurements of their own, none of them needed by the headline
+        if args.full and world == 1 and not args.no_mapping_build:
             # M2: the materialised nearest gather at the scene's V (outside the step timer)
             g = gather_bench(scene)
             res["gather_GBps"] = g["GBps"]
             res["gather"] = g
             res["mapping_build"] = mapping_build_bench(device)
             res["neighborhood_features"] = neighborhood_bench(device)
-        if world == 1 and not args.no_secondary and default_workload:
+        if args.full and world == 1 and not args.no_secondary and default_workload:
             del scene
             torch.cuda.empty_cache()
             res["workloads"] = {
@@ -1507,7 +1525,7 @@ def main():
                 # a multi-setting batch (two map sizes) on the fused bilinear path (round 6)
                 "bilinear_two_settings": two_setting_bilinear_workload(device, args.log2_points, views),
             }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # cpu_baseline.value = the build's own C + OpenMP restatement of the WHOLE step on all host
             # cores; the PyTorch-CPU op sequence (dispatch-bound, effectively one core) and the
             # gather + attention-only twin are sub-keys

@@ -212,12 +212,18 @@ __global__ __launch_bounds__(1024) void tile_offsets_kernel(const int32_t* __res
 
 // ------------------------------------------------------------------------------------------------
 // first and second moments of the mapping features (fp64 sums): BatchNorm-1 statistics are a function of
-// them (z1 = W1 x is linear), and so is the Q term of the first layer's weight gradient
+// them (z1 = W1 x is linear), and so is the Q term of the first layer's weight gradient.
+// The per-thread and per-wavefront partial sums are fp32, so they are taken of d = x - K with K = the first view's
+// features: sum x x^T - (sum x)(sum x)^T / V then cancels in fp64 (moments_unshift_kernel) instead of in the fp32
+// partials.  Without the shift, features whose mean is large against their spread (x = 1 + 0.03 rand: |mean| / sd of
+// z1 up to 300) lost the BatchNorm-1 variance to 7e-5 relative at V = 2^25.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void moments_kernel(const float* __restrict__ x_map, int64_t V,
                                                       double* __restrict__ mom /* 8 + 36 */) {
   __shared__ float s_red[4][44];      // one slot per wavefront, summed in a fixed order (see flush_stats)
   const __amdgpu_buffer_rsrc_t X = make_rsrc(x_map, (uint64_t)V * 32);
+  const float4 ka = as_f4(ld128(X, 0u)), kb = as_f4(ld128(X, 16u));
+  const float K[8] = {ka.x, ka.y, ka.z, ka.w, kb.x, kb.y, kb.z, kb.w};
   float s1[8], s2[36];
 #pragma unroll
   for (int i = 0; i < 8; ++i) s1[i] = 0.f;
@@ -226,7 +232,8 @@ __global__ __launch_bounds__(256) void moments_kernel(const float* __restrict__ 
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < V; v += stride) {
     const float4 a = as_f4(ld128(X, (uint32_t)(v * 32))), b = as_f4(ld128(X, (uint32_t)(v * 32 + 16)));
-    const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    const float x[8] = {a.x - K[0], a.y - K[1], a.z - K[2], a.w - K[3], b.x - K[4], b.y - K[5], b.z - K[6],
+                        b.w - K[7]};
     int k = 0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -247,6 +254,26 @@ __global__ __launch_bounds__(256) void moments_kernel(const float* __restrict__ 
   if (threadIdx.x < 44)
     atomicAdd(&mom[threadIdx.x], (((double)s_red[0][threadIdx.x] + (double)s_red[1][threadIdx.x]) +
                                   (double)s_red[2][threadIdx.x]) + (double)s_red[3][threadIdx.x]);
+}
+
+// shifted moments (sum d, sum d d^T, d = x - K) -> moments of x, in fp64: one block of 64 threads, V > 0
+__global__ __launch_bounds__(64) void moments_unshift_kernel(const float* __restrict__ x_map, int64_t V,
+                                                             double* __restrict__ mom) {
+  __shared__ double s_d[8];
+  double K[8];
+  for (int i = 0; i < 8; ++i) K[i] = (double)x_map[i];
+  const int t = threadIdx.x;
+  if (t < 8) s_d[t] = mom[t];
+  __syncthreads();
+  const double n = (double)V;
+  if (t < 8) {
+    mom[t] = s_d[t] + n * K[t];
+  } else if (t < 44) {
+    int a = 0, k = t - 8;                 // row-major upper triangle: (a, b), b >= a
+    while (k >= 8 - a) { k -= 8 - a; ++a; }
+    const int b = a + k;
+    mom[t] += K[a] * s_d[b] + K[b] * s_d[a] + n * K[a] * K[b];
+  }
 }
 
 // statistics of z1 = bf16(W1) x from the moments: stats = sum z1 | sum z1^2 (the form dva_bn_finalize takes)
@@ -1147,6 +1174,8 @@ int dva_chain_moments(const float* x_map, int64_t n_views, const float* W1, int3
     const int cap = chain_grid(8);
     hipLaunchKernelGGL(moments_kernel, dim3((int)(blocks < cap ? blocks : cap)), dim3(256), 0, (hipStream_t)stream,
                        x_map, n_views, moments);
+    DVA_CHECK_LAUNCH();
+    hipLaunchKernelGGL(moments_unshift_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, x_map, n_views, moments);
     DVA_CHECK_LAUNCH();
   }
   hipLaunchKernelGGL(stats1_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, moments, W1, (int)exact_w1, stats1);

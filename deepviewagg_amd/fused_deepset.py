@@ -117,7 +117,14 @@ class _DeepSetLinear(torch.autograd.Function):
 
         # ---- elt MLP 1: x_map -> a1 -> a2
         s1 = zstats()
-        if training:
+        if training and act == torch.float32 and V * 32 < (1 << 32) - 16:
+            # z1 = Wa x is linear in x: its statistics from the fp64 moments of x_map (dva_chain_moments, shifted
+            # accumulation), as the fp32 chain does -- the fp32 per-lane sums of the pass below lose the variance when
+            # |mean| / sd of z1 is large (2.2e-4 relative at |mean| / sd = 300, V = 2^25)
+            mom = ops.zeros_small(44, torch.float64, dev)
+            with ops._timed("deepset_moments", V * 32):
+                check(lib.dva_chain_moments(ptr(x_map), V, ptr(Wa), 1, ptr(mom), ptr(s1), st), "dva_chain_moments")
+        elif training:
             with ops._timed("deepset_fwd_first_stats", V * 32):
                 check(lib.dva_deepset_fwd_first(ptr(x_map), ptr(Wa), None, None, None, ptr(s1), V, 8, 1, ALGO, AC, st),
                       "dva_deepset_fwd_first")

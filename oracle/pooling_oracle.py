@@ -28,7 +28,7 @@ import torch.nn as nn
 def dense_index(csr_idx):
     """pooling.py:779-782: group id of every element."""
     sizes = csr_idx[1:] - csr_idx[:-1]
-    return torch.arange(csr_idx.shape[0] - 1).repeat_interleave(sizes)
+    return torch.arange(csr_idx.shape[0] - 1, device=csr_idx.device).repeat_interleave(sizes)
 
 
 def segment_arg(src, csr_idx, reduce):
@@ -52,11 +52,12 @@ def segment_arg_fast(src, csr_idx, reduce):
     M = src2.shape[0]
     idx = dense_index(csr_idx).view(-1, 1).expand(M, C)
     init = float('-inf') if reduce == 'max' else float('inf')
-    ext = torch.full((n, C), init, dtype=src2.dtype).scatter_reduce(
+    ext = torch.full((n, C), init, dtype=src2.dtype, device=src2.device).scatter_reduce(
         0, idx, src2, 'amax' if reduce == 'max' else 'amin', include_self=True)
-    rows = torch.arange(M).view(-1, 1).expand(M, C)
+    rows = torch.arange(M, device=src2.device).view(-1, 1).expand(M, C)
     cand = torch.where(src2 == ext.gather(0, idx), rows, torch.full_like(rows, M))
-    arg = torch.full((n, C), M, dtype=torch.long).scatter_reduce(0, idx, cand, 'amin', include_self=True)
+    arg = torch.full((n, C), M, dtype=torch.long, device=src2.device).scatter_reduce(0, idx, cand, 'amin',
+                                                                                     include_self=True)
     arg = torch.where(arg == M, torch.full_like(arg, -1), arg)
     return arg.reshape((n,) + tuple(src.shape[1:]))
 
@@ -67,13 +68,13 @@ def segment_csr(src, csr_idx, reduce='sum'):
     sizes = csr_idx[1:] - csr_idx[:-1]
     tail = tuple(src.shape[1:])
     if reduce in ('sum', 'add', 'mean'):
-        out = torch.zeros((n,) + tail, dtype=src.dtype).index_add(0, dense_index(csr_idx), src)
+        out = torch.zeros((n,) + tail, dtype=src.dtype, device=src.device).index_add(0, dense_index(csr_idx), src)
         if reduce == 'mean':
             out = out / sizes.clamp(min=1).to(src.dtype).view((-1,) + (1,) * len(tail))
         return out
     if reduce in ('max', 'min'):
         arg = segment_arg_fast(src, csr_idx, reduce)
-        src0 = torch.cat([src, torch.zeros((1,) + tail, dtype=src.dtype)])  # row M == zeros
+        src0 = torch.cat([src, torch.zeros((1,) + tail, dtype=src.dtype, device=src.device)])  # row M == zeros
         arg0 = torch.where(arg < 0, torch.full_like(arg, src.shape[0]), arg)
         return src0.gather(0, arg0) if src.dim() > 1 else src0[arg0]
     raise ValueError(reduce)
@@ -113,7 +114,7 @@ def expand_group_feat(A, num_groups, num_channels):
     if num_groups == 1:
         return A.view(-1, 1)
     if num_groups < num_channels:
-        return A.repeat_interleave(group_sizes(num_channels, num_groups), dim=1)
+        return A.repeat_interleave(group_sizes(num_channels, num_groups).to(A.device), dim=1)
     return A
 
 

@@ -8,6 +8,7 @@ import torch
 
 from conftest import load_golden, t, state_dict_from
 from oracle import pooling_oracle as O
+import tolerances as T
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -46,28 +47,28 @@ def test_pool_modules_match_reference(name):
     x_mod, x_map = t(g["x_mod"], DEV).requires_grad_(), t(g["x_map"], DEV).requires_grad_()
     x_main = t(g["x_main"], DEV).requires_grad_() if "x_main" in g else None
     out = m(x_main, x_mod, x_map, csr)
-    close(out, g["out"])
+    close(out, g["out"], **T.FIXTURE_OUT)
     # raw compatibilities reach |C| ~ 5e2 on the QKV fixtures (sums of products through three fp32 layers whose
     # BatchNorm runs in the row kernels): 5e-4 relative
-    close(m._last_C, g["last_C"], rtol=5e-4, atol=1e-5)
-    close(m._last_A, g["last_A"])
+    close(m._last_C, g["last_C"], **T.FIXTURE_LAST_C)
+    close(m._last_A, g["last_A"], **T.FIXTURE_OUT)
     if m.G is not None:
-        close(m._last_G, g["last_G"])
+        close(m._last_G, g["last_G"], **T.FIXTURE_OUT)
     assert torch.equal(m._last_view_num.cpu(), t(g["csr"])[1:] - t(g["csr"])[:-1])
     ins = [x_mod, x_map] + ([x_main] if x_main is not None else [])
     names = [n for n, _ in m.named_parameters()]
     grads = torch.autograd.grad((out * t(g["w"], DEV)).sum(), ins + list(m.parameters()), allow_unused=True)
-    close(grads[0], g["grad_x_mod"], rtol=1e-3, atol=1e-5)
-    close(grads[1], g["grad_x_map"], rtol=1e-3, atol=1e-5)
+    close(grads[0], g["grad_x_mod"], **T.FIXTURE_GRAD_IN)
+    close(grads[1], g["grad_x_map"], **T.FIXTURE_GRAD_IN)
     if x_main is not None:
-        close(grads[2], g["grad_x_main"], rtol=1e-3, atol=1e-5)
+        close(grads[2], g["grad_x_main"], **T.FIXTURE_GRAD_IN)
     for n, gr in zip(names, grads[len(ins):]):
         ref = t(g["gp/" + n])
         gr = gr if gr is not None else torch.zeros_like(ref)
-        close(gr, ref, rtol=2e-3, atol=3e-4)
+        close(gr, ref, **T.FIXTURE_GRAD_PARAM)
     for k, v in m.state_dict().items():
         if "running" in k:
-            close(v, g["sd_after/" + k], rtol=1e-4, atol=1e-6)
+            close(v, g["sd_after/" + k], **T.FIXTURE_RUNNING)
 
 
 def test_simple_pools_and_fusion():

@@ -9,8 +9,11 @@ per tensor, the yardstick of the E_map / E_mod parameters floored by its median 
 import pytest
 import torch
 
+import rowwise as RW
 from oracle import pooling_oracle as O
+from rowwise import edges
 from test_gpu_chain import rel, ragged, ragged_long, full32
+from tolerances import Report
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -429,8 +432,11 @@ def test_anchor_scatter_workspace_chunks_and_gram_form():
     (ragged_long, 1200, 96, 256, 4, False),
     (ragged, 3000, 64, 64, 4, True),            # the register-resident widths for comparison
     (ragged_long, 1500, 128, 32, 4, True),
+    (edges, 4001, 96, 256, 4, True),            # every position class of the tile table at a wide level
 ])
 def test_fused_bilinear_matches_bf16_emulation(sizes_fn, N, C_in, C_out, G, train):
+    """Whole-tensor gates as before and -- tests/rowwise.py -- output per point, scores per point and the feature-map
+    gradient per pixel row, by stratum, against the float64 twin of the emulation (measured: profiles/rowwise_report.txt)."""
     from deepviewagg_amd import ops
     from deepviewagg_amd.modules.multimodal import pooling as P
     from oracle.chain_emulation import emulated_chain, emulated_emod
@@ -459,12 +465,13 @@ def test_fused_bilinear_matches_bf16_emulation(sizes_fn, N, C_in, C_out, G, trai
     names = ["x"] + [n for n, _ in ref.named_parameters()]
     with torch.no_grad():
         vals = emulated_emod(ref, case["x"], case["images"], case["pixels"], case["msize"])
-        out_own, sc_own = emulated_chain(ref, vals, case["x_map"], csr, dev_invstd=dev_invstd, return_scores=True)
+        out_own, sc_own = emulated_chain(ref, vals, case["x_map"], csr, dev_invstd=dev_invstd, return_scores=True,
+                                           set_split=True)
     ref.load_state_dict(sd)
     xr = case["x"].clone().requires_grad_()
     # (a backward behind an EVAL forward differentiates the evaluation from the stored bf16 z_a: stored_za=True)
     vals = emulated_emod(ref, xr, case["images"], case["pixels"], case["msize"], stored_za=True)
-    out_ref = emulated_chain(ref, vals, case["x_map"], csr, dev_invstd=dev_invstd, dev_scores=dev_scores)
+    out_ref = emulated_chain(ref, vals, case["x_map"], csr, dev_invstd=dev_invstd, dev_scores=dev_scores, set_split=True)
     g_ref = torch.autograd.grad((out_ref * w).sum(), [xr] + list(ref.parameters()), allow_unused=True)
     r_out, r_sc = rel(out, out_own), rel(dev_scores, sc_own)
     report, bad, par = [("out", round(r_out, 5)), ("scores", round(r_sc, 5))], [], []
@@ -499,6 +506,90 @@ def test_fused_bilinear_matches_bf16_emulation(sizes_fn, N, C_in, C_out, G, trai
     assert not bad, (bad, report)
     if train:
         assert sorted(par)[len(par) // 2] < EMU_TOL["param_train_median"], report
+    # ---- row-wise, against the float64 twin (same bf16 roundings, the device's dev_invstd / dev_scores) ----
+    from deepviewagg_amd import fused_chain
+    ev = {}
+    for sp, dt in ((False, torch.float32), (False, torch.float64), (True, torch.float32), (True, torch.float64)):
+        ref.load_state_dict(sd)
+        mod = ref if dt == torch.float32 else RW.double_twin(ref)
+        kw = dict(dev_invstd=dev_invstd, set_split=sp)
+        with torch.no_grad():
+            vals = emulated_emod(mod, case["x"].to(dt), case["images"], case["pixels"], case["msize"])
+            o_own, sc = emulated_chain(mod, vals, case["x_map"].to(dt), csr, return_scores=True, **kw)
+        x_dt = case["x"].to(dt).requires_grad_()
+        vals = emulated_emod(mod, x_dt, case["images"], case["pixels"], case["msize"], stored_za=True)
+        o = emulated_chain(mod, vals, case["x_map"].to(dt), csr, dev_scores=dev_scores.to(dt), **kw)
+        ev[(sp, dt)] = (o_own, sc, torch.autograd.grad((o * w.to(dt)).sum(), [x_dt])[0])
+    ref.load_state_dict(sd)
+    # output and scores: the emulation with the set-branch split of chain_set.hip (its noise is larger than the plain
+    # one: noted in the report); feature-map gradient (evaluated at the device's scores): the PLAIN yardstick
+    (out32, sc32, _), (out64, sc64, _) = ev[(True, torch.float32)], ev[(True, torch.float64)]
+    (pout32, psc32, gx32), (pout64, psc64, gx64) = ev[(False, torch.float32)], ev[(False, torch.float64)]
+    tiles, n_tiles = fused_chain.build_tiles(csr.to(DEV), V)
+    masks = RW.strata(csr, tiles[:int(n_tiles)].cpu(), fused_chain.VIEWS_PER_CHUNK)
+    seen = csr[1:] > csr[:-1]
+    if sizes_fn is edges:
+        for k, mk in masks.items():
+            assert int(mk.sum()) >= (1 if k.startswith("cloud_") else 16), (k, int(mk.sum()))
+    label = f"bilinear {sizes_fn.__name__} N={N} {C_in}->{C_out} {'train' if train else 'eval'}"
+    rep = Report("fused bilinear path against the float64 emulation, row-wise: " + label)
+    opened = ROW_OPEN.get((sizes_fn.__name__, N, C_in, C_out, train))
+    assert float(out64[~seen].abs().max() if (~seen).any() else 0.0) == 0.0
+    noise = RW.row_err(RW.as_device_rounds(out32, out), out64, seen)
+    worst = {"out": RW.gate_rows(rep, label, "out", RW.row_err(out, out64, seen), noise, masks, seen,
+                                  open_findings=opened,
+                                  plain_noise=RW.row_err(RW.as_device_rounds(pout32, out), pout64, seen))}
+    worst["scores"] = RW.gate_rows(rep, label, "scores", RW.score_err(dev_scores, sc64, csr),
+                                   RW.score_err(sc32, sc64, csr), masks, seen,
+                                   plain_noise=RW.score_err(psc32, psc64, csr))
+
+    def pixel_rows(t):      # [B, C, H, W] -> one row per pixel
+        return t.detach().permute(0, 2, 3, 1).reshape(-1, t.shape[1])
+    read, read_live = RW.read_strata(bilinear_taps(case), pixel_rows(gx64).shape[0])
+    assert float(pixel_rows(g[0]).float().cpu()[~read_live].abs().max() if (~read_live).any() else 0.0) == 0.0
+    noise = RW.row_err(RW.as_device_rounds(pixel_rows(gx32), g[0]), pixel_rows(gx64), read_live)
+    worst["x_grad"] = RW.gate_rows(rep, label, "x_grad", RW.row_err(pixel_rows(g[0]), pixel_rows(gx64), read_live), noise,
+                                   read, read_live, open_findings=opened)
+    print("worst ratio to the float32 emulation's own noise:", {k: round(v, 2) for k, v in worst.items()})
+    RW.write_report(rep)
+    rep.check()
+
+
+# Open row-wise findings (Report.add_open: the row must still miss its gate and must not grow past 1.5 x the value recorded
+# here).  Both are single rows behind a DISCRETE decision that one bf16 rounding-boundary flip upstream moves, of the kind
+# the whole-tensor comparison already shares with the device where it can (dev_invstd, dev_scores); the float32 and float64
+# emulations happen to agree on it in these cases, so the noise yardstick does not contain the event.
+_KINK_B = ("one view (1589) of 3600: BatchNorm_b(z_b) of E_mod channel 184 is -2.5e-3 (z_b: 2.4e-3 of a sum of scale 5), the device's "
+           "z_b lies on the other side, LeakyReLU_b' is 1 instead of 0.2 there; the difference of pixel rows (0,5,0) and (0,6,0) is "
+           "that channel's back-projection (cosine 0.99) in the ratio of the view's two tap weights")
+_GATE_1 = ("point 1130 has ONE view: out = value row x tanh(relu(w score + b)) with gate arguments 0.68 / 0.22; the device's score "
+           "there differs by 1.16e-3 max|score| (one flipped bf16 activation, inside the score gate) and the float64 emulation "
+           "moved by exactly that reproduces the row error (1.41e-2)")
+ROW_OPEN = {
+    ("ragged_long", 1200, 96, 256, False): {("x_grad", "all", "max"): (2.49e-2, _KINK_B),
+                                            ("x_grad", "read_32_511", "max"): (2.49e-2, _KINK_B)},
+    # (recorded at 1.08 x its gate, and the gate is a measured noise statistic: a run that moves either a little turns the
+    #  entry "resolved" -- Report.check says so -- and the entry then goes)
+    ("ragged_long", 1500, 128, 32, True): {("out", "all", "max"): (1.41e-2, _GATE_1), ("out", "views_1", "max"): (1.41e-2, _GATE_1),
+                                           ("out", "tile_interior", "max"): (1.41e-2, _GATE_1)},
+}
+
+
+def bilinear_taps(case):
+    """Pixel-row index (b, h, w) -> b H W + h W + w of every tap with a non-zero weight of every view: the index
+    arithmetic of O.sparse_interpolation (replicated border: padded index r reads pixel clamp(r - 1))."""
+    B, _, H, W = case["x"].shape
+    coords = (case["pixels"] / (torch.Tensor([case["msize"]]) - 1))[:, [1, 0]]
+    p = coords * torch.Tensor([[H, W]]) + 0.5
+    rows, cols = (torch.floor(p[:, 0]), torch.floor(p[:, 0] + 1)), (torch.floor(p[:, 1]), torch.floor(p[:, 1] + 1))
+    taps = []
+    for i in (0, 1):
+        for j in (0, 1):
+            wgt = ((p[:, 0] - rows[1 - i]) * (p[:, 1] - cols[1 - j])).abs()     # weight of a corner: area to the opposite one
+            r = (rows[i].long() - 1).clamp(0, H - 1)
+            c = (cols[j].long() - 1).clamp(0, W - 1)
+            taps.append((case["images"].long() * H * W + r * W + c)[wgt > 0])
+    return torch.cat(taps)
 
 
 def test_interpolated_features_cat_equals_torch_composition():

@@ -8,7 +8,10 @@ import numpy as np
 import pytest
 import torch
 
+import rowwise as RW
 from oracle import pooling_oracle as O
+from rowwise import edges
+from tolerances import AUTOCAST_ROW_HEADROOM, Report
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -17,6 +20,24 @@ DEV = "cuda:0"
 def rel(a, b):
     a, b = a.detach().float().cpu(), b.detach().float().cpu()
     return float((a - b).norm() / (b.norm() + 1e-12))
+
+
+def check_rows_against_autocast(label, out, out_amp, out_ref, csr):
+    """The tests whose yardstick is the oracle under CPU autocast (whole-tensor: rel L2 <= 1.5 x the autocast oracle's)
+    hold it per row as well (tests/rowwise.py): the max -- and the p99 of strata of >= 200 points -- of the device's row
+    error against the fp32 oracle, per stratum of points, <= AUTOCAST_ROW_HEADROOM = 1.5 x the same statistic of the
+    autocast oracle over all seen points.  Strata from the device's tile table of ``csr``."""
+    from deepviewagg_amd import fused_chain
+    csr = csr.cpu()
+    seen = csr[1:] > csr[:-1]
+    tiles, n_tiles = fused_chain.build_tiles(csr.to(DEV), int(csr[-1]))
+    masks = RW.strata(csr, tiles[:int(n_tiles)].cpu(), fused_chain.VIEWS_PER_CHUNK)
+    rep = Report("row-wise against the fp32 oracle, yardstick = the oracle under autocast: " + label)
+    worst = RW.gate_rows(rep, label, "out", RW.row_err(out, out_ref, seen), RW.row_err(out_amp, out_ref, seen), masks, seen,
+                         headroom=AUTOCAST_ROW_HEADROOM)
+    print(f"{label}: worst row-wise ratio to the autocast oracle {worst:.2f} (gate {AUTOCAST_ROW_HEADROOM})")
+    RW.write_report(rep)
+    rep.check()
 
 
 @pytest.fixture(params=["permutation_plan", "split_plan"])
@@ -157,6 +178,8 @@ def test_chain_forward_matches_oracle(sizes_fn, N, C, G, train):
         for (k, a), b in zip(m.state_dict().items(), ref.state_dict().values()):
             if "running" in k:
                 torch.testing.assert_close(a.cpu(), b, rtol=2e-2, atol=2e-3)
+    check_rows_against_autocast(f"chain fwd {sizes_fn.__name__} N={N} C={C} G={G} {'train' if train else 'eval'}",
+                                out, out_amp, out_ref, case["csr"])
 
 
 def test_tile_table_properties():
@@ -363,8 +386,12 @@ from oracle.chain_emulation import emulated_chain, _bf      # noqa: E402  (the b
     (ragged, 1500, 128, 1, True, False, True),
     (ragged_long, 700, 512, 4, True, True, True),
     (ragged_long, 900, 256, 2, False, True, True),
+    (edges, 4001, 64, 4, True, True, True),        # every position class of the tile table, hot and cold map rows
 ])
 def test_chain_matches_bf16_emulation(sizes_fn, N, C, G, train, gating, scaling, plan_kind):
+    """Whole-tensor gates (EMU_TOL, below) and -- tests/rowwise.py -- the same comparison per point and per map row,
+    by stratum, against the float64 twin of the emulation; the row gates are FP32_HEADROOM x the noise of
+    bf16(float32 emulation) against that twin, computed here.  Measured: profiles/rowwise_report.txt."""
     from deepviewagg_amd import ops, fused_chain
     case = make_case(13, N, C, sizes_fn)
     gen = case["gen"]
@@ -372,6 +399,14 @@ def test_chain_matches_bf16_emulation(sizes_fn, N, C, G, train, gating, scaling,
     R = 777
     rows = (torch.randn(R, C, generator=gen)).bfloat16()
     row_idx = torch.randint(0, R, (V,), generator=gen, dtype=torch.int32)
+    if sizes_fn is edges:
+        # map rows read by >= 512 views (16 hot rows take 40 % of the views), by 32 .. 511, by a few, by one, by none
+        R = 20000
+        rows = (torch.randn(R, C, generator=gen)).bfloat16()
+        u = torch.rand(V, generator=gen)
+        row_idx = torch.where(u < 0.4, torch.randint(0, 16, (V,), generator=gen),
+                              torch.where(u < 0.7, torch.randint(16, 1000, (V,), generator=gen),
+                                          torch.randint(1000, R, (V,), generator=gen))).int()
     ref, m = build(case, G, train, gating=gating, scaling=scaling)
     sd = {k: v.clone() for k, v in ref.state_dict().items()}
     chain_params = [p for n, p in ref.named_parameters() if not n.startswith("E_mod")]
@@ -401,11 +436,11 @@ def test_chain_matches_bf16_emulation(sizes_fn, N, C, G, train, gating, scaling,
     rows_ref = rows.float().requires_grad_()
     with torch.no_grad():      # forward parity: the emulation's own output and scores
         out_plain, sc_own = emulated_chain(ref, rows_ref[row_idx.long()], case["x_map"], csr, dev_invstd=dev_invstd,
-                                           return_scores=True)
+                                           return_scores=True, set_split=True)
     ref.load_state_dict(sd)
     # gradient parity: the attention tail evaluated at the device's scores (same arg-max views, same gate branches)
     out_ref = emulated_chain(ref, rows_ref[row_idx.long()], case["x_map"], csr, dev_invstd=dev_invstd,
-                             dev_scores=dev_scores)
+                             dev_scores=dev_scores, set_split=True)
     g_ref = torch.autograd.grad((out_ref * case["w"]).sum(), [rows_ref] + chain_params, allow_unused=True)
     sens_out = rel(out_ref, out_fp.detach())
     dev_params = [p for n, p in m.named_parameters() if not n.startswith("E_mod")]
@@ -473,6 +508,22 @@ def test_chain_matches_bf16_emulation(sizes_fn, N, C, G, train, gating, scaling,
         for (k, a), b in zip(m.state_dict().items(), ref.state_dict().values()):
             if "running" in k and not k.startswith("E_mod"):
                 torch.testing.assert_close(a.cpu(), b, rtol=1e-3, atol=1e-4)
+    # ---- row-wise: per point / per map row, by stratum, against the float64 twin of the emulation (tests/rowwise.py) ----
+    assert RW.VIEWS_PER_CHUNK == fused_chain.VIEWS_PER_CHUNK
+    tiles, n_tiles = fused_chain.build_tiles(csr.to(DEV), V)
+    masks = RW.strata(csr, tiles[:int(n_tiles)].cpu(), fused_chain.VIEWS_PER_CHUNK)
+    read, read_live = RW.read_strata(row_idx, R)
+    if sizes_fn is edges:
+        for k, mk in list(masks.items()) + list(read.items()):
+            assert int(mk.sum()) >= (1 if k.startswith("cloud_") else 16), (k, int(mk.sum()))
+        assert int((~read_live).sum()) >= 16
+    ev = RW.emulate_all(ref, sd, rows, row_idx, case["x_map"], csr, case["w"], dev_invstd, dev_scores)
+    label = f"{sizes_fn.__name__} N={N} C={C} {'train' if train else 'eval'} {plan_kind['kind'][:5]}"
+    rep = Report("bf16 chain against the float64 emulation, row-wise: " + label)
+    worst = RW.gate_chain(rep, label, ev, csr, masks, out, dev_scores, g[0], read, read_live)
+    print("worst ratio to the float32 emulation's own noise:", {k: round(v, 2) for k, v in worst.items()})
+    RW.write_report(rep)
+    rep.check()
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -516,6 +567,7 @@ def test_chain_against_reference_fixture(name, plan_kind):
     assert r < max(2e-2, 1.5 * r_amp), (r, r_amp)
     unseen = csr[1:] == csr[:-1]
     assert float(out.detach().float().cpu()[unseen].abs().max()) == 0.0
+    check_rows_against_autocast(f"fixture {name} {plan_kind['kind'][:5]}", out, out_amp, t(g["out"]), csr)
     names = ["x_mod"] + [n for n, _ in m.named_parameters()]
     refs = [t(g["grad_x_mod"])] + [t(g["gp/" + n]) for n in names[1:]]
     amps = sorted(rel(c, b) for n, b, c in zip(names, refs, g_amp) if c is not None and n.startswith("E_map"))

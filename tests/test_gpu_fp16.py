@@ -10,8 +10,8 @@ import pytest
 import torch
 
 from oracle import pooling_oracle as O
-from test_gpu_chain import (DEV, _oracle_grads, build, check_plan_kind, full32, make_case, plan_kind, ragged,  # noqa: F401
-                            ragged_long, rel)
+from test_gpu_chain import (DEV, _oracle_grads, build, check_plan_kind, check_rows_against_autocast, full32,  # noqa: F401
+                            make_case, plan_kind, ragged, ragged_long, rel)
 
 pytestmark = pytest.mark.gpu
 
@@ -426,6 +426,8 @@ def test_chain_forward_fp16_matches_oracle(sizes_fn, N, C, G, train, chain_calls
     r, r_bf, r_amp = rel(out, out_ref), rel(out_bf, out_ref), rel(out_amp, out_ref)
     print(f"fp16 chain fwd rel err {r:.4f} (bf16 chain {r_bf:.4f}, reference under autocast {r_amp:.4f})")
     assert r < max(2e-2, 1.5 * r_amp), (r, r_amp)
+    check_rows_against_autocast(f"fp16 fwd {sizes_fn.__name__} N={N} C={C} G={G} {'train' if train else 'eval'}",
+                                out, out_amp, out_ref, case["csr"])
     assert r <= 1.1 * r_bf + 1e-6, (r, r_bf)
 
 

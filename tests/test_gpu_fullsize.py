@@ -163,15 +163,19 @@ def chain_scene():
     return dict(csr=csr, row_idx=row_idx, rows=rows, x_map=x_map, w=w, m=m, V=V, R=R, unread=unread)
 
 
-def _chain_step(s, sl=None, chain=True):
-    """forward + backward of GroupBimodalCSRPool's attention part on value rows that are already E_mod(rows)."""
+def _chain_step(s, sl=None, chain=True, saved=None):
+    """forward + backward of GroupBimodalCSRPool's attention part on value rows that are already E_mod(rows).
+    ``sl``: the first ``sl`` points of the scene, or (first point, number of points).  ``saved``: a dict that receives
+    the BatchNorm invstd of the folded layers and the scores the forward kernel left for the backward."""
     from deepviewagg_amd import ops, fused_chain, fused_deepset
     rows = s["rows"].clone().requires_grad_()
     if sl is None:
         csr, row_idx, x_map, w = s["csr"], s["row_idx"], s["x_map"], s["w"]
-    else:                                      # the first `sl` points of the same scene
-        csr, row_idx = s["csr"][:sl + 1].contiguous(), s["row_idx"][:sl * VIEWS].contiguous()
-        x_map, w = s["x_map"][:sl * VIEWS].contiguous(), s["w"][:sl].contiguous()
+    else:                                      # a run of points of the same scene
+        p0, n = (0, sl) if isinstance(sl, int) else sl
+        csr = (s["csr"][p0:p0 + n + 1] - s["csr"][p0]).contiguous()
+        row_idx = s["row_idx"][p0 * VIEWS:(p0 + n) * VIEWS].contiguous()
+        x_map, w = s["x_map"][p0 * VIEWS:(p0 + n) * VIEWS].contiguous(), s["w"][p0:p0 + n].contiguous()
     gf = ops.GatheredFeatures(rows, row_idx, None, True, None)
     m = s["m"]
     params = [p for n_, p in m.named_parameters() if not n_.startswith("E_mod")]
@@ -181,6 +185,10 @@ def _chain_step(s, sl=None, chain=True):
             out = fused_chain.chain_pool(m, gf, x_map, csr)
         finally:
             fused_chain.FORCE = None
+        if saved is not None:       # as tests/test_gpu_chain.py::test_chain_matches_bf16_emulation reads them
+            sv = out.grad_fn.saved_tensors
+            saved["invstd"] = {1: sv[12][1].cpu(), 2: sv[13][1].cpu(), 6: sv[15][1].cpu()}
+            saved["scores"] = sv[17].cpu()[:, :G].clone()
     else:
         # the first-generation path: stored-activation DeepSet kernels + the team attention kernels
         compat = fused_deepset.deepset_linear(m.E_map, m.E_score, x_map, csr)
@@ -245,8 +253,50 @@ def test_chain_full_size_agrees_with_stored_activation_path_on_a_slice(chain_sce
         rel = lambda a, b: float((a.float() - b.float()).norm() / (b.float().norm() + 1e-30))
         assert rel(out_sl, out_b) < 2e-2, rel(out_sl, out_b)
         assert rel(g_sl[0], g_b[0]) < 5e-2, rel(g_sl[0], g_b[0])
+        _far_slices_row_wise(s, out_full)
     finally:
         m.train()
+
+
+def _far_slices_row_wise(s, out_full):
+    """Eval mode (the caller set it): 2^12 points at the END of the cloud and 2^12 in the middle that start inside a
+    512-view construction chunk, behind view 2^24.  The full-size rows of the slice against (a) a run on the slice alone
+    and (b) the float64 emulation of those points on the CPU (131 k views), both row-wise with the gate of
+    tests/rowwise.py: FP32_HEADROOM x the float32 emulation's own error against the float64 one on the slice."""
+    import rowwise as RW
+    from deepviewagg_amd import fused_chain
+    from oracle import pooling_oracle as O
+    from tolerances import Report
+    n = 1 << 12
+    ref = O.GroupBimodalCSRPool(in_map=8, in_mod=C, num_groups=G, use_num=True)
+    ref.load_state_dict({k: v.cpu() for k, v in s["m"].state_dict().items()})
+    ref.eval()
+    sd = {k: v.clone() for k, v in ref.state_dict().items()}
+    rows = s["rows"].cpu()
+    for name, p0 in (("end", N - n), ("middle", N // 2 + 5)):
+        assert (p0 * VIEWS) % fused_chain.VIEWS_PER_CHUNK != 0 or name == "end"
+        saved = {}
+        out_sl, _ = _chain_step(s, sl=(p0, n), saved=saved)
+        csr = torch.arange(0, n * VIEWS + 1, VIEWS)
+        row_idx = s["row_idx"][p0 * VIEWS:(p0 + n) * VIEWS].cpu()
+        x_map, w = s["x_map"][p0 * VIEWS:(p0 + n) * VIEWS].cpu(), s["w"][p0:p0 + n].float().cpu()
+        ev = RW.emulate_all(ref, sd, rows, row_idx, x_map, csr, w, saved["invstd"], saved["scores"])
+        tiles, n_tiles = fused_chain.build_tiles(csr.to(DEV), n * VIEWS)
+        masks = RW.strata(csr, tiles[:int(n_tiles)].cpu(), fused_chain.VIEWS_PER_CHUNK)
+        live = torch.ones(n, dtype=torch.bool)
+        got = out_full[p0:p0 + n]
+        label = f"full size, {name} slice [{p0}, {p0 + n})"
+        rep = Report("headline scene against the float64 emulation, row-wise: " + label)
+        # (a) the slice run: the plain yardstick (both are the device; the slice is tiled on its own)
+        p32, p64 = ev[(False, torch.float32)], ev[(False, torch.float64)]
+        noise = RW.row_err(RW.as_device_rounds(p32["out"], got), p64["out"], live)
+        worst = {"full vs slice": RW.gate_rows(rep, label, "out: full vs slice run", RW.row_err(got, out_sl, live), noise,
+                                               masks, live)}
+        # (b) the float64 emulation of the slice
+        worst.update(RW.gate_chain(rep, label, ev, csr, masks, got, saved["scores"]))
+        print(label, "worst ratio to the float32 emulation's own noise:", {k: round(v, 2) for k, v in worst.items()})
+        RW.write_report(rep)
+        rep.check()
 
 
 # ---------------------------------------------------------------------------------------------------------------

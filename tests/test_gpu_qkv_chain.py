@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from oracle import pooling_oracle as O
-from test_gpu_chain import rel, make_case, ragged, ragged_long, full32
+from test_gpu_chain import rel, make_case, ragged, ragged_long, full32, check_rows_against_autocast
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -107,6 +107,8 @@ def test_qkv_pool_on_the_chain_matches_oracle(sizes_fn, N, C, G, nc_qk, train):
     r, r_amp = rel(out, out_ref), rel(out_amp, out_ref)
     print(f"qkv chain fwd rel err {r:.4f} (oracle under autocast {r_amp:.4f})")
     assert r < max(2e-2, 1.5 * r_amp), (r, r_amp)
+    check_rows_against_autocast(f"qkv {sizes_fn.__name__} N={N} C={C} G={G} qk={nc_qk} {'train' if train else 'eval'}",
+                                out, out_amp, out_ref, case["csr"])
     unseen = case["csr"][1:] == case["csr"][:-1]
     assert float(out.detach().float().cpu()[unseen].abs().max() if unseen.any() else 0.0) == 0.0
     if train:

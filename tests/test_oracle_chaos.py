@@ -74,3 +74,23 @@ def test_eval_mode_parameter_gradients_are_well_conditioned():
     out, rows, med, worst = _self_deviation(train=False, eps=1e-6)
     print(f"eval, 1e-6: out {out:.2e} rows {rows:.2e} parameters median {med:.2e} max {worst:.2e}")
     assert out < 5e-3 and rows < 5e-3 and worst < 3e-2
+
+
+def test_float32_emulation_is_unchanged_by_the_dtype_preserving_form(monkeypatch):
+    """oracle/chain_emulation.py keeps the dtype of its input (``.to(t.dtype)`` where it said ``.float()``) so that a
+    float64 twin can be evaluated (tests/rowwise.py).  What is checked here: with the rounding helper ``_bf`` -- the edit
+    that every layer passes -- put back to its ``.float()`` form the float32 output is bit-equal and float32 throughout.
+    (The x16 lines, set_num and the dev_invstd branch are identities on float32 by reading; they are not put back here.)
+    Bit-equal output (the gradients are compared
+    to 1e-5: the CPU's index_add of the backward is not run-to-run deterministic, ~5e-7 of the same code twice)."""
+    import oracle.chain_emulation as CE
+    ref, csr, x_map, w, rows, row_idx = _case(13, 1500, 64, 4, True)
+    sd = {k: v.clone() for k, v in ref.state_dict().items()}
+    o_new, g_new = _grads(ref, sd, csr, x_map, w, rows, row_idx)
+    monkeypatch.setattr(CE, "_bf", lambda t: t + (t.bfloat16().float() - t).detach())
+    o_old, g_old = _grads(ref, sd, csr, x_map, w, rows, row_idx)
+    assert o_new.dtype == torch.float32 and torch.equal(o_new, o_old)
+    for a, b in zip(g_new, g_old):
+        assert (a is None) == (b is None)
+        if a is not None:
+            assert a.dtype == torch.float32 and _rel(a, b) < 1e-5

@@ -21,6 +21,16 @@ CLASS_GATES = {
 }
 FP32_HEADROOM = 4.0         # how far above a plain fp32 evaluation's own error a gate may be raised
 
+# Row-wise gates of the bf16 pooling path (tests/rowwise.py): per stratum of rows, the max and -- for strata of at least
+# P99_MIN_ROWS rows -- the 99th percentile of the per-row error against the float64 emulation.  These classes have NO
+# typed-in gate: the gate is FP32_HEADROOM x the same statistic of bf16(float32 emulation) against the float64
+# emulation over all live rows of the case, computed at test time (AUTOCAST_ROW_HEADROOM x the statistic of the oracle
+# under CPU autocast in the tests whose yardstick is that oracle: the factor they already use for whole outputs).
+ROW_MAX, ROW_P99 = "row_max", "row_p99"
+CLASS_GATES[ROW_MAX] = CLASS_GATES[ROW_P99] = 0.0
+P99_MIN_ROWS = 200
+AUTOCAST_ROW_HEADROOM = 1.5
+
 # parameter gradients that are zero in exact arithmetic when the module has no gate (a bias common to all views of a
 # point) -> the sibling whose max-abs is the scale.  Used when the float64 tensor is below 1e-9 of that sibling.
 STRUCTURAL_ZERO_SIBLING = {
@@ -57,12 +67,13 @@ def rel_err(got, ref, scale=None):
     return num / den
 
 
-def gate(cls, fp32_err=None):
-    """The enforced gate of a tensor of class ``cls``: the class gate, raised to at most FP32_HEADROOM x the error of a
-    plain fp32 evaluation of the same case when that error is known."""
+def gate(cls, fp32_err=None, headroom=FP32_HEADROOM):
+    """The enforced gate of a tensor of class ``cls``: the class gate, raised to at most ``headroom`` (FP32_HEADROOM
+    unless the test's yardstick states its own factor) x the error of a plain evaluation of the same case when that
+    error is known."""
     g = CLASS_GATES[cls]
     if fp32_err is not None:
-        g = max(g, FP32_HEADROOM * float(fp32_err))
+        g = max(g, headroom * float(fp32_err))
     return g
 
 
@@ -79,10 +90,10 @@ class Report:
     """Collects (case, tensor, class, err, gate) rows; ``check()`` prints the table (-s) and asserts every row."""
 
     def __init__(self, title):
-        self.title, self.rows, self.open = title, [], []
+        self.title, self.rows, self.open, self.notes = title, [], [], []
 
-    def add(self, case, name, cls, err, fp32_err=None):
-        g = gate(cls, fp32_err)
+    def add(self, case, name, cls, err, fp32_err=None, headroom=FP32_HEADROOM):
+        g = gate(cls, fp32_err, headroom)
         self.rows.append((case, name, cls, float(err), g, fp32_err))
         return err
 
@@ -99,6 +110,7 @@ class Report:
             flag = "" if err <= g else ("  OPEN" if (case, name) in opened else "  FAIL")
             e32s = f"{e32:9.2e}" if e32 is not None else f"{'-':>9s}"
             lines.append(f"{case:34s} {name:46s} {cls:10s} {err:9.2e} {g:9.2e} {e32s}{flag}")
+        lines += ["   note: " + n for n in self.notes]
         return "\n".join(lines)
 
     def check(self):
@@ -107,6 +119,8 @@ class Report:
         bad = [(c, n, e, g) for c, n, _, e, g, _ in self.rows if not e <= g and (c, n) not in opened]
         assert not bad, bad
         for c, n, e, g, measured, why in self.open:
+            # (an entry recorded close to its gate can flip to "resolved" when the gate, itself a measured noise
+            #  statistic, moves a little: the entry says so and is then taken out)
             assert e > g, f"{c} {n}: {e:.2e} now meets its gate {g:.2e} -- the open finding is resolved ({why})"
             assert e <= 1.5 * measured, f"{c} {n}: {e:.2e} grew past the recorded {measured:.2e} ({why})"
 

@@ -218,6 +218,9 @@ SIGNATURES = {
     "dva_grid_cluster": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "dva_grid_mean": (ctypes.c_int, [_vp, _i32, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
     "dva_grid_majority": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _vp]),
+    "dva_radius_query_workspace_bytes": (ctypes.c_int64, [_i64, _i64]),
+    "dva_radius_count": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i32, _f64, _vp, _vp, _vp, _i64, _vp]),
+    "dva_radius_fill": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i32, _f64, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
     "dva_lex_workspace_bytes": (ctypes.c_int64, [_i64]),
     "dva_argsort_i64": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "dva_argunique_i64": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp]),

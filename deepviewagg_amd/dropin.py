@@ -5,7 +5,9 @@ The reference finds its modules by name at the dotted paths
 models/base_architectures/unet.py:69-101), ``torch_points3d.core.multimodal.visibility``
 (MapImages, core/data_transform/multimodal/image.py:214-215), finds its pre-transforms
 (PCAComputePointwise, EigenFeatures) in ``torch_points3d.core.data_transform.features``, GridSampling3D and
-SaveOriginalPosId in ``torch_points3d.core.data_transform.grid_transform`` and on the package
+SaveOriginalPosId in ``torch_points3d.core.data_transform.grid_transform``, the sphere and cylinder samplers
+(SphereSampling, CylinderSampling, GridSphereSampling, GridCylinderSampling, Select) in
+``torch_points3d.core.data_transform.transforms``, and both groups on the package
 ``torch_points3d.core.data_transform`` itself (``instantiate_transform`` and ``cT.GridSampling3D`` look them up there),
 and imports the data classes from
 ``torch_points3d.core.multimodal.{csr,image}``.  ``install()`` either patches an importable
@@ -24,6 +26,7 @@ _ALIASES = {
     "torch_points3d.core.data_transform.multimodal.image": "deepviewagg_amd.core.data_transform.multimodal.image",
     "torch_points3d.core.data_transform.features": "deepviewagg_amd.core.data_transform.features",
     "torch_points3d.core.data_transform.grid_transform": "deepviewagg_amd.core.data_transform.grid_transform",
+    "torch_points3d.core.data_transform.transforms": "deepviewagg_amd.core.data_transform.transforms",
     "torch_points3d.core.multimodal.csr": "deepviewagg_amd.core.multimodal.csr",
     "torch_points3d.core.multimodal.image": "deepviewagg_amd.core.multimodal.image",
     "torch_points3d.core.multimodal.visibility": "deepviewagg_amd.core.multimodal.visibility",
@@ -36,6 +39,8 @@ _ALIASES = {
 _PACKAGE_NAMES = [
     ("torch_points3d.core.data_transform", "deepviewagg_amd.core.data_transform.grid_transform",
      ("GridSampling3D", "SaveOriginalPosId")),
+    ("torch_points3d.core.data_transform", "deepviewagg_amd.core.data_transform.transforms",
+     ("SphereSampling", "CylinderSampling", "GridSphereSampling", "GridCylinderSampling", "Select")),
 ]
 
 

@@ -14,6 +14,7 @@ ops; names and argument meaning follow the reference call site
 ``grid_cluster``           core/data_transform/grid_transform.py:143-148 (grid_cluster / voxel_grid)
 ``grid_mean``              grid_transform.py:81 (``scatter_mean``)
 ``grid_majority``          grid_transform.py:76-79 (one_hot + ``scatter_add`` + argmax)
+``radius_query``           core/data_transform/transforms.py:147,215,332,386 (KDTree.query_radius)
 =========================  ==========================================================
 
 All ops require tensors on a HIP device and raise otherwise (no CPU fallback).
@@ -22,6 +23,7 @@ import os
 
 import threading
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1919,3 +1921,101 @@ def view_occlusion(csr_idx, images, neighbors, k_list, n_images):
                                  k, ptr(kl), kl.shape[0], ptr(bits), ptr(out), stream_of(images)),
           "dva_view_occlusion")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# exact radius query (core/data_transform/transforms.py:99-232, :301-405: KDTree.query_radius)
+# ---------------------------------------------------------------------------------------------
+
+_RADIUS_TABLE_BYTES = 256 << 20      # budget of the per-(tile, centre) count table of one launch
+
+
+def _radius_centres(centres, dims):
+    """Centres as a float64 CPU tensor [B, dims]: a numpy array or a tensor of any float dtype, [dims] or [B, dims]."""
+    c = centres if torch.is_tensor(centres) else torch.as_tensor(np.asarray(centres))
+    if c.is_complex() or c.dtype == torch.bool:
+        raise TypeError(f"ops.radius_query: centres must be real numbers, got {c.dtype}")
+    c = c.detach().to(torch.float64)
+    if c.dim() == 1:
+        c = c.unsqueeze(0) if c.shape[0] else c.reshape(0, dims)
+    if c.dim() != 2 or c.shape[1] != dims:
+        raise ValueError(f"ops.radius_query: centres must be [B, {dims}] for dims = {dims}, got {tuple(c.shape)}")
+    return c.contiguous()
+
+
+def radius_query(pos, centres, radius, dims=3):
+    """All points of ``pos`` fp32 [n, 3] within ``radius`` of every centre: ``(ptr int64 [B + 1], idx int64
+    [ptr[B]])`` on the current HIP device (``pos`` is moved there when it lives elsewhere); the members of centre b are
+    ``idx[ptr[b]:ptr[b + 1]]`` in ascending point index.  ``dims = 3`` is the sphere, ``dims = 2`` the cylinder along z (centres [B, 2]).  ``centres`` is a numpy
+    array or a tensor of any float dtype and is converted to float64, as scikit-learn's tree does; ``radius`` is one
+    number or one per centre.  The membership test is scikit-learn's leaf test, exactly: ``d <= r * r`` with
+    ``d = ((dx dx) + dy dy) + dz dz`` in float64, ``dx = float64(p.x) - c.x``, each operation rounded on its own, the
+    boundary included; a point with a non-finite coordinate is never a member.  Brute force over all pairs
+    (csrc/ball.hip), no atomics: the same call gives the same bytes.  The centres are split so that the count table
+    of one launch stays within ``_RADIUS_TABLE_BYTES``; one host read per split (the size of ``idx``)."""
+    lib = _lib.load()
+    if dims not in (2, 3):
+        raise ValueError(f"ops.radius_query: dims must be 2 (cylinder) or 3 (sphere), got {dims}")
+    if not torch.is_tensor(pos):
+        raise TypeError("ops.radius_query: pos must be a tensor")
+    if pos.dtype == torch.float64:
+        raise TypeError("ops.radius_query: pos is float64; the reference's clouds are float32 and the membership "
+                        "test is defined on float32 coordinates widened to float64: cast pos to float32")
+    if pos.dtype != torch.float32:
+        raise TypeError(f"ops.radius_query: pos must be float32, got {pos.dtype}")
+    if pos.dim() != 2 or pos.shape[1] != 3:
+        raise ValueError(f"ops.radius_query: pos must be [N, 3], got {tuple(pos.shape)}")
+    n = pos.shape[0]
+    if n >= 1 << 31:
+        raise ValueError(f"ops.radius_query: N = {n} points, the kernels take N < 2^31")
+    cen = _radius_centres(centres, dims)
+    B = cen.shape[0]
+    radii = None
+    if torch.is_tensor(radius) or isinstance(radius, np.ndarray):
+        r = torch.as_tensor(radius).detach().to(torch.float64).cpu().reshape(-1)
+        if r.numel() == 1:
+            radius = float(r)
+        elif r.numel() != B:
+            raise ValueError(f"ops.radius_query: {r.numel()} radii for {B} centres")
+        else:
+            radii = r
+    if radii is None:
+        radius = float(radius)
+        if not radius >= 0:
+            raise ValueError(f"ops.radius_query: the radius must be a non-negative number, got {radius}")
+    elif B and not bool((radii >= 0).all()):
+        raise ValueError("ops.radius_query: every radius must be a non-negative number")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    pos = pos.detach().to(dev).contiguous()
+    if B == 0 or n == 0:
+        return torch.zeros(B + 1, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int64, device=dev)
+    cen = cen.to(dev)
+    if radii is not None:
+        radii = radii.to(dev)
+    tiles = (n + 511) // 512
+    step = max(1, min(B, _RADIUS_TABLE_BYTES // (4 * tiles)))
+    s = stream_of(pos)
+    ptrs, idxs, total = [], [], 0
+    for b0 in range(0, B, step):
+        nb = min(step, B - b0)
+        c = cen[b0:b0 + nb]
+        rr = None if radii is None else radii[b0:b0 + nb]
+        nbytes = lib.dva_radius_query_workspace_bytes(n, nb)
+        if nbytes < 0:
+            raise _lib.DvaError(f"dva_radius_query_workspace_bytes({n}, {nb})", int(nbytes))
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+        ptr_b = torch.empty(nb + 1, dtype=torch.int64, device=dev)
+        rad = 0.0 if radii is not None else radius
+        with _timed("radius_count", n * 12 + tiles * nb * 12):
+            check(lib.dva_radius_count(ptr(pos), n, ptr(c), nb, int(dims), rad, ptr(rr), ptr(ptr_b), ptr(ws),
+                                       int(nbytes), s), "dva_radius_count")
+        m = int(ptr_b[nb])                                # host read: the size of idx
+        idx_b = torch.empty(m, dtype=torch.int64, device=dev)
+        with _timed("radius_fill", n * 12 + tiles * nb * 4 + m * 8):
+            check(lib.dva_radius_fill(ptr(pos), n, ptr(c), nb, int(dims), rad, ptr(rr), ptr(ptr_b), ptr(idx_b), m,
+                                      ptr(ws), int(nbytes), s), "dva_radius_fill")
+        ptrs.append(ptr_b[:nb] + total)
+        idxs.append(idx_b)
+        total += m
+    ptrs.append(torch.tensor([total], dtype=torch.int64, device=dev))
+    return torch.cat(ptrs), (idxs[0] if len(idxs) == 1 else torch.cat(idxs))

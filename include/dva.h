@@ -982,6 +982,31 @@ int dva_grid_majority(const int64_t* labels, int64_t n, const int64_t* cluster, 
                       void* stream);
 
 /* ------------------------------------------------------------------------------------------ *
+ * Exact radius query.  Replaces scikit-learn's KDTree.query_radius under SphereSampling / CylinderSampling and
+ * GridSphereSampling / GridCylinderSampling (core/data_transform/transforms.py:99-232, :301-405), all centres in
+ * one call.  pos fp32 [n, 3]; centres fp64 [n_centres, dims], dims = 3 (sphere) or 2 (cylinder: z is ignored);
+ * radius fp64 >= 0, or radii fp64 [n_centres] (nullable; when given, radius is ignored and a negative or NaN entry
+ * gives an empty ball).  Point p is a member of centre c iff d <= r * r with d = ((dx dx) + dy dy) + dz dz,
+ * dx = (double)p.x - c.x, every product and sum rounded on its own in fp64 (no fused multiply-add), r * r computed
+ * once, the boundary inclusive: scikit-learn's leaf test.  A point with a non-finite coordinate is never a member.
+ *   dva_radius_count  ptr int64 [n_centres + 1] (device) = CSR offsets; ptr[n_centres] is the number of members of
+ *                     all centres and may exceed 2^31.  Leaves the per-(tile, centre) offsets in the workspace.
+ *   dva_radius_fill   idx int64 [ptr[n_centres]] = the members of every centre in ascending point index, from the
+ *                     SAME workspace, untouched since dva_radius_count of the same arguments.  idx_capacity = the
+ *                     number of elements idx holds; nothing is written beyond it.
+ * Brute force over all pairs in two passes, no atomics: bitwise reproducible.  n < 2^31 (DVA_ERR_UNSUPPORTED beyond);
+ * n = 0, n_centres = 0 and empty balls are valid.  The workspace grows with n * n_centres (4 bytes per centre and
+ * 512 points): the caller splits the centres to its budget.  Argument errors return DVA_ERR_INVALID before any HIP
+ * call. */
+int64_t dva_radius_query_workspace_bytes(int64_t n, int64_t n_centres);
+int dva_radius_count(const float* pos, int64_t n, const double* centres, int64_t n_centres, int32_t dims,
+                     double radius, const double* radii, int64_t* ptr, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+int dva_radius_fill(const float* pos, int64_t n, const double* centres, int64_t n_centres, int32_t dims,
+                    double radius, const double* radii, const int64_t* ptr, int64_t* idx, int64_t idx_capacity,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------ *
  * Lexicographic integer keys.  Replace utils/multimodal.py:36-94 (lexargsort / lexargunique on a
  * composite int64 key, :97-179 CompositeTensor, :253-323 lex ops).
  * ------------------------------------------------------------------------------------------ */

@@ -221,6 +221,11 @@ SIGNATURES = {
     "dva_radius_query_workspace_bytes": (ctypes.c_int64, [_i64, _i64]),
     "dva_radius_count": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i32, _f64, _vp, _vp, _vp, _i64, _vp]),
     "dva_radius_fill": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i32, _f64, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "dva_minmax3_workspace_bytes": (ctypes.c_int64, []),
+    "dva_minmax3_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _i64, _vp]),
+    "dva_elastic_workspace_bytes": (ctypes.c_int64, [_i64, _i64, _i64]),
+    "dva_elastic_smooth": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "dva_elastic_displace": (ctypes.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _f64, _vp, _vp]),
     "dva_lex_workspace_bytes": (ctypes.c_int64, [_i64]),
     "dva_argsort_i64": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "dva_argunique_i64": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp]),

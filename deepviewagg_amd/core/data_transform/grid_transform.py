@@ -22,8 +22,15 @@ the ``last`` gathers are ``index_select``.  Results are the reference's, bit for
 Results land on the input's device (CPU data in gives CPU tensors out, which the reference's ``ShiftVoxels`` needs);
 the work runs on the current HIP device.  ``dropin.install()`` copies every public name of this module onto the
 reference's module, so the public namespace is the two classes: everything else is imported under ``_`` names.
+
+``ElasticDistortion`` (reference grid_transform.py:194-256), the augmentation that opens the ScanNet
+``train_transform``, is the third class of the reference's module.  It is defined at the end of this file, kept out
+of the eagerly listed names above and served by the module's ``__getattr__``: ``grid_transform.ElasticDistortion``,
+``from ...grid_transform import ElasticDistortion`` and pickling by name all resolve, and ``dropin.install()`` sets it
+on the reference's module and package by name.
 """
 import logging as _logging
+import random as _random
 import re as _re
 
 import torch as _torch
@@ -174,3 +181,63 @@ class SaveOriginalPosId:
 
     def __repr__(self):
         return self.__class__.__name__
+
+
+class ElasticDistortion:
+    """Apply elastic distortion on sparse coordinate space. First projects the position onto a
+    voxel grid and then apply the distortion to the voxel grid.
+
+    Parameters
+    ----------
+    granularity: List[float]
+        Granularity of the noise in meters
+    magnitude: List[float]
+        Noise multiplier in meters
+
+    Returns the same data object with a distorted ``pos``: the reference's result bit for bit under the same seeds of
+    ``random`` (the 0.95 gate) and ``numpy.random`` (the noise volume of every level, drawn on the host exactly as the
+    reference draws it).  The bounds, the smoothing of the noise and the interpolation at every point run on the
+    current HIP device (``ops.elastic_distortion``, csrc/elastic.hip); every level reads six floats back, the bounds
+    of the previous level's output.  ``pos`` is float32 [N, 3] on the CPU or on a device, and the result lands on
+    the device ``pos`` came from.  An empty cloud raises ValueError, as numpy's reduction does in the reference;
+    non-finite ``pos`` is not supported.
+    """
+
+    def __init__(self, apply_distorsion=True, granularity=[0.2, 0.8], magnitude=[0.4, 1.6]):
+        assert len(magnitude) == len(granularity)
+        self._apply_distorsion = apply_distorsion
+        self._granularity = granularity
+        self._magnitude = magnitude
+
+    @staticmethod
+    def elastic_distortion(coords, granularity, magnitude):
+        from ... import ops as _ops
+        return _ops.elastic_distortion(coords, granularity, magnitude).to(coords.device)
+
+    def __call__(self, data):
+        if self._apply_distorsion:
+            if _random.random() < 0.95:
+                from ... import ops as _ops
+                pos = _get(data, "pos")
+                out = pos
+                for i in range(len(self._granularity)):
+                    # a level's bounds are those of the previous level's output, which stays on the HIP device
+                    out = _ops.elastic_distortion(out, self._granularity[i], self._magnitude[i])
+                _set(data, "pos", out.to(pos.device))
+        return data
+
+    def __repr__(self):
+        return "{}(apply_distorsion={}, granularity={}, magnitude={})".format(
+            self.__class__.__name__, self._apply_distorsion, self._granularity, self._magnitude,
+        )
+
+
+_LAZY = {"ElasticDistortion": ElasticDistortion}
+del ElasticDistortion
+
+
+def __getattr__(name):
+    try:
+        return _LAZY[name]
+    except KeyError:
+        raise AttributeError(f"module {__name__!r} has no attribute {name!r}") from None

@@ -4,9 +4,9 @@ The reference finds its modules by name at the dotted paths
 ``torch_points3d.modules.multimodal.{pooling,fusion}`` (ModalityFactory.get_module,
 models/base_architectures/unet.py:69-101), ``torch_points3d.core.multimodal.visibility``
 (MapImages, core/data_transform/multimodal/image.py:214-215), finds its pre-transforms
-(PCAComputePointwise, EigenFeatures) in ``torch_points3d.core.data_transform.features``, GridSampling3D and
-SaveOriginalPosId in ``torch_points3d.core.data_transform.grid_transform``, the sphere and cylinder samplers
-(SphereSampling, CylinderSampling, GridSphereSampling, GridCylinderSampling, Select) in
+(PCAComputePointwise, EigenFeatures) in ``torch_points3d.core.data_transform.features``, GridSampling3D,
+SaveOriginalPosId and ElasticDistortion in ``torch_points3d.core.data_transform.grid_transform``, the sphere and
+cylinder samplers (SphereSampling, CylinderSampling, GridSphereSampling, GridCylinderSampling, Select) in
 ``torch_points3d.core.data_transform.transforms``, and both groups on the package
 ``torch_points3d.core.data_transform`` itself (``instantiate_transform`` and ``cT.GridSampling3D`` look them up there),
 and imports the data classes from
@@ -38,7 +38,10 @@ _ALIASES = {
 # (package, our module, names): set on the package after the aliases above
 _PACKAGE_NAMES = [
     ("torch_points3d.core.data_transform", "deepviewagg_amd.core.data_transform.grid_transform",
-     ("GridSampling3D", "SaveOriginalPosId")),
+     ("GridSampling3D", "SaveOriginalPosId", "ElasticDistortion")),
+    # our module serves this name through its __getattr__: on a patched reference module it has to be set by name
+    ("torch_points3d.core.data_transform.grid_transform", "deepviewagg_amd.core.data_transform.grid_transform",
+     ("ElasticDistortion",)),
     ("torch_points3d.core.data_transform", "deepviewagg_amd.core.data_transform.transforms",
      ("SphereSampling", "CylinderSampling", "GridSphereSampling", "GridCylinderSampling", "Select")),
 ]
@@ -76,6 +79,8 @@ def install(patch_existing=True):
         pkg = sys.modules.get(pkg_name)
         if pkg is None:
             pkg = importlib.import_module(pkg_name)
+        if pkg is ours:
+            continue
         for k in names:
             setattr(pkg, k, getattr(ours, k))
     return done

@@ -15,6 +15,9 @@ ops; names and argument meaning follow the reference call site
 ``grid_mean``              grid_transform.py:81 (``scatter_mean``)
 ``grid_majority``          grid_transform.py:76-79 (one_hot + ``scatter_add`` + argmax)
 ``radius_query``           core/data_transform/transforms.py:147,215,332,386 (KDTree.query_radius)
+``elastic_smooth``         grid_transform.py:231-234 (six ``scipy.ndimage.convolve`` calls)
+``elastic_displace``       grid_transform.py:241-242 (``RegularGridInterpolator``)
+``elastic_distortion``     grid_transform.py:218-243 (one level of ElasticDistortion)
 =========================  ==========================================================
 
 All ops require tensors on a HIP device and raise otherwise (no CPU fallback).
@@ -2019,3 +2022,137 @@ def radius_query(pos, centres, radius, dims=3):
         total += m
     ptrs.append(torch.tensor([total], dtype=torch.int64, device=dev))
     return torch.cat(ptrs), (idxs[0] if len(idxs) == 1 else torch.cat(idxs))
+
+
+# ---------------------------------------------------------------------------------------------
+# elastic distortion (core/data_transform/grid_transform.py:194-256, ElasticDistortion)
+# ---------------------------------------------------------------------------------------------
+
+def _current_device():
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _elastic_volume(volume, what):
+    """A [Dx, Dy, Dz, 3] float32 volume (tensor or numpy array) as a contiguous tensor on the current HIP device."""
+    v = volume if torch.is_tensor(volume) else torch.as_tensor(np.ascontiguousarray(volume))
+    if v.dtype != torch.float32:
+        raise TypeError(f"ops.{what} must be float32, got {v.dtype}")
+    if v.dim() != 4 or v.shape[3] != 3 or min(v.shape[:3]) < 1:
+        raise ValueError(f"ops.{what} must be [Dx, Dy, Dz, 3] with Dx, Dy, Dz >= 1, got {tuple(v.shape)}")
+    if v.numel() >= 1 << 31:
+        raise ValueError(f"ops.{what} has {v.numel()} elements, the kernels take fewer than 2^31")
+    return v.detach().to(_current_device()).contiguous()
+
+
+def _elastic_pos(pos, what):
+    if not torch.is_tensor(pos):
+        raise TypeError(f"ops.{what}: pos must be a tensor")
+    if pos.dtype != torch.float32:
+        raise TypeError(f"ops.{what}: pos must be float32 (the reference's clouds are), got {pos.dtype}")
+    if pos.dim() != 2 or pos.shape[1] != 3:
+        raise ValueError(f"ops.{what}: pos must be [N, 3], got {tuple(pos.shape)}")
+    if pos.numel() >= 1 << 31:
+        raise ValueError(f"ops.{what}: N = {pos.shape[0]} points, the kernels take 3 N < 2^31")
+    return pos.detach().to(_current_device()).contiguous()
+
+
+def elastic_smooth(noise):
+    """The reference's smoothing of an ElasticDistortion noise volume ``noise`` float32 [Dx, Dy, Dz, 3] (tensor or
+    numpy array): two rounds of ``scipy.ndimage.convolve`` with the 3-tap box kernels along axes 0, 1, 2
+    (``mode="constant"``, ``cval=0``), bit for bit -- float64 accumulation over the taps in ascending order with
+    ``w = float64(float32(1) / 3)``, every pass stored as float32.  Returns a new float32 tensor of the same shape on
+    the current HIP device; ``noise`` is not modified.  Six launches of one kernel (csrc/elastic.hip)."""
+    lib = _lib.load()
+    vol = _elastic_volume(noise, "elastic_smooth: noise")
+    dx, dy, dz = (int(d) for d in vol.shape[:3])
+    nbytes = lib.dva_elastic_workspace_bytes(dx, dy, dz)
+    if nbytes < 0:
+        raise _lib.DvaError(f"dva_elastic_workspace_bytes({dx}, {dy}, {dz})", int(nbytes))
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=vol.device)
+    out = torch.empty_like(vol)
+    with _timed("elastic_smooth", 6 * 2 * vol.numel() * 4):
+        check(lib.dva_elastic_smooth(ptr(vol), dx, dy, dz, ptr(out), ptr(ws), int(nbytes), stream_of(vol)),
+              "dva_elastic_smooth")
+    return out
+
+
+def elastic_displace(pos, field, axes, magnitude):
+    """``pos + interp(pos) * magnitude`` of the reference's ElasticDistortion: ``pos`` float32 [N, 3], ``field``
+    float32 [Dx, Dy, Dz, 3] (the smoothed noise), ``axes`` the three ascending float64 knot vectors of lengths Dx, Dy,
+    Dz (at least 2 knots each; numpy arrays or tensors), ``magnitude`` a number.  ``interp`` is scipy's
+    ``RegularGridInterpolator(axes, field, bounds_error=0, fill_value=0)`` bit for bit: trilinear in float64, the cell
+    of a coordinate is the last knot not above it, 0 outside the axes; the sum is rounded to float32 once, at the end.
+    Returns float32 [N, 3] on the current HIP device.  One thread per point (csrc/elastic.hip); non-finite ``pos`` is
+    not supported."""
+    lib = _lib.load()
+    p = _elastic_pos(pos, "elastic_displace")
+    f = _elastic_volume(field, "elastic_displace: field")
+    if len(axes) != 3:
+        raise ValueError(f"ops.elastic_displace: axes must be three knot vectors, got {len(axes)}")
+    knots = []
+    for d, a in zip(f.shape[:3], axes):
+        a = (a.detach().cpu() if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))).to(torch.float64).reshape(-1)
+        if a.shape[0] != d or d < 2:
+            raise ValueError(f"ops.elastic_displace: an axis of {a.shape[0]} knots for a field of shape "
+                             f"{tuple(f.shape)} (every axis needs its dimension's length, at least 2)")
+        if not bool((a[1:] > a[:-1]).all()):
+            raise ValueError("ops.elastic_displace: the knots of an axis must be strictly ascending")
+        knots.append(a)
+    ax = torch.cat(knots).to(p.device)
+    n = p.shape[0]
+    out = torch.empty_like(p)
+    if n == 0:
+        return out
+    dx, dy, dz = (int(d) for d in f.shape[:3])
+    with _timed("elastic_displace", n * 24 + f.numel() * 4):
+        check(lib.dva_elastic_displace(ptr(p), n, ptr(f), ptr(ax), dx, dy, dz, float(magnitude), ptr(out),
+                                       stream_of(p)), "dva_elastic_displace")
+    return out
+
+
+def minmax3(pos):
+    """Column minima and maxima of ``pos`` float32 [N, 3], N >= 1: float32 [6] on the current HIP device (the three
+    minima, then the three maxima).  Exact; one pass over ``pos``."""
+    lib = _lib.load()
+    p = _elastic_pos(pos, "minmax3")
+    if p.shape[0] == 0:
+        raise ValueError("zero-size array to reduction operation minimum which has no identity")
+    nbytes = int(lib.dva_minmax3_workspace_bytes())
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=p.device)
+    out = torch.empty(6, dtype=torch.float32, device=p.device)
+    with _timed("minmax3", p.numel() * 4):
+        check(lib.dva_minmax3_f32(ptr(p), p.shape[0], ptr(out), ptr(ws), nbytes, stream_of(p)), "dva_minmax3_f32")
+    return out
+
+
+def elastic_distortion(pos, granularity, magnitude, noise=None):
+    """One level of the reference's ``ElasticDistortion.elastic_distortion(coords, granularity, magnitude)``, bit for
+    bit, for ``pos`` float32 [N, 3] on any device; returns float32 [N, 3] on the current HIP device.
+
+    The bounds of ``pos`` are reduced on the device and read back (six floats, the one host synchronisation); the
+    shape of the noise volume and its knot axes are then computed on the host with the reference's own numpy
+    expressions, whose promotion rules decide their bits.  ``noise`` float32 ``[*noise_dim, 3]`` is drawn from numpy's
+    global generator when it is not given, exactly as the reference draws it (``np.random.seed`` gives the same
+    sample), and uploaded; a ``noise`` of another shape raises ValueError.  Smoothing and interpolation are
+    ``elastic_smooth`` and ``elastic_displace``.  An empty cloud raises as numpy's reduction does; non-finite ``pos``
+    is not supported."""
+    p = _elastic_pos(pos, "elastic_distortion")
+    bounds = minmax3(p).cpu().numpy()                      # host read: the volume's shape follows from the bounds
+    coords_min = bounds[:3]
+    # fp32(x - min) is monotone in x, so this is the reference's (coords - coords_min).max(0)
+    extent = bounds[3:] - coords_min
+    noise_dim = (extent // granularity).astype(int) + 3
+    shape = tuple(int(d) for d in noise_dim) + (3,)
+    if 3 * int(noise_dim[0]) * int(noise_dim[1]) * int(noise_dim[2]) >= 1 << 31:
+        raise ValueError(f"ops.elastic_distortion: a noise volume of shape {shape} at granularity {granularity}; "
+                         f"the kernels take fewer than 2^31 elements")
+    if noise is None:
+        noise = np.random.randn(*noise_dim, 3).astype(np.float32)
+    elif tuple(noise.shape) != shape:
+        raise ValueError(f"ops.elastic_distortion: noise of shape {tuple(noise.shape)}, the bounds of pos at "
+                         f"granularity {granularity} need {shape}")
+    ax = [
+        np.linspace(d_min, d_max, d)
+        for d_min, d_max, d in zip(coords_min - granularity, coords_min + granularity * (noise_dim - 2), noise_dim)
+    ]
+    return elastic_displace(p, elastic_smooth(noise), ax, magnitude)

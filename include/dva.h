@@ -1007,6 +1007,39 @@ int dva_radius_fill(const float* pos, int64_t n, const double* centres, int64_t 
                     void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------ *
+ * ElasticDistortion (core/data_transform/grid_transform.py:194-256: six scipy.ndimage.convolve calls over a noise
+ * volume and a scipy RegularGridInterpolator over every point, on the host).  One distortion level is
+ *   dva_minmax3_f32       out fp32 [6] (device) = the column minima, then the column maxima, of pos fp32 [n, 3];
+ *                         n >= 1.  Exact and independent of the order of reduction; non-finite values are not
+ *                         supported (a NaN is skipped).  Workspace: dva_minmax3_workspace_bytes().
+ *                         The caller derives the volume's shape [dx, dy, dz] and the three knot axes from these six
+ *                         numbers on the host (numpy's promotion rules decide their bits).
+ *   dva_elastic_smooth    out fp32 [dx, dy, dz, 3] = the noise volume after two rounds of three 3-tap passes along
+ *                         axes 0, 1, 2, zero padded: per pass ((0 + a w) + b w) + c w in fp64 over the neighbours in
+ *                         ascending order, w = (double)(1.0f / 3.0f), every product and sum rounded on its own, the
+ *                         pass stored as fp32 -- scipy.ndimage.convolve of a float32 array with the reference's blur
+ *                         kernels.  noise is not modified; out may not alias it.  Workspace (two volumes the passes
+ *                         alternate between): dva_elastic_workspace_bytes(dx, dy, dz).
+ *   dva_elastic_displace  out fp32 [n, 3] = fp32(fp64(pos) + value * magnitude); value = the trilinear interpolant of
+ *                         field fp32 [dx, dy, dz, 3] at pos over the knots axes fp64 [dx + dy + dz] (the three axes
+ *                         one after the other, each ascending, at least 2 knots), in fp64: per axis the cell i = the
+ *                         largest index with ax[i] <= x clipped to [0, d - 2], y = (x - ax[i]) / (ax[i + 1] - ax[i]),
+ *                         the eight corners in the order of itertools.product (axis 0 slowest, lower corner first),
+ *                         weight = (w0 w1) w2 with w = 1 - y | y, value += field[corner] * weight from 0; 0 for a
+ *                         point outside the axes.  No fused multiply-add, correctly rounded division: scipy's
+ *                         RegularGridInterpolator(method="linear", bounds_error=False, fill_value=0) bit for bit.
+ *                         out may alias pos.
+ * 3 n < 2^31 and 3 dx dy dz < 2^31 (DVA_ERR_UNSUPPORTED beyond).  No atomics: bitwise reproducible.  Argument errors
+ * return DVA_ERR_INVALID before any HIP call. */
+int64_t dva_minmax3_workspace_bytes(void);
+int dva_minmax3_f32(const float* pos, int64_t n, float* out, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t dva_elastic_workspace_bytes(int64_t dx, int64_t dy, int64_t dz);
+int dva_elastic_smooth(const float* noise, int64_t dx, int64_t dy, int64_t dz, float* out, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+int dva_elastic_displace(const float* pos, int64_t n, const float* field, const double* axes, int64_t dx, int64_t dy,
+                         int64_t dz, double magnitude, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------ *
  * Lexicographic integer keys.  Replace utils/multimodal.py:36-94 (lexargsort / lexargunique on a
  * composite int64 key, :97-179 CompositeTensor, :253-323 lex ops).
  * ------------------------------------------------------------------------------------------ */

@@ -66,6 +66,127 @@ def sparse_conv(x, W, bias, nbr, nbr_t=None):
     return out if bias is None else out + bias.to(x.dtype)
 
 
+def kernel_map_sorted(src_coords, dst_coords, offsets):
+    """``kernel_map`` without the Python loops (the dict version takes minutes above ~50 k voxels): shift every
+    column to non-negative, pack a row into one int64 key, stable sort of the source keys (equal keys keep their
+    row order, so the first of a run is the smallest row: the dict version's rule for duplicates), binary search
+    of the keys of ``dst + offset``."""
+    src = np.asarray(torch.as_tensor(src_coords).cpu(), dtype=np.int64).reshape(-1, 4)
+    dst = np.asarray(torch.as_tensor(dst_coords).cpu(), dtype=np.int64).reshape(-1, 4)
+    offs = np.asarray(torch.as_tensor(offsets).cpu(), dtype=np.int64).reshape(-1, 3)
+    nbr = np.full((offs.shape[0], dst.shape[0]), -1, dtype=np.int32)
+    if src.shape[0] == 0 or dst.shape[0] == 0:
+        return torch.from_numpy(nbr)
+    reach = np.abs(offs).max(0)
+    lo = np.minimum(src.min(0), dst.min(0))
+    hi = np.maximum(src.max(0), dst.max(0))
+    lo[:3] -= reach
+    hi[:3] += reach
+    span = hi - lo + 1
+    assert float(np.prod(span.astype(np.float64))) < 2.0 ** 62, "voxel grid too large to pack into one 64-bit key"
+
+    def key(rows):
+        r = rows - lo
+        return ((r[:, 3] * span[2] + r[:, 2]) * span[1] + r[:, 1]) * span[0] + r[:, 0]
+    order = np.argsort(key(src), kind="stable")
+    skey = key(src)[order]
+    for k, o in enumerate(offs):
+        q = key(dst + np.array([o[0], o[1], o[2], 0], dtype=np.int64))
+        pos = np.searchsorted(skey, q, side="left")
+        hit = skey[np.minimum(pos, skey.shape[0] - 1)] == q
+        nbr[k, hit] = order[pos[hit]]
+    return torch.from_numpy(nbr)
+
+
+def split_bf16(t):
+    """(hi, lo) = (bf16(t), bf16(t - hi)), both round-to-nearest-even, in the dtype of ``t``: the operand split of
+    sparseconv.hip (``sc_split8``, ``sconv_prep_weights_kernel``, ``sc_tileT_put``)."""
+    hi = t.to(torch.bfloat16).to(t.dtype)
+    lo = (t - hi).to(torch.bfloat16).to(t.dtype)
+    return hi, lo
+
+
+def sparse_conv_split(x, W, bias, nbr, order="hh,lh,hl"):
+    """What ``sconv_apply_kernel`` computes on fp32 features: the three bf16 products ``xh Wh + xl Wh + xh Wl`` (the
+    ``lo lo`` product is dropped), everything else in the dtype of ``x`` (float64: the exact value of the split,
+    float32: one plain evaluation of it).  ``order``: the terms are summed as listed, each accumulated over all offsets
+    on its own (the kernel interleaves them per 16 channels; the sum is the same in exact arithmetic)."""
+    xh, xl = split_bf16(x)
+    Wh, Wl = split_bf16(W.to(x.dtype))
+    parts = {"hh": (xh, Wh), "lh": (xl, Wh), "hl": (xh, Wl)}
+    out = None
+    for name in order.split(","):
+        a, b = parts[name]
+        term = sparse_conv(a, b, None, nbr)
+        out = term if out is None else out + term
+    return out if bias is None else out + bias.to(x.dtype)
+
+
+def sparse_conv_split_mfma_order(x, W, bias, nbr, step=8):
+    """``sparse_conv_split`` in float32 in the ACCUMULATION ORDER of ``sconv_apply_kernel``: one fp32 accumulator per
+    output element over all offsets (ascending), the three terms interleaved per 16 input channels (``xh Wh``,
+    ``xh Wl``, ``xl Wh``), one rounding to float32 per group of ``step`` products (summed in float64 here: exact to
+    the last bit or so; an offset the wavefront skips adds zeros).  ``step`` = 8: ``v_mfma_f32_32x32x16_bf16`` takes
+    channels 16 m + 8 h .. + 7 from lane half h and the device's rows sit where two roundings per instruction put them
+    -- at 1.0 x this evaluation's noise; with ``step`` = 16 at sqrt(2) x in every case except 5 input channels, whose
+    second half is all zeros.  ``sparse_conv_split`` in float32 sums each offset's products inside a
+    blocked matrix product first; this is the honest float32 evaluation of a chain of K Cin / 8 x 3 dependent
+    additions, what the kernel does by construction."""
+    assert x.dtype == torch.float32
+    pad = (-x.shape[1]) % 16                                    # the host pads the channel count with zeros
+    x, W = torch.nn.functional.pad(x, (0, pad)), torch.nn.functional.pad(W.to(x.dtype), (0, 0, 0, pad))
+    xh, xl = split_bf16(x)
+    Wh, Wl = split_bf16(W)
+    acc = torch.zeros((nbr.shape[1], W.shape[2]), dtype=torch.float32)
+    for k in range(nbr.shape[0]):
+        dst = torch.nonzero(nbr[k] >= 0).flatten()
+        if not dst.numel():
+            continue
+        src = nbr[k][dst].long()
+        part = acc[dst].double()
+        # [steps, pairs, Cout] per term: the exact sums of one instruction each
+        prods = [torch.bmm(a[src].double().reshape(src.numel(), -1, step).transpose(0, 1),
+                           b[k].double().reshape(-1, step, W.shape[2])) for a, b in ((xh, Wh), (xh, Wl), (xl, Wh))]
+        per16 = 16 // step
+        for i in range(0, prods[0].shape[0], per16):
+            for p in prods:
+                for h in range(per16):
+                    part = (part + p[i + h]).float().double()
+        part = part.float()
+        acc[dst] = part
+    return acc if bias is None else acc + bias.to(x.dtype)
+
+
+def sparse_conv_split_grad_x(g, W, nbr_t):
+    """The device's input gradient (``sconv_apply_kernel`` in mode 1): the split convolution of ``grad_out`` with
+    ``W_k^T`` through the transposed map -- NOT the autograd of ``sparse_conv_split``."""
+    return sparse_conv_split(g, W.transpose(1, 2), None, nbr_t)
+
+
+def sparse_conv_split_grad_w(x, g, nbr):
+    """The device's fp32 weight gradient (``sconv_wgrad_kernel``): ``Xh^T Gh + Xl^T Gh + Xh^T Gl`` per offset over
+    its pairs, with both the gathered rows and ``grad_out`` split."""
+    xh, xl = split_bf16(x)
+    gh, gl = split_bf16(g)
+    out = torch.zeros((nbr.shape[0], x.shape[1], g.shape[1]), dtype=x.dtype)
+    for k in range(nbr.shape[0]):
+        dst = torch.nonzero(nbr[k] >= 0).flatten()
+        if dst.numel():
+            src = nbr[k][dst].long()
+            out[k] = xh[src].t() @ gh[dst] + xl[src].t() @ gh[dst] + xh[src].t() @ gl[dst]
+    return out
+
+
+def sparse_conv_grad_w(x, g, nbr):
+    """``grad W[k] = X_k^T G_k`` over the pairs of offset k, no split (the bf16 kernel: bf16 operands, fp32 sums)."""
+    out = torch.zeros((nbr.shape[0], x.shape[1], g.shape[1]), dtype=x.dtype)
+    for k in range(nbr.shape[0]):
+        dst = torch.nonzero(nbr[k] >= 0).flatten()
+        if dst.numel():
+            out[k] = x[nbr[k][dst].long()].t() @ g[dst]
+    return out
+
+
 def batchnorm_act_rows(y, bn, slope, counts=None, n=None):
     """nn.BatchNorm1d on the rows followed by leaky_relu(slope) (slope 1: none, slope 0: ReLU)."""
     assert counts is None

@@ -103,3 +103,90 @@ def test_cpu_twin_of_a_stage_runs_on_the_oracle(monkeypatch):
     assert z.s == 1 and torch.equal(z.C, coords) and z.F.shape == (coords.shape[0], 12)
     z.F.square().mean().backward()
     assert x.F.grad is not None and down.conv_in[0].kernel.grad.abs().sum() > 0
+
+
+# ---- the additions the row-wise GPU tests stand on (tests/sparse_rows.py) --------------------------------------------
+import pytest                                                   # noqa: E402
+
+import sparse_rows as SR                                        # noqa: E402
+
+
+@pytest.mark.parametrize("n_src", SR.MAP_SIZES)
+@pytest.mark.parametrize("duplicates", [False, True])
+def test_sorted_kernel_map_matches_dict_version(n_src, duplicates):
+    """src != dst, destinations without any neighbour, negative coordinates, equal coordinates in two batch items,
+    duplicate source rows (smallest row wins), both directions."""
+    src, dst = SR.map_cloud(n_src, seed=n_src, duplicates=duplicates)
+    offs = O.kernel_offsets(3)
+    nbr = O.kernel_map_sorted(src, dst, offs)
+    assert nbr.dtype == torch.int32 and torch.equal(nbr, O.kernel_map(src, dst, offs))
+    assert torch.equal(O.kernel_map_sorted(dst, src, -offs), O.kernel_map(dst, src, -offs))
+    if n_src >= 31:
+        assert bool((nbr >= 0).any()) and bool((nbr < 0).all(0).any())          # hits, and rows without any
+    if duplicates and n_src >= 31:
+        assert np.unique(src.numpy(), axis=0).shape[0] < n_src
+    if n_src >= 2:                                              # never across the batch column
+        k, j = torch.nonzero(nbr >= 0, as_tuple=True)
+        assert torch.equal(src[nbr[k, j].long(), 3], dst[j, 3]) and bool((src[:, 3] == 1).any())
+
+
+@pytest.mark.parametrize("k,stride,ts,dilation", [(3, 1, 1, 1), (2, 2, 1, 1), (3, 2, 1, 1), (3, 1, 2, 1), (2, 2, 4, 1),
+                                                   (3, 1, 1, 2)])
+def test_sorted_kernel_map_on_the_strata_cloud(k, stride, ts, dilation):
+    coords = SR.strata_cloud(1, 1500, stride=ts)
+    dst = coords if stride == 1 else O.downsample_coords(coords, ts * stride)
+    offs = O.kernel_offsets(k, ts, dilation)
+    assert torch.equal(O.kernel_map_sorted(coords, dst, offs), O.kernel_map(coords, dst, offs))
+    assert torch.equal(O.kernel_map_sorted(dst, coords, -offs), O.kernel_map(dst, coords, -offs))
+    assert torch.equal(O.kernel_map_sorted(coords[:0], dst, offs), torch.full((k ** 3, dst.shape[0]), -1).int())
+    assert O.kernel_map_sorted(coords, dst[:0], offs).shape == (k ** 3, 0)
+
+
+def test_strata_cloud_fills_every_stratum():
+    coords = SR.strata_cloud(1, 1500)
+    n_struct = SR.structured_part().shape[0]
+    head = coords[:n_struct].long()
+    key = ((head[:, 3] * 4096 + head[:, 2]) * 4096 + head[:, 1]) * 4096 + head[:, 0]
+    assert bool((key[1:] > key[:-1]).all())                     # the structured part is sorted ascending (b, z, y, x)
+    _, _, nbr, _ = SR.maps(coords)
+    s = SR.conv_strata(nbr, require=("nbr_1", "nbr_2_8", "nbr_9_26", "nbr_27", "tile_edge", "last_tile", "wave_skips",
+                                     "wave_no_skip"))
+    assert int(s["nbr_1"].sum()) >= 70 and int(s["nbr_27"].sum()) == 128 and not bool(s["nbr_0"].any())
+    skipped = SR.skipped_offsets(nbr)
+    assert 24 in skipped and 18 in skipped and 0 in skipped     # line, plane, block / surface
+    # the surface part alone, shuffled: a block misses a corner offset at most (the earlier clouds hardly reached the
+    # branch, and never with most offsets skipped)
+    _, _, nbr_s, _ = SR.maps(coords[n_struct:])
+    assert max(SR.skipped_offsets(nbr_s)[:-1]) <= 2
+
+
+@pytest.mark.parametrize("k,stride,transpose", [(3, 1, False), (2, 2, False), (3, 2, True)])
+def test_split_statement_is_the_old_gate(k, stride, transpose):
+    """float64 evaluation of the 3-term split against exact float64: inside the 2e-5 the GPU tests hold the kernel to
+    (now a statement about the algorithm), forward and the explicit statements of the device's backward against
+    float64 autograd of the exact oracle."""
+    c = SR.conv_case(f"oracle_k{k}s{stride}t{int(transpose)}", SR.strata_cloud(1, 1500), 96, 64, k=k, stride=stride,
+                     bias=True, transpose=transpose)
+    for key, ex in (("out64", "out"), ("gx64", "gx"), ("gW64", "gW")):
+        err = SR.old_metric(c[key], c["exact"][ex])
+        assert 1e-7 < err <= 2e-5, (key, err)                   # and it IS a different function: the lo lo term is gone
+    assert SR.old_metric(c["gb64"], c["exact"]["gb"]) <= 1e-12
+
+
+def test_split_bf16_and_autograd():
+    t = torch.randn(1000, dtype=torch.float64)
+    hi, lo = O.split_bf16(t)
+    assert hi.dtype == lo.dtype == torch.float64
+    assert torch.equal(hi, t.bfloat16().double()) and torch.equal(lo, (t - hi).bfloat16().double())
+    assert float((t - hi - lo).abs().max()) <= 2.0 ** -16 * float(t.abs().max())
+    h32, l32 = O.split_bf16(t.float())
+    assert h32.dtype == torch.float32 and torch.equal(h32, t.float().bfloat16().float())
+    coords = SR.strata_cloud(1, 0)
+    _, _, nbr, _ = SR.maps(coords)
+    x = torch.randn(coords.shape[0], 8, dtype=torch.float64, requires_grad=True)
+    W = torch.randn(27, 8, 4, dtype=torch.float64, requires_grad=True)
+    O.sparse_conv_split(x, W, None, nbr).sum().backward()
+    assert x.grad is not None and W.grad is not None and float(x.grad.abs().max()) > 0
+    a = O.sparse_conv_split(x.detach(), W.detach(), None, nbr)
+    b = O.sparse_conv_split(x.detach(), W.detach(), None, nbr, order="hl,lh,hh")
+    assert float((a - b).abs().max()) <= 1e-12 * float(a.abs().max())

@@ -128,9 +128,6 @@ SIGNATURES = {
     "dva_chain_stats2": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "dva_chain_pooled": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp]),
     "dva_chain_stats": (ctypes.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
-    "dva_chain_stats_a2": (ctypes.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
-    "dva_chain_score_stats_a2": (ctypes.c_int, [_vp] * 12 + [_i32, _i64, _i64, _vp]),
-    "dva_chain_bwd_layer6_a2": (ctypes.c_int, [_vp] * 13 + [_i32, _i64, _i64, _vp]),
     "dva_chain_attn_fwd": (ctypes.c_int, [_vp] * 18 + [_i64, _i64, _i64, _i32, _i32, _i32, _f32, _vp]),
     "dva_chain_attn_bwd": (ctypes.c_int, [_vp] * 14 + [_i64, _i64, _i64, _i32, _i32, _i32, _f32, _vp]),
     "dva_chain_attn_fwd_dt": (ctypes.c_int, [_vp] * 18 + [_i64, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _vp]),
@@ -138,7 +135,6 @@ SIGNATURES = {
     "dva_chain_attn_bwd_f32": (ctypes.c_int, [_vp] * 14 + [_i64, _i64, _i64, _i32, _i32, _i32, _f32, _vp]),
     "dva_gather_segment_max_fwd": (ctypes.c_int, [_vp] * 5 + [_i64, _i64, _i64, _i32, _i32, _vp]),
     "dva_gather_segment_max_bwd": (ctypes.c_int, [_vp] * 8 + [_i64, _i64, _i64, _i32, _i32, _vp]),
-    "dva_chain_keys": (ctypes.c_int, [_vp] * 12 + [_i64, _i64, _vp]),
     "dva_chain_keys_compat": (ctypes.c_int, [_vp] * 14 + [_i32, _f32, _i64, _i64, _vp]),
     "dva_chain_attn_fwd_keys": (ctypes.c_int, [_vp] * 12 + [_f32] + [_vp] * 8 + [_i64, _i64, _i64, _i32, _i32, _i32, _f32, _vp]),
     "dva_qkv_dquery": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _i64, _i64, _i32, _f32, _vp]),
@@ -146,8 +142,6 @@ SIGNATURES = {
     "dva_chain_bwd_layer6_keys": (ctypes.c_int, [_vp] * 16 + [_i32, _f32, _i64, _i64, _vp]),
     "dva_qkv_compat": (ctypes.c_int, [_vp] * 4 + [_i64, _i32, _f32, _vp]),
     "dva_qkv_compat_bwd": (ctypes.c_int, [_vp] * 7 + [_i64, _i64, _i32, _f32, _vp]),
-    "dva_chain_attn_bwd_planrec": (ctypes.c_int, [_vp] * 15 + [_i64, _i64, _i64, _i32, _i32, _i32, _f32, _vp]),
-    "dva_plan_inverse": (ctypes.c_int, [_vp, _vp, _i64, _vp]),
     "dva_plan_split_table_bytes": (ctypes.c_int64, [_i64, _i64]),
     "dva_plan_split_build": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
     "dva_plan_split_sort_records": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
@@ -168,9 +162,6 @@ SIGNATURES = {
     "dva_emod_attn_bwd": (ctypes.c_int, [_vp] * 20 + [_i64, _i64, _i64, _i32, _i32, _i32, _f32, _vp]),
     "dva_emod_stats1_plan": (ctypes.c_int, [_vp] * 6 + [_i64, _i64, _i32, _vp]),
     "dva_emod_bwd": (ctypes.c_int, [_i32] + [_vp] * 16 + [_i64, _i64, _i64, _i32, _i32, _vp]),
-    "dva_chain_score_l6_stats": (ctypes.c_int, [_vp] * 16 + [_i32, _i64, _i64, _vp]),
-    "dva_chain_l6_consts": (ctypes.c_int, [_vp] * 7),
-    "dva_chain_bwd_layer5_merged": (ctypes.c_int, [_vp] * 18 + [_i32, _i64, _i64, _vp]),
     "dva_chain_route_stats": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "dva_copy_ceiling": (ctypes.c_int, [_vp, _vp, _i64, _vp]),
     "dva_zero_unseen_rows": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp]),
@@ -179,7 +170,6 @@ SIGNATURES = {
     "dva_concat_cast_fwd": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     "dva_concat_cast_bwd": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     "dva_mapping_row_index": (ctypes.c_int, [_vp, _vp, _vp, _i32, ctypes.c_double, _i64, _i64, _i32, _i32, _i32, _vp, _vp]),
-    "dva_view_gather_rows_grad_rec16": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     "dva_view_gather_rows_grad_rec16_to": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp]),
     "dva_chain_tile_chunks": (ctypes.c_int, [_vp, _i64, _i64, _i32, _vp, _vp]),
     "dva_chain_tile_offsets": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp]),

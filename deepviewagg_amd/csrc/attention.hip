@@ -989,7 +989,7 @@ __global__ __launch_bounds__(256) void rows_grad_team_kernel(
     const int32_t* __restrict__ row_ptr, const float* __restrict__ rec, int rs,
     TO* __restrict__ grows, int64_t R, int C, int G, int lpr, int lpg, int c0 = 0) {
   // C = row stride in elements; a launch covers the channels [c0, c0 + lpr * VEC) of every row (c0 = 0, lpr * VEC = C:
-  // whole rows; channel slabs: dva_view_gather_rows_grad_rec16)
+  // whole rows; channel slabs: dva_view_gather_rows_grad_rec16_to)
   constexpr int VEC = Vec16<T>::N;
   constexpr int U = 4;
   typedef typename Vec16<T>::raw raw_t;
@@ -1569,9 +1569,9 @@ int dva_view_gather_attention_bwd(const void* grad_out, const void* rows, const 
                              n_views, C, G, scaling, dtype, algo, stream);
 }
 
-static int rows_grad_rec16_impl(const void* grad_out, const int32_t* perm, const int32_t* row_ptr,
-                                const void* view_rec16, void* grad_rows, int32_t out_dtype, int64_t n_rows,
-                                int64_t n_views, int32_t C, int32_t G, int32_t dtype, void* stream) {
+int dva_view_gather_rows_grad_rec16_to(const void* grad_out, const int32_t* perm, const int32_t* row_ptr,
+                                       const void* view_rec16, void* grad_rows, int32_t out_dtype, int64_t n_rows,
+                                       int64_t n_views, int32_t C, int32_t G, int32_t dtype, void* stream) {
   if (n_rows < 0 || n_views < 0 || C <= 0 || G <= 0 || G > 4 || (G & (G - 1))) return DVA_ERR_INVALID;
   if (out_dtype != DVA_F32 && out_dtype != DVA_BF16 && out_dtype != DVA_F16) return DVA_ERR_INVALID;
   if (n_views > 0x7fffffffLL) return DVA_ERR_UNSUPPORTED;
@@ -1597,20 +1597,6 @@ static int rows_grad_rec16_impl(const void* grad_out, const int32_t* perm, const
                                    (hipStream_t)stream);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
-}
-
-int dva_view_gather_rows_grad_rec16(const void* grad_out, const int32_t* perm, const int32_t* row_ptr,
-                                    const void* view_rec16, float* grad_rows, int64_t n_rows, int64_t n_views,
-                                    int32_t C, int32_t G, int32_t dtype, void* stream) {
-  return rows_grad_rec16_impl(grad_out, perm, row_ptr, view_rec16, grad_rows, DVA_F32, n_rows, n_views, C, G, dtype,
-                              stream);
-}
-
-int dva_view_gather_rows_grad_rec16_to(const void* grad_out, const int32_t* perm, const int32_t* row_ptr,
-                                       const void* view_rec16, void* grad_rows, int32_t out_dtype, int64_t n_rows,
-                                       int64_t n_views, int32_t C, int32_t G, int32_t dtype, void* stream) {
-  return rows_grad_rec16_impl(grad_out, perm, row_ptr, view_rec16, grad_rows, out_dtype, n_rows, n_views, C, G, dtype,
-                              stream);
 }
 
 int dva_view_gather_rows_grad(const void* grad_out, const float* att, const float* gate,

@@ -27,22 +27,18 @@ struct ChainKeep {
 // the raw output z6 (BatchNorm backward, statistics) and the folded product t6 = 0.6 y6 (block W6F) whose sign the
 // forward's activation saw and whose activation a6 feeds the score layer.  tabs[0..3] = layers 1, 2, 5, 6.
 // L6: 0 = z6 only, 1 = + t6, 2 = + t6 and a6.
-// A2IN (round 6, the stored-a2 hybrid): k.a2 already holds the layer-2 activation row the forward stored
-// (stats_mid_kernel<5, 1>: the very operand computed below): layers 1 and 2 are skipped, x is not read.
 // MASK = false: activations of lanes without a view are not zeroed (chain_common.h act_pack) -- for passes whose every sum
 // over views is guarded on the gradient side (score gradients of such a lane are zero, gradient rows go through pack16).
-template <int W6F, int L6, bool A2IN = false, bool MASK = true>
+template <int W6F, int L6, bool MASK = true>
 __device__ __forceinline__ void chain_forward(const uint4* s_ops, int lane, const float (*tabs)[TAB_FLOATS], int h,
                                               uint32_t keep, const float4& x, const f32x16& uacc, ChainKeep& k) {
   const f32x16 zero = {0};
-  if constexpr (!A2IN) {
-    bf16x8 a1[2];
-    asm volatile("" ::: "memory");
-    const f32x16 t1 = CH_MFMA(lds_op(s_ops, OP_W1, lane), pack_x(x), bias_acc(tabs[0], T_B6, h));
-    act_fold<MASK>(t1, keep, a1);
-    const f32x16 t2 = mm32_lds(s_ops, OP_W2, lane, a1, bias_acc(tabs[1], T_B6, h));
-    act_fold<MASK>(t2, keep, k.a2);
-  }
+  bf16x8 a1[2];
+  asm volatile("" ::: "memory");
+  const f32x16 t1 = CH_MFMA(lds_op(s_ops, OP_W1, lane), pack_x(x), bias_acc(tabs[0], T_B6, h));
+  act_fold<MASK>(t1, keep, a1);
+  const f32x16 t2 = mm32_lds(s_ops, OP_W2, lane, a1, bias_acc(tabs[1], T_B6, h));
+  act_fold<MASK>(t2, keep, k.a2);
   k.z5 = mm32_lds(s_ops, OP_W5, lane, k.a2, uacc);
   act_pack<MASK>(k.z5, tabs[2], h, keep, k.a5);
   k.z6 = mm32_lds(s_ops, OP_W6, lane, k.a5, zero);
@@ -122,10 +118,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && LPR <= 8) ? 4 : 3) void att
     const int32_t* __restrict__ n_tiles_dev, const T* __restrict__ rows, const int32_t* __restrict__ row_idx,
     const int64_t* __restrict__ ptr, const float* __restrict__ gw, const float* __restrict__ gb,
     const T* __restrict__ gout, const T* __restrict__ out, float* __restrict__ dc_out,
-    uint32_t* __restrict__ rec, float* __restrict__ gwb, int scaling, float eps, int64_t V, int64_t N, int64_t R,
-    const int32_t* __restrict__ rec_pos = nullptr) {
-  // rec_pos (nullable, 16-byte records only): the record of view v goes to slot rec_pos[v] (= its position in the row
-  // plan: dva_plan_inverse) instead of slot v -- the rows-gradient pass then streams the records (A/B of round 4)
+    uint32_t* __restrict__ rec, float* __restrict__ gwb, int scaling, float eps, int64_t V, int64_t N, int64_t R) {
   constexpr int VEC = 16 / (int)sizeof(T), C = LPR * VEC, ROWS = 64 / LPR, KV = 32 / ROWS;
   constexpr uint32_t RB = C * sizeof(T);       // bytes of a value / gradient row
   constexpr bool F32 = sizeof(T) == 4;
@@ -351,9 +344,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && LPR <= 8) ? 4 : 3) void att
     } else {   // 16-byte record: the rows gradient is rounded to bf16 anyway, its weights travel as bf16
       // word 3 = the view's row key: the split plan (plan_split.hip) sorts the records themselves by it
       const u32x4 r = {(uint32_t)p.vpj, pack_bf16x2(ga4[0], ga4[1]), pack_bf16x2(ga4[2], ga4[3]), (uint32_t)p.rij};
-      uint32_t slot = vg;
-      if (rec_pos) slot = wr ? (uint32_t)rec_pos[vg] : 0u;       // (uniform branch: a kernel argument)
-      st128(RC, wr ? slot * 16u : OOB, r);
+      st128(RC, wr ? vg * 16u : OOB, r);
     }
     wave_sync();
   });
@@ -413,14 +404,14 @@ __device__ __forceinline__ void dkeys_operand(const float4& dcv, __amdgpu_buffer
   dkp[1] = pack8(&d[8]);
 }
 
-template <bool KEYS, bool A2IN = false>
+template <bool KEYS>
 __global__ __launch_bounds__(256, 3) void score_stats_kernel(
     const float* __restrict__ x_map, const int32_t* __restrict__ vp, const float* __restrict__ u,
     const int2* __restrict__ tiles, const int32_t* __restrict__ n_tiles_dev, const uint4* __restrict__ ops,
     const float* __restrict__ bn1, const float* __restrict__ bn2, const float* __restrict__ bn5,
     const float* __restrict__ bn6, const float* __restrict__ dc, double* __restrict__ stats6,
     float* __restrict__ dWs, float* __restrict__ dbs, int G, int64_t V, int64_t N, const float* __restrict__ qp,
-    float qscale, const bf16_t* __restrict__ a2buf = nullptr) {
+    float qscale) {
   constexpr int L_W6F = 7, L_WST = 9, NOPS = KEYS ? 11 : 10;
   __shared__ __attribute__((aligned(16))) float s_tab[4][TAB_FLOATS];
   __shared__ __attribute__((aligned(16))) uint4 s_ops[NOPS * 64];
@@ -433,22 +424,17 @@ __global__ __launch_bounds__(256, 3) void score_stats_kernel(
   for (int i = threadIdx.x; i < 4 * 64; i += blockDim.x) s_ops[OP_W5 * 64 + i] = ops[OP_W5 * 64 + i];   // W5, W6
   for (int i = threadIdx.x; i < (KEYS ? 128 : 64); i += blockDim.x)
     s_ops[L_WST * 64 + i] = ops[(KEYS ? OP_WKT : OP_WST) * 64 + i];
-  if (!A2IN) {
-    fold_ops(s_ops, OP_W1, ops, OP_W1, 1, bn1);
-    fold_ops(s_ops, OP_W2, ops, OP_W2, 2, bn2);
-  }
+  fold_ops(s_ops, OP_W1, ops, OP_W1, 1, bn1);
+  fold_ops(s_ops, OP_W2, ops, OP_W2, 2, bn2);
   fold_ops(s_ops, L_W6F, ops, OP_W6, 2, bn6);
-  if (!A2IN) {
-    stage_tab(s_tab[0], bn1, nullptr);
-    stage_tab(s_tab[1], bn2, nullptr);
-  }
+  stage_tab(s_tab[0], bn1, nullptr);
+  stage_tab(s_tab[1], bn2, nullptr);
   stage_tab(s_tab[2], bn5, nullptr);
   stage_tab(s_tab[3], bn6, nullptr);
   __syncthreads();
-  const __amdgpu_buffer_rsrc_t X = make_rsrc(x_map, A2IN ? 0 : (uint64_t)V * 32), P = make_rsrc(vp, (uint64_t)V * 4),
+  const __amdgpu_buffer_rsrc_t X = make_rsrc(x_map, (uint64_t)V * 32), P = make_rsrc(vp, (uint64_t)V * 4),
                                U = make_rsrc(u, (uint64_t)N * 128), DC = make_rsrc(dc, (uint64_t)V * 16),
-                               QP = make_rsrc(qp, KEYS ? (uint64_t)N * 128 : 0),
-                               A2 = make_rsrc(a2buf, A2IN ? (uint64_t)V * 64 : 0);
+                               QP = make_rsrc(qp, KEYS ? (uint64_t)N * 128 : 0);
   bf16_t* tc = s_tc[wv];
   bf16_t* td = s_td[wv];
   f32x16 accS = {0};
@@ -462,7 +448,6 @@ __global__ __launch_bounds__(256, 3) void score_stats_kernel(
   struct Pre {
     TileInfo ti;
     float4 x, dc;
-    u32x4 alo, ahi;
     int vpj;
   };
   run_tiles<Pre>(tiles, ta, tb, [&](const TileInfo& ti, int t) {
@@ -470,12 +455,7 @@ __global__ __launch_bounds__(256, 3) void score_stats_kernel(
     p.ti = ti;
     const bool ok = j < p.ti.nv;
     const uint32_t view = (uint32_t)(p.ti.v0 + j);
-    if constexpr (A2IN) {
-      p.alo = ld128(A2, ok ? view * 64u + 32u * h : OOB);
-      p.ahi = ld128(A2, ok ? view * 64u + 32u * h + 16u : OOB);
-    } else {
-      p.x = as_f4(ld128(X, ok ? view * 32u + 16u * h : OOB));
-    }
+    p.x = as_f4(ld128(X, ok ? view * 32u + 16u * h : OOB));
     p.vpj = (int)ld32(P, ok ? view * 4u : OOB);
     p.dc = as_f4(ld128(DC, ok && (KEYS || h == 0) ? view * 16u : OOB));      // KEYS: both halves need the four groups
     return p;
@@ -484,13 +464,9 @@ __global__ __launch_bounds__(256, 3) void score_stats_kernel(
     const uint32_t keep = ok ? 0xffffffffu : 0u;
     const f32x16 uacc = load_u(U, ok, p.vpj, h);
     ChainKeep k;
-    if constexpr (A2IN) {
-      k.a2[0] = __builtin_bit_cast(bf16x8, p.alo);
-      k.a2[1] = __builtin_bit_cast(bf16x8, p.ahi);
-    }
     // unmasked activations: the score gradients (KEYS: the dK operand) of a lane without a view are zero, so dy6 is, and
     // the a6 / z6 garbage of such a lane meets a zero in every product and sum below
-    chain_forward<L_W6F, 2, A2IN, false>(s_ops, lane, s_tab, h, keep, p.x, uacc, k);
+    chain_forward<L_W6F, 2, false>(s_ops, lane, s_tab, h, keep, p.x, uacc, k);
     if constexpr (KEYS) {
       // dK of the view as the packed B operand (zeros for lanes without a view)
       bf16x8 dkp[2];
@@ -556,268 +532,6 @@ __global__ __launch_bounds__(256, 3) void score_stats_kernel(
                                                            (s_red[8 + threadIdx.x] + s_red[12 + threadIdx.x]));
 }
 
-// column sums of natural tiles this wavefront has just written: lane (n, hh) receives 16 of the 32 views of image column
-// n through the transpose read; two registers per statistic pair instead of 32 per-lane accumulators (merged stage 5)
-__device__ __forceinline__ void col_sums_xy(const bf16_t* tx, const bf16_t* ty, int lane, float& sx, float& sxy) {
-  // packed bf16 pairs straight into v_dot2c_f32_bf16 (fp32 accumulation): four dot products per eight values for
-  // sum x y, four against a pair of ones for sum x -- no unpacking
-  const uint32_t ones = 0x3f803f80u;
-#pragma unroll
-  for (int m = 0; m < 2; ++m) {
-    const u32x4 x = __builtin_bit_cast(u32x4, tileN_get(tx, lane, m)), y = __builtin_bit_cast(u32x4, tileN_get(ty, lane, m));
-    const uint32_t xx[4] = {x.x, x.y, x.z, x.w}, yy[4] = {y.x, y.y, y.z, y.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      sx = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, xx[i]), __builtin_bit_cast(bf16x2_t, ones), sx, false);
-      sxy = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, xx[i]), __builtin_bit_cast(bf16x2_t, yy[i]), sxy, false);
-    }
-  }
-}
-// the two halves of the column sums (lanes n and n + 32) -> fp64 atomics in a fixed per-block order; column n of a
-// natural tile = channel cperm(n).  s_red: 4 x 2 x 32 floats.
-__device__ __forceinline__ void flush_col_stats(float v0, float v1, double* __restrict__ out, float* s_red) {
-  const int wv = threadIdx.x >> 6, n = threadIdx.x & 31;
-  {
-    uint32_t a = __float_as_uint(v0), b = a;
-    swap_halves(a, b);
-    v0 += __uint_as_float((threadIdx.x & 32) ? a : b);
-    uint32_t c = __float_as_uint(v1), d = c;
-    swap_halves(c, d);
-    v1 += __uint_as_float((threadIdx.x & 32) ? c : d);
-  }
-  __syncthreads();
-  if ((threadIdx.x & 32) == 0) {
-    s_red[(wv * 2 + 0) * 32 + n] = v0;
-    s_red[(wv * 2 + 1) * 32 + n] = v1;
-  }
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    const int which = threadIdx.x >> 5;
-    double acc = 0.0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) acc += (double)s_red[(w * 2 + which) * 32 + n];
-    atomicAdd(&out[which * D + cperm(n)], acc);
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Merged backward (round 5): the score pass ALSO produces what stage 6 existed for -- the statistics S5 of the
-// BatchNorm-5 backward -- so that stage 6 disappears and stage 5 starts from the score gradients.
-//   dz6 = G6 dy6 - K1 - K2 z6 is linear in the two constants this very pass is still summing (K1, K2 per channel from
-//   S6), so S5 = sum_v dy5 | sum_v dy5 z5 with dy5 = m5 (W6^T dz6), m5 = leaky'(y5) in {1, 0.2}, splits into
-//     S5a[c] = e1[c] - n5[c] sum_j W6[j][c] K1[j] - sum_j W6[j][c] K2[j] P2[c][j]
-//     S5b[c] = e2[c] - q5[c] sum_j W6[j][c] K1[j] - sum_j W6[j][c] K2[j] Q2[c][j]
-//   with the sums this kernel accumulates per view from quantities it has in registers anyway:
-//     e = W6^T (G6 dy6)  (one more product),  e1 = sum m5 e,  e2 = sum (m5 z5) e,  n5 = sum m5,  q5 = sum m5 z5  (vectors),
-//     P2[c][j] = sum_v m5[c] z6[j],  Q2[c][j] = sum_v (m5 z5)[c] z6[j]   (two 32 x 32 products over natural LDS tiles).
-//   l6_consts_kernel finishes S5 once S6 is complete.  Stage 5 (layer_bwd_kernel<5, ., false, true>) then evaluates
-//   dy6 -> dz6 -> da5 -> dy5 itself (three more products on idle matrix cores; it reads 16 bytes of score gradients per
-//   view instead of the 64-byte dy5 row) and takes dW6 along.  Gone: one chain evaluation, the [V, 32] bf16 dy5 tensor
-//   (2.1 GB written + read), one launch.  Roundings: the operands of the new products are bf16 like every other
-//   weight-gradient operand (sums over all views: unbiased, they average out); S5 is no longer the sum of the very dy5
-//   values stage 5 uses but of the same expression before its bf16 operand rounding -- a difference of 2^-9 / sqrt(V)
-//   relative in the subtracted means.
-// acc5 fp32 [2][32][32] = P2 | Q2 (channel indices, caller-zeroed), vec5 fp64 [4][32] = e1 | e2 | n5 | q5 (caller-zeroed).
-// LDS operand table: chain positions 0..6 (W1', W2', W5, W6), 7..8 = W6' (folded), 9 = Ws^T, 10..11 = W6^T.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256, 3) void score_l6_kernel(
-    const float* __restrict__ x_map, const int32_t* __restrict__ vp, const float* __restrict__ u,
-    const int2* __restrict__ tiles, const int32_t* __restrict__ n_tiles_dev, const uint4* __restrict__ ops,
-    const float* __restrict__ bn1, const float* __restrict__ bn2, const float* __restrict__ bn5,
-    const float* __restrict__ bn6, const float* __restrict__ dc, double* __restrict__ stats6,
-    float* __restrict__ dWs, float* __restrict__ dbs, float* __restrict__ acc5, double* __restrict__ vec5, int G,
-    int64_t V, int64_t N) {
-  constexpr int L_W6F = 7, L_WST = 9, L_W6T = 10, NOPS = 12;
-  __shared__ __attribute__((aligned(16))) float s_tab[4][TAB_FLOATS];
-  __shared__ __attribute__((aligned(16))) uint4 s_ops[NOPS * 64];
-  // THREE natural tile buffers per wavefront, used in turn (the LDS budget of three blocks per CU), and the 4-row
-  // transposed score-gradient tile (+ one zero row).  Every vector statistic is a column sum of such tiles (two registers
-  // per pair, col_sums_xy) instead of 16 per-lane accumulators: the register budget of three wavefronts per SIMD.
-  __shared__ __attribute__((aligned(16))) bf16_t s_t0[4][32 * TSB], s_t1[4][32 * TSB], s_t2[4][32 * TSB], s_td[4][5 * TSB];
-  float* s_red = reinterpret_cast<float*>(&s_t0[0][0]);        // epilogue only
-  static_assert(sizeof(bf16_t) * 4 * 32 * TSB >= sizeof(float) * D * D, "epilogue buffer");
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
-  for (int i = threadIdx.x; i < 4 * 5 * TSB; i += blockDim.x) (&s_td[0][0])[i] = 0;
-  for (int i = threadIdx.x; i < 4 * 64; i += blockDim.x) s_ops[OP_W5 * 64 + i] = ops[OP_W5 * 64 + i];   // W5, W6
-  for (int i = threadIdx.x; i < 64; i += blockDim.x) s_ops[L_WST * 64 + i] = ops[OP_WST * 64 + i];
-  for (int i = threadIdx.x; i < 2 * 64; i += blockDim.x) s_ops[L_W6T * 64 + i] = ops[OP_W6T * 64 + i];
-  fold_ops(s_ops, OP_W1, ops, OP_W1, 1, bn1);
-  fold_ops(s_ops, OP_W2, ops, OP_W2, 2, bn2);
-  fold_ops(s_ops, L_W6F, ops, OP_W6, 2, bn6);
-  stage_tab(s_tab[0], bn1, nullptr);
-  stage_tab(s_tab[1], bn2, nullptr);
-  stage_tab(s_tab[2], bn5, nullptr);
-  stage_tab(s_tab[3], bn6, nullptr);
-  __syncthreads();
-  const __amdgpu_buffer_rsrc_t X = make_rsrc(x_map, (uint64_t)V * 32), P = make_rsrc(vp, (uint64_t)V * 4),
-                               U = make_rsrc(u, (uint64_t)N * 128), DC = make_rsrc(dc, (uint64_t)V * 16);
-  bf16_t* b0 = s_t0[wv];
-  bf16_t* b1 = s_t1[wv];
-  bf16_t* b2 = s_t2[wv];
-  bf16_t* td = s_td[wv];
-  f32x16 accS = {0}, accP = {0}, accQ = {0};
-  float dbsum[4] = {0.f, 0.f, 0.f, 0.f};
-  float s6a = 0.f, s6b = 0.f, n5 = 0.f, e1 = 0.f, q5 = 0.f, e2 = 0.f;       // column sums (lane = image column, half)
-  const int n_tiles = n_tiles_dev[0];
-  int ta, tb;
-  wave_tile_range(tiles, n_tiles, ta, tb);
-  struct Pre {
-    TileInfo ti;
-    float4 x, dc;
-    int vpj;
-  };
-  run_tiles_single<Pre>(tiles, ta, tb, [&](const TileInfo& ti, int t) {
-    Pre p;
-    p.ti = ti;
-    const bool ok = j < p.ti.nv;
-    const uint32_t view = (uint32_t)(p.ti.v0 + j);
-    p.x = as_f4(ld128(X, ok ? view * 32u + 16u * h : OOB));
-    p.vpj = (int)ld32(P, ok ? view * 4u : OOB);
-    p.dc = as_f4(ld128(DC, ok && h == 0 ? view * 16u : OOB));
-    return p;
-  }, [&](const Pre& p) {
-    const bool ok = j < p.ti.nv;
-    const uint32_t keep = ok ? 0xffffffffu : 0u;
-    const f32x16 uacc = load_u(U, ok, p.vpj, h);
-    ChainKeep k;
-    chain_forward<L_W6F, 2>(s_ops, lane, s_tab, h, keep, p.x, uacc, k);
-    const float dc4[4] = {p.dc.x, p.dc.y, p.dc.z, p.dc.w};      // zeros in the lanes without a view and for h = 1
-    // ---- phase 1: b0 = a6, td = dc (score-weight gradient); b1 = z6, b2 = dy6 (S6 as column sums of the rounded values)
-    tileN_put_packed(b0, j, h, k.a6);
-    if (h == 0) {
-      const uint32_t d01 = pack_bf16x2(dc4[0], dc4[1]), d23 = pack_bf16x2(dc4[2], dc4[3]);
-      td[0 * TSB + j] = (bf16_t)(d01 & 0xffffu);
-      td[1 * TSB + j] = (bf16_t)(d01 >> 16);
-      td[2 * TSB + j] = (bf16_t)(d23 & 0xffffu);
-      td[3 * TSB + j] = (bf16_t)(d23 >> 16);
-#pragma unroll
-      for (int g = 0; g < 4; ++g) dbsum[g] += dc4[g];
-    }
-    f32x16 dy6 = score_bwd<L_WST>(s_ops, lane, dc4, h);
-    dleaky_mul(k.t6, dy6);
-    f32x16 e;
-    {
-      // z6 and dy6 tiles (zeros for lanes without a view: a5 is masked and dc reads 0); G6 dy6 as the operand of
-      // e = W6^T (G6 dy6); constants four channels at a time
-      float t16[16], gd[16];
-      asm volatile("" ::: "memory");
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float4 g4 = *reinterpret_cast<const float4*>(s_tab[3] + T_G * D + 16 * h + 4 * q);
-        const float g[4] = {g4.x, g4.y, g4.z, g4.w};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          t16[4 * q + c] = dy6[4 * q + c];
-          gd[4 * q + c] = dy6[4 * q + c] * g[c];
-        }
-      }
-      bf16x8 pk[2];
-      pack16(t16, 0xffffffffu, pk);
-      tileN_put_packed(b2, j, h, pk);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) t16[r] = k.z6[r];
-      pack16(t16, 0xffffffffu, pk);
-      tileN_put_packed(b1, j, h, pk);
-      pack16(gd, 0xffffffffu, pk);
-      const f32x16 zero = {0};
-      e = mm32_lds(s_ops, L_W6T, lane, pk, zero);
-    }
-    wave_sync();
-    accS = wgradN_T(b0, td, lane, j, 4, h, accS);
-    col_sums_xy(b2, b1, lane, s6a, s6b);                        // sum dy6 | sum dy6 z6
-    wave_sync();
-    // ---- phase 2: b0 = m5, b2 = m5 z5 (b1 = z6 stays): P2, Q2
-    {
-      const float one = ok ? 1.f : 0.f, low = ok ? SLOPE : 0.f;
-      float m16[16], q16[16];
-      asm volatile("" ::: "memory");
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float4 g4 = *reinterpret_cast<const float4*>(s_tab[2] + T_G * D + 16 * h + 4 * q);
-        const float4 b4 = *reinterpret_cast<const float4*>(s_tab[2] + T_B * D + 16 * h + 4 * q);
-        const float g[4] = {g4.x, g4.y, g4.z, g4.w}, b[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const int r = 4 * q + c;
-          const float y5 = __builtin_fmaf(k.z5[r], g[c], b[c]);      // layer 5 is evaluated plain: sign of G5 z5 + B5
-          m16[r] = y5 > 0.f ? one : low;
-          q16[r] = m16[r] * k.z5[r];
-        }
-      }
-      bf16x8 mp[2], qp[2];
-      pack16(m16, 0xffffffffu, mp);
-      pack16(q16, 0xffffffffu, qp);
-      tileN_put_packed(b0, j, h, mp);
-      tileN_put_packed(b2, j, h, qp);
-    }
-    wave_sync();
-    {
-      const bf16x8 z0 = tileN_get(b1, lane, 0), z1 = tileN_get(b1, lane, 1);
-      accP = CH_MFMA(tileN_get(b0, lane, 0), z0, accP);       // P2[c][j] = sum_v m5[v][c] z6[v][j]
-      accP = CH_MFMA(tileN_get(b0, lane, 1), z1, accP);
-      accQ = CH_MFMA(tileN_get(b2, lane, 0), z0, accQ);       // Q2[c][j] = sum_v (m5 z5)[v][c] z6[v][j]
-      accQ = CH_MFMA(tileN_get(b2, lane, 1), z1, accQ);
-    }
-    wave_sync();
-    // ---- phase 3: b1 = e: n5 | e1 = sum m5 | sum m5 e,  q5 | e2 = sum m5 z5 | sum (m5 z5) e
-    {
-      float t16[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) t16[r] = e[r];
-      bf16x8 ep[2];
-      pack16(t16, 0xffffffffu, ep);
-      tileN_put_packed(b1, j, h, ep);
-    }
-    wave_sync();
-    col_sums_xy(b0, b1, lane, n5, e1);
-    col_sums_xy(b2, b1, lane, q5, e2);
-    wave_sync();
-  });
-  flush_matrix_nat(accS, dWs, D, G, true, s_red, false);
-  flush_matrix_nat(accP, acc5, D, D, false, s_red, true);
-  flush_matrix_nat(accQ, acc5 + D * D, D, D, false, s_red, true);
-  flush_col_stats(s6a, s6b, stats6, s_red);
-  flush_col_stats(e1, e2, vec5, s_red);
-  flush_col_stats(n5, q5, vec5 + 2 * D, s_red);
-  __syncthreads();       // dbs: one atomic per block and group (see the attention backward)
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    float v = dbsum[g];
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off);
-    if (lane == 0) s_red[wv * 4 + g] = v;
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < G) atomicAdd(&dbs[threadIdx.x], (s_red[threadIdx.x] + s_red[4 + threadIdx.x]) +
-                                                           (s_red[8 + threadIdx.x] + s_red[12 + threadIdx.x]));
-}
-
-// S5 (fp64 [64] = sum dy5 | sum dy5 z5, the form the layer passes accumulate) from the sums of score_l6_kernel once S6 is
-// complete: sm6 fp32 [64] = S1/M | S2_hat/M of layer 6 (dva_bn_bwd_consts), bn6 [4+][32], W6 fp32 [32][32] (rounded to
-// bf16 here like the operand of the W6^T product), acc5 = P2 | Q2, vec5 = e1 | e2 | n5 | q5.  One block of 32 threads.
-__global__ void l6_consts_kernel(const float* __restrict__ sm6, const float* __restrict__ bn6,
-                                 const float* __restrict__ W6, const float* __restrict__ acc5,
-                                 const double* __restrict__ vec5, double* __restrict__ s5) {
-  __shared__ double k1[D], k2[D];
-  const int c = threadIdx.x;
-  if (c < D) {
-    const double mean = bn6[c], inv = bn6[D + c], g = (double)bn6[2 * D + c] * inv;
-    const double s1 = sm6[c], s2 = sm6[D + c];
-    k1[c] = g * (s1 - mean * inv * s2);          // dz = G dy - K1 - K2 z (stage_tab)
-    k2[c] = g * inv * s2;
-  }
-  __syncthreads();
-  if (c >= D) return;
-  double t1 = 0.0, tp = 0.0, tq = 0.0;
-  for (int jj = 0; jj < D; ++jj) {
-    const double w = (double)bf2f(f2bf(W6[jj * D + c]));
-    t1 += w * k1[jj];
-    tp += w * k2[jj] * (double)acc5[c * D + jj];
-    tq += w * k2[jj] * (double)acc5[D * D + c * D + jj];
-  }
-  s5[c] = vec5[c] - vec5[2 * D + c] * t1 - tp;
-  s5[D + c] = vec5[D + c] - vec5[3 * D + c] * t1 - tq;
-}
-
 // ------------------------------------------------------------------------------------------------
 // layer passes.  STAGE 6: dz6 -> dW6, S5; hands dy5 = leaky'(y5) da5 (bf16 [V, 32]) to the next pass.
 // STAGE 5: dy5 -> dz5 -> dW5, du, S2 (view part); hands dy2 = leaky'(t2) da2 to the next pass.
@@ -849,10 +563,7 @@ __device__ __forceinline__ f32x16 unpack_da(const u32x4& lo, const u32x4& hi) {
   return d;
 }
 
-// MERGED (STAGE 5 only, round 5): no stage 6 ran -- the pass starts from the score gradients dc [V, 4] and the constants
-// of the BatchNorm-6 backward (sm6), evaluates dy6 -> dz6 -> da5 -> dy5 itself and takes dW6 along (written to `Pm`);
-// S5 came from score_l6_kernel + l6_consts_kernel.
-template <int STAGE, int OCC, bool KEYS = false, bool MERGED = false, bool A2IN = false>
+template <int STAGE, int OCC, bool KEYS = false>
 __global__ __launch_bounds__(256, OCC) void layer_bwd_kernel(
     const float* __restrict__ x_map, const int32_t* __restrict__ vp, const float* __restrict__ u,
     const int2* __restrict__ tiles, const int32_t* __restrict__ n_tiles_dev, const uint4* __restrict__ ops,
@@ -862,9 +573,7 @@ __global__ __launch_bounds__(256, OCC) void layer_bwd_kernel(
     const float* __restrict__ dpooled, const bf16_t* __restrict__ da_in, bf16_t* __restrict__ da_out,
     float* __restrict__ dW,
     float* __restrict__ du, float* __restrict__ Pm, double* __restrict__ stats, int G, int64_t V, int64_t N,
-    const float* __restrict__ qp, float qscale, const bf16_t* __restrict__ a2buf = nullptr) {
-  static_assert(!A2IN || STAGE == 6, "the stored a2 row replaces x_map in stage 6 only (stages 5, 2 need layers 1-2)");
-  constexpr bool A2_PREFETCH = false;     // the row is loaded in the body: a second prefetch set of it spills (56 bytes of scratch)
+    const float* __restrict__ qp, float qscale) {
   __shared__ __attribute__((aligned(16))) float s_tab[4][TAB_FLOATS];
   __shared__ __attribute__((aligned(16))) bf16_t s_ta[4][32 * TSB], s_tb[4][32 * TSB];
   // second operand tile of the small products: 4 (score gradients) / 17 (x_map hi | lo | ones) rows + one shared zero row
@@ -883,11 +592,8 @@ __global__ __launch_bounds__(256, OCC) void layer_bwd_kernel(
   // place, W2 as a second operand (the raw z2 feeds the statistics) -> local 7, 8; stage 2: W1 as a second operand
   // -> local 5
   // stage 6: W1' W2' W5 W6 at their table positions 0..6, then W6T -> 7, 8; WST -> 9; W6' (folded) -> 10, 11
-  static_assert(!MERGED || STAGE == 5, "the merged form is a stage-5 instance");
-  constexpr int NOPS = STAGE == 6 ? (KEYS ? 13 : 12) : (STAGE == 5 ? (MERGED ? 16 : 9) : 6);      // (KEYS: W_k^T takes two blocks at L6_WST, the folded W6 moves up one)
+  constexpr int NOPS = STAGE == 6 ? (KEYS ? 13 : 12) : (STAGE == 5 ? 9 : 6);      // (KEYS: W_k^T takes two blocks at L6_WST, the folded W6 moves up one)
   constexpr int L_W5T = 5, L_W2T = 3, L_W2F = 7, L_W1F = 5, L6_W6T = 7, L6_WST = 9, L6_W6F = KEYS ? 11 : 10;
-  // merged stage 5: W6 -> 9, 10; W6' (folded) -> 11, 12; W6^T -> 13, 14; Ws^T -> 15
-  constexpr int L5_W6 = 9, L5_W6F = 11, L5_W6T = 13, L5_WST = 15;
   __shared__ __attribute__((aligned(16))) uint4 s_ops[NOPS * 64];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
   if (STAGE == 6) {
@@ -901,10 +607,8 @@ __global__ __launch_bounds__(256, OCC) void layer_bwd_kernel(
       for (int i = threadIdx.x; i < 2 * 64; i += blockDim.x) s_ops[L6_WST * 64 + i] = ops[OP_WKT * 64 + i];
     }
     for (int i = threadIdx.x; i < 2 * 64; i += blockDim.x) s_ops[L6_W6T * 64 + i] = ops[OP_W6T * 64 + i];
-    if (!A2IN) {
-      fold_ops(s_ops, OP_W1, ops, OP_W1, 1, bn1);
-      fold_ops(s_ops, OP_W2, ops, OP_W2, 2, bn2);
-    }
+    fold_ops(s_ops, OP_W1, ops, OP_W1, 1, bn1);
+    fold_ops(s_ops, OP_W2, ops, OP_W2, 2, bn2);
     fold_ops(s_ops, L6_W6F, ops, OP_W6, 2, bn6);
   } else {
     for (int i = threadIdx.x; i < (STAGE == 5 ? 7 : 5) * 64; i += blockDim.x) {
@@ -913,29 +617,18 @@ __global__ __launch_bounds__(256, OCC) void layer_bwd_kernel(
       if (STAGE == 2 && op >= 3) op = OP_W2T + (op - 3);
       s_ops[i] = ops[op * 64 + (i & 63)];
     }
-    if (MERGED) {
-      for (int i = threadIdx.x; i < 5 * 64; i += blockDim.x) {
-        const int blk = i >> 6, l = i & 63;
-        if (blk < 2) s_ops[(L5_W6 + blk) * 64 + l] = ops[(OP_W6 + blk) * 64 + l];
-        else if (blk < 4) s_ops[(L5_W6T + blk - 2) * 64 + l] = ops[(OP_W6T + blk - 2) * 64 + l];
-        else s_ops[L5_WST * 64 + l] = ops[OP_WST * 64 + l];
-      }
-    }
     __syncthreads();
     if (STAGE == 5) {
       fold_ops(s_ops, OP_W1, ops, OP_W1, 1, bn1);
       fold_ops(s_ops, L_W2F, ops, OP_W2, 2, bn2);
-      if (MERGED) fold_ops(s_ops, L5_W6F, ops, OP_W6, 2, bn6);
     } else {
       fold_ops(s_ops, L_W1F, ops, OP_W1, 1, bn1);
     }
   }
-  if (!A2IN) {
-    stage_tab(s_tab[0], bn1, nullptr);
-    stage_tab(s_tab[1], bn2, STAGE == 2 ? sm2 : nullptr);
-  }
+  stage_tab(s_tab[0], bn1, nullptr);
+  stage_tab(s_tab[1], bn2, STAGE == 2 ? sm2 : nullptr);
   stage_tab(s_tab[2], bn5, STAGE == 5 ? sm5 : nullptr);
-  stage_tab(s_tab[3], bn6, (STAGE == 6 || MERGED) ? sm6 : nullptr);
+  stage_tab(s_tab[3], bn6, STAGE == 6 ? sm6 : nullptr);
   // second operand tiles hold rows that are never rewritten (score gradients: rows >= 4, x_map: rows >= 8)
   for (int i = threadIdx.x; i < 4 * 32 * TSB; i += blockDim.x) {
     if (STAGE == 2) {
@@ -945,16 +638,14 @@ __global__ __launch_bounds__(256, OCC) void layer_bwd_kernel(
     }
   }
   __syncthreads();
-  const __amdgpu_buffer_rsrc_t X = make_rsrc(x_map, A2IN ? 0 : (uint64_t)V * 32), P = make_rsrc(vp, (uint64_t)V * 4),
+  const __amdgpu_buffer_rsrc_t X = make_rsrc(x_map, (uint64_t)V * 32), P = make_rsrc(vp, (uint64_t)V * 4),
                                U = make_rsrc(u, (uint64_t)N * 128), DC = make_rsrc(dc, (uint64_t)V * 16), QP = make_rsrc(qp, KEYS ? (uint64_t)N * 128 : 0),
                                AR = make_rsrc(arg, (uint64_t)N * 128), DP = make_rsrc(dpooled, (uint64_t)N * 128),
-                               DI = make_rsrc(da_in, (uint64_t)V * 64), DO = make_rsrc(da_out, (uint64_t)V * 64),
-                               A2 = make_rsrc(a2buf, A2IN ? (uint64_t)V * 64 : 0);
+                               DI = make_rsrc(da_in, (uint64_t)V * 64), DO = make_rsrc(da_out, (uint64_t)V * 64);
   float st[2][16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) st[0][r] = st[1][r] = 0.f;
-  float cs1 = 0.f, cs2 = 0.f;         // merged stage 5: S2 (view part) as column sums of natural tiles
-  f32x16 accW = {0}, accS = {0};      // layer weight gradient; P (STAGE 2) / dW6 (merged stage 5)
+  f32x16 accW = {0}, accS = {0};      // layer weight gradient; P (STAGE 2)
   bf16_t* ta = s_ta[wv];
   bf16_t* tb_ = s_tb[wv];
   bf16_t* tc = s_tc[STAGE == 2 ? wv : 0];
@@ -971,23 +662,12 @@ __global__ __launch_bounds__(256, OCC) void layer_bwd_kernel(
     u32x4 dlo, dhi;
     int vpj;
   };
-  auto loop = [&](auto&& load, auto&& body) {
-    if constexpr (MERGED) run_tiles_single<Pre>(tiles, t0, t1, load, body);      // one register set: the occupancy step
-    else run_tiles<Pre>(tiles, t0, t1, load, body);
-  };
-  loop([&](const TileInfo& ti, int t) {
+  run_tiles<Pre>(tiles, t0, t1, [&](const TileInfo& ti, int t) {
     Pre p;
     p.ti = ti;
     const bool ok = j < p.ti.nv;
     const uint32_t view = (uint32_t)(p.ti.v0 + j);
-    if constexpr (A2IN) {      // the stored layer-2 activation row instead of x_map
-      if constexpr (A2_PREFETCH) {      // (dlo | dhi are free in stage 6)
-        p.dlo = ld128(A2, ok ? view * 64u + 32u * h : OOB);
-        p.dhi = ld128(A2, ok ? view * 64u + 32u * h + 16u : OOB);
-      }
-    } else {
-      p.x = as_f4(ld128(X, ok ? view * 32u + 16u * h : OOB));
-    }
+    p.x = as_f4(ld128(X, ok ? view * 32u + 16u * h : OOB));
     p.vpj = (int)ld32(P, ok ? view * 4u : OOB);
     if (STAGE == 2) {
       p.dlo = ld128(DI, ok ? view * 64u + 32u * h : OOB);
@@ -1013,18 +693,10 @@ __global__ __launch_bounds__(256, OCC) void layer_bwd_kernel(
       {
         bf16x8 a1[2], a2[2];
         asm volatile("" ::: "memory");
-        if constexpr (A2IN && A2_PREFETCH) {
-          a2[0] = __builtin_bit_cast(bf16x8, p.dlo);
-          a2[1] = __builtin_bit_cast(bf16x8, p.dhi);
-        } else if constexpr (A2IN) {
-          a2[0] = __builtin_bit_cast(bf16x8, ld128(A2, ok ? view * 64u + 32u * h : OOB));
-          a2[1] = __builtin_bit_cast(bf16x8, ld128(A2, ok ? view * 64u + 32u * h + 16u : OOB));
-        } else {
-          const f32x16 t1 = CH_MFMA(lds_op(s_ops, OP_W1, lane), pack_x(p.x), bias_acc(s_tab[0], T_B6, h));
-          act_fold<false>(t1, keep, a1);
-          const f32x16 t2 = mm32_lds(s_ops, OP_W2, lane, a1, bias_acc(s_tab[1], T_B6, h));
-          act_fold<false>(t2, keep, a2);
-        }
+        const f32x16 t1 = CH_MFMA(lds_op(s_ops, OP_W1, lane), pack_x(p.x), bias_acc(s_tab[0], T_B6, h));
+        act_fold<false>(t1, keep, a1);
+        const f32x16 t2 = mm32_lds(s_ops, OP_W2, lane, a1, bias_acc(s_tab[1], T_B6, h));
+        act_fold<false>(t2, keep, a2);
         z5 = mm32_lds(s_ops, OP_W5, lane, a2, uacc);
         act_pack<false>(z5, s_tab[2], h, keep, a5);      // unmasked: dz6 below is (pack16), so da5 = dy5 = 0 without a view
       }
@@ -1058,14 +730,8 @@ __global__ __launch_bounds__(256, OCC) void layer_bwd_kernel(
       wave_sync();
     } else if constexpr (STAGE == 5) {
       f32x16 uacc = load_u(U, ok, p.vpj, h);
-      u32x4 dlo = {0, 0, 0, 0}, dhi = {0, 0, 0, 0};
-      float4 dcv = make_float4(0.f, 0.f, 0.f, 0.f);
-      if constexpr (MERGED) {
-        dcv = as_f4(ld128(DC, ok && h == 0 ? view * 16u : OOB));
-      } else {
-        dlo = ld128(DI, ok ? view * 64u + 32u * h : OOB);
-        dhi = ld128(DI, ok ? view * 64u + 32u * h + 16u : OOB);
-      }
+      const u32x4 dlo = ld128(DI, ok ? view * 64u + 32u * h : OOB);
+      const u32x4 dhi = ld128(DI, ok ? view * 64u + 32u * h + 16u : OOB);
       // forward up to layer 5
       bf16x8 a1[2], a2[2];
       asm volatile("" ::: "memory");
@@ -1073,55 +739,16 @@ __global__ __launch_bounds__(256, OCC) void layer_bwd_kernel(
       act_fold(t1, 0xffffffffu, a1);
       {
         const f32x16 t2 = mm32_lds(s_ops, L_W2F, lane, a1, bias_acc(s_tab[1], T_B6, h));
-        act_fold<MERGED>(t2, keep, a2);      // unmasked: dz5 is masked (pack16) before it meets a2 in the dW5 product
+        act_fold<false>(t2, keep, a2);      // unmasked: dz5 is masked (pack16) before it meets a2 in the dW5 product
       }
       {
         const f32x16 z5 = mm32_lds(s_ops, OP_W5, lane, a2, uacc);
-        f32x16 dy5;
-        if constexpr (MERGED) {
-          // what stage 6 did for this view: dy6 = leaky'(t6) Ws^T dc, dz6 = BatchNorm-6 backward, da5 = W6^T dz6,
-          // dy5 = leaky'(y5) da5 (fp32: no bf16 row in between); dW6 from the two natural tiles
-          bf16x8 a5[2];
-          act_pack(z5, s_tab[2], h, keep, a5);
-          const float dc4[4] = {dcv.x, dcv.y, dcv.z, dcv.w};
-          f32x16 dy6 = score_bwd<L5_WST>(s_ops, lane, dc4, h);
-          {
-            const f32x16 t6 = mm32_lds(s_ops, L5_W6F, lane, a5, bias_acc(s_tab[3], T_B6, h));
-            dleaky_mul(t6, dy6);
-          }
-          float dz6[16];
-          {
-            const f32x16 z6 = mm32_lds(s_ops, L5_W6, lane, a5, zero);
-            bn_bwd_apply(z6, dy6, s_tab[3], h, dz6);
-          }
-          bf16x8 dzp6[2];
-          pack16(dz6, keep, dzp6);
-          tileN_put_packed(ta, j, h, dzp6);
-          tileN_put_packed(tb_, j, h, a5);
-          const f32x16 da5 = mm32_lds(s_ops, L5_W6T, lane, dzp6, zero);
-          asm volatile("" ::: "memory");
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {        // four channels at a time: two float4 of constants live
-            const float4 g4 = *reinterpret_cast<const float4*>(s_tab[2] + T_G * D + 16 * h + 4 * q);
-            const float4 b4 = *reinterpret_cast<const float4*>(s_tab[2] + T_B * D + 16 * h + 4 * q);
-            const float g[4] = {g4.x, g4.y, g4.z, g4.w}, b[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const int r = 4 * q + e;
-              dy5[r] = __builtin_fmaf(z5[r], g[e], b[e]) > 0.f ? da5[r] : SLOPE * da5[r];
-            }
-          }
-          wave_sync();
-          accS = wgradN(ta, tb_, lane, accS);      // dW6[n][k] = sum_v dz6[v][n] a5[v][k]
-          wave_sync();
-        } else {
-          dy5 = unpack_da(dlo, dhi);           // stage 6 hands leaky'(y5) da5
-        }
+        const f32x16 dy5 = unpack_da(dlo, dhi);           // stage 6 hands leaky'(y5) da5
         bn_bwd_apply(z5, dy5, s_tab[2], h, dz);
       }
       pack16(dz, keep, dzp);
       tileN_put_packed(ta, j, h, dzp);
-      if constexpr (!MERGED) tileN_put_packed(tb_, j, h, a2);      // (merged: a2 is packed again below, see there)
+      tileN_put_packed(tb_, j, h, a2);
       // du[p][c] = sum of dz5 over the views of point p = dz5^T . indicator: one more product on the matrix cores
       // (operands: the transposed dz5 tile and a [local point][view] indicator tile of 1.0 / 0)
       const int prv = shfl(p.vpj, lane - 1);
@@ -1138,15 +765,9 @@ __global__ __launch_bounds__(256, OCC) void layer_bwd_kernel(
         // layer 2 was evaluated folded: leaky' follows the sign of t2 (evaluated again here: a1 is 8 registers, t2 16)
         const f32x16 t2 = mm32_lds(s_ops, L_W2F, lane, a1, bias_acc(s_tab[1], T_B6, h));
         dleaky_mul(t2, dy2);
-        if constexpr (MERGED) {
-          // the a2 operand of the dW5 product from the same t2: 8 registers that do not live across the layer-6 block
-          bf16x8 a2b[2];
-          act_fold(t2, keep, a2b);
-          tileN_put_packed(tb_, j, h, a2b);
-        }
       }
-      if constexpr (!MERGED) {
-        store_da(DO, ok, view, h, dy2);
+      store_da(DO, ok, view, h, dy2);
+      {
         const f32x16 z2 = mm32_lds(s_ops, OP_W2, lane, a1, zero);     // the raw output: sum dy2 z2
         bn_bwd_stats(z2, dy2, st);
       }
@@ -1155,31 +776,6 @@ __global__ __launch_bounds__(256, OCC) void layer_bwd_kernel(
       const int frag = p.ti.frag;
       const f32x16 accU = wgradN_T(ta, ind, lane, j, 32, h, zero);      // du[image column][local point j] of this tile
       if (h == 0 && ok) ind[lpj * TSB + j] = 0;           // leave the indicator tile clean for the next tile
-      if constexpr (MERGED) {
-        // the row that is handed over (bf16) and the raw z2 as natural tiles in the buffers the products have just read:
-        // S2 = sum dy2 | sum dy2 z2 through column sums -- two registers instead of the 32 per-lane accumulators
-        // (the third wavefront per SIMD of this instance); statistics of the rounded values
-        wave_sync();
-        float t16[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) t16[r] = dy2[r];
-        bf16x8 dyp[2];
-        pack16(t16, keep, dyp);
-        const uint32_t off = ok ? view * 64u + 32u * h : OOB;
-        st128(DO, off, __builtin_bit_cast(u32x4, dyp[0]));
-        st128(DO, ok ? off + 16u : OOB, __builtin_bit_cast(u32x4, dyp[1]));
-        tileN_put_packed(ta, j, h, dyp);
-        {
-          const f32x16 z2 = mm32_lds(s_ops, OP_W2, lane, a1, zero);
-#pragma unroll
-          for (int r = 0; r < 16; ++r) t16[r] = z2[r];
-          bf16x8 zp[2];
-          pack16(t16, keep, zp);
-          tileN_put_packed(tb_, j, h, zp);
-        }
-        wave_sync();
-        col_sums_xy(ta, tb_, lane, cs1, cs2);
-      }
       {
         const bool wr = j < nseg;
         const uint32_t pt = wr ? (uint32_t)plp[j] : 0u;
@@ -1270,9 +866,7 @@ __global__ __launch_bounds__(256, OCC) void layer_bwd_kernel(
     }
   });
   flush_matrix_nat(accW, dW, STAGE == 5 ? 2 * D : D, D, false, s_red, true);
-  if (MERGED) flush_matrix_nat(accS, Pm, D, D, false, s_red, true);          // dW6
   if (STAGE == 2) flush_matrix_nat(accS, Pm, 20, 17, false, s_red, false);
-  else if (MERGED) flush_col_stats(cs1, cs2, stats, s_red);
   else flush_stats<2>(st, stats, s_red);
 }
 
@@ -1409,7 +1003,7 @@ using namespace dva::chain;
 
 extern "C" {
 
-static int chain_attn_bwd_impl(const int32_t* rec_pos, const float* scores, const int32_t* view_point, const void* tiles, const int32_t* n_tiles,
+static int chain_attn_bwd_impl(const float* scores, const int32_t* view_point, const void* tiles, const int32_t* n_tiles,
                        const void* rows, const int32_t* row_idx, const int64_t* ptr, const float* gate_w,
                        const float* gate_b, const void* grad_out, const void* out, float* grad_scores, void* view_rec,
                        float* grad_gate_wb, int64_t n_points, int64_t n_views, int64_t n_rows, int32_t C, int32_t G,
@@ -1428,7 +1022,7 @@ static int chain_attn_bwd_impl(const int32_t* rec_pos, const float* scores, cons
   hipLaunchKernelGGL((attn_bwd_kernel<T_, LPR_, G_>), grid, block, 0, s, scores, view_point,                      \
                      (const int2*)tiles, n_tiles, (const T_*)rows, row_idx, ptr, gate_w, gate_b,                  \
                      (const T_*)grad_out, (const T_*)out, grad_scores, (uint32_t*)view_rec, grad_gate_wb,         \
-                     scaling, eps, n_views, n_points, n_rows, rec_pos)
+                     scaling, eps, n_views, n_points, n_rows)
 #define DVA_ATTN_BWD(LPR_, G_)                                                                                    \
   do {                                                                                                            \
     if (dtype == DVA_F16) DVA_ATTN_BWD_T(f16_t, LPR_, G_);                                                        \
@@ -1464,7 +1058,7 @@ int dva_chain_attn_bwd(const float* scores, const int32_t* view_point, const voi
                        const float* gate_b, const void* grad_out, const void* out, float* grad_scores, void* view_rec,
                        float* grad_gate_wb, int64_t n_points, int64_t n_views, int64_t n_rows, int32_t C, int32_t G,
                        int32_t scaling, float eps, void* stream) {
-  return chain_attn_bwd_impl(nullptr, scores, view_point, tiles, n_tiles, rows, row_idx, ptr, gate_w, gate_b, grad_out, out,
+  return chain_attn_bwd_impl(scores, view_point, tiles, n_tiles, rows, row_idx, ptr, gate_w, gate_b, grad_out, out,
                              grad_scores, view_rec, grad_gate_wb, n_points, n_views, n_rows, C, G, scaling, eps, DVA_BF16,
                              stream);
 }
@@ -1474,19 +1068,8 @@ int dva_chain_attn_bwd_dt(const float* scores, const int32_t* view_point, const 
                           const float* gate_b, const void* grad_out, const void* out, float* grad_scores, void* view_rec,
                           float* grad_gate_wb, int64_t n_points, int64_t n_views, int64_t n_rows, int32_t C, int32_t G,
                           int32_t scaling, float eps, int32_t dtype, void* stream) {
-  return chain_attn_bwd_impl(nullptr, scores, view_point, tiles, n_tiles, rows, row_idx, ptr, gate_w, gate_b, grad_out, out,
+  return chain_attn_bwd_impl(scores, view_point, tiles, n_tiles, rows, row_idx, ptr, gate_w, gate_b, grad_out, out,
                              grad_scores, view_rec, grad_gate_wb, n_points, n_views, n_rows, C, G, scaling, eps, dtype,
-                             stream);
-}
-
-int dva_chain_attn_bwd_planrec(const int32_t* rec_pos, const float* scores, const int32_t* view_point, const void* tiles,
-                               const int32_t* n_tiles, const void* rows, const int32_t* row_idx, const int64_t* ptr,
-                               const float* gate_w, const float* gate_b, const void* grad_out, const void* out,
-                               float* grad_scores, void* view_rec, float* grad_gate_wb, int64_t n_points, int64_t n_views,
-                               int64_t n_rows, int32_t C, int32_t G, int32_t scaling, float eps, void* stream) {
-  if (!rec_pos && n_views > 0) return DVA_ERR_INVALID;
-  return chain_attn_bwd_impl(rec_pos, scores, view_point, tiles, n_tiles, rows, row_idx, ptr, gate_w, gate_b, grad_out, out,
-                             grad_scores, view_rec, grad_gate_wb, n_points, n_views, n_rows, C, G, scaling, eps, DVA_BF16,
                              stream);
 }
 
@@ -1546,48 +1129,6 @@ int dva_chain_score_stats(const float* x_map, const int32_t* view_point, const f
   return DVA_OK;
 }
 
-// The stored-a2 hybrid (round 6): the same pass starting from the layer-2 activation row the forward stored
-// (dva_chain_stats_a2(5): bf16 [V, 32], accumulator order) instead of x_map -- 64 instead of 32 bytes per view in, layers 1
-// and 2 not evaluated.  Same results bit for bit (the row IS the operand layer 5 consumes).
-int dva_chain_score_stats_a2(const void* a2, const int32_t* view_point, const float* u, const void* tiles,
-                             const int32_t* n_tiles, const void* ops, const float* bn5, const float* bn6,
-                             const float* grad_scores, double* stats6, float* dWs, float* dbs, int32_t G,
-                             int64_t n_views, int64_t n_points, void* stream) {
-  if (n_views < 0 || n_points < 0 || G < 1 || G > 4) return DVA_ERR_INVALID;
-  if (n_views == 0) return DVA_OK;
-  if (!a2 || !view_point || !u || !tiles || !n_tiles || !ops || !bn5 || !bn6 || !grad_scores || !stats6 || !dWs ||
-      !dbs || ((uintptr_t)a2 & 15))
-    return DVA_ERR_INVALID;
-  if (n_views * 64 > 0xfffffff0ll || n_points * 128 > 0xfffffff0ll) return DVA_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL((score_stats_kernel<false, true>), dim3(chain_grid(3)), dim3(256), 0, (hipStream_t)stream,
-                     (const float*)nullptr, view_point, u, (const int2*)tiles, n_tiles, (const uint4*)ops,
-                     (const float*)nullptr, (const float*)nullptr, bn5, bn6, grad_scores, stats6, dWs, dbs, (int)G,
-                     n_views, n_points, (const float*)nullptr, 0.f, (const bf16_t*)a2);
-  DVA_CHECK_LAUNCH();
-  return DVA_OK;
-}
-
-// stage 6 of dva_chain_bwd_layer from the stored a2 row: dW6, dy5 (da_out bf16 [V, 32]), S of layer 5
-int dva_chain_bwd_layer6_a2(const void* a2, const int32_t* view_point, const float* u, const void* tiles,
-                            const int32_t* n_tiles, const void* ops, const float* bn5, const float* bn6,
-                            const float* sm6, const float* grad_scores, void* da_out, float* dW, double* stats,
-                            int32_t G, int64_t n_views, int64_t n_points, void* stream) {
-  if (n_views < 0 || n_points < 0 || G < 1 || G > 4) return DVA_ERR_INVALID;
-  if (n_views == 0) return DVA_OK;
-  if (!a2 || !view_point || !u || !tiles || !n_tiles || !ops || !bn5 || !bn6 || !sm6 || !grad_scores || !da_out ||
-      !dW || !stats || ((uintptr_t)a2 & 15))
-    return DVA_ERR_INVALID;
-  if (n_views * 64 > 0xfffffff0ll || n_points * 128 > 0xfffffff0ll) return DVA_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL((layer_bwd_kernel<6, 3, false, false, true>), dim3(chain_grid(3)), dim3(256), 0,
-                     (hipStream_t)stream, (const float*)nullptr, view_point, u, (const int2*)tiles, n_tiles,
-                     (const uint4*)ops, (const float*)nullptr, (const float*)nullptr, bn5, bn6, (const float*)nullptr,
-                     (const float*)nullptr, sm6, grad_scores, (const int32_t*)nullptr, (const float*)nullptr,
-                     (const bf16_t*)nullptr, (bf16_t*)da_out, dW, (float*)nullptr, (float*)nullptr, stats, (int)G,
-                     n_views, n_points, (const float*)nullptr, 0.f, (const bf16_t*)a2);
-  DVA_CHECK_LAUNCH();
-  return DVA_OK;
-}
-
 // key layer of QKVBimodalCSRPool as the chain's last layer: grad_compat fp32 [V][4] (G = 1, 2, 4 query-key groups used),
 // queries fp32 [N][32] in position order, scale = 1 / sqrt(nc_qk) or 1; dWk [32][32], dbk [32]
 int dva_chain_score_stats_keys(const float* x_map, const int32_t* view_point, const float* u, const void* tiles,
@@ -1636,61 +1177,6 @@ int dva_chain_bwd_layer(int32_t stage, const float* x_map, const int32_t* view_p
   else if (stage == 5) DVA_LAYER_BWD(5, 3);
   else DVA_LAYER_BWD(2, 3);
 #undef DVA_LAYER_BWD
-  DVA_CHECK_LAUNCH();
-  return DVA_OK;
-}
-
-// Merged backward (round 5): score layer + the linear pieces of S5 in one pass (score_l6_kernel), S5 from them
-// (l6_consts_kernel), stage 5 from the score gradients (layer_bwd_kernel<5, ., false, true>): no stage 6, no dy5 tensor.
-int dva_chain_score_l6_stats(const float* x_map, const int32_t* view_point, const float* u, const void* tiles,
-                             const int32_t* n_tiles, const void* ops, const float* bn1, const float* bn2,
-                             const float* bn5, const float* bn6, const float* grad_scores, double* stats6, float* dWs,
-                             float* dbs, float* acc5, double* vec5, int32_t G, int64_t n_views, int64_t n_points,
-                             void* stream) {
-  if (n_views < 0 || n_points < 0 || G < 1 || G > 4) return DVA_ERR_INVALID;
-  if (n_views == 0) return DVA_OK;
-  if (!x_map || !view_point || !u || !tiles || !n_tiles || !ops || !bn1 || !bn2 || !bn5 || !bn6 || !grad_scores ||
-      !stats6 || !dWs || !dbs || !acc5 || !vec5)
-    return DVA_ERR_INVALID;
-  if (n_views * 32 > 0xfffffff0ll || n_points * 128 > 0xfffffff0ll) return DVA_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(score_l6_kernel, dim3(chain_grid(3)), dim3(256), 0, (hipStream_t)stream, x_map, view_point, u,
-                     (const int2*)tiles, n_tiles, (const uint4*)ops, bn1, bn2, bn5, bn6, grad_scores, stats6, dWs, dbs,
-                     acc5, vec5, (int)G, n_views, n_points);
-  DVA_CHECK_LAUNCH();
-  return DVA_OK;
-}
-
-int dva_chain_l6_consts(const float* sm6, const float* bn6, const float* W6, const float* acc5, const double* vec5,
-                        double* stats5, void* stream) {
-  if (!sm6 || !bn6 || !W6 || !acc5 || !vec5 || !stats5) return DVA_ERR_INVALID;
-  hipLaunchKernelGGL(l6_consts_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sm6, bn6, W6, acc5, vec5, stats5);
-  DVA_CHECK_LAUNCH();
-  return DVA_OK;
-}
-
-int dva_chain_bwd_layer5_merged(const float* x_map, const int32_t* view_point, const float* u, const void* tiles,
-                                const int32_t* n_tiles, const void* ops, const float* bn1, const float* bn2,
-                                const float* bn5, const float* bn6, const float* sm5, const float* sm6,
-                                const float* grad_scores, void* da_out, float* dW5, float* dW6, float* du, double* stats2,
-                                int32_t G, int64_t n_views, int64_t n_points, void* stream) {
-  if (n_views < 0 || n_points < 0 || G < 1 || G > 4) return DVA_ERR_INVALID;
-  if (n_views == 0) return DVA_OK;
-  if (!x_map || !view_point || !u || !tiles || !n_tiles || !ops || !bn1 || !bn2 || !bn5 || !bn6 || !sm5 || !sm6 ||
-      !grad_scores || !da_out || !dW5 || !dW6 || !du || !stats2)
-    return DVA_ERR_INVALID;
-  if (n_views * 64 > 0xfffffff0ll || n_points * 128 > 0xfffffff0ll) return DVA_ERR_UNSUPPORTED;
-  const dim3 block(256);
-  hipStream_t s = (hipStream_t)stream;
-  static const int occ = tune_int("DVA_STAGE5M_OCC", 3);
-#define DVA_LAYER5M(OCC_)                                                                                        \
-  hipLaunchKernelGGL((layer_bwd_kernel<5, OCC_, false, true>), dim3(chain_grid(OCC_)), block, 0, s, x_map,        \
-                     view_point, u, (const int2*)tiles, n_tiles, (const uint4*)ops, bn1, bn2, bn5, bn6,           \
-                     (const float*)nullptr, sm5, sm6, grad_scores, (const int32_t*)nullptr, (const float*)nullptr, \
-                     (const bf16_t*)nullptr, (bf16_t*)da_out, dW5, du, dW6, stats2, (int)G, n_views, n_points,    \
-                     (const float*)nullptr, 0.f)
-  if (occ == 3) DVA_LAYER5M(3);
-  else DVA_LAYER5M(2);
-#undef DVA_LAYER5M
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }

@@ -2,7 +2,7 @@
 // compatibilities = (keys.view(V, G, nc_qk) * queries.view(V, G, nc_qk)).sum(2) / sqrt(nc_qk), queries = the point's query
 // row expanded to its views).
 //
-// keys K' bf16 [V][32] come from dva_chain_keys in ACCUMULATOR order: position i = 16 h + r holds key channel
+// keys K' bf16 [V][32] come from dva_chain_keys_compat in ACCUMULATOR order: position i = 16 h + r holds key channel
 // chan(r, h) = (r & 3) + 8 (r >> 2) + 4 h, so the 32 bytes a lane of the chain kernels holds are contiguous -- the layout of
 // the rows the chain's backward passes hand to each other, and the layout in which d keys goes back into
 // dva_chain_score_stats / dva_chain_bwd_layer(6) (G = 32).  The group of position i is chan(i & 15, i >> 4) / nc_qk

@@ -15,7 +15,7 @@
  * of "feature" buffers (void*): fp32, bf16 or fp16; scores / mapping features / statistics are fp32.
  * DVA_F16 (torch.float16, autocast(float16)) is accepted by: dva_segment_csr_fwd / _bwd, dva_gather_csr,
  * dva_gather_nearest_fwd / _bwd, dva_gather_bilinear_fwd / _bwd, dva_gather_rows_sum, dva_gather_segment_max_fwd /
- * _bwd, dva_view_attention_*, dva_view_gather_attention_*, dva_view_gather_rows_grad, dva_view_gather_rows_grad_rec16,
+ * _bwd, dva_view_attention_*, dva_view_gather_attention_*, dva_view_gather_rows_grad,
  * dva_view_gather_rows_grad_rec16_to, dva_rowbn_*, dva_chain_attn_fwd_dt, dva_chain_attn_bwd_dt and
  * dva_plan_split_rows_grad (dtype = out_dtype = DVA_F16).  Every other entry with a dtype argument returns
  * DVA_ERR_UNSUPPORTED for it before launching anything.
@@ -220,7 +220,7 @@ int dva_row_plan(const int32_t* row_idx, int64_t n_views, int64_t n_rows, int32_
  * dva_plan_split_sort_records: rec [n_views][16] in view order -> rec_sorted in plan order (record i = plan entry i, views of
  * a row in view order, word 3 of a record = its row key), through buf [n_views][16]; rec_sorted may be rec (or NULL: pass A only, see dva_plan_split_rows_grad); row_idx NULL: word 3
  * of the records already holds the row key (dva_chain_attn_bwd writes it there).  The rows gradient
- * (dva_view_gather_rows_grad_rec16* with perm = NULL) then streams its records: no permutation exists, no random 16-byte
+ * (dva_view_gather_rows_grad_rec16_to with perm = NULL) then streams its records: no permutation exists, no random 16-byte
  * fetch per view.  Replaces the index_add of core/multimodal/image.py:1262-1287's backward like dva_row_plan. */
 int64_t dva_plan_split_table_bytes(int64_t n_views, int64_t n_rows);
 int dva_plan_split_build(const int32_t* row_idx, int64_t n_views, int64_t n_rows, int32_t* row_ptr, int32_t* counts,
@@ -232,7 +232,7 @@ int dva_plan_split_sort_records(const int32_t* row_idx, const void* rec, int64_t
  * NULL runs pass A only (view order -> bucket order, into buf); then ONE workgroup per bucket of 512 map rows keeps their C
  * fp32 sums in its registers, ranks and stages the bucket's tiles in LDS like pass B and consumes the staged records where
  * they lie (the 16 bytes per view pass B writes and the rows gradient reads again never exist).  grad_rows [n_rows][C]
- * bf16, written; deterministic; a row is summed by one lane team in view order (dva_view_gather_rows_grad_rec16* splits
+ * bf16, written; deterministic; a row is summed by one lane team in view order (dva_view_gather_rows_grad_rec16_to splits
  * it over 8 lane slots: the two agree to fp32 rounding).  bf16 / bf16 or fp16 / fp16 (fp32 sums, one rounding), C in
  * {32, 64}, G in {1, 2, 4}; otherwise
  * DVA_ERR_UNSUPPORTED (the caller runs pass B and dva_view_gather_rows_grad_rec16_to).
@@ -259,11 +259,8 @@ int dva_view_gather_rows_grad(const void* grad_out, const float* att, const floa
 /* The same reduction over packed 16-byte view records {int32 point | 4 x bf16 weight | pad} (dva_chain_attn_bwd):
  * bf16 grad_out, G in {1, 2, 4}, C / 8 a power of two <= 64, (C / G) % 8 == 0. */
 /* (perm may be NULL: the records then lie in plan order -- record i belongs to plan entry i -- as
- * dva_chain_attn_bwd_planrec writes them.) */
-int dva_view_gather_rows_grad_rec16(const void* grad_out, const int32_t* perm, const int32_t* row_ptr,
-                                    const void* view_rec16, float* grad_rows, int64_t n_rows, int64_t n_views,
-                                    int32_t C, int32_t G, int32_t dtype, void* stream);
-/* The same with the output dtype chosen by the caller: out_dtype = DVA_F32 (as above) or the 2-byte dtype of grad_out
+ * dva_plan_split_sort_records leaves them.) */
+/* The output dtype is chosen by the caller: out_dtype = DVA_F32 (fp32 [n_rows, C] as above) or the 2-byte dtype of grad_out
  * (DVA_BF16 / DVA_F16) -- the summed row is
  * rounded once where it is summed, for maps that are bf16 anyway (the gradient autograd hands on has the map's dtype:
  * core/multimodal/image.py:1262-1287 is an index_add in the map's dtype); no fp32 [n_rows, C] tensor, no conversion pass. */
@@ -455,7 +452,7 @@ int dva_scale_f64(const double* in, double scale, float* out, int32_t n, void* s
  * blocks + an fp32 copy of the forward ones, from which the kernels build BatchNorm-folded operands
  * bf16(0.6 gamma invstd W) for the layers whose raw output a pass does not need).  W1 [32][8], W2 [32][32],
  * W5 [32][ld5] (the first 32 columns: the per-view half of the concatenation layer), W6 [32][32], Ws [G][32], G <= 4 -- or
- * G = 32: the last layer is the KEY layer of QKVBimodalCSRPool (dva_chain_keys / dva_chain_keys_compat; its backward runs
+ * G = 32: the last layer is the KEY layer of QKVBimodalCSRPool (dva_chain_keys_compat; its backward runs
  * through dva_chain_score_stats_keys / dva_chain_bwd_layer6_keys). */
 #define DVA_CHAIN_OPS_BYTES (18 * 64 * 16 + 7 * 64 * 32)
 int dva_chain_prep(const float* W1, const float* W2, const float* W5, int32_t ld5, const float* W6,
@@ -506,30 +503,19 @@ int dva_chain_stats(int32_t layer, const float* x_map, const int32_t* view_point
                     const void* tiles, const int32_t* n_tiles, const void* ops, const float* bn1,
                     const float* bn2, const float* bn5, double* stats, int64_t n_views, int64_t n_points,
                     void* stream);
-/* The stored-a2 hybrid (round 6; reference maths unchanged: modules/multimodal/pooling.py:658-669, DeepSetFeat.forward):
- * layer = 5: dva_chain_stats(5) that also WRITES a2 bf16 [V][32] = the layer-2 activation leaky(BN2(W2 a1)) of every view in
- * ACCUMULATOR order (position 16 h + r = channel (r & 3) + 8 (r >> 2) + 4 h), i.e. the packed operand layer 5 consumes;
- * layer = 6: dva_chain_stats(6) starting from that row instead of x_map (x_map may be NULL).  a2 16-byte aligned. */
-int dva_chain_stats_a2(int32_t layer, const float* x_map, const int32_t* view_point, const float* u,
-                       const void* tiles, const int32_t* n_tiles, const void* ops, const float* bn1,
-                       const float* bn2, const float* bn5, double* stats, int64_t n_views, int64_t n_points,
-                       void* a2, void* stream);
 /* Key layer of QKVBimodalCSRPool on the recompute chain (round 4; reference modules/multimodal/pooling.py:454-547:
  * keys = K(E_map(x_map))): ops prepared by dva_chain_prep with Ws = K.weight [32][32], G = 32.  keys bf16 [V][32] in
  * ACCUMULATOR order: position 16 h + r holds key channel (r & 3) + 8 (r >> 2) + 4 h (the layout of the rows the chain's
  * backward passes hand to each other).
- * dva_chain_keys_compat: the same pass also writes the compatibilities (pooling.py:520-531) compat fp32 [V][4] =
+ * The same pass also writes the compatibilities (pooling.py:520-531) compat fp32 [V][4] =
  * scale * sum over the 32 / G key channels of group g of the (bf16-rounded) key * queries[point(v)][.] -- queries fp32 [N][32]
  * in the keys' position order, G in {1, 2, 4} query-key groups (columns >= G are written as 0), 16-byte aligned. */
-int dva_chain_keys(const float* x_map, const int32_t* view_point, const float* u, const void* tiles,
-                   const int32_t* n_tiles, const void* ops, const float* bn1, const float* bn2, const float* bn5,
-                   const float* bn6, const float* key_bias, void* keys, int64_t n_views, int64_t n_points, void* stream);
 int dva_chain_keys_compat(const float* x_map, const int32_t* view_point, const float* u, const void* tiles,
                           const int32_t* n_tiles, const void* ops, const float* bn1, const float* bn2, const float* bn5,
                           const float* bn6, const float* key_bias, void* keys, const float* queries, float* compat,
                           int32_t G, float scale, int64_t n_views, int64_t n_points, void* stream);
 /* compat fp32 [V][G] = scale * sum over the nc_qk = 32 / G key channels of group g of keys[v] * queries[point(v)]
- * (pooling.py:520-531), keys as dva_chain_keys writes them, queries fp32 [N][32] in the same position order; G in {1, 2, 4}.
+ * (pooling.py:520-531), keys as dva_chain_keys_compat writes them, queries fp32 [N][32] in the same position order; G in {1, 2, 4}.
  * _bwd: grad_keys bf16 [V][32] (position order; NULL: skipped -- the chain backward builds it in registers),
  * grad_queries fp32 [N][32] (written).  dva_qkv_dquery: grad_queries alone, grad_compat with leading dimension ld >= G
  * (the [V][4] layout of dva_chain_keys_compat / dva_chain_attn_bwd: ld = 4). */
@@ -653,32 +639,10 @@ int dva_chain_set_bwd(int32_t stage, const float* pooled, const int64_t* ptr, co
                       const float* bn_s1, const float* bn_s2, const float* sm_s1, const float* sm_s2,
                       const float* du, float* dpooled, float* dW, int32_t ld_dw, float* dw33, double* stats,
                       int64_t n_points, void* stream);
-/* Merged chain backward (round 5; autograd of modules/multimodal/pooling.py:263-315, :658-669 as the entries around it): the
- * score pass also accumulates the pieces the statistics of the BatchNorm-5 backward are linear in (dz6 = G6 dy6 - K1 - K2 z6
- * is linear in the constants K1, K2 the same pass is still summing), so that stage 6 -- one chain evaluation, the bf16
- * [V][32] dy5 tensor, one launch -- disappears:
- *   dva_chain_score_l6_stats   dva_chain_score_stats + acc5 fp32 [2][32][32] = P2 | Q2 and vec5 fp64 [4][32] = e1 | e2 | n5 | q5
- *                              (both caller-zeroed; see csrc/chain_bwd.hip score_l6_kernel)
- *   dva_chain_l6_consts        stats5 fp64 [64] = sum dy5 | sum dy5 z5 from them, sm6 (dva_bn_bwd_consts of stats6), bn6 and
- *                              the fp32 weight W6 [32][32]
- *   dva_chain_bwd_layer5_merged  stage 5 of dva_chain_bwd_layer starting from grad_scores [V][4] and sm6 instead of the dy5
- *                              row: also writes dW6 [32][32] (caller-zeroed) */
-int dva_chain_score_l6_stats(const float* x_map, const int32_t* view_point, const float* u, const void* tiles,
-                             const int32_t* n_tiles, const void* ops, const float* bn1, const float* bn2,
-                             const float* bn5, const float* bn6, const float* grad_scores, double* stats6, float* dWs,
-                             float* dbs, float* acc5, double* vec5, int32_t G, int64_t n_views, int64_t n_points,
-                             void* stream);
-int dva_chain_l6_consts(const float* sm6, const float* bn6, const float* W6, const float* acc5, const double* vec5,
-                        double* stats5, void* stream);
-int dva_chain_bwd_layer5_merged(const float* x_map, const int32_t* view_point, const float* u, const void* tiles,
-                                const int32_t* n_tiles, const void* ops, const float* bn1, const float* bn2,
-                                const float* bn5, const float* bn6, const float* sm5, const float* sm6,
-                                const float* grad_scores, void* da_out, float* dW5, float* dW6, float* du, double* stats2,
-                                int32_t G, int64_t n_views, int64_t n_points, void* stream);
 /* Backward of the softmax / weighted sum / gate of dva_chain_attn_fwd from the scores it left (scores fp32 [V][4]):
  * no chain evaluation.  grad_out / out bf16 [N][C] (out = the forward result; only read for points with more than 32
  * views).  Outputs: grad_scores fp32 [V][4] (columns >= G zero), view_rec = V packed 16-byte records {int32 point id |
- * gate * attention of groups 0..3 as bf16 | 4 unused bytes} (what dva_view_gather_rows_grad_rec16 consumes: the rows
+ * gate * attention of groups 0..3 as bf16 | 4 unused bytes} (what dva_view_gather_rows_grad_rec16_to consumes: the rows
  * gradient is rounded to bf16, its weights travel as bf16), grad_gate_wb fp32 [2 G] (caller-zeroed, d gate_w |
  * d gate_b; nullable with gating off). */
 int dva_chain_attn_bwd(const float* scores, const int32_t* view_point, const void* tiles, const int32_t* n_tiles,
@@ -693,16 +657,6 @@ int dva_chain_attn_bwd_dt(const float* scores, const int32_t* view_point, const 
                           const float* gate_b, const void* grad_out, const void* out, float* grad_scores, void* view_rec,
                           float* grad_gate_wb, int64_t n_points, int64_t n_views, int64_t n_rows, int32_t C, int32_t G,
                           int32_t scaling, float eps, int32_t dtype, void* stream);
-/* A/B variant of round 4 (profiles/r04*_rows_grad_planrec_ab.json): dva_chain_attn_bwd that writes the
- * 16-byte record of view v to slot rec_pos[v] -- its position in the row plan, rec_pos = dva_plan_inverse(perm) -- so that
- * dva_view_gather_rows_grad_rec16(perm = NULL) streams the records instead of gathering them. */
-int dva_chain_attn_bwd_planrec(const int32_t* rec_pos, const float* scores, const int32_t* view_point, const void* tiles,
-                               const int32_t* n_tiles, const void* rows, const int32_t* row_idx, const int64_t* ptr,
-                               const float* gate_w, const float* gate_b, const void* grad_out, const void* out,
-                               float* grad_scores, void* view_rec, float* grad_gate_wb, int64_t n_points, int64_t n_views,
-                               int64_t n_rows, int32_t C, int32_t G, int32_t scaling, float eps, void* stream);
-/* inv[perm[i]] = i for a permutation of n_views entries (the row plan's `perm`). */
-int dva_plan_inverse(const int32_t* perm, int32_t* inv, int64_t n_views, void* stream);
 /* dva_chain_attn_bwd for fp32 value rows (the no-autocast path: ops.view_gather_attention backward when the scores
  * are fp32 [V][4]): rows / grad_out / out fp32, C in {32, 64, 128, 256}, view_rec = fp32 [V][8] records
  * {point id (int bits) | gate * attention per group | pad} as dva_view_gather_rows_grad reads them (rec_stride 8). */
@@ -731,16 +685,6 @@ int dva_chain_score_stats(const float* x_map, const int32_t* view_point, const f
                           const int32_t* n_tiles, const void* ops, const float* bn1, const float* bn2,
                           const float* bn5, const float* bn6, const float* grad_scores, double* stats6, float* dWs,
                           float* dbs, int32_t G, int64_t n_views, int64_t n_points, void* stream);
-/* dva_chain_score_stats / stage 6 of dva_chain_bwd_layer starting from the a2 row of dva_chain_stats_a2 instead of x_map
- * (64 instead of 32 bytes per view read, layers 1 and 2 not evaluated; same results bit for bit). */
-int dva_chain_score_stats_a2(const void* a2, const int32_t* view_point, const float* u, const void* tiles,
-                             const int32_t* n_tiles, const void* ops, const float* bn5, const float* bn6,
-                             const float* grad_scores, double* stats6, float* dWs, float* dbs, int32_t G,
-                             int64_t n_views, int64_t n_points, void* stream);
-int dva_chain_bwd_layer6_a2(const void* a2, const int32_t* view_point, const float* u, const void* tiles,
-                            const int32_t* n_tiles, const void* ops, const float* bn5, const float* bn6,
-                            const float* sm6, const float* grad_scores, void* da_out, float* dW, double* stats,
-                            int32_t G, int64_t n_views, int64_t n_points, void* stream);
 /* The same pass below the KEY layer of QKVBimodalCSRPool (ops prepared with G = 32): the gradient of a view's key row is
  * built in registers, dK'[v][i] = scale grad_compat[v][g(i)] queries[point(v)][i] (grad_compat fp32 [V][4], queries fp32
  * [N][32] in position order, G in {1, 2, 4} query-key groups); dWk fp32 [32][32] / dbk fp32 [32] (caller-zeroed) += the

@@ -988,8 +988,8 @@ __global__ __launch_bounds__(256) void rows_grad_team_kernel(
     const int32_t* __restrict__ vp, const int32_t* __restrict__ perm,
     const int32_t* __restrict__ row_ptr, const float* __restrict__ rec, int rs,
     TO* __restrict__ grows, int64_t R, int C, int G, int lpr, int lpg, int c0 = 0) {
-  // C = row stride in elements; a launch covers the channels [c0, c0 + lpr * VEC) of every row (c0 = 0, lpr * VEC = C:
-  // whole rows; channel slabs: dva_view_gather_rows_grad_rec16_to)
+  // C = row stride in elements; a launch covers the channels [c0, c0 + lpr * VEC) of every row.  Every caller passes
+  // c0 = 0, lpr * VEC = C: whole rows (channel slabs, one launch each, lost: 7.01 ms against 7.14 - 10.37, HISTORY.md)
   constexpr int VEC = Vec16<T>::N;
   constexpr int U = 4;
   typedef typename Vec16<T>::raw raw_t;
@@ -1434,8 +1434,8 @@ using namespace dva;
 template <typename T>
 static void rows_grad_rec16_launch(const void* grad_out, const int32_t* perm, const int32_t* row_ptr,
                                    const void* view_rec16, void* grad_rows, bool to_16, int64_t n_rows, int64_t n_views,
-                                   int C, int G, int slab, hipStream_t s) {
-  const int lpr = C / 8, lpr_s = slab / 8;
+                                   int C, int G, hipStream_t s) {
+  const int lpr = C / 8;
   if (n_views <= 2 * n_rows && lpr < 64) {
     // sparse plan (view-level identity gathers): a lane team per row
     const int64_t waves = (n_rows + (64 / lpr) - 1) / (64 / lpr);
@@ -1449,16 +1449,15 @@ static void rows_grad_rec16_launch(const void* grad_out, const int32_t* perm, co
                          lpr, lpr / G);
     return;
   }
-  for (int c0 = 0; c0 < C; c0 += slab) {
-    if (to_16)
-      hipLaunchKernelGGL((rows_grad_team_kernel<T, true, T>), dim3(grid_cap((n_rows + 3) / 4)), dim3(256), 0, s,
-                         (const T*)grad_out, (const float*)nullptr, (const float*)nullptr, (const int32_t*)nullptr, perm,
-                         row_ptr, (const float*)view_rec16, 4, (T*)grad_rows, n_rows, C, G, lpr_s, lpr / G, c0);
-    else
-      hipLaunchKernelGGL((rows_grad_team_kernel<T, true>), dim3(grid_cap((n_rows + 3) / 4)), dim3(256), 0, s,
-                         (const T*)grad_out, (const float*)nullptr, (const float*)nullptr, (const int32_t*)nullptr, perm,
-                         row_ptr, (const float*)view_rec16, 4, (float*)grad_rows, n_rows, C, G, lpr_s, lpr / G, c0);
-  }
+  // whole rows, one launch
+  if (to_16)
+    hipLaunchKernelGGL((rows_grad_team_kernel<T, true, T>), dim3(grid_cap((n_rows + 3) / 4)), dim3(256), 0, s,
+                       (const T*)grad_out, (const float*)nullptr, (const float*)nullptr, (const int32_t*)nullptr, perm,
+                       row_ptr, (const float*)view_rec16, 4, (T*)grad_rows, n_rows, C, G, lpr, lpr / G, 0);
+  else
+    hipLaunchKernelGGL((rows_grad_team_kernel<T, true>), dim3(grid_cap((n_rows + 3) / 4)), dim3(256), 0, s,
+                       (const T*)grad_out, (const float*)nullptr, (const float*)nullptr, (const int32_t*)nullptr, perm,
+                       row_ptr, (const float*)view_rec16, 4, (float*)grad_rows, n_rows, C, G, lpr, lpr / G, 0);
 }
 
 extern "C" {
@@ -1583,17 +1582,12 @@ int dva_view_gather_rows_grad_rec16_to(const void* grad_out, const int32_t* perm
   if ((C % 8) || !is_pow2(lpr) || lpr > 64 || (C % G) || ((C / G) % 8) || ((uintptr_t)grad_out % 16) ||
       ((uintptr_t)grad_rows % 16))
     return DVA_ERR_UNSUPPORTED;
-  // wide rows in channel slabs (one launch per slab: the slab of grad_out, n_points x slab x 2 bytes, is what the
-  // 32 re-reads of a point's row hit): DVA_ROWS_GRAD_SLAB = channels per slab, 0 = whole rows (A/B in profiles/r04*)
-  static const int slab_env = tune_int("DVA_ROWS_GRAD_SLAB", 0);
-  int slab = slab_env;
-  if (slab <= 0 || slab >= C || (slab % 8) || !is_pow2(slab / 8) || (C % slab)) slab = C;
   const bool to_16 = out_dtype != DVA_F32;
   if (dtype == DVA_F16)
-    rows_grad_rec16_launch<f16_t>(grad_out, perm, row_ptr, view_rec16, grad_rows, to_16, n_rows, n_views, C, G, slab,
+    rows_grad_rec16_launch<f16_t>(grad_out, perm, row_ptr, view_rec16, grad_rows, to_16, n_rows, n_views, C, G,
                                   (hipStream_t)stream);
   else
-    rows_grad_rec16_launch<bf16_t>(grad_out, perm, row_ptr, view_rec16, grad_rows, to_16, n_rows, n_views, C, G, slab,
+    rows_grad_rec16_launch<bf16_t>(grad_out, perm, row_ptr, view_rec16, grad_rows, to_16, n_rows, n_views, C, G,
                                    (hipStream_t)stream);
   DVA_CHECK_LAUNCH();
   return DVA_OK;

@@ -1171,9 +1171,8 @@ int dva_chain_bwd_layer(int32_t stage, const float* x_map, const int32_t* view_p
                      (const int2*)tiles, n_tiles, (const uint4*)ops, bn1, bn2, bn5, bn6, sm2, sm5, sm6,          \
                      grad_scores, arg, dpooled, (const bf16_t*)da_in, (bf16_t*)da_out, dW, du, P, stats, G, \
                      n_views, n_points, (const float*)nullptr, 0.f)
-  static const int occ5 = tune_int("DVA_STAGE5_OCC", 3);
+  // three wavefronts per SIMD for every stage
   if (stage == 6) DVA_LAYER_BWD(6, 3);
-  else if (stage == 5 && occ5 == 2) DVA_LAYER_BWD(5, 2);
   else if (stage == 5) DVA_LAYER_BWD(5, 3);
   else DVA_LAYER_BWD(2, 3);
 #undef DVA_LAYER_BWD

@@ -305,11 +305,9 @@ __device__ __forceinline__ void stage_tab_fwd(float* tab, const float* __restric
 // same column of the product, so the garbage (finite: such a lane loaded zeros) stays in lanes that own no view; what has
 // to be exact is every REDUCTION OVER VIEWS, and each of those is guarded where it happens (statistics under `if (ok)`,
 // gradient rows masked by pack16 before the weight-gradient products).  v_cndmask costs two issue slots (tools/ubench):
-// the eight per layer and tile were a quarter of the vector time of a statistics pass.
-#ifndef DVA_MASK_ACT
-#define DVA_MASK_ACT 0      // 1: the A/B build (csrc/Makefile EXTRA=-DDVA_MASK_ACT=1) keeps every activation mask
-#endif
-template <bool MASK_ = true>
+// the eight per layer and tile were a quarter of the vector time of a statistics pass (-0.15 ... -0.2 ms per step,
+// profiles/r06_unmask_ab.json).
+template <bool MASK = true>
 __device__ __forceinline__ void act_pack(const f32x16& z, const float* tab, int h, uint32_t keep, bf16x8 (&a)[2],
                                          int rg = T_G6, int rb = T_B6, float* sum = nullptr) {
   asm volatile("" ::: "memory");
@@ -325,7 +323,6 @@ __device__ __forceinline__ void act_pack(const f32x16& z, const float* tab, int 
 #pragma unroll
     for (int r = 0; r < 16; ++r) sum[r] += av[r];
   }
-  constexpr bool MASK = MASK_ || DVA_MASK_ACT;
   a[0] = MASK ? mask8(pack8(&av[0]), keep) : pack8(&av[0]);
   a[1] = MASK ? mask8(pack8(&av[8]), keep) : pack8(&av[8]);
 }
@@ -378,7 +375,7 @@ __device__ __forceinline__ f32x16 bias_acc(const float* tab, int row, int h) {
   return c;
 }
 // activation of a folded layer (t = 0.6 y from the product) + bf16 packing as the next B operand
-template <bool MASK_ = true>
+template <bool MASK = true>
 __device__ __forceinline__ void act_fold(const f32x16& t, uint32_t keep, bf16x8 (&a)[2], float* sum = nullptr) {
   float av[16];
 #pragma unroll
@@ -387,7 +384,6 @@ __device__ __forceinline__ void act_fold(const f32x16& t, uint32_t keep, bf16x8 
 #pragma unroll
     for (int r = 0; r < 16; ++r) sum[r] += av[r];
   }
-  constexpr bool MASK = MASK_ || DVA_MASK_ACT;
   a[0] = MASK ? mask8(pack8(&av[0]), keep) : pack8(&av[0]);
   a[1] = MASK ? mask8(pack8(&av[8]), keep) : pack8(&av[8]);
 }

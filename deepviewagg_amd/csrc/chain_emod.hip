@@ -919,7 +919,7 @@ __global__ __launch_bounds__((CO >= 256 && ZM == 1) ? 512 : 256, CO > 64 ? (CO =
 //   dc [V, 4], view records {point | gate * attention (bf16 x 4) | pad}, statistics of the BatchNorm_b backward
 //   (S1 = sum dy_b | sum dy_b z_b with dy_b = leaky'(y_b) gate attention grad_out)
 // ------------------------------------------------------------------------------------------------
-template <int CO, int G, int OCC = (CO == 32 ? 4 : (CO >= 128 ? 1 : 2))>
+template <int CO, int G, int OCC = (CO == 32 ? 4 : (CO >= 256 ? 1 : 2))>
 __global__ __launch_bounds__(CO >= 256 ? 512 : 256, OCC) void emod_attn_bwd_kernel(
     const float* __restrict__ compat, const int32_t* __restrict__ vp, const int2* __restrict__ tiles,
     const int32_t* __restrict__ n_tiles_dev, const bf16_t* __restrict__ Yp, const int4* __restrict__ rows4,
@@ -1531,10 +1531,9 @@ __global__ __launch_bounds__(256, 2) void emod_bwd_kernel(
 //          -> dW_b += dz_b^T y_a through the transpose read (wgradN).
 // One more evaluation of Linear_b (2 V CO^2 flop) against 8 CO more bytes per view for handing dz_b over.
 // ------------------------------------------------------------------------------------------------
-//   MODE 3 / MODE 4 (C_o = 256, one wavefront per SIMD): MODE 1 cut in two, because the operands of W_b (128 KB per
-//          orientation) do not fit LDS together: MODE 3 = z_b -> dz_b, written as bf16 [V][CO] into the buffer that will hold
-//          dy_a; MODE 4 = the stored dz_b -> dy_a IN PLACE (a lane reads and writes the same 32-byte pieces of its view) + S of
-//          BatchNorm_a.  Between the two, emodw_wgrad_coop_kernel takes dW_b from the stored dz_b.
+//   MODE 3 (C_o = 256, one wavefront per SIMD): the first half of MODE 1, because the operands of W_b (128 KB per
+//          orientation) do not fit LDS together: z_b -> dz_b, written as bf16 [V][CO] into the buffer that will hold dy_a.
+//          emodw_wgrad_coop_kernel takes dW_b from the stored dz_b and turns it into dy_a in place + S of BatchNorm_a.
 template <int CO, int G, int MODE>
 __global__ __launch_bounds__(MODE == 2 ? 256 : 512, 1) void emodw_bwd_kernel(
     const int2* __restrict__ tiles, const int32_t* __restrict__ n_tiles_dev, const uint4* __restrict__ eops,
@@ -1542,27 +1541,23 @@ __global__ __launch_bounds__(MODE == 2 ? 256 : 512, 1) void emodw_bwd_kernel(
     const uint32_t* __restrict__ rec, const bf16_t* __restrict__ gout, bf16_t* __restrict__ da, float* __restrict__ dWb,
     double* __restrict__ stats_a, const bf16_t* __restrict__ zst, int64_t V, int64_t N) {
   constexpr int NB = CO / 32, GS = CO / G, NW = MODE == 2 ? 4 : 8;
-  constexpr bool FWD = MODE != 4;                    // evaluates z_b -> dz_b
-  constexpr bool DYA = MODE == 1 || MODE == 4;       // evaluates dy_a
+  constexpr bool DYA = MODE == 1;                    // evaluates dy_a
   constexpr int NT = MODE == 2 ? NB : 1;
   constexpr int N_EOPS = (MODE == 1 ? 2 : 1) * NB * NB * 2 * 64;
-  constexpr int BWD_BASE = MODE == 4 ? NB * NB * 2 : 0;      // MODE 4 holds the second half of the table only
   __shared__ __attribute__((aligned(16))) float s_taba[NB][TAB_FLOATS];
-  __shared__ __attribute__((aligned(16))) float s_tabb[FWD ? NB : 1][FWD ? TAB_FLOATS : 8];
+  __shared__ __attribute__((aligned(16))) float s_tabb[NB][TAB_FLOATS];
   __shared__ __attribute__((aligned(16))) uint4 s_eops[N_EOPS];
-  // MODE 1 / 4: [0] = the dy_a block, [1] = the z_a block;  MODE 2: NB tiles of dz_b, NB tiles of y_a;  MODE 3: unused
-  // (MODE 4: ONE tile per wavefront, used twice per block -- dy_a, then the products dy_a z_a: with W_b^T filling 128 KB there
-  //  is room for 8 x 1 tiles, not 8 x 2)
+  // MODE 1: [0] = the dy_a block, [1] = the z_a block;  MODE 2: NB tiles of dz_b, NB tiles of y_a;  MODE 3: unused
   __shared__ __attribute__((aligned(16))) bf16_t s_ta[MODE == 3 ? 1 : NW][NT][MODE == 3 ? 8 : 32 * TSB],
-      s_tb[(MODE == 3 || MODE == 4) ? 1 : NW][NT][(MODE == 3 || MODE == 4) ? 8 : 32 * TSB];
+      s_tb[MODE == 3 ? 1 : NW][NT][MODE == 3 ? 8 : 32 * TSB];
   float* s_red = reinterpret_cast<float*>(&s_ta[0][0][0]);     // epilogue: D x D floats | NW x 64 floats
   static_assert(MODE == 3 || sizeof(bf16_t) * NW * NT * 32 * TSB >= sizeof(float) * (MODE == 2 ? D * D : NW * 64),
                 "epilogue buffer");
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
-  for (int i = threadIdx.x; i < N_EOPS; i += blockDim.x) s_eops[i] = eops[BWD_BASE * 64 + i];
+  for (int i = threadIdx.x; i < N_EOPS; i += blockDim.x) s_eops[i] = eops[i];
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
-    if (FWD) stage_tab_c(s_tabb[b], bnb, CO, 32 * b, smb);
+    stage_tab_c(s_tabb[b], bnb, CO, 32 * b, smb);
     stage_tab_c(s_taba[b], bna, CO, 32 * b, nullptr);
   }
   __syncthreads();
@@ -1589,7 +1584,6 @@ __global__ __launch_bounds__(MODE == 2 ? 256 : 512, 1) void emodw_bwd_kernel(
   struct Pre {
     TileInfo ti;
     ZaRows<NB> z;        // the stored z_a
-    ZaRows<MODE == 4 ? NB : 1> dz;      // MODE 4: the stored dz_b
     u32x4 rc;
   };
   auto loop = [&](auto&& ld, auto&& bd) {
@@ -1601,76 +1595,67 @@ __global__ __launch_bounds__(MODE == 2 ? 256 : 512, 1) void emodw_bwd_kernel(
     p.ti = ti;
     const bool ok = j < p.ti.nv;
     p.z = load_za<CO>(zst, ti, j, h);
-    if constexpr (MODE == 4) p.dz = load_za<CO>(da, ti, j, h);
-    else p.rc = ld128(RC, ok ? (uint32_t)(p.ti.v0 + j) * 16u : OOB);
+    p.rc = ld128(RC, ok ? (uint32_t)(p.ti.v0 + j) * 16u : OOB);
     return p;
   }, [&](const Pre& p) {
     const bool ok = j < p.ti.nv;
     const uint32_t keep = ok ? 0xffffffffu : 0u;
     // (the handed-over gradient [V][CO] exceeds 4 GiB at the headline size: one descriptor per tile)
     const __amdgpu_buffer_rsrc_t DA = make_rsrc(da + (int64_t)p.ti.v0 * CO, (uint64_t)p.ti.nv * CO * 2);
-    bf16x8 dzp[(MODE == 1 || MODE == 4) ? NB : 1][2];
-    if constexpr (FWD) {
-      bf16x8 a[NB][2];
-      act_a_rows<NB>(p.z, s_taba, h, keep, a);
-      if (MODE == 2) {
+    bf16x8 dzp[MODE == 1 ? NB : 1][2];
+    bf16x8 a[NB][2];
+    act_a_rows<NB>(p.z, s_taba, h, keep, a);
+    if (MODE == 2) {
 #pragma unroll
-        for (int b = 0; b < NB; ++b) tileN_put_packed(s_tb[wv][b], j, h, a[b]);
+      for (int b = 0; b < NB; ++b) tileN_put_packed(s_tb[wv][b], j, h, a[b]);
+    }
+    // d value[ch] = (gate attention)[g(ch)] grad_out[point][ch] for the lane's channels 32 mb + chan(r, h)
+    const uint32_t pid = p.rc.x;
+    const float ga4[4] = {__uint_as_float(p.rc.y << 16), __uint_as_float(p.rc.y & 0xffff0000u),
+                          __uint_as_float(p.rc.z << 16), __uint_as_float(p.rc.z & 0xffff0000u)};
+#pragma unroll
+    for (int mb = 0; mb < NB; ++mb) {
+      const f32x16 zb = linear_b_std_blk<NB>(s_eops, lane, a, mb);
+      f32x16 dy;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int c0 = 32 * mb + 8 * q + 4 * h;            // channels c0 .. c0 + 3 = chan(4 q + i, h) + 32 mb
+        const u32x2 gv = ld64(GO, ok ? pid * (uint32_t)(CO * 2) + (uint32_t)c0 * 2u : OOB);
+        const float gg = ga4[G == 1 ? 0 : c0 / GS];
+        dy[4 * q] = gg * __uint_as_float(gv.x << 16);
+        dy[4 * q + 1] = gg * __uint_as_float(gv.x & 0xffff0000u);
+        dy[4 * q + 2] = gg * __uint_as_float(gv.y << 16);
+        dy[4 * q + 3] = gg * __uint_as_float(gv.y & 0xffff0000u);
       }
-      // d value[ch] = (gate attention)[g(ch)] grad_out[point][ch] for the lane's channels 32 mb + chan(r, h)
-      const uint32_t pid = p.rc.x;
-      const float ga4[4] = {__uint_as_float(p.rc.y << 16), __uint_as_float(p.rc.y & 0xffff0000u),
-                            __uint_as_float(p.rc.z << 16), __uint_as_float(p.rc.z & 0xffff0000u)};
+      // dy_b = leaky'(y_b) d value, y_b = G_b z_b + B_b;  dz_b = G_b dy_b - K1 - K2 z_b
+      float dz[16];
+      {
+        asm volatile("" ::: "memory");
+        float g_[16], b_[16];
+        tab16(s_tabb[mb], T_G, h, g_);
+        tab16(s_tabb[mb], T_B, h, b_);
 #pragma unroll
-      for (int mb = 0; mb < NB; ++mb) {
-        const f32x16 zb = linear_b_std_blk<NB>(s_eops, lane, a, mb);
-        f32x16 dy;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int c0 = 32 * mb + 8 * q + 4 * h;            // channels c0 .. c0 + 3 = chan(4 q + i, h) + 32 mb
-          const u32x2 gv = ld64(GO, ok ? pid * (uint32_t)(CO * 2) + (uint32_t)c0 * 2u : OOB);
-          const float gg = ga4[G == 1 ? 0 : c0 / GS];
-          dy[4 * q] = gg * __uint_as_float(gv.x << 16);
-          dy[4 * q + 1] = gg * __uint_as_float(gv.x & 0xffff0000u);
-          dy[4 * q + 2] = gg * __uint_as_float(gv.y << 16);
-          dy[4 * q + 3] = gg * __uint_as_float(gv.y & 0xffff0000u);
-        }
-        // dy_b = leaky'(y_b) d value, y_b = G_b z_b + B_b;  dz_b = G_b dy_b - K1 - K2 z_b
-        float dz[16];
-        {
-          asm volatile("" ::: "memory");
-          float g_[16], b_[16];
-          tab16(s_tabb[mb], T_G, h, g_);
-          tab16(s_tabb[mb], T_B, h, b_);
-#pragma unroll
-          for (int r = 0; r < 16; ++r) dy[r] = __builtin_fmaf(zb[r], g_[r], b_[r]) > 0.f ? dy[r] : SLOPE * dy[r];
-        }
-        bn_bwd_apply(zb, dy, s_tabb[mb], h, dz);
-        if (MODE == 1) {
-          pack16(dz, keep, dzp[mb]);
-        } else {
-          bf16x8 t2[2];
-          pack16(dz, keep, t2);
-          if (MODE == 2) {
-            tileN_put_packed(s_ta[wv][mb], j, h, t2);
-          } else {      // MODE 3: hand dz_b over (position order, the lane's 32 bytes of block mb)
-            const uint32_t off = ok ? (uint32_t)j * (uint32_t)(CO * 2) + (uint32_t)(32 * mb + 16 * h) * 2u : OOB;
-            st128(DA, off, __builtin_bit_cast(u32x4, t2[0]));
-            st128(DA, ok ? off + 16u : OOB, __builtin_bit_cast(u32x4, t2[1]));
-          }
-        }
+        for (int r = 0; r < 16; ++r) dy[r] = __builtin_fmaf(zb[r], g_[r], b_[r]) > 0.f ? dy[r] : SLOPE * dy[r];
       }
-    } else {
-#pragma unroll
-      for (int mb = 0; mb < NB; ++mb) {
-        dzp[mb][0] = __builtin_bit_cast(bf16x8, p.dz.q[mb][0]);
-        dzp[mb][1] = __builtin_bit_cast(bf16x8, p.dz.q[mb][1]);
+      bn_bwd_apply(zb, dy, s_tabb[mb], h, dz);
+      if (MODE == 1) {
+        pack16(dz, keep, dzp[mb]);
+      } else {
+        bf16x8 t2[2];
+        pack16(dz, keep, t2);
+        if (MODE == 2) {
+          tileN_put_packed(s_ta[wv][mb], j, h, t2);
+        } else {      // MODE 3: hand dz_b over (position order, the lane's 32 bytes of block mb)
+          const uint32_t off = ok ? (uint32_t)j * (uint32_t)(CO * 2) + (uint32_t)(32 * mb + 16 * h) * 2u : OOB;
+          st128(DA, off, __builtin_bit_cast(u32x4, t2[0]));
+          st128(DA, ok ? off + 16u : OOB, __builtin_bit_cast(u32x4, t2[1]));
+        }
       }
     }
     if constexpr (DYA) {
       // da = W_b^T dz_b, dy_a = leaky'(y_a) da, handed over as bf16 (position order);  S of BatchNorm_a from the stored rows
       bf16_t* tdy = s_ta[wv][0];
-      bf16_t* tz = s_tb[MODE == 4 ? 0 : wv][0];      // (MODE 4 has no second tile)
+      bf16_t* tz = s_tb[wv][0];
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
         f32x16 dya = {0};
@@ -1679,7 +1664,7 @@ __global__ __launch_bounds__(MODE == 2 ? 256 : 512, 1) void emodw_bwd_kernel(
         for (int mb = 0; mb < NB; ++mb) {
 #pragma unroll
           for (int m = 0; m < 2; ++m)
-            dya = CH_MFMA(lds_op(s_eops, op_bwd<NB>(b, mb, m) - BWD_BASE, lane), dzp[mb][m], dya);
+            dya = CH_MFMA(lds_op(s_eops, op_bwd<NB>(b, mb, m), lane), dzp[mb][m], dya);
         }
         f32x16 za;
         unpack_za_blk<NB>(p.z, b, za);
@@ -1696,29 +1681,12 @@ __global__ __launch_bounds__(MODE == 2 ? 256 : 512, 1) void emodw_bwd_kernel(
         const uint32_t off = ok ? (uint32_t)j * (uint32_t)(CO * 2) + (uint32_t)(32 * b + 16 * h) * 2u : OOB;
         st128(DA, off, __builtin_bit_cast(u32x4, pk[0]));
         st128(DA, ok ? off + 16u : OOB, __builtin_bit_cast(u32x4, pk[1]));
-        if constexpr (MODE == 4) {
-          tileN_put_packed(tdy, j, h, pk);
-          wave_sync();
-          col_sum1(tdy, lane, sa1[b]);
-          wave_sync();
-          float dyr[16], pr[16];      // the stored (rounded) dy_a times the stored z_a, rounded once more for the tile
-          unpack8(pk[0], reinterpret_cast<float(&)[8]>(dyr[0]));
-          unpack8(pk[1], reinterpret_cast<float(&)[8]>(dyr[8]));
-#pragma unroll
-          for (int r = 0; r < 16; ++r) pr[r] = dyr[r] * za[r];
-          bf16x8 pp[2] = {pack8(&pr[0]), pack8(&pr[8])};
-          tileN_put_packed(tdy, j, h, pp);
-          wave_sync();
-          col_sum1(tdy, lane, sa2[b]);
-          wave_sync();
-        } else {
-          bf16x8 zk[2] = {__builtin_bit_cast(bf16x8, p.z.q[b][0]), __builtin_bit_cast(bf16x8, p.z.q[b][1])};
-          tileN_put_packed(tdy, j, h, pk);
-          tileN_put_packed(tz, j, h, zk);
-          wave_sync();
-          col_sums2(tdy, tz, lane, sa1[b], sa2[b]);
-          wave_sync();
-        }
+        bf16x8 zk[2] = {__builtin_bit_cast(bf16x8, p.z.q[b][0]), __builtin_bit_cast(bf16x8, p.z.q[b][1])};
+        tileN_put_packed(tdy, j, h, pk);
+        tileN_put_packed(tz, j, h, zk);
+        wave_sync();
+        col_sums2(tdy, tz, lane, sa1[b], sa2[b]);
+        wave_sync();
       }
     } else if constexpr (MODE == 2) {
       wave_sync();
@@ -1751,15 +1719,15 @@ __global__ __launch_bounds__(MODE == 2 ? 256 : 512, 1) void emodw_bwd_kernel(
 // block w of z_a and of dz_b, applies BatchNorm_a + LeakyReLU, writes both as natural LDS tiles, and owns the rows of
 // dW_b of output block w (NB accumulator blocks = 128 registers at C_o = 256): after the block barrier it reads its own
 // dz_b tile and the y_a tiles of all input blocks through the transpose read.  No weight operands in LDS at all.
-// DYA (round 6, C_o = 256): the same launch also turns the stored dz_b into dy_a IN PLACE -- what emodw_bwd MODE 4 did in a
-// pass of its own (z_a + dz_b read once more, 1 KB per view).  Wavefront w keeps its 32 x CO slice of W_b^T in registers
+// Round 6: the same launch also turns the stored dz_b into dy_a IN PLACE -- what a pass of its own did before (z_a + dz_b
+// read once more, 1 KB per view; removed, last present in 2e12a5d).  Wavefront w keeps its 32 x CO slice of W_b^T in registers
 // (weight-stationary: 64 VGPRs at C_o = 256; the 128 KB of the whole orientation do not fit LDS next to the tiles), the
 // dz_b tiles of ALL blocks are in LDS anyway (natural tiles: what a lane stored is the packed B operand of its view), so
 // da[block w] = sum_mb W_b^T[w][mb] dz_b[mb] is 2 NB more matrix instructions per wavefront and tile, dy_a = leaky'(y_a) da
 // goes back over the wavefront's own 32 bytes of the view's dz_b row (every reader of the row takes it from LDS), and S of
-// BatchNorm_a are column sums through the wavefront's slot of the idle tile buffer, exactly as MODE 4 took them
-// (statistics of the stored, rounded values).
-template <int CO, bool DYA>
+// BatchNorm_a are column sums through the wavefront's slot of the idle tile buffer (statistics of the stored, rounded
+// values).
+template <int CO>
 __global__ __launch_bounds__(CO * 2, 1) void emodw_wgrad_coop_kernel(
     const int2* __restrict__ tiles, const int32_t* __restrict__ n_tiles_dev, const float* __restrict__ bna,
     bf16_t* __restrict__ dzst, const bf16_t* __restrict__ zst, float* __restrict__ dWb, const uint4* __restrict__ eops,
@@ -1779,14 +1747,12 @@ __global__ __launch_bounds__(CO * 2, 1) void emodw_wgrad_coop_kernel(
   }
   // the wavefront's slice of W_b^T: the first k-half of every block in registers (32 VGPRs), the second in LDS (64 KB for
   // the eight wavefronts: all 64 VGPRs next to the 128 accumulators of dW_b spilled)
-  __shared__ __attribute__((aligned(16))) uint4 s_wt[DYA ? NB : 1][DYA ? NB : 1][DYA ? 64 : 1];
-  bf16x8 wT[DYA ? NB : 1];
-  if constexpr (DYA) {
+  __shared__ __attribute__((aligned(16))) uint4 s_wt[NB][NB][64];
+  bf16x8 wT[NB];
 #pragma unroll
-    for (int mb = 0; mb < NB; ++mb) {
-      wT[mb] = load_op(eops, op_bwd<NB>(w, mb, 0), lane);
-      s_wt[w][mb][lane] = eops[op_bwd<NB>(w, mb, 1) * 64 + lane];
-    }
+  for (int mb = 0; mb < NB; ++mb) {
+    wT[mb] = load_op(eops, op_bwd<NB>(w, mb, 0), lane);
+    s_wt[w][mb][lane] = eops[op_bwd<NB>(w, mb, 1) * 64 + lane];
   }
   float sa1 = 0.f, sa2 = 0.f;
   const int n_tiles = n_tiles_dev[0];
@@ -1831,53 +1797,51 @@ __global__ __launch_bounds__(CO * 2, 1) void emodw_wgrad_coop_kernel(
     __syncthreads();       // tiles of all blocks written (the other buffer is free: its readers passed this barrier once more)
 #pragma unroll
     for (int b = 0; b < NB; ++b) accW[b] = wgradN(s_ta[buf][w], s_tb[buf][b], lane, accW[b]);      // dW_b[32 w ..][32 b ..]
-    if constexpr (DYA) {
-      f32x16 dya = {0};
+    f32x16 dya = {0};
 #pragma unroll
-      for (int mb = 0; mb < NB; ++mb) {
-        const bf16_t* row = s_ta[buf][mb] + j * TSB + 16 * h;        // the packed dz_b operand of view j, block mb
-        dya = CH_MFMA(wT[mb], *reinterpret_cast<const bf16x8*>(row), dya);
-        dya = CH_MFMA(__builtin_bit_cast(bf16x8, s_wt[w][mb][lane]), *reinterpret_cast<const bf16x8*>(row + 8), dya);
-      }
-      const uint32_t zv[8] = {zk0.x, zk0.y, zk0.z, zk0.w, zk1.x, zk1.y, zk1.z, zk1.w};
-      float tt[16], zaf[16];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {        // four channels at a time: two float4 of constants live
-        const float4 g4 = *reinterpret_cast<const float4*>(s_taba[w] + T_G * D + 16 * h + 4 * q);
-        const float4 b4 = *reinterpret_cast<const float4*>(s_taba[w] + T_B * D + 16 * h + 4 * q);
-        const float g_[4] = {g4.x, g4.y, g4.z, g4.w}, b_[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int r = 4 * q + e;
-          zaf[r] = (r & 1) ? __uint_as_float(zv[r >> 1] & 0xffff0000u) : __uint_as_float(zv[r >> 1] << 16);
-          tt[r] = __builtin_fmaf(zaf[r], g_[e], b_[e]) > 0.f ? dya[r] : SLOPE * dya[r];
-        }
-      }
-      bf16x8 pk[2] = {pack8(&tt[0]), pack8(&tt[8])};     // lanes without a view: dz_b = 0 -> dy_a = 0
-      {
-        const __amdgpu_buffer_rsrc_t DA = make_rsrc(dzst + (int64_t)ti.v0 * CO, (uint64_t)ti.nv * CO * 2);
-        const uint32_t off = ok_cur ? (uint32_t)j * (uint32_t)(CO * 2) + (uint32_t)(32 * w + 16 * h) * 2u : OOB;
-        st128(DA, off, __builtin_bit_cast(u32x4, pk[0]));
-        st128(DA, ok_cur ? off + 16u : OOB, __builtin_bit_cast(u32x4, pk[1]));
-      }
-      // S of BatchNorm_a: column sums of the stored dy_a and of dy_a z_a (rounded once more for the tile, as MODE 4 did)
-      // through this wavefront's slot of the OTHER buffer: nobody reads it before this wavefront refills it
-      bf16_t* tdy = s_ta[buf ^ 1][w];
-      tileN_put_packed(tdy, j, h, pk);
-      wave_sync();
-      col_sum1(tdy, lane, sa1);
-      wave_sync();
-      float dyr[16], pr[16];
-      unpack8(pk[0], reinterpret_cast<float(&)[8]>(dyr[0]));
-      unpack8(pk[1], reinterpret_cast<float(&)[8]>(dyr[8]));
-#pragma unroll
-      for (int r = 0; r < 16; ++r) pr[r] = dyr[r] * zaf[r];
-      bf16x8 pp[2] = {pack8(&pr[0]), pack8(&pr[8])};
-      tileN_put_packed(tdy, j, h, pp);
-      wave_sync();
-      col_sum1(tdy, lane, sa2);
-      wave_sync();
+    for (int mb = 0; mb < NB; ++mb) {
+      const bf16_t* row = s_ta[buf][mb] + j * TSB + 16 * h;        // the packed dz_b operand of view j, block mb
+      dya = CH_MFMA(wT[mb], *reinterpret_cast<const bf16x8*>(row), dya);
+      dya = CH_MFMA(__builtin_bit_cast(bf16x8, s_wt[w][mb][lane]), *reinterpret_cast<const bf16x8*>(row + 8), dya);
     }
+    const uint32_t zv[8] = {zk0.x, zk0.y, zk0.z, zk0.w, zk1.x, zk1.y, zk1.z, zk1.w};
+    float tt[16], zaf[16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {        // four channels at a time: two float4 of constants live
+      const float4 g4 = *reinterpret_cast<const float4*>(s_taba[w] + T_G * D + 16 * h + 4 * q);
+      const float4 b4 = *reinterpret_cast<const float4*>(s_taba[w] + T_B * D + 16 * h + 4 * q);
+      const float g_[4] = {g4.x, g4.y, g4.z, g4.w}, b_[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int r = 4 * q + e;
+        zaf[r] = (r & 1) ? __uint_as_float(zv[r >> 1] & 0xffff0000u) : __uint_as_float(zv[r >> 1] << 16);
+        tt[r] = __builtin_fmaf(zaf[r], g_[e], b_[e]) > 0.f ? dya[r] : SLOPE * dya[r];
+      }
+    }
+    bf16x8 pk[2] = {pack8(&tt[0]), pack8(&tt[8])};     // lanes without a view: dz_b = 0 -> dy_a = 0
+    {
+      const __amdgpu_buffer_rsrc_t DA = make_rsrc(dzst + (int64_t)ti.v0 * CO, (uint64_t)ti.nv * CO * 2);
+      const uint32_t off = ok_cur ? (uint32_t)j * (uint32_t)(CO * 2) + (uint32_t)(32 * w + 16 * h) * 2u : OOB;
+      st128(DA, off, __builtin_bit_cast(u32x4, pk[0]));
+      st128(DA, ok_cur ? off + 16u : OOB, __builtin_bit_cast(u32x4, pk[1]));
+    }
+    // S of BatchNorm_a: column sums of the stored dy_a and of dy_a z_a (rounded once more for the tile)
+    // through this wavefront's slot of the OTHER buffer: nobody reads it before this wavefront refills it
+    bf16_t* tdy = s_ta[buf ^ 1][w];
+    tileN_put_packed(tdy, j, h, pk);
+    wave_sync();
+    col_sum1(tdy, lane, sa1);
+    wave_sync();
+    float dyr[16], pr[16];
+    unpack8(pk[0], reinterpret_cast<float(&)[8]>(dyr[0]));
+    unpack8(pk[1], reinterpret_cast<float(&)[8]>(dyr[8]));
+#pragma unroll
+    for (int r = 0; r < 16; ++r) pr[r] = dyr[r] * zaf[r];
+    bf16x8 pp[2] = {pack8(&pr[0]), pack8(&pr[8])};
+    tileN_put_packed(tdy, j, h, pp);
+    wave_sync();
+    col_sum1(tdy, lane, sa2);
+    wave_sync();
   }
   // rows of the accumulator = image columns of the dz_b tile, columns = image columns of the y_a tile (cperm)
 #pragma unroll
@@ -1886,215 +1850,10 @@ __global__ __launch_bounds__(CO * 2, 1) void emodw_wgrad_coop_kernel(
     for (int r = 0; r < 16; ++r)
       atomicAdd(&dWb[(size_t)(32 * w + cperm(chan(r, h))) * CO + 32 * b + cperm(j)], accW[b][r]);
   }
-  if constexpr (DYA) {
-    const float a0 = sa1 + other_half(sa1), a1 = sa2 + other_half(sa2);
-    if (h == 0) {          // lane n of the first half-wave: image column n of block w = channel 32 w + cperm(n)
-      atomicAdd(&stats_a[32 * w + cperm(j)], (double)a0);
-      atomicAdd(&stats_a[CO + 32 * w + cperm(j)], (double)a1);
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// C_o = 256 backward WITHOUT the dz_b hand-off (round 6): two cooperative kernels that each evaluate dz_b of a 32-view
-// tile themselves -- the eight wavefronts of a block own one output block each and share the tile through LDS --
-//   WGRAD = false:  z_a -> y_a tiles | barrier | z_b[w] = W_b[w][:] y_a, dz_b[w] (BatchNorm_b backward of the attention's
-//                   value gradient) -> dz_b tiles | barrier | dy_a[w] = leaky'(y_a) W_b^T[w][:] dz_b -> bf16 [V][CO] (written
-//                   once), S of BatchNorm_a (column sums);
-//   WGRAD = true:   the same up to the dz_b tiles | barrier | dW_b[32 w ..][:] += dz_b[w]^T y_a (128 accumulator registers).
-// Both keep their W_b slice weight-stationary (WGRAD = false: W_b and W_b^T slices in 128 VGPRs; WGRAD = true: the first
-// k-halves of W_b in 32 VGPRs, the second in 64 KB of LDS next to the accumulators).  Against MODE 3 + the merged
-// cooperative kernel: 1 KB per view less (dz_b is never written or read: 512 + 512 B), 128 matrix instructions per tile
-// more (dz_b evaluated twice).  MEASURED (round 6): 25.9 against 23.3 ms for the pair it replaces -- 51 GB in 25.9 ms is
-// 2 TB/s and the matrix pipe is ~30 % busy: the eight wavefronts run in lockstep through two block barriers per tile and
-// one block per CU (233 / 246 VGPRs) leaves nothing to overlap them with.  Opt-in (DVA_EMOD_COOP2=1), kept for the A/B.  The bf16 rounding of dz_b is the stored one's (pack16), so the results are those of
-// the three-kernel form up to the order of the fp32 atomics.  One tile buffer per kind suffices: two barriers per tile.
-template <int CO, int G, bool WGRAD>
-__global__ __launch_bounds__(CO * 2, 1) void emodw_coop2_kernel(
-    const int2* __restrict__ tiles, const int32_t* __restrict__ n_tiles_dev, const uint4* __restrict__ eops,
-    const float* __restrict__ bna, const float* __restrict__ bnb, const float* __restrict__ smb,
-    const uint32_t* __restrict__ rec, const bf16_t* __restrict__ gout, bf16_t* __restrict__ da, float* __restrict__ dWb,
-    double* __restrict__ stats_a, const bf16_t* __restrict__ zst, int64_t V, int64_t N) {
-  constexpr int NB = CO / 32, GS = CO / G;
-  __shared__ __attribute__((aligned(16))) float s_taba[NB][TAB_FLOATS], s_tabb[NB][TAB_FLOATS];
-  __shared__ __attribute__((aligned(16))) bf16_t s_ta[NB][32 * TSB], s_tb[NB][32 * TSB];     // dz_b tiles | y_a tiles
-  __shared__ __attribute__((aligned(16))) uint4 s_wb[WGRAD ? NB : 1][WGRAD ? NB : 1][WGRAD ? 64 : 1];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    stage_tab_c(s_taba[b], bna, CO, 32 * b, nullptr);
-    stage_tab_c(s_tabb[b], bnb, CO, 32 * b, smb);
-  }
-  // weight-stationary slices of this wavefront's output block
-  bf16x8 wB0[NB], wB1[WGRAD ? 1 : NB], wT[WGRAD ? 1 : NB][2];
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    wB0[b] = load_op(eops, op_fwd<NB>(w, b, 0), lane);
-    if constexpr (WGRAD) {
-      s_wb[w][b][lane] = eops[op_fwd<NB>(w, b, 1) * 64 + lane];
-    } else {
-      wB1[b] = load_op(eops, op_fwd<NB>(w, b, 1), lane);
-      wT[b][0] = load_op(eops, op_bwd<NB>(w, b, 0), lane);
-      wT[b][1] = load_op(eops, op_bwd<NB>(w, b, 1), lane);
-    }
-  }
-  __syncthreads();
-  f32x16 accW[WGRAD ? NB : 1];
-#pragma unroll
-  for (int b = 0; b < (WGRAD ? NB : 1); ++b) {
-    const f32x16 zero = {0};
-    accW[b] = zero;
-  }
-  float sa1 = 0.f, sa2 = 0.f;
-  const __amdgpu_buffer_rsrc_t RC = make_rsrc(rec, (uint64_t)V * 16), GO = make_rsrc(gout, (uint64_t)N * CO * 2);
-  const int n_tiles = n_tiles_dev[0];
-  const int t0 = (int)((int64_t)n_tiles * blockIdx.x / gridDim.x), t1 = (int)((int64_t)n_tiles * (blockIdx.x + 1) / gridDim.x);
-  auto fetch = [&](int t, u32x4 (&z)[2], u32x4& rc, bool& ok, TileInfo& ti) {
-    ti = get_tile(tiles, t);
-    ok = j < ti.nv;
-    const __amdgpu_buffer_rsrc_t Z = make_rsrc(zst + (int64_t)ti.v0 * CO, (uint64_t)ti.nv * CO * 2);
-    const uint32_t off = ok ? (uint32_t)j * (uint32_t)(CO * 2) + (uint32_t)(32 * w + 16 * h) * 2u : OOB;
-    z[0] = ld128(Z, off);
-    z[1] = ld128(Z, ok ? off + 16u : OOB);
-    rc = ld128(RC, ok ? (uint32_t)(ti.v0 + j) * 16u : OOB);
-  };
-  u32x4 zq[2], rq;
-  bool ok = false;
-  TileInfo ti_next;
-  ti_next.v0 = ti_next.nv = ti_next.frag = 0;
-  if (t0 < t1) fetch(t0, zq, rq, ok, ti_next);
-  for (int t = t0; t < t1; ++t) {
-    const bool ok_cur = ok;
-    const uint32_t keep = ok_cur ? 0xffffffffu : 0u;
-    const TileInfo ti = ti_next;
-    const u32x4 zk0 = zq[0], zk1 = zq[1], rc = rq;
-    {
-      // this wavefront's block of y_a = leaky(BatchNorm_a(z_a)) (0 for lanes without a view) -> its tile
-      f32x16 za;
-      const uint32_t v[8] = {zk0.x, zk0.y, zk0.z, zk0.w, zk1.x, zk1.y, zk1.z, zk1.w};
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        za[2 * i] = __uint_as_float(v[i] << 16);
-        za[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u);
-      }
-      bf16x8 a[2];
-      act_pack(za, s_taba[w], h, keep, a);
-      tileN_put_packed(s_tb[w], j, h, a);
-    }
-    // the value gradient of this block, requested before the first barrier: (gate attention)[g] grad_out[point][ch]
-    u32x2 gv[4];
-    {
-      const uint32_t pid = rc.x;
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        gv[q] = ld64(GO, ok_cur ? pid * (uint32_t)(CO * 2) + (uint32_t)(32 * w + 8 * q + 4 * h) * 2u : OOB);
-    }
-    if (t + 1 < t1) fetch(t + 1, zq, rq, ok, ti_next);       // the next tile's loads fly during the products
-    __syncthreads();       // y_a tiles of all blocks written (and: the dz_b tiles of the previous tile are consumed)
-    // ---- z_b[w] = sum_b W_b[w][b] y_a[b]
-    f32x16 zb = {0};
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      const bf16_t* row = s_tb[b] + j * TSB + 16 * h;          // the packed y_a operand of view j, block b
-      zb = CH_MFMA(wB0[b], *reinterpret_cast<const bf16x8*>(row), zb);
-      if constexpr (WGRAD) zb = CH_MFMA(__builtin_bit_cast(bf16x8, s_wb[w][b][lane]), *reinterpret_cast<const bf16x8*>(row + 8), zb);
-      else zb = CH_MFMA(wB1[b], *reinterpret_cast<const bf16x8*>(row + 8), zb);
-    }
-    // ---- dz_b[w]: dy_b = leaky'(y_b) d value, dz_b = G_b dy_b - K1 - K2 z_b (as emodw_bwd MODE 3)
-    {
-      const float ga4[4] = {__uint_as_float(rc.y << 16), __uint_as_float(rc.y & 0xffff0000u),
-                            __uint_as_float(rc.z << 16), __uint_as_float(rc.z & 0xffff0000u)};
-      const float gg = ga4[G == 1 ? 0 : (32 * w) / GS];      // a 32-channel block lies inside one group (GS >= 32)
-      static_assert(GS % 32 == 0, "a block inside one channel group");
-      float dz[16];
-      asm volatile("" ::: "memory");
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {        // four channels at a time: sixteen constants live instead of 64 (register budget)
-        const float dy[4] = {gg * __uint_as_float(gv[q].x << 16), gg * __uint_as_float(gv[q].x & 0xffff0000u),
-                             gg * __uint_as_float(gv[q].y << 16), gg * __uint_as_float(gv[q].y & 0xffff0000u)};
-        const int o = 16 * h + 4 * q;
-        const float4 g4 = *reinterpret_cast<const float4*>(s_tabb[w] + T_G * D + o);
-        const float4 b4 = *reinterpret_cast<const float4*>(s_tabb[w] + T_B * D + o);
-        const float4 a4 = *reinterpret_cast<const float4*>(s_tabb[w] + T_K1 * D + o);
-        const float4 c4 = *reinterpret_cast<const float4*>(s_tabb[w] + T_K2 * D + o);
-        const float g_[4] = {g4.x, g4.y, g4.z, g4.w}, b_[4] = {b4.x, b4.y, b4.z, b4.w};
-        const float k1[4] = {a4.x, a4.y, a4.z, a4.w}, k2[4] = {c4.x, c4.y, c4.z, c4.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int r = 4 * q + e;
-          const float dyb = __builtin_fmaf(zb[r], g_[e], b_[e]) > 0.f ? dy[e] : SLOPE * dy[e];
-          dz[r] = __builtin_fmaf(-k2[e], zb[r], __builtin_fmaf(g_[e], dyb, -k1[e]));       // = bn_bwd_apply
-        }
-      }
-      bf16x8 t2[2];
-      pack16(dz, keep, t2);
-      tileN_put_packed(s_ta[w], j, h, t2);
-    }
-    __syncthreads();       // dz_b tiles of all blocks written (and: the y_a tiles are consumed by the products above)
-    if constexpr (WGRAD) {
-#pragma unroll
-      for (int b = 0; b < NB; ++b) accW[b] = wgradN(s_ta[w], s_tb[b], lane, accW[b]);      // dW_b[32 w ..][32 b ..]
-    } else {
-      f32x16 dya = {0};
-#pragma unroll
-      for (int mb = 0; mb < NB; ++mb) {
-        const bf16_t* row = s_ta[mb] + j * TSB + 16 * h;        // the packed dz_b operand of view j, block mb
-        dya = CH_MFMA(wT[mb][0], *reinterpret_cast<const bf16x8*>(row), dya);
-        dya = CH_MFMA(wT[mb][1], *reinterpret_cast<const bf16x8*>(row + 8), dya);
-      }
-      const uint32_t zv[8] = {zk0.x, zk0.y, zk0.z, zk0.w, zk1.x, zk1.y, zk1.z, zk1.w};
-      float tt[16], zaf[16];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float4 g4 = *reinterpret_cast<const float4*>(s_taba[w] + T_G * D + 16 * h + 4 * q);
-        const float4 b4 = *reinterpret_cast<const float4*>(s_taba[w] + T_B * D + 16 * h + 4 * q);
-        const float g_[4] = {g4.x, g4.y, g4.z, g4.w}, b_[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int r = 4 * q + e;
-          zaf[r] = (r & 1) ? __uint_as_float(zv[r >> 1] & 0xffff0000u) : __uint_as_float(zv[r >> 1] << 16);
-          tt[r] = __builtin_fmaf(zaf[r], g_[e], b_[e]) > 0.f ? dya[r] : SLOPE * dya[r];
-        }
-      }
-      bf16x8 pk[2] = {pack8(&tt[0]), pack8(&tt[8])};     // lanes without a view: dz_b = 0 -> dy_a = 0
-      {
-        const __amdgpu_buffer_rsrc_t DA = make_rsrc(da + (int64_t)ti.v0 * CO, (uint64_t)ti.nv * CO * 2);
-        const uint32_t off = ok_cur ? (uint32_t)j * (uint32_t)(CO * 2) + (uint32_t)(32 * w + 16 * h) * 2u : OOB;
-        st128(DA, off, __builtin_bit_cast(u32x4, pk[0]));
-        st128(DA, ok_cur ? off + 16u : OOB, __builtin_bit_cast(u32x4, pk[1]));
-      }
-      // S of BatchNorm_a through this wavefront's own y_a tile: every reader passed the second barrier, and this
-      // wavefront refills the tile before the next first barrier
-      bf16_t* tdy = s_tb[w];
-      tileN_put_packed(tdy, j, h, pk);
-      wave_sync();
-      col_sum1(tdy, lane, sa1);
-      wave_sync();
-      float dyr[16], pr[16];
-      unpack8(pk[0], reinterpret_cast<float(&)[8]>(dyr[0]));
-      unpack8(pk[1], reinterpret_cast<float(&)[8]>(dyr[8]));
-#pragma unroll
-      for (int r = 0; r < 16; ++r) pr[r] = dyr[r] * zaf[r];
-      bf16x8 pp[2] = {pack8(&pr[0]), pack8(&pr[8])};
-      tileN_put_packed(tdy, j, h, pp);
-      wave_sync();
-      col_sum1(tdy, lane, sa2);
-      wave_sync();
-    }
-  }
-  if constexpr (WGRAD) {
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        atomicAdd(&dWb[(size_t)(32 * w + cperm(chan(r, h))) * CO + 32 * b + cperm(j)], accW[b][r]);
-    }
-  } else {
-    const float a0 = sa1 + other_half(sa1), a1 = sa2 + other_half(sa2);
-    if (h == 0) {
-      atomicAdd(&stats_a[32 * w + cperm(j)], (double)a0);
-      atomicAdd(&stats_a[CO + 32 * w + cperm(j)], (double)a1);
-    }
+  const float a0 = sa1 + other_half(sa1), a1 = sa2 + other_half(sa2);
+  if (h == 0) {          // lane n of the first half-wave: image column n of block w = channel 32 w + cperm(n)
+    atomicAdd(&stats_a[32 * w + cperm(j)], (double)a0);
+    atomicAdd(&stats_a[CO + 32 * w + cperm(j)], (double)a1);
   }
 }
 
@@ -2231,9 +1990,9 @@ int dva_emod_attn_bwd(const float* scores, const int32_t* view_point, const void
     return DVA_ERR_INVALID;
   DVA_EMOD_CHECK_SIZES();
   if (n_points * (int64_t)C_out * 2 > 0xfffffff0ll) return DVA_ERR_UNSUPPORTED;
-  static const int bpc32 = tune_int("DVA_EMOD_ABWD_BPC", 4);      // read once (getenv), like the other switches
-  static const int occ128 = tune_int("DVA_EMOD_ABWD128_OCC", 2);  // C_out = 128: two wavefronts per SIMD (206 - 215 VGPRs)
-  const dim3 grid(chain_grid(C_out == 32 ? bpc32 : (C_out == 128 ? occ128 : (C_out == 256 ? 1 : 2)))), block(C_out == 256 ? 512 : 256);
+  // blocks per CU = the kernel's wavefronts per SIMD (the OCC default of its template): 4 / 2 / 2 / 1 at C_out = 32 / 64 /
+  // 128 / 256 (C_out = 128: two wavefronts per SIMD at 206 - 215 VGPRs)
+  const dim3 grid(chain_grid(C_out == 32 ? 4 : (C_out == 256 ? 1 : 2))), block(C_out == 256 ? 512 : 256);
   hipStream_t s = (hipStream_t)stream;
 #define DVA_EMOD_BWD(CO_, G_)                                                                                      \
   hipLaunchKernelGGL((emod_attn_bwd_kernel<CO_, G_>), grid, block, 0, s, scores, view_point, (const int2*)tiles,     \
@@ -2248,23 +2007,10 @@ int dva_emod_attn_bwd(const float* scores, const int32_t* view_point, const void
     case 64 * 8 + 1: DVA_EMOD_BWD(64, 1); break;
     case 64 * 8 + 2: DVA_EMOD_BWD(64, 2); break;
     case 64 * 8 + 4: DVA_EMOD_BWD(64, 4); break;
-#define DVA_EMOD_BWD_O(CO_, G_, O_)                                                                                \
-  hipLaunchKernelGGL((emod_attn_bwd_kernel<CO_, G_, O_>), grid, block, 0, s, scores, view_point, (const int2*)tiles, \
-                     n_tiles, (const bf16_t*)Y, (const int4*)tap_rows, (const float4*)tap_weights,                   \
-                     (const uint4*)eops, bn_a, bn_b, ptr, gate_w, gate_b, (const bf16_t*)grad_out,                   \
-                     (const bf16_t*)out, grad_scores, (uint32_t*)view_rec, grad_gate_wb, stats_b,                     \
-                     (const bf16_t*)z_a, scaling, eps, n_views, n_points, n_rows)
-#define DVA_EMOD_BWD128(G_)                    \
-  do {                                         \
-    if (occ128 == 2) DVA_EMOD_BWD_O(128, G_, 2); \
-    else DVA_EMOD_BWD_O(128, G_, 1);             \
-  } while (0)
-    case 128 * 8 + 1: DVA_EMOD_BWD128(1); break;
-    case 128 * 8 + 2: DVA_EMOD_BWD128(2); break;
-    case 128 * 8 + 4: DVA_EMOD_BWD128(4); break;
-    case 256 * 8 + 4: DVA_EMOD_BWD_O(256, 4, 1); break;
-#undef DVA_EMOD_BWD128
-#undef DVA_EMOD_BWD_O
+    case 128 * 8 + 1: DVA_EMOD_BWD(128, 1); break;
+    case 128 * 8 + 2: DVA_EMOD_BWD(128, 2); break;
+    case 128 * 8 + 4: DVA_EMOD_BWD(128, 4); break;
+    case 256 * 8 + 4: DVA_EMOD_BWD(256, 4); break;
     default: return DVA_ERR_UNSUPPORTED;
   }
 #undef DVA_EMOD_BWD
@@ -2332,42 +2078,14 @@ int dva_emod_bwd(int32_t stage, const void* Y, const int32_t* tap_rows, const fl
       case 128 * 8 + 4: DVA_EMODW(4); break;
 #undef DVA_EMODW
       case 256 * 8 + 4:
-        {
-          // round 6 (second form, A/B): no dz_b hand-off at all -- two cooperative kernels that each evaluate dz_b themselves
-          // (emodw_coop2_kernel).  Parity-green and SLOWER (25.9 against 23.3 ms, profiles/r06_emod_coop2_ab.json): with one
-          // 512-thread block per CU nothing overlaps its two barriers per tile.  DVA_EMOD_COOP2=1 selects it; default:
-          // MODE 3 + the merged cooperative kernel below
-          static const int coop2 = tune_int("DVA_EMOD_COOP2", 0);
-          if (coop2) {
-            hipLaunchKernelGGL((emodw_coop2_kernel<256, 4, false>), dim3(chain_grid(1)), dim3(512), 0, s, (const int2*)tiles,
-                               n_tiles, (const uint4*)eops, bn_a, bn_b, sm_b, (const uint32_t*)view_rec,
-                               (const bf16_t*)grad_out, (bf16_t*)da, dWb, stats_a, (const bf16_t*)z_a, n_views, n_points);
-            hipLaunchKernelGGL((emodw_coop2_kernel<256, 4, true>), dim3(chain_grid(1)), dim3(512), 0, s, (const int2*)tiles,
-                               n_tiles, (const uint4*)eops, bn_a, bn_b, sm_b, (const uint32_t*)view_rec,
-                               (const bf16_t*)grad_out, (bf16_t*)da, dWb, stats_a, (const bf16_t*)z_a, n_views, n_points);
-            break;
-          }
-        }
         // W_b (128 KB per orientation) does not fit LDS twice: dz_b -> `da`, dW_b from the stored dz_b, dy_a in place
         hipLaunchKernelGGL((emodw_bwd_kernel<256, 4, 3>), dim3(chain_grid(1)), dim3(512), 0, s, (const int2*)tiles, n_tiles,
                            (const uint4*)eops, bn_a, bn_b, sm_b, (const uint32_t*)view_rec, (const bf16_t*)grad_out,
                            (bf16_t*)da, dWb, stats_a, (const bf16_t*)z_a, n_views, n_points);
-        {
-          // round 6: dW_b AND dy_a (in place) + S of BatchNorm_a from the stored dz_b in ONE launch (weight-stationary W_b^T
-          // slices); DVA_EMOD_COOP_DYA=0: the round-4 pair (emodw_wgrad_coop + emodw_bwd MODE 4), the A/B
-          static const int coop_dya = tune_int("DVA_EMOD_COOP_DYA", 1);
-          if (coop_dya) {
-            hipLaunchKernelGGL((emodw_wgrad_coop_kernel<256, true>), dim3(chain_grid(1)), dim3(512), 0, s,
-                               (const int2*)tiles, n_tiles, bn_a, (bf16_t*)da, (const bf16_t*)z_a, dWb, (const uint4*)eops,
-                               stats_a);
-            break;
-          }
-        }
-        hipLaunchKernelGGL((emodw_wgrad_coop_kernel<256, false>), dim3(chain_grid(1)), dim3(512), 0, s, (const int2*)tiles,
-                           n_tiles, bn_a, (bf16_t*)da, (const bf16_t*)z_a, dWb, (const uint4*)eops, stats_a);
-        hipLaunchKernelGGL((emodw_bwd_kernel<256, 4, 4>), dim3(chain_grid(1)), dim3(512), 0, s, (const int2*)tiles, n_tiles,
-                           (const uint4*)eops, bn_a, bn_b, sm_b, (const uint32_t*)view_rec, (const bf16_t*)grad_out,
-                           (bf16_t*)da, dWb, stats_a, (const bf16_t*)z_a, n_views, n_points);
+        // round 6: dW_b AND dy_a (in place) + S of BatchNorm_a from the stored dz_b in ONE launch (weight-stationary W_b^T
+        // slices): 74.6 -> 69.8 ms at 512 -> 256 against the round-4 pair of launches (profiles/r06_emod_coop_dya_ab.json)
+        hipLaunchKernelGGL((emodw_wgrad_coop_kernel<256>), dim3(chain_grid(1)), dim3(512), 0, s, (const int2*)tiles, n_tiles,
+                           bn_a, (bf16_t*)da, (const bf16_t*)z_a, dWb, (const uint4*)eops, stats_a);
         break;
       default: return DVA_ERR_UNSUPPORTED;
     }

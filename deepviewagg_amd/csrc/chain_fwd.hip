@@ -1189,8 +1189,7 @@ int dva_chain_stats(int32_t layer, const float* x_map, const int32_t* view_point
     return DVA_ERR_INVALID;
   if (n_views * 32 > 0xfffffff0ll || n_points * 128 > 0xfffffff0ll) return DVA_ERR_UNSUPPORTED;
   // layer 5 fits 116 VGPRs: four blocks per CU; layer 6 (150) three
-  static const int bpc5 = tune_int("DVA_STATS5_BPC", 4);      // read once
-  const dim3 grid(chain_grid(layer == 5 ? bpc5 : 3)), block(256);
+  const dim3 grid(chain_grid(layer == 5 ? 4 : 3)), block(256);
   hipStream_t s = (hipStream_t)stream;
 #define DVA_STATS_MID(L_)                                                                                        \
   hipLaunchKernelGGL((stats_mid_kernel<L_>), grid, block, 0, s, x_map, view_point, u, (const int2*)tiles, n_tiles, \
@@ -1236,8 +1235,7 @@ int dva_chain_attn_fwd_dt(const float* x_map, const int32_t* view_point, const f
   if (n_views * 32 > 0xfffffff0ll || n_points * 128 > 0xfffffff0ll || n_rows * C * 2 > 0xfffffff0ll ||
       n_points * C * 2 > 0xfffffff0ll)
     return DVA_ERR_UNSUPPORTED;
-  static const int occ_env = getenv("DVA_ATTN_FWD_OCC") ? atoi(getenv("DVA_ATTN_FWD_OCC")) : 0;   // A/B: 3 or 4
-  const bool dense = occ_env ? (occ_env == 4 && C <= 64) : (C <= 64 && n_views >= 24 * n_points);   // mostly one point per tile
+  const bool dense = C <= 64 && n_views >= 24 * n_points;   // mostly one point per tile
   const dim3 grid(chain_grid(dense ? 4 : 3)), block(256);
   hipStream_t s = (hipStream_t)stream;
 #define DVA_ATTN_FWD_T(LPR_, G_, OCC_, T_)                                                                      \

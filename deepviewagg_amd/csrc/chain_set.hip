@@ -203,8 +203,7 @@ int dva_chain_set_fwd(int32_t stage, const float* pooled, const int64_t* ptr, co
     return DVA_ERR_INVALID;
   if (n_points * 128 > 0xfffffff0ll) return DVA_ERR_UNSUPPORTED;
   const int64_t tiles = (n_points + 31) / 32;
-  static const int bpc = tune_int("DVA_SET_FWD_BPC", 2);       // blocks per CU of the grid (read once)
-  const int cap = chain_grid(bpc);
+  const int cap = chain_grid(2);      // two blocks per CU
   // at least 8 tiles per wavefront: every block pays the 24 KB operand table and the flush (3e5 points: 170 -> 149 us
   // for the three backward stages with half the blocks)
   const int64_t want = (tiles + 31) / 32;
@@ -234,8 +233,7 @@ int dva_chain_set_bwd(int32_t stage, const float* pooled, const int64_t* ptr, co
     return DVA_ERR_INVALID;
   if (n_points * 128 > 0xfffffff0ll) return DVA_ERR_UNSUPPORTED;
   const int64_t tiles = (n_points + 31) / 32;
-  static const int bpc = tune_int("DVA_SET_BWD_BPC", 2);       // blocks per CU of the grid (read once)
-  const int cap = chain_grid(bpc);
+  const int cap = chain_grid(2);      // two blocks per CU
   const int64_t want = (tiles + 31) / 32;      // at least 8 tiles per wavefront (see dva_chain_set_fwd)
   const dim3 grid((int)(want < cap ? want : cap)), block(256);
   hipStream_t s = (hipStream_t)stream;

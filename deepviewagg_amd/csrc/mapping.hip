@@ -1111,10 +1111,9 @@ int dva_visibility_batch(const float* xyz, int64_t n, const dva_camera* cam0, co
                      idx1, simg, dist, xp, yp, cnt);
   hipLaunchKernelGGL(splat_batch_kernel, dim3(grid_for(nc)), dim3(256), 0, s, xyz, idx1, simg, dist, xp, yp, cams_dev,
                      cnt, splat);
-  static const int tiled = tune_int("DVA_ZBUF_TILED", 1);
   // (box corners are packed into 16 bits; tile_off is an int32 scan of up to ZT_BIG entries per candidate: beyond
   //  2^31 - 1 possible entries the whole batch takes the atomic plane)
-  if (tiled && cam0->img_w < 65536 && Hc < 65536 && nc * ZT_BIG <= 0x7fffffffLL) {
+  if (cam0->img_w < 65536 && Hc < 65536 && nc * ZT_BIG <= 0x7fffffffLL) {
     int32_t* tile_count = (int32_t*)(ws + L.tile_count);
     int32_t* tile_cursor = (int32_t*)(ws + L.tile_cursor);
     int32_t* ctl = (int32_t*)(ws + L.ctl);

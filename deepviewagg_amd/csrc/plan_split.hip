@@ -26,14 +26,11 @@ constexpr int BINS = 512;
 constexpr int LO_BITS = 9;
 constexpr int HEAD_INTS = 4096;   // tot[512] | bucket_start[513] | tile_start[513] (padded) | order[512] at 2048
 
-// DVA_PLAN_TILE = 4096 (default: 512 threads, 76 KB of LDS, two workgroups per CU whose load and write-out phases overlap,
-// 128-byte runs that the XCD-aware tile order below pairs up in one L2) or 8192 (1024 threads, 148 KB, one workgroup per
-// CU, 256-byte runs: pass A 0.29 against 0.23 ms, the build 0.24 against 0.26 ms; before the XCD-aware order the larger
-// tile was the faster one); read once, build and record passes of a plan must agree
-static inline int tile_size() {
-  static const int t = tune_int("DVA_PLAN_TILE", 4096) == 8192 ? 8192 : 4096;
-  return t;
-}
+// The tile of the build and of the record passes: 4096 entries = 512 threads, 76 KB of LDS, two workgroups per CU whose
+// load and write-out phases overlap, 128-byte runs that the XCD-aware tile order below pairs up in one L2.  (8192: 1024
+// threads, 148 KB, one workgroup per CU, 256-byte runs -- pass A 0.29 against 0.23 ms, the build 0.24 against 0.26 ms;
+// before the XCD-aware order the larger tile was the faster one.)
+constexpr int PLAN_TILE = 4096;
 
 struct Layout {
   int64_t nt, nb, ntb;
@@ -46,8 +43,7 @@ static inline bool eligible(int64_t n_views, int64_t n_rows) {
 
 static inline Layout layout(int64_t n, int64_t n_rows) {
   Layout L;
-  const int TILE = tile_size();
-  L.nt = (n + TILE - 1) / TILE;
+  L.nt = (n + PLAN_TILE - 1) / PLAN_TILE;
   L.nb = (n_rows + BINS - 1) / BINS;
   L.ntb = L.nt + L.nb;
   L.off_tot = 0;
@@ -235,7 +231,7 @@ __device__ __forceinline__ uint64_t match_digit(int d, bool valid) {
 }
 
 // keys NULL (REC_A): word 3 of the records already is the row key (dva_chain_attn_bwd writes it).
-// One workgroup per tile, in an XCD-aware order (xcd_order, gridDim.x a multiple of 8): workgroup i runs on XCD i % 8, so
+// One workgroup per tile, in an XCD-aware order (gridDim.x a multiple of 8): workgroup i runs on XCD i % 8, so
 // XCD x takes the x-th eighth of the tiles and its CUs hold NEIGHBOURING tiles at any time -- the two halves of a 128-byte
 // line shared by the runs of two neighbouring tiles then meet in one L2 instead of leaving two partial writes (0.66 ->
 // 0.56 ms for the two record passes).  Persistent workgroups that request the next tile's entries under the write-out of
@@ -251,7 +247,7 @@ __global__ __launch_bounds__(TILE / IPT) void scatter_kernel(const uint32_t* __r
                                                              const int32_t* __restrict__ tile_start,
                                                              const int4* __restrict__ desc,
                                                              const int32_t* __restrict__ off,
-                                                             const int32_t* __restrict__ row_ptr, int xcd_order) {
+                                                             const int32_t* __restrict__ row_ptr) {
   constexpr int THREADS = TILE / IPT, WAVES = THREADS / 64;
   typedef typename Elem<MODE>::type E;
   static_assert(RW == 4 || (RW == 8 && MODE == MODE_REC_A), "32-byte records only go through pass A");
@@ -264,7 +260,7 @@ __global__ __launch_bounds__(TILE / IPT) void scatter_kernel(const uint32_t* __r
   static_assert(THREADS >= BINS, "one thread per digit in the scan over the wavefronts");
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int n_tiles = MODE == MODE_REC_B ? tile_start[nb] : (int)nt;
-  const int tile = xcd_order ? ((int)blockIdx.x & 7) * ((int)gridDim.x >> 3) + ((int)blockIdx.x >> 3) : (int)blockIdx.x;
+  const int tile = ((int)blockIdx.x & 7) * ((int)gridDim.x >> 3) + ((int)blockIdx.x >> 3);
   if (tile >= n_tiles) return;
   int b = 0, count;
   int64_t start;
@@ -618,13 +614,8 @@ __global__ __launch_bounds__(1024) void bucket_rows_grad_f32_kernel(const uint4*
 template <int C, typename T>
 static void bucket_rows_grad(const uint4* rec, const T* gout, T* grows, int64_t n_rows, int G, int nb,
                              const int32_t* bstart, const int32_t* order, hipStream_t s) {
-  static const int bt = tune_int("DVA_PLAN_BT", 8192);
-  if (bt == 2048)
-    hipLaunchKernelGGL((bucket_rows_grad_kernel<C, 2048, T>), dim3(nb), dim3(1024), 0, s, rec, gout, grows, n_rows, G, bstart, order);
-  else if (bt == 4096)
-    hipLaunchKernelGGL((bucket_rows_grad_kernel<C, 4096, T>), dim3(nb), dim3(1024), 0, s, rec, gout, grows, n_rows, G, bstart, order);
-  else
-    hipLaunchKernelGGL((bucket_rows_grad_kernel<C, 8192, T>), dim3(nb), dim3(1024), 0, s, rec, gout, grows, n_rows, G, bstart, order);
+  // the kernel's own tile: 8192 records 0.63 ms, 4096 0.65, 2048 0.78
+  hipLaunchKernelGGL((bucket_rows_grad_kernel<C, 8192, T>), dim3(nb), dim3(1024), 0, s, rec, gout, grows, n_rows, G, bstart, order);
 }
 
 }  // namespace ps
@@ -642,42 +633,34 @@ static inline Tables tables_of(void* tables, const Layout& L) {
           (int32_t*)(tb + L.off_order), (int32_t*)(tb + L.off_a), (int32_t*)(tb + L.off_b), (int4*)(tb + L.off_desc)};
 }
 
-// grid of a scatter pass: its tiles rounded up to a multiple of 8 for the XCD-aware order (the extra workgroups exit);
-// DVA_PLAN_XCD=0: plain order, the A/B
-static inline bool xcd_on() {
-  static const int on = tune_int("DVA_PLAN_XCD", 1);
-  return on != 0;
-}
-static inline unsigned scatter_grid(int64_t tiles) { return (unsigned)(xcd_on() ? (tiles + 7) / 8 * 8 : tiles); }
+// grid of a scatter pass: its tiles rounded up to a multiple of 8 for the XCD-aware order (the extra workgroups exit)
+static inline unsigned scatter_grid(int64_t tiles) { return (unsigned)((tiles + 7) / 8 * 8); }
 
-template <int TILE>
 static void build(const uint32_t* keys, int64_t n, int64_t n_rows, int32_t* row_ptr, int32_t* counts, const Layout& L,
                   const Tables& T, void* scratch, hipStream_t s) {
-  constexpr int THREADS = TILE / IPT;
+  constexpr int TILE = PLAN_TILE, THREADS = TILE / IPT;
   const int nb = (int)L.nb;
   hipLaunchKernelGGL(hist_hi_kernel<TILE>, dim3((unsigned)L.nt), dim3(THREADS), 0, s, keys, n, nb, L.nt, T.offA);
   hipLaunchKernelGGL(scan_tiles_kernel, dim3(nb), dim3(256), 0, s, T.offA, L.nt, T.tot);
   hipLaunchKernelGGL(bucket_starts_kernel, dim3(1), dim3(BINS), 0, s, T.tot, nb, TILE, T.bstart, T.tstart, T.desc, T.order);
   hipLaunchKernelGGL((scatter_kernel<MODE_LOWS, TILE>), dim3(scatter_grid(L.nt)), dim3(THREADS), 0, s, keys,
                      (const uint4*)nullptr, scratch, n, nb, n_rows, L.nt, T.bstart, T.tstart, T.desc, T.offA,
-                     (const int32_t*)nullptr, (int)xcd_on());
+                     (const int32_t*)nullptr);
   hipLaunchKernelGGL(hist_lo_kernel<TILE>, dim3((unsigned)L.ntb), dim3(THREADS), 0, s, (const uint16_t*)scratch, nb,
                      T.tstart, T.desc, T.offB);
   hipLaunchKernelGGL(scan_rows_kernel, dim3(nb), dim3(BINS), 0, s, T.offB, T.bstart, T.tstart, n_rows, n, row_ptr, counts);
 }
 
-template <int TILE>
 static void sort_records(const uint32_t* keys, const uint4* rec, int64_t n, int64_t n_rows, const int32_t* row_ptr,
                          const Layout& L, const Tables& T, void* buf, void* out, hipStream_t s) {
-  constexpr int THREADS = TILE / IPT;
+  constexpr int TILE = PLAN_TILE, THREADS = TILE / IPT;
   const int nb = (int)L.nb;
   hipLaunchKernelGGL((scatter_kernel<MODE_REC_A, TILE>), dim3(scatter_grid(L.nt)), dim3(THREADS), 0, s, keys, rec,
-                     buf, n, nb, n_rows, L.nt, T.bstart, T.tstart, T.desc, T.offA, (const int32_t*)nullptr,
-                     (int)xcd_on());
+                     buf, n, nb, n_rows, L.nt, T.bstart, T.tstart, T.desc, T.offA, (const int32_t*)nullptr);
   if (!out) return;                 // pass A only: the caller consumes the bucket-ordered records (dva_plan_split_rows_grad)
   hipLaunchKernelGGL((scatter_kernel<MODE_REC_B, TILE>), dim3(scatter_grid(L.ntb)), dim3(THREADS), 0, s,
                      (const uint32_t*)nullptr, (const uint4*)buf, out, n, nb, n_rows, L.nt, T.bstart, T.tstart, T.desc,
-                     T.offB, row_ptr, (int)xcd_on());
+                     T.offB, row_ptr);
 }
 }  // namespace ps
 }  // namespace dva
@@ -700,10 +683,7 @@ int dva_plan_split_build(const int32_t* row_idx, int64_t n_views, int64_t n_rows
   const ps::Layout L = ps::layout(n_views, n_rows);
   if ((int64_t)L.total > tables_bytes || scratch_bytes < n_views * 2) return DVA_ERR_INVALID;
   const ps::Tables T = ps::tables_of(tables, L);
-  if (ps::tile_size() == 4096)
-    ps::build<4096>((const uint32_t*)row_idx, n_views, n_rows, row_ptr, counts, L, T, scratch, (hipStream_t)stream);
-  else
-    ps::build<8192>((const uint32_t*)row_idx, n_views, n_rows, row_ptr, counts, L, T, scratch, (hipStream_t)stream);
+  ps::build((const uint32_t*)row_idx, n_views, n_rows, row_ptr, counts, L, T, scratch, (hipStream_t)stream);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -718,12 +698,8 @@ int dva_plan_split_sort_records(const int32_t* row_idx, const void* rec, int64_t
   const ps::Layout L = ps::layout(n_views, n_rows);
   if ((int64_t)L.total > tables_bytes) return DVA_ERR_INVALID;
   const ps::Tables T = ps::tables_of(const_cast<void*>(tables), L);
-  if (ps::tile_size() == 4096)
-    ps::sort_records<4096>((const uint32_t*)row_idx, (const uint4*)rec, n_views, n_rows, row_ptr, L, T, buf, rec_sorted,
-                           (hipStream_t)stream);
-  else
-    ps::sort_records<8192>((const uint32_t*)row_idx, (const uint4*)rec, n_views, n_rows, row_ptr, L, T, buf, rec_sorted,
-                           (hipStream_t)stream);
+  ps::sort_records((const uint32_t*)row_idx, (const uint4*)rec, n_views, n_rows, row_ptr, L, T, buf, rec_sorted,
+                   (hipStream_t)stream);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -733,16 +709,16 @@ int dva_plan_split_sort_records(const int32_t* row_idx, const void* rec, int64_t
 int dva_plan_split_sort_records32(const int32_t* row_idx, const void* rec, int64_t n_views, int64_t n_rows,
                                   const void* tables, int64_t tables_bytes, void* buf, void* stream) {
   if (n_views < 0 || n_rows < 0) return DVA_ERR_INVALID;
-  if (!ps::eligible(n_views, n_rows) || ps::tile_size() != 4096) return DVA_ERR_UNSUPPORTED;      // (two LDS planes of a tile)
+  if (!ps::eligible(n_views, n_rows)) return DVA_ERR_UNSUPPORTED;
   if (!row_idx || !rec || !tables || !buf || buf == rec) return DVA_ERR_INVALID;
   if (((uintptr_t)rec % 16) || ((uintptr_t)buf % 16)) return DVA_ERR_UNSUPPORTED;
   const ps::Layout L = ps::layout(n_views, n_rows);
   if ((int64_t)L.total > tables_bytes) return DVA_ERR_INVALID;
   const ps::Tables T = ps::tables_of(const_cast<void*>(tables), L);
-  constexpr int TILE = 4096, THREADS = TILE / ps::IPT;
+  constexpr int TILE = ps::PLAN_TILE, THREADS = TILE / ps::IPT;      // (two 16-byte LDS planes of a tile)
   hipLaunchKernelGGL((ps::scatter_kernel<ps::MODE_REC_A, TILE, 8>), dim3(ps::scatter_grid(L.nt)), dim3(THREADS), 0,
                      (hipStream_t)stream, (const uint32_t*)row_idx, (const uint4*)rec, buf, n_views, (int)L.nb, n_rows,
-                     L.nt, T.bstart, T.tstart, T.desc, T.offA, (const int32_t*)nullptr, (int)ps::xcd_on());
+                     L.nt, T.bstart, T.tstart, T.desc, T.offA, (const int32_t*)nullptr);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }

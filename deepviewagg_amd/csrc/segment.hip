@@ -318,7 +318,7 @@ using namespace dva;
 
 extern "C" {
 
-int dva_version(void) { return 312; }
+int dva_version(void) { return 313; }
 
 int dva_device_count(void) {
   int n = 0;

@@ -27,8 +27,6 @@ _POS = {}
 # BatchNorm_a backward inside the anchor scatter: at the level of the anchor (Gram matrix of the tap weights x the four
 # rows of Y: one random row per view) instead of row by row from the stored z_a (two)
 ANCHOR_GRAM = os.environ.get("DVA_ANCHOR_GRAM", "1") == "1"
-# the first statistics pass (taps of Y -> z_a) in anchor order (round 4): 0 = in view order over the tile table (round 3)
-ANCHOR_ORDER_STATS = os.environ.get("DVA_ANCHOR_ORDER_STATS", "1") == "1"
 
 
 def position_order(C, device):
@@ -119,8 +117,9 @@ class _EmodPool(torch.autograd.Function):
 
         # train mode: the first statistics pass walks the views in ANCHOR order (the plan the backward scatters through,
         # built here once): neighbouring lanes then read the same four rows of Y and the tap gathers become cache hits
-        # (C_out = 32: one block per view, nothing to overlap the random record reads with -- 2.4 against 1.9 ms in view order)
-        plan = ops.anchor_plan(anchors, bhw) if (training and ANCHOR_ORDER_STATS and C >= 64) else None
+        # (C_out = 32: one block per view, nothing to overlap the random record reads with -- 2.4 against 1.9 ms in view
+        # order; C_out >= 64: the view-order pass lost, 4.0 -> 3.4, 8.7 -> 4.9, 17.9 -> 10.1 ms)
+        plan = ops.anchor_plan(anchors, bhw) if (training and C >= 64) else None
 
         def stats(layer, tab_a):
             s = ops.zeros_small(2 * C, torch.float64, dev)

@@ -735,7 +735,7 @@ class SplitPlan:
         lib = _lib.load()
         V, R = self.row_idx.shape[0], self.n_rows
         if (gout.dtype != torch.float32 or C not in (32, 64) or G not in (1, 2, 4) or (C // 4) % G
-                or gout.data_ptr() % 16 or not gout.is_contiguous() or os.environ.get("DVA_PLAN_TILE", "4096") != "4096"):
+                or gout.data_ptr() % 16 or not gout.is_contiguous()):
             return None
         assert rec.shape == (V, 8) and rec.dtype == torch.float32 and rec.is_contiguous()
         brec = torch.empty_like(rec)

@@ -78,3 +78,16 @@ def test_ctypes_signatures_match_the_header_prototypes():
         got = ["ptr" if (isinstance(a, type) and issubclass(a, ctypes._Pointer)) else kind[a] for a in argtypes]
         want = [norm(t) for t in ptypes]
         assert got == want, (name, got, want)
+
+
+def test_kernel_sources_read_no_environment():
+    """include/dva.h promises "no hidden global state, re-entrant": no kernel source or header reads the process
+    environment, directly or through a helper -- every launch constant is written where it is used."""
+    import glob
+    csrc = os.path.join(ROOT, "deepviewagg_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    assert len(files) >= 20
+    files.append(os.path.join(ROOT, "include", "dva.h"))
+    hits = [(os.path.relpath(f, ROOT), word) for f in files for word in ("getenv", "environ", "tune_int")
+            if word in open(f).read()]
+    assert not hits, hits

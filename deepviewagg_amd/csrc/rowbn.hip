@@ -11,7 +11,10 @@
 //     dz_r = gout_r leaky'(z_r);  S1 = sum_r dz_r;  S2 = sum_r dz_r a_r   (a = normalised y)
 //     dy_r = gamma invstd (dz_r - w_r S1 / n - w_r a_r S2 / n);  dgamma = S2;  dbeta = S1
 // Four row-streaming passes (statistics / apply, forward and backward): lanes over channels (coalesced
-// rows), fp32 partial sums per thread, LDS per block, fp64 atomics per block.
+// rows), fp64 sums per thread (the bf16 vector statistics: fp32 over four rows, then fp64), LDS per block, fp64
+// atomics per block.
+#include <type_traits>
+
 #include "dva_common.h"
 
 namespace dva {
@@ -22,16 +25,18 @@ constexpr int RB_ROWS = 4;  // rows per block iteration (blockDim = 64 x 4)
 template <typename T, typename F>
 __device__ __forceinline__ void row_sums(int64_t R, int C, double* __restrict__ sums, double* s_red, F&& f) {
   // fp64 partial sums: the variance is E[y^2] - mean^2, and with fp32 partials the cancellation showed up as
-  // 1e-4 relative errors downstream when |mean| >> std (the passes are memory bound, fp64 adds are free)
+  // 1e-4 relative errors downstream when |mean| >> std (the passes are memory bound, fp64 adds are free).  `F` hands
+  // its terms over in fp64 for the same reason: w y^2 rounded to fp32 before the sum left 3e-5 .. 4e-4 of the variance
+  // at |mean| = 100 std, or in a channel whose few rows nearly agree (tests/test_gpu_primitives_f64.py)
   for (int i = threadIdx.y * 64 + threadIdx.x; i < 2 * C; i += 256) s_red[i] = 0.0;
   __syncthreads();
   for (int c = threadIdx.x; c < C; c += 64) {
     double a0 = 0.0, a1 = 0.0;
     for (int64_t r = (int64_t)blockIdx.x * RB_ROWS + threadIdx.y; r < R; r += (int64_t)gridDim.x * RB_ROWS) {
-      float f1, f2;
+      double f1, f2;
       f(r, c, f1, f2);
-      a0 += (double)f1;
-      a1 += (double)f2;
+      a0 += f1;
+      a1 += f2;
     }
     atomicAdd(&s_red[c], a0);
     atomicAdd(&s_red[C + c], a1);
@@ -45,8 +50,9 @@ __global__ __launch_bounds__(256) void rowbn_stats_kernel(const T* __restrict__ 
                                                            const int32_t* __restrict__ counts,
                                                            double* __restrict__ sums, int64_t R, int C) {
   extern __shared__ double s_red[];
-  row_sums<T>(R, C, sums, s_red, [&](int64_t r, int c, float& f1, float& f2) {
-    const float w = counts ? (float)counts[r] : 1.f, v = Elt<T>::ld(y, r * C + c);
+  row_sums<T>(R, C, sums, s_red, [&](int64_t r, int c, double& f1, double& f2) {
+    // fp64 products: exact while w (views per row) has no more than 5 bits, v having at most 24; one fp64 rounding beyond
+    const double w = counts ? (double)counts[r] : 1.0, v = (double)Elt<T>::ld(y, r * C + c);
     f1 = w * v;
     f2 = w * v * v;
   });
@@ -75,12 +81,12 @@ __global__ __launch_bounds__(256) void rowbn_bwd_stats_kernel(const T* __restric
                                                                double* __restrict__ sums, int64_t R,
                                                                int C, float slope) {
   extern __shared__ double s_red[];
-  row_sums<T>(R, C, sums, s_red, [&](int64_t r, int c, float& f1, float& f2) {
+  row_sums<T>(R, C, sums, s_red, [&](int64_t r, int c, double& f1, double& f2) {
     const float a = (Elt<T>::ld(y, r * C + c) - bn[c]) * bn[C + c];
     const float z = a * bn[2 * C + c] + bn[3 * C + c];
     const float dz = Elt<T>::ld(gout, r * C + c) * (z > 0.f ? 1.f : slope);
-    f1 = dz;
-    f2 = dz * a;
+    f1 = (double)dz;
+    f2 = (double)(dz * a);
   });
 }
 
@@ -163,7 +169,14 @@ __global__ __launch_bounds__(256) void rowbn_sums_vec_kernel(const T* __restrict
     be[k] = MODE == 1 ? bn[3 * C + c0 + k] : 0.f;
   }
   // four rows per thread in flight (round 5): with one 16-byte load per iteration the pass was latency-bound
-  // (134 MB in 54 us at C = 512: 2.5 TB/s); fp32 partial sums over the four rows, fp64 across iterations
+  // (134 MB in 54 us at C = 512: 2.5 TB/s); fp32 partial sums over the four rows, fp64 across iterations.
+  // EXACT: the forward statistics of fp32 / fp16 rows take w y and w y^2 as fp64 products instead (row_sums has the
+  // figures).  bf16 rows keep the fp32 partials, the kernel of the headline workload as it was: an 8-bit significand
+  // squares into 16 bits, so the terms are exact and only the four-row fp32 sum rounds; measured, not proven: variance
+  // error 3e-12 at |mean| = 100 std and at most 3.1e-7 over the widths and row counts of test_gpu_primitives_f64.py
+  // Cost of the fp64 products, 134 MB of rows, median of 30 launches: fp32 C = 64 48.9 -> 51.3 us, C = 256 48.5 -> 50.3 us,
+  // fp16 C = 512 54.7 -> 55.8 us (fastest launch 40 .. 45 us either way); scalar kernel, fp32 C = 12: 229.9 -> 231.1 us
+  constexpr bool EXACT = MODE == 0 && !std::is_same<T, bf16_t>::value;
   constexpr int U = 4;
   const int64_t stride = (int64_t)gridDim.x * rpb;
   for (int64_t r0 = (int64_t)blockIdx.x * rpb + slot; r0 < R; r0 += stride * U) {
@@ -184,7 +197,14 @@ __global__ __launch_bounds__(256) void rowbn_sums_vec_kernel(const T* __restrict
     for (int u = 0; u < U; ++u) {
       float v[VEC];
       RVec<T>::unpack(yr[u], v);
-      if (MODE == 0) {
+      if (EXACT) {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+          const double wv = (double)w[u] * (double)v[k];
+          a0[k] += wv;
+          a1[k] += wv * (double)v[k];
+        }
+      } else if (MODE == 0) {
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
           const float wv = w[u] * v[k];
@@ -204,10 +224,12 @@ __global__ __launch_bounds__(256) void rowbn_sums_vec_kernel(const T* __restrict
         }
       }
     }
+    if (!EXACT) {
 #pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-      a0[k] += (double)p0[k];
-      a1[k] += (double)p1[k];
+      for (int k = 0; k < VEC; ++k) {
+        a0[k] += (double)p0[k];
+        a1[k] += (double)p1[k];
+      }
     }
   }
   // the threads of a wavefront that own the same channels (lanes ci, ci + cpr, ...) reduce with shuffles first:

@@ -122,10 +122,27 @@ __global__ __launch_bounds__(256) void segment_softmax_bwd_kernel(const float* _
     const int g = (int)(t - p * G);
     const int64_t beg = ptr[p], end = ptr[p + 1];
     if (end <= beg) continue;
-    float dot = 0.f;
-    for (int64_t r = beg; r < end; ++r) dot += out[r * G + g] * gout[r * G + g];
+    // The reference differentiates through the group max as well (pooling.py:787): with eps the outputs of a group
+    // sum to 1 - eps / (S + eps), so shifting the max moves every output, and that term, -dot (1 - sum out) / d, goes
+    // to the arg row of the max.  The largest output marks it (first row on ties, as segment_csr's max): exp is
+    // monotone.  At the default eps = 1e-12 the term is below fp32 resolution; at eps = 1e-2 it is 5 % of the gradient.
+    float dot = 0.f, so = 0.f, best = out[beg * G + g];
+    int64_t a = beg;
+    for (int64_t r = beg; r < end; ++r) {
+      const float o = out[r * G + g];
+      dot += o * gout[r * G + g];
+      so += o;
+      if (o > best) {
+        best = o;
+        a = r;
+      }
+    }
     const float d = scaling ? sqrtf((float)(end - beg)) : 1.f;
-    for (int64_t r = beg; r < end; ++r) gsrc[r * G + g] = out[r * G + g] * (gout[r * G + g] - dot) / d;
+    for (int64_t r = beg; r < end; ++r) {
+      float gr = out[r * G + g] * (gout[r * G + g] - dot) / d;
+      if (r == a) gr -= dot * (1.f - so) / d;
+      gsrc[r * G + g] = gr;
+    }
   }
 }
 

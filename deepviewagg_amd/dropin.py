@@ -10,7 +10,9 @@ cylinder samplers (SphereSampling, CylinderSampling, GridSphereSampling, GridCyl
 ``torch_points3d.core.data_transform.transforms``, and both groups on the package
 ``torch_points3d.core.data_transform`` itself (``instantiate_transform`` and ``cT.GridSampling3D`` look them up there),
 and imports the data classes from
-``torch_points3d.core.multimodal.{csr,image}``.  ``install()`` either patches an importable
+``torch_points3d.core.multimodal.{csr,image}``, and takes ``lovasz_softmax`` and ``ConfusionMatrix`` from
+``torch_points3d.metrics.{lovasz_loss,confusion_matrix}``; where the reference's ``SegmentationTracker`` can be imported,
+its ``_compute_metrics`` becomes ``deepviewagg_amd.metrics.segmentation_tracker.compute_metrics``.  ``install()`` either patches an importable
 ``torch_points3d`` in place (attribute by attribute) or, when the package is absent, registers alias
 modules under those dotted names in ``sys.modules``.
 """
@@ -33,6 +35,8 @@ _ALIASES = {
     "torch_points3d.utils.multimodal": "deepviewagg_amd.utils.multimodal",
     "torch_points3d.modules.SparseConv3d.modules": "deepviewagg_amd.modules.SparseConv3d.modules",
     "torch_points3d.modules.SparseConv3d.nn": "deepviewagg_amd.modules.SparseConv3d.nn",
+    "torch_points3d.metrics.lovasz_loss": "deepviewagg_amd.metrics.lovasz_loss",
+    "torch_points3d.metrics.confusion_matrix": "deepviewagg_amd.metrics.confusion_matrix",
 }
 
 # (package, our module, names): set on the package after the aliases above
@@ -83,4 +87,23 @@ def install(patch_existing=True):
             continue
         for k in names:
             setattr(pkg, k, getattr(ours, k))
+    _bind_tracker(patch_existing)
     return done
+
+
+def _bind_tracker(patch_existing):
+    """The reference's SegmentationTracker, when it can be imported, counts on the device from now on."""
+    name = "torch_points3d.metrics.segmentation_tracker"
+    tracker = sys.modules.get(name)
+    if tracker is None and patch_existing:
+        try:
+            tracker = importlib.import_module(name)
+        except Exception:
+            tracker = None
+    cls = getattr(tracker, "SegmentationTracker", None)
+    if cls is None:
+        return
+    from .metrics.confusion_matrix import ConfusionMatrix
+    from .metrics.segmentation_tracker import compute_metrics
+    cls._compute_metrics = compute_metrics
+    tracker.ConfusionMatrix = ConfusionMatrix

@@ -18,6 +18,9 @@ ops; names and argument meaning follow the reference call site
 ``elastic_smooth``         grid_transform.py:231-234 (six ``scipy.ndimage.convolve`` calls)
 ``elastic_displace``       grid_transform.py:241-242 (``RegularGridInterpolator``)
 ``elastic_distortion``     grid_transform.py:218-243 (one level of ElasticDistortion)
+``log_softmax_nll``        models/segmentation/sparseconv3d.py:45-51 (``F.log_softmax`` + ``F.nll_loss``)
+``lovasz_softmax_flat``    metrics/lovasz_loss.py:174-215 (``flatten_probas`` + ``lovasz_softmax_flat``)
+``confusion_counts``       metrics/segmentation_tracker.py:72-83 (mask + ``np.argmax`` + ``np.bincount``)
 =========================  ==========================================================
 
 All ops require tensors on a HIP device and raise otherwise (no CPU fallback).
@@ -2156,3 +2159,173 @@ def elastic_distortion(pos, granularity, magnitude, noise=None):
         for d_min, d_max, d in zip(coords_min - granularity, coords_min + granularity * (noise_dim - 2), noise_dim)
     ]
     return elastic_displace(p, elastic_smooth(noise), ax, magnitude)
+
+
+# ---------------------------------------------------------------------------------------------
+# the tail of the segmentation step (csrc/segloss.hip): log-softmax + weighted NLL, Lovasz-softmax, confusion counts
+# ---------------------------------------------------------------------------------------------
+
+SEG_MAX_CLASSES = 64
+LOVASZ_TILE = 1024      # sorted elements per block of the segmented Lovasz pass (DVA_LOVASZ_TILE; tests size their cases by it)
+
+
+def _seg_inputs(what, scores, labels, dtypes):
+    """``scores`` [P, C] and ``labels`` [P] on one HIP device, within the kernels' limits; labels as contiguous int64."""
+    if not torch.is_tensor(scores) or not torch.is_tensor(labels):
+        raise TypeError(f"ops.{what} takes tensors")
+    require_device(scores, labels)
+    if scores.dtype not in dtypes:
+        raise TypeError(f"ops.{what}: [P, C] input of dtype {scores.dtype}; supported: {', '.join(str(d) for d in dtypes)}")
+    if scores.dim() != 2:
+        raise ValueError(f"ops.{what}: the scores must be [P, C], got {tuple(scores.shape)}")
+    P, C = int(scores.shape[0]), int(scores.shape[1])
+    if labels.dim() != 1 or labels.shape[0] != P:
+        raise ValueError(f"ops.{what}: labels must be [P] = [{P}], got {tuple(labels.shape)}")
+    if labels.dtype.is_floating_point or labels.dtype == torch.bool:
+        raise TypeError(f"ops.{what}: labels must be integers, got {labels.dtype}")
+    if not 1 <= C <= SEG_MAX_CLASSES:
+        raise ValueError(f"ops.{what}: C = {C} classes; the kernels take 1 <= C <= {SEG_MAX_CLASSES}")
+    if P * C >= 1 << 31:
+        raise ValueError(f"ops.{what}: P * C = {P} * {C} elements; the kernels take fewer than 2^31")
+    return P, C, labels.detach().to(torch.int64).contiguous()
+
+
+_SEG_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+
+
+class _LogSoftmaxNLL(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, weight, ignore_index):
+        lib = _lib.load()
+        x = logits.detach().contiguous()
+        P, C = x.shape
+        dev = x.device
+        logp = torch.empty((P, C), dtype=torch.float32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        numden = torch.empty(2, dtype=torch.float64, device=dev)
+        nbytes = int(lib.dva_seg_nll_workspace_bytes())
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        with _timed("seg_logsoftmax_nll_fwd", x.numel() * (x.element_size() + 4)):
+            check(lib.dva_seg_logsoftmax_nll_fwd(ptr(x), dtype_code(x), ptr(labels), ptr(weight), int(ignore_index), P, C,
+                                                 ptr(logp), ptr(loss), ptr(numden), ptr(ws), nbytes, stream_of(x)),
+                  "dva_seg_logsoftmax_nll_fwd")
+        ctx.save_for_backward(logp, labels, weight, numden)
+        ctx.ignore_index = int(ignore_index)
+        ctx.dtype = x.dtype
+        ctx.set_materialize_grads(False)
+        return logp, loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g_logp, g_loss):
+        logp, labels, weight, numden = ctx.saved_tensors
+        if g_logp is None and g_loss is None:
+            return None, None, None, None
+        lib = _lib.load()
+        P, C = logp.shape
+        if g_logp is not None:
+            g_logp = g_logp.to(torch.float32).contiguous()
+        if g_loss is not None:
+            g_loss = g_loss.to(torch.float32).reshape(1).contiguous()
+        out = torch.empty((P, C), dtype=ctx.dtype, device=logp.device)
+        with _timed("seg_logsoftmax_nll_bwd", logp.numel() * (8 + out.element_size())):
+            check(lib.dva_seg_logsoftmax_nll_bwd(ptr(logp), ptr(labels), ptr(weight), ptr(numden), ptr(g_loss), ptr(g_logp),
+                                                 ctx.ignore_index, P, C, ptr(out), dtype_code(out), stream_of(logp)),
+                  "dva_seg_logsoftmax_nll_bwd")
+        return out, None, None, None
+
+
+def log_softmax_nll(logits, labels, weight=None, ignore_index=-1):
+    """``F.log_softmax(logits, -1)`` and ``F.nll_loss(., labels, weight=weight, ignore_index=ignore_index)`` in one pass
+    over ``logits`` [P, C] (float32, bfloat16 or float16; upcast exactly): returns ``(log_probs, loss)``, float32
+    [P, C] and a float32 scalar, both differentiable (one backward kernel takes both upstream gradients and writes
+    the logits gradient in the logits' dtype).  The loss is ``sum w[y] (-logp[y]) / sum w[y]`` over the rows whose
+    label is not ``ignore_index``, reduced in float64 in a fixed order (bitwise reproducible); NaN when every label is
+    ignored, as torch.  A label outside [0, C) that is not ``ignore_index`` takes no part (torch asserts on it).
+    1 <= C <= 64 and P C < 2^31.  No host synchronisation."""
+    P, C, lab = _seg_inputs("log_softmax_nll", logits, labels, _SEG_DTYPES)
+    if weight is not None:
+        require_device(logits, weight)
+        if weight.dim() != 1 or weight.shape[0] != C:
+            raise ValueError(f"ops.log_softmax_nll: weight must be [C] = [{C}], got {tuple(weight.shape)}")
+        weight = weight.detach().to(torch.float32).contiguous()
+    return _LogSoftmaxNLL.apply(logits, lab, weight, int(ignore_index))
+
+
+class _LovaszSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, probas, labels, class_mask, present_only, ignore):
+        lib = _lib.load()
+        p = probas.detach().contiguous()
+        P, C = p.shape
+        dev = p.device
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        grad = torch.empty((P, C), dtype=torch.float32, device=dev)
+        nbytes = lib.dva_lovasz_workspace_bytes(P, C)
+        if nbytes < 0:
+            raise _lib.DvaError(f"dva_lovasz_workspace_bytes({P}, {C})", int(nbytes))
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+        with _timed("lovasz_softmax", p.numel() * 32):
+            check(lib.dva_lovasz_softmax(ptr(p), ptr(labels), P, C, 0 if ignore is None else int(ignore),
+                                         0 if ignore is None else 1, ptr(class_mask), int(bool(present_only)), ptr(loss),
+                                         ptr(grad), ptr(ws), int(nbytes), stream_of(p)), "dva_lovasz_softmax")
+        ctx.save_for_backward(grad)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        grad, = ctx.saved_tensors
+        return grad * g, None, None, None, None      # the Jaccard increments are the gradient: backward is a scale
+
+
+def lovasz_softmax_flat(probas, labels, classes="present", ignore=None):
+    """The reference's ``lovasz_softmax_flat(*flatten_probas(probas, labels, ignore), classes=classes)`` for ``probas``
+    float32 [P, C] (any values) and ``labels`` [P]: a float32 scalar with a gradient to ``probas``.
+
+    ``classes``: ``'present'`` (classes some non-ignored point carries), ``'all'``, or a list of class numbers.  Per class
+    the errors ``|fg - p_c|`` (float32, as the reference forms them) are sorted descending -- ties in ascending point
+    order, where torch's sort leaves them unspecified -- and the Jaccard values come from integer counts in float64, so
+    the gradient keeps its precision at any P (the reference differences two float32 values close to 1).  The loss is
+    the mean over the classes taking part; 0, with a zero gradient, when there is none (every point ignored, an empty
+    list): the shape quirks of the reference for that case live in ``deepviewagg_amd.metrics.lovasz_loss``.  All sizes
+    are static: ignored points are sorted into a sentinel segment, nothing is read back.  1 <= C <= 64, P C < 2^31."""
+    P, C, lab = _seg_inputs("lovasz_softmax_flat", probas, labels, (torch.float32,))
+    mask = None
+    if isinstance(classes, str):
+        if classes not in ("present", "all"):
+            raise ValueError(f"ops.lovasz_softmax_flat: classes must be 'present', 'all' or a list, got {classes!r}")
+    else:
+        wanted = sorted({int(c) for c in classes})
+        if any(c < 0 or c >= C for c in wanted):
+            raise IndexError(f"ops.lovasz_softmax_flat: classes {wanted} for C = {C}")
+        mask = torch.zeros(C, dtype=torch.uint8, device=probas.device)
+        for c in wanted:                                     # fills, no host-to-device copy (which would synchronise)
+            mask[c:c + 1].fill_(1)
+    if P == 0:
+        return probas.sum() * 0.
+    return _LovaszSoftmax.apply(probas, lab, mask, classes == "present" if isinstance(classes, str) else False, ignore)
+
+
+def confusion_counts(outputs, labels, num_classes, ignore_index=-1, out=None):
+    """Adds the confusion counts of ``outputs`` [P, C] (float32, bfloat16 or float16 scores of any kind) against
+    ``labels`` [P] into ``out`` int64 [C, C] (row = label, column = ``argmax`` as numpy's: first maximum, a NaN is the
+    maximum); a new zero matrix when ``out`` is None.  Rows whose label is ``ignore_index`` are skipped; rows with
+    another label outside [0, C) are counted in ``n_bad`` instead.  Returns ``(counts, n_bad)``, int64 [C, C] and int64
+    [1], both on the device; no host synchronisation.  Replaces the full device-to-host copy of the outputs in
+    ``SegmentationTracker._compute_metrics``."""
+    P, C, lab = _seg_inputs("confusion_counts", outputs, labels, _SEG_DTYPES)
+    if int(num_classes) != C:
+        raise ValueError(f"ops.confusion_counts: outputs have {C} columns for num_classes = {num_classes}")
+    dev = outputs.device
+    if out is None:
+        out = torch.zeros((C, C), dtype=torch.int64, device=dev)
+    else:
+        require_device(outputs, out)
+        if out.dtype != torch.int64 or tuple(out.shape) != (C, C) or not out.is_contiguous():
+            raise ValueError(f"ops.confusion_counts: out must be a contiguous int64 [{C}, {C}] tensor")
+    n_bad = torch.zeros(1, dtype=torch.int64, device=dev)
+    x = outputs.detach().contiguous()
+    lib = _lib.load()
+    with _timed("confusion_counts", x.numel() * x.element_size()):
+        check(lib.dva_confusion_counts(ptr(x), dtype_code(x), ptr(lab), int(ignore_index), P, C, ptr(out), ptr(n_bad),
+                                       stream_of(x)), "dva_confusion_counts")
+    return out, n_bad

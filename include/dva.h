@@ -984,6 +984,58 @@ int dva_elastic_displace(const float* pos, int64_t n, const float* field, const 
                          int64_t dz, double magnitude, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------ *
+ * The tail of the segmentation step (segloss.hip).  Replaces F.log_softmax + F.nll_loss and lovasz_softmax of
+ * models/segmentation/sparseconv3d.py:42-55 (metrics/lovasz_loss.py:155-202) and the argmax + bincount of
+ * SegmentationTracker._compute_metrics (metrics/segmentation_tracker.py:71-91).
+ * Limits of every entry: 1 <= C <= 64 (C < 1: DVA_ERR_INVALID, C > 64: DVA_ERR_UNSUPPORTED) and P C < 2^31
+ * (DVA_ERR_UNSUPPORTED beyond).  Argument errors are returned before any HIP call.  No float atomics: two runs
+ * give the same bits.  labels int64 [P]; a label equal to ignore_index takes no part.
+ *
+ *   dva_seg_logsoftmax_nll_fwd  logits [P, C] of dtype DVA_F32 / DVA_BF16 / DVA_F16, upcast exactly; log_probs fp32
+ *                               [P, C] = (x - max) - log(sum exp(x - max)) in fp32.  num = sum w[y] (-logp[y]) and
+ *                               den = sum w[y] over the rows whose label is in [0, C) (weight fp32 [C] nullable = all
+ *                               ones; another label outside [0, C) takes no part either), reduced in fp64 from
+ *                               per-block partials in a fixed order; numden fp64 [2] = {num, den}, loss fp32 [1] =
+ *                               num / den (NaN when no row is counted, as torch).  Workspace:
+ *                               dva_seg_nll_workspace_bytes().
+ *   dva_seg_logsoftmax_nll_bwd  grad_logits [P, C] of dtype `dtype`, one pass: with g = grad_log_probs (fp32 [P, C],
+ *                               nullable = 0) + [j == y] (-w[y] / den) grad_loss[0] (device fp32, nullable = 0):
+ *                               grad_logits = g - exp(log_probs) sum_j g.
+ *   dva_confusion_counts        counts int64 [C, C] += 1 at [label, argmax(outputs row)]; argmax as numpy's: the first
+ *                               maximum, a NaN is the maximum and the first NaN wins.  Rows whose label is neither
+ *                               ignore_index nor in [0, C) add 1 to n_bad int64 [1] instead.  Per-block LDS histogram,
+ *                               integer atomics.
+ *   dva_lovasz_softmax          lovasz_softmax_flat of probas fp32 [P, C] (any values) over the points whose label is
+ *                               not ignore_index (use_ignore = 0: over all points).  Class c takes part when
+ *                               class_mask[c] != 0 (uint8 [C], nullable = all) and, with present_only, when some valid
+ *                               point carries label c.  Per class: err = |fg - p_c| in fp32, sorted descending, ties
+ *                               in ascending point order (stable); with n_k foreground points among the first k and G
+ *                               in all, J_k = 1 - (G - n_k) / (G + k - n_k) from the integer counts in fp64, J_0 = 0,
+ *                               grad_k = J_k - J_{k-1}, loss_c = sum err_k grad_k in fp64.  loss fp32 [1] = the mean
+ *                               over the n_used classes taking part (0 when there is none); grad fp32 [P, C] =
+ *                               dloss / dprobas = sign(p - fg) grad_k / n_used rounded once, 0 where p == fg, for
+ *                               ignored points and for classes that take no part.  Nothing is read back to the host.
+ *                               Workspace: dva_lovasz_workspace_bytes(P, C) (24 bytes per element of probas + the
+ *                               sort's own).  The segmented pass works in tiles of DVA_LOVASZ_TILE sorted elements
+ *                               (dva_lovasz_tile()); the carry across tiles is one exclusive prefix per class, linear in P. */
+#define DVA_LOVASZ_TILE 1024
+int dva_lovasz_tile(void);
+int64_t dva_seg_nll_workspace_bytes(void);
+int dva_seg_logsoftmax_nll_fwd(const void* logits, int32_t dtype, const int64_t* labels, const float* weight,
+                               int64_t ignore_index, int64_t P, int32_t C, float* log_probs, float* loss,
+                               double* numden, void* workspace, int64_t workspace_bytes, void* stream);
+int dva_seg_logsoftmax_nll_bwd(const float* log_probs, const int64_t* labels, const float* weight,
+                               const double* numden, const float* grad_loss, const float* grad_log_probs,
+                               int64_t ignore_index, int64_t P, int32_t C, void* grad_logits, int32_t dtype,
+                               void* stream);
+int dva_confusion_counts(const void* outputs, int32_t dtype, const int64_t* labels, int64_t ignore_index, int64_t P,
+                         int32_t C, int64_t* counts, int64_t* n_bad, void* stream);
+int64_t dva_lovasz_workspace_bytes(int64_t P, int32_t C);
+int dva_lovasz_softmax(const float* probas, const int64_t* labels, int64_t P, int32_t C, int64_t ignore_index,
+                       int32_t use_ignore, const uint8_t* class_mask, int32_t present_only, float* loss, float* grad,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------ *
  * Lexicographic integer keys.  Replace utils/multimodal.py:36-94 (lexargsort / lexargunique on a
  * composite int64 key, :97-179 CompositeTensor, :253-323 lex ops).
  * ------------------------------------------------------------------------------------------ */

@@ -223,6 +223,10 @@ SIGNATURES = {
     "dva_confusion_counts": (ctypes.c_int, [_vp, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
     "dva_lovasz_workspace_bytes": (ctypes.c_int64, [_i64, _i32]),
     "dva_lovasz_softmax": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "dva_vote_workspace_bytes": (ctypes.c_int64, [_i64]),
+    "dva_vote_add": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp]),
+    "dva_knn_interpolate": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
+                                           _vp]),
     "dva_lex_workspace_bytes": (ctypes.c_int64, [_i64]),
     "dva_argsort_i64": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "dva_argunique_i64": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp]),

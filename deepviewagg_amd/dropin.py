@@ -11,7 +11,8 @@ cylinder samplers (SphereSampling, CylinderSampling, GridSphereSampling, GridCyl
 ``torch_points3d.core.data_transform`` itself (``instantiate_transform`` and ``cT.GridSampling3D`` look them up there),
 and imports the data classes from
 ``torch_points3d.core.multimodal.{csr,image}``, and takes ``lovasz_softmax`` and ``ConfusionMatrix`` from
-``torch_points3d.metrics.{lovasz_loss,confusion_matrix}``; where the reference's ``SegmentationTracker`` can be imported,
+``torch_points3d.metrics.{lovasz_loss,confusion_matrix}`` and ``SegmentationVoter`` from
+``torch_points3d.metrics.segmentation_helpers``; where the reference's ``SegmentationTracker`` can be imported,
 its ``_compute_metrics`` becomes ``deepviewagg_amd.metrics.segmentation_tracker.compute_metrics``.  ``install()`` either patches an importable
 ``torch_points3d`` in place (attribute by attribute) or, when the package is absent, registers alias
 modules under those dotted names in ``sys.modules``.
@@ -37,6 +38,7 @@ _ALIASES = {
     "torch_points3d.modules.SparseConv3d.nn": "deepviewagg_amd.modules.SparseConv3d.nn",
     "torch_points3d.metrics.lovasz_loss": "deepviewagg_amd.metrics.lovasz_loss",
     "torch_points3d.metrics.confusion_matrix": "deepviewagg_amd.metrics.confusion_matrix",
+    "torch_points3d.metrics.segmentation_helpers": "deepviewagg_amd.metrics.segmentation_helpers",
 }
 
 # (package, our module, names): set on the package after the aliases above

@@ -2329,3 +2329,155 @@ def confusion_counts(outputs, labels, num_classes, ignore_index=-1, out=None):
         check(lib.dva_confusion_counts(ptr(x), dtype_code(x), ptr(lab), int(ignore_index), P, C, ptr(out), ptr(n_bad),
                                        stream_of(x)), "dva_confusion_counts")
     return out, n_bad
+
+
+# ---------------------------------------------------------------------------------------------
+# voting on the raw cloud and K-NN interpolation of the votes (csrc/vote.hip)
+# ---------------------------------------------------------------------------------------------
+
+KNN_INTERPOLATE_CHUNK = 1 << 22     # queries per K-NN call: bounds the K-NN workspace and the [chunk, k] tables
+
+
+def vote_slots(num_points, device):
+    """The int32 slot array ``vote_add`` works in (one slot per raw point, all -1): created once per accumulator."""
+    nbytes = _lib.load().dva_vote_workspace_bytes(int(num_points))
+    if nbytes < 0:
+        raise _lib.DvaError(f"dva_vote_workspace_bytes({num_points})", int(nbytes))
+    return torch.full((int(nbytes) // 4,), -1, dtype=torch.int32, device=device)
+
+
+def vote_add(votes, counts, ids, outputs, slots):
+    """``votes[ids] += outputs; counts[ids] += 1`` in place on the device, for ``votes`` float32 [N, C], ``counts`` int32
+    [N], ``ids`` [P] (integers) and ``outputs`` [P, C] (float32, bfloat16 or float16; widened exactly).  An id that
+    occurs several times in ``ids`` is counted once, as in the reference, and it is always the LAST occurrence (torch
+    leaves open which one).  ``slots`` comes from ``vote_slots(N, device)`` and reads all -1 before and after the call.
+    An id outside [0, N) writes nothing and is counted in the returned ``n_bad`` (int64 [1], on the device).  No float
+    atomics, so two runs give the same bits; no host synchronisation.  1 <= C <= 64."""
+    for t in (votes, counts, ids, outputs, slots):
+        if not torch.is_tensor(t):
+            raise TypeError("ops.vote_add takes tensors")
+    dev = require_device(votes, counts, ids, outputs, slots)
+    if votes.dim() != 2 or votes.dtype != torch.float32 or not votes.is_contiguous():
+        raise ValueError("ops.vote_add: votes must be a contiguous float32 [N, C] tensor")
+    N, C = int(votes.shape[0]), int(votes.shape[1])
+    if counts.dtype != torch.int32 or tuple(counts.shape) != (N,) or not counts.is_contiguous():
+        raise ValueError(f"ops.vote_add: counts must be a contiguous int32 [{N}] tensor")
+    if slots.dtype != torch.int32 or slots.dim() != 1 or not slots.is_contiguous():
+        raise ValueError("ops.vote_add: slots must come from ops.vote_slots")
+    if not 1 <= C <= SEG_MAX_CLASSES:
+        raise ValueError(f"ops.vote_add: C = {C} classes; the kernels take 1 <= C <= {SEG_MAX_CLASSES}")
+    if ids.dtype.is_floating_point or ids.dtype == torch.bool:
+        raise TypeError(f"ops.vote_add: ids must be integers, got {ids.dtype}")
+    if outputs.dtype not in _SEG_DTYPES:
+        raise TypeError(f"ops.vote_add: outputs of dtype {outputs.dtype}; supported: float32, bfloat16, float16")
+    ids = ids.detach().reshape(-1).to(torch.int64).contiguous()
+    P = int(ids.shape[0])
+    if tuple(outputs.shape) != (P, C):
+        raise ValueError(f"ops.vote_add: outputs must be [P, C] = [{P}, {C}], got {tuple(outputs.shape)}")
+    out = outputs.detach().contiguous()
+    n_bad = torch.zeros(1, dtype=torch.int64, device=dev)
+    lib = _lib.load()
+    with _timed("vote_add", P * (16 + C * (out.element_size() + 8))):
+        check(lib.dva_vote_add(ptr(votes), ptr(counts), N, C, ptr(ids), ptr(out), dtype_code(out), P, ptr(slots),
+                               int(slots.numel()) * 4, ptr(n_bad), stream_of(votes)), "dva_vote_add")
+    return n_bad
+
+
+def _interpolate_inputs(what, x, pos_x, pos_y, k):
+    for t in (x, pos_x, pos_y):
+        if not torch.is_tensor(t):
+            raise TypeError(f"ops.{what} takes tensors")
+    require_device(x, pos_x, pos_y)
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError(f"ops.{what}: x must be float32 [M, C], got {x.dtype} {tuple(x.shape)}")
+    M, C = int(x.shape[0]), int(x.shape[1])
+    if pos_x.dim() != 2 or tuple(pos_x.shape) != (M, 3) or pos_y.dim() != 2 or pos_y.shape[1] != 3:
+        raise ValueError(f"ops.{what}: pos_x must be [M, 3] = [{M}, 3] and pos_y [n, 3], got {tuple(pos_x.shape)} and "
+                         f"{tuple(pos_y.shape)}")
+    if not 1 <= C <= SEG_MAX_CLASSES:
+        raise ValueError(f"ops.{what}: C = {C} columns; the kernel takes 1 <= C <= {SEG_MAX_CLASSES}")
+    if not isinstance(k, int) or isinstance(k, bool) or not 0 < k <= 128:
+        raise ValueError(f"ops.{what}: k = {k!r}; the K-NN keeps 1 <= k <= 128 neighbours")
+    if k > M:
+        raise ValueError(f"ops.{what}: k = {k} neighbours requested from {M} points")
+    return (x.detach().contiguous(), pos_x.detach().float().contiguous(), pos_y.detach().float().contiguous(), M, C,
+            int(pos_y.shape[0]))
+
+
+def _interpolate_chunks(x, pos_x, pos_y, k, chunk, own, y, pred, labels, ignore_index, counts, n_bad):
+    """One K-NN and one interpolation launch per chunk of queries; every output is written in place."""
+    lib = _lib.load()
+    M, C = x.shape
+    n = int(pos_y.shape[0])
+    chunk = KNN_INTERPOLATE_CHUNK if chunk is None else int(chunk)
+    if chunk < 1:
+        raise ValueError(f"ops.knn_interpolate: chunk = {chunk}")
+    for a in range(0, n, chunk):
+        b = min(a + chunk, n)
+        nbr, d2 = knn_query(pos_y[a:b], pos_x, k)
+        with _timed("knn_interpolate", (b - a) * (k * (8 + 4 * C) + 8)):
+            check(lib.dva_knn_interpolate(ptr(x), M, C, ptr(nbr), ptr(d2), b - a, k,
+                                          None if own is None else ptr(own[a:b]), None if y is None else ptr(y[a:b]),
+                                          None if pred is None else ptr(pred[a:b]),
+                                          None if labels is None else ptr(labels[a:b]), int(ignore_index), ptr(counts),
+                                          ptr(n_bad), stream_of(x)), "dva_knn_interpolate")
+
+
+def knn_interpolate(x, pos_x, pos_y, batch_x=None, batch_y=None, k=3, chunk=None):
+    """``torch_geometric.nn.unpool.knn_interpolate(x, pos_x, pos_y, k=k)``: ``y`` float32 [n, C], per query the mean of
+    the rows of ``x`` float32 [M, C] at its k nearest points of ``pos_x`` [M, 3], weighted by ``1 / max(d2, 1e-16)``.
+    All in float32, every operation rounded on its own, summed in neighbour rank order (``ops.knn_query``: ascending by
+    (float32 squared distance, index); torch_cluster's tie order is not defined).  The queries are processed in
+    chunks of ``chunk`` (default 2^22) so that the K-NN's tables stay bounded; the result does not depend on it.
+    ``batch_x`` / ``batch_y`` are not supported.  The K-NN reads one scalar back per chunk."""
+    if batch_x is not None or batch_y is not None:
+        raise NotImplementedError("ops.knn_interpolate: batch_x / batch_y are not supported (one cloud per call)")
+    x, pos_x, pos_y, M, C, n = _interpolate_inputs("knn_interpolate", x, pos_x, pos_y, k)
+    y = torch.empty((n, C), dtype=torch.float32, device=x.device)
+    _interpolate_chunks(x, pos_x, pos_y, k, chunk, None, y, None, None, 0, None, None)
+    return y
+
+
+def knn_interpolate_labels(x, pos_x, pos_y, k=1, labels=None, num_classes=None, ignore_index=-1, out=None,
+                           keep_counts=None, chunk=None):
+    """``knn_interpolate(x, pos_x, pos_y, k=k).argmax(1)`` without the [n, C] tensor: returns ``(pred, counts, n_bad)``.
+
+    ``pred`` int64 [n] is the first maximum of the interpolated row (a NaN is the maximum, as ``ops.confusion_counts``).
+    With ``labels`` [n], the pairs ``(labels[i], pred[i])`` whose label is not ``ignore_index`` are added to ``counts``
+    int64 [C, C] (``out``, or a new zero matrix) and a label outside [0, C) is counted in ``n_bad`` int64 [1] instead;
+    without ``labels`` both are None.  ``keep_counts`` [n] (integers) serves KITTI-360's fill: the queries with a
+    positive entry are, in their order, the M points ``x`` and ``pos_x`` were taken from (``x = votes[keep_counts > 0]``),
+    and each of them keeps the ``argmax`` of its own row; only the others are interpolated.  Everything stays on the
+    device; the K-NN reads one scalar back per chunk of ``chunk`` queries (default 2^22)."""
+    x, pos_x, pos_y, M, C, n = _interpolate_inputs("knn_interpolate_labels", x, pos_x, pos_y, k)
+    dev = x.device
+    if num_classes is not None and int(num_classes) != C:
+        raise ValueError(f"ops.knn_interpolate_labels: x has {C} columns for num_classes = {num_classes}")
+    counts = n_bad = lab = None
+    if labels is not None:
+        require_device(x, labels)
+        if labels.dim() != 1 or labels.shape[0] != n:
+            raise ValueError(f"ops.knn_interpolate_labels: labels must be [n] = [{n}], got {tuple(labels.shape)}")
+        if labels.dtype.is_floating_point or labels.dtype == torch.bool:
+            raise TypeError(f"ops.knn_interpolate_labels: labels must be integers, got {labels.dtype}")
+        lab = labels.detach().to(torch.int64).contiguous()
+        if out is None:
+            out = torch.zeros((C, C), dtype=torch.int64, device=dev)
+        else:
+            require_device(x, out)
+            if out.dtype != torch.int64 or tuple(out.shape) != (C, C) or not out.is_contiguous():
+                raise ValueError(f"ops.knn_interpolate_labels: out must be a contiguous int64 [{C}, {C}] tensor")
+        counts = out
+        n_bad = torch.zeros(1, dtype=torch.int64, device=dev)
+    elif out is not None:
+        raise ValueError("ops.knn_interpolate_labels: out without labels")
+    own = None
+    if keep_counts is not None:
+        require_device(x, keep_counts)
+        if keep_counts.dim() != 1 or keep_counts.shape[0] != n:
+            raise ValueError(f"ops.knn_interpolate_labels: keep_counts must be [n] = [{n}]")
+        kept = keep_counts > 0
+        own = torch.where(kept, torch.cumsum(kept, 0, dtype=torch.int32) - 1, -1).to(torch.int32).contiguous()
+    pred = torch.empty(n, dtype=torch.int64, device=dev)
+    _interpolate_chunks(x, pos_x, pos_y, k, chunk, own, None, pred, lab, ignore_index, counts, n_bad)
+    return pred, counts, n_bad

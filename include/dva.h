@@ -1036,7 +1036,42 @@ int dva_lovasz_softmax(const float* probas, const int64_t* labels, int64_t P, in
                        void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------ *
- * Lexicographic integer keys.  Replace utils/multimodal.py:36-94 (lexargsort / lexargunique on a
+ * Voting on the raw cloud and K-NN interpolation of the votes (vote.hip).  Replaces the host accumulation
+ * `votes[ids] += outputs; counts[ids] += 1` of metrics/s3dis_tracker.py:56-61, metrics/segmentation_helpers.py
+ * (SegmentationVoter.add_vote) and metrics/kitti360_tracker.py:144-152, and torch_geometric's knn_interpolate + argmax +
+ * ConfusionMatrix of s3dis_tracker.py:94-118, segmentation_helpers.py:76-83 and kitti360_tracker.py:188-222.
+ * Limits: 1 <= C <= 64 (C < 1: DVA_ERR_INVALID, C > 64: DVA_ERR_UNSUPPORTED), N, P, M < 2^31, n k < 2^31, k <= 128
+ * (DVA_ERR_UNSUPPORTED beyond).  Argument errors are returned before any HIP call; zero rows is a no-op.  No float
+ * atomics: two runs give the same bits.  Nothing synchronises.
+ *
+ *   dva_vote_add          votes fp32 [N, C] and counts int32 [N], in place: for every id in ids int64 [P] that lies in
+ *                         [0, N), votes[id] += outputs[p] and counts[id] += 1 with p the LAST row of this call that
+ *                         carries the id (an id that occurs several times is counted once, as in the reference, where
+ *                         torch leaves open which occurrence).  outputs [P, C] of dtype DVA_F32 / DVA_BF16 / DVA_F16,
+ *                         widened exactly.  An id outside [0, N) writes nothing and adds 1 to n_bad int64 [1].
+ *                         slots int32 [dva_vote_workspace_bytes(N) / 4]: all -1 on entry (the caller fills it once)
+ *                         and all -1 again on exit.
+ *   dva_knn_interpolate   x fp32 [M, C]; neighbors int32 [n, k] and dist2 fp32 [n, k] as dva_knn_query returns them
+ *                         (k <= M).  Per query, in fp32, every operation rounded on its own, in neighbour rank order:
+ *                         w_r = 1 / max(d2_r, 1e-16); num = ((0 + x[nbr_0] w_0) + x[nbr_1] w_1) + ...;
+ *                         den = ((0 + w_0) + w_1) + ...; value = num / den: torch_geometric's knn_interpolate.
+ *                         own int32 [n] (nullable): where own[i] >= 0 the value of query i is the row x[own[i]] as it
+ *                         is (a point that has votes keeps them; kitti360_tracker.py:219-222).
+ *                         Outputs, each nullable, at least one given: y fp32 [n, C] = the values; pred int64 [n] =
+ *                         their argmax as numpy's (the first maximum, a NaN is the maximum); counts int64 [C, C] += 1
+ *                         at [labels[i], pred[i]] (labels int64 [n], required with counts) for the rows whose label is
+ *                         not ignore_index, a label outside [0, C) adding 1 to n_bad int64 [1] instead (required
+ *                         with counts).  A neighbour or own index outside [0, M) gives a NaN row, pred -1, no count
+ *                         and 1 in n_bad.  With y NULL no [n, C] buffer exists. */
+int64_t dva_vote_workspace_bytes(int64_t N);
+int dva_vote_add(float* votes, int32_t* counts, int64_t N, int32_t C, const int64_t* ids, const void* outputs,
+                 int32_t dtype, int64_t P, int32_t* slots, int64_t slots_bytes, int64_t* n_bad, void* stream);
+int dva_knn_interpolate(const float* x, int64_t M, int32_t C, const int32_t* neighbors, const float* dist2, int64_t n,
+                        int32_t k, const int32_t* own, float* y, int64_t* pred, const int64_t* labels,
+                        int64_t ignore_index, int64_t* counts, int64_t* n_bad, void* stream);
+
+/* ------------------------------------------------------------------------------------------ *
+ * Lexicographic integer keys. Replace utils/multimodal.py:36-94 (lexargsort / lexargunique on a
  * composite int64 key, :97-179 CompositeTensor, :253-323 lex ops).
  * ------------------------------------------------------------------------------------------ */
 

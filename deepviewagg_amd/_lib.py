@@ -227,6 +227,11 @@ SIGNATURES = {
     "dva_vote_add": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp]),
     "dva_knn_interpolate": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
                                            _vp]),
+    "dva_mapping_merge_tile_atoms": (ctypes.c_int, []),
+    "dva_mapping_merge_workspace_bytes": (ctypes.c_int64, [_i64, _i64, _i64]),
+    "dva_mapping_merge_count": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "dva_mapping_merge_fill": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i64, _i64, _i64, _i64, _i64, _i64,
+                                              _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "dva_lex_workspace_bytes": (ctypes.c_int64, [_i64]),
     "dva_argsort_i64": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "dva_argunique_i64": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp]),

@@ -305,21 +305,51 @@ class ImageMapping(CSRData):
         point_ids = point_ids[out.pointers[1:] - 1]
         return out.insert_empty_groups(point_ids, num_groups=self.num_groups), seen
 
+    # test / measurement hook: False sends device mappings through the torch composition as well
+    MERGE_ON_DEVICE = True
+
     def select_points(self, idx, mode='pick'):
         """'pick': keep the points ``idx`` (in that order). 'merge': point i becomes voxel idx[i];
         views of merged points are united, duplicate pixels removed, features of a merged view are
-        averaged (reference image.py:2167-2277)."""
+        averaged (reference image.py:2167-2277).  A merge of a device mapping is one device op
+        (``ops.merge_mapping``, a single readback of the output sizes); CPU mappings, and what the op
+        does not take, go through ``_merge_points_composition``."""
         modes = ['pick', 'merge']
         assert mode in modes, f"Unknown mode '{mode}'. Supported modes are {modes}."
         idx = tensor_idx(idx).to(self.device)
         if idx is None or idx.shape[0] == 0 or self.num_groups == 0:
             return self.clone()
-        if self.num_items == 0:
+        on_device = mode == 'merge' and self.MERGE_ON_DEVICE and self.pointers.is_cuda
+        # num_views is a shape, num_items a read of the last pointer: the same number, without the host sync
+        if (self.num_views if on_device else self.num_items) == 0:
             out = self.clone()
             out.pointers = torch.zeros(idx.shape[0] + 1, dtype=torch.long, device=self.device)
             return out
         if mode == 'pick':
             return self[idx]
+        if on_device:
+            return self._merge_points_device(idx)
+        return self._merge_points_composition(idx)
+
+    def _merge_points_device(self, idx):
+        from ..._lib import DvaError
+        try:
+            pointers, images, atom_ptr, pixels, features, ok = ops.merge_mapping(
+                self.pointers, self.images, self.values[1].pointers, self.pixels, self.features, idx)
+        except DvaError as err:
+            if err.code != -2:      # DVA_ERR_UNSUPPORTED: dtypes / sizes outside the kernels' range
+                raise
+            return self._merge_points_composition(idx)
+        if not ok:
+            return self.clone()
+        values = [images, CSRData(atom_ptr, pixels, dense=False)]
+        if features is not None:
+            values.append(features)
+        return ImageMapping(pointers, *values, dense=False, is_index_value=[True, False, False][:len(values)])
+
+    def _merge_points_composition(self, idx):
+        """The reference's composition (image.py:2211-2273) in torch: expansion to atom rows, a four-key
+        ``lexargunique`` and ``from_dense``.  Serves CPU mappings and is the yardstick of the device op."""
         if not idx.shape[0] == self.num_groups > 0:
             return self.clone()
         if not torch.arange(int(idx.max()) + 1, device=self.device).equal(idx.unique()):

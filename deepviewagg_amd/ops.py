@@ -21,6 +21,7 @@ ops; names and argument meaning follow the reference call site
 ``log_softmax_nll``        models/segmentation/sparseconv3d.py:45-51 (``F.log_softmax`` + ``F.nll_loss``)
 ``lovasz_softmax_flat``    metrics/lovasz_loss.py:174-215 (``flatten_probas`` + ``lovasz_softmax_flat``)
 ``confusion_counts``       metrics/segmentation_tracker.py:72-83 (mask + ``np.argmax`` + ``np.bincount``)
+``merge_mapping``          core/multimodal/image.py:2211-2273 (``select_points(mode='merge')`` + ``from_dense``)
 =========================  ==========================================================
 
 All ops require tensors on a HIP device and raise otherwise (no CPU fallback).
@@ -1491,6 +1492,80 @@ def voxel_parent_index(in_coords, out_coords, stride_out, batch_col=3):
         check(lib.dva_voxel_parent_index(ptr(ic), n_in, ptr(oc), n_out, int(stride_out), int(batch_col), ptr(idx),
                                          ptr(ws), int(nbytes), stream_of(ic)), "dva_voxel_parent_index")
     return idx
+
+
+# ---------------------------------------------------------------------------------------------
+# mapping merge after a strided 3D convolution (core/multimodal/image.py:2211-2273 + :1728-1795)
+# ---------------------------------------------------------------------------------------------
+MERGE_TILE_ATOMS = 512      # atoms of a voxel merged in LDS (dva_mapping_merge_tile_atoms); larger voxels sort in the workspace
+
+
+def _merge_unsupported(what):
+    return _lib.DvaError(f"ops.merge_mapping: {what}: {_lib._ERRORS[-2]}", code=-2)
+
+
+def merge_mapping(pointers, images, atom_ptr, pixels, features, idx):
+    """Mapping of the voxels ``idx[i]`` of the points of a mapping: ``(pointers', images', atom_ptr', pixels',
+    features', ok)``.  The views of the points of a voxel are united per image (ascending image id), the pixels of a
+    merged view are its distinct (x, y) in ascending order, its features the fp32 mean of the source views in
+    ascending point order (``features`` [V, F] or [V] or None).  ``ok`` is False, and the inputs come back, when
+    ``idx`` is not one id per point or some id below ``max(idx)`` has no point (the reference returns the mapping
+    unchanged then).  One host synchronisation: the readback of the output sizes.  Raises ``DvaError`` with
+    ``code == -2`` for what the kernels do not take (pixels other than int16, indices other than int64, 2^31 or more
+    views or atoms)."""
+    lib = _lib.load()
+    dev = require_device(pointers, images, atom_ptr, pixels, features, idx)
+    for name, t in (("pointers", pointers), ("images", images), ("atom_ptr", atom_ptr), ("idx", idx)):
+        if t.dim() != 1:
+            raise ValueError(f"ops.merge_mapping: {name} must be 1-D, got {tuple(t.shape)}")
+        if t.dtype != torch.int64:
+            raise _merge_unsupported(f"{name} is {t.dtype}, not int64")
+    if pixels.dim() != 2 or pixels.shape[1] != 2:
+        raise ValueError(f"ops.merge_mapping: pixels must be [P, 2], got {tuple(pixels.shape)}")
+    if pixels.dtype != torch.int16:
+        raise _merge_unsupported(f"pixels are {pixels.dtype}, not int16")
+    n, v, p = pointers.shape[0] - 1, images.shape[0], pixels.shape[0]
+    if n < 1 or atom_ptr.shape[0] != v + 1:
+        raise ValueError(f"ops.merge_mapping: {n} points, {v} views and {atom_ptr.shape[0]} atom pointers")
+    if features is not None and (features.dim() not in (1, 2) or features.shape[0] != v):
+        raise ValueError(f"ops.merge_mapping: features must be [{v}, F] or [{v}], got {tuple(features.shape)}")
+    if idx.shape[0] != n:
+        return pointers, images, atom_ptr, pixels, features, False
+    nbytes = lib.dva_mapping_merge_workspace_bytes(n, v, p)
+    if nbytes == -2:
+        raise _merge_unsupported(f"{n} points, {v} views, {p} atoms")
+    if nbytes < 0:
+        raise _lib.DvaError(f"dva_mapping_merge_workspace_bytes({n}, {v}, {p})", int(nbytes))
+    pointers, images, atom_ptr = pointers.contiguous(), images.contiguous(), atom_ptr.contiguous()
+    pixels, idx = pixels.contiguous(), idx.contiguous()
+    feat = None
+    if features is not None:
+        feat = features.detach().float().reshape(v, -1).contiguous()
+    f = 0 if feat is None else feat.shape[1]
+    feat_in = feat if f > 0 else None
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    sizes = torch.empty(4, dtype=torch.int64, device=dev)
+    s = stream_of(pointers)
+    read = n * 8 + v * 16 + p * 4
+    with _timed("mapping_merge_count", read + n * 8):
+        check(lib.dva_mapping_merge_count(ptr(pointers), ptr(images), ptr(atom_ptr), ptr(pixels), 2, ptr(idx), n, v, p,
+                                          ptr(sizes), ptr(ws), int(nbytes), s), "dva_mapping_merge_count")
+    m, v_out, p_out, ok = sizes.tolist()                  # host read: the sizes of the outputs
+    if not ok:
+        return pointers, images, atom_ptr, pixels, features, False
+    out_ptr = torch.empty(m + 1, dtype=torch.int64, device=dev)
+    out_img = torch.empty(v_out, dtype=torch.int64, device=dev)
+    out_aptr = torch.empty(v_out + 1, dtype=torch.int64, device=dev)
+    out_pix = torch.empty((p_out, 2), dtype=torch.int16, device=dev)
+    out_feat = None if feat is None else torch.empty((v_out, f), dtype=torch.float32, device=dev)
+    with _timed("mapping_merge_fill", read + v * f * 4 + m * 8 + v_out * 16 + p_out * 4 + v_out * f * 4):
+        check(lib.dva_mapping_merge_fill(ptr(pointers), ptr(images), ptr(atom_ptr), ptr(pixels), 2, ptr(feat_in), f,
+                                         n, v, p, m, v_out, p_out, ptr(out_ptr), ptr(out_img), ptr(out_aptr),
+                                         ptr(out_pix), ptr(out_feat if f > 0 else None), ptr(ws), int(nbytes), s),
+              "dva_mapping_merge_fill")
+    if out_feat is not None and features.dim() == 1:
+        out_feat = out_feat.view(-1)
+    return out_ptr, out_img, out_aptr, out_pix, out_feat, True
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1163,6 +1163,39 @@ int dva_mapping_features(const float* xyz, const int64_t* idx, const float* dept
                          const float* scattering, const float* normals, const dva_camera* cam,
                          int64_t q, float* features, int32_t* n_cols, void* stream);
 
+/* ------------------------------------------------------------------------------------------ *
+ * Mapping merge after a strided 3D convolution.  Replaces ImageMapping.select_points(idx,
+ * mode='merge') + from_dense (core/multimodal/image.py:2211-2273, :1728-1795): point i becomes voxel
+ * idx[i]; the views of a voxel's points are united per image (ascending image id), duplicate pixels
+ * of a merged view removed (ascending x, then y), the features of a merged view are the fp32 mean of
+ * its source views, added in ascending point order and divided by their number.
+ * Mapping over n_points points: pointers int64 [n_points + 1], images int64 [n_views] (< 2^31),
+ * atom_ptr int64 [n_views + 1], pixels int16 [n_atoms, 2] as (x, y), non-negative (pixel_bytes = 2;
+ * 1 / 4 / 8 return DVA_ERR_UNSUPPORTED), features fp32 [n_views, F] nullable; idx int64 [n_points].
+ * n_points, n_views, n_atoms >= 2^31 - 1 return DVA_ERR_UNSUPPORTED.
+ * dva_mapping_merge_count writes sizes[4] (device) = {M = max(idx) + 1, views of the result, atoms of
+ * the result, ok}; ok = 0 when some id in [0, M) has no point or an id is outside [0, n_points): the
+ * caller keeps the input mapping (image.py:2229-2233) and does not call the fill.  The caller reads
+ * sizes back (the only host synchronisation of the operation), allocates the outputs and calls
+ * dva_mapping_merge_fill with the SAME workspace, untouched in between: out_pointers int64 [M + 1],
+ * out_images int64 [V'], out_atom_ptr int64 [V' + 1], out_pixels int16 [P', 2], out_features fp32
+ * [V', F] (null iff features is null).  Every output element is written exactly once, without float
+ * atomics: two calls give the same bits.  dva_mapping_merge_tile_atoms: the atoms of a voxel up to
+ * which it is merged in LDS; larger voxels are sorted in the workspace.
+ * ------------------------------------------------------------------------------------------ */
+int dva_mapping_merge_tile_atoms(void);
+int64_t dva_mapping_merge_workspace_bytes(int64_t n_points, int64_t n_views, int64_t n_atoms);
+int dva_mapping_merge_count(const int64_t* pointers, const int64_t* images, const int64_t* atom_ptr,
+                            const void* pixels, int32_t pixel_bytes, const int64_t* idx, int64_t n_points,
+                            int64_t n_views, int64_t n_atoms, int64_t* sizes, void* workspace,
+                            int64_t workspace_bytes, void* stream);
+int dva_mapping_merge_fill(const int64_t* pointers, const int64_t* images, const int64_t* atom_ptr,
+                           const void* pixels, int32_t pixel_bytes, const float* features, int32_t F,
+                           int64_t n_points, int64_t n_views, int64_t n_atoms, int64_t n_voxels,
+                           int64_t n_views_out, int64_t n_atoms_out, int64_t* out_pointers, int64_t* out_images,
+                           int64_t* out_atom_ptr, void* out_pixels, float* out_features, void* workspace,
+                           int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

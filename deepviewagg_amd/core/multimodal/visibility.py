@@ -284,11 +284,14 @@ class VisibilityModel:
         ncol = 2 + sum(a is not None for a in (lin, pla, sca, nrm))
         feats = torch.empty((q, ncol), dtype=torch.float32, device=dev)
         row_image = torch.empty(q, dtype=torch.int32, device=dev)
-        got = ctypes.c_int32(0)
-        check(lib.dva_mapping_features_batch(ptr(xyz_d), ptr(idx), ptr(depth), ptr(y_proj), ptr(lin), ptr(pla),
-                                             ptr(sca), ptr(nrm), ptr(cams_d), ptr(row_ptr), B, q, ptr(feats),
-                                             ptr(row_image), ctypes.byref(got), st), "dva_mapping_features_batch")
-        assert got.value == ncol
+        # no rows: nothing to compute (and the attributes of an EMPTY cloud have null data pointers, which the entry would
+        # read as "attribute not given": its column count would not be ncol)
+        if q > 0:
+            got = ctypes.c_int32(0)
+            check(lib.dva_mapping_features_batch(ptr(xyz_d), ptr(idx), ptr(depth), ptr(y_proj), ptr(lin), ptr(pla),
+                                                 ptr(sca), ptr(nrm), ptr(cams_d), ptr(row_ptr), B, q, ptr(feats),
+                                                 ptr(row_image), ctypes.byref(got), st), "dva_mapping_features_batch")
+            assert got.value == ncol
         return {'idx': idx[:q].to(in_device), 'x': x_pix[:q].to(in_device), 'y': y_pix[:q].to(in_device),
                 'depth': depth[:q].to(in_device), 'features': feats.to(in_device),
                 'x_proj': x_proj[:q].to(in_device), 'y_proj': y_proj[:q].to(in_device),

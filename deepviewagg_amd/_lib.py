@@ -216,6 +216,10 @@ SIGNATURES = {
     "dva_elastic_workspace_bytes": (ctypes.c_int64, [_i64, _i64, _i64]),
     "dva_elastic_smooth": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
     "dva_elastic_displace": (ctypes.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _f64, _vp, _vp]),
+    "dva_image_tail_workspace_bytes": (ctypes.c_int64, [_i64]),
+    "dva_image_tail_u8": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64,
+                                         _vp]),
+    "dva_image_normalize_f32": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "dva_lovasz_tile": (ctypes.c_int, []),
     "dva_seg_nll_workspace_bytes": (ctypes.c_int64, []),
     "dva_seg_logsoftmax_nll_fwd": (ctypes.c_int, [_vp, _i32, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),

@@ -592,8 +592,152 @@ class RandomHorizontalFlip(ImageTransform):
 
 
 class ToFloatImage(ImageTransform):
-    """[0, 255] uint8 images -> [0, 1] float tensors (:1221-1232)."""
+    """[0, 255] uint8 images -> [0, 1] float tensors (:1221-1232).  uint8 ``[B, 3, H, W]`` images on the device take
+    ``ops.image_tail``: the correctly rounded ``f32(p) / f32(255)`` of the reference's host division in one pass.
+    (torch's device division by a scalar multiplies by the rounded reciprocal instead, which is one ulp away from the
+    reference for 126 of the 256 byte values; anything else keeps that expression.)"""
 
     def _process(self, data, images):
-        images.x = images.x.float() / 255
+        x = images.x
+        if x.is_cuda and x.dtype == torch.uint8 and x.dim() == 4 and x.shape[1] == 3:
+            from .... import ops
+            images.x = ops.image_tail(x, to_float=True)
+        else:
+            images.x = x.float() / 255
         return data, images
+
+
+# ---- the radiometric tail of the chains (reference :64-68, :1235-1282) -----------------------------------------
+# The reference's ColorJitter and Normalize wrap torchvision.transforms 0.8.2 objects.  torchvision is no dependency
+# here and no fixture of it exists, so parity with it is unpinned: the arithmetic documented at ``ops.image_tail``,
+# restated from torchvision 0.8.2's ColorJitter.forward and functional_tensor, is the contract.  Hue, GaussianBlur
+# (no shipped config uses it), LoadImages and NonStaticMask are not provided.
+
+class ToImageData(ImageTransform):
+    """Wrap a ``SameSettingImageData`` into an ``ImageData`` of one setting (:64-68)."""
+
+    def _process(self, data, images):
+        from ...multimodal.image import ImageData
+        return data, ImageData([images])
+
+
+class ColorJitter(ImageTransform):
+    """Randomly change the brightness, contrast and saturation of uint8 ``[B, 3, H, W]`` images (:1249-1259), one set of
+    factors for all the images of the setting.  Each argument is a number ``v >= 0``, giving the range
+    ``[max(0, 1 - v), 1 + v]``, or a pair ``(lo, hi)`` with ``0 <= lo <= hi``; a range ``[1, 1]`` leaves the op out.
+
+    ``draw()`` makes torchvision 0.8.2's draws on the host default generator: ``torch.randperm(4)`` orders brightness,
+    contrast, saturation and hue (ids 0-3; hue is never present and draws nothing), and every present op, in that
+    order, draws ``torch.tensor(1.0).uniform_(lo, hi).item()``.  The ops are applied in that order by
+    ``ops.image_tail``, whose docstring states the pixel arithmetic (the contract; parity with torchvision is
+    unpinned)."""
+    _NAMES = ('brightness', 'contrast', 'saturation')
+
+    def __init__(self, brightness=0, contrast=0, saturation=0):
+        self.brightness = brightness
+        self.contrast = contrast
+        self.saturation = saturation
+        for name in self._NAMES:
+            self._range(name)
+
+    def _range(self, name):
+        """(lo, hi) of the factor of op ``name``, None when the op is absent."""
+        value = getattr(self, name)
+        if isinstance(value, (int, float)):
+            if value < 0:
+                raise ValueError(f"If {name} is a single number, it must be non negative.")
+            lo, hi = max(1.0 - float(value), 0.0), 1.0 + float(value)
+        elif isinstance(value, (tuple, list)) and len(value) == 2:
+            lo, hi = float(value[0]), float(value[1])
+            if not 0.0 <= lo <= hi < float('inf'):
+                raise ValueError(f"{name} values should be between (0, inf) and ordered, got {value}.")
+        else:
+            raise TypeError(f"{name} should be a single number or a list/tuple with length 2.")
+        return None if lo == hi == 1.0 else (lo, hi)
+
+    def draw(self):
+        """The ``[(name, factor), ...]`` list of one application, in application order.  Host only."""
+        out = []
+        for op_id in torch.randperm(4).tolist():
+            if op_id == 3:
+                continue
+            bounds = self._range(self._NAMES[op_id])
+            if bounds is not None:
+                out.append((self._NAMES[op_id], torch.tensor(1.0).uniform_(bounds[0], bounds[1]).item()))
+        return out
+
+    def _process(self, data, images):
+        from .... import ops
+        images.x = ops.image_tail(images.x, jitter=self.draw())
+        return data, images
+
+
+class Normalize(ImageTransform):
+    """``(x - mean[c]) / std[c]`` on float32 ``[B, C, H, W]`` images (:1271-1282; the defaults are the ImageNet / ADE20K
+    statistics of the reference)."""
+
+    def __init__(self, mean=[0.485, 0.456, 0.406], std=[0.229, 0.224, 0.225]):
+        self.mean = mean
+        self.std = std
+
+    def _process(self, data, images):
+        from .... import ops
+        images.x = ops.image_tail(images.x, mean=self.mean, std=self.std)
+        return data, images
+
+
+class FusedImageTail(ImageTransform):
+    """``ColorJitter -> RandomHorizontalFlip -> ToFloatImage -> Normalize`` (each optional) as one pass over the uint8
+    images: ``ops.image_tail`` reads the pixels once and writes the encoder's float32 input once, in at most two
+    kernel launches per setting.  Built from instances of those classes; from the same generator state it gives the
+    ``images.x`` (bit for bit) and the flipped ``mappings.pixels[:, 0]`` of the eager chain and leaves the same
+    generator state.
+
+    On an ``ImageData`` the eager chain draws transform by transform -- every setting's jitter first, then every
+    setting's flip -- so this transform takes the whole ``ImageData`` and draws in that order before it launches."""
+    _PROCESS_IMAGE_DATA = True
+
+    def __init__(self, color_jitter=None, flip=None, to_float=True, normalize=None):
+        self.color_jitter = color_jitter
+        self.flip = flip
+        self.to_float = to_float
+        self.normalize = normalize
+
+    def _process(self, data, images):
+        from .... import ops
+        from ...multimodal.image import ImageData
+        settings = list(images) if isinstance(images, ImageData) else [images]
+        jitters = [self.color_jitter.draw() if self.color_jitter is not None else () for _ in settings]
+        flips = [bool(torch.rand(1) <= self.flip.p) if self.flip is not None else False for _ in settings]
+        stats = {} if self.normalize is None else dict(mean=self.normalize.mean, std=self.normalize.std)
+        for im, jitter, flip in zip(settings, jitters, flips):
+            im.x = ops.image_tail(im.x, jitter=jitter, flip=flip, to_float=bool(self.to_float), **stats)
+            if flip:
+                width = im.x.shape[-1]
+                pix = im.mappings.pixels
+                pix[:, 0] = (width - 1 - pix[:, 0].long()).to(pix.dtype)
+        return data, (ImageData(settings) if isinstance(images, ImageData) else images)
+
+
+def fuse_image_tail(transforms):
+    """A new list in which every maximal run ``[ColorJitter] [RandomHorizontalFlip] ToFloatImage [Normalize]`` of
+    ``transforms`` (in that order, the bracketed ones optional) is replaced by one ``FusedImageTail`` holding those
+    instances.  A run without ``ToFloatImage`` and everything else stay as they are, in order."""
+    transforms = list(transforms)
+    out, i = [], 0
+    while i < len(transforms):
+        j, parts = i, {}
+        for key, cls in (('color_jitter', ColorJitter), ('flip', RandomHorizontalFlip), ('to_float', ToFloatImage),
+                         ('normalize', Normalize)):
+            if j < len(transforms) and type(transforms[j]) is cls:
+                parts[key] = transforms[j]
+                j += 1
+            elif cls is ToFloatImage:
+                break
+        if 'to_float' in parts:
+            out.append(FusedImageTail(**parts))
+            i = j
+        else:
+            out.append(transforms[i])
+            i += 1
+    return out

@@ -335,7 +335,7 @@ using namespace dva;
 
 extern "C" {
 
-int dva_version(void) { return 316; }
+int dva_version(void) { return 317; }
 
 int dva_device_count(void) {
   int n = 0;

@@ -13,7 +13,10 @@ and imports the data classes from
 ``torch_points3d.core.multimodal.{csr,image}``, and takes ``lovasz_softmax`` and ``ConfusionMatrix`` from
 ``torch_points3d.metrics.{lovasz_loss,confusion_matrix}`` and ``SegmentationVoter`` from
 ``torch_points3d.metrics.segmentation_helpers``; where the reference's ``SegmentationTracker`` can be imported,
-its ``_compute_metrics`` becomes ``deepviewagg_amd.metrics.segmentation_tracker.compute_metrics``.  ``install()`` either patches an importable
+its ``_compute_metrics`` becomes ``deepviewagg_amd.metrics.segmentation_tracker.compute_metrics``.  The image transforms
+of the data configs resolve on ``torch_points3d.core.data_transform.multimodal.image``, which is aliased whole: with
+``ColorJitter``, ``Normalize`` and ``ToImageData`` every per-sample image transform the shipped chains name is there, next
+to ``FusedImageTail`` and ``fuse_image_tail`` (one pass for the tail of a chain).  ``install()`` either patches an importable
 ``torch_points3d`` in place (attribute by attribute) or, when the package is absent, registers alias
 modules under those dotted names in ``sys.modules``.
 """

@@ -18,6 +18,7 @@ ops; names and argument meaning follow the reference call site
 ``elastic_smooth``         grid_transform.py:231-234 (six ``scipy.ndimage.convolve`` calls)
 ``elastic_displace``       grid_transform.py:241-242 (``RegularGridInterpolator``)
 ``elastic_distortion``     grid_transform.py:218-243 (one level of ElasticDistortion)
+``image_tail``             core/data_transform/multimodal/image.py:1195-1282 (ColorJitter, flip, ToFloatImage, Normalize)
 ``log_softmax_nll``        models/segmentation/sparseconv3d.py:45-51 (``F.log_softmax`` + ``F.nll_loss``)
 ``lovasz_softmax_flat``    metrics/lovasz_loss.py:174-215 (``flatten_probas`` + ``lovasz_softmax_flat``)
 ``confusion_counts``       metrics/segmentation_tracker.py:72-83 (mask + ``np.argmax`` + ``np.bincount``)
@@ -2234,6 +2235,117 @@ def elastic_distortion(pos, granularity, magnitude, noise=None):
         for d_min, d_max, d in zip(coords_min - granularity, coords_min + granularity * (noise_dim - 2), noise_dim)
     ]
     return elastic_displace(p, elastic_smooth(noise), ax, magnitude)
+
+
+# ---------------------------------------------------------------------------------------------
+# the image tail (core/data_transform/multimodal/image.py:1195-1282: ColorJitter, RandomHorizontalFlip, ToFloatImage,
+# Normalize; csrc/image_tail.hip)
+# ---------------------------------------------------------------------------------------------
+
+JITTER_CODE = {"brightness": 0, "contrast": 1, "saturation": 2}      # DVA_JITTER_*
+IMAGE_MAX_CHANNELS = 64                                               # DVA_IMAGE_MAX_CHANNELS
+
+
+def _image_tail_stats(mean, std, channels):
+    """``mean`` / ``std`` as two ctypes float arrays of ``channels`` entries, or (None, None)."""
+    import ctypes
+    if mean is None and std is None:
+        return None, None
+    if mean is None or std is None:
+        raise ValueError("ops.image_tail: mean and std go together")
+    mean, std = [float(v) for v in mean], [float(v) for v in std]
+    if len(mean) != channels or len(std) != channels:
+        raise ValueError(f"ops.image_tail: {len(mean)} means and {len(std)} stds for {channels} channels")
+    if channels > IMAGE_MAX_CHANNELS:
+        raise ValueError(f"ops.image_tail: {channels} channels, the kernel normalises at most {IMAGE_MAX_CHANNELS}")
+    arr = ctypes.c_float * channels
+    std_f32 = arr(*std)
+    if any(v == 0 for v in std_f32):
+        raise ValueError(f"ops.image_tail: std evaluated to zero after conversion to float32: {std}")
+    return arr(*mean), std_f32
+
+
+def image_tail(x, jitter=(), flip=False, to_float=False, mean=None, std=None):
+    """The per-pixel tail of the image transform chains in one pass: the ``jitter`` ops, the horizontal ``flip``,
+    ``ToFloatImage`` (``to_float``) and ``Normalize`` (``mean`` / ``std``), in that order, whichever are asked for.
+
+    ``x`` uint8 ``[B, 3, H, W]``: ``jitter`` is a sequence of ``(name, factor)`` with the names ``brightness``,
+    ``contrast``, ``saturation``, each at most once, applied in the given order with ``factor >= 0``.  Returns uint8
+    ``[B, 3, H, W]`` without ``to_float`` and float32 with it; ``mean`` / ``std`` (three numbers each) need
+    ``to_float``.  ``x`` float32 ``[B, C, H, W]``: ``mean`` / ``std`` (C numbers each, C <= 64) alone.
+
+    The contract is this arithmetic, restated from torchvision 0.8.2's ``ColorJitter.forward`` and
+    ``functional_tensor`` (the reference's transforms wrap that package; parity with it is unpinned, no fixture of it
+    exists) -- float32 throughout, every operation rounded on its own, true division, ``u8`` = truncation:
+    ``gray = u8((f32(0.2989) r + f32(0.587) g) + f32(0.114) b)``; ``blend(p, q, f) = u8(clamp(f32(f) p + f32(1.0 - f)
+    q, 0, 255))`` with ``1.0 - f`` taken in double; brightness ``blend(p, 0, f)``, saturation ``blend(p, gray, f)``,
+    contrast ``blend(p, m_i, f)`` with ``m_i = f32(S_i) / f32(H W)``, ``S_i`` the exact integer sum of ``gray`` over
+    image ``i`` after the ops that precede contrast (where ``H W <= 65793`` this is ``torch.mean`` of the gray image
+    bit for bit, beyond it ``torch.mean`` depends on torch's summation order and the integer sum is the definition);
+    flip: output column ``w`` takes source column ``W - 1 - w``; ``f32(p) / f32(255)``; ``(v - mean[c]) / std[c]``.
+
+    One kernel, two with contrast (integer atomics only: the same call gives the same bytes); no host
+    synchronisation.  A call that asks for nothing returns ``x`` itself."""
+    if not torch.is_tensor(x):
+        raise TypeError("ops.image_tail: x must be a tensor")
+    dev = require_device(x)
+    jitter = [(str(name), float(factor)) for name, factor in jitter]
+    if x.dim() != 4:
+        raise ValueError(f"ops.image_tail: x must be [B, C, H, W], got {tuple(x.shape)}")
+    B, C, H, W = (int(d) for d in x.shape)
+    if x.dtype != torch.uint8:
+        if jitter:
+            raise TypeError(f"ops.image_tail: jitter takes uint8 images, got {x.dtype}")
+        if x.dtype != torch.float32:
+            raise TypeError(f"ops.image_tail takes uint8 or float32 images, got {x.dtype}")
+        if to_float:
+            raise TypeError("ops.image_tail: to_float takes uint8 images, x is float32 already")
+        if flip:
+            raise TypeError("ops.image_tail: the flip is fused into the uint8 pass only, x is float32")
+    else:
+        if C != 3:
+            raise ValueError(f"ops.image_tail: uint8 images must be [B, 3, H, W], got {tuple(x.shape)}")
+        if (mean is not None or std is not None) and not to_float:
+            raise TypeError("ops.image_tail: Normalize takes float images; pass to_float=True for uint8 input")
+    names = [name for name, _ in jitter]
+    for name, factor in jitter:
+        if name not in JITTER_CODE:
+            raise ValueError(f"ops.image_tail: unknown jitter op {name!r} (one of {sorted(JITTER_CODE)})")
+        if not (0.0 <= factor < float("inf")):
+            raise ValueError(f"ops.image_tail: the {name} factor must be a finite number >= 0, got {factor}")
+    if len(set(names)) != len(names):
+        raise ValueError(f"ops.image_tail: every jitter op at most once, got {names}")
+    mean_c, std_c = _image_tail_stats(mean, std, C)
+    lib = _lib.load()
+    import ctypes
+    if x.dtype == torch.float32:
+        if mean_c is None:
+            return x
+        x = x.contiguous()
+        out = torch.empty_like(x)
+        if x.numel() == 0:
+            return out
+        with _timed("image_normalize_f32", 2 * x.numel() * 4):
+            check(lib.dva_image_normalize_f32(ptr(x), B, C, H * W, mean_c, std_c, ptr(out), stream_of(x)),
+                  "dva_image_normalize_f32")
+        return out
+    if not jitter and not flip and not to_float:
+        return x
+    x = x.contiguous()
+    out = torch.empty((B, C, H, W), dtype=torch.float32 if to_float else torch.uint8, device=dev)
+    if x.numel() == 0:
+        return out
+    ws, ws_bytes = None, 0
+    if "contrast" in names:
+        ws_bytes = int(lib.dva_image_tail_workspace_bytes(B))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    codes = (ctypes.c_int32 * len(jitter))(*[JITTER_CODE[name] for name in names])
+    factors = (ctypes.c_double * len(jitter))(*[factor for _, factor in jitter])
+    pixels = B * H * W
+    with _timed("image_tail", pixels * (3 + (3 if ws is not None else 0) + (12 if to_float else 3))):
+        check(lib.dva_image_tail_u8(ptr(x), B, H, W, codes, factors, len(jitter), int(bool(flip)), int(bool(to_float)),
+                                    mean_c, std_c, ptr(out), ptr(ws), ws_bytes, stream_of(x)), "dva_image_tail_u8")
+    return out
 
 
 # ---------------------------------------------------------------------------------------------

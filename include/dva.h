@@ -984,6 +984,48 @@ int dva_elastic_displace(const float* pos, int64_t n, const float* field, const 
                          int64_t dz, double magnitude, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------ *
+ * The image tail of the multimodal transform chains (image_tail.hip): ColorJitter -> RandomHorizontalFlip ->
+ * ToFloatImage -> Normalize of core/data_transform/multimodal/image.py:1195-1282, where ColorJitter and Normalize are
+ * torchvision.transforms 0.8.2 objects.  Parity with torchvision is UNPINNED (it is no dependency and no fixture of it
+ * exists): the arithmetic stated here, restated from its ColorJitter.forward and functional_tensor, is the contract.
+ * All of it is fp32, every operation rounded on its own, no fused multiply-add, correctly rounded division;
+ * u8(v) = truncation toward zero.
+ *   dva_image_tail_u8        x uint8 [B, 3, H, W].  The n_ops <= 3 ops op_codes[k] (DVA_JITTER_*, each at most once) are
+ *                            applied in order with the factors factors[k] >= 0 (HOST arrays; f = f32(factors[k]), the
+ *                            complement f32(1.0 - factors[k]) is taken in double here):
+ *                              gray            u8((f32(0.2989) r + f32(0.587) g) + f32(0.114) b)
+ *                              blend(p, q, f)  u8(clamp(f p + (1 - f) q, 0, 255))
+ *                              brightness      blend(p, 0, f);  saturation  blend(p, gray(pixel), f)
+ *                              contrast        blend(p, m_i, f), m_i = f32(S_i) / f32(H W), S_i = the exact int64 sum
+ *                                              of gray over image i after the ops that precede contrast (per image,
+ *                                              not per batch)
+ *                            then, with flip, output column w takes source column W - 1 - w; with to_float the value
+ *                            is f32(p) / f32(255), and with mean / std (HOST fp32 [3] each, both or neither, to_float
+ *                            required, no zero in std) it is (v - mean[c]) / std[c].  out is uint8 [B, 3, H, W]
+ *                            without to_float and fp32 [B, 3, H, W] with it; it may not alias x.
+ *                            Launches: with contrast, a clear of the B accumulators on the stream and the gray-sum
+ *                            kernel (integer partial sums, one 64-bit integer atomic add per block: order-free, the
+ *                            same call gives the same bytes), then the apply kernel; one kernel otherwise.
+ *                            workspace: dva_image_tail_workspace_bytes(B), needed with contrast only (nullable
+ *                            otherwise); it need not be cleared by the caller.
+ *   dva_image_normalize_f32  out fp32 [B, C, HW] = (x - mean[c]) / std[c] for x fp32 [B, C, HW], 1 <= C <=
+ *                            DVA_IMAGE_MAX_CHANNELS (DVA_ERR_UNSUPPORTED beyond); mean / std HOST fp32 [C].  out may
+ *                            alias x.
+ * B <= 65535 and B H ceil(W / 4) < 2^31 (DVA_ERR_UNSUPPORTED beyond); B = 0 or an empty image is a no-op.  Argument
+ * errors (null pointer, negative size, more than three ops, a repeated or unknown op code, a negative factor, a zero
+ * in std) return DVA_ERR_INVALID before any HIP call.  Nothing synchronises. */
+#define DVA_JITTER_BRIGHTNESS 0
+#define DVA_JITTER_CONTRAST 1
+#define DVA_JITTER_SATURATION 2
+#define DVA_IMAGE_MAX_CHANNELS 64
+int64_t dva_image_tail_workspace_bytes(int64_t B);
+int dva_image_tail_u8(const uint8_t* x, int64_t B, int64_t H, int64_t W, const int32_t* op_codes,
+                      const double* factors, int32_t n_ops, int32_t flip, int32_t to_float, const float* mean,
+                      const float* std, void* out, void* workspace, int64_t workspace_bytes, void* stream);
+int dva_image_normalize_f32(const float* x, int64_t B, int64_t C, int64_t HW, const float* mean, const float* std,
+                            float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------ *
  * The tail of the segmentation step (segloss.hip).  Replaces F.log_softmax + F.nll_loss and lovasz_softmax of
  * models/segmentation/sparseconv3d.py:42-55 (metrics/lovasz_loss.py:155-202) and the argmax + bincount of
  * SegmentationTracker._compute_metrics (metrics/segmentation_tracker.py:71-91).

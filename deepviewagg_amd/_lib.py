@@ -299,6 +299,22 @@ def check(rc, what):
         raise DvaError(f"{what} failed: {_ERRORS.get(rc, rc)}", code=rc)
 
 
+def workspace_bytes(query_name, *args):
+    """Answer of a ``*_workspace_bytes`` query; a negative one is a DVA_ERR_* code and raises."""
+    nbytes = int(getattr(load(), query_name)(*args))
+    if nbytes < 0:
+        raise DvaError(f"{query_name}({', '.join(map(str, args))}) failed: {_ERRORS.get(nbytes, nbytes)}", code=nbytes)
+    return nbytes
+
+
+def workspace(query_name, device, *args):
+    """Scratch of an entry point on ``device``: ``(uint8 tensor, its size)``.  A refused query raises before the device
+    is touched."""
+    import torch
+    nbytes = workspace_bytes(query_name, *args)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+
 def ptr(t):
     """Device pointer of a tensor (None -> NULL)."""
     return None if t is None else ctypes.c_void_p(t.data_ptr())

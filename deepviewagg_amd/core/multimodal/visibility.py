@@ -142,10 +142,7 @@ class VisibilityModel:
         x_proj = torch.empty(cap, dtype=torch.float64, device=dev)
         y_proj = torch.empty(cap, dtype=torch.float64, device=dev)
         n_out = torch.zeros(1, dtype=torch.int64, device=dev)
-        ws_bytes = lib.dva_visibility_workspace_bytes(ctypes.byref(cam), n)
-        if ws_bytes < 0:
-            check(int(ws_bytes), "dva_visibility_workspace_bytes")
-        ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
+        ws, ws_bytes = _lib.workspace("dva_visibility_workspace_bytes", dev, ctypes.byref(cam), n)
         check(lib.dva_visibility(ptr(xyz_d), n, ctypes.byref(cam), ptr(mask_d), ptr(idx), ptr(x_pix),
                                  ptr(y_pix), ptr(depth), ptr(x_proj), ptr(y_proj), ptr(n_out), ptr(ws),
                                  int(ws_bytes), stream_of(xyz_d)), "dva_visibility")
@@ -267,10 +264,7 @@ class VisibilityModel:
         y_proj = torch.empty(cap, dtype=torch.float64, device=dev)
         row_ptr = torch.zeros(B + 1, dtype=torch.int64, device=dev)
         n_out = torch.zeros(1, dtype=torch.int64, device=dev)
-        ws_bytes = lib.dva_visibility_batch_workspace_bytes(ctypes.byref(cam0), n, B)
-        if ws_bytes < 0:
-            check(int(ws_bytes), "dva_visibility_batch_workspace_bytes")
-        ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
+        ws, ws_bytes = _lib.workspace("dva_visibility_batch_workspace_bytes", dev, ctypes.byref(cam0), n, B)
         st = stream_of(xyz_d)
         check(lib.dva_visibility_batch(ptr(xyz_d), n, ctypes.byref(cam0), ptr(cams_d), B, ptr(mask_d), ptr(idx),
                                        ptr(x_pix), ptr(y_pix), ptr(depth), ptr(x_proj), ptr(y_proj), ptr(row_ptr),
@@ -373,10 +367,7 @@ class _ProjectionVisibility(VisibilityModel):
         x_proj = torch.empty(cap, dtype=torch.float64, device=dev)
         y_proj = torch.empty(cap, dtype=torch.float64, device=dev)
         n_out = torch.zeros(1, dtype=torch.int64, device=dev)
-        ws_bytes = lib.dva_visibility_workspace_bytes(ctypes.byref(cam), n)
-        if ws_bytes < 0:
-            check(int(ws_bytes), "dva_visibility_workspace_bytes")
-        ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
+        ws, ws_bytes = _lib.workspace("dva_visibility_workspace_bytes", dev, ctypes.byref(cam), n)
         st = stream_of(xyz_d)
         check(lib.dva_camera_projection(ptr(xyz_d), n, ctypes.byref(cam), ptr(mask_d), ptr(idx1), ptr(dist),
                                         ptr(x_proj), ptr(y_proj), ptr(n_out), ptr(ws), int(ws_bytes), st),

@@ -901,12 +901,7 @@ static bool team_geometry(int C, int G, int64_t N, int64_t V, TeamGeom* tg) {
   return tg->lpg >= 1;
 }
 
-static inline int grid_cap(int64_t blocks) {
-  const int64_t cap = 256 * 16;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
-}
+static inline int grid_cap(int64_t blocks) { return capped_grid(blocks, 1, 256 * 16); }
 
 template <typename T>
 static int fwd_impl(const void* val, const int32_t* row_idx, const float* compat, const int64_t* ptr,

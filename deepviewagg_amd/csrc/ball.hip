@@ -41,7 +41,6 @@ struct __attribute__((aligned(32))) BallCentre {
   double x, y, z, r2;
 };
 
-static inline size_t balign(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline int64_t ball_tiles(int64_t n) { return (n + BALL_TILE - 1) / BALL_TILE; }
 static inline int64_t ball_segs(int64_t tiles) { return (tiles + BALL_SEG - 1) / BALL_SEG; }
 
@@ -232,15 +231,16 @@ __global__ __launch_bounds__(BALL_TPB) void ball_tile_offset_kernel(uint32_t* __
 }
 
 struct BallLayout {
-  size_t cnt, seg, total;
+  uint32_t *cnt, *seg;
+  size_t total;
 };
 
-static void ball_layout(int64_t n, int64_t B, BallLayout* L) {
+static void ball_layout(void* ws, int64_t n, int64_t B, BallLayout* L) {
   const int64_t tiles = ball_tiles(n);
-  size_t off = 0;
-  L->cnt = off; off += balign((size_t)tiles * (size_t)B * 4);
-  L->seg = off; off += balign((size_t)ball_segs(tiles) * (size_t)B * 4);
-  L->total = off < 256 ? 256 : off;
+  Carver c(ws);
+  L->cnt = c.take<uint32_t>((size_t)tiles * (size_t)B);
+  L->seg = c.take<uint32_t>((size_t)ball_segs(tiles) * (size_t)B);
+  L->total = c.used() < 256 ? 256 : c.used();
 }
 
 static int ball_check(const float* pos, int64_t n, const double* centres, int64_t B, int32_t dims, double radius,
@@ -262,7 +262,7 @@ int64_t dva_radius_query_workspace_bytes(int64_t n, int64_t n_centres) {
   if (n < 0 || n_centres < 0) return DVA_ERR_INVALID;
   if (n > BALL_MAX_N) return DVA_ERR_UNSUPPORTED;
   BallLayout L;
-  ball_layout(n, n_centres, &L);
+  ball_layout(nullptr, n, n_centres, &L);
   return (int64_t)L.total;
 }
 
@@ -273,7 +273,7 @@ int dva_radius_count(const float* pos, int64_t n, const double* centres, int64_t
   if (rc) return rc;
   if (!ptr) return DVA_ERR_INVALID;
   BallLayout L;
-  ball_layout(n, n_centres, &L);
+  ball_layout(workspace, n, n_centres, &L);
   if ((int64_t)L.total > workspace_bytes) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   const int64_t B = n_centres, tiles = ball_tiles(n), segs = ball_segs(tiles);
@@ -281,19 +281,17 @@ int dva_radius_count(const float* pos, int64_t n, const double* centres, int64_t
     if (hipMemsetAsync(ptr, 0, (size_t)(B + 1) * 8, s) != hipSuccess) return DVA_ERR_LAUNCH;
     return DVA_OK;
   }
-  uint32_t* cnt = (uint32_t*)((char*)workspace + L.cnt);
-  uint32_t* seg = (uint32_t*)((char*)workspace + L.seg);
   const dim3 pgrid((unsigned)((tiles + BALL_WAVES - 1) / BALL_WAVES));
   if (dims == 3)
     hipLaunchKernelGGL(ball_count_kernel<3>, pgrid, dim3(BALL_TPB), 0, s, pos, n, centres, B, radius, radii, tiles,
-                       cnt);
+                       L.cnt);
   else
     hipLaunchKernelGGL(ball_count_kernel<2>, pgrid, dim3(BALL_TPB), 0, s, pos, n, centres, B, radius, radii, tiles,
-                       cnt);
+                       L.cnt);
   const dim3 sgrid((unsigned)((B + BALL_TPB - 1) / BALL_TPB), (unsigned)segs);
-  hipLaunchKernelGGL(ball_seg_sum_kernel, sgrid, dim3(BALL_TPB), 0, s, cnt, B, tiles, seg);
-  hipLaunchKernelGGL(ball_ptr_kernel, dim3(1), dim3(BALL_SCAN_TPB), 0, s, seg, B, segs, ptr);
-  hipLaunchKernelGGL(ball_tile_offset_kernel, sgrid, dim3(BALL_TPB), 0, s, cnt, B, tiles, seg);
+  hipLaunchKernelGGL(ball_seg_sum_kernel, sgrid, dim3(BALL_TPB), 0, s, L.cnt, B, tiles, L.seg);
+  hipLaunchKernelGGL(ball_ptr_kernel, dim3(1), dim3(BALL_SCAN_TPB), 0, s, L.seg, B, segs, ptr);
+  hipLaunchKernelGGL(ball_tile_offset_kernel, sgrid, dim3(BALL_TPB), 0, s, L.cnt, B, tiles, L.seg);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -305,19 +303,18 @@ int dva_radius_fill(const float* pos, int64_t n, const double* centres, int64_t 
   if (rc) return rc;
   if (!ptr || idx_capacity < 0 || (idx_capacity > 0 && !idx)) return DVA_ERR_INVALID;
   BallLayout L;
-  ball_layout(n, n_centres, &L);
+  ball_layout(workspace, n, n_centres, &L);
   if ((int64_t)L.total > workspace_bytes) return DVA_ERR_INVALID;
   const int64_t B = n_centres, tiles = ball_tiles(n);
   if (B == 0 || n == 0 || idx_capacity == 0) return DVA_OK;
   hipStream_t s = (hipStream_t)stream;
-  const uint32_t* cnt = (const uint32_t*)((char*)workspace + L.cnt);
   const dim3 pgrid((unsigned)((tiles + BALL_WAVES - 1) / BALL_WAVES));
   if (dims == 3)
-    hipLaunchKernelGGL(ball_fill_kernel<3>, pgrid, dim3(BALL_TPB), 0, s, pos, n, centres, B, radius, radii, tiles, cnt,
-                       ptr, idx, idx_capacity);
+    hipLaunchKernelGGL(ball_fill_kernel<3>, pgrid, dim3(BALL_TPB), 0, s, pos, n, centres, B, radius, radii, tiles,
+                       L.cnt, ptr, idx, idx_capacity);
   else
-    hipLaunchKernelGGL(ball_fill_kernel<2>, pgrid, dim3(BALL_TPB), 0, s, pos, n, centres, B, radius, radii, tiles, cnt,
-                       ptr, idx, idx_capacity);
+    hipLaunchKernelGGL(ball_fill_kernel<2>, pgrid, dim3(BALL_TPB), 0, s, pos, n, centres, B, radius, radii, tiles,
+                       L.cnt, ptr, idx, idx_capacity);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }

@@ -693,10 +693,7 @@ __global__ __launch_bounds__(256) void csr_expand_kernel(const int64_t* __restri
 
 static inline int grid_rows(int64_t V) {
   // one wavefront per 32-row tile, 4 wavefronts per block, capped at 8 blocks per CU
-  int64_t b = ((V + TILE - 1) / TILE + 3) / 4;
-  if (b > 256 * 8) b = 256 * 8;
-  if (b < 1) b = 1;
-  return (int)b;
+  return capped_grid((V + TILE - 1) / TILE, 4, 256 * 8);
 }
 
 // fp32-MFMA generation of the layer kernels (deepset_mfma.hip); bf = bf16 activation storage

@@ -1196,12 +1196,7 @@ __global__ __launch_bounds__(256) void dsm_bwd_score_kernel(
   flush_stats<2>(stv, st, s_red, lane);
 }
 
-static inline int grid_tiles(int64_t V) {
-  int64_t b = ((V + 31) / 32 + 3) / 4;
-  if (b > 256 * 8) b = 256 * 8;
-  if (b < 1) b = 1;
-  return (int)b;
-}
+static inline int grid_tiles(int64_t V) { return capped_grid((V + 31) / 32, 4, 256 * 8); }
 
 // launchers used by the C entry points in deepset.hip; `bf` = the [V, 32] activation / gradient tensors
 // are stored as bf16 (else fp32)

@@ -121,4 +121,33 @@ struct __attribute__((aligned(8))) PackedIdx {
 
 static inline int blocks_for(int64_t n, int threads) { return (int)((n + threads - 1) / threads); }
 
+// Launch grid of a grid-stride kernel: ceil(n / per_block) blocks, at most `cap`, at least 1.
+static inline int capped_grid(int64_t n, int64_t per_block, int64_t cap) {
+  int64_t b = (n + per_block - 1) / per_block;
+  if (b > cap) b = cap;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+
+// `align` is a power of two: 256 for the regions of a workspace (16 inside the mapping merge's).
+static inline size_t align_up(size_t bytes, size_t align = 256) { return (bytes + align - 1) & ~(align - 1); }
+
+// Carves a caller-provided workspace into typed regions, each padded to `align` bytes.  A null base answers a size
+// query: the same sequence of take() calls then only adds up used().  (Addresses are uintptr_t, so that is defined.)
+class Carver {
+ public:
+  explicit Carver(void* base, size_t align = 256) : base_((uintptr_t)base), align_(align) {}
+  template <typename T>
+  T* take(size_t count) {
+    T* p = (T*)(base_ + off_);
+    off_ += align_up(count * sizeof(T), align_);
+    return p;
+  }
+  size_t used() const { return off_; }
+
+ private:
+  uintptr_t base_;
+  size_t off_ = 0, align_;
+};
+
 }  // namespace dva

@@ -27,8 +27,6 @@ constexpr int EL_MINMAX_BLOCKS = 256;                 // partial rows of the bou
 constexpr int EL_LDS_AXES = 4096;                     // knots (of the three axes together) staged in LDS: 32 KiB
 constexpr int64_t EL_MAX_ELEMS = 0x7fffffffLL;        // elements of pos and of the volume
 
-static inline size_t ealign(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // ---------------------------------------------------------------------------------------------------------------
 // bounds: out[0..2] = column minima, out[3..5] = column maxima.  min / max are exact and order-free.
 // ---------------------------------------------------------------------------------------------------------------
@@ -206,7 +204,7 @@ using namespace dva;
 
 extern "C" {
 
-int64_t dva_minmax3_workspace_bytes(void) { return (int64_t)ealign((size_t)EL_MINMAX_BLOCKS * 6 * sizeof(float)); }
+int64_t dva_minmax3_workspace_bytes(void) { return (int64_t)align_up((size_t)EL_MINMAX_BLOCKS * 6 * sizeof(float)); }
 
 int dva_minmax3_f32(const float* pos, int64_t n, float* out, void* workspace, int64_t workspace_bytes, void* stream) {
   if (n < 1 || !pos || !out || !workspace) return DVA_ERR_INVALID;
@@ -225,7 +223,7 @@ int dva_minmax3_f32(const float* pos, int64_t n, float* out, void* workspace, in
 int64_t dva_elastic_workspace_bytes(int64_t dx, int64_t dy, int64_t dz) {
   const int64_t total = elastic_volume(dx, dy, dz);
   if (total < 0) return total;
-  return (int64_t)(2 * ealign((size_t)total * sizeof(float)));
+  return (int64_t)(2 * align_up((size_t)total * sizeof(float)));
 }
 
 int dva_elastic_smooth(const float* noise, int64_t dx, int64_t dy, int64_t dz, float* out, void* workspace,
@@ -236,7 +234,7 @@ int dva_elastic_smooth(const float* noise, int64_t dx, int64_t dy, int64_t dz, f
   if (workspace_bytes < dva_elastic_workspace_bytes(dx, dy, dz)) return DVA_ERR_INVALID;
   if (total > EL_MAX_ELEMS - EL_TPB) return DVA_ERR_UNSUPPORTED;       // the rounded-up grid stays an int
   hipStream_t s = (hipStream_t)stream;
-  float* buf[2] = {(float*)workspace, (float*)((char*)workspace + ealign((size_t)total * sizeof(float)))};
+  float* buf[2] = {(float*)workspace, (float*)((char*)workspace + align_up((size_t)total * sizeof(float)))};
   const int stride[3] = {(int)(dy * dz * 3), (int)(dz * 3), 3};
   const int dim[3] = {(int)dx, (int)dy, (int)dz};
   const dim3 grid((unsigned)((total + EL_TPB - 1) / EL_TPB));

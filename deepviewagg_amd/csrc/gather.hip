@@ -570,14 +570,6 @@ __global__ __launch_bounds__(256) void gather_segment_max_plan_bwd_kernel(
   }
 }
 
-static inline int grid_for(int64_t total) {
-  int64_t b = (total + 255) / 256;
-  const int64_t cap = 256 * 32;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 }  // namespace dva
 
 using namespace dva;
@@ -590,7 +582,7 @@ int dva_pack_gather_index(const int64_t* images, const int64_t* atom_ptr, const 
   if (n_views < 0 || n_atoms < 0 || !(ratio >= 1.0)) return DVA_ERR_INVALID;
   if (n_views == 0 || n_atoms == 0) return DVA_OK;
   if (!images || !atom_ptr || !pixels || !packed_idx) return DVA_ERR_INVALID;
-  const int grid = grid_for(n_views);
+  const int grid = capped_grid(n_views, 256, 256 * 32);
   hipStream_t s = (hipStream_t)stream;
   PackedIdx* out = (PackedIdx*)packed_idx;
   switch (pix_bytes) {
@@ -620,7 +612,7 @@ int dva_mapping_row_index(const int64_t* images, const int64_t* atom_ptr, const 
   if ((int64_t)B * H * W > 0x7fffffffLL || H > 32767 || W > 32767) return DVA_ERR_UNSUPPORTED;
   if (n_views == 0 || n_atoms == 0) return DVA_OK;
   if (!images || !atom_ptr || !pixels || !row_idx) return DVA_ERR_INVALID;
-  const int grid = grid_for(n_views);
+  const int grid = capped_grid(n_views, 256, 256 * 32);
   hipStream_t s = (hipStream_t)stream;
   switch (pix_bytes) {
     case 2:
@@ -648,7 +640,7 @@ int dva_gather_row_index(const void* packed_idx, int64_t n_atoms, int32_t B, int
   if ((int64_t)B * H * W + row_offset > 0x7fffffffLL) return DVA_ERR_UNSUPPORTED;
   if (n_atoms == 0) return DVA_OK;
   if (!packed_idx || !row_idx) return DVA_ERR_INVALID;
-  hipLaunchKernelGGL(row_index_kernel, dim3(grid_for(n_atoms)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(row_index_kernel, dim3(capped_grid(n_atoms, 256, 256 * 32)), dim3(256), 0, (hipStream_t)stream,
                      (const PackedIdx*)packed_idx, n_atoms, H, W, row_offset, row_idx, counts);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
@@ -673,15 +665,15 @@ int dva_gather_nearest_fwd(const void* x, const void* packed_idx, void* out, int
   const bool al16 = ((uintptr_t)x % 16 == 0) && ((uintptr_t)out % 16 == 0);
   if (row_bytes % 16 == 0 && al16) {
     const int u = (int)(row_bytes / 16);
-    hipLaunchKernelGGL((gather_nearest_fwd_kernel<uint4>), dim3(grid_for(n_atoms * u)), dim3(256), 0,
+    hipLaunchKernelGGL((gather_nearest_fwd_kernel<uint4>), dim3(capped_grid(n_atoms * u, 256, 256 * 32)), dim3(256), 0,
                        s, (const uint4*)x, idx, (uint4*)out, n_atoms, H, W, u);
   } else if (row_bytes % 4 == 0) {
     const int u = (int)(row_bytes / 4);
-    hipLaunchKernelGGL((gather_nearest_fwd_kernel<uint32_t>), dim3(grid_for(n_atoms * u)), dim3(256),
+    hipLaunchKernelGGL((gather_nearest_fwd_kernel<uint32_t>), dim3(capped_grid(n_atoms * u, 256, 256 * 32)), dim3(256),
                        0, s, (const uint32_t*)x, idx, (uint32_t*)out, n_atoms, H, W, u);
   } else {
     const int u = (int)(row_bytes / 2);
-    hipLaunchKernelGGL((gather_nearest_fwd_kernel<uint16_t>), dim3(grid_for(n_atoms * u)), dim3(256),
+    hipLaunchKernelGGL((gather_nearest_fwd_kernel<uint16_t>), dim3(capped_grid(n_atoms * u, 256, 256 * 32)), dim3(256),
                        0, s, (const uint16_t*)x, idx, (uint16_t*)out, n_atoms, H, W, u);
   }
   DVA_CHECK_LAUNCH();
@@ -697,7 +689,7 @@ int dva_gather_nearest_bwd(const void* grad_out, const void* packed_idx, float* 
   if (!grad_out || !packed_idx || !grad_x) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   const PackedIdx* idx = (const PackedIdx*)packed_idx;
-  const int grid = grid_for(n_atoms * (int64_t)C);
+  const int grid = capped_grid(n_atoms * (int64_t)C, 256, 256 * 32);
   if (dtype == DVA_F32)
     hipLaunchKernelGGL((gather_nearest_bwd_kernel<float>), dim3(grid), dim3(256), 0, s,
                        (const float*)grad_out, idx, grad_x, n_atoms, H, W, C);
@@ -725,7 +717,7 @@ int dva_gather_bilinear_fwd(const void* x, const void* packed_idx, const float* 
                       ((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0;
   if (vec_ok) {
     const int slots = 64 / lpr;
-    const int gridv = grid_for(((n_atoms + slots - 1) / slots) * 64);
+    const int gridv = capped_grid(((n_atoms + slots - 1) / slots) * 64, 256, 256 * 32);
     if (dtype == DVA_F32)
       hipLaunchKernelGGL((gather_bilinear_fwd_vec_kernel<float>), dim3(gridv), dim3(256), 0, s, (const float*)x, idx,
                          coords, (float*)out, n_atoms, H, W, C, lpr);
@@ -738,7 +730,7 @@ int dva_gather_bilinear_fwd(const void* x, const void* packed_idx, const float* 
     DVA_CHECK_LAUNCH();
     return DVA_OK;
   }
-  const int grid = grid_for(n_atoms * (int64_t)C);
+  const int grid = capped_grid(n_atoms * (int64_t)C, 256, 256 * 32);
   if (dtype == DVA_F32)
     hipLaunchKernelGGL((gather_bilinear_fwd_kernel<float>), dim3(grid), dim3(256), 0, s,
                        (const float*)x, idx, coords, (float*)out, n_atoms, H, W, C);
@@ -761,7 +753,7 @@ int dva_gather_bilinear_bwd(const void* grad_out, const void* packed_idx, const 
   if (!grad_out || !packed_idx || !coords || !grad_x) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   const PackedIdx* idx = (const PackedIdx*)packed_idx;
-  const int grid = grid_for(n_atoms * (int64_t)C);
+  const int grid = capped_grid(n_atoms * (int64_t)C, 256, 256 * 32);
   if (dtype == DVA_F32)
     hipLaunchKernelGGL((gather_bilinear_bwd_kernel<float>), dim3(grid), dim3(256), 0, s,
                        (const float*)grad_out, idx, coords, grad_x, n_atoms, H, W, C);
@@ -787,7 +779,7 @@ int dva_gather_bilinear_taps_anchor(const void* packed_idx, const float* coords,
   if ((int64_t)B * (H + 1) * (W + 1) >= 0x7fffffffLL || n_atoms > 0x1fffffffLL) return DVA_ERR_UNSUPPORTED;
   if (n_atoms == 0) return DVA_OK;
   if (!packed_idx || !coords || !rows || !weights) return DVA_ERR_INVALID;
-  hipLaunchKernelGGL(bilinear_taps_kernel, dim3(grid_for(n_atoms)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(bilinear_taps_kernel, dim3(capped_grid(n_atoms, 256, 256 * 32)), dim3(256), 0, (hipStream_t)stream,
                      (const PackedIdx*)packed_idx, coords, n_atoms, H, W, rows, weights, anchors,
                      (int32_t)((int64_t)B * (H + 1) * (W + 1)));
   DVA_CHECK_LAUNCH();
@@ -822,8 +814,8 @@ int dva_bilinear_taps_cat(int32_t n_settings, const void* const* tap_rows, const
   if (!rows_out || !weights_out || !anchors_out) return DVA_ERR_INVALID;
   a.n = n_settings;
   a.dummy = (int32_t)an;
-  hipLaunchKernelGGL(taps_cat_kernel, dim3(grid_for(n_views_total)), dim3(256), 0, (hipStream_t)stream, a, order,
-                     n_views_total, (int4*)rows_out, (float4*)weights_out, anchors_out);
+  hipLaunchKernelGGL(taps_cat_kernel, dim3(capped_grid(n_views_total, 256, 256 * 32)), dim3(256), 0,
+                     (hipStream_t)stream, a, order, n_views_total, (int4*)rows_out, (float4*)weights_out, anchors_out);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -832,8 +824,8 @@ int dva_anchor_combine(const float* S, float* grad_rows, int32_t B, int32_t H, i
   if (B < 0 || H <= 0 || W <= 0 || C <= 0 || (C % 4)) return DVA_ERR_INVALID;
   if (B == 0) return DVA_OK;
   if (!S || !grad_rows) return DVA_ERR_INVALID;
-  hipLaunchKernelGGL(anchor_combine_kernel, dim3(grid_for((int64_t)B * H * W * (C / 4))), dim3(256), 0,
-                     (hipStream_t)stream, S, grad_rows, (int)B, (int)H, (int)W, (int)C);
+  hipLaunchKernelGGL(anchor_combine_kernel, dim3(capped_grid((int64_t)B * H * W * (C / 4), 256, 256 * 32)), dim3(256),
+                     0, (hipStream_t)stream, S, grad_rows, (int)B, (int)H, (int)W, (int)C);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -848,13 +840,13 @@ int dva_anchor_fixup(const void* grad, const int32_t* rows, const float* weights
   const int32_t dummy = (int32_t)((int64_t)B * (H + 1) * (W + 1));
   hipStream_t s = (hipStream_t)stream;
   if (dtype == DVA_F32)
-    hipLaunchKernelGGL((anchor_fixup_kernel<float>), dim3(grid_for(n_atoms)), dim3(256), 0, s, (const float*)grad, rows,
-                       weights, anchors, dummy, grad_rows, n_atoms, (int)C, (const float*)nullptr, (const float*)nullptr,
-                       (const float*)nullptr);
+    hipLaunchKernelGGL((anchor_fixup_kernel<float>), dim3(capped_grid(n_atoms, 256, 256 * 32)), dim3(256), 0, s,
+                       (const float*)grad, rows, weights, anchors, dummy, grad_rows, n_atoms, (int)C,
+                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
   else
-    hipLaunchKernelGGL((anchor_fixup_kernel<bf16_t>), dim3(grid_for(n_atoms)), dim3(256), 0, s, (const bf16_t*)grad,
-                       rows, weights, anchors, dummy, grad_rows, n_atoms, (int)C, (const bf16_t*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr);
+    hipLaunchKernelGGL((anchor_fixup_kernel<bf16_t>), dim3(capped_grid(n_atoms, 256, 256 * 32)), dim3(256), 0, s,
+                       (const bf16_t*)grad, rows, weights, anchors, dummy, grad_rows, n_atoms, (int)C,
+                       (const bf16_t*)nullptr, (const float*)nullptr, (const float*)nullptr);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -866,9 +858,9 @@ int dva_anchor_fixup_bn(const void* dy_a, const void* z_a, const float* bn_a, co
   if (n_atoms == 0) return DVA_OK;
   if (!dy_a || !z_a || !bn_a || !sm_a || !rows || !weights || !anchors || !grad_rows) return DVA_ERR_INVALID;
   const int32_t dummy = (int32_t)((int64_t)B * (H + 1) * (W + 1));
-  hipLaunchKernelGGL((anchor_fixup_kernel<bf16_t>), dim3(grid_for(n_atoms)), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)dy_a, rows, weights, anchors, dummy, grad_rows, n_atoms, (int)C, (const bf16_t*)z_a,
-                     bn_a, sm_a);
+  hipLaunchKernelGGL((anchor_fixup_kernel<bf16_t>), dim3(capped_grid(n_atoms, 256, 256 * 32)), dim3(256), 0,
+                     (hipStream_t)stream, (const bf16_t*)dy_a, rows, weights, anchors, dummy, grad_rows, n_atoms,
+                     (int)C, (const bf16_t*)z_a, bn_a, sm_a);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -883,14 +875,14 @@ int dva_gather_segment_max_fwd(const void* rows, const int32_t* row_idx, const i
   const int64_t total = n_views * (C / vec);
   hipStream_t s = (hipStream_t)stream;
   if (dtype == DVA_F32)
-    hipLaunchKernelGGL((gather_segment_max_fwd_kernel<float>), dim3(grid_for(total)), dim3(256), 0, s, (const float*)rows,
-                       row_idx, atom_ptr, (float*)out, (uint16_t*)arg, n_views, (int)C);
+    hipLaunchKernelGGL((gather_segment_max_fwd_kernel<float>), dim3(capped_grid(total, 256, 256 * 32)), dim3(256), 0, s,
+                       (const float*)rows, row_idx, atom_ptr, (float*)out, (uint16_t*)arg, n_views, (int)C);
   else if (dtype == DVA_F16)
-    hipLaunchKernelGGL((gather_segment_max_fwd_kernel<f16_t>), dim3(grid_for(total)), dim3(256), 0, s, (const f16_t*)rows,
-                       row_idx, atom_ptr, (f16_t*)out, (uint16_t*)arg, n_views, (int)C);
+    hipLaunchKernelGGL((gather_segment_max_fwd_kernel<f16_t>), dim3(capped_grid(total, 256, 256 * 32)), dim3(256), 0, s,
+                       (const f16_t*)rows, row_idx, atom_ptr, (f16_t*)out, (uint16_t*)arg, n_views, (int)C);
   else
-    hipLaunchKernelGGL((gather_segment_max_fwd_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, s, (const bf16_t*)rows,
-                       row_idx, atom_ptr, (bf16_t*)out, (uint16_t*)arg, n_views, (int)C);
+    hipLaunchKernelGGL((gather_segment_max_fwd_kernel<bf16_t>), dim3(capped_grid(total, 256, 256 * 32)), dim3(256), 0,
+                       s, (const bf16_t*)rows, row_idx, atom_ptr, (bf16_t*)out, (uint16_t*)arg, n_views, (int)C);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -933,14 +925,14 @@ int dva_gather_segment_max_bwd(const void* grad_out, const void* arg, const int3
   if (!grad_out || !arg || !row_idx) return DVA_ERR_INVALID;
   const int64_t total = n_views * (C / vec);
   if (dtype == DVA_F32)
-    hipLaunchKernelGGL((gather_segment_max_bwd_kernel<float>), dim3(grid_for(total)), dim3(256), 0, s, (const float*)grad_out,
-                       (const uint16_t*)arg, row_idx, atom_ptr, grad_rows, n_views, (int)C);
+    hipLaunchKernelGGL((gather_segment_max_bwd_kernel<float>), dim3(capped_grid(total, 256, 256 * 32)), dim3(256), 0, s,
+                       (const float*)grad_out, (const uint16_t*)arg, row_idx, atom_ptr, grad_rows, n_views, (int)C);
   else if (dtype == DVA_F16)
-    hipLaunchKernelGGL((gather_segment_max_bwd_kernel<f16_t>), dim3(grid_for(total)), dim3(256), 0, s, (const f16_t*)grad_out,
-                       (const uint16_t*)arg, row_idx, atom_ptr, grad_rows, n_views, (int)C);
+    hipLaunchKernelGGL((gather_segment_max_bwd_kernel<f16_t>), dim3(capped_grid(total, 256, 256 * 32)), dim3(256), 0, s,
+                       (const f16_t*)grad_out, (const uint16_t*)arg, row_idx, atom_ptr, grad_rows, n_views, (int)C);
   else
-    hipLaunchKernelGGL((gather_segment_max_bwd_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, s, (const bf16_t*)grad_out,
-                       (const uint16_t*)arg, row_idx, atom_ptr, grad_rows, n_views, (int)C);
+    hipLaunchKernelGGL((gather_segment_max_bwd_kernel<bf16_t>), dim3(capped_grid(total, 256, 256 * 32)), dim3(256), 0,
+                       s, (const bf16_t*)grad_out, (const uint16_t*)arg, row_idx, atom_ptr, grad_rows, n_views, (int)C);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }

@@ -36,14 +36,6 @@ constexpr int GRID_STATS = 9;               // min x y z b, max x y z b, flags
 constexpr int64_t GRID_MAX_N = 0x7fffffffLL; // point indices ride in 32 bits of the packed maxima
 constexpr int GRID_UNROLL = 16;
 
-static inline size_t galign(size_t x) { return (x + 255) & ~(size_t)255; }
-static inline int ggrid(int64_t n) {
-  int64_t b = (n + GRID_TPB - 1) / GRID_TPB;
-  if (b > 8192) b = 8192;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // quantise
 // ---------------------------------------------------------------------------------------------------------------
@@ -250,10 +242,10 @@ __global__ __launch_bounds__(GRID_TPB) void grid_mean_kernel(const T* __restrict
 template <typename T>
 static int launch_mean(const void* src, int64_t n, int C, const int64_t* order, const int64_t* offsets, int64_t m,
                        void* out, void* ws, hipStream_t s) {
-  hipLaunchKernelGGL(grid_permute_kernel<T>, dim3(ggrid(n * (int64_t)C)), dim3(GRID_TPB), 0, s, (const T*)src, order,
-                     n, C, (T*)ws);
-  hipLaunchKernelGGL(grid_mean_kernel<T>, dim3(ggrid(m * (int64_t)C)), dim3(GRID_TPB), 0, s, (const T*)ws, offsets,
-                     m, C, (T*)out);
+  hipLaunchKernelGGL(grid_permute_kernel<T>, dim3(capped_grid(n * (int64_t)C, GRID_TPB, 8192)), dim3(GRID_TPB), 0, s,
+                     (const T*)src, order, n, C, (T*)ws);
+  hipLaunchKernelGGL(grid_mean_kernel<T>, dim3(capped_grid(m * (int64_t)C, GRID_TPB, 8192)), dim3(GRID_TPB), 0, s,
+                     (const T*)ws, offsets, m, C, (T*)out);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -303,10 +295,14 @@ __global__ __launch_bounds__(GRID_TPB) void grid_majority_out_kernel(const uint6
 // workspace layouts
 // ---------------------------------------------------------------------------------------------------------------
 struct GridLayout {
-  size_t a, b, c, d, runs, temp, temp_bytes, total;
+  uint64_t *a, *b, *c;
+  uint32_t* d;
+  int64_t* runs;
+  char* temp;
+  size_t temp_bytes, total;
 };
 
-static int grid_layout(int64_t n, GridLayout* L) {
+static int grid_layout(void* ws, int64_t n, GridLayout* L) {
   size_t sort_tmp = 0, keys_tmp = 0, scan_tmp = 0, rle_tmp = 0;
   uint64_t* k = nullptr;
   int64_t* v = nullptr;
@@ -325,23 +321,21 @@ static int grid_layout(int64_t n, GridLayout* L) {
   if (keys_tmp > t) t = keys_tmp;
   if (scan_tmp > t) t = scan_tmp;
   if (rle_tmp > t) t = rle_tmp;
-  const size_t row8 = galign((size_t)n * 8);
-  size_t off = 0;
-  L->a = off;    off += row8;                          // keys in / head flags / representative maxima / uniq
-  L->b = off;    off += row8;                          // sorted keys
-  L->c = off;    off += row8;                          // voxel ids (+1) / majority maxima
-  L->d = off;    off += galign((size_t)n * 4);         // run counts
-  L->runs = off; off += galign(GRID_QBLOCKS * GRID_STATS * 8);   // run count / quantise partials
-  L->temp = off;
+  Carver w(ws);
+  L->a = w.take<uint64_t>((size_t)n);                      // keys in / head flags / representative maxima / uniq
+  L->b = w.take<uint64_t>((size_t)n);                      // sorted keys
+  L->c = w.take<uint64_t>((size_t)n);                      // voxel ids (+1) / majority maxima
+  L->d = w.take<uint32_t>((size_t)n);                      // run counts
+  L->runs = w.take<int64_t>(GRID_QBLOCKS * GRID_STATS);    // run count / quantise partials
   L->temp_bytes = t;
-  off += galign(t);
-  L->total = off;
+  L->temp = w.take<char>(t);
+  L->total = w.used();
   return DVA_OK;
 }
 
 static int grid_check(int64_t n, void* ws, int64_t wsb, GridLayout* L) {
   if (!ws) return DVA_ERR_INVALID;
-  const int rc = grid_layout(n, L);
+  const int rc = grid_layout(ws, n, L);
   if (rc) return rc;
   return (int64_t)L->total > wsb ? DVA_ERR_INVALID : DVA_OK;
 }
@@ -355,10 +349,10 @@ extern "C" {
 int64_t dva_grid_workspace_bytes(int64_t n, int64_t row_bytes) {
   if (n < 0 || row_bytes < 0) return DVA_ERR_INVALID;
   if (n > GRID_MAX_N) return DVA_ERR_UNSUPPORTED;
-  if (row_bytes > 0) return (int64_t)galign((size_t)n * (size_t)row_bytes);
+  if (row_bytes > 0) return (int64_t)align_up((size_t)n * (size_t)row_bytes);
   if (n == 0) return 256;
   GridLayout L;
-  const int rc = grid_layout(n, &L);
+  const int rc = grid_layout(nullptr, n, &L);
   return rc ? rc : (int64_t)L.total;
 }
 
@@ -371,7 +365,7 @@ int dva_grid_quantize(const void* pos, int32_t dtype, int64_t n, double size, co
   const int rc = grid_check(n, workspace, workspace_bytes, &L);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  int64_t* partials = (int64_t*)((char*)workspace + L.runs);
+  int64_t* partials = L.runs;
   int nb = (int)((n + GRID_TPB - 1) / GRID_TPB);
   if (nb > GRID_QBLOCKS) nb = GRID_QBLOCKS;
   if (dtype == DVA_GRID_F32)
@@ -396,21 +390,20 @@ int dva_grid_cluster(const int32_t* coords, const int64_t* batch, const int64_t*
   const int rc = grid_check(n, workspace, workspace_bytes, &L);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  uint64_t* keys = (uint64_t*)(ws + L.a);
-  uint64_t* sorted = (uint64_t*)(ws + L.b);
-  int64_t* vid1 = (int64_t*)(ws + L.c);
-  const int g = ggrid(n);
+  uint64_t* keys = L.a;
+  uint64_t* sorted = L.b;
+  int64_t* vid1 = (int64_t*)L.c;
+  const int g = capped_grid(n, GRID_TPB, 8192);
   hipLaunchKernelGGL(grid_key_kernel, dim3(g), dim3(GRID_TPB), 0, s, coords, batch, n, stats, keys);
   size_t tmp = L.temp_bytes;
   rocprim::counting_iterator<int64_t> iota(0);
-  if (rocprim::radix_sort_pairs(ws + L.temp, tmp, keys, sorted, iota, order, (size_t)n, 0, (unsigned)end_bit, s) !=
+  if (rocprim::radix_sort_pairs(L.temp, tmp, keys, sorted, iota, order, (size_t)n, 0, (unsigned)end_bit, s) !=
       hipSuccess)
     return DVA_ERR_LAUNCH;
   int64_t* head = (int64_t*)keys;   // the unsorted keys are consumed
   hipLaunchKernelGGL(grid_head_kernel, dim3(g), dim3(GRID_TPB), 0, s, sorted, n, head);
   tmp = L.temp_bytes;
-  if (rocprim::inclusive_scan(ws + L.temp, tmp, head, vid1, (size_t)n, rocprim::plus<int64_t>(), s) != hipSuccess)
+  if (rocprim::inclusive_scan(L.temp, tmp, head, vid1, (size_t)n, rocprim::plus<int64_t>(), s) != hipSuccess)
     return DVA_ERR_LAUNCH;
   uint64_t* best = keys;            // the head flags are consumed
   if (hipMemsetAsync(best, 0, (size_t)n * 8, s) != hipSuccess) return DVA_ERR_LAUNCH;
@@ -432,7 +425,7 @@ int dva_grid_mean(const void* src, int32_t dtype, int64_t n, int32_t C, const in
     case DVA_GRID_F64: case DVA_GRID_I64: esz = 8; break;
     default: return DVA_ERR_INVALID;
   }
-  if ((int64_t)galign((size_t)n * C * esz) > workspace_bytes) return DVA_ERR_INVALID;
+  if ((int64_t)align_up((size_t)n * C * esz) > workspace_bytes) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   switch (dtype) {
     case DVA_GRID_F32: return launch_mean<float>(src, n, C, order, offsets, n_voxels, out, workspace, s);
@@ -452,27 +445,26 @@ int dva_grid_majority(const int64_t* labels, int64_t n, const int64_t* cluster, 
   const int rc = grid_check(n, workspace, workspace_bytes, &L);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  uint64_t* keys = (uint64_t*)(ws + L.a);
-  uint64_t* sorted = (uint64_t*)(ws + L.b);
-  uint64_t* best = (uint64_t*)(ws + L.c);
-  uint32_t* counts = (uint32_t*)(ws + L.d);
-  uint32_t* n_runs = (uint32_t*)(ws + L.runs);
-  const int g = ggrid(n);
+  uint64_t* keys = L.a;
+  uint64_t* sorted = L.b;
+  uint64_t* best = L.c;
+  uint32_t* counts = L.d;
+  uint32_t* n_runs = (uint32_t*)L.runs;
+  const int g = capped_grid(n, GRID_TPB, 8192);
   hipLaunchKernelGGL(grid_label_key_kernel, dim3(g), dim3(GRID_TPB), 0, s, labels, cluster, n, label_min, n_labels,
                      keys);
   size_t tmp = L.temp_bytes;
-  if (rocprim::radix_sort_keys(ws + L.temp, tmp, keys, sorted, (size_t)n, 0, (unsigned)end_bit, s) != hipSuccess)
+  if (rocprim::radix_sort_keys(L.temp, tmp, keys, sorted, (size_t)n, 0, (unsigned)end_bit, s) != hipSuccess)
     return DVA_ERR_LAUNCH;
   uint64_t* uniq = keys;            // the unsorted keys are consumed
   tmp = L.temp_bytes;
-  if (rocprim::run_length_encode(ws + L.temp, tmp, sorted, (unsigned int)n, uniq, counts, n_runs, s) != hipSuccess)
+  if (rocprim::run_length_encode(L.temp, tmp, sorted, (unsigned int)n, uniq, counts, n_runs, s) != hipSuccess)
     return DVA_ERR_LAUNCH;
   if (hipMemsetAsync(best, 0, (size_t)n_voxels * 8, s) != hipSuccess) return DVA_ERR_LAUNCH;
   hipLaunchKernelGGL(grid_runs_kernel, dim3(g), dim3(GRID_TPB), 0, s, uniq, counts, n_runs, n, n_labels, n_voxels,
                      best);
-  hipLaunchKernelGGL(grid_majority_out_kernel, dim3(ggrid(n_voxels)), dim3(GRID_TPB), 0, s, best, n_voxels,
-                     label_min, out);
+  hipLaunchKernelGGL(grid_majority_out_kernel, dim3(capped_grid(n_voxels, GRID_TPB, 8192)), dim3(GRID_TPB), 0, s, best,
+                     n_voxels, label_min, out);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }

@@ -275,7 +275,7 @@ __global__ __launch_bounds__(IT_TPB) void image_normalize_f32_kernel(const float
   for (int64_t i = i0; i < i1; ++i) out[plane * hw + i] = __fdiv_rn(x[plane * hw + i] - mu, sd);
 }
 
-static inline int64_t it_sums_bytes(int64_t B) { return ((B > 0 ? B : 1) * 8 + 255) & ~(int64_t)255; }
+static inline int64_t it_sums_bytes(int64_t B) { return (int64_t)align_up((size_t)(B > 0 ? B : 1) * 8); }
 
 // mean / std (host, C floats each, both or neither) into the kernel argument
 static int it_norm(const float* mean, const float* std, int64_t C, ItNorm* nrm) {

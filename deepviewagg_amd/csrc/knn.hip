@@ -215,15 +215,17 @@ __global__ __launch_bounds__(256) void occlusion_kernel(const int32_t* __restric
   }
 }
 
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 struct KnnLayout {
-  size_t keys, ids, keys_sorted, perm, pts, tkeys, tvals, qkeys, qids, qkeys_sorted, qperm, qpts, temp, temp_bytes,
-      total;
+  uint64_t *keys, *keys_sorted, *tkeys, *qkeys, *qkeys_sorted;
+  int32_t *ids, *perm, *tvals, *qids, *qperm;
+  float4 *pts, *qpts;
+  char* temp;
+  size_t temp_bytes, total;
   uint64_t cap;
 };
 // n search points; nq > 0: a separate query cloud (dva_knn_query) with its own sort; the two sorts share the
 // temp storage
-static int knn_layout(int64_t n, KnnLayout* L, int64_t nq = 0) {
+static int knn_layout(void* ws, int64_t n, KnnLayout* L, int64_t nq = 0) {
   size_t tmp = 0, qtmp = 0;
   uint64_t* nk = nullptr;
   int32_t* nv = nullptr;
@@ -237,28 +239,23 @@ static int knn_layout(int64_t n, KnnLayout* L, int64_t nq = 0) {
   uint64_t cap = 64;
   while (cap < 2 * (uint64_t)n) cap <<= 1;
   L->cap = cap;
-  size_t off = 0;
-  L->keys = off;        off += al256((size_t)n * 8);
-  L->ids = off;         off += al256((size_t)n * 4);
-  L->keys_sorted = off; off += al256((size_t)n * 8);
-  L->perm = off;        off += al256((size_t)n * 4);
-  L->pts = off;         off += al256((size_t)n * 16);
-  L->tkeys = off;       off += al256(cap * 8);
-  L->tvals = off;       off += al256(cap * 4);
-  L->qkeys = off;        off += al256((size_t)nq * 8);
-  L->qids = off;         off += al256((size_t)nq * 4);
-  L->qkeys_sorted = off; off += al256((size_t)nq * 8);
-  L->qperm = off;        off += al256((size_t)nq * 4);
-  L->qpts = off;         off += al256((size_t)nq * 16);
-  L->temp = off;        L->temp_bytes = tmp; off += al256(tmp);
-  L->total = off;
+  Carver c(ws);
+  L->keys = c.take<uint64_t>((size_t)n);
+  L->ids = c.take<int32_t>((size_t)n);
+  L->keys_sorted = c.take<uint64_t>((size_t)n);
+  L->perm = c.take<int32_t>((size_t)n);
+  L->pts = c.take<float4>((size_t)n);
+  L->tkeys = c.take<uint64_t>(cap);
+  L->tvals = c.take<int32_t>(cap);
+  L->qkeys = c.take<uint64_t>((size_t)nq);
+  L->qids = c.take<int32_t>((size_t)nq);
+  L->qkeys_sorted = c.take<uint64_t>((size_t)nq);
+  L->qperm = c.take<int32_t>((size_t)nq);
+  L->qpts = c.take<float4>((size_t)nq);
+  L->temp_bytes = tmp;
+  L->temp = c.take<char>(tmp);
+  L->total = c.used();
   return DVA_OK;
-}
-static inline int grid256(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b > 8192) b = 8192;
-  if (b < 1) b = 1;
-  return (int)b;
 }
 
 static void launch_knn_query(const float4* qpts, int64_t nq, const float4* pts, const uint64_t* keys_sorted,
@@ -286,7 +283,7 @@ int64_t dva_knn_workspace_bytes(int64_t n) {
   if (n > 0x3fffffffLL) return DVA_ERR_UNSUPPORTED;
   if (n == 0) return 256;
   KnnLayout L;
-  int rc = knn_layout(n, &L);
+  int rc = knn_layout(nullptr, n, &L);
   if (rc) return rc;
   return (int64_t)L.total;
 }
@@ -299,28 +296,21 @@ int dva_knn(const float* xyz, int64_t n, const float* bbox, float cell, int32_t 
   if (n == 0) return DVA_OK;
   if (!xyz || !bbox || !neighbors || !workspace) return DVA_ERR_INVALID;
   KnnLayout L;
-  int rc = knn_layout(n, &L);
+  int rc = knn_layout(workspace, n, &L);
   if (rc) return rc;
   if ((int64_t)L.total > workspace_bytes) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  uint64_t* keys = (uint64_t*)(ws + L.keys);
-  int32_t* ids = (int32_t*)(ws + L.ids);
-  uint64_t* keys_sorted = (uint64_t*)(ws + L.keys_sorted);
-  int32_t* perm = (int32_t*)(ws + L.perm);
-  float4* pts = (float4*)(ws + L.pts);
-  uint64_t* tkeys = (uint64_t*)(ws + L.tkeys);
-  int32_t* tvals = (int32_t*)(ws + L.tvals);
-  hipLaunchKernelGGL(knn_keys_kernel, dim3(grid256(n)), dim3(256), 0, s, xyz, n, bbox, 1.f / cell, keys, ids);
+  hipLaunchKernelGGL(knn_keys_kernel, dim3(capped_grid(n, 256, 8192)), dim3(256), 0, s, xyz, n, bbox, 1.f / cell,
+                     L.keys, L.ids);
   size_t tmp = L.temp_bytes;
-  if (rocprim::radix_sort_pairs(ws + L.temp, tmp, keys, keys_sorted, ids, perm, (size_t)n, 0, 3 * CELL_BITS, s) !=
+  if (rocprim::radix_sort_pairs(L.temp, tmp, L.keys, L.keys_sorted, L.ids, L.perm, (size_t)n, 0, 3 * CELL_BITS, s) !=
       hipSuccess)
     return DVA_ERR_LAUNCH;
-  if (hipMemsetAsync(tkeys, 0xff, L.cap * 8, s) != hipSuccess) return DVA_ERR_LAUNCH;
-  hipLaunchKernelGGL(knn_cells_kernel, dim3(grid256(n)), dim3(256), 0, s, xyz, keys_sorted, perm, n, pts, tkeys,
-                     tvals, (uint32_t)(L.cap - 1));
-  launch_knn_query(pts, n, pts, keys_sorted, n, bbox, cell, tkeys, tvals, (uint32_t)(L.cap - 1), k, max_shell, done,
-                   neighbors, dist2, s);
+  if (hipMemsetAsync(L.tkeys, 0xff, L.cap * 8, s) != hipSuccess) return DVA_ERR_LAUNCH;
+  hipLaunchKernelGGL(knn_cells_kernel, dim3(capped_grid(n, 256, 8192)), dim3(256), 0, s, xyz, L.keys_sorted, L.perm, n,
+                     L.pts, L.tkeys, L.tvals, (uint32_t)(L.cap - 1));
+  launch_knn_query(L.pts, n, L.pts, L.keys_sorted, n, bbox, cell, L.tkeys, L.tvals, (uint32_t)(L.cap - 1), k, max_shell,
+                   done, neighbors, dist2, s);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -330,7 +320,7 @@ int64_t dva_knn_query_workspace_bytes(int64_t n_query, int64_t n_search) {
   if (n_query > 0x7fffffffLL || n_search > 0x3fffffffLL) return DVA_ERR_UNSUPPORTED;
   if (n_query == 0 || n_search == 0) return 256;
   KnnLayout L;
-  int rc = knn_layout(n_search, &L, n_query);
+  int rc = knn_layout(nullptr, n_search, &L, n_query);
   if (rc) return rc;
   return (int64_t)L.total;
 }
@@ -344,44 +334,32 @@ int dva_knn_query(const float* query_xyz, int64_t n_query, const float* search_x
   if (n_query == 0) return DVA_OK;
   if (!query_xyz || !search_xyz || !bbox || !neighbors || !workspace) return DVA_ERR_INVALID;
   KnnLayout L;
-  int rc = knn_layout(n_search, &L, n_query);
+  int rc = knn_layout(workspace, n_search, &L, n_query);
   if (rc) return rc;
   if ((int64_t)L.total > workspace_bytes) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  uint64_t* keys = (uint64_t*)(ws + L.keys);
-  int32_t* ids = (int32_t*)(ws + L.ids);
-  uint64_t* keys_sorted = (uint64_t*)(ws + L.keys_sorted);
-  int32_t* perm = (int32_t*)(ws + L.perm);
-  float4* pts = (float4*)(ws + L.pts);
-  uint64_t* tkeys = (uint64_t*)(ws + L.tkeys);
-  int32_t* tvals = (int32_t*)(ws + L.tvals);
-  uint64_t* qkeys = (uint64_t*)(ws + L.qkeys);
-  int32_t* qids = (int32_t*)(ws + L.qids);
-  uint64_t* qkeys_sorted = (uint64_t*)(ws + L.qkeys_sorted);
-  int32_t* qperm = (int32_t*)(ws + L.qperm);
-  float4* qpts = (float4*)(ws + L.qpts);
   const float inv_cell = 1.f / cell;
   // the grid of the search cloud
-  hipLaunchKernelGGL(knn_keys_kernel, dim3(grid256(n_search)), dim3(256), 0, s, search_xyz, n_search, bbox, inv_cell,
-                     keys, ids);
+  hipLaunchKernelGGL(knn_keys_kernel, dim3(capped_grid(n_search, 256, 8192)), dim3(256), 0, s, search_xyz, n_search,
+                     bbox, inv_cell, L.keys, L.ids);
   size_t tmp = L.temp_bytes;
-  if (rocprim::radix_sort_pairs(ws + L.temp, tmp, keys, keys_sorted, ids, perm, (size_t)n_search, 0, 3 * CELL_BITS,
+  if (rocprim::radix_sort_pairs(L.temp, tmp, L.keys, L.keys_sorted, L.ids, L.perm, (size_t)n_search, 0, 3 * CELL_BITS,
                                 s) != hipSuccess)
     return DVA_ERR_LAUNCH;
-  if (hipMemsetAsync(tkeys, 0xff, L.cap * 8, s) != hipSuccess) return DVA_ERR_LAUNCH;
-  hipLaunchKernelGGL(knn_cells_kernel, dim3(grid256(n_search)), dim3(256), 0, s, search_xyz, keys_sorted, perm,
-                     n_search, pts, tkeys, tvals, (uint32_t)(L.cap - 1));
+  if (hipMemsetAsync(L.tkeys, 0xff, L.cap * 8, s) != hipSuccess) return DVA_ERR_LAUNCH;
+  hipLaunchKernelGGL(knn_cells_kernel, dim3(capped_grid(n_search, 256, 8192)), dim3(256), 0, s, search_xyz,
+                     L.keys_sorted, L.perm, n_search, L.pts, L.tkeys, L.tvals, (uint32_t)(L.cap - 1));
   // the queries in the cell order of the same grid, so that the lanes of a wavefront walk the same cells
-  hipLaunchKernelGGL(knn_keys_kernel, dim3(grid256(n_query)), dim3(256), 0, s, query_xyz, n_query, bbox, inv_cell,
-                     qkeys, qids);
+  hipLaunchKernelGGL(knn_keys_kernel, dim3(capped_grid(n_query, 256, 8192)), dim3(256), 0, s, query_xyz, n_query, bbox,
+                     inv_cell, L.qkeys, L.qids);
   tmp = L.temp_bytes;
-  if (rocprim::radix_sort_pairs(ws + L.temp, tmp, qkeys, qkeys_sorted, qids, qperm, (size_t)n_query, 0, 3 * CELL_BITS,
-                                s) != hipSuccess)
+  if (rocprim::radix_sort_pairs(L.temp, tmp, L.qkeys, L.qkeys_sorted, L.qids, L.qperm, (size_t)n_query, 0,
+                                3 * CELL_BITS, s) != hipSuccess)
     return DVA_ERR_LAUNCH;
-  hipLaunchKernelGGL(knn_query_points_kernel, dim3(grid256(n_query)), dim3(256), 0, s, query_xyz, qperm, n_query, qpts);
-  launch_knn_query(qpts, n_query, pts, keys_sorted, n_search, bbox, cell, tkeys, tvals, (uint32_t)(L.cap - 1), k,
-                   max_shell, done, neighbors, dist2, s);
+  hipLaunchKernelGGL(knn_query_points_kernel, dim3(capped_grid(n_query, 256, 8192)), dim3(256), 0, s, query_xyz,
+                     L.qperm, n_query, L.qpts);
+  launch_knn_query(L.qpts, n_query, L.pts, L.keys_sorted, n_search, bbox, cell, L.tkeys, L.tvals, (uint32_t)(L.cap - 1),
+                   k, max_shell, done, neighbors, dist2, s);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -395,10 +373,10 @@ int dva_view_occlusion(const int32_t* view_point, const int64_t* images, int64_t
   const int n_words = (n_images + 63) / 64;
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(bits, 0, (size_t)n_points * n_words * 8, s) != hipSuccess) return DVA_ERR_LAUNCH;
-  hipLaunchKernelGGL(view_bits_kernel, dim3(grid256(n_views)), dim3(256), 0, s, view_point, images, n_views,
-                     n_words, (unsigned long long*)bits);
-  hipLaunchKernelGGL(occlusion_kernel, dim3(grid256(n_views)), dim3(256), 0, s, view_point, images, n_views,
-                     neighbors, k, (const unsigned long long*)bits, n_words, k_list, n_k, out);
+  hipLaunchKernelGGL(view_bits_kernel, dim3(capped_grid(n_views, 256, 8192)), dim3(256), 0, s, view_point, images,
+                     n_views, n_words, (unsigned long long*)bits);
+  hipLaunchKernelGGL(occlusion_kernel, dim3(capped_grid(n_views, 256, 8192)), dim3(256), 0, s, view_point, images,
+                     n_views, neighbors, k, (const unsigned long long*)bits, n_words, k_list, n_k, out);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }

@@ -28,13 +28,14 @@ __global__ __launch_bounds__(256) void head_flags_kernel(const int64_t* __restri
     flags[i] = (i == 0 || sorted[i] != sorted[i - 1]) ? 1 : 0;
 }
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct LexLayout {
-  size_t off_iota, off_keys, off_vals, off_flags, off_temp, temp_bytes, total;
+  int64_t *iota, *keys, *vals;
+  uint8_t* flags;
+  char* temp;
+  size_t temp_bytes, total;
 };
 
-static int lex_layout(int64_t n, LexLayout* L) {
+static int lex_layout(void* ws, int64_t n, LexLayout* L) {
   size_t sort_tmp = 0, sel_tmp = 0;
   int64_t* nul = nullptr;
   uint8_t* nulf = nullptr;
@@ -43,15 +44,14 @@ static int lex_layout(int64_t n, LexLayout* L) {
     return DVA_ERR_LAUNCH;
   if (rocprim::select(nullptr, sel_tmp, nul, nulf, nul, nul, (size_t)n, (hipStream_t)0) != hipSuccess)
     return DVA_ERR_LAUNCH;
-  size_t off = 0;
-  L->off_iota = off;  off += align256((size_t)n * 8);
-  L->off_keys = off;  off += align256((size_t)n * 8);
-  L->off_vals = off;  off += align256((size_t)n * 8);
-  L->off_flags = off; off += align256((size_t)n);
-  L->off_temp = off;
+  Carver c(ws);
+  L->iota = c.take<int64_t>((size_t)n);
+  L->keys = c.take<int64_t>((size_t)n);
+  L->vals = c.take<int64_t>((size_t)n);
+  L->flags = c.take<uint8_t>((size_t)n);
   L->temp_bytes = sort_tmp > sel_tmp ? sort_tmp : sel_tmp;
-  off += align256(L->temp_bytes);
-  L->total = off;
+  L->temp = c.take<char>(L->temp_bytes);
+  L->total = c.used();
   return DVA_OK;
 }
 
@@ -83,7 +83,9 @@ __global__ __launch_bounds__(256) void ptr_diff_kernel(const int32_t* __restrict
 }
 
 struct PlanLayout {
-  size_t off_iota, off_keys, off_temp, temp_bytes, total;
+  uint32_t* keys;
+  char* temp;
+  size_t temp_bytes, total;
 };
 
 static int key_bits(int64_t n_rows) {
@@ -132,27 +134,18 @@ static hipError_t plan_sort(void* temp, size_t& tmp, const uint32_t* kin, uint32
   return rocprim::radix_sort_pairs<PlanSortLib>(temp, tmp, kin, kout, vin, vout, n, 0, bits, s);
 }
 
-static int plan_layout(int64_t n, int bits, PlanLayout* L) {
+static int plan_layout(void* ws, int64_t n, int bits, PlanLayout* L) {
   size_t tmp = 0;
   uint32_t* nk = nullptr;
   int32_t* nv = nullptr;
   if (plan_sort(nullptr, tmp, nk, nk, nv, (size_t)n, bits, (hipStream_t)0) != hipSuccess)
     return DVA_ERR_LAUNCH;
-  size_t off = 0;
-  L->off_iota = off;                                       // (no view-number array: a counting iterator feeds the sort)
-  L->off_keys = off;  off += align256((size_t)n * 4);
-  L->off_temp = off;
+  Carver c(ws);
+  L->keys = c.take<uint32_t>((size_t)n);  // (no view-number array: a counting iterator feeds the sort)
   L->temp_bytes = tmp;
-  off += align256(tmp);
-  L->total = off;
+  L->temp = c.take<char>(tmp);
+  L->total = c.used();
   return DVA_OK;
-}
-
-static inline int grid_for(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b > 8192) b = 8192;
-  if (b < 1) b = 1;
-  return (int)b;
 }
 
 }  // namespace dva
@@ -165,7 +158,7 @@ int64_t dva_lex_workspace_bytes(int64_t n) {
   if (n < 0) return DVA_ERR_INVALID;
   if (n == 0) return 256;
   LexLayout L;
-  int rc = lex_layout(n, &L);
+  int rc = lex_layout(nullptr, n, &L);
   if (rc) return rc;
   return (int64_t)L.total;
 }
@@ -176,17 +169,14 @@ int dva_argsort_i64(const int64_t* keys, int64_t n, int64_t* order, int64_t* key
   if (n == 0) return DVA_OK;
   if (!keys || !order || !workspace) return DVA_ERR_INVALID;
   LexLayout L;
-  int rc = lex_layout(n, &L);
+  int rc = lex_layout(workspace, n, &L);
   if (rc) return rc;
   if ((int64_t)L.total > workspace_bytes) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  int64_t* iota = (int64_t*)(ws + L.off_iota);
-  int64_t* kout = keys_sorted ? keys_sorted : (int64_t*)(ws + L.off_keys);
-  hipLaunchKernelGGL(iota_kernel, dim3(grid_for(n)), dim3(256), 0, s, iota, n);
+  int64_t* kout = keys_sorted ? keys_sorted : L.keys;
+  hipLaunchKernelGGL(iota_kernel, dim3(capped_grid(n, 256, 8192)), dim3(256), 0, s, L.iota, n);
   size_t tmp = L.temp_bytes;
-  if (rocprim::radix_sort_pairs(ws + L.off_temp, tmp, keys, kout, iota, order, (size_t)n, 0, 64, s) !=
-      hipSuccess)
+  if (rocprim::radix_sort_pairs(L.temp, tmp, keys, kout, L.iota, order, (size_t)n, 0, 64, s) != hipSuccess)
     return DVA_ERR_LAUNCH;
   DVA_CHECK_LAUNCH();
   return DVA_OK;
@@ -202,23 +192,16 @@ int dva_argunique_i64(const int64_t* keys, int64_t n, int64_t* first, int64_t* n
   }
   if (!keys || !first || !workspace) return DVA_ERR_INVALID;
   LexLayout L;
-  int rc = lex_layout(n, &L);
+  int rc = lex_layout(workspace, n, &L);
   if (rc) return rc;
   if ((int64_t)L.total > workspace_bytes) return DVA_ERR_INVALID;
-  char* ws = (char*)workspace;
-  int64_t* iota = (int64_t*)(ws + L.off_iota);
-  int64_t* kout = (int64_t*)(ws + L.off_keys);
-  int64_t* vout = (int64_t*)(ws + L.off_vals);
-  uint8_t* flags = (uint8_t*)(ws + L.off_flags);
-  hipLaunchKernelGGL(iota_kernel, dim3(grid_for(n)), dim3(256), 0, s, iota, n);
+  hipLaunchKernelGGL(iota_kernel, dim3(capped_grid(n, 256, 8192)), dim3(256), 0, s, L.iota, n);
   size_t tmp = L.temp_bytes;
-  if (rocprim::radix_sort_pairs(ws + L.off_temp, tmp, keys, kout, iota, vout, (size_t)n, 0, 64, s) !=
-      hipSuccess)
+  if (rocprim::radix_sort_pairs(L.temp, tmp, keys, L.keys, L.iota, L.vals, (size_t)n, 0, 64, s) != hipSuccess)
     return DVA_ERR_LAUNCH;
-  hipLaunchKernelGGL(head_flags_kernel, dim3(grid_for(n)), dim3(256), 0, s, kout, flags, n);
+  hipLaunchKernelGGL(head_flags_kernel, dim3(capped_grid(n, 256, 8192)), dim3(256), 0, s, L.keys, L.flags, n);
   tmp = L.temp_bytes;
-  if (rocprim::select(ws + L.off_temp, tmp, vout, flags, first, n_unique_dev, (size_t)n, s) !=
-      hipSuccess)
+  if (rocprim::select(L.temp, tmp, L.vals, L.flags, first, n_unique_dev, (size_t)n, s) != hipSuccess)
     return DVA_ERR_LAUNCH;
   DVA_CHECK_LAUNCH();
   return DVA_OK;
@@ -229,7 +212,7 @@ int64_t dva_row_plan_workspace_bytes(int64_t n_views, int64_t n_rows) {
   if (n_views > 0x7fffffffLL || n_rows > 0x7fffffffLL) return DVA_ERR_UNSUPPORTED;
   if (n_views == 0) return 256;
   PlanLayout L;
-  int rc = plan_layout(n_views, key_bits(n_rows), &L);
+  int rc = plan_layout(nullptr, n_views, key_bits(n_rows), &L);
   if (rc) return rc;
   return (int64_t)L.total;
 }
@@ -249,19 +232,16 @@ int dva_row_plan(const int32_t* row_idx, int64_t n_views, int64_t n_rows, int32_
   if (!row_idx || !perm || !workspace) return DVA_ERR_INVALID;
   PlanLayout L;
   const int bits = key_bits(n_rows);
-  int rc = plan_layout(n_views, bits, &L);
+  int rc = plan_layout(workspace, n_views, bits, &L);
   if (rc) return rc;
   if ((int64_t)L.total > workspace_bytes) return DVA_ERR_INVALID;
-  char* ws = (char*)workspace;
-  uint32_t* kout = (uint32_t*)(ws + L.off_keys);
   size_t tmp = L.temp_bytes;
-  if (plan_sort(ws + L.off_temp, tmp, (const uint32_t*)row_idx, kout, perm, (size_t)n_views, bits, s) != hipSuccess)
+  if (plan_sort(L.temp, tmp, (const uint32_t*)row_idx, L.keys, perm, (size_t)n_views, bits, s) != hipSuccess)
     return DVA_ERR_LAUNCH;
-  hipLaunchKernelGGL(row_ptr_kernel, dim3(grid_for(n_views + 1)), dim3(256), 0, s, kout, n_views,
+  hipLaunchKernelGGL(row_ptr_kernel, dim3(capped_grid(n_views + 1, 256, 8192)), dim3(256), 0, s, L.keys, n_views,
                      n_rows, row_ptr);
   if (counts)
-    hipLaunchKernelGGL(ptr_diff_kernel, dim3(grid_for(n_rows)), dim3(256), 0, s, row_ptr, n_rows,
-                       counts);
+    hipLaunchKernelGGL(ptr_diff_kernel, dim3(capped_grid(n_rows, 256, 8192)), dim3(256), 0, s, row_ptr, n_rows, counts);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }

@@ -798,14 +798,19 @@ __global__ __launch_bounds__(256) void features_batch_kernel(
   }
 }
 
-static inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct VisLayout {
-  size_t flag, pos, dist_u, xp_u, yp_u, idx1, dist, xp, yp, splat, seen, cnt, zbuf, pixmap, pixflag,
-      pixpos, temp, temp_bytes, total;
+  int32_t *flag, *pos, *idx1, *pixmap, *pixflag, *pixpos;
+  float *dist_u, *dist;
+  double *xp_u, *yp_u, *xp, *yp;
+  int4* splat;
+  uint8_t* seen;
+  MapCounters* cnt;
+  unsigned long long* zbuf;
+  char* temp;
+  size_t temp_bytes, total;
 };
 
-static int vis_layout(const dva_camera* c, int64_t n, VisLayout* L) {
+static int vis_layout(void* ws, const dva_camera* c, int64_t n, VisLayout* L) {
   const int64_t Hc = (int64_t)c->img_h - c->crop_top - c->crop_bottom;
   if (c->img_w <= 0 || Hc <= 0) return DVA_ERR_INVALID;
   const size_t npix = (size_t)c->img_w * (size_t)Hc;
@@ -815,47 +820,48 @@ static int vis_layout(const dva_camera* c, int64_t n, VisLayout* L) {
   if (rocprim::exclusive_scan(nullptr, scan_tmp, nul, nul, 0, big, rocprim::plus<int32_t>(),
                               (hipStream_t)0) != hipSuccess)
     return DVA_ERR_LAUNCH;
-  size_t o = 0;
-  L->flag = o;    o += al((size_t)n * 4);
-  L->pos = o;     o += al((size_t)n * 4);
-  L->dist_u = o;  o += al((size_t)n * 4);
-  L->xp_u = o;    o += al((size_t)n * 8);
-  L->yp_u = o;    o += al((size_t)n * 8);
-  L->idx1 = o;    o += al((size_t)n * 4);
-  L->dist = o;    o += al((size_t)n * 4);
-  L->xp = o;      o += al((size_t)n * 8);
-  L->yp = o;      o += al((size_t)n * 8);
-  L->splat = o;   o += al((size_t)n * 16);
-  L->seen = o;    o += al((size_t)n);
-  L->cnt = o;     o += al(sizeof(MapCounters));
-  L->zbuf = o;    o += al(npix * 8);
-  L->pixmap = o;  o += al(npix * 4);
-  L->pixflag = o; o += al(npix * 4);
-  L->pixpos = o;  o += al(npix * 4);
-  L->temp = o;
+  Carver w(ws);
+  L->flag = w.take<int32_t>((size_t)n);
+  L->pos = w.take<int32_t>((size_t)n);
+  L->dist_u = w.take<float>((size_t)n);
+  L->xp_u = w.take<double>((size_t)n);
+  L->yp_u = w.take<double>((size_t)n);
+  L->idx1 = w.take<int32_t>((size_t)n);
+  L->dist = w.take<float>((size_t)n);
+  L->xp = w.take<double>((size_t)n);
+  L->yp = w.take<double>((size_t)n);
+  L->splat = w.take<int4>((size_t)n);
+  L->seen = w.take<uint8_t>((size_t)n);
+  L->cnt = w.take<MapCounters>(1);
+  L->zbuf = w.take<unsigned long long>(npix);
+  L->pixmap = w.take<int32_t>(npix);
+  L->pixflag = w.take<int32_t>(npix);
+  L->pixpos = w.take<int32_t>(npix);
   L->temp_bytes = scan_tmp;
-  o += al(scan_tmp);
-  L->total = o;
+  L->temp = w.take<char>(scan_tmp);
+  L->total = w.used();
   return DVA_OK;
 }
 
-static inline int grid_for(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b > 4096) b = 4096;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 struct VisBatchLayout {
-  size_t flag, pos, dist_u, xp_u, yp_u, idx1, simg, dist, xp, yp, splat, seen, cnt, zbuf, pixmap, pixflag, pixpos,
-      temp, temp_bytes, total;
+  int32_t *flag, *pos, *idx1, *simg, *pixmap, *pixflag, *pixpos;
+  float *dist_u, *dist;
+  double *xp_u, *yp_u, *xp, *yp;
+  int4* splat;
+  uint8_t* seen;
+  MapCounters* cnt;
+  unsigned long long* zbuf;
+  char* temp;
+  size_t temp_bytes, total;
   // tiled z-buffer: tile_count | tile_cursor | ctl are one zero-filled region
-  size_t tile_count, tile_cursor, ctl, tile_zero_bytes, tile_off, list, big_list, fb_list;
+  int32_t *tile_count, *tile_cursor, *ctl, *tile_off, *fb_list;
+  int4 *list, *big_list;
+  size_t tile_zero_bytes;
   int64_t list_cap;
   int Tx, Ty;
 };
 
-static int vis_batch_layout(const dva_camera* c, int64_t n, int64_t B, VisBatchLayout* L) {
+static int vis_batch_layout(void* ws, const dva_camera* c, int64_t n, int64_t B, VisBatchLayout* L) {
   const int64_t Hc = (int64_t)c->img_h - c->crop_top - c->crop_bottom;
   if (c->img_w <= 0 || Hc <= 0 || B < 1) return DVA_ERR_INVALID;
   const size_t npix = (size_t)c->img_w * (size_t)Hc * (size_t)B, nc = (size_t)n * (size_t)B;
@@ -865,40 +871,40 @@ static int vis_batch_layout(const dva_camera* c, int64_t n, int64_t B, VisBatchL
   if (rocprim::exclusive_scan(nullptr, scan_tmp, nul, nul, 0, big, rocprim::plus<int32_t>(), (hipStream_t)0) !=
       hipSuccess)
     return DVA_ERR_LAUNCH;
-  size_t o = 0;
-  L->flag = o;    o += al(nc * 4);
-  L->pos = o;     o += al(nc * 4);
-  L->dist_u = o;  o += al(nc * 4);
-  L->xp_u = o;    o += al(nc * 8);
-  L->yp_u = o;    o += al(nc * 8);
-  L->idx1 = o;    o += al(nc * 4);
-  L->simg = o;    o += al(nc * 4);
-  L->dist = o;    o += al(nc * 4);
-  L->xp = o;      o += al(nc * 8);
-  L->yp = o;      o += al(nc * 8);
-  L->splat = o;   o += al(nc * 16);
-  L->seen = o;    o += al(nc);
-  L->cnt = o;     o += al(sizeof(MapCounters));
-  L->zbuf = o;    o += al(npix * 8);
-  L->pixmap = o;  o += al(npix * 4);
-  L->pixflag = o; o += al(npix * 4);
-  L->pixpos = o;  o += al(npix * 4);
-  L->temp = o;
+  Carver w(ws);
+  L->flag = w.take<int32_t>(nc);
+  L->pos = w.take<int32_t>(nc);
+  L->dist_u = w.take<float>(nc);
+  L->xp_u = w.take<double>(nc);
+  L->yp_u = w.take<double>(nc);
+  L->idx1 = w.take<int32_t>(nc);
+  L->simg = w.take<int32_t>(nc);
+  L->dist = w.take<float>(nc);
+  L->xp = w.take<double>(nc);
+  L->yp = w.take<double>(nc);
+  L->splat = w.take<int4>(nc);
+  L->seen = w.take<uint8_t>(nc);
+  L->cnt = w.take<MapCounters>(1);
+  L->zbuf = w.take<unsigned long long>(npix);
+  L->pixmap = w.take<int32_t>(npix);
+  L->pixflag = w.take<int32_t>(npix);
+  L->pixpos = w.take<int32_t>(npix);
   L->temp_bytes = scan_tmp;
-  o += al(scan_tmp);
+  L->temp = w.take<char>(scan_tmp);
   L->Tx = (int)((c->img_w + ZT - 1) / ZT);
   L->Ty = (int)((Hc + ZT - 1) / ZT);
   const size_t nt = (size_t)L->Tx * (size_t)L->Ty * (size_t)B;
-  L->tile_count = o;  o += al(nt * 4);
-  L->tile_cursor = o; o += al(nt * 4);
-  L->ctl = o;         o += al((size_t)(B + 1) * 4);
-  L->tile_zero_bytes = o - L->tile_count;
-  L->tile_off = o;    o += al(nt * 4);
+  const size_t zero_from = w.used();
+  L->tile_count = w.take<int32_t>(nt);
+  L->tile_cursor = w.take<int32_t>(nt);
+  L->ctl = w.take<int32_t>((size_t)(B + 1));
+  L->tile_zero_bytes = w.used() - zero_from;
+  L->tile_off = w.take<int32_t>(nt);
   L->list_cap = (int64_t)nc * 4;
-  L->list = o;        o += al((size_t)L->list_cap * 16);
-  L->big_list = o;    o += al((size_t)B * ZT_BIGCAP * 16);
-  L->fb_list = o;     o += al(nc * 4);
-  L->total = o;
+  L->list = w.take<int4>((size_t)L->list_cap);
+  L->big_list = w.take<int4>((size_t)B * ZT_BIGCAP);
+  L->fb_list = w.take<int32_t>(nc);
+  L->total = w.used();
   return DVA_OK;
 }
 
@@ -946,22 +952,17 @@ int dva_camera_projection(const float* xyz, int64_t n, const dva_camera* cam, co
   if (n > 0x7fffffff) return DVA_ERR_UNSUPPORTED;
   if (!xyz || !idx || !depth || !x_proj || !y_proj || !workspace) return DVA_ERR_INVALID;
   VisLayout L;
-  int rc = vis_layout(cam, n, &L);
+  int rc = vis_layout(workspace, cam, n, &L);
   if (rc) return rc;
   if ((int64_t)L.total > workspace_bytes) return DVA_ERR_INVALID;
-  char* ws = (char*)workspace;
-  int32_t* flag = (int32_t*)(ws + L.flag);
-  int32_t* pos = (int32_t*)(ws + L.pos);
-  float* dist_u = (float*)(ws + L.dist_u);
-  double* xp_u = (double*)(ws + L.xp_u);
-  double* yp_u = (double*)(ws + L.yp_u);
   const dva_camera c = *cam;
-  hipLaunchKernelGGL(project_kernel, dim3(grid_for(n)), dim3(256), 0, s, xyz, n, c, mask, flag, dist_u, xp_u, yp_u);
+  hipLaunchKernelGGL(project_kernel, dim3(capped_grid(n, 256, 4096)), dim3(256), 0, s, xyz, n, c, mask, L.flag,
+                     L.dist_u, L.xp_u, L.yp_u);
   size_t tmp = L.temp_bytes;
-  if (rocprim::exclusive_scan(ws + L.temp, tmp, flag, pos, 0, (size_t)n, rocprim::plus<int32_t>(), s) != hipSuccess)
+  if (rocprim::exclusive_scan(L.temp, tmp, L.flag, L.pos, 0, (size_t)n, rocprim::plus<int32_t>(), s) != hipSuccess)
     return DVA_ERR_LAUNCH;
-  hipLaunchKernelGGL(projection_out_kernel, dim3(grid_for(n)), dim3(256), 0, s, n, flag, pos, dist_u, xp_u, yp_u, idx,
-                     depth, x_proj, y_proj, n_out_dev);
+  hipLaunchKernelGGL(projection_out_kernel, dim3(capped_grid(n, 256, 4096)), dim3(256), 0, s, n, L.flag, L.pos,
+                     L.dist_u, L.xp_u, L.yp_u, idx, depth, x_proj, y_proj, n_out_dev);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -969,7 +970,7 @@ int dva_camera_projection(const float* xyz, int64_t n, const dva_camera* cam, co
 int64_t dva_visibility_workspace_bytes(const dva_camera* cam, int64_t n) {
   if (!cam || n < 0) return DVA_ERR_INVALID;
   VisLayout L;
-  int rc = vis_layout(cam, n > 0 ? n : 1, &L);
+  int rc = vis_layout(nullptr, cam, n > 0 ? n : 1, &L);
   if (rc) return rc;
   return (int64_t)L.total;
 }
@@ -989,62 +990,45 @@ int dva_visibility(const float* xyz, int64_t n, const dva_camera* cam, const uin
   if (!xyz || !idx || !x_pix || !y_pix || !depth || !x_proj || !y_proj || !workspace)
     return DVA_ERR_INVALID;
   VisLayout L;
-  int rc = vis_layout(cam, n, &L);
+  int rc = vis_layout(workspace, cam, n, &L);
   if (rc) return rc;
   if ((int64_t)L.total > workspace_bytes) return DVA_ERR_INVALID;
-  char* ws = (char*)workspace;
   const int Hc = cam->img_h - cam->crop_top - cam->crop_bottom;
   const int64_t npix = (int64_t)cam->img_w * Hc;
-  int32_t* flag = (int32_t*)(ws + L.flag);
-  int32_t* pos = (int32_t*)(ws + L.pos);
-  float* dist_u = (float*)(ws + L.dist_u);
-  double* xp_u = (double*)(ws + L.xp_u);
-  double* yp_u = (double*)(ws + L.yp_u);
-  int32_t* idx1 = (int32_t*)(ws + L.idx1);
-  float* dist = (float*)(ws + L.dist);
-  double* xp = (double*)(ws + L.xp);
-  double* yp = (double*)(ws + L.yp);
-  int4* splat = (int4*)(ws + L.splat);
-  uint8_t* seen = (uint8_t*)(ws + L.seen);
-  MapCounters* cnt = (MapCounters*)(ws + L.cnt);
-  unsigned long long* zbuf = (unsigned long long*)(ws + L.zbuf);
-  int32_t* pixmap = (int32_t*)(ws + L.pixmap);
-  int32_t* pixflag = (int32_t*)(ws + L.pixflag);
-  int32_t* pixpos = (int32_t*)(ws + L.pixpos);
 
   const dva_camera c = *cam;
-  hipLaunchKernelGGL(project_kernel, dim3(grid_for(n)), dim3(256), 0, s, xyz, n, c, mask, flag, dist_u,
-                     xp_u, yp_u);
+  hipLaunchKernelGGL(project_kernel, dim3(capped_grid(n, 256, 4096)), dim3(256), 0, s, xyz, n, c, mask, L.flag,
+                     L.dist_u, L.xp_u, L.yp_u);
   size_t tmp = L.temp_bytes;
-  if (rocprim::exclusive_scan(ws + L.temp, tmp, flag, pos, 0, (size_t)n, rocprim::plus<int32_t>(), s) !=
-      hipSuccess)
+  if (rocprim::exclusive_scan(L.temp, tmp, L.flag, L.pos, 0, (size_t)n, rocprim::plus<int32_t>(), s) != hipSuccess)
     return DVA_ERR_LAUNCH;
-  hipLaunchKernelGGL(compact_kernel, dim3(grid_for(n)), dim3(256), 0, s, n, flag, pos, dist_u, xp_u, yp_u,
-                     idx1, dist, xp, yp, cnt);
-  hipLaunchKernelGGL(splat_kernel, dim3(grid_for(n)), dim3(256), 0, s, xyz, idx1, dist, xp, yp, c, cnt,
-                     splat);
-  if (hipMemsetAsync(zbuf, 0xFF, (size_t)npix * 8, s) != hipSuccess) return DVA_ERR_LAUNCH;
+  hipLaunchKernelGGL(compact_kernel, dim3(capped_grid(n, 256, 4096)), dim3(256), 0, s, n, L.flag, L.pos, L.dist_u,
+                     L.xp_u, L.yp_u, L.idx1, L.dist, L.xp, L.yp, L.cnt);
+  hipLaunchKernelGGL(splat_kernel, dim3(capped_grid(n, 256, 4096)), dim3(256), 0, s, xyz, L.idx1, L.dist, L.xp, L.yp, c,
+                     L.cnt, L.splat);
+  if (hipMemsetAsync(L.zbuf, 0xFF, (size_t)npix * 8, s) != hipSuccess) return DVA_ERR_LAUNCH;
   {
     int64_t blocks = (n + 3) / 4;  // 4 wavefronts (points) per block
     if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(zbuffer_kernel, dim3((int)blocks), dim3(256), 0, s, splat, dist, cnt, zbuf, Hc);
+    hipLaunchKernelGGL(zbuffer_kernel, dim3((int)blocks), dim3(256), 0, s, L.splat, L.dist, L.cnt, L.zbuf, Hc);
   }
   if (c.exact) {
-    if (hipMemsetAsync(seen, 0, (size_t)n, s) != hipSuccess) return DVA_ERR_LAUNCH;
-    if (hipMemsetAsync(pixmap, 0xFF, (size_t)npix * 4, s) != hipSuccess) return DVA_ERR_LAUNCH;
-    hipLaunchKernelGGL(seen_kernel, dim3(grid_for(npix)), dim3(256), 0, s, zbuf, npix, seen);
-    hipLaunchKernelGGL(resplat_kernel, dim3(grid_for(n)), dim3(256), 0, s, seen, xp, yp, cnt, pixmap, Hc,
-                       c.crop_top);
+    if (hipMemsetAsync(L.seen, 0, (size_t)n, s) != hipSuccess) return DVA_ERR_LAUNCH;
+    if (hipMemsetAsync(L.pixmap, 0xFF, (size_t)npix * 4, s) != hipSuccess) return DVA_ERR_LAUNCH;
+    hipLaunchKernelGGL(seen_kernel, dim3(capped_grid(npix, 256, 4096)), dim3(256), 0, s, L.zbuf, npix, L.seen);
+    hipLaunchKernelGGL(resplat_kernel, dim3(capped_grid(n, 256, 4096)), dim3(256), 0, s, L.seen, L.xp, L.yp, L.cnt,
+                       L.pixmap, Hc, c.crop_top);
   } else {
-    hipLaunchKernelGGL(winners_kernel, dim3(grid_for(npix)), dim3(256), 0, s, zbuf, npix, pixmap);
+    hipLaunchKernelGGL(winners_kernel, dim3(capped_grid(npix, 256, 4096)), dim3(256), 0, s, L.zbuf, npix, L.pixmap);
   }
-  hipLaunchKernelGGL(pixflag_kernel, dim3(grid_for(npix)), dim3(256), 0, s, pixmap, npix, pixflag);
+  hipLaunchKernelGGL(pixflag_kernel, dim3(capped_grid(npix, 256, 4096)), dim3(256), 0, s, L.pixmap, npix, L.pixflag);
   tmp = L.temp_bytes;
-  if (rocprim::exclusive_scan(ws + L.temp, tmp, pixflag, pixpos, 0, (size_t)npix,
+  if (rocprim::exclusive_scan(L.temp, tmp, L.pixflag, L.pixpos, 0, (size_t)npix,
                               rocprim::plus<int32_t>(), s) != hipSuccess)
     return DVA_ERR_LAUNCH;
-  hipLaunchKernelGGL(emit_kernel, dim3(grid_for(npix)), dim3(256), 0, s, pixmap, pixflag, pixpos, npix, Hc,
-                     c.crop_top, idx1, dist, xp, yp, idx, x_pix, y_pix, depth, x_proj, y_proj, n_out_dev);
+  hipLaunchKernelGGL(emit_kernel, dim3(capped_grid(npix, 256, 4096)), dim3(256), 0, s, L.pixmap, L.pixflag, L.pixpos,
+                     npix, Hc, c.crop_top, L.idx1, L.dist, L.xp, L.yp, idx, x_pix, y_pix, depth, x_proj, y_proj,
+                     n_out_dev);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -1052,7 +1036,7 @@ int dva_visibility(const float* xyz, int64_t n, const dva_camera* cam, const uin
 int64_t dva_visibility_batch_workspace_bytes(const dva_camera* cam, int64_t n, int32_t n_images) {
   if (!cam || n < 0 || n_images < 1) return DVA_ERR_INVALID;
   VisBatchLayout L;
-  int rc = vis_batch_layout(cam, n > 0 ? n : 1, n_images, &L);
+  int rc = vis_batch_layout(nullptr, cam, n > 0 ? n : 1, n_images, &L);
   if (rc) return rc;
   return (int64_t)L.total;
 }
@@ -1075,109 +1059,87 @@ int dva_visibility_batch(const float* xyz, int64_t n, const dva_camera* cam0, co
   if (n * B > 0x7fffffffLL || npix * B > 0x7fffffffLL) return DVA_ERR_UNSUPPORTED;
   if (!xyz || !idx || !x_pix || !y_pix || !depth || !x_proj || !y_proj || !workspace) return DVA_ERR_INVALID;
   VisBatchLayout L;
-  int rc = vis_batch_layout(cam0, n, B, &L);
+  int rc = vis_batch_layout(workspace, cam0, n, B, &L);
   if (rc) return rc;
   if ((int64_t)L.total > workspace_bytes) return DVA_ERR_INVALID;
-  char* ws = (char*)workspace;
-  int32_t* flag = (int32_t*)(ws + L.flag);
-  int32_t* pos = (int32_t*)(ws + L.pos);
-  float* dist_u = (float*)(ws + L.dist_u);
-  double* xp_u = (double*)(ws + L.xp_u);
-  double* yp_u = (double*)(ws + L.yp_u);
-  int32_t* idx1 = (int32_t*)(ws + L.idx1);
-  int32_t* simg = (int32_t*)(ws + L.simg);
-  float* dist = (float*)(ws + L.dist);
-  double* xp = (double*)(ws + L.xp);
-  double* yp = (double*)(ws + L.yp);
-  int4* splat = (int4*)(ws + L.splat);
-  uint8_t* seen = (uint8_t*)(ws + L.seen);
-  MapCounters* cnt = (MapCounters*)(ws + L.cnt);
-  unsigned long long* zbuf = (unsigned long long*)(ws + L.zbuf);
-  int32_t* pixmap = (int32_t*)(ws + L.pixmap);
-  int32_t* pixflag = (int32_t*)(ws + L.pixflag);
-  int32_t* pixpos = (int32_t*)(ws + L.pixpos);
   const int64_t nc = n * B, npt = npix * B;
 
   {
-    int gx = grid_for(n);
+    int gx = capped_grid(n, 256, 4096);
     if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(project_batch_kernel, dim3(gx, B), dim3(256), 0, s, xyz, n, cams_dev, mask, flag, dist_u, xp_u,
-                       yp_u);
+    hipLaunchKernelGGL(project_batch_kernel, dim3(gx, B), dim3(256), 0, s, xyz, n, cams_dev, mask, L.flag, L.dist_u,
+                       L.xp_u, L.yp_u);
   }
   size_t tmp = L.temp_bytes;
-  if (rocprim::exclusive_scan(ws + L.temp, tmp, flag, pos, 0, (size_t)nc, rocprim::plus<int32_t>(), s) != hipSuccess)
+  if (rocprim::exclusive_scan(L.temp, tmp, L.flag, L.pos, 0, (size_t)nc, rocprim::plus<int32_t>(), s) != hipSuccess)
     return DVA_ERR_LAUNCH;
-  hipLaunchKernelGGL(compact_batch_kernel, dim3(grid_for(nc)), dim3(256), 0, s, n, B, flag, pos, dist_u, xp_u, yp_u,
-                     idx1, simg, dist, xp, yp, cnt);
-  hipLaunchKernelGGL(splat_batch_kernel, dim3(grid_for(nc)), dim3(256), 0, s, xyz, idx1, simg, dist, xp, yp, cams_dev,
-                     cnt, splat);
+  hipLaunchKernelGGL(compact_batch_kernel, dim3(capped_grid(nc, 256, 4096)), dim3(256), 0, s, n, B, L.flag, L.pos,
+                     L.dist_u, L.xp_u, L.yp_u, L.idx1, L.simg, L.dist, L.xp, L.yp, L.cnt);
+  hipLaunchKernelGGL(splat_batch_kernel, dim3(capped_grid(nc, 256, 4096)), dim3(256), 0, s, xyz, L.idx1, L.simg, L.dist,
+                     L.xp, L.yp, cams_dev, L.cnt, L.splat);
   // (box corners are packed into 16 bits; tile_off is an int32 scan of up to ZT_BIG entries per candidate: beyond
   //  2^31 - 1 possible entries the whole batch takes the atomic plane)
   if (cam0->img_w < 65536 && Hc < 65536 && nc * ZT_BIG <= 0x7fffffffLL) {
-    int32_t* tile_count = (int32_t*)(ws + L.tile_count);
-    int32_t* tile_cursor = (int32_t*)(ws + L.tile_cursor);
-    int32_t* ctl = (int32_t*)(ws + L.ctl);
-    int32_t* tile_off = (int32_t*)(ws + L.tile_off);
-    int4* list = (int4*)(ws + L.list);
-    int4* big_list = (int4*)(ws + L.big_list);
-    int32_t* fb_list = (int32_t*)(ws + L.fb_list);
     const size_t nt = (size_t)L.Tx * (size_t)L.Ty * (size_t)B;
     const int T = L.Tx * L.Ty;
     const int n_img = T <= 4096 ? 2 : (T <= 8192 ? 1 : 0);        // images whose tile counters fit the block's LDS
     const size_t lds = (size_t)n_img * T * 4;
     int bin_blocks = (int)((nc + ZT_CHUNK - 1) / ZT_CHUNK);
     if (bin_blocks > 4096) bin_blocks = 4096;
-    if (hipMemsetAsync(ws + L.tile_count, 0, L.tile_zero_bytes, s) != hipSuccess) return DVA_ERR_LAUNCH;
-    hipLaunchKernelGGL((tile_bin_kernel<false>), dim3(bin_blocks), dim3(ZT_BLOCK), lds, s, splat, simg, dist, cnt, L.Tx,
-                       L.Ty, B, n_img, tile_count, tile_off, tile_cursor, list, L.list_cap, ctl, big_list, fb_list);
+    if (hipMemsetAsync(L.tile_count, 0, L.tile_zero_bytes, s) != hipSuccess) return DVA_ERR_LAUNCH;
+    hipLaunchKernelGGL((tile_bin_kernel<false>), dim3(bin_blocks), dim3(ZT_BLOCK), lds, s, L.splat, L.simg, L.dist,
+                       L.cnt, L.Tx, L.Ty, B, n_img, L.tile_count, L.tile_off, L.tile_cursor, L.list, L.list_cap, L.ctl,
+                       L.big_list, L.fb_list);
     tmp = L.temp_bytes;
-    if (rocprim::exclusive_scan(ws + L.temp, tmp, tile_count, tile_off, 0, nt, rocprim::plus<int32_t>(), s) !=
+    if (rocprim::exclusive_scan(L.temp, tmp, L.tile_count, L.tile_off, 0, nt, rocprim::plus<int32_t>(), s) !=
         hipSuccess)
       return DVA_ERR_LAUNCH;
-    hipLaunchKernelGGL((tile_bin_kernel<true>), dim3(bin_blocks), dim3(ZT_BLOCK), 2 * lds, s, splat, simg, dist, cnt,
-                       L.Tx, L.Ty, B, n_img, tile_count, tile_off, tile_cursor, list, L.list_cap, ctl, big_list,
-                       fb_list);
-    hipLaunchKernelGGL(zbuffer_cond_clear_kernel, dim3(grid_for(npt)), dim3(256), 0, s, ctl, B, zbuf, npt);
-    hipLaunchKernelGGL(zbuffer_fallback_kernel, dim3(256), dim3(256), 0, s, fb_list, ctl, B, splat, simg, dist, zbuf,
-                       Hc, npix);
-    if (cam0->exact && hipMemsetAsync(seen, 0, (size_t)nc, s) != hipSuccess) return DVA_ERR_LAUNCH;
-    hipLaunchKernelGGL(tile_raster_kernel, dim3((unsigned)nt), dim3(256), 0, s, tile_off, tile_count, list, L.list_cap,
-                       ctl, big_list, zbuf, seen, pixmap, (int)cam0->img_w, Hc, L.Tx, L.Ty, B, (int)cam0->exact);
+    hipLaunchKernelGGL((tile_bin_kernel<true>), dim3(bin_blocks), dim3(ZT_BLOCK), 2 * lds, s, L.splat, L.simg, L.dist,
+                       L.cnt, L.Tx, L.Ty, B, n_img, L.tile_count, L.tile_off, L.tile_cursor, L.list, L.list_cap, L.ctl,
+                       L.big_list, L.fb_list);
+    hipLaunchKernelGGL(zbuffer_cond_clear_kernel, dim3(capped_grid(npt, 256, 4096)), dim3(256), 0, s, L.ctl, B, L.zbuf,
+                       npt);
+    hipLaunchKernelGGL(zbuffer_fallback_kernel, dim3(256), dim3(256), 0, s, L.fb_list, L.ctl, B, L.splat, L.simg,
+                       L.dist, L.zbuf, Hc, npix);
+    if (cam0->exact && hipMemsetAsync(L.seen, 0, (size_t)nc, s) != hipSuccess) return DVA_ERR_LAUNCH;
+    hipLaunchKernelGGL(tile_raster_kernel, dim3((unsigned)nt), dim3(256), 0, s, L.tile_off, L.tile_count, L.list,
+                       L.list_cap, L.ctl, L.big_list, L.zbuf, L.seen, L.pixmap, (int)cam0->img_w, Hc, L.Tx, L.Ty, B,
+                       (int)cam0->exact);
     if (cam0->exact)
-      hipLaunchKernelGGL(resplat_batch_kernel, dim3(grid_for(nc)), dim3(256), 0, s, seen, simg, xp, yp, cnt, pixmap,
-                         Hc, cam0->crop_top, npix);
+      hipLaunchKernelGGL(resplat_batch_kernel, dim3(capped_grid(nc, 256, 4096)), dim3(256), 0, s, L.seen, L.simg, L.xp,
+                         L.yp, L.cnt, L.pixmap, Hc, cam0->crop_top, npix);
   } else {
-    if (hipMemsetAsync(zbuf, 0xFF, (size_t)npt * 8, s) != hipSuccess) return DVA_ERR_LAUNCH;
+    if (hipMemsetAsync(L.zbuf, 0xFF, (size_t)npt * 8, s) != hipSuccess) return DVA_ERR_LAUNCH;
     {
       int64_t blocks = (nc + 15) / 16;          // 4 wavefronts x 4 survivors per block iteration
       if (blocks > 256 * 32) blocks = 256 * 32;
-      hipLaunchKernelGGL(zbuffer_batch_kernel, dim3((int)blocks), dim3(256), 0, s, splat, simg, dist, cnt, zbuf, Hc,
-                         npix);
+      hipLaunchKernelGGL(zbuffer_batch_kernel, dim3((int)blocks), dim3(256), 0, s, L.splat, L.simg, L.dist, L.cnt,
+                         L.zbuf, Hc, npix);
     }
     if (cam0->exact) {
-      if (hipMemsetAsync(seen, 0, (size_t)nc, s) != hipSuccess) return DVA_ERR_LAUNCH;
-      if (hipMemsetAsync(pixmap, 0xFF, (size_t)npt * 4, s) != hipSuccess) return DVA_ERR_LAUNCH;
-      hipLaunchKernelGGL(seen_kernel, dim3(grid_for(npt)), dim3(256), 0, s, zbuf, npt, seen);
-      hipLaunchKernelGGL(resplat_batch_kernel, dim3(grid_for(nc)), dim3(256), 0, s, seen, simg, xp, yp, cnt, pixmap, Hc,
-                         cam0->crop_top, npix);
+      if (hipMemsetAsync(L.seen, 0, (size_t)nc, s) != hipSuccess) return DVA_ERR_LAUNCH;
+      if (hipMemsetAsync(L.pixmap, 0xFF, (size_t)npt * 4, s) != hipSuccess) return DVA_ERR_LAUNCH;
+      hipLaunchKernelGGL(seen_kernel, dim3(capped_grid(npt, 256, 4096)), dim3(256), 0, s, L.zbuf, npt, L.seen);
+      hipLaunchKernelGGL(resplat_batch_kernel, dim3(capped_grid(nc, 256, 4096)), dim3(256), 0, s, L.seen, L.simg, L.xp,
+                         L.yp, L.cnt, L.pixmap, Hc, cam0->crop_top, npix);
     } else {
-      hipLaunchKernelGGL(winners_kernel, dim3(grid_for(npt)), dim3(256), 0, s, zbuf, npt, pixmap);
+      hipLaunchKernelGGL(winners_kernel, dim3(capped_grid(npt, 256, 4096)), dim3(256), 0, s, L.zbuf, npt, L.pixmap);
     }
 }
   // output position of every mapped pixel: per-block counts, a scan over the blocks, positions inside a block from
   // ballots (the map-sized exclusive scan of round 3a: one write + one read of a B x map-sized plane more)
   {
     const int64_t n_blocks = (npt + EB_PIX - 1) / EB_PIX;
-    int32_t* block_count = pixflag;                       // [n_blocks] (the flag plane is otherwise unused here)
-    int32_t* block_off = pixpos;
-    hipLaunchKernelGGL(pix_block_count_kernel, dim3((unsigned)n_blocks), dim3(256), 0, s, pixmap, npt, block_count);
+    int32_t* block_count = L.pixflag;                     // [n_blocks] (the flag plane is otherwise unused here)
+    int32_t* block_off = L.pixpos;
+    hipLaunchKernelGGL(pix_block_count_kernel, dim3((unsigned)n_blocks), dim3(256), 0, s, L.pixmap, npt, block_count);
     tmp = L.temp_bytes;
-    if (rocprim::exclusive_scan(ws + L.temp, tmp, block_count, block_off, 0, (size_t)n_blocks,
+    if (rocprim::exclusive_scan(L.temp, tmp, block_count, block_off, 0, (size_t)n_blocks,
                                 rocprim::plus<int32_t>(), s) != hipSuccess)
       return DVA_ERR_LAUNCH;
-    hipLaunchKernelGGL(emit_blocks_kernel, dim3((unsigned)n_blocks), dim3(256), 0, s, pixmap, block_off, n_blocks, npix,
-                       B, Hc, cam0->crop_top, idx1, dist, xp, yp, idx, x_pix, y_pix, depth, x_proj, y_proj, row_ptr,
-                       n_out_dev);
+    hipLaunchKernelGGL(emit_blocks_kernel, dim3((unsigned)n_blocks), dim3(256), 0, s, L.pixmap, block_off, n_blocks,
+                       npix, B, Hc, cam0->crop_top, L.idx1, L.dist, L.xp, L.yp, idx, x_pix, y_pix, depth, x_proj,
+                       y_proj, row_ptr, n_out_dev);
   }
   DVA_CHECK_LAUNCH();
   return DVA_OK;
@@ -1194,9 +1156,9 @@ int dva_mapping_features_batch(const float* xyz, const int64_t* idx, const float
   if (n_cols) *n_cols = ncol;
   if (q == 0) return DVA_OK;
   if (!xyz || !idx || !depth || !y_proj || !features) return DVA_ERR_INVALID;
-  hipLaunchKernelGGL(features_batch_kernel, dim3(grid_for(q)), dim3(256), 0, (hipStream_t)stream, xyz, idx, depth,
-                     y_proj, linearity, planarity, scattering, normals, cams_dev, row_ptr, (int)n_images, q, ncol,
-                     features, row_image);
+  hipLaunchKernelGGL(features_batch_kernel, dim3(capped_grid(q, 256, 4096)), dim3(256), 0, (hipStream_t)stream, xyz,
+                     idx, depth, y_proj, linearity, planarity, scattering, normals, cams_dev, row_ptr, (int)n_images, q,
+                     ncol, features, row_image);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -1211,7 +1173,7 @@ int dva_mapping_features(const float* xyz, const int64_t* idx, const float* dept
   if (n_cols) *n_cols = ncol;
   if (q == 0) return DVA_OK;
   if (!xyz || !idx || !depth || !y_proj || !features) return DVA_ERR_INVALID;
-  hipLaunchKernelGGL(features_kernel, dim3(grid_for(q)), dim3(256), 0, (hipStream_t)stream, xyz, idx,
+  hipLaunchKernelGGL(features_kernel, dim3(capped_grid(q, 256, 4096)), dim3(256), 0, (hipStream_t)stream, xyz, idx,
                      depth, y_proj, linearity, planarity, scattering, normals, *cam, q, ncol, features);
   DVA_CHECK_LAUNCH();
   return DVA_OK;

@@ -41,36 +41,34 @@ typedef unsigned long long u64;
 enum { C_BAD = 0, C_M = 1, C_NBIG = 2, C_AUSED = 3, C_VUSED = 4, C_COUNT = 8 };
 
 struct MergeLayout {
-  int64_t ctr, hist, voxel_ptr, members, nviews, natoms, view_base, atom_base, bsum, big_j, big_na, big_nv, big_aoff,
-      big_voff, scratch_a, scratch_v, total;
-  int64_t bigcap, nb;
+  u64 *ctr, *scratch_a, *scratch_v;
+  int *hist, *voxel_ptr, *members, *nviews, *natoms, *view_base, *atom_base, *bsum, *big_j, *big_na, *big_nv;
+  int64_t *big_aoff, *big_voff;
+  int64_t total, bigcap, nb;
 };
 
-static inline int64_t pad16(int64_t b) { return (b + 15) & ~(int64_t)15; }
-
-static inline MergeLayout merge_layout(int64_t N, int64_t V, int64_t P) {
+static inline MergeLayout merge_layout(void* ws, int64_t N, int64_t V, int64_t P) {
   MergeLayout L;
   L.nb = (N + SCAN_BLOCK - 1) / SCAN_BLOCK;
   L.bigcap = P / (MERGE_TILE + 1) + 1;
-  int64_t o = 0;
-  auto take = [&](int64_t bytes) { int64_t at = o; o += pad16(bytes); return at; };
-  L.ctr = take(C_COUNT * 8);
-  L.hist = take(N * 4);
-  L.voxel_ptr = take((N + 1) * 4);
-  L.members = take(N * 4);
-  L.nviews = take(N * 4);
-  L.natoms = take(N * 4);
-  L.view_base = take((N + 1) * 4);
-  L.atom_base = take((N + 1) * 4);
-  L.bsum = take((L.nb + 1) * 4);
-  L.big_j = take(L.bigcap * 4);
-  L.big_na = take(L.bigcap * 4);
-  L.big_nv = take(L.bigcap * 4);
-  L.big_aoff = take(L.bigcap * 8);
-  L.big_voff = take(L.bigcap * 8);
-  L.scratch_a = take(P * 8);
-  L.scratch_v = take(V * 8);
-  L.total = o;
+  Carver c(ws, 16);
+  L.ctr = c.take<u64>(C_COUNT);
+  L.hist = c.take<int>(N);
+  L.voxel_ptr = c.take<int>(N + 1);
+  L.members = c.take<int>(N);
+  L.nviews = c.take<int>(N);
+  L.natoms = c.take<int>(N);
+  L.view_base = c.take<int>(N + 1);
+  L.atom_base = c.take<int>(N + 1);
+  L.bsum = c.take<int>(L.nb + 1);
+  L.big_j = c.take<int>(L.bigcap);
+  L.big_na = c.take<int>(L.bigcap);
+  L.big_nv = c.take<int>(L.bigcap);
+  L.big_aoff = c.take<int64_t>(L.bigcap);
+  L.big_voff = c.take<int64_t>(L.bigcap);
+  L.scratch_a = c.take<u64>(P);
+  L.scratch_v = c.take<u64>(V);
+  L.total = (int64_t)c.used();
   return L;
 }
 
@@ -601,13 +599,6 @@ __global__ __launch_bounds__(BIG_THREADS) void merge_fill_big_kernel(const u64* 
   }
 }
 
-static inline int grid_for(int64_t n, int threads, int cap) {
-  int64_t b = (n + threads - 1) / threads;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 static inline int merge_check_sizes(int64_t N, int64_t V, int64_t P) {
   if (N < 1 || V < 0 || P < 0) return DVA_ERR_INVALID;
   if (N >= 0x7fffffffLL || V >= 0x7fffffffLL || P >= 0x7fffffffLL) return DVA_ERR_UNSUPPORTED;
@@ -625,7 +616,7 @@ int dva_mapping_merge_tile_atoms(void) { return MERGE_TILE; }
 int64_t dva_mapping_merge_workspace_bytes(int64_t n_points, int64_t n_views, int64_t n_atoms) {
   const int rc = merge_check_sizes(n_points, n_views, n_atoms);
   if (rc != DVA_OK) return rc;
-  return merge_layout(n_points, n_views, n_atoms).total;
+  return merge_layout(nullptr, n_points, n_views, n_atoms).total;
 }
 
 int dva_mapping_merge_count(const int64_t* pointers, const int64_t* images, const int64_t* atom_ptr,
@@ -639,37 +630,25 @@ int dva_mapping_merge_count(const int64_t* pointers, const int64_t* images, cons
   if (!pointers || !atom_ptr || !idx || !sizes || !workspace) return DVA_ERR_INVALID;
   if ((n_views > 0 && !images) || (n_atoms > 0 && !pixels)) return DVA_ERR_INVALID;
   if (((uintptr_t)pixels & 3) || ((uintptr_t)workspace & 15)) return DVA_ERR_INVALID;
-  const MergeLayout L = merge_layout(n_points, n_views, n_atoms);
+  const MergeLayout L = merge_layout(workspace, n_points, n_views, n_atoms);
   if (workspace_bytes < L.total) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  u64* ctr = (u64*)(ws + L.ctr);
-  int* hist = (int*)(ws + L.hist);
-  int* voxel_ptr = (int*)(ws + L.voxel_ptr);
-  int* members = (int*)(ws + L.members);
-  int* nviews = (int*)(ws + L.nviews);
-  int* natoms = (int*)(ws + L.natoms);
-  int* view_base = (int*)(ws + L.view_base);
-  int* atom_base = (int*)(ws + L.atom_base);
-  int* bsum = (int*)(ws + L.bsum);
   const int64_t N = n_points;
   // ctr and hist are adjacent
-  if (hipMemsetAsync(ws + L.ctr, 0, (size_t)(L.voxel_ptr - L.ctr), s) != hipSuccess) return DVA_ERR_LAUNCH;
-  hipLaunchKernelGGL(merge_hist_kernel, dim3(grid_for(N, 256, 4096)), dim3(256), 0, s, idx, N, hist, ctr);
-  launch_scan(hist, N, bsum, L.nb, voxel_ptr, s);
-  hipLaunchKernelGGL(merge_scatter_kernel, dim3(grid_for(N, 256, 4096)), dim3(256), 0, s, idx, N, hist,
-                     (const int*)voxel_ptr, members);
-  const MergeIn in = {pointers, images, atom_ptr, (const uint32_t*)pixels, voxel_ptr, members};
-  hipLaunchKernelGGL(merge_count_small_kernel, dim3(grid_for(N, 1, MERGE_GRID)), dim3(DVA_WAVE), 0, s, in, N, ctr,
-                     nviews, natoms, (int*)(ws + L.big_j), (int*)(ws + L.big_na), (int*)(ws + L.big_nv), L.bigcap);
-  hipLaunchKernelGGL(merge_count_big_kernel, dim3(grid_for(L.bigcap, 1, BIG_GRID)), dim3(BIG_THREADS), 0, s, in, ctr,
-                     nviews, natoms, (const int*)(ws + L.big_j), (int*)(ws + L.big_na), (const int*)(ws + L.big_nv),
-                     (int64_t*)(ws + L.big_aoff), (int64_t*)(ws + L.big_voff), L.bigcap, (u64*)(ws + L.scratch_a),
-                     (u64*)(ws + L.scratch_v), n_atoms, n_views);
-  launch_scan(nviews, N, bsum, L.nb, view_base, s);
-  launch_scan(natoms, N, bsum, L.nb, atom_base, s);
-  hipLaunchKernelGGL(merge_sizes_kernel, dim3(1), dim3(1), 0, s, (const u64*)ctr, (const int*)view_base,
-                     (const int*)atom_base, N, sizes);
+  if (hipMemsetAsync(L.ctr, 0, (size_t)((char*)L.voxel_ptr - (char*)L.ctr), s) != hipSuccess) return DVA_ERR_LAUNCH;
+  hipLaunchKernelGGL(merge_hist_kernel, dim3(capped_grid(N, 256, 4096)), dim3(256), 0, s, idx, N, L.hist, L.ctr);
+  launch_scan(L.hist, N, L.bsum, L.nb, L.voxel_ptr, s);
+  hipLaunchKernelGGL(merge_scatter_kernel, dim3(capped_grid(N, 256, 4096)), dim3(256), 0, s, idx, N, L.hist,
+                     L.voxel_ptr, L.members);
+  const MergeIn in = {pointers, images, atom_ptr, (const uint32_t*)pixels, L.voxel_ptr, L.members};
+  hipLaunchKernelGGL(merge_count_small_kernel, dim3(capped_grid(N, 1, MERGE_GRID)), dim3(DVA_WAVE), 0, s, in, N, L.ctr,
+                     L.nviews, L.natoms, L.big_j, L.big_na, L.big_nv, L.bigcap);
+  hipLaunchKernelGGL(merge_count_big_kernel, dim3(capped_grid(L.bigcap, 1, BIG_GRID)), dim3(BIG_THREADS), 0, s, in,
+                     L.ctr, L.nviews, L.natoms, L.big_j, L.big_na, L.big_nv, L.big_aoff, L.big_voff, L.bigcap,
+                     L.scratch_a, L.scratch_v, n_atoms, n_views);
+  launch_scan(L.nviews, N, L.bsum, L.nb, L.view_base, s);
+  launch_scan(L.natoms, N, L.bsum, L.nb, L.atom_base, s);
+  hipLaunchKernelGGL(merge_sizes_kernel, dim3(1), dim3(1), 0, s, L.ctr, L.view_base, L.atom_base, N, sizes);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -693,22 +672,16 @@ int dva_mapping_merge_fill(const int64_t* pointers, const int64_t* images, const
   if ((n_views_out > 0 && !out_images) || (n_atoms_out > 0 && !out_pixels)) return DVA_ERR_INVALID;
   if ((features != nullptr) != (out_features != nullptr) || (features && F < 1)) return DVA_ERR_INVALID;
   if (((uintptr_t)pixels & 3) || ((uintptr_t)out_pixels & 3) || ((uintptr_t)workspace & 15)) return DVA_ERR_INVALID;
-  const MergeLayout L = merge_layout(n_points, n_views, n_atoms);
+  const MergeLayout L = merge_layout(workspace, n_points, n_views, n_atoms);
   if (workspace_bytes < L.total) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  const MergeIn in = {pointers, images, atom_ptr, (const uint32_t*)pixels, (const int*)(ws + L.voxel_ptr),
-                      (const int*)(ws + L.members)};
+  const MergeIn in = {pointers, images, atom_ptr, (const uint32_t*)pixels, L.voxel_ptr, L.members};
   const MergeOut out = {out_pointers, out_images, out_atom_ptr, (uint32_t*)out_pixels, out_features};
-  hipLaunchKernelGGL(merge_fill_small_kernel, dim3(grid_for(n_voxels, 1, MERGE_GRID)), dim3(DVA_WAVE), 0, s, in,
-                     features, (int)F, n_voxels, (const int*)(ws + L.view_base), (const int*)(ws + L.atom_base), out,
-                     n_views_out, n_atoms_out);
-  hipLaunchKernelGGL(merge_fill_big_kernel, dim3(grid_for(L.bigcap, 1, BIG_GRID)), dim3(BIG_THREADS), 0, s,
-                     (const u64*)(ws + L.ctr), features, (int)F, (const int*)(ws + L.view_base),
-                     (const int*)(ws + L.atom_base), (const int*)(ws + L.big_j), (const int*)(ws + L.big_na),
-                     (const int*)(ws + L.big_nv), (const int64_t*)(ws + L.big_aoff),
-                     (const int64_t*)(ws + L.big_voff), L.bigcap, (u64*)(ws + L.scratch_a), (u64*)(ws + L.scratch_v),
-                     out);
+  hipLaunchKernelGGL(merge_fill_small_kernel, dim3(capped_grid(n_voxels, 1, MERGE_GRID)), dim3(DVA_WAVE), 0, s, in,
+                     features, (int)F, n_voxels, L.view_base, L.atom_base, out, n_views_out, n_atoms_out);
+  hipLaunchKernelGGL(merge_fill_big_kernel, dim3(capped_grid(L.bigcap, 1, BIG_GRID)), dim3(BIG_THREADS), 0, s, L.ctr,
+                     features, (int)F, L.view_base, L.atom_base, L.big_j, L.big_na, L.big_nv, L.big_aoff, L.big_voff,
+                     L.bigcap, L.scratch_a, L.scratch_v, out);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }

@@ -15,13 +15,6 @@
 namespace dva {
 namespace qkv {
 
-static inline int grid_for(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b > 256 * 32) b = 256 * 32;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 __host__ __device__ __forceinline__ int chan_of(int i) {
   const int r = i & 15, h = i >> 4;
   return (r & 3) + 8 * (r >> 2) + 4 * h;
@@ -128,8 +121,8 @@ int dva_qkv_compat(const void* keys, const float* queries, const int32_t* view_p
   if (n_views == 0) return DVA_OK;
   if (!keys || !queries || !view_point || !compat || ((uintptr_t)keys & 15) || ((uintptr_t)queries & 15))
     return DVA_ERR_INVALID;
-  hipLaunchKernelGGL(qkv::compat_kernel, dim3(qkv::grid_for(n_views)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)keys,
-                     queries, view_point, compat, n_views, (int)G, scale);
+  hipLaunchKernelGGL(qkv::compat_kernel, dim3(capped_grid(n_views, 256, 256 * 32)), dim3(256), 0,
+                     (hipStream_t)stream, (const bf16_t*)keys, queries, view_point, compat, n_views, (int)G, scale);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -147,12 +140,12 @@ int dva_qkv_compat_bwd(const float* grad_compat, const void* keys, const float* 
     // query rows (dva_chain_score_stats_keys / dva_chain_bwd_layer6_keys); only dQ' is produced here
     if (grad_keys) {
       if (!queries || !view_point || ((uintptr_t)grad_keys & 15) || ((uintptr_t)queries & 15)) return DVA_ERR_INVALID;
-      hipLaunchKernelGGL(qkv::dkeys_kernel, dim3(qkv::grid_for(n_views)), dim3(256), 0, s, grad_compat, queries, view_point,
-                         (bf16_t*)grad_keys, n_views, (int)G, scale);
+      hipLaunchKernelGGL(qkv::dkeys_kernel, dim3(capped_grid(n_views, 256, 256 * 32)), dim3(256), 0, s,
+                         grad_compat, queries, view_point, (bf16_t*)grad_keys, n_views, (int)G, scale);
     }
   }
-  hipLaunchKernelGGL(qkv::dquery_kernel, dim3(qkv::grid_for(n_points * 32)), dim3(256), 0, s, grad_compat, (const bf16_t*)keys,
-                     ptr, grad_queries, n_points, (int)G, scale, (int)G);
+  hipLaunchKernelGGL(qkv::dquery_kernel, dim3(capped_grid(n_points * 32, 256, 256 * 32)), dim3(256), 0, s,
+                     grad_compat, (const bf16_t*)keys, ptr, grad_queries, n_points, (int)G, scale, (int)G);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -163,8 +156,9 @@ int dva_qkv_dquery(const float* grad_compat, int32_t ld, const void* keys, const
   if (n_views < 0 || n_points < 0 || (G != 1 && G != 2 && G != 4) || ld < G) return DVA_ERR_INVALID;
   if (n_points == 0) return DVA_OK;
   if (!ptr || !grad_queries || (n_views > 0 && (!grad_compat || !keys))) return DVA_ERR_INVALID;
-  hipLaunchKernelGGL(qkv::dquery_kernel, dim3(qkv::grid_for(n_points * 32)), dim3(256), 0, (hipStream_t)stream, grad_compat,
-                     (const bf16_t*)keys, ptr, grad_queries, n_points, (int)G, scale, (int)ld);
+  hipLaunchKernelGGL(qkv::dquery_kernel, dim3(capped_grid(n_points * 32, 256, 256 * 32)), dim3(256), 0,
+                     (hipStream_t)stream, grad_compat, (const bf16_t*)keys, ptr, grad_queries, n_points, (int)G, scale,
+                     (int)ld);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }

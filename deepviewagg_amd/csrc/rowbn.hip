@@ -318,19 +318,6 @@ static inline bool rv_ok(int C, const void* a, const void* b, const void* c) {
          (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) % 16 == 0);
 }
 
-static inline int rows_grid(int64_t R) {
-  int64_t b = (R + RB_ROWS - 1) / RB_ROWS;
-  if (b > 256 * 8) b = 256 * 8;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-static inline int elems_grid(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b > 256 * 16) b = 256 * 16;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 }  // namespace dva
 
 using namespace dva;
@@ -362,14 +349,14 @@ int dva_rowbn_stats(const void* y, const int32_t* counts, double* sums, int64_t 
     return DVA_OK;
   }
   if (dtype == DVA_F32)
-    hipLaunchKernelGGL((rowbn_stats_kernel<float>), dim3(rows_grid(R)), block, lds, (hipStream_t)stream,
-                       (const float*)y, counts, sums, R, C);
+    hipLaunchKernelGGL((rowbn_stats_kernel<float>), dim3(capped_grid(R, RB_ROWS, 256 * 8)), block, lds,
+                       (hipStream_t)stream, (const float*)y, counts, sums, R, C);
   else if (dtype == DVA_F16)
-    hipLaunchKernelGGL((rowbn_stats_kernel<f16_t>), dim3(rows_grid(R)), block, lds, (hipStream_t)stream,
-                       (const f16_t*)y, counts, sums, R, C);
+    hipLaunchKernelGGL((rowbn_stats_kernel<f16_t>), dim3(capped_grid(R, RB_ROWS, 256 * 8)), block, lds,
+                       (hipStream_t)stream, (const f16_t*)y, counts, sums, R, C);
   else
-    hipLaunchKernelGGL((rowbn_stats_kernel<bf16_t>), dim3(rows_grid(R)), block, lds, (hipStream_t)stream,
-                       (const bf16_t*)y, counts, sums, R, C);
+    hipLaunchKernelGGL((rowbn_stats_kernel<bf16_t>), dim3(capped_grid(R, RB_ROWS, 256 * 8)), block, lds,
+                       (hipStream_t)stream, (const bf16_t*)y, counts, sums, R, C);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -381,7 +368,7 @@ int dva_rowbn_apply(const void* y, const float* bn, void* out, int64_t R, int32_
   if (R == 0) return DVA_OK;
   if (!y || !bn || !out) return DVA_ERR_INVALID;
   if (dtype == DVA_F32 ? rv_ok<float>(C, y, out, out) : rv_ok<bf16_t>(C, y, out, out)) {
-    const dim3 vg(elems_grid(R * (C / (dtype == DVA_F32 ? 4 : 8))));
+    const dim3 vg(capped_grid(R * (C / (dtype == DVA_F32 ? 4 : 8)), 256, 256 * 16));
     if (dtype == DVA_F32)
       hipLaunchKernelGGL((rowbn_apply_vec_kernel<float, 0>), vg, dim3(256), 0, (hipStream_t)stream, (const float*)y,
                          (const float*)nullptr, (const int32_t*)nullptr, bn, (const float*)nullptr, (float*)out, R,
@@ -397,7 +384,7 @@ int dva_rowbn_apply(const void* y, const float* bn, void* out, int64_t R, int32_
     DVA_CHECK_LAUNCH();
     return DVA_OK;
   }
-  const dim3 grid(elems_grid(R * C));
+  const dim3 grid(capped_grid(R * C, 256, 256 * 16));
   if (dtype == DVA_F32)
     hipLaunchKernelGGL((rowbn_apply_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream,
                        (const float*)y, bn, (float*)out, R, C, slope);
@@ -436,16 +423,14 @@ int dva_rowbn_bwd_stats(const void* grad_out, const void* y, const float* bn, do
     return DVA_OK;
   }
   if (dtype == DVA_F32)
-    hipLaunchKernelGGL((rowbn_bwd_stats_kernel<float>), dim3(rows_grid(R)), block, lds,
+    hipLaunchKernelGGL((rowbn_bwd_stats_kernel<float>), dim3(capped_grid(R, RB_ROWS, 256 * 8)), block, lds,
                        (hipStream_t)stream, (const float*)grad_out, (const float*)y, bn, sums, R, C, slope);
   else if (dtype == DVA_F16)
-    hipLaunchKernelGGL((rowbn_bwd_stats_kernel<f16_t>), dim3(rows_grid(R)), block, lds,
-                       (hipStream_t)stream, (const f16_t*)grad_out, (const f16_t*)y, bn, sums, R, C,
-                       slope);
+    hipLaunchKernelGGL((rowbn_bwd_stats_kernel<f16_t>), dim3(capped_grid(R, RB_ROWS, 256 * 8)), block, lds,
+                       (hipStream_t)stream, (const f16_t*)grad_out, (const f16_t*)y, bn, sums, R, C, slope);
   else
-    hipLaunchKernelGGL((rowbn_bwd_stats_kernel<bf16_t>), dim3(rows_grid(R)), block, lds,
-                       (hipStream_t)stream, (const bf16_t*)grad_out, (const bf16_t*)y, bn, sums, R, C,
-                       slope);
+    hipLaunchKernelGGL((rowbn_bwd_stats_kernel<bf16_t>), dim3(capped_grid(R, RB_ROWS, 256 * 8)), block, lds,
+                       (hipStream_t)stream, (const bf16_t*)grad_out, (const bf16_t*)y, bn, sums, R, C, slope);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -458,7 +443,7 @@ int dva_rowbn_bwd_apply(const void* grad_out, const void* y, const int32_t* coun
   if (R == 0) return DVA_OK;
   if (!grad_out || !y || !bn || !sm || !grad_y) return DVA_ERR_INVALID;
   if (dtype == DVA_F32 ? rv_ok<float>(C, y, grad_out, grad_y) : rv_ok<bf16_t>(C, y, grad_out, grad_y)) {
-    const dim3 vg(elems_grid(R * (C / (dtype == DVA_F32 ? 4 : 8))));
+    const dim3 vg(capped_grid(R * (C / (dtype == DVA_F32 ? 4 : 8)), 256, 256 * 16));
     if (dtype == DVA_F32)
       hipLaunchKernelGGL((rowbn_apply_vec_kernel<float, 1>), vg, dim3(256), 0, (hipStream_t)stream, (const float*)y,
                          (const float*)grad_out, counts, bn, sm, (float*)grad_y, R, C, slope);
@@ -471,7 +456,7 @@ int dva_rowbn_bwd_apply(const void* grad_out, const void* y, const int32_t* coun
     DVA_CHECK_LAUNCH();
     return DVA_OK;
   }
-  const dim3 grid(elems_grid(R * C));
+  const dim3 grid(capped_grid(R * C, 256, 256 * 16));
   if (dtype == DVA_F32)
     hipLaunchKernelGGL((rowbn_bwd_apply_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream,
                        (const float*)grad_out, (const float*)y, counts, bn, sm, (float*)grad_y, R, C, slope);

@@ -23,7 +23,6 @@ constexpr int LOVASZ_ITEMS = DVA_LOVASZ_TILE / SEG_THREADS;
 static_assert(LOVASZ_ITEMS * SEG_THREADS == DVA_LOVASZ_TILE, "tile = threads x items");
 constexpr int SEG_MAX_C = 64;
 
-static inline size_t seg_align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // sum of v over the block's 256 threads, in a fixed order; every thread gets the result.  red: LDS [256]
 template <typename V>
@@ -175,7 +174,11 @@ static int lovasz_class_bits(int C) {
 }
 
 struct LovaszLayout {
-  size_t off_k0, off_k1, off_v0, off_v1, off_cnt, off_tile, off_part, off_temp, temp_bytes, total;
+  uint64_t *k0, *k1;
+  uint32_t *v0, *v1, *cnt, *tile_cnt;
+  double* tile_loss;
+  char* temp;
+  size_t temp_bytes, total;
   int64_t tiles;
 };
 
@@ -371,33 +374,25 @@ static hipError_t lovasz_sort(void* temp, size_t& tmp, rocprim::double_buffer<ui
   return rocprim::radix_sort_pairs(temp, tmp, k, v, n, LV_LOW_BITS, LV_CLASS_SHIFT + lovasz_class_bits(C), s);
 }
 
-static int lovasz_layout(int64_t P, int C, LovaszLayout* L) {
+static int lovasz_layout(void* ws, int64_t P, int C, LovaszLayout* L) {
   const size_t N = (size_t)P * C;
   size_t tmp = 0;
   rocprim::double_buffer<uint64_t> k(nullptr, nullptr);
   rocprim::double_buffer<uint32_t> v(nullptr, nullptr);
   if (lovasz_sort(nullptr, tmp, k, v, N, C, (hipStream_t)0) != hipSuccess) return DVA_ERR_LAUNCH;
   L->tiles = (P + DVA_LOVASZ_TILE - 1) / DVA_LOVASZ_TILE;
-  size_t off = 0;
-  L->off_k0 = off;   off += seg_align256(N * 8);
-  L->off_k1 = off;   off += seg_align256(N * 8);
-  L->off_v0 = off;   off += seg_align256(N * 4);
-  L->off_v1 = off;   off += seg_align256(N * 4);
-  L->off_cnt = off;  off += seg_align256((size_t)(C + 1) * 4);
-  L->off_tile = off; off += seg_align256((size_t)C * L->tiles * 4);
-  L->off_part = off; off += seg_align256((size_t)C * L->tiles * 8);
-  L->off_temp = off;
+  Carver c(ws);
+  L->k0 = c.take<uint64_t>(N);
+  L->k1 = c.take<uint64_t>(N);
+  L->v0 = c.take<uint32_t>(N);
+  L->v1 = c.take<uint32_t>(N);
+  L->cnt = c.take<uint32_t>((size_t)(C + 1));
+  L->tile_cnt = c.take<uint32_t>((size_t)C * L->tiles);
+  L->tile_loss = c.take<double>((size_t)C * L->tiles);
   L->temp_bytes = tmp;
-  off += seg_align256(tmp);
-  L->total = off;
+  L->temp = c.take<char>(tmp);
+  L->total = c.used();
   return DVA_OK;
-}
-
-static inline int seg_grid(int64_t n, int cap) {
-  int64_t b = (n + SEG_THREADS - 1) / SEG_THREADS;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
 }
 
 // 1 <= C <= 64 and P * C < 2^31
@@ -429,7 +424,7 @@ int dva_seg_logsoftmax_nll_fwd(const void* logits, int32_t dtype, const int64_t*
   if (P > 0 && (!logits || !labels || !log_probs)) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   double* partial = (double*)workspace;
-  const int grid = seg_grid(P, SEG_MAX_BLOCKS);
+  const int grid = capped_grid(P, SEG_THREADS, SEG_MAX_BLOCKS);
   if (dtype == DVA_F32)
     hipLaunchKernelGGL(seg_nll_fwd_kernel<float>, dim3(grid), dim3(SEG_THREADS), 0, s, (const float*)logits, labels,
                        weight, ignore_index, P, (int)C, log_probs, partial);
@@ -455,7 +450,7 @@ int dva_seg_logsoftmax_nll_bwd(const float* log_probs, const int64_t* labels, co
   if (P == 0) return DVA_OK;
   if (!log_probs || !labels || !grad_logits) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
-  const int grid = seg_grid(P, 1 << 16);
+  const int grid = capped_grid(P, SEG_THREADS, 1 << 16);
   if (dtype == DVA_F32)
     hipLaunchKernelGGL(seg_nll_bwd_kernel<float>, dim3(grid), dim3(SEG_THREADS), 0, s, log_probs, labels, weight, numden,
                        grad_loss, grad_log_probs, ignore_index, P, (int)C, (float*)grad_logits);
@@ -478,7 +473,7 @@ int dva_confusion_counts(const void* outputs, int32_t dtype, const int64_t* labe
   if (P == 0) return DVA_OK;
   if (!outputs || !labels) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
-  const int grid = seg_grid(P, 2048);
+  const int grid = capped_grid(P, SEG_THREADS, 2048);
   if (dtype == DVA_F32)
     hipLaunchKernelGGL(confusion_kernel<float>, dim3(grid), dim3(SEG_THREADS), 0, s, (const float*)outputs, labels,
                        ignore_index, P, (int)C, (long long*)counts, (long long*)n_bad);
@@ -497,7 +492,7 @@ int64_t dva_lovasz_workspace_bytes(int64_t P, int32_t C) {
   if (rc) return rc;
   if (P == 0) return 256;
   LovaszLayout L;
-  rc = lovasz_layout(P, C, &L);
+  rc = lovasz_layout(nullptr, P, C, &L);
   if (rc) return rc;
   return (int64_t)L.total;
 }
@@ -515,31 +510,28 @@ int dva_lovasz_softmax(const float* probas, const int64_t* labels, int64_t P, in
     return DVA_OK;
   }
   LovaszLayout L;
-  rc = lovasz_layout(P, C, &L);
+  rc = lovasz_layout(workspace, P, C, &L);
   if (rc) return rc;
   if ((int64_t)L.total > workspace_bytes) return DVA_ERR_INVALID;
   const int64_t N = P * C;
-  char* ws = (char*)workspace;
-  uint32_t* cnt = (uint32_t*)(ws + L.off_cnt);
-  uint32_t* tile_cnt = (uint32_t*)(ws + L.off_tile);
-  double* tile_loss = (double*)(ws + L.off_part);
-  rocprim::double_buffer<uint64_t> keys((uint64_t*)(ws + L.off_k0), (uint64_t*)(ws + L.off_k1));
-  rocprim::double_buffer<uint32_t> vals((uint32_t*)(ws + L.off_v0), (uint32_t*)(ws + L.off_v1));
-  if (hipMemsetAsync(cnt, 0, (size_t)(C + 1) * 4, s) != hipSuccess) return DVA_ERR_LAUNCH;
+  rocprim::double_buffer<uint64_t> keys(L.k0, L.k1);
+  rocprim::double_buffer<uint32_t> vals(L.v0, L.v1);
+  if (hipMemsetAsync(L.cnt, 0, (size_t)(C + 1) * 4, s) != hipSuccess) return DVA_ERR_LAUNCH;
   if (hipMemsetAsync(grad, 0, (size_t)N * 4, s) != hipSuccess) return DVA_ERR_LAUNCH;
-  hipLaunchKernelGGL(lovasz_keys_kernel, dim3(seg_grid(N, 8192)), dim3(SEG_THREADS), 0, s, probas, labels,
-                     ignore_index, (int)use_ignore, class_mask, P, (int)C, keys.current(), vals.current(), cnt);
+  hipLaunchKernelGGL(lovasz_keys_kernel, dim3(capped_grid(N, SEG_THREADS, 8192)), dim3(SEG_THREADS), 0, s, probas,
+                     labels, ignore_index, (int)use_ignore, class_mask, P, (int)C, keys.current(), vals.current(),
+                     L.cnt);
   size_t tmp = L.temp_bytes;
-  if (lovasz_sort(ws + L.off_temp, tmp, keys, vals, (size_t)N, C, s) != hipSuccess) return DVA_ERR_LAUNCH;
+  if (lovasz_sort(L.temp, tmp, keys, vals, (size_t)N, C, s) != hipSuccess) return DVA_ERR_LAUNCH;
   const dim3 grid((unsigned)L.tiles, (unsigned)C);
-  hipLaunchKernelGGL(lovasz_count_kernel, grid, dim3(SEG_THREADS), 0, s, keys.current(), cnt, class_mask,
-                     (int)present_only, (int)C, L.tiles, tile_cnt);
-  hipLaunchKernelGGL(lovasz_prefix_kernel, dim3((unsigned)C), dim3(SEG_THREADS), 0, s, cnt, class_mask,
-                     (int)present_only, (int)C, L.tiles, tile_cnt);
-  hipLaunchKernelGGL(lovasz_scan_kernel, grid, dim3(SEG_THREADS), 0, s, keys.current(), vals.current(), cnt,
-                     class_mask, (int)present_only, (int)C, L.tiles, tile_cnt, tile_loss, grad);
-  hipLaunchKernelGGL(lovasz_finish_kernel, dim3(1), dim3(SEG_THREADS), 0, s, cnt, class_mask, (int)present_only, (int)C,
-                     L.tiles, tile_loss, loss);
+  hipLaunchKernelGGL(lovasz_count_kernel, grid, dim3(SEG_THREADS), 0, s, keys.current(), L.cnt, class_mask,
+                     (int)present_only, (int)C, L.tiles, L.tile_cnt);
+  hipLaunchKernelGGL(lovasz_prefix_kernel, dim3((unsigned)C), dim3(SEG_THREADS), 0, s, L.cnt, class_mask,
+                     (int)present_only, (int)C, L.tiles, L.tile_cnt);
+  hipLaunchKernelGGL(lovasz_scan_kernel, grid, dim3(SEG_THREADS), 0, s, keys.current(), vals.current(), L.cnt,
+                     class_mask, (int)present_only, (int)C, L.tiles, L.tile_cnt, L.tile_loss, grad);
+  hipLaunchKernelGGL(lovasz_finish_kernel, dim3(1), dim3(SEG_THREADS), 0, s, L.cnt, class_mask, (int)present_only,
+                     (int)C, L.tiles, L.tile_loss, loss);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }

@@ -271,19 +271,13 @@ static inline bool vec_ok(const void* a, const void* b, int C) {
   return C % SVec<T>::N == 0 && ((uintptr_t)a % 16 == 0) && ((uintptr_t)b % 16 == 0);
 }
 
-static inline int grid_for(int64_t total) {
-  int64_t b = (total + 255) / 256;
-  const int64_t cap = 256 * 32;  // 256 CUs x 32 blocks, grid-stride beyond
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
-}
+constexpr int64_t CSR_GRID_CAP = 256 * 32;  // 256 CUs x 32 blocks, grid-stride beyond
 
 template <typename T>
 static int launch_segment_fwd(const void* src, const int64_t* ptr, void* out, int32_t* arg,
                               int64_t n, int C, int reduce, hipStream_t s) {
   const bool vec = vec_ok<T>(src, out, C);
-  const int grid = grid_for(n * (int64_t)(vec ? C / SVec<T>::N : C));
+  const int grid = capped_grid(n * (int64_t)(vec ? C / SVec<T>::N : C), 256, CSR_GRID_CAP);
 #define DVA_L(R)                                                                                        \
   do {                                                                                                  \
     if (vec)                                                                                            \
@@ -308,7 +302,7 @@ template <typename T>
 static int launch_segment_bwd(const void* gout, const int64_t* ptr, const int32_t* arg, void* gsrc,
                               int64_t n, int C, int reduce, hipStream_t s) {
   const bool vec = vec_ok<T>(gout, gsrc, C);
-  const int grid = grid_for(n * (int64_t)(vec ? C / SVec<T>::N : C));
+  const int grid = capped_grid(n * (int64_t)(vec ? C / SVec<T>::N : C), 256, CSR_GRID_CAP);
 #define DVA_L(R)                                                                                         \
   do {                                                                                                   \
     if (vec)                                                                                             \
@@ -399,12 +393,12 @@ int dva_gather_csr(const void* src, const int64_t* ptr, void* out, int64_t n_gro
   if (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16) return DVA_ERR_INVALID;
   if (row_bytes % 16 == 0 && ((uintptr_t)src % 16 == 0) && ((uintptr_t)out % 16 == 0)) {
     const int u = (int)(row_bytes / 16);
-    hipLaunchKernelGGL((gather_csr_kernel<uint4>), dim3(grid_for(n_groups * (int64_t)u)), dim3(256), 0,
-                       (hipStream_t)stream, (const uint4*)src, ptr, (uint4*)out, n_groups, u);
+    hipLaunchKernelGGL((gather_csr_kernel<uint4>), dim3(capped_grid(n_groups * (int64_t)u, 256, CSR_GRID_CAP)),
+                       dim3(256), 0, (hipStream_t)stream, (const uint4*)src, ptr, (uint4*)out, n_groups, u);
     DVA_CHECK_LAUNCH();
     return DVA_OK;
   }
-  const int grid = grid_for(n_groups * (int64_t)C);
+  const int grid = capped_grid(n_groups * (int64_t)C, 256, CSR_GRID_CAP);
   if (dtype == DVA_F32)
     hipLaunchKernelGGL((gather_csr_kernel<float>), dim3(grid), dim3(256), 0, (hipStream_t)stream,
                        (const float*)src, ptr, (float*)out, n_groups, C);
@@ -420,7 +414,7 @@ int dva_segment_softmax_csr_fwd(const float* src, const int64_t* ptr, float* out
                                 void* stream) {
   if (n_groups < 0 || G < 0 || !ptr) return DVA_ERR_INVALID;
   if (n_groups == 0 || G == 0) return DVA_OK;
-  const int grid = grid_for(n_groups * (int64_t)G);
+  const int grid = capped_grid(n_groups * (int64_t)G, 256, CSR_GRID_CAP);
   hipLaunchKernelGGL(segment_softmax_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, src,
                      ptr, out, n_groups, G, scaling, eps);
   DVA_CHECK_LAUNCH();
@@ -432,7 +426,7 @@ int dva_segment_softmax_csr_bwd(const float* grad_out, const float* out, const i
                                 void* stream) {
   if (n_groups < 0 || G < 0 || !ptr) return DVA_ERR_INVALID;
   if (n_groups == 0 || G == 0) return DVA_OK;
-  const int grid = grid_for(n_groups * (int64_t)G);
+  const int grid = capped_grid(n_groups * (int64_t)G, 256, CSR_GRID_CAP);
   hipLaunchKernelGGL(segment_softmax_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream,
                      grad_out, out, ptr, grad_src, n_groups, G, scaling);
   DVA_CHECK_LAUNCH();

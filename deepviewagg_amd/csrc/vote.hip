@@ -25,13 +25,6 @@ constexpr int VOTE_ROWS = VOTE_THREADS / VOTE_GROUP;      // queries per block a
 constexpr int VOTE_PER_LANE = VOTE_MAX_C / VOTE_GROUP;    // classes per lane
 static_assert(DVA_WAVE % VOTE_GROUP == 0, "a query's lanes stay inside one wavefront");
 
-static inline int vote_grid(int64_t n, int per_block, int cap) {
-  int64_t b = (n + per_block - 1) / per_block;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // vote accumulation
 // ---------------------------------------------------------------------------------------------------------------
@@ -197,7 +190,7 @@ extern "C" {
 int64_t dva_vote_workspace_bytes(int64_t N) {
   if (N < 0) return DVA_ERR_INVALID;
   if (N > 0x7fffffffLL) return DVA_ERR_UNSUPPORTED;
-  const int64_t bytes = (N * 4 + 255) & ~(int64_t)255;
+  const int64_t bytes = (int64_t)align_up((size_t)N * 4);
   return bytes < 256 ? 256 : bytes;
 }
 
@@ -211,8 +204,8 @@ int dva_vote_add(float* votes, int32_t* counts, int64_t N, int32_t C, const int6
   if (P == 0) return DVA_OK;
   if (!ids || !outputs) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
-  const int rows_grid = vote_grid(P, VOTE_THREADS, 1 << 16);
-  const int elts_grid = vote_grid(P * C, VOTE_THREADS, 1 << 16);
+  const int rows_grid = capped_grid(P, VOTE_THREADS, 1 << 16);
+  const int elts_grid = capped_grid(P * C, VOTE_THREADS, 1 << 16);
   hipLaunchKernelGGL(vote_claim_kernel, dim3(rows_grid), dim3(VOTE_THREADS), 0, s, ids, P, N, slots,
                      (long long*)n_bad);
   if (dtype == DVA_F32)
@@ -242,9 +235,9 @@ int dva_knn_interpolate(const float* x, int64_t M, int32_t C, const int32_t* nei
   if (!x || !neighbors || !dist2) return DVA_ERR_INVALID;
   if (counts && !labels) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(knn_interpolate_kernel, dim3(vote_grid(n, VOTE_ROWS, 2048)), dim3(VOTE_THREADS), 0, s, x, M, (int)C,
-                     neighbors, dist2, n, (int)k, own, y, (long long*)pred, labels, ignore_index, (long long*)counts,
-                     (long long*)n_bad);
+  hipLaunchKernelGGL(knn_interpolate_kernel, dim3(capped_grid(n, VOTE_ROWS, 2048)), dim3(VOTE_THREADS), 0, s, x, M,
+                     (int)C, neighbors, dist2, n, (int)k, own, y, (long long*)pred, labels, ignore_index,
+                     (long long*)counts, (long long*)n_bad);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }

@@ -116,13 +116,6 @@ static inline uint64_t table_capacity(int64_t n_out) {
   while (cap < 2 * (uint64_t)n_out) cap <<= 1;
   return cap;
 }
-static inline int grid_of(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b > 8192) b = 8192;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 }  // namespace dva
 
 using namespace dva;
@@ -150,10 +143,10 @@ int dva_voxel_parent_index(const int32_t* in_coords, int64_t n_in, const int32_t
   int32_t* table = (int32_t*)workspace;
   if (hipMemsetAsync(table, 0xff, cap * sizeof(int32_t), s) != hipSuccess) return DVA_ERR_LAUNCH;
   if (n_out > 0)
-    hipLaunchKernelGGL(voxel_insert_kernel, dim3(grid_of(n_out)), dim3(256), 0, s, (const int4*)out_coords,
-                       n_out, table, (uint32_t)(cap - 1));
-  hipLaunchKernelGGL(voxel_query_kernel, dim3(grid_of(n_in)), dim3(256), 0, s, (const int4*)in_coords, n_in,
-                     (const int4*)out_coords, table, (uint32_t)(cap - 1), stride_out, batch_col, idx);
+    hipLaunchKernelGGL(voxel_insert_kernel, dim3(capped_grid(n_out, 256, 8192)), dim3(256), 0, s,
+                       (const int4*)out_coords, n_out, table, (uint32_t)(cap - 1));
+  hipLaunchKernelGGL(voxel_query_kernel, dim3(capped_grid(n_in, 256, 8192)), dim3(256), 0, s, (const int4*)in_coords,
+                     n_in, (const int4*)out_coords, table, (uint32_t)(cap - 1), stride_out, batch_col, idx);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -173,9 +166,9 @@ int dva_voxel_kernel_map(const int32_t* src_coords, int64_t n_src, const int32_t
   int32_t* table = (int32_t*)workspace;
   if (hipMemsetAsync(table, 0xff, cap * sizeof(int32_t), s) != hipSuccess) return DVA_ERR_LAUNCH;
   if (n_src > 0)
-    hipLaunchKernelGGL(voxel_insert_kernel, dim3(grid_of(n_src)), dim3(256), 0, s, (const int4*)src_coords,
-                       n_src, table, (uint32_t)(cap - 1));
-  hipLaunchKernelGGL(voxel_kernel_map_kernel, dim3(grid_of(n_dst * K)), dim3(256), 0, s,
+    hipLaunchKernelGGL(voxel_insert_kernel, dim3(capped_grid(n_src, 256, 8192)), dim3(256), 0, s,
+                       (const int4*)src_coords, n_src, table, (uint32_t)(cap - 1));
+  hipLaunchKernelGGL(voxel_kernel_map_kernel, dim3(capped_grid(n_dst * K, 256, 8192)), dim3(256), 0, s,
                      (const int4*)src_coords, (const int4*)dst_coords, n_dst, offsets, (int)K, table,
                      (uint32_t)(cap - 1), nbr);
   DVA_CHECK_LAUNCH();

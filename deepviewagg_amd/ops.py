@@ -671,10 +671,7 @@ def _legacy_row_plan(row_idx, n_rows, with_counts):
     perm = torch.empty(V, dtype=torch.int32, device=dev)
     row_ptr = torch.empty(n_rows + 1, dtype=torch.int32, device=dev)
     counts = torch.empty(n_rows, dtype=torch.int32, device=dev) if with_counts else None
-    nbytes = lib.dva_row_plan_workspace_bytes(V, n_rows)
-    if nbytes < 0:
-        raise _lib.DvaError("dva_row_plan_workspace_bytes", int(nbytes))
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    ws, nbytes = _lib.workspace("dva_row_plan_workspace_bytes", dev, V, n_rows)
     with _timed("row_plan", V * 16):
         check(lib.dva_row_plan(ptr(row_idx), V, n_rows, ptr(perm), ptr(row_ptr), ptr(counts), ptr(ws),
                                int(nbytes), stream_of(row_idx)), "dva_row_plan")
@@ -1485,10 +1482,7 @@ def voxel_parent_index(in_coords, out_coords, stride_out, batch_col=3):
     oc = out_coords.to(torch.int32).contiguous()
     n_in, n_out = ic.shape[0], oc.shape[0]
     idx = torch.empty(n_in, dtype=torch.int64, device=ic.device)
-    nbytes = lib.dva_voxel_parent_workspace_bytes(n_out)
-    if nbytes < 0:
-        raise _lib.DvaError("dva_voxel_parent_workspace_bytes", int(nbytes))
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=ic.device)
+    ws, nbytes = _lib.workspace("dva_voxel_parent_workspace_bytes", ic.device, n_out)
     with _timed("voxel_parent_index", n_in * 24 + n_out * 24):
         check(lib.dva_voxel_parent_index(ptr(ic), n_in, ptr(oc), n_out, int(stride_out), int(batch_col), ptr(idx),
                                          ptr(ws), int(nbytes), stream_of(ic)), "dva_voxel_parent_index")
@@ -1532,11 +1526,12 @@ def merge_mapping(pointers, images, atom_ptr, pixels, features, idx):
         raise ValueError(f"ops.merge_mapping: features must be [{v}, F] or [{v}], got {tuple(features.shape)}")
     if idx.shape[0] != n:
         return pointers, images, atom_ptr, pixels, features, False
-    nbytes = lib.dva_mapping_merge_workspace_bytes(n, v, p)
-    if nbytes == -2:
-        raise _merge_unsupported(f"{n} points, {v} views, {p} atoms")
-    if nbytes < 0:
-        raise _lib.DvaError(f"dva_mapping_merge_workspace_bytes({n}, {v}, {p})", int(nbytes))
+    try:
+        ws, nbytes = _lib.workspace("dva_mapping_merge_workspace_bytes", dev, n, v, p)
+    except _lib.DvaError as e:
+        if e.code != -2:
+            raise
+        raise _merge_unsupported(f"{n} points, {v} views, {p} atoms") from None
     pointers, images, atom_ptr = pointers.contiguous(), images.contiguous(), atom_ptr.contiguous()
     pixels, idx = pixels.contiguous(), idx.contiguous()
     feat = None
@@ -1544,7 +1539,6 @@ def merge_mapping(pointers, images, atom_ptr, pixels, features, idx):
         feat = features.detach().float().reshape(v, -1).contiguous()
     f = 0 if feat is None else feat.shape[1]
     feat_in = feat if f > 0 else None
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
     sizes = torch.empty(4, dtype=torch.int64, device=dev)
     s = stream_of(pointers)
     read = n * 8 + v * 16 + p * 4
@@ -1584,10 +1578,7 @@ def voxel_kernel_map(src_coords, dst_coords, offsets):
     off = torch.as_tensor(offsets, dtype=torch.int32).reshape(-1, 3).to(sc.device).contiguous()
     K, n_src, n_dst = off.shape[0], sc.shape[0], dc.shape[0]
     nbr = torch.empty((K, n_dst), dtype=torch.int32, device=sc.device)
-    nbytes = lib.dva_voxel_parent_workspace_bytes(n_src)
-    if nbytes < 0:
-        raise _lib.DvaError("dva_voxel_parent_workspace_bytes", int(nbytes))
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=sc.device)
+    ws, nbytes = _lib.workspace("dva_voxel_parent_workspace_bytes", sc.device, n_src)
     with _timed("voxel_kernel_map", n_src * 24 + K * n_dst * 24):
         check(lib.dva_voxel_kernel_map(ptr(sc), n_src, ptr(dc), n_dst, ptr(off), K, ptr(nbr), ptr(ws), int(nbytes),
                                        stream_of(sc)), "dva_voxel_kernel_map")
@@ -1622,8 +1613,7 @@ def _sparse_conv_apply(x, nbr, W, bias, n_dst, mode):
     bias = None if bias is None else bias.detach().float().contiguous()
     out = torch.empty((n_dst, cout_p), dtype=x.dtype, device=x.device)
     code = dtype_code(x)
-    nbytes = int(lib.dva_sparse_conv_workspace_bytes(K, cin_p, cout_p, code))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    ws, nbytes = _lib.workspace("dva_sparse_conv_workspace_bytes", x.device, K, cin_p, cout_p, code)
     s = x.element_size()
     with _timed(f"sparse_conv_apply{SPARSE_CONV_TIMER_SHAPES and f'[{K}x{cin_p}->{cout_p}@{n_dst}]' or ''}",
                 n_dst * (K * 4 + cout_p * s) + x.shape[0] * cin_p * s):
@@ -1725,10 +1715,7 @@ def knn(xyz, k, cell=None):
     if cell is None:
         cell = _knn_default_cell(lo, hi, ext, n, k)
     cell = max(float(cell), ext / (1 << 19), 1e-12)
-    nbytes = lib.dva_knn_workspace_bytes(n)
-    if nbytes < 0:
-        raise _lib.DvaError("dva_knn_workspace_bytes", int(nbytes))
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=xyz.device)
+    ws, nbytes = _lib.workspace("dva_knn_workspace_bytes", xyz.device, n)
     done = torch.zeros(n, dtype=torch.uint8, device=xyz.device)
     # levels: a query that is not provably complete within 2 shells of cells (sparse region, outlier) is
     # retried on a 4x coarser grid; the last level covers the whole cloud
@@ -1772,10 +1759,7 @@ def knn_query(query, search, k, cell=None):
     if cell is None:
         cell = _knn_default_cell(s_lo, s_hi, float((s_hi - s_lo).max()), m, k)
     cell = max(float(cell), ext / (1 << 19), 1e-12)
-    nbytes = lib.dva_knn_query_workspace_bytes(n, m)
-    if nbytes < 0:
-        raise _lib.DvaError("dva_knn_query_workspace_bytes", int(nbytes))
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=query.device)
+    ws, nbytes = _lib.workspace("dva_knn_query_workspace_bytes", query.device, n, m)
     done = torch.zeros(n, dtype=torch.uint8, device=query.device)
     # the level loop of knn: queries not provably complete within 2 shells are retried on a 4x coarser grid
     shells = 2
@@ -1845,13 +1829,6 @@ class GridClusters:
         return f"GridClusters(num_points={self.num_points}, num_voxels={self.num_voxels})"
 
 
-def _grid_workspace(lib, n, row_bytes, device):
-    nbytes = lib.dva_grid_workspace_bytes(n, row_bytes)
-    if nbytes < 0:
-        raise _lib.DvaError(f"dva_grid_workspace_bytes({n}, {row_bytes})", int(nbytes))
-    return torch.empty(int(nbytes), dtype=torch.uint8, device=device), int(nbytes)
-
-
 def grid_cluster(pos, size, batch=None, rank=None):
     """Voxel clustering of ``pos`` [N, 3] (fp32 or fp64) on a grid of ``size``: the reference's
     ``coords = round(pos / size)`` (division correctly rounded in the dtype of ``pos``, ties to even), torch_cluster's
@@ -1884,7 +1861,7 @@ def grid_cluster(pos, size, batch=None, rank=None):
         rank = rank.to(torch.int64).reshape(-1).contiguous()
         if rank.shape[0] != n:
             raise ValueError(f"ops.grid_cluster: rank has {rank.shape[0]} entries for {n} points")
-    ws, nbytes = _grid_workspace(lib, n, 0, dev)
+    ws, nbytes = _lib.workspace("dva_grid_workspace_bytes", dev, n, 0)
     coords = torch.empty((n, 3), dtype=torch.int32, device=dev)
     stats = torch.empty(9, dtype=torch.int64, device=dev)
     s = stream_of(pos)
@@ -1953,7 +1930,7 @@ def grid_mean(src, clusters):
     if C == 0:
         return out
     x = src.contiguous()
-    ws, nbytes = _grid_workspace(lib, n, C * x.element_size(), src.device)
+    ws, nbytes = _lib.workspace("dva_grid_workspace_bytes", src.device, n, C * x.element_size())
     with _timed("grid_mean", 2 * n * C * x.element_size() + n * 8 + m * C * x.element_size()):
         check(lib.dva_grid_mean(ptr(x), _GRID_DTYPES[src.dtype], n, C, ptr(clusters.order), ptr(clusters.offsets), m,
                                 ptr(out), ptr(ws), nbytes, stream_of(x)), "dva_grid_mean")
@@ -1980,7 +1957,7 @@ def grid_majority(labels, clusters):
     if end_bit > 63:
         raise ValueError(f"ops.grid_majority: {m} voxels x {n_labels} labels do not fit a 63-bit key")
     out = torch.empty(m, dtype=torch.int64, device=lab.device)
-    ws, nbytes = _grid_workspace(lib, n, 0, lab.device)
+    ws, nbytes = _lib.workspace("dva_grid_workspace_bytes", lab.device, n, 0)
     with _timed("grid_majority", n * 56):
         check(lib.dva_grid_majority(ptr(lab), n, ptr(clusters.cluster), m, lo, n_labels, end_bit, ptr(out), ptr(ws),
                                     nbytes, stream_of(lab)), "dva_grid_majority")
@@ -2082,10 +2059,7 @@ def radius_query(pos, centres, radius, dims=3):
         nb = min(step, B - b0)
         c = cen[b0:b0 + nb]
         rr = None if radii is None else radii[b0:b0 + nb]
-        nbytes = lib.dva_radius_query_workspace_bytes(n, nb)
-        if nbytes < 0:
-            raise _lib.DvaError(f"dva_radius_query_workspace_bytes({n}, {nb})", int(nbytes))
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+        ws, nbytes = _lib.workspace("dva_radius_query_workspace_bytes", dev, n, nb)
         ptr_b = torch.empty(nb + 1, dtype=torch.int64, device=dev)
         rad = 0.0 if radii is not None else radius
         with _timed("radius_count", n * 12 + tiles * nb * 12):
@@ -2144,10 +2118,7 @@ def elastic_smooth(noise):
     lib = _lib.load()
     vol = _elastic_volume(noise, "elastic_smooth: noise")
     dx, dy, dz = (int(d) for d in vol.shape[:3])
-    nbytes = lib.dva_elastic_workspace_bytes(dx, dy, dz)
-    if nbytes < 0:
-        raise _lib.DvaError(f"dva_elastic_workspace_bytes({dx}, {dy}, {dz})", int(nbytes))
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=vol.device)
+    ws, nbytes = _lib.workspace("dva_elastic_workspace_bytes", vol.device, dx, dy, dz)
     out = torch.empty_like(vol)
     with _timed("elastic_smooth", 6 * 2 * vol.numel() * 4):
         check(lib.dva_elastic_smooth(ptr(vol), dx, dy, dz, ptr(out), ptr(ws), int(nbytes), stream_of(vol)),
@@ -2196,8 +2167,7 @@ def minmax3(pos):
     p = _elastic_pos(pos, "minmax3")
     if p.shape[0] == 0:
         raise ValueError("zero-size array to reduction operation minimum which has no identity")
-    nbytes = int(lib.dva_minmax3_workspace_bytes())
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=p.device)
+    ws, nbytes = _lib.workspace("dva_minmax3_workspace_bytes", p.device)
     out = torch.empty(6, dtype=torch.float32, device=p.device)
     with _timed("minmax3", p.numel() * 4):
         check(lib.dva_minmax3_f32(ptr(p), p.shape[0], ptr(out), ptr(ws), nbytes, stream_of(p)), "dva_minmax3_f32")
@@ -2337,8 +2307,7 @@ def image_tail(x, jitter=(), flip=False, to_float=False, mean=None, std=None):
         return out
     ws, ws_bytes = None, 0
     if "contrast" in names:
-        ws_bytes = int(lib.dva_image_tail_workspace_bytes(B))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws, ws_bytes = _lib.workspace("dva_image_tail_workspace_bytes", dev, B)
     codes = (ctypes.c_int32 * len(jitter))(*[JITTER_CODE[name] for name in names])
     factors = (ctypes.c_double * len(jitter))(*[factor for _, factor in jitter])
     pixels = B * H * W
@@ -2390,8 +2359,7 @@ class _LogSoftmaxNLL(torch.autograd.Function):
         logp = torch.empty((P, C), dtype=torch.float32, device=dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         numden = torch.empty(2, dtype=torch.float64, device=dev)
-        nbytes = int(lib.dva_seg_nll_workspace_bytes())
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws, nbytes = _lib.workspace("dva_seg_nll_workspace_bytes", dev)
         with _timed("seg_logsoftmax_nll_fwd", x.numel() * (x.element_size() + 4)):
             check(lib.dva_seg_logsoftmax_nll_fwd(ptr(x), dtype_code(x), ptr(labels), ptr(weight), int(ignore_index), P, C,
                                                  ptr(logp), ptr(loss), ptr(numden), ptr(ws), nbytes, stream_of(x)),
@@ -2447,10 +2415,7 @@ class _LovaszSoftmax(torch.autograd.Function):
         dev = p.device
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         grad = torch.empty((P, C), dtype=torch.float32, device=dev)
-        nbytes = lib.dva_lovasz_workspace_bytes(P, C)
-        if nbytes < 0:
-            raise _lib.DvaError(f"dva_lovasz_workspace_bytes({P}, {C})", int(nbytes))
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+        ws, nbytes = _lib.workspace("dva_lovasz_workspace_bytes", dev, P, C)
         with _timed("lovasz_softmax", p.numel() * 32):
             check(lib.dva_lovasz_softmax(ptr(p), ptr(labels), P, C, 0 if ignore is None else int(ignore),
                                          0 if ignore is None else 1, ptr(class_mask), int(bool(present_only)), ptr(loss),
@@ -2527,10 +2492,8 @@ KNN_INTERPOLATE_CHUNK = 1 << 22     # queries per K-NN call: bounds the K-NN wor
 
 def vote_slots(num_points, device):
     """The int32 slot array ``vote_add`` works in (one slot per raw point, all -1): created once per accumulator."""
-    nbytes = _lib.load().dva_vote_workspace_bytes(int(num_points))
-    if nbytes < 0:
-        raise _lib.DvaError(f"dva_vote_workspace_bytes({num_points})", int(nbytes))
-    return torch.full((int(nbytes) // 4,), -1, dtype=torch.int32, device=device)
+    nbytes = _lib.workspace_bytes("dva_vote_workspace_bytes", int(num_points))
+    return torch.full((nbytes // 4,), -1, dtype=torch.int32, device=device)
 
 
 def vote_add(votes, counts, ids, outputs, slots):

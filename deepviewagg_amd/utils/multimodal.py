@@ -97,13 +97,6 @@ class CompositeTensor:
         return f"{self.__class__.__name__}(shape={self.shape}, dtype={self.dtype}, device={self.device})"
 
 
-def _workspace(lib, n, device):
-    nbytes = lib.dva_lex_workspace_bytes(n)
-    if nbytes < 0:
-        check(int(nbytes), "dva_lex_workspace_bytes")
-    return torch.empty(int(nbytes), dtype=torch.uint8, device=device), int(nbytes)
-
-
 def argsort_keys(keys):
     """Stable argsort of an int64 key tensor on the device -> (order, sorted_keys)."""
     lib = _lib.load()
@@ -112,7 +105,7 @@ def argsort_keys(keys):
     n = keys.shape[0]
     order = torch.empty(n, dtype=torch.int64, device=keys.device)
     keys_sorted = torch.empty_like(keys)
-    ws, nbytes = _workspace(lib, n, keys.device)
+    ws, nbytes = _lib.workspace("dva_lex_workspace_bytes", keys.device, n)
     check(lib.dva_argsort_i64(ptr(keys), n, ptr(order), ptr(keys_sorted), ptr(ws), nbytes, stream_of(keys)),
           "dva_argsort_i64")
     return order, keys_sorted
@@ -126,7 +119,7 @@ def argunique_keys(keys):
     n = keys.shape[0]
     first = torch.empty(n, dtype=torch.int64, device=keys.device)
     n_unique = torch.zeros(1, dtype=torch.int64, device=keys.device)
-    ws, nbytes = _workspace(lib, n, keys.device)
+    ws, nbytes = _lib.workspace("dva_lex_workspace_bytes", keys.device, n)
     check(lib.dva_argunique_i64(ptr(keys), n, ptr(first), ptr(n_unique), ptr(ws), nbytes, stream_of(keys)),
           "dva_argunique_i64")
     return first[:int(n_unique.item())]

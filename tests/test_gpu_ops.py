@@ -1008,3 +1008,79 @@ def test_view_gather_attention_f32_split_plan_equals_permutation_plan(C, gating)
     assert torch.equal(a[0], b[0]) and torch.equal(a[2], b[2])
     torch.testing.assert_close(b[1], a[1], rtol=1e-5, atol=1e-5 * float(a[1].abs().max()))
     assert float(b[1][R - 20:].abs().max()) == 0.0 and float(b[1].abs().max()) > 0.0
+
+
+def _short_workspace_calls():
+    """name -> (size query, its arguments, call(lib, ws, nbytes, stream) -> rc, output buffers filled with a sentinel)
+    for the entry points whose "workspace too small" check compares against the carved layout's total."""
+    import ctypes
+    from deepviewagg_amd._lib import DvaCamera, ptr
+
+    def i64(*shape):
+        return torch.full(shape, -77, dtype=torch.int64, device=DEV)
+
+    def i32(*shape):
+        return torch.full(shape, -77, dtype=torch.int32, device=DEV)
+
+    def f32(*shape):
+        return torch.full(shape, -77.0, dtype=torch.float32, device=DEV)
+
+    gen = torch.Generator().manual_seed(5)
+    calls = {}
+
+    keys, order, keys_sorted = torch.tensor([4, 1, 3, 1, 0], device=DEV), i64(5), i64(5)
+    calls["argsort_i64"] = ("dva_lex_workspace_bytes", (5,), lambda lib, ws, nb, st: lib.dva_argsort_i64(
+        ptr(keys), 5, ptr(order), ptr(keys_sorted), ptr(ws), nb, st), [order, keys_sorted])
+
+    coords = torch.randint(0, 3, (5, 3), generator=gen).int().to(DEV)
+    stats = torch.tensor([0, 0, 0, 0, 2, 2, 2, 0, 0], device=DEV)
+    g_out = [i64(5), i64(5), i64(6), i64(5), i64(1)]
+    calls["grid_cluster"] = ("dva_grid_workspace_bytes", (5, 0), lambda lib, ws, nb, st: lib.dva_grid_cluster(
+        ptr(coords), None, None, 5, ptr(stats), 8, ptr(g_out[0]), ptr(g_out[1]), ptr(g_out[2]), ptr(g_out[3]), None,
+        ptr(g_out[4]), ptr(ws), nb, st), g_out)
+
+    xyz = torch.rand(5, 3, generator=gen).to(DEV)
+    bbox = torch.tensor([0., 0., 0., 1., 1., 1.], device=DEV)
+    done, nbrs, d2 = torch.full((5,), 7, dtype=torch.uint8, device=DEV), i32(5, 2), f32(5, 2)
+    calls["knn"] = ("dva_knn_workspace_bytes", (5,), lambda lib, ws, nb, st: lib.dva_knn(
+        ptr(xyz), 5, ptr(bbox), 0.5, 2, 2, ptr(done), ptr(nbrs), ptr(d2), ptr(ws), nb, st), [done, nbrs, d2])
+
+    probas = torch.softmax(torch.randn(5, 3, generator=gen), 1).to(DEV)
+    labels = torch.tensor([0, 2, 1, 1, 0], device=DEV)
+    loss, grad = f32(1), f32(5, 3)
+    calls["lovasz_softmax"] = ("dva_lovasz_workspace_bytes", (5, 3), lambda lib, ws, nb, st: lib.dva_lovasz_softmax(
+        ptr(probas), ptr(labels), 5, 3, 0, 0, None, 0, ptr(loss), ptr(grad), ptr(ws), nb, st), [loss, grad])
+
+    row_idx = torch.tensor([2, 0, 1, 2, 0], dtype=torch.int32, device=DEV)
+    perm, row_ptr, counts = i32(5), i32(4), i32(3)
+    calls["row_plan"] = ("dva_row_plan_workspace_bytes", (5, 3), lambda lib, ws, nb, st: lib.dva_row_plan(
+        ptr(row_idx), 5, 3, ptr(perm), ptr(row_ptr), ptr(counts), ptr(ws), nb, st), [perm, row_ptr, counts])
+
+    cam = DvaCamera()
+    cam.model, cam.img_w, cam.img_h = 0, 8, 4
+    cam.r_min, cam.r_max, cam.r_min_d, cam.r_max_d = 0.1, 10.0, 0.1, 10.0
+    cam.voxel, cam.k_swell, cam.d_swell = 0.1, 1.0, 1000.0
+    cam.rot[:] = [1, 0, 0, 0, 1, 0, 0, 0, 1]
+    pts = (torch.rand(5, 3, generator=gen) * 2 - 1).to(DEV)
+    v_out = [i64(32), i64(32), i64(32), f32(32), torch.full((32,), -77.0, dtype=torch.float64, device=DEV),
+             torch.full((32,), -77.0, dtype=torch.float64, device=DEV), i64(1)]
+    calls["visibility"] = ("dva_visibility_workspace_bytes", (ctypes.byref(cam), 5),
+                           lambda lib, ws, nb, st: lib.dva_visibility(
+        ptr(pts), 5, ctypes.byref(cam), None, ptr(v_out[0]), ptr(v_out[1]), ptr(v_out[2]), ptr(v_out[3]),
+        ptr(v_out[4]), ptr(v_out[5]), ptr(v_out[6]), ptr(ws), nb, st), v_out)
+    return calls
+
+
+@pytest.mark.parametrize("family", ["argsort_i64", "grid_cluster", "knn", "lovasz_softmax", "row_plan", "visibility"])
+def test_workspace_one_byte_short_is_refused_before_any_launch(family):
+    """workspace_bytes one below the size query's answer: DVA_ERR_INVALID, and no output buffer is written."""
+    from deepviewagg_amd import _lib
+    lib = _lib.load()
+    query, args, call, outputs = _short_workspace_calls()[family]
+    ws, nbytes = _lib.workspace(query, DEV, *args)
+    assert nbytes >= 256
+    before = [o.clone() for o in outputs]
+    assert call(lib, ws, nbytes - 1, _lib.stream_of(ws)) == -1
+    torch.cuda.synchronize()
+    for o, b in zip(outputs, before):
+        assert torch.equal(o, b)

@@ -691,7 +691,8 @@ class FusedImageTail(ImageTransform):
     images: ``ops.image_tail`` reads the pixels once and writes the encoder's float32 input once, in at most two
     kernel launches per setting.  Built from instances of those classes; from the same generator state it gives the
     ``images.x`` (bit for bit) and the flipped ``mappings.pixels[:, 0]`` of the eager chain and leaves the same
-    generator state.
+    generator state.  A setting that is still deferred (``DeferImages``) goes through ``ops.image_window`` instead: the
+    same pass, reading the window of every image from the source images.
 
     On an ``ImageData`` the eager chain draws transform by transform -- every setting's jitter first, then every
     setting's flip -- so this transform takes the whole ``ImageData`` and draws in that order before it launches."""
@@ -711,12 +712,35 @@ class FusedImageTail(ImageTransform):
         flips = [bool(torch.rand(1) <= self.flip.p) if self.flip is not None else False for _ in settings]
         stats = {} if self.normalize is None else dict(mean=self.normalize.mean, std=self.normalize.std)
         for im, jitter, flip in zip(settings, jitters, flips):
-            im.x = ops.image_tail(im.x, jitter=jitter, flip=flip, to_float=bool(self.to_float), **stats)
+            if getattr(im, 'is_deferred', False):
+                # a deferred setting (DeferImages): selection, roll and crop are applied by the tail's own pass
+                im.x = ops.image_window(im.source, im.source_index, im.source_roll, im.crop_offsets, im.crop_size,
+                                        jitter=jitter, flip=flip, to_float=bool(self.to_float), **stats)
+            else:
+                im.x = ops.image_tail(im.x, jitter=jitter, flip=flip, to_float=bool(self.to_float), **stats)
             if flip:
                 width = im.x.shape[-1]
                 pix = im.mappings.pixels
                 pix[:, 0] = (width - 1 - pix[:, 0].long()).to(pix.dtype)
         return data, (ImageData(settings) if isinstance(images, ImageData) else images)
+
+
+class DeferImages(ImageTransform):
+    """Put in front of an online image chain: every qualifying setting (uint8 ``[N, 3, H, W]`` pixels, no downscale,
+    crop or roll yet) becomes its deferred view, ``SameSettingImageData.windowed()``.  The image selections,
+    ``CenterRoll`` and ``CropImageGroups`` that follow then touch indices, offsets and mappings only, and
+    ``FusedImageTail`` reads each surviving window from the untouched source images in its one pass.  A transform
+    that reads ``images.x`` in between gets the bytes of the eager chain (the window is materialised there).  No
+    draws; a setting that does not qualify passes through."""
+
+    def _process(self, data, images):
+        return data, images.windowed()
+
+
+def defer_image_windows(transforms):
+    """``[DeferImages()] + fuse_image_tail(transforms)``: the chain with its image roll, crop and selection deferred
+    into the fused tail.  Same results and generator state as ``transforms``."""
+    return [DeferImages()] + fuse_image_tail(transforms)
 
 
 def fuse_image_tail(transforms):

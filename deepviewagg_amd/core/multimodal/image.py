@@ -720,6 +720,13 @@ class SameSettingImageData:
         out._mask = mv(self.mask)
         return out
 
+    def windowed(self):
+        """The deferred view of this setting (``WindowedSameSettingImageData``): image selection, rolls and crops then
+        move indices and offsets only, and the pixels of ``x`` are read once, by whoever reads ``x`` first -- the fused
+        image tail does it in its own pass.  Needs uint8 ``x`` ``[N, 3, H, W]`` at ``downscale == 1`` with no crop or
+        roll applied yet; any other setting is returned as it is."""
+        return WindowedSameSettingImageData.defer(self)
+
     @property
     def device(self):
         return self.pos.device
@@ -783,6 +790,133 @@ class SameSettingImageData:
             return ops.lazy_gather_nearest_mapping(self.x, mappings.images, mappings.values[1].pointers,
                                                    mappings.pixels, ratio, exact=self.mappings.is_exact)
         return ops.gather_nearest(self.x, mappings.packed_gather_index(ratio=ratio))
+
+
+class WindowedSameSettingImageData(SameSettingImageData):
+    """A ``SameSettingImageData`` whose pixels are deferred: instead of ``x`` it holds the uint8 ``source``
+    ``[N, 3, H, W]`` it was made from (shared, never copied), the ``source_index`` [B] of its images in it and their
+    effective ``source_roll`` [B] (accumulated mod W: a second ``update_rollings`` REPLACES ``rollings`` but rolls the
+    pixels of the eager class again); the crop is the ``crop_offsets`` / ``crop_size`` state the base class keeps
+    anyway.  ``__getitem__``, ``select_points``, ``select_views``, ``update_rollings``, ``update_cropping``, ``clone``
+    and ``to`` run the base class's code with the pixels out of sight, so the mapping side is the same code.
+
+    Reading ``x`` materialises the uint8 window (``ops.image_window`` without a tail on a device, the base class's
+    torch composition on the host) and ends the deferral, as does setting ``x``; from then on the object behaves as
+    its base class.  ``FusedImageTail`` reads ``source`` directly and never materialises the window."""
+
+    def __init__(self, *args, **kwargs):
+        self._source = self._source_index = self._source_roll = None
+        self._pixels_hidden = False
+        super().__init__(*args, **kwargs)
+
+    @classmethod
+    def defer(cls, images):
+        """The deferred view of ``images`` if it qualifies, ``images`` itself otherwise."""
+        x = images._x
+        if (type(images) is not SameSettingImageData or x is None or x.dtype != torch.uint8 or x.dim() != 4
+                or x.shape[1] != 3 or images.downscale != 1 or tuple(images.crop_size) != tuple(images.ref_size)
+                or (x.shape[3], x.shape[2]) != tuple(images.ref_size) or bool(images.rollings.any())):
+            return images                   # (a crop would have changed crop_size or the size of x)
+        out = copy.copy(images)
+        out.__class__ = cls
+        out._pixels_hidden = False
+        out._x = None
+        out._mappings = images.mappings.clone() if images.mappings is not None else None
+        out._source = x.contiguous()
+        out._source_index = torch.arange(x.shape[0], device=images.device)
+        out._source_roll = torch.zeros(x.shape[0], dtype=torch.int64, device=images.device)
+        return out
+
+    @property
+    def is_deferred(self):
+        return self._source is not None
+
+    @property
+    def source(self):
+        return self._source
+
+    @property
+    def source_index(self):
+        return self._source_index
+
+    @property
+    def source_roll(self):
+        return self._source_roll
+
+    def _end_deferral(self):
+        self._source = self._source_index = self._source_roll = None
+
+    def _materialize(self):
+        """The uint8 window ``[B, 3, Hc, Wc]`` the eager class would hold now."""
+        src, idx, roll, off = self._source, self._source_index, self._source_roll, self.crop_offsets
+        Wc, Hc = (int(v) for v in self.crop_size)
+        if src.is_cuda:
+            return ops.image_window(src, idx, roll, off, (Wc, Hc))
+        eager = SameSettingImageData(pos=self.pos, ref_size=self.ref_size, proj_upscale=self.proj_upscale, x=src[idx])
+        eager.update_rollings(roll)
+        if (Wc, Hc) != tuple(self.ref_size):
+            eager.update_cropping((Wc, Hc), off)
+        return eager.x
+
+    def _get_x(self):
+        if not self.is_deferred:
+            return self._x
+        if self._pixels_hidden:
+            return None
+        self._x = self._materialize()
+        self._end_deferral()
+        return self._x
+
+    def _set_x(self, x):
+        self._end_deferral()
+        SameSettingImageData.x.fset(self, x)
+
+    x = property(_get_x, _set_x, doc="The image features; a read or a write ends the deferral.")
+
+    def _without_pixels(self, method, *args, **kwargs):
+        """``method`` of the base class with ``x`` reading None: it then updates the mappings and the roll / crop
+        state and leaves the pixels alone."""
+        if not self.is_deferred:
+            return method(self, *args, **kwargs)
+        self._pixels_hidden = True
+        try:
+            return method(self, *args, **kwargs)
+        finally:
+            self._pixels_hidden = False
+
+    def _follow(self, out, idx=None, device=None):
+        """Hands the deferred pixels of ``self`` to ``out``, which the base class built without pixels."""
+        if self.is_deferred:
+            out._pixels_hidden = False
+            out._source = self._source if device is None else self._source.to(device)
+            index, roll = self._source_index, self._source_roll
+            if idx is not None:
+                index, roll = index[idx], roll[idx]
+            out._source_index = index if device is None else index.to(device)
+            out._source_roll = roll if device is None else roll.to(device)
+        return out
+
+    def __getitem__(self, idx):
+        out = self._without_pixels(SameSettingImageData.__getitem__, idx)
+        return self._follow(out, idx=tensor_idx(idx).to(self.device))
+
+    def clone(self):
+        return self._follow(self._without_pixels(SameSettingImageData.clone))
+
+    def to(self, device):
+        return self._follow(self._without_pixels(SameSettingImageData.to, device), device=device)
+
+    def update_rollings(self, rollings):
+        deferred = self.is_deferred
+        self._without_pixels(SameSettingImageData.update_rollings, rollings)
+        if deferred:
+            self._source_roll = (self._source_roll + self.rollings) % self._source.shape[3]
+        return self
+
+    def update_cropping(self, crop_size, crop_offsets):
+        if self.is_deferred:
+            assert self.downscale == 1, "A deferred setting holds full-resolution pixels."
+        return self._without_pixels(SameSettingImageData.update_cropping, crop_size, crop_offsets)
 
 
 class SameSettingImageBatch(SameSettingImageData):

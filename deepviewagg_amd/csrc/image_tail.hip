@@ -23,6 +23,14 @@
 // (row tail) or whose address is not a multiple of its vector width (rows of a width that is no multiple of VEC) takes
 // the scalar path.  image_normalize_f32_kernel is the float32-input mode: Normalize alone, any channel count up to
 // DVA_IMAGE_MAX_CHANNELS.  No float atomics, no LDS beyond the block reduction of the sums.
+//
+// The windowed tail (dva_image_window_u8) runs the same two passes over a window of a source image that is never
+// materialised: image index[b] of src [N, 3, H, W], rolled along W by rolls[b], cropped to Wc x Hc at offsets[b].  Its
+// kernels image_window_gray_sums_kernel / image_window_u8_kernel share every device function above with the plain
+// tail; the contrast mean is taken over the window alone.  The destination chunk of a lane is aligned as before, its
+// source address is arbitrary (offsets[b, 0] - rolls[b] per image), so a full chunk inside a row loads through
+// it_load_any (the aligned vector load, or the covering aligned dwords shifted into place) and a chunk across the wrap
+// column W goes byte by byte; image_window_u8_kernel's comment lists the cases.
 #include "dva_common.h"
 
 #pragma clang fp contract(off)
@@ -85,32 +93,68 @@ __device__ __forceinline__ float it_tail(float p, const ItNorm& nrm, int c) {
   return p;
 }
 
-// VEC consecutive uint8 as floats; `rev`: in reverse order (the mirrored source chunk of a flipped row)
+// VEC bytes held in VEC / 4 words (byte k of the chunk = bits 8 (k mod 4) of word k / 4) as floats; `rev`: in reverse
+// order (the mirrored source chunk of a flipped row)
+template <int VEC>
+__device__ __forceinline__ void it_unpack(uint32_t* w, bool rev, float* v) {
+  if (rev) {
+#pragma unroll
+    for (int j = 0; j < VEC / 8; ++j) {
+      const uint32_t a = __builtin_bswap32(w[VEC / 4 - 1 - j]);
+      w[VEC / 4 - 1 - j] = __builtin_bswap32(w[j]);
+      w[j] = a;
+    }
+    if (VEC == 4) w[0] = __builtin_bswap32(w[0]);
+  }
+#pragma unroll
+  for (int j = 0; j < VEC / 4; ++j) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[4 * j + k] = (float)((w[j] >> (8 * k)) & 0xffu);
+  }
+}
+
+// VEC consecutive uint8 at an address that is a multiple of VEC, as floats
 template <int VEC>
 __device__ __forceinline__ void it_load(const uint8_t* p, bool rev, float* v);
 template <>
 __device__ __forceinline__ void it_load<4>(const uint8_t* p, bool rev, float* v) {
-  uint32_t w = *reinterpret_cast<const uint32_t*>(p);
-  if (rev) w = __builtin_bswap32(w);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = (float)((w >> (8 * k)) & 0xffu);
+  uint32_t w[1] = {*reinterpret_cast<const uint32_t*>(p)};
+  it_unpack<4>(w, rev, v);
 }
 template <>
 __device__ __forceinline__ void it_load<16>(const uint8_t* p, bool rev, float* v) {
   const uint4 q = *reinterpret_cast<const uint4*>(p);
   uint32_t w[4] = {q.x, q.y, q.z, q.w};
-  if (rev) {
-    const uint32_t a = __builtin_bswap32(w[3]), b = __builtin_bswap32(w[2]);
-    w[3] = __builtin_bswap32(w[0]);
-    w[2] = __builtin_bswap32(w[1]);
-    w[0] = a;
-    w[1] = b;
+  it_unpack<16>(w, rev, v);
+}
+
+// VEC consecutive uint8 at ANY address, as VEC / 4 words: the aligned load where the address allows it, otherwise the
+// aligned words that cover the chunk (VEC / 4, one more when the address is no multiple of 4), shifted into place.
+// Every word read holds at least one byte of the chunk, so no read leaves the pages of the chunk.
+template <int VEC>
+__device__ __forceinline__ void it_words_any(const uint8_t* p, uint32_t* w) {
+  const uintptr_t a = (uintptr_t)p;
+  if (VEC == 16 && (a % 16) == 0) {
+    const uint4 q = *reinterpret_cast<const uint4*>(p);
+    w[0] = q.x, w[1] = q.y, w[2] = q.z, w[3] = q.w;
+    return;
   }
+  const uint32_t* q = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
+  const int sh = (int)(a & 3) * 8;
+  uint32_t lo = q[0];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[4 * j + k] = (float)((w[j] >> (8 * k)) & 0xffu);
+  for (int j = 0; j < VEC / 4; ++j) {
+    const uint32_t hi = (j + 1 < VEC / 4 || sh) ? q[j + 1] : 0u;
+    w[j] = sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
+    lo = hi;
   }
+}
+
+template <int VEC>
+__device__ __forceinline__ void it_load_any(const uint8_t* p, bool rev, float* v) {
+  uint32_t w[VEC / 4];
+  it_words_any<VEC>(p, w);
+  it_unpack<VEC>(w, rev, v);
 }
 
 __device__ __forceinline__ uint32_t it_pack4(const float* v) {
@@ -121,12 +165,77 @@ __device__ __forceinline__ float it_mean(const int64_t* __restrict__ sums, int64
   return sums ? __fdiv_rn((float)sums[b], (float)hw) : 0.f;
 }
 
+// the finished chunk of VEC pixels (three planes, `hw` elements apart) at element dst0 of `out`, 16-byte stores: fp32
+// after ToFloatImage / Normalize (FOUT) or uint8
+template <int VEC, bool FOUT>
+__device__ __forceinline__ void it_store_chunk(void* __restrict__ out, int64_t dst0, int64_t hw, const float* r,
+                                               const float* g, const float* bl, const ItNorm& nrm) {
+  if (FOUT) {
+    float* o = static_cast<float*>(out) + dst0;
+#pragma unroll
+    for (int k0 = 0; k0 < VEC; k0 += 4) {
+      *reinterpret_cast<float4*>(o + k0) =
+          make_float4(it_tail(r[k0], nrm, 0), it_tail(r[k0 + 1], nrm, 0),
+                      it_tail(r[k0 + 2], nrm, 0), it_tail(r[k0 + 3], nrm, 0));
+      *reinterpret_cast<float4*>(o + hw + k0) =
+          make_float4(it_tail(g[k0], nrm, 1), it_tail(g[k0 + 1], nrm, 1),
+                      it_tail(g[k0 + 2], nrm, 1), it_tail(g[k0 + 3], nrm, 1));
+      *reinterpret_cast<float4*>(o + 2 * hw + k0) =
+          make_float4(it_tail(bl[k0], nrm, 2), it_tail(bl[k0 + 1], nrm, 2),
+                      it_tail(bl[k0 + 2], nrm, 2), it_tail(bl[k0 + 3], nrm, 2));
+    }
+  } else {
+    uint8_t* o = static_cast<uint8_t*>(out) + dst0;
+    if (VEC == 16) {
+      *reinterpret_cast<uint4*>(o) = make_uint4(it_pack4(r), it_pack4(r + 4), it_pack4(r + 8), it_pack4(r + 12));
+      *reinterpret_cast<uint4*>(o + hw) = make_uint4(it_pack4(g), it_pack4(g + 4), it_pack4(g + 8), it_pack4(g + 12));
+      *reinterpret_cast<uint4*>(o + 2 * hw) =
+          make_uint4(it_pack4(bl), it_pack4(bl + 4), it_pack4(bl + 8), it_pack4(bl + 12));
+    } else {
+      *reinterpret_cast<uint32_t*>(o) = it_pack4(r);
+      *reinterpret_cast<uint32_t*>(o + hw) = it_pack4(g);
+      *reinterpret_cast<uint32_t*>(o + 2 * hw) = it_pack4(bl);
+    }
+  }
+}
+
+// one finished pixel at element d of `out`
+template <bool FOUT>
+__device__ __forceinline__ void it_store_pixel(void* __restrict__ out, int64_t d, int64_t hw, float r, float g, float bl,
+                                               const ItNorm& nrm) {
+  if (FOUT) {
+    float* o = static_cast<float*>(out);
+    o[d] = it_tail(r, nrm, 0);
+    o[d + hw] = it_tail(g, nrm, 1);
+    o[d + 2 * hw] = it_tail(bl, nrm, 2);
+  } else {
+    uint8_t* o = static_cast<uint8_t*>(out);
+    o[d] = (uint8_t)r;
+    o[d + hw] = (uint8_t)g;
+    o[d + 2 * hw] = (uint8_t)bl;
+  }
+}
+
+// sums[slot] += the block's total of `acc`: one wave reduction, one 64-bit integer atomic add per block
+__device__ __forceinline__ void it_block_add(unsigned long long acc, int64_t* __restrict__ sums, int64_t slot) {
+  __shared__ unsigned long long sh[IT_TPB / DVA_WAVE];
+#pragma unroll
+  for (int off = DVA_WAVE / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+  const int lane = threadIdx.x & (DVA_WAVE - 1), wave = threadIdx.x >> 6;
+  if (lane == 0) sh[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long s = sh[0];
+    for (int w = 1; w < IT_TPB / DVA_WAVE; ++w) s += sh[w];
+    if (s) atomicAdd(reinterpret_cast<unsigned long long*>(sums) + slot, s);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // gray sums: sums[b] += sum over the pixels of image b of gray(after the first ops.n ops).  grid (blocks, B).
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(IT_TPB) void image_gray_sums_kernel(const uint8_t* __restrict__ x, int64_t hw, ItOps ops,
                                                                  int64_t* __restrict__ sums) {
-  __shared__ unsigned long long sh[IT_TPB / DVA_WAVE];
   const uint8_t* r0 = x + (int64_t)blockIdx.y * 3 * hw;
   const uint8_t* g0 = r0 + hw;
   const uint8_t* b0 = g0 + hw;
@@ -163,16 +272,7 @@ __global__ __launch_bounds__(IT_TPB) void image_gray_sums_kernel(const uint8_t* 
     }
     acc += part;
   }
-#pragma unroll
-  for (int off = DVA_WAVE / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-  const int lane = threadIdx.x & (DVA_WAVE - 1), wave = threadIdx.x >> 6;
-  if (lane == 0) sh[wave] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long s = sh[0];
-    for (int w = 1; w < IT_TPB / DVA_WAVE; ++w) s += sh[w];
-    if (s) atomicAdd(reinterpret_cast<unsigned long long*>(sums) + blockIdx.y, s);
-  }
+  it_block_add(acc, sums, blockIdx.y);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -203,33 +303,7 @@ __global__ __launch_bounds__(IT_TPB) void image_tail_u8_kernel(const uint8_t* __
     it_load<VEC>(x + src0 + 2 * hw, flip, bl);
 #pragma unroll
     for (int k = 0; k < VEC; ++k) it_jitter(ops, ops.n, m, r[k], g[k], bl[k]);
-    if (FOUT) {
-      float* o = static_cast<float*>(out) + dst0;
-#pragma unroll
-      for (int k0 = 0; k0 < VEC; k0 += 4) {
-        *reinterpret_cast<float4*>(o + k0) =
-            make_float4(it_tail(r[k0], nrm, 0), it_tail(r[k0 + 1], nrm, 0),
-                        it_tail(r[k0 + 2], nrm, 0), it_tail(r[k0 + 3], nrm, 0));
-        *reinterpret_cast<float4*>(o + hw + k0) =
-            make_float4(it_tail(g[k0], nrm, 1), it_tail(g[k0 + 1], nrm, 1),
-                        it_tail(g[k0 + 2], nrm, 1), it_tail(g[k0 + 3], nrm, 1));
-        *reinterpret_cast<float4*>(o + 2 * hw + k0) =
-            make_float4(it_tail(bl[k0], nrm, 2), it_tail(bl[k0 + 1], nrm, 2),
-                        it_tail(bl[k0 + 2], nrm, 2), it_tail(bl[k0 + 3], nrm, 2));
-      }
-    } else {
-      uint8_t* o = static_cast<uint8_t*>(out) + dst0;
-      if (VEC == 16) {
-        *reinterpret_cast<uint4*>(o) = make_uint4(it_pack4(r), it_pack4(r + 4), it_pack4(r + 8), it_pack4(r + 12));
-        *reinterpret_cast<uint4*>(o + hw) = make_uint4(it_pack4(g), it_pack4(g + 4), it_pack4(g + 8), it_pack4(g + 12));
-        *reinterpret_cast<uint4*>(o + 2 * hw) =
-            make_uint4(it_pack4(bl), it_pack4(bl + 4), it_pack4(bl + 8), it_pack4(bl + 12));
-      } else {
-        *reinterpret_cast<uint32_t*>(o) = it_pack4(r);
-        *reinterpret_cast<uint32_t*>(o + hw) = it_pack4(g);
-        *reinterpret_cast<uint32_t*>(o + 2 * hw) = it_pack4(bl);
-      }
-    }
+    it_store_chunk<VEC, FOUT>(out, dst0, hw, r, g, bl, nrm);
     return;
   }
   const int c1 = c0 + VEC < W ? c0 + VEC : W;
@@ -238,17 +312,7 @@ __global__ __launch_bounds__(IT_TPB) void image_tail_u8_kernel(const uint8_t* __
     const int64_t s = line + (flip ? W - 1 - c : c), d = line + c;
     float r = (float)x[s], g = (float)x[s + hw], bl = (float)x[s + 2 * hw];
     it_jitter(ops, ops.n, m, r, g, bl);
-    if (FOUT) {
-      float* o = static_cast<float*>(out);
-      o[d] = it_tail(r, nrm, 0);
-      o[d + hw] = it_tail(g, nrm, 1);
-      o[d + 2 * hw] = it_tail(bl, nrm, 2);
-    } else {
-      uint8_t* o = static_cast<uint8_t*>(out);
-      o[d] = (uint8_t)r;
-      o[d + hw] = (uint8_t)g;
-      o[d + 2 * hw] = (uint8_t)bl;
-    }
+    it_store_pixel<FOUT>(out, d, hw, r, g, bl, nrm);
   }
 }
 
@@ -275,6 +339,134 @@ __global__ __launch_bounds__(IT_TPB) void image_normalize_f32_kernel(const float
   for (int64_t i = i0; i < i1; ++i) out[plane * hw + i] = __fdiv_rn(x[plane * hw + i] - mu, sd);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// the windowed tail: the same passes over a window of a source image that is never materialised
+//   win[b, c, y, x] = src[index[b], c, offsets[b, 1] + y, (offsets[b, 0] + x - rolls[b]) mod W]
+// ---------------------------------------------------------------------------------------------------------------
+// output image b in its source: plane 0 of the source image, the first source row of the window and the source column
+// of window column 0.  index / offsets / rolls are device data nobody has validated: the image is clamped to [0, N - 1]
+// and the rows to [0, H - 1] (iw_row), the column is in [0, W) by the mod.
+struct IwImage {
+  const uint8_t* plane0;
+  int64_t y0;
+  int64_t x0;
+};
+
+__device__ __forceinline__ IwImage iw_image(const uint8_t* __restrict__ src, int64_t N, int64_t hw, int64_t H, int64_t W,
+                                            const int64_t* __restrict__ index, const int64_t* __restrict__ rolls,
+                                            const int64_t* __restrict__ offsets, int64_t b) {
+  int64_t i = index[b];
+  i = i < 0 ? 0 : (i >= N ? N - 1 : i);
+  // the difference in unsigned arithmetic: absurd values wrap (their result is unspecified) instead of overflowing
+  int64_t x0 = (int64_t)((uint64_t)offsets[2 * b] - (uint64_t)rolls[b]) % W;
+  if (x0 < 0) x0 += W;
+  int64_t y0 = offsets[2 * b + 1];
+  y0 = y0 < 0 ? 0 : (y0 >= H ? H - 1 : y0);
+  return {src + i * 3 * hw, y0, x0};
+}
+
+__device__ __forceinline__ int64_t iw_row(const IwImage& im, int64_t y, int64_t H) {
+  return im.y0 + y < H ? im.y0 + y : H - 1;
+}
+
+// source column of window column w (w < Wc <= W, so one subtraction wraps)
+__device__ __forceinline__ int64_t iw_col(const IwImage& im, int64_t w, int64_t W) {
+  const int64_t s = im.x0 + w;
+  return s >= W ? s - W : s;
+}
+
+// gray sums over the window: sums[b] += sum over the Hc x Wc window pixels of gray(after the first ops.n ops).
+// grid (blocks, B); a lane takes chunks of IT_SUM_VEC pixels of one window row, loaded as in the apply kernel.
+__global__ __launch_bounds__(IT_TPB) void image_window_gray_sums_kernel(
+    const uint8_t* __restrict__ src, int64_t N, int H, int W, const int64_t* __restrict__ index,
+    const int64_t* __restrict__ rolls, const int64_t* __restrict__ offsets, int Hc, int Wc, ItOps ops,
+    int64_t* __restrict__ sums) {
+  const int64_t hw = (int64_t)H * W;
+  const IwImage im = iw_image(src, N, hw, H, W, index, rolls, offsets, blockIdx.y);
+  const int chunks_per_row = (Wc + IT_SUM_VEC - 1) / IT_SUM_VEC;
+  const int64_t chunks = (int64_t)Hc * chunks_per_row;
+  unsigned long long acc = 0;
+  for (int64_t j = (int64_t)blockIdx.x * IT_TPB + threadIdx.x; j < chunks; j += (int64_t)gridDim.x * IT_TPB) {
+    const int64_t y = j / chunks_per_row;
+    const int c0 = (int)(j - y * chunks_per_row) * IT_SUM_VEC;
+    const int n = Wc - c0 < IT_SUM_VEC ? Wc - c0 : IT_SUM_VEC;
+    const uint8_t* line = im.plane0 + iw_row(im, y, H) * W;
+    const int64_t s = iw_col(im, c0, W);
+    uint32_t part = 0;
+    if (n == IT_SUM_VEC && s + IT_SUM_VEC <= W) {
+      uint32_t wr[IT_SUM_VEC / 4], wg[IT_SUM_VEC / 4], wb[IT_SUM_VEC / 4];
+      it_words_any<IT_SUM_VEC>(line + s, wr);
+      it_words_any<IT_SUM_VEC>(line + s + hw, wg);
+      it_words_any<IT_SUM_VEC>(line + s + 2 * hw, wb);
+#pragma unroll
+      for (int i = 0; i < IT_SUM_VEC / 4; ++i) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          float r = (float)((wr[i] >> (8 * k)) & 0xffu), g = (float)((wg[i] >> (8 * k)) & 0xffu),
+                bl = (float)((wb[i] >> (8 * k)) & 0xffu);
+          it_jitter(ops, ops.n, 0.f, r, g, bl);
+          part += (uint32_t)it_gray(r, g, bl);
+        }
+      }
+    } else {
+      for (int k = 0; k < n; ++k) {
+        const int64_t col = iw_col(im, c0 + k, W);
+        float r = (float)line[col], g = (float)line[col + hw], bl = (float)line[col + 2 * hw];
+        it_jitter(ops, ops.n, 0.f, r, g, bl);
+        part += (uint32_t)it_gray(r, g, bl);
+      }
+    }
+    acc += part;
+  }
+  it_block_add(acc, sums, blockIdx.y);
+}
+
+// apply over the window: one thread per chunk of VEC consecutive output pixels of one window row, all three planes.
+// Which load a chunk takes (all give the same bytes):
+//   full chunk, its source columns do not pass the wrap column W, 16-byte aligned destination
+//     source address a multiple of VEC (16 for uint8 output, 4 for fp32 output)   one aligned vector load per plane
+//     any other source address (odd, or a multiple of 4 but not of 16)            the aligned dwords that cover the
+//                                                                                 chunk, shifted into place
+//   a chunk that is not full (row tail of a width that is no multiple of VEC), that straddles the wrap column, or
+//   whose destination is not 16-byte aligned (Hc Wc no multiple of VEC)           byte by byte, the column wrapped
+template <int VEC, bool FOUT>
+__global__ __launch_bounds__(IT_TPB) void image_window_u8_kernel(
+    const uint8_t* __restrict__ src, int64_t N, int H, int W, const int64_t* __restrict__ index,
+    const int64_t* __restrict__ rolls, const int64_t* __restrict__ offsets, int64_t rows, int Hc, int Wc,
+    int chunks_per_row, ItOps ops, const int64_t* __restrict__ sums, int flip, ItNorm nrm, void* __restrict__ out,
+    int aligned) {
+  const int64_t t = (int64_t)blockIdx.x * IT_TPB + threadIdx.x;
+  if (t >= rows * chunks_per_row) return;
+  const int64_t row = t / chunks_per_row;               // b * Hc + y
+  const int c0 = (int)(t - row * chunks_per_row) * VEC;  // first output column of the chunk
+  const int64_t b = row / Hc;
+  const int64_t y = row - b * Hc;
+  const int64_t hw = (int64_t)H * W, hwc = (int64_t)Hc * Wc;
+  const float m = it_mean(sums, b, hwc);
+  const IwImage im = iw_image(src, N, hw, H, W, index, rolls, offsets, b);
+  const uint8_t* line = im.plane0 + iw_row(im, y, H) * W;
+  const int64_t dst_line = (b * 3 * Hc + y) * Wc;        // plane 0; plane c adds c * hwc
+  const int n = Wc - c0 < VEC ? Wc - c0 : VEC;
+  // a flipped chunk reads the mirrored window columns Wc - c0 - n .. Wc - 1 - c0 in reverse
+  const int64_t s = iw_col(im, flip ? Wc - c0 - n : c0, W);
+  if (aligned && n == VEC && s + VEC <= W && ((dst_line + c0) % VEC) == 0 && (hwc % VEC) == 0) {
+    float r[VEC], g[VEC], bl[VEC];
+    it_load_any<VEC>(line + s, flip, r);
+    it_load_any<VEC>(line + s + hw, flip, g);
+    it_load_any<VEC>(line + s + 2 * hw, flip, bl);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) it_jitter(ops, ops.n, m, r[k], g[k], bl[k]);
+    it_store_chunk<VEC, FOUT>(out, dst_line + c0, hwc, r, g, bl, nrm);
+    return;
+  }
+  for (int c = c0; c < c0 + n; ++c) {
+    const int64_t col = iw_col(im, flip ? Wc - 1 - c : c, W);
+    float r = (float)line[col], g = (float)line[col + hw], bl = (float)line[col + 2 * hw];
+    it_jitter(ops, ops.n, m, r, g, bl);
+    it_store_pixel<FOUT>(out, dst_line + c, hwc, r, g, bl, nrm);
+  }
+}
+
 static inline int64_t it_sums_bytes(int64_t B) { return (int64_t)align_up((size_t)(B > 0 ? B : 1) * 8); }
 
 // mean / std (host, C floats each, both or neither) into the kernel argument
@@ -292,6 +484,26 @@ static int it_norm(const float* mean, const float* std, int64_t C, ItNorm* nrm) 
   return DVA_OK;
 }
 
+// the op list (host arrays) into the kernel argument; *contrast_at = the position of contrast in it, or -1
+static int it_ops(const int32_t* op_codes, const double* factors, int32_t n_ops, ItOps* ops, int* contrast_at) {
+  if (n_ops < 0 || n_ops > 3) return DVA_ERR_INVALID;
+  if (n_ops > 0 && (!op_codes || !factors)) return DVA_ERR_INVALID;
+  *contrast_at = -1;
+  for (int k = 0; k < n_ops; ++k) {
+    const int code = op_codes[k];
+    if (code != IT_BRIGHTNESS && code != IT_CONTRAST && code != IT_SATURATION) return DVA_ERR_INVALID;
+    for (int j = 0; j < k; ++j)
+      if (ops->code[j] == code) return DVA_ERR_INVALID;
+    if (!(factors[k] >= 0.0)) return DVA_ERR_INVALID;      // negative or NaN
+    ops->code[k] = code;
+    ops->f[k] = (float)factors[k];
+    ops->g[k] = (float)(1.0 - factors[k]);
+    if (code == IT_CONTRAST) *contrast_at = k;
+  }
+  ops->n = n_ops;
+  return DVA_OK;
+}
+
 }  // namespace dva
 
 using namespace dva;
@@ -306,22 +518,10 @@ int64_t dva_image_tail_workspace_bytes(int64_t B) {
 int dva_image_tail_u8(const uint8_t* x, int64_t B, int64_t H, int64_t W, const int32_t* op_codes,
                       const double* factors, int32_t n_ops, int32_t flip, int32_t to_float, const float* mean,
                       const float* std, void* out, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (B < 0 || H < 0 || W < 0 || n_ops < 0 || n_ops > 3) return DVA_ERR_INVALID;
-  if (n_ops > 0 && (!op_codes || !factors)) return DVA_ERR_INVALID;
+  if (B < 0 || H < 0 || W < 0) return DVA_ERR_INVALID;
   ItOps ops = {};
   int contrast_at = -1;
-  for (int k = 0; k < n_ops; ++k) {
-    const int code = op_codes[k];
-    if (code != IT_BRIGHTNESS && code != IT_CONTRAST && code != IT_SATURATION) return DVA_ERR_INVALID;
-    for (int j = 0; j < k; ++j)
-      if (ops.code[j] == code) return DVA_ERR_INVALID;
-    if (!(factors[k] >= 0.0)) return DVA_ERR_INVALID;      // negative or NaN
-    ops.code[k] = code;
-    ops.f[k] = (float)factors[k];
-    ops.g[k] = (float)(1.0 - factors[k]);
-    if (code == IT_CONTRAST) contrast_at = k;
-  }
-  ops.n = n_ops;
+  if (it_ops(op_codes, factors, n_ops, &ops, &contrast_at) != DVA_OK) return DVA_ERR_INVALID;
   ItNorm nrm = {};
   const int rc = it_norm(mean, std, 3, &nrm);
   if (rc != DVA_OK) return rc;
@@ -356,6 +556,60 @@ int dva_image_tail_u8(const uint8_t* x, int64_t B, int64_t H, int64_t W, const i
   else
     hipLaunchKernelGGL((image_tail_u8_kernel<16, false>), grid, dim3(IT_TPB), 0, s, x, B * H, (int)H, (int)W,
                        (int)chunks_per_row, ops, (const int64_t*)sums, (int)(flip != 0), nrm, out, aligned);
+  DVA_CHECK_LAUNCH();
+  return DVA_OK;
+}
+
+int64_t dva_image_window_workspace_bytes(int64_t B) {
+  if (B < 0) return DVA_ERR_INVALID;
+  return it_sums_bytes(B);
+}
+
+int dva_image_window_u8(const uint8_t* src, int64_t N, int64_t H, int64_t W, const int64_t* index,
+                        const int64_t* rolls, const int64_t* offsets, int64_t B, int64_t Wc, int64_t Hc,
+                        const int32_t* op_codes, const double* factors, int32_t n_ops, int32_t flip, int32_t to_float,
+                        const float* mean, const float* std, void* out, void* workspace, int64_t workspace_bytes,
+                        void* stream) {
+  if (N < 0 || H < 0 || W < 0 || B < 0 || Wc < 0 || Hc < 0 || Wc > W || Hc > H) return DVA_ERR_INVALID;
+  ItOps ops = {};
+  int contrast_at = -1;
+  if (it_ops(op_codes, factors, n_ops, &ops, &contrast_at) != DVA_OK) return DVA_ERR_INVALID;
+  ItNorm nrm = {};
+  const int rc = it_norm(mean, std, 3, &nrm);
+  if (rc != DVA_OK) return rc;
+  if (nrm.on && !to_float) return DVA_ERR_INVALID;          // Normalize takes the [0, 1] floats of ToFloatImage
+  if (B == 0) return DVA_OK;
+  if (N < 1 || Wc < 1 || Hc < 1) return DVA_ERR_INVALID;    // nothing to index, or no window
+  if (!src || !index || !rolls || !offsets || !out) return DVA_ERR_INVALID;
+  if (contrast_at >= 0 && (!workspace || workspace_bytes < it_sums_bytes(B))) return DVA_ERR_INVALID;
+  if (H > 0x7fffffffLL || W > 0x7fffffffLL - 16 || B > 65535) return DVA_ERR_UNSUPPORTED;
+  const bool fout = to_float != 0;
+  const int vec = fout ? 4 : 16;
+  const int64_t chunks_per_row = (Wc + vec - 1) / vec;
+  if (B * Hc > IT_MAX_THREADS / chunks_per_row) return DVA_ERR_UNSUPPORTED;
+  const int64_t threads = B * Hc * chunks_per_row;
+  hipStream_t s = (hipStream_t)stream;
+  int64_t* sums = nullptr;
+  if (contrast_at >= 0) {
+    sums = (int64_t*)workspace;
+    if (hipMemsetAsync(sums, 0, (size_t)B * 8, s) != hipSuccess) return DVA_ERR_LAUNCH;
+    ItOps pre = ops;
+    pre.n = contrast_at;
+    const int64_t sum_chunks = Hc * ((Wc + IT_SUM_VEC - 1) / IT_SUM_VEC);
+    const dim3 sgrid((unsigned)capped_grid(sum_chunks, IT_TPB, IT_SUM_BLOCKS), (unsigned)B);
+    hipLaunchKernelGGL(image_window_gray_sums_kernel, sgrid, dim3(IT_TPB), 0, s, src, N, (int)H, (int)W, index, rolls,
+                       offsets, (int)Hc, (int)Wc, pre, sums);
+  }
+  const int aligned = ((uintptr_t)out % 16) == 0;
+  const dim3 grid((unsigned)blocks_for(threads, IT_TPB));
+  if (fout)
+    hipLaunchKernelGGL((image_window_u8_kernel<4, true>), grid, dim3(IT_TPB), 0, s, src, N, (int)H, (int)W, index,
+                       rolls, offsets, B * Hc, (int)Hc, (int)Wc, (int)chunks_per_row, ops, (const int64_t*)sums,
+                       (int)(flip != 0), nrm, out, aligned);
+  else
+    hipLaunchKernelGGL((image_window_u8_kernel<16, false>), grid, dim3(IT_TPB), 0, s, src, N, (int)H, (int)W, index,
+                       rolls, offsets, B * Hc, (int)Hc, (int)Wc, (int)chunks_per_row, ops, (const int64_t*)sums,
+                       (int)(flip != 0), nrm, out, aligned);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }

@@ -16,7 +16,9 @@ and imports the data classes from
 its ``_compute_metrics`` becomes ``deepviewagg_amd.metrics.segmentation_tracker.compute_metrics``.  The image transforms
 of the data configs resolve on ``torch_points3d.core.data_transform.multimodal.image``, which is aliased whole: with
 ``ColorJitter``, ``Normalize`` and ``ToImageData`` every per-sample image transform the shipped chains name is there, next
-to ``FusedImageTail`` and ``fuse_image_tail`` (one pass for the tail of a chain).  ``install()`` either patches an importable
+to ``FusedImageTail`` and ``fuse_image_tail`` (one pass for the tail of a chain) and to ``DeferImages`` and
+``defer_image_windows`` (image selection, roll and crop deferred into that pass; the deferred setting is
+``WindowedSameSettingImageData`` / ``SameSettingImageData.windowed()`` in ``core.multimodal.image``).  ``install()`` either patches an importable
 ``torch_points3d`` in place (attribute by attribute) or, when the package is absent, registers alias
 modules under those dotted names in ``sys.modules``.
 """

@@ -19,6 +19,7 @@ ops; names and argument meaning follow the reference call site
 ``elastic_displace``       grid_transform.py:241-242 (``RegularGridInterpolator``)
 ``elastic_distortion``     grid_transform.py:218-243 (one level of ElasticDistortion)
 ``image_tail``             core/data_transform/multimodal/image.py:1195-1282 (ColorJitter, flip, ToFloatImage, Normalize)
+``image_window``           the same tail over deferred windows: core/multimodal/image.py:578-722 (rolls, crops) folded in
 ``log_softmax_nll``        models/segmentation/sparseconv3d.py:45-51 (``F.log_softmax`` + ``F.nll_loss``)
 ``lovasz_softmax_flat``    metrics/lovasz_loss.py:174-215 (``flatten_probas`` + ``lovasz_softmax_flat``)
 ``confusion_counts``       metrics/segmentation_tracker.py:72-83 (mask + ``np.argmax`` + ``np.bincount``)
@@ -2216,23 +2217,40 @@ JITTER_CODE = {"brightness": 0, "contrast": 1, "saturation": 2}      # DVA_JITTE
 IMAGE_MAX_CHANNELS = 64                                               # DVA_IMAGE_MAX_CHANNELS
 
 
-def _image_tail_stats(mean, std, channels):
+def _image_tail_stats(mean, std, channels, what="ops.image_tail"):
     """``mean`` / ``std`` as two ctypes float arrays of ``channels`` entries, or (None, None)."""
     import ctypes
     if mean is None and std is None:
         return None, None
     if mean is None or std is None:
-        raise ValueError("ops.image_tail: mean and std go together")
+        raise ValueError(f"{what}: mean and std go together")
     mean, std = [float(v) for v in mean], [float(v) for v in std]
     if len(mean) != channels or len(std) != channels:
-        raise ValueError(f"ops.image_tail: {len(mean)} means and {len(std)} stds for {channels} channels")
+        raise ValueError(f"{what}: {len(mean)} means and {len(std)} stds for {channels} channels")
     if channels > IMAGE_MAX_CHANNELS:
-        raise ValueError(f"ops.image_tail: {channels} channels, the kernel normalises at most {IMAGE_MAX_CHANNELS}")
+        raise ValueError(f"{what}: {channels} channels, the kernel normalises at most {IMAGE_MAX_CHANNELS}")
     arr = ctypes.c_float * channels
     std_f32 = arr(*std)
     if any(v == 0 for v in std_f32):
-        raise ValueError(f"ops.image_tail: std evaluated to zero after conversion to float32: {std}")
+        raise ValueError(f"{what}: std evaluated to zero after conversion to float32: {std}")
     return arr(*mean), std_f32
+
+
+def _image_jitter_ops(jitter, what="ops.image_tail"):
+    """The ``(name, factor)`` list of a call, checked: ``(names, int32 codes, double factors)`` for the C ABI."""
+    import ctypes
+    jitter = [(str(name), float(factor)) for name, factor in jitter]
+    names = [name for name, _ in jitter]
+    for name, factor in jitter:
+        if name not in JITTER_CODE:
+            raise ValueError(f"{what}: unknown jitter op {name!r} (one of {sorted(JITTER_CODE)})")
+        if not (0.0 <= factor < float("inf")):
+            raise ValueError(f"{what}: the {name} factor must be a finite number >= 0, got {factor}")
+    if len(set(names)) != len(names):
+        raise ValueError(f"{what}: every jitter op at most once, got {names}")
+    codes = (ctypes.c_int32 * len(jitter))(*[JITTER_CODE[name] for name in names])
+    factors = (ctypes.c_double * len(jitter))(*[factor for _, factor in jitter])
+    return names, codes, factors
 
 
 def image_tail(x, jitter=(), flip=False, to_float=False, mean=None, std=None):
@@ -2277,17 +2295,9 @@ def image_tail(x, jitter=(), flip=False, to_float=False, mean=None, std=None):
             raise ValueError(f"ops.image_tail: uint8 images must be [B, 3, H, W], got {tuple(x.shape)}")
         if (mean is not None or std is not None) and not to_float:
             raise TypeError("ops.image_tail: Normalize takes float images; pass to_float=True for uint8 input")
-    names = [name for name, _ in jitter]
-    for name, factor in jitter:
-        if name not in JITTER_CODE:
-            raise ValueError(f"ops.image_tail: unknown jitter op {name!r} (one of {sorted(JITTER_CODE)})")
-        if not (0.0 <= factor < float("inf")):
-            raise ValueError(f"ops.image_tail: the {name} factor must be a finite number >= 0, got {factor}")
-    if len(set(names)) != len(names):
-        raise ValueError(f"ops.image_tail: every jitter op at most once, got {names}")
+    names, codes, factors = _image_jitter_ops(jitter)
     mean_c, std_c = _image_tail_stats(mean, std, C)
     lib = _lib.load()
-    import ctypes
     if x.dtype == torch.float32:
         if mean_c is None:
             return x
@@ -2308,12 +2318,72 @@ def image_tail(x, jitter=(), flip=False, to_float=False, mean=None, std=None):
     ws, ws_bytes = None, 0
     if "contrast" in names:
         ws, ws_bytes = _lib.workspace("dva_image_tail_workspace_bytes", dev, B)
-    codes = (ctypes.c_int32 * len(jitter))(*[JITTER_CODE[name] for name in names])
-    factors = (ctypes.c_double * len(jitter))(*[factor for _, factor in jitter])
     pixels = B * H * W
     with _timed("image_tail", pixels * (3 + (3 if ws is not None else 0) + (12 if to_float else 3))):
         check(lib.dva_image_tail_u8(ptr(x), B, H, W, codes, factors, len(jitter), int(bool(flip)), int(bool(to_float)),
                                     mean_c, std_c, ptr(out), ptr(ws), ws_bytes, stream_of(x)), "dva_image_tail_u8")
+    return out
+
+
+def image_window(src, index, rollings=None, offsets=None, size=None, jitter=(), flip=False, to_float=False, mean=None,
+                 std=None):
+    """``ops.image_tail`` over windows of source images that are never materialised: the deferred roll, crop and image
+    selection of the online image chains, folded into the tail's one pass.
+
+    ``src`` uint8 ``[N, 3, H, W]``; ``index`` int64 ``[B]`` picks the source image of every output image, ``rollings``
+    int64 ``[B]`` rolls it along W (``None``: no roll), ``offsets`` int64 ``[B, 2]`` holds the (x, y) of the window in
+    the rolled image (``None``: zeros) and ``size = (Wc, Hc)`` its size in the project's (W, H) convention (``None``:
+    the whole image), ``1 <= Wc <= W``, ``1 <= Hc <= H``::
+
+        win[b, c, y, x] = src[index[b], c, offsets[b, 1] + y, (offsets[b, 0] + x - rollings[b]) mod W]
+        out             = image_tail(win, jitter, flip, to_float, mean, std)
+
+    which is ``update_cropping(update_rollings(src[index]))`` of ``SameSettingImageData`` followed by
+    ``ops.image_tail``, bit for bit: the flip mirrors window columns, the contrast mean is taken over the window of
+    each output image alone.  Returns uint8 ``[B, 3, Hc, Wc]`` without ``to_float`` and float32 with it (always a new
+    tensor).  ``index`` / ``rollings`` / ``offsets`` stay on the device and are not read back: an image outside
+    ``[0, N)`` or a window row outside the image is the caller's error, clamped by the kernel for memory safety, its
+    pixels unspecified.  One kernel, two with contrast; no host synchronisation."""
+    what = "ops.image_window"
+    if not torch.is_tensor(src) or not torch.is_tensor(index):
+        raise TypeError(f"{what}: src and index must be tensors")
+    dev = require_device(src, index, rollings, offsets)
+    if src.dim() != 4 or src.shape[1] != 3:
+        raise ValueError(f"{what}: uint8 images must be [N, 3, H, W], got {tuple(src.shape)}")
+    if src.dtype != torch.uint8:
+        raise TypeError(f"{what} takes uint8 images, got {src.dtype}")
+    N, _, H, W = (int(d) for d in src.shape)
+    if index.dim() != 1 or index.dtype != torch.int64:
+        raise TypeError(f"{what}: index must be int64 [B], got {index.dtype} {tuple(index.shape)}")
+    B = int(index.shape[0])
+    if rollings is not None and (rollings.dtype != torch.int64 or tuple(rollings.shape) != (B,)):
+        raise TypeError(f"{what}: rollings must be int64 [{B}], got {rollings.dtype} {tuple(rollings.shape)}")
+    if offsets is not None and (offsets.dtype != torch.int64 or tuple(offsets.shape) != (B, 2)):
+        raise TypeError(f"{what}: offsets must be int64 [{B}, 2], got {offsets.dtype} {tuple(offsets.shape)}")
+    Wc, Hc = (W, H) if size is None else (int(size[0]), int(size[1]))
+    if not (1 <= Wc <= W and 1 <= Hc <= H):
+        raise ValueError(f"{what}: the window (W, H) = {(Wc, Hc)} does not fit the images {(W, H)}")
+    if (mean is not None or std is not None) and not to_float:
+        raise TypeError(f"{what}: Normalize takes float images; pass to_float=True for uint8 input")
+    names, codes, factors = _image_jitter_ops(jitter, what)
+    mean_c, std_c = _image_tail_stats(mean, std, 3, what)
+    lib = _lib.load()
+    out = torch.empty((B, 3, Hc, Wc), dtype=torch.float32 if to_float else torch.uint8, device=dev)
+    if B == 0:
+        return out
+    if N == 0:
+        raise ValueError(f"{what}: {B} images asked of an empty source")
+    src, index = src.contiguous(), index.contiguous()
+    rollings = torch.zeros(B, dtype=torch.int64, device=dev) if rollings is None else rollings.contiguous()
+    offsets = torch.zeros((B, 2), dtype=torch.int64, device=dev) if offsets is None else offsets.contiguous()
+    ws, ws_bytes = None, 0
+    if "contrast" in names:
+        ws, ws_bytes = _lib.workspace("dva_image_window_workspace_bytes", dev, B)
+    pixels = B * Hc * Wc
+    with _timed("image_window", pixels * (3 + (3 if ws is not None else 0) + (12 if to_float else 3))):
+        check(lib.dva_image_window_u8(ptr(src), N, H, W, ptr(index), ptr(rollings), ptr(offsets), B, Wc, Hc, codes,
+                                      factors, len(names), int(bool(flip)), int(bool(to_float)), mean_c, std_c, ptr(out),
+                                      ptr(ws), ws_bytes, stream_of(src)), "dva_image_window_u8")
     return out
 
 

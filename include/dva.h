@@ -1011,9 +1011,28 @@ int dva_elastic_displace(const float* pos, int64_t n, const float* field, const 
  *   dva_image_normalize_f32  out fp32 [B, C, HW] = (x - mean[c]) / std[c] for x fp32 [B, C, HW], 1 <= C <=
  *                            DVA_IMAGE_MAX_CHANNELS (DVA_ERR_UNSUPPORTED beyond); mean / std HOST fp32 [C].  out may
  *                            alias x.
- * B <= 65535 and B H ceil(W / 4) < 2^31 (DVA_ERR_UNSUPPORTED beyond); B = 0 or an empty image is a no-op.  Argument
- * errors (null pointer, negative size, more than three ops, a repeated or unknown op code, a negative factor, a zero
- * in std) return DVA_ERR_INVALID before any HIP call.  Nothing synchronises. */
+ *   dva_image_window_u8      the same tail over a window of a source image that is never materialised (the deferred
+ *                            CenterRoll / CropImageGroups / image selection of the online chains).  src uint8
+ *                            [N, 3, H, W] contiguous; index int64 [B], rolls int64 [B], offsets int64 [B, 2] = (x, y),
+ *                            all DEVICE arrays; the window is Wc x Hc with 1 <= Wc <= W, 1 <= Hc <= H:
+ *                              win[b, c, y, x] = src[index[b], c, offsets[b, 1] + y,
+ *                                                    (offsets[b, 0] + x - rolls[b]) mod W]      (non-negative mod)
+ *                              out             = dva_image_tail_u8(win, ...)
+ *                            that is the roll of image index[b] along W by rolls[b], then the crop at offsets[b], then
+ *                            the tail, with the same op list, flip, to_float, mean and std arguments.  The flip mirrors
+ *                            WINDOW columns (output column x takes window column Wc - 1 - x) and the contrast mean is
+ *                            m_b = f32(S_b) / f32(Hc Wc), S_b the exact int64 sum of gray over the window of output
+ *                            image b alone.  out is uint8 [B, 3, Hc, Wc] without to_float and fp32 with it; it may not
+ *                            alias src.  Launches and workspace (dva_image_window_workspace_bytes(B)) as for
+ *                            dva_image_tail_u8: at most two kernels, integer atomics only.
+ *                            index, rolls and offsets cannot be validated without a synchronisation, so the kernels
+ *                            clamp for memory safety: the source image to [0, N - 1], the source row to [0, H - 1];
+ *                            the column is in range after the mod.  Values outside 0 <= index[b] < N or
+ *                            0 <= offsets[b, 1] <= H - Hc are the caller's error: the result is unspecified, no access
+ *                            leaves src.  Wc > W, Hc > H, Wc < 1, Hc < 1 or N < 1 with B > 0 are DVA_ERR_INVALID.
+ * B <= 65535 and B H ceil(W / 4) < 2^31 (DVA_ERR_UNSUPPORTED beyond; B Hc ceil(Wc / 4) for the window); B = 0 or an
+ * empty image is a no-op.  Argument errors (null pointer, negative size, more than three ops, a repeated or unknown op
+ * code, a negative factor, a zero in std) return DVA_ERR_INVALID before any HIP call.  Nothing synchronises. */
 #define DVA_JITTER_BRIGHTNESS 0
 #define DVA_JITTER_CONTRAST 1
 #define DVA_JITTER_SATURATION 2
@@ -1024,6 +1043,12 @@ int dva_image_tail_u8(const uint8_t* x, int64_t B, int64_t H, int64_t W, const i
                       const float* std, void* out, void* workspace, int64_t workspace_bytes, void* stream);
 int dva_image_normalize_f32(const float* x, int64_t B, int64_t C, int64_t HW, const float* mean, const float* std,
                             float* out, void* stream);
+int64_t dva_image_window_workspace_bytes(int64_t B);
+int dva_image_window_u8(const uint8_t* src, int64_t N, int64_t H, int64_t W, const int64_t* index,
+                        const int64_t* rolls, const int64_t* offsets, int64_t B, int64_t Wc, int64_t Hc,
+                        const int32_t* op_codes, const double* factors, int32_t n_ops, int32_t flip, int32_t to_float,
+                        const float* mean, const float* std, void* out, void* workspace, int64_t workspace_bytes,
+                        void* stream);
 
 /* ------------------------------------------------------------------------------------------ *
  * The tail of the segmentation step (segloss.hip).  Replaces F.log_softmax + F.nll_loss and lovasz_softmax of

@@ -118,6 +118,10 @@ SIGNATURES = {
     "dva_rowbn_apply": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, _i32, _vp]),
     "dva_rowbn_bwd_stats": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _i32, _vp]),
     "dva_rowbn_bwd_apply": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _i32, _vp]),
+    "dva_emod_rows_grid": (ctypes.c_int, [_i64, _i32, _i32]),
+    "dva_emod_rows_fwd": (ctypes.c_int, [_vp] * 6 + [_i64, _i32, _i32, _f32, _i32, _vp]),
+    "dva_emod_rows_bwd": (ctypes.c_int, [_vp] * 11 + [_i64, _i32, _i32, _f32, _f32, _i32, _vp]),
+    "dva_emod_rows_dw_reduce": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
     "dva_bn_finalize": (ctypes.c_int, [_vp, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _i32, _i32, _vp,
                                        _vp]),
     "dva_scale_f64": (ctypes.c_int, [_vp, ctypes.c_double, _vp, _i32, _vp]),

@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "dva_common.h"
+#include "rowbn_math.h"
 
 namespace dva {
 
@@ -68,9 +69,9 @@ __global__ __launch_bounds__(256) void rowbn_apply_kernel(const T* __restrict__ 
   for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total;
        t += (int64_t)gridDim.x * blockDim.x) {
     const int c = (int)(t % C);
-    const float a = (Elt<T>::ld(y, t) - bn[c]) * bn[C + c];
-    const float z = a * bn[2 * C + c] + bn[3 * C + c];
-    Elt<T>::st(out, t, z > 0.f ? z : slope * z);
+    const float a = rowbn::norm(Elt<T>::ld(y, t), bn[c], bn[C + c]);
+    const float z = rowbn::affine(a, bn[2 * C + c], bn[3 * C + c]);
+    Elt<T>::st(out, t, rowbn::act(z, slope));
   }
 }
 
@@ -82,9 +83,9 @@ __global__ __launch_bounds__(256) void rowbn_bwd_stats_kernel(const T* __restric
                                                                int C, float slope) {
   extern __shared__ double s_red[];
   row_sums<T>(R, C, sums, s_red, [&](int64_t r, int c, double& f1, double& f2) {
-    const float a = (Elt<T>::ld(y, r * C + c) - bn[c]) * bn[C + c];
-    const float z = a * bn[2 * C + c] + bn[3 * C + c];
-    const float dz = Elt<T>::ld(gout, r * C + c) * (z > 0.f ? 1.f : slope);
+    const float a = rowbn::norm(Elt<T>::ld(y, r * C + c), bn[c], bn[C + c]);
+    const float z = rowbn::affine(a, bn[2 * C + c], bn[3 * C + c]);
+    const float dz = Elt<T>::ld(gout, r * C + c) * rowbn::dact(z, slope);
     f1 = (double)dz;
     f2 = (double)(dz * a);
   });
@@ -101,11 +102,11 @@ __global__ __launch_bounds__(256) void rowbn_bwd_apply_kernel(
        t += (int64_t)gridDim.x * blockDim.x) {
     const int64_t r = t / C;
     const int c = (int)(t - r * C);
-    const float a = (Elt<T>::ld(y, t) - bn[c]) * bn[C + c];
-    const float z = a * bn[2 * C + c] + bn[3 * C + c];
-    const float dz = Elt<T>::ld(gout, t) * (z > 0.f ? 1.f : slope);
+    const float a = rowbn::norm(Elt<T>::ld(y, t), bn[c], bn[C + c]);
+    const float z = rowbn::affine(a, bn[2 * C + c], bn[3 * C + c]);
+    const float dz = Elt<T>::ld(gout, t) * rowbn::dact(z, slope);
     const float w = counts ? (float)counts[r] : 1.f;
-    Elt<T>::st(dy, t, bn[2 * C + c] * bn[C + c] * (dz - w * sm[c] - w * a * sm[C + c]));
+    Elt<T>::st(dy, t, rowbn::grad_y(dz, a, w, bn[2 * C + c], bn[C + c], sm[c], sm[C + c]));
   }
 }
 
@@ -216,9 +217,9 @@ __global__ __launch_bounds__(256) void rowbn_sums_vec_kernel(const T* __restrict
         RVec<T>::unpack(gr[u], g);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
-          const float a = (v[k] - mu[k]) * is[k];
-          const float z = a * ga[k] + be[k];
-          const float dz = w[u] * g[k] * (z > 0.f ? 1.f : slope);
+          const float a = rowbn::norm(v[k], mu[k], is[k]);
+          const float z = rowbn::affine(a, ga[k], be[k]);
+          const float dz = w[u] * g[k] * rowbn::dact(z, slope);
           p0[k] += dz;
           p1[k] = fmaf(dz, a, p1[k]);
         }
@@ -292,8 +293,8 @@ __global__ __launch_bounds__(256) void rowbn_apply_vec_kernel(const T* __restric
     if (MODE == 0) {
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
-        const float z = (v[k] - mu[k]) * is[k] * ga[k] + be[k];
-        o[k] = z > 0.f ? z : slope * z;
+        const float z = rowbn::affine(rowbn::norm(v[k], mu[k], is[k]), ga[k], be[k]);
+        o[k] = rowbn::act(z, slope);
       }
     } else {
       float g[VEC];
@@ -301,10 +302,10 @@ __global__ __launch_bounds__(256) void rowbn_apply_vec_kernel(const T* __restric
       const float w = counts ? (float)counts[r] : 1.f;
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
-        const float a = (v[k] - mu[k]) * is[k];
-        const float z = a * ga[k] + be[k];
-        const float dz = g[k] * (z > 0.f ? 1.f : slope);
-        o[k] = ga[k] * is[k] * (dz - w * s0[k] - w * a * s1[k]);
+        const float a = rowbn::norm(v[k], mu[k], is[k]);
+        const float z = rowbn::affine(a, ga[k], be[k]);
+        const float dz = g[k] * rowbn::dact(z, slope);
+        o[k] = rowbn::grad_y(dz, a, w, ga[k], is[k], s0[k], s1[k]);
       }
     }
     *reinterpret_cast<raw_t*>(out + r * C + c0) = RVec<T>::pack(o);

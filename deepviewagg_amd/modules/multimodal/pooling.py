@@ -74,7 +74,7 @@ def batchnorm_act_rows(y, bn, slope, counts=None, n=None):
                          mean, invstd, n, batch_stats, slope)
 
 
-def mlp_on_gathered_rows(mlp, rows, counts, n_views=None, first_linear_done=False):
+def mlp_on_gathered_rows(mlp, rows, counts, n_views=None, first_linear_done=False, map_rows=True):
     """Evaluate ``mlp(rows[row_idx])`` WITHOUT gathering: returns ``out_rows`` such that
     ``out_rows[row_idx] == mlp(rows[row_idx])`` row for row.
 
@@ -85,7 +85,15 @@ def mlp_on_gathered_rows(mlp, rows, counts, n_views=None, first_linear_done=Fals
     per-view evaluation of the reference (pooling.py:245,275) and no [P, C] tensor is materialised.
     Backward is plain autograd over the [R, C] tensors.
     ``first_linear_done``: ``rows`` already are the output of the first block's Linear (hoisted by the caller).
+    ``map_rows``: the rows are feature-map rows (not V-sized materialised views): a two-block MLP of widths 32 / 64 on
+    bf16 rows in train mode then runs as six fused row passes (``ops.emod_rows``) instead of the composition below.
     """
+    if ops.EMOD_FUSED and map_rows and not first_linear_done and len(mlp) == 2:
+        linears, norms = [b[0] for b in mlp], [b[1].batch_norm for b in mlp]
+        slopes = [_leaky_slope(b[2]) for b in mlp]
+        if None not in slopes and ops.emod_rows_serves(rows, counts, linears, norms):
+            n = float(n_views if n_views is not None else (counts.sum() if counts is not None else rows.shape[0]))
+            return ops.emod_rows(rows, counts, linears, norms, slopes, n)
     x = rows
     n = None
     for i, block in enumerate(mlp):
@@ -107,7 +115,7 @@ def _mlp_rows(mlp, x):
     """``mlp(x)`` for a materialised [V, C] tensor through the row kernels (every row counts once): the library
     BatchNorm path is two orders of magnitude slower at V ~ 3e7 rows (64-bit indexing)."""
     if x.is_cuda and x.dim() == 2 and x.shape[0] > 0:
-        return mlp_on_gathered_rows(mlp, x, None, x.shape[0])
+        return mlp_on_gathered_rows(mlp, x, None, x.shape[0], map_rows=False)
     return mlp(x)
 
 

@@ -1470,6 +1470,158 @@ def rowbn_act(y, counts, gamma, beta, mean, invstd, n, batch_stats, slope, bn_ta
 
 
 # ---------------------------------------------------------------------------------------------
+# E_mod on the map rows, fused: two blocks of Linear + weighted BatchNorm + LeakyReLU in six row passes
+# (csrc/emod_rows.hip) instead of library GEMMs, casts and rowbn passes
+# ---------------------------------------------------------------------------------------------
+EMOD_FUSED = True             # False: pooling.mlp_on_gathered_rows keeps the composition (the A/B partner in tests)
+EMOD_ROWS_MAX_BLOCKS = 0      # test hook: cap of the launch grids of the fused row kernels (0: the default grid)
+EMOD_ROWS_WIDTHS = (32, 64)
+EMOD_ROWS_MAX_BYTES = 0xfffffff0      # (R + 32) * 128 stays below it: 32-bit byte offsets, the rows of a last tile included
+
+
+def emod_rows_serves(rows, counts, linears, norms):
+    """Whether ``emod_rows`` covers this MLP on these rows: two blocks of Linear (no bias, fp32 weight, widths 32 / 64)
+    and train-mode BatchNorm1d (fp32 parameters and buffers, a momentum) on contiguous 16-byte-aligned bf16 rows."""
+    if len(linears) != 2 or not isinstance(rows, torch.Tensor):
+        return False
+    if not (rows.is_cuda and rows.dim() == 2 and rows.dtype == torch.bfloat16 and rows.is_contiguous()
+            and rows.data_ptr() % 16 == 0 and rows.shape[0] > 0
+            and (rows.shape[0] + 32) * 128 <= EMOD_ROWS_MAX_BYTES):
+        return False
+    if torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') != torch.bfloat16:
+        return False
+    if counts is not None and not (counts.dtype == torch.int32 and counts.is_cuda and counts.is_contiguous()
+                                   and counts.shape == (rows.shape[0],)):
+        return False
+    c_in = rows.shape[1]
+    for lin, bn in zip(linears, norms):
+        w = lin.weight
+        if not (lin.bias is None and w.dtype == torch.float32 and w.is_cuda and w.is_contiguous()
+                and w.data_ptr() % 16 == 0 and w.shape[1] == c_in and c_in in EMOD_ROWS_WIDTHS
+                and w.shape[0] in EMOD_ROWS_WIDTHS):
+            return False
+        if not (isinstance(bn, torch.nn.BatchNorm1d) and bn.training and bn.momentum is not None
+                and bn.num_features == w.shape[0]
+                and all(t is None or (t.dtype == torch.float32 and t.is_cuda)
+                        for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var))):
+            return False
+        c_in = w.shape[0]
+    return True
+
+
+def emod_rows_forward(x, counts, w_a, w_b, bn_a, bn_b, n, slope_a, slope_b, max_blocks=0):
+    """The three forward passes; returns ``out`` and what the backward reads: y_a, y_b, the two BatchNorm tables
+    (the running statistics of ``bn_a`` / ``bn_b`` are updated as the modules do)."""
+    lib = _lib.load()
+    require_device(x, counts, w_a, w_b)
+    R, c_i = x.shape
+    c_m, c_o = w_a.shape[0], w_b.shape[0]
+    st, dev, mb = stream_of(x), x.device, int(max_blocks)
+    sums_a = zeros_small(2 * c_m, torch.float64, dev)
+    y_a = torch.empty((R, c_m), dtype=torch.bfloat16, device=dev)
+    with _timed("emod_rows_fwd", R * (c_i + c_m) * 2):
+        check(lib.dva_emod_rows_fwd(ptr(x), ptr(w_a), None, ptr(counts), ptr(y_a), ptr(sums_a), R, c_i, c_m, 0.0, mb,
+                                    st), "dva_emod_rows_fwd")
+    tab_a = bn_table(sums_a, n, bn_a, True)
+    sums_b = zeros_small(2 * c_o, torch.float64, dev)
+    y_b = torch.empty((R, c_o), dtype=torch.bfloat16, device=dev)
+    with _timed("emod_rows_fwd", R * (c_m + c_o) * 2):
+        check(lib.dva_emod_rows_fwd(ptr(y_a), ptr(w_b), ptr(tab_a), ptr(counts), ptr(y_b), ptr(sums_b), R, c_m, c_o,
+                                    float(slope_a), mb, st), "dva_emod_rows_fwd")
+    tab_b = bn_table(sums_b, n, bn_b, True)
+    out = torch.empty_like(y_b)
+    with _timed("emod_rows_fwd", R * c_o * 4):
+        check(lib.dva_rowbn_apply(ptr(y_b), ptr(tab_b), ptr(out), R, c_o, float(slope_b), _lib.DVA_BF16, st),
+              "dva_rowbn_apply")
+    return dict(out=out, y_a=y_a, y_b=y_b, tab_a=tab_a, tab_b=tab_b, sums_a=sums_a, sums_b=sums_b)
+
+
+def emod_rows_backward(gout, x, counts, w_a, w_b, fwd, n, slope_a, slope_b, need_gx=True, max_blocks=0):
+    """The three backward passes from ``gout`` [R, C_out] bf16 and the forward's tensors; returns g_x (None unless
+    ``need_gx``), the six parameter gradients and the stored intermediate g_a."""
+    lib = _lib.load()
+    R, c_i = x.shape
+    c_m, c_o = w_a.shape[0], w_b.shape[0]
+    st, dev, mb = stream_of(x), x.device, int(max_blocks)
+    inv_n = 1.0 / max(float(n), 1.0)      # the clamped normaliser of bn_table
+    y_a, y_b, tab_a, tab_b = fwd["y_a"], fwd["y_b"], fwd["tab_a"], fwd["tab_b"]
+    small = torch.empty(4 * (c_o + c_m), dtype=torch.float32, device=dev)    # per layer: S/n [2C] | d gamma | d beta
+    sm_b, dg_b, db_b = small[:2 * c_o], small[2 * c_o:3 * c_o], small[3 * c_o:4 * c_o]
+    o = 4 * c_o
+    sm_a, dg_a, db_a = small[o:o + 2 * c_m], small[o + 2 * c_m:o + 3 * c_m], small[o + 3 * c_m:]
+    sums_b = zeros_small(2 * c_o, torch.float64, dev)
+    with _timed("emod_rows_bwd", R * c_o * 4):
+        check(lib.dva_rowbn_bwd_stats(ptr(gout), ptr(y_b), ptr(tab_b), ptr(sums_b), R, c_o, float(slope_b),
+                                      _lib.DVA_BF16, st), "dva_rowbn_bwd_stats")
+    check(lib.dva_bn_bwd_consts(ptr(sums_b), None, inv_n, 0, ptr(sm_b), ptr(dg_b), ptr(db_b), c_o, st),
+          "dva_bn_bwd_consts")
+    parts = int(lib.dva_emod_rows_grid(R, 1, mb))
+    n_b, n_a = c_o * c_m, c_m * c_i
+    ws = torch.empty(parts * (n_b + n_a), dtype=torch.float32, device=dev)
+    ws_b, ws_a = ws[:parts * n_b], ws[parts * n_b:]
+    g_a = torch.empty((R, c_m), dtype=torch.bfloat16, device=dev)
+    sums_a = zeros_small(2 * c_m, torch.float64, dev)
+    with _timed("emod_rows_bwd", R * (2 * c_o + 2 * c_m) * 2 + parts * n_b * 4):
+        check(lib.dva_emod_rows_bwd(ptr(gout), ptr(y_b), ptr(tab_b), ptr(sm_b), ptr(counts), ptr(y_a), ptr(tab_a),
+                                    ptr(w_b), ptr(g_a), ptr(ws_b), ptr(sums_a), R, c_m, c_o, float(slope_b),
+                                    float(slope_a), mb, st), "dva_emod_rows_bwd")
+    check(lib.dva_bn_bwd_consts(ptr(sums_a), None, inv_n, 0, ptr(sm_a), ptr(dg_a), ptr(db_a), c_m, st),
+          "dva_bn_bwd_consts")
+    g_x = torch.empty((R, c_i), dtype=torch.bfloat16, device=dev) if need_gx else None
+    with _timed("emod_rows_bwd", R * (2 * c_m + (2 if need_gx else 1) * c_i) * 2 + parts * n_a * 4):
+        check(lib.dva_emod_rows_bwd(ptr(g_a), ptr(y_a), ptr(tab_a), ptr(sm_a), ptr(counts), ptr(x), None, ptr(w_a),
+                                    ptr(g_x), ptr(ws_a), None, R, c_i, c_m, float(slope_a), 0.0, mb, st),
+              "dva_emod_rows_bwd")
+    dw = torch.empty(n_b + n_a, dtype=torch.float32, device=dev)
+    with _timed("emod_rows_bwd", (parts + 1) * (n_b + n_a) * 4):
+        check(lib.dva_emod_rows_dw_reduce(ptr(ws_b), n_b, parts, ptr(dw), ptr(ws_a), n_a, parts, ptr(dw[n_b:]), st),
+              "dva_emod_rows_dw_reduce")
+    return dict(g_x=g_x, g_a=g_a, dw_a=dw[n_b:].view(c_m, c_i), dw_b=dw[:n_b].view(c_o, c_m), dgamma_a=dg_a,
+                dbeta_a=db_a, dgamma_b=dg_b, dbeta_b=db_b, sm_a=sm_a, sm_b=sm_b)
+
+
+class _EmodRows(torch.autograd.Function):
+    """``mlp(rows[row_idx])`` evaluated on the map rows (``pooling.mlp_on_gathered_rows``) for a two-block MLP the
+    fused row kernels cover (``emod_rows_serves``)."""
+
+    @staticmethod
+    def forward(ctx, x, counts, w_a, gamma_a, beta_a, w_b, gamma_b, beta_b, bn_a, bn_b, n, slope_a, slope_b,
+                max_blocks):
+        fwd = emod_rows_forward(x, counts, w_a, w_b, bn_a, bn_b, n, slope_a, slope_b, max_blocks)
+        ctx.save_for_backward(x, w_a, w_b, fwd["y_a"], fwd["y_b"], fwd["tab_a"], fwd["tab_b"],
+                              *([counts] if counts is not None else []))
+        ctx.meta = (float(n), float(slope_a), float(slope_b), int(max_blocks))
+        return fwd["out"]
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, w_a, w_b, y_a, y_b, tab_a, tab_b = ctx.saved_tensors[:7]
+        counts = ctx.saved_tensors[7] if len(ctx.saved_tensors) > 7 else None
+        n, slope_a, slope_b, mb = ctx.meta
+        gout = gout.contiguous().to(torch.bfloat16)
+        if gout.data_ptr() % 16:
+            gout = gout.clone()
+        need = ctx.needs_input_grad
+        g = emod_rows_backward(gout, x, counts, w_a, w_b, dict(y_a=y_a, y_b=y_b, tab_a=tab_a, tab_b=tab_b), n, slope_a,
+                               slope_b, need[0], mb)
+        return (g["g_x"], None, g["dw_a"] if need[2] else None, g["dgamma_a"] if need[3] else None,
+                g["dbeta_a"] if need[4] else None, g["dw_b"] if need[5] else None,
+                g["dgamma_b"] if need[6] else None, g["dbeta_b"] if need[7] else None, None, None, None, None, None,
+                None)
+
+
+def emod_rows(x, counts, linears, norms, slopes, n, max_blocks=None):
+    """Two blocks of Linear -> weighted BatchNorm1d -> LeakyReLU on the rows ``x`` [R, C] (bf16), ``counts`` views per
+    row (None: one each), ``n`` views in all: six row passes (csrc/emod_rows.hip).  ``emod_rows_serves`` says when."""
+    (lin_a, lin_b), (bn_a, bn_b) = linears, norms
+    mb = EMOD_ROWS_MAX_BLOCKS if max_blocks is None else max_blocks
+    return _EmodRows.apply(x, counts, lin_a.weight, bn_a.weight if bn_a.affine else None,
+                           bn_a.bias if bn_a.affine else None, lin_b.weight, bn_b.weight if bn_b.affine else None,
+                           bn_b.bias if bn_b.affine else None, bn_a, bn_b, float(n), float(slopes[0]),
+                           float(slopes[1]), int(mb))
+
+
+# ---------------------------------------------------------------------------------------------
 # voxel parent index after a strided sparse 3D convolution (modules.py:176-198)
 # ---------------------------------------------------------------------------------------------
 

@@ -421,6 +421,38 @@ int dva_rowbn_bwd_apply(const void* grad_out, const void* y, const int32_t* coun
                         const float* sm, void* grad_y, int64_t R, int32_t C, float slope, int32_t dtype,
                         void* stream);
 
+/* ------------------------------------------------------------------------------------------ *
+ * E_mod on the map rows as fused row kernels (csrc/emod_rows.hip): the two-block MLP [Linear (no bias) ->
+ * weighted BatchNorm1d -> LeakyReLU] x 2 in train mode on bf16 rows, widths 32 or 64, matrix products on
+ * v_mfma_f32_32x32x16_bf16.  The Linear of a block, the BatchNorm + activation of the block before it and the
+ * statistics of the BatchNorm after it are one pass; dva_bn_finalize / dva_bn_bwd_consts run between the
+ * passes, dva_rowbn_apply is the last forward pass and dva_rowbn_bwd_stats the first backward pass.  All
+ * rows bf16, contiguous, 16-byte aligned; W fp32 [C_out][C_in] (rounded to bf16 in the kernel); bn / bn_in
+ * fp32 [4][C] as above; counts int32 [R] nullable; (R + 32) * 128 bytes must stay below 2^32
+ * (DVA_ERR_UNSUPPORTED otherwise, as for a width other than 32 / 64).  max_blocks > 0 caps the launch grid
+ * (0 = the default grid); dva_emod_rows_grid tells the grid a call will use.
+ * ------------------------------------------------------------------------------------------ */
+int dva_emod_rows_grid(int64_t R, int32_t backward, int32_t max_blocks);
+/* y [R, C_out] = bf16(op(in) W^T), op = identity (bn_in NULL) or bf16(leaky(BatchNorm(in))) with the
+ * constants bn_in [4][C_in] and negative slope `slope`; sums (caller-zeroed double[2 * C_out]) += sum_r
+ * counts_r y_r | sum_r counts_r y_r^2 of the rounded y. */
+int dva_emod_rows_fwd(const void* in, const float* W, const float* bn_in, const int32_t* counts, void* y,
+                      double* sums, int64_t R, int32_t C_in, int32_t C_out, float slope, int32_t max_blocks,
+                      void* stream);
+/* One block backwards.  dy [R, C_out] = bf16 of dva_rowbn_bwd_apply's formula from grad_in, y, bn, sm, counts
+ * and `slope` (never stored); dw_ws fp32 [grid][C_out][C_in]: every block writes the partial sum of
+ * dy^T op(x_in) over its rows; grad_x [R, C_in] = bf16(dy W), nullable when bn_in is NULL (then no product
+ * is formed).  bn_in non-NULL: op(x_in) = bf16(leaky(BatchNorm(x_in))) with slope_in, and sums (caller-zeroed
+ * double[2 * C_in]) += S1 | S2 of dz = grad_x leaky'(z_in) as dva_rowbn_bwd_stats defines them. */
+int dva_emod_rows_bwd(const void* grad_in, const void* y, const float* bn, const float* sm, const int32_t* counts,
+                      const void* x_in, const float* bn_in, const float* W, void* grad_x, float* dw_ws,
+                      double* sums, int64_t R, int32_t C_in, int32_t C_out, float slope, float slope_in,
+                      int32_t max_blocks, void* stream);
+/* out_a[i] = sum_p ws_a[p][i] (i < n_a, p < parts_a), the same for b: the partials in a fixed order (two
+ * calls give the same bits).  n_a is a multiple of 16. */
+int dva_emod_rows_dw_reduce(const float* ws_a, int32_t n_a, int32_t parts_a, float* out_a, const float* ws_b,
+                            int32_t n_b, int32_t parts_b, float* out_b, void* stream);
+
 /* BatchNorm1d bookkeeping between two passes (one launch): sums = double[2*C] (sum | sum of squares over m
  * rows) -> bn = fp32 [4][C] = mean | invstd | gamma | beta.  training: batch statistics (biased variance),
  * running_mean / running_var (nullable pair) updated with `momentum` using the unbiased variance,

@@ -903,13 +903,17 @@ static bool team_geometry(int C, int G, int64_t N, int64_t V, TeamGeom* tg) {
 
 static inline int grid_cap(int64_t blocks) { return capped_grid(blocks, 1, 256 * 16); }
 
+// the team kernels move whole 16-byte vectors: a base pointer that is no multiple of 16 takes the generic kernels
+// (a NULL pointer -- a tensor the form does not have -- passes)
+static inline bool aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
+
 template <typename T>
 static int fwd_impl(const void* val, const int32_t* row_idx, const float* compat, const int64_t* ptr,
                     const float* gw,
                     const float* gb, void* out, float* att, float* gate, int32_t* amax, int64_t N,
                     int64_t V_hint, int C, int G, int scaling, float eps, int algo, hipStream_t s) {
   TeamGeom tg;
-  const bool team_ok = team_geometry<T>(C, G, N, V_hint, &tg);
+  const bool team_ok = team_geometry<T>(C, G, N, V_hint, &tg) && aligned16(val) && aligned16(out);
   if (algo == 2 && !team_ok) return DVA_ERR_UNSUPPORTED;
   if (algo != 1 && team_ok) {
     const int tpb = 256 / tg.ts;
@@ -939,7 +943,7 @@ static int bwd_impl(const void* gout, const void* val, const int32_t* row_idx, f
                     void* gval, float* gcompat, float* gwb, float* rec, int rs, int64_t N, int64_t V_hint,
                     int C, int G, int scaling, int algo, hipStream_t s) {
   TeamGeom tg;
-  const bool team_ok = team_geometry<T>(C, G, N, V_hint, &tg);
+  const bool team_ok = team_geometry<T>(C, G, N, V_hint, &tg) && aligned16(gout) && aligned16(val) && aligned16(gval);
   if (algo == 2 && !team_ok) return DVA_ERR_UNSUPPORTED;
   if (rec && !(algo != 1 && team_ok)) return DVA_ERR_UNSUPPORTED;  // records come from the team kernel
   if (algo != 1 && team_ok) {
@@ -1561,6 +1565,20 @@ int dva_view_gather_attention_bwd(const void* grad_out, const void* rows, const 
   return attention_bwd_entry(grad_out, rows, row_idx, grad_rows, compat, att, gate, amax, ptr, gate_w,
                              gate_b, nullptr, grad_compat, grad_gate_wb, view_rec, rec_stride, n_points,
                              n_views, C, G, scaling, dtype, algo, stream);
+}
+
+int dva_view_attention_geometry(int32_t C, int32_t G, int64_t n_points, int64_t n_views, int32_t dtype, int32_t* lpr,
+                                int32_t* rows) {
+  if (C <= 0 || G <= 0 || G > C || n_points < 0 || n_views < 0 || !lpr || !rows) return DVA_ERR_INVALID;
+  TeamGeom tg = {0, 0, 0, 0};
+  bool team;
+  if (dtype == DVA_F32) team = team_geometry<float>(C, G, n_points, n_views, &tg);
+  else if (dtype == DVA_BF16) team = team_geometry<bf16_t>(C, G, n_points, n_views, &tg);
+  else if (dtype == DVA_F16) team = team_geometry<f16_t>(C, G, n_points, n_views, &tg);
+  else return DVA_ERR_INVALID;
+  *lpr = team ? tg.lpr : 0;
+  *rows = team ? tg.rows : 0;
+  return team ? 1 : 0;
 }
 
 int dva_view_gather_rows_grad_rec16_to(const void* grad_out, const int32_t* perm, const int32_t* row_ptr,

@@ -1298,7 +1298,9 @@ class _ViewGatherAttention(torch.autograd.Function):
         # sector per view instead of scattered reads of view_point, att and gate
         rs = ((G + 1 + 7) // 8) * 8
         rec = None
-        if use_plan and ATTENTION_ALGO != 1 and _team_records_ok(C, G, rows.dtype):
+        # (the team kernel takes 16-byte aligned value and gradient rows only: csrc/attention.hip bwd_impl)
+        if (use_plan and ATTENTION_ALGO != 1 and _team_records_ok(C, G, rows.dtype) and rows.data_ptr() % 16 == 0
+                and gout.data_ptr() % 16 == 0):
             rec = torch.empty((V, rs), dtype=torch.float32, device=rows.device)
         with _timed("view_gather_attention_bwd",
                     V * (C * es + 4 + 2 * G * 4 + (C * 4 * 2 if grows is not None else 0)

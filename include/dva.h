@@ -202,6 +202,16 @@ int dva_view_gather_attention_bwd(const void* grad_out, const void* rows, const 
                                   int64_t n_points, int64_t n_views, int32_t C, int32_t G,
                                   int32_t scaling, int32_t dtype, int32_t algo, void* stream);
 
+/* Which kernels a view-attention call of this shape runs (host only: nothing is launched, no device is touched): the
+ * answer of the geometry rule the four entries above dispatch on.  Returns 1 = the wavefront-team kernels, with *lpr =
+ * lanes per view row (C / 4 for fp32, C / 8 for bf16 / fp16) and *rows = view rows in flight per team, which shrinks
+ * with the average segment n_views / n_points; 0 = the generic kernels (*lpr = *rows = 0); DVA_ERR_INVALID otherwise.
+ * (lpr, rows) in {(8, 8), (16, 4), (8, 4), (16, 2)} are compiled instances, every other pair takes the instance with
+ * a run-time geometry.  A call whose val / rows, out, grad_out or grad_val pointer is no multiple of 16 bytes, or
+ * whose algo is 1, runs the generic kernels whatever the shape. */
+int dva_view_attention_geometry(int32_t C, int32_t G, int64_t n_points, int64_t n_views, int32_t dtype, int32_t* lpr,
+                                int32_t* rows);
+
 /* Transposed view of a row index (views grouped by the feature-map row they read): the backward of
  * the gather in image.py:1285 (index_select -> index_add) as a CSR over rows.
  * row_idx int32 [n_views] with values in [0, n_rows).  Outputs: perm int32 [n_views] (view ids

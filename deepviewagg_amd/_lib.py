@@ -323,6 +323,15 @@ def workspace(query_name, device, *args):
     return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
 
 
+# the kernels address a whole array with 32-bit byte offsets into one buffer descriptor (the last 16-byte access included)
+BUFFER_BYTES_MAX = (1 << 32) - 16
+
+
+def fits_buffer(*nbytes):
+    """Does every one of these array sizes (bytes) stay below ``BUFFER_BYTES_MAX``?"""
+    return all(n < BUFFER_BYTES_MAX for n in nbytes)
+
+
 def ptr(t):
     """Device pointer of a tensor (None -> NULL)."""
     return None if t is None else ctypes.c_void_p(t.data_ptr())

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib, ops, fused_chain, fused_deepset
 from ._lib import check, ptr, require_device, stream_of
-from .fused_chain_bwd import Arena, chain_epilogue
+from .fused_chain_bwd import Arena, bn_bwd_consts, chain_epilogue
 
 _POS = {}
 # BatchNorm_a backward inside the anchor scatter: at the level of the anchor (Gram matrix of the tap weights x the four
@@ -85,8 +85,7 @@ def size_limits_ok(V, R, N, C):
     table [V, 4] int32, the 64-byte rows the DeepSetFeat chain hands between its backward passes (x_map rows are 32
     bytes), the map rows Y [R, C] bf16 and the per-point rows [N, max(2 C, 128)].  z_a / dy_a [V, C] bf16 take one
     descriptor per TILE and have no such limit (4 GiB at V = 2^25, C = 64)."""
-    lim = (1 << 32) - 16
-    return 4 * V < (1 << 31) and V * 64 < lim and R * C * 2 < lim and N * max(C * 2, 128) < lim
+    return 4 * V < (1 << 31) and _lib.fits_buffer(V * 64, R * C * 2, N * max(C * 2, 128))
 
 
 class _EmodPool(torch.autograd.Function):
@@ -146,9 +145,8 @@ class _EmodPool(torch.autograd.Function):
                                         ptr(w4), ptr(eops), ptr(tab_a), ptr(tab_b), ptr(csr_idx), ptr(S.gw), ptr(S.gb),
                                         ptr(out), ptr(scores), ptr(za), N, V, R, C, G, int(scaling), float(eps), st),
                   "dva_emod_attn_fwd")
-        ctx.save_for_backward(Y, rows4, w4, x_map, csr_idx, S.vp, S.tiles, S.n_tiles, S.wops, S.t_add, S.zstar, S.arg,
-                              S.mom, S.bn1, S.bn2, S.bn5, S.bn6, out, scores, S.bs, S.gw, S.gb, S.W1, eops, tab_a, tab_b,
-                              za)
+        ctx.save_for_backward(Y, rows4, w4, x_map, csr_idx, *S.saved(), out, scores, S.bs, S.gw, S.gb, S.W1, eops, tab_a,
+                              tab_b, za)
         ctx.module = module
         ctx.set_saved = S.set_saved
         ctx.training = training
@@ -159,13 +157,10 @@ class _EmodPool(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        from types import SimpleNamespace
         lib = _lib.load()
-        if ctx.set_saved is None:
-            raise RuntimeError("the recompute chain's backward ran twice on the same graph (retain_graph is not "
-                               "supported on this path)")
-        (Y, rows4, w4, x_map, csr_idx, vp, tiles, n_tiles, wops, t_add, zstar, arg, mom, bn1, bn2, bn5, bn6, out,
-         scores, bs, gw, gb, W1, eops, tab_a, tab_b, za) = ctx.saved_tensors
+        set_saved = fused_chain.take_set_saved(ctx)
+        (Y, rows4, w4, x_map, csr_idx, *chain, out, scores, bs, gw, gb, W1, eops, tab_a, tab_b,
+         za) = ctx.saved_tensors
         module, training = ctx.module, ctx.training
         scaling, eps = ctx.meta
         gate = module.G
@@ -174,9 +169,8 @@ class _EmodPool(torch.autograd.Function):
         G = module.E_score.weight.shape[0]
         st = stream_of(x_map)
         gout = gout.contiguous().to(torch.bfloat16)
-        inv_m = (1.0 / float(max(V, 1))) if training else 0.0
-        S = SimpleNamespace(vp=vp, tiles=tiles, n_tiles=n_tiles, wops=wops, t_add=t_add, zstar=zstar, arg=arg, mom=mom,
-                            bn1=bn1, bn2=bn2, bn5=bn5, bn6=bn6, W1=W1, G=G, training=training)
+        S = fused_chain.ChainState.restore(chain, W1=W1, G=G, training=training)
+        vp, tiles, n_tiles = S.vp, S.tiles, S.n_tiles
         arena = Arena(dev, n_floats=(1 << 15) + C * C)      # + dW_b (65 536 floats at C_out = 256)
         za_bytes = V * C * 2
         if za is None:      # forward ran in eval mode: the backward passes read the stored z_a, build it now
@@ -186,10 +180,7 @@ class _EmodPool(torch.autograd.Function):
                                      ptr(za), V, R, C, st), "dva_emod_stats")
 
         def consts(stats, tab):
-            sm, dg, db = arena.take(2 * C), arena.take(C), arena.take(C)
-            check(lib.dva_bn_bwd_consts(ptr(stats), ptr(tab), inv_m, 1, ptr(sm), ptr(dg), ptr(db), C, st),
-                  "dva_bn_bwd_consts")
-            return sm, dg, db
+            return bn_bwd_consts(lib, arena, stats, tab, float(max(V, 1)), training, st, width=C)
         # ---- attention + gate backward (scores from the forward, E_mod re-evaluated): dc, view records, S of BatchNorm_b
         dc = torch.empty((V, 4), dtype=torch.float32, device=dev)
         rec = torch.empty((V, 4), dtype=torch.int32, device=dev)
@@ -228,8 +219,7 @@ class _EmodPool(torch.autograd.Function):
             dY = ops.bilinear_scatter(da, rows4, w4, ctx.anchors, ctx.bhw, plan=ctx.anchor_plan,
                                       bn_backward=(za, tab_a, sm_a, Y if ANCHOR_GRAM else None)).to(Y.dtype)
         del da, za
-        grads = chain_epilogue(lib, arena, S, module, x_map, csr_idx, dc, gwb, ctx.set_saved)
-        ctx.set_saved = None
+        grads = chain_epilogue(lib, arena, S, module, x_map, csr_idx, dc, gwb, set_saved)
         return (dY, None, None, None, None, None, None, None, None, None, dg_a, db_a, dWb, dg_b, db_b) + tuple(grads)
 
 

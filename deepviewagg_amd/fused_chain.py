@@ -15,12 +15,13 @@ Under float16 the value rows, the pooled output and the rows gradient are fp16; 
 operands (its [V, 32] gradient rows carry the GradScaler factor, which fp16 cannot hold).
 The per-point set branch (``mlp_set`` on N rows) runs on the same kind of kernels (``csrc/chain_set.hip``).
 """
+import collections
 import os
 
 import torch
 
 from . import _lib, ops, fused_deepset
-from ._lib import check, ptr, require_device, stream_of
+from ._lib import check, fits_buffer, ptr, require_device, stream_of
 from .fused_deepset import D, _bn_of, _bn_consts
 
 # None = auto (inside torch.autocast(bfloat16 / float16) only); True / False pin the choice (tests, bench A/B)
@@ -54,7 +55,7 @@ def applicable(module, x_mod, x_map, csr_idx=None):
     # 32-bit buffer addressing inside the kernels: x_map (32 B / view), value rows, the [V, 32] bf16 gradient row
     V, R = x_map.shape[0], x_mod.rows.shape[0]
     N = csr_idx.shape[0] - 1 if csr_idx is not None else 0
-    return V * 64 < (1 << 32) - 16 and R * C * 2 < (1 << 32) - 16 and N * max(C * 2, 128) < (1 << 32) - 16
+    return fits_buffer(V * 64, R * C * 2, N * max(C * 2, 128))
 
 
 def pooled_output(csr_idx, N, C, dev, dtype=torch.bfloat16):
@@ -169,33 +170,63 @@ def _set_branch_backward(saved, dt, dWc, training, zstats, arena):
     return dpooled, [dWsa, g1, b1, dWsb, g2, b2]
 
 
+# the chain's tensors a backward needs, in their order in ctx.saved_tensors (between the path's own tensors):
+# tests/test_gpu_chain.py reads bn1 ..., scores by position
+CHAIN_SAVED = ("vp", "tiles", "n_tiles", "wops", "t_add", "zstar", "arg", "mom", "bn1", "bn2", "bn5", "bn6")
+
+
+class ChainState(collections.namedtuple(
+        "ChainState", CHAIN_SAVED + ("W1", "G", "training", "bs", "gw", "gb", "set_saved"), defaults=(None,) * 4)):
+    """What a chain prologue leaves for the view kernel and the backward: the ``CHAIN_SAVED`` tensors, the first layer's
+    weight ``W1``, the number of scores ``G``, ``training``, and for the forward alone the score bias ``bs``, the gate
+    parameters ``gw`` / ``gb`` and the set branch's ``set_saved``.  ``saved()`` / ``restore()`` carry the tensors
+    through ``ctx.save_for_backward``."""
+    __slots__ = ()
+
+    def saved(self):
+        return self[:len(CHAIN_SAVED)]
+
+    @classmethod
+    def restore(cls, saved, W1, G, training):
+        return cls(*saved, W1=W1, G=G, training=training)       # (TypeError unless ``saved`` are the twelve)
+
+
+def take_set_saved(ctx, say_released=False):
+    """``ctx.set_saved``, handed out once: a second backward over the same graph is refused (``say_released``: the longer
+    message of the paths that word it so)."""
+    set_saved, ctx.set_saved = ctx.set_saved, None
+    if set_saved is None:
+        why = ": its per-step workspaces are released after the first backward" if say_released else ""
+        raise RuntimeError(f"the recompute chain's backward ran twice on the same graph{why} (retain_graph is not "
+                           "supported on this path)")
+    return set_saved
+
+
+def chain_weights(e_map, e_score):
+    """(W1, W2, W5, W6, Ws, bs, the four BatchNorm modules) of DeepSetFeat + the score layer, detached and contiguous."""
+    blocks = (e_map.mlp_elt_1[0], e_map.mlp_elt_1[1], e_map.mlp_elt_2[0], e_map.mlp_elt_2[1])
+    weights = [blk[0].weight.detach().contiguous() for blk in blocks]      # W5 [32, 64]: per-view half | per-point half
+    return (*weights, e_score.weight.detach().contiguous(), e_score.bias.detach().contiguous(),
+            [_bn_of(blk) for blk in blocks])
+
+
 def chain_prologue(module, x_map, csr_idx):
     """Everything of a chain forward that does not depend on the values: tile table, view -> point index, weight
     operands, the statistics passes of the four BatchNorm layers of DeepSetFeat (train mode), the set branch.
-    Returns a namespace with the tensors the fused view kernel and the backward need (shared by the nearest path
+    Returns the ``ChainState`` the fused view kernel and the backward need (shared by the nearest path
     below and the bilinear path of fused_bilinear.py)."""
-    from types import SimpleNamespace
     lib = _lib.load()
-    e_map, e_score, gate = module.E_map, module.E_score, module.G
+    e_map, gate = module.E_map, module.G
     dev, V, N = x_map.device, x_map.shape[0], csr_idx.shape[0] - 1
     st = stream_of(x_map)
     training = e_map.training
-    W1 = e_map.mlp_elt_1[0][0].weight.detach().contiguous()
-    W2 = e_map.mlp_elt_1[1][0].weight.detach().contiguous()
-    W5 = e_map.mlp_elt_2[0][0].weight.detach().contiguous()       # [32, 64]: per-view half | per-point half
-    W6 = e_map.mlp_elt_2[1][0].weight.detach().contiguous()
-    Ws, bs = e_score.weight.detach().contiguous(), e_score.bias.detach().contiguous()
+    W1, W2, W5, W6, Ws, bs, bns = chain_weights(e_map, module.E_score)
     G = Ws.shape[0]
-    bns = [_bn_of(e_map.mlp_elt_1[0]), _bn_of(e_map.mlp_elt_1[1]),
-           _bn_of(e_map.mlp_elt_2[0]), _bn_of(e_map.mlp_elt_2[1])]
     gw = gate.weight.detach().reshape(-1).float().contiguous() if gate is not None else None
     gb = gate.bias.detach().reshape(-1).float().contiguous() if gate is not None else None
 
-    zpool = iter(ops.zeros_small((11, 3 * D), torch.float64, dev))   # sum | sum of squares | input sums (+ moments)
-
-    def zstats():
-        return next(zpool)
-
+    # sum | sum of squares | input sums (+ moments)
+    zstats = iter(ops.zeros_small((11, 3 * D), torch.float64, dev)).__next__
     with ops._timed("chain_tiles", N * 8):
         tiles, n_tiles = build_tiles(csr_idx, V)
         vp = torch.empty(V, dtype=torch.int32, device=dev)
@@ -234,13 +265,8 @@ def chain_prologue(module, x_map, csr_idx):
             check(lib.dva_chain_stats(6, ptr(x_map), ptr(vp), ptr(t_add), ptr(tiles), ptr(n_tiles), ptr(wops),
                                       ptr(bn1), ptr(bn2), ptr(bn5), ptr(s6), V, N, st), "dva_chain_stats")
     bn6 = _chain_bn(s6, V, bns[3], training, W6, D, s6[2 * D:])
-    return SimpleNamespace(vp=vp, tiles=tiles, n_tiles=n_tiles, wops=wops, t_add=t_add, zstar=zstar, arg=arg, mom=mom,
-                           bn1=bn1, bn2=bn2, bn5=bn5, bn6=bn6, bs=bs, gw=gw, gb=gb, W1=W1, G=G, training=training,
-                           set_saved=set_saved)
-
-
-# order of the chain's tensors in ctx.saved_tensors (after the path's own): tests/test_gpu_chain.py reads bn1 ..., scores
-CHAIN_SAVED = ("vp", "tiles", "n_tiles", "wops", "t_add", "zstar", "arg", "mom", "bn1", "bn2", "bn5", "bn6")
+    return ChainState(vp=vp, tiles=tiles, n_tiles=n_tiles, wops=wops, t_add=t_add, zstar=zstar, arg=arg, mom=mom, bn1=bn1,
+                      bn2=bn2, bn5=bn5, bn6=bn6, W1=W1, G=G, training=training, bs=bs, gw=gw, gb=gb, set_saved=set_saved)
 
 
 class _ChainPool(torch.autograd.Function):
@@ -270,12 +296,8 @@ class _ChainPool(torch.autograd.Function):
                                             ptr(rows), ptr(row_idx), ptr(csr_idx), ptr(S.gw), ptr(S.gb), ptr(out),
                                             ptr(scores), N, V, R, C, S.G, int(scaling), float(eps),
                                             _lib.dtype_code(rows), st), "dva_chain_attn_fwd_dt")
-        ctx.save_for_backward(rows, row_idx, x_map, csr_idx, S.vp, S.tiles, S.n_tiles, S.wops, S.t_add, S.zstar, S.arg,
-                              S.mom, S.bn1, S.bn2, S.bn5, S.bn6, out, scores, S.bs, S.gw, S.gb, S.W1)
-        ctx.plan = plan
-        ctx.module = module
-        ctx.set_saved = S.set_saved
-        ctx.training = S.training
+        ctx.save_for_backward(rows, row_idx, x_map, csr_idx, *S.saved(), out, scores, S.bs, S.gw, S.gb, S.W1)
+        ctx.plan, ctx.module, ctx.set_saved, ctx.training = plan, module, S.set_saved, S.training
         ctx.meta = (int(scaling), float(eps))
         return out
 
@@ -340,7 +362,7 @@ def keys_applicable(module, x_mod, x_map, csr_idx):
     if not fused_deepset.applicable(module.E_map, module.K, x_map):
         return False
     V, N = x_map.shape[0], csr_idx.shape[0] - 1
-    return V * 64 < (1 << 32) - 16 and N * 128 < (1 << 32) - 16
+    return fits_buffer(V * 64, N * 128)
 
 
 def keys_rows_ok(module, x_mod):
@@ -352,7 +374,7 @@ def keys_rows_ok(module, x_mod):
         return False
     if module.G is not None and any(t is not None and t.dtype != torch.float32 for t in (module.G.weight, module.G.bias)):
         return False
-    return rows.shape[0] * C * 2 < (1 << 32) - 16
+    return fits_buffer(rows.shape[0] * C * 2)
 
 
 class _KeyAdapter:
@@ -387,8 +409,7 @@ class _ChainQKVPool(torch.autograd.Function):
                                               ptr(rows), ptr(row_idx), ptr(csr_idx), ptr(S.gw), ptr(S.gb), ptr(out),
                                               ptr(scores), ptr(keys), N, V, R, C, int(groups), int(scaling), float(eps), st),
                   "dva_chain_attn_fwd_keys")
-        ctx.save_for_backward(rows, row_idx, x_map, csr_idx, S.vp, S.tiles, S.n_tiles, S.wops, S.t_add, S.zstar, S.arg,
-                              S.mom, S.bn1, S.bn2, S.bn5, S.bn6, out, scores, S.bs, S.gw, S.gb, S.W1, keys, Qp)
+        ctx.save_for_backward(rows, row_idx, x_map, csr_idx, *S.saved(), out, scores, S.bs, S.gw, S.gb, S.W1, keys, Qp)
         ctx.plan, ctx.module, ctx.set_saved, ctx.training = plan, module, S.set_saved, S.training
         ctx.meta = (int(scaling), float(eps))
         ctx.qk = (int(groups), float(scale))
@@ -421,22 +442,17 @@ class _ChainCompat(torch.autograd.Function):
             check(lib.dva_chain_keys_compat(ptr(x_map), ptr(S.vp), ptr(S.t_add), ptr(S.tiles), ptr(S.n_tiles), ptr(S.wops),
                                             ptr(S.bn1), ptr(S.bn2), ptr(S.bn5), ptr(S.bn6), ptr(S.bs), ptr(keys), ptr(Qp),
                                             ptr(compat), int(groups), float(scale), V, N, st), "dva_chain_keys_compat")
-        ctx.save_for_backward(x_map, csr_idx, S.vp, S.tiles, S.n_tiles, S.wops, S.t_add, S.zstar, S.arg, S.mom, S.bn1,
-                              S.bn2, S.bn5, S.bn6, S.W1, keys, Qp)
+        ctx.save_for_backward(x_map, csr_idx, *S.saved(), S.W1, keys, Qp)
         ctx.adapter, ctx.set_saved, ctx.training = adapter, S.set_saved, S.training
         ctx.meta = (int(groups), float(scale))
         return compat
 
     @staticmethod
     def backward(ctx, dcompat):
-        from types import SimpleNamespace
         from .fused_chain_bwd import Arena, chain_epilogue
         lib = _lib.load()
-        if ctx.set_saved is None:
-            raise RuntimeError("the recompute chain's backward ran twice on the same graph (retain_graph is not "
-                               "supported on this path)")
-        (x_map, csr_idx, vp, tiles, n_tiles, wops, t_add, zstar, arg, mom, bn1, bn2, bn5, bn6, W1, keys,
-         Qp) = ctx.saved_tensors
+        set_saved = take_set_saved(ctx)
+        x_map, csr_idx, *chain, W1, keys, Qp = ctx.saved_tensors
         groups, scale = ctx.meta
         V, N = x_map.shape[0], csr_idx.shape[0] - 1
         dcompat = dcompat.float().contiguous()
@@ -444,11 +460,9 @@ class _ChainCompat(torch.autograd.Function):
         with ops._timed("qkv_dquery", V * (64 + 16) + N * 136):
             check(lib.dva_qkv_dquery(ptr(dcompat), 4, ptr(keys), ptr(csr_idx), ptr(dQ), N, V, groups, scale,
                                      stream_of(x_map)), "dva_qkv_dquery")
-        S = SimpleNamespace(vp=vp, tiles=tiles, n_tiles=n_tiles, wops=wops, t_add=t_add, zstar=zstar, arg=arg, mom=mom,
-                            bn1=bn1, bn2=bn2, bn5=bn5, bn6=bn6, W1=W1, G=D, training=ctx.training)
-        grads = chain_epilogue(lib, Arena(x_map.device), S, ctx.adapter, x_map, csr_idx, dcompat, None, ctx.set_saved,
+        S = ChainState.restore(chain, W1=W1, G=D, training=ctx.training)
+        grads = chain_epilogue(lib, Arena(x_map.device), S, ctx.adapter, x_map, csr_idx, dcompat, None, set_saved,
                                keys=(Qp, groups, scale))
-        ctx.set_saved = None
         return (None, None, dQ if ctx.needs_input_grad[2] else None, None, None, None) + tuple(grads)
 
 

@@ -26,19 +26,19 @@ class Arena:
         return self.buf[off:off + n].view(*shape)
 
 
-def bn_bwd_consts(lib, arena, stats, bn, m_rows, training, st, hat=True, out=True):
+def bn_bwd_consts(lib, arena, stats, bn, m_rows, training, st, hat=True, out=True, width=D):
     sm = dg = db = None
     if out:
-        sm, dg, db = arena.take(2 * D), arena.take(D), arena.take(D)
+        sm, dg, db = arena.take(2 * width), arena.take(width), arena.take(width)
     check(lib.dva_bn_bwd_consts(ptr(stats), ptr(bn), (1.0 / m_rows) if training else 0.0, 1 if hat else 0,
-                                ptr(sm), ptr(dg), ptr(db), D, st), "dva_bn_bwd_consts")
+                                ptr(sm), ptr(dg), ptr(db), width, st), "dva_bn_bwd_consts")
     return sm, dg, db
 
 
 def chain_epilogue(lib, arena, S, module, x_map, csr_idx, dc, gwb, set_saved, keys=None):
     """Everything of a chain backward behind the attention backward (which is specific to how the values are
     produced): score layer + BatchNorm-6 statistics, the three layer passes, the per-point set branch, layer 1.
-    ``S``: namespace with vp, tiles, n_tiles, wops, t_add, zstar, arg, mom, bn1, bn2, bn5, bn6, W1, G, training.
+    ``S``: the fused_chain.ChainState (its CHAIN_SAVED tensors, W1, G, training).
     ``dc`` fp32 [V, 4] score gradients (consumed), ``gwb`` fp32 [2 G] gate gradients or None.
     ``keys`` = (Qp fp32 [N, 32], groups, scale): the last layer is the KEY layer of a QKVBimodalCSRPool (S.G = 32) and
     ``dc`` the gradient of the compatibilities [V, 4]; the passes build dK' = scale dc[g] Q'[point] in registers.
@@ -51,10 +51,7 @@ def chain_epilogue(lib, arena, S, module, x_map, csr_idx, dc, gwb, set_saved, ke
     bn1, bn2, bn5, bn6 = S.bn1, S.bn2, S.bn5, S.bn6
     st = stream_of(x_map)
     m_rows = float(max(V, 1))
-    zpool = iter(ops.zeros_small((10, 2 * D), torch.float64, dev))
-
-    def zstats():
-        return next(zpool)
+    zstats = iter(ops.zeros_small((10, 2 * D), torch.float64, dev)).__next__
 
     def consts(stats, bn, hat=True, out=True):
         """The arithmetic between two passes in one launch (dva_bn_bwd_consts): S2 -> z_hat form in place,
@@ -132,15 +129,12 @@ def chain_epilogue(lib, arena, S, module, x_map, csr_idx, dc, gwb, set_saved, ke
 
 
 def backward(ctx, gout):
-    from types import SimpleNamespace
+    from .fused_chain import ChainState, take_set_saved
     lib = _lib.load()
-    if ctx.set_saved is None:
-        raise RuntimeError("the recompute chain's backward ran twice on the same graph: its per-step workspaces are "
-                           "released after the first backward (retain_graph is not supported on this path)")
+    set_saved = take_set_saved(ctx, say_released=True)
     qk = getattr(ctx, "qk", None)          # QKVBimodalCSRPool in the view kernel: (groups, scale); two more saved tensors
     saved = ctx.saved_tensors
-    (rows, row_idx, x_map, csr_idx, vp, tiles, n_tiles, wops, t_add, zstar, arg, mom,
-     bn1, bn2, bn5, bn6, out, scores, bs, gw, gb, W1) = saved[:22]
+    rows, row_idx, x_map, csr_idx, *chain, out, scores, bs, gw, gb, W1 = saved if qk is None else saved[:-2]
     module, training = ctx.module, ctx.training
     scaling, eps = ctx.meta
     gate = module.G
@@ -149,8 +143,7 @@ def backward(ctx, gout):
     G = qk[0] if qk is not None else module.E_score.weight.shape[0]
     st = stream_of(x_map)
     gout = gout.contiguous().to(rows.dtype)          # bf16, or fp16 under autocast(float16)
-    S = SimpleNamespace(vp=vp, tiles=tiles, n_tiles=n_tiles, wops=wops, t_add=t_add, zstar=zstar, arg=arg, mom=mom,
-                        bn1=bn1, bn2=bn2, bn5=bn5, bn6=bn6, W1=W1, G=G if qk is None else D, training=training)
+    S = ChainState.restore(chain, W1=W1, G=G if qk is None else D, training=training)
     arena = Arena(dev)          # every small fp32 accumulator / gradient of this backward: one zero fill
     # ---- attention + gate backward from the scores the forward left: score gradients, view records (no chain)
     dc = torch.empty((V, 4), dtype=torch.float32, device=dev)
@@ -160,9 +153,9 @@ def backward(ctx, gout):
     # grad_out row (+ out row for points with more than 32 views)
     plan = None
     if ctx.needs_input_grad[0]:
-        plan = ctx.plan if ctx.plan is not None else ops.row_plan(row_idx, R, with_counts=False)[0]
+        plan = ops._plan_or_build(ctx.plan, row_idx, R, True)
     with ops._timed("chain_attn_bwd", V * (C * 2 + 16 + 8 + 16 + 16) + N * (C * 2 + 8)):
-        check(lib.dva_chain_attn_bwd_dt(ptr(scores), ptr(vp), ptr(tiles), ptr(n_tiles), ptr(rows), ptr(row_idx),
+        check(lib.dva_chain_attn_bwd_dt(ptr(scores), ptr(S.vp), ptr(S.tiles), ptr(S.n_tiles), ptr(rows), ptr(row_idx),
                                         ptr(csr_idx), ptr(gw), ptr(gb), ptr(gout), ptr(out), ptr(dc), ptr(rec),
                                         ptr(gwb), N, V, R, C, G, scaling, eps, _lib.dtype_code(rows), st),
               "dva_chain_attn_bwd_dt")
@@ -177,13 +170,12 @@ def backward(ctx, gout):
     keys_arg = None
     if qk is not None:
         # dQ' from the stored key rows; the key gradient itself is built inside the chain passes (chain_epilogue keys=...)
-        keys_rows, Qp = saved[22], saved[23]
+        keys_rows, Qp = saved[-2:]
         dQ = torch.empty((N, D), dtype=torch.float32, device=dev)
         with ops._timed("qkv_dquery", V * (64 + 16) + N * 136):
             check(lib.dva_qkv_dquery(ptr(dc), 4, ptr(keys_rows), ptr(csr_idx), ptr(dQ), N, V, G, qk[1], st),
                   "dva_qkv_dquery")
         keys_arg = (Qp, G, qk[1])
         lead = lead + (dQ, None)
-    grads = chain_epilogue(lib, arena, S, module, x_map, csr_idx, dc, gwb, ctx.set_saved, keys=keys_arg)
-    ctx.set_saved = None
+    grads = chain_epilogue(lib, arena, S, module, x_map, csr_idx, dc, gwb, set_saved, keys=keys_arg)
     return lead + tuple(grads)

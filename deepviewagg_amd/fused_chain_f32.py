@@ -16,8 +16,9 @@ import torch
 
 from . import _lib, ops, fused_deepset
 from ._lib import check, ptr, require_device, stream_of
-from .fused_deepset import D, _bn_of
-from .fused_chain import build_tiles, _chain_bn, _set_branch_forward, _set_branch_backward, chain_params
+from .fused_deepset import D
+from .fused_chain import (ChainState, build_tiles, _chain_bn, _set_branch_forward,
+                          _set_branch_backward, chain_params, chain_weights, take_set_saved)
 from .fused_chain_bwd import Arena, bn_bwd_consts
 
 # False: the stored-activation passes of fused_deepset (tests, A/B)
@@ -32,7 +33,7 @@ def applicable(e_map, linear, x_map, csr_idx):
     if not ENABLED or not fused_deepset.applicable(e_map, linear, x_map) or linear.out_features > 4:
         return False
     V, N = x_map.shape[0], csr_idx.shape[0] - 1
-    return 0 < V and V * 32 < (1 << 32) - 16 and N * 128 < (1 << 32) - 16
+    return 0 < V and _lib.fits_buffer(V * 32, N * 128)
 
 
 class _ChainScores(torch.autograd.Function):
@@ -43,22 +44,13 @@ class _ChainScores(torch.autograd.Function):
         lib = _lib.load()
         require_device(x_map, csr_idx)
         x_map = x_map.contiguous()
-        e_map, e_score = shim.E_map, shim.E_score
+        e_map = shim.E_map
         dev, V, N = x_map.device, x_map.shape[0], csr_idx.shape[0] - 1
         st = stream_of(x_map)
         training = e_map.training
-        W1 = e_map.mlp_elt_1[0][0].weight.detach().contiguous()
-        W2 = e_map.mlp_elt_1[1][0].weight.detach().contiguous()
-        W5 = e_map.mlp_elt_2[0][0].weight.detach().contiguous()       # [32, 64]: per-view half | per-point half
-        W6 = e_map.mlp_elt_2[1][0].weight.detach().contiguous()
-        Ws, bs = e_score.weight.detach().contiguous(), e_score.bias.detach().contiguous()
+        W1, W2, W5, W6, Ws, bs, bns = chain_weights(e_map, shim.E_score)
         G = Ws.shape[0]
-        bns = [_bn_of(e_map.mlp_elt_1[0]), _bn_of(e_map.mlp_elt_1[1]),
-               _bn_of(e_map.mlp_elt_2[0]), _bn_of(e_map.mlp_elt_2[1])]
-        zpool = iter(ops.zeros_small((10, 3 * D), torch.float64, dev))
-
-        def zstats():
-            return next(zpool)
+        zstats = iter(ops.zeros_small((10, 3 * D), torch.float64, dev)).__next__
 
         with ops._timed("chain_tiles", N * 8):
             tiles, n_tiles = build_tiles(csr_idx, V)
@@ -105,8 +97,9 @@ class _ChainScores(torch.autograd.Function):
                                         ptr(scores), V, st), "dva_chain3_scores")
         need_bwd = any(ctx.needs_input_grad)
         if need_bwd:
-            ctx.save_for_backward(x_map, csr_idx, vp, tiles, n_tiles, wops, t_add, zstar, arg, mom, bn1, bn2, bn5,
-                                  bn6, W1, z2, z5)
+            S = ChainState(vp=vp, tiles=tiles, n_tiles=n_tiles, wops=wops, t_add=t_add, zstar=zstar, arg=arg, mom=mom,
+                           bn1=bn1, bn2=bn2, bn5=bn5, bn6=bn6, W1=W1, G=G, training=training)
+            ctx.save_for_backward(x_map, csr_idx, *S.saved(), S.W1, z2, z5)
         ctx.shim = shim
         ctx.set_saved = set_saved if need_bwd else None
         ctx.training = training
@@ -116,12 +109,10 @@ class _ChainScores(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dscores):
         lib = _lib.load()
-        if ctx.set_saved is None:
-            raise RuntimeError("the recompute chain's backward ran twice on the same graph: its per-step workspaces "
-                               "are released after the first backward (retain_graph is not supported on this path)")
-        (x_map, csr_idx, vp, tiles, n_tiles, wops, t_add, zstar, arg, mom, bn1, bn2, bn5, bn6, W1, z2,
-         z5) = ctx.saved_tensors
+        set_saved = take_set_saved(ctx, say_released=True)
+        x_map, csr_idx, *chain, W1, z2, z5 = ctx.saved_tensors
         G, training = ctx.G, ctx.training
+        S = ChainState.restore(chain, W1=W1, G=G, training=training)
         dev, V, N = x_map.device, x_map.shape[0], csr_idx.shape[0] - 1
         st = stream_of(x_map)
         dc = dscores.contiguous().float()
@@ -129,10 +120,7 @@ class _ChainScores(torch.autograd.Function):
             dc = torch.nn.functional.pad(dc, (0, 4 - G))
         arena = Arena(dev)
         m_rows = float(max(V, 1))
-        zpool = iter(ops.zeros_small((10, 2 * D), torch.float64, dev))
-
-        def zstats():
-            return next(zpool)
+        zstats = iter(ops.zeros_small((10, 2 * D), torch.float64, dev)).__next__
 
         def consts(stats, bn, hat=True, out=True):
             return bn_bwd_consts(lib, arena, stats, bn, m_rows, training, st, hat, out)
@@ -141,50 +129,49 @@ class _ChainScores(torch.autograd.Function):
         s6 = zstats()
         dWs, dbs = arena.take(G, D), arena.take(G)
         with ops._timed("chain3_score_stats", V * (ROW + 16)):
-            check(lib.dva_chain3_score_stats(ptr(z5), ptr(tiles), ptr(n_tiles), ptr(wops), ptr(bn5), ptr(bn6),
+            check(lib.dva_chain3_score_stats(ptr(z5), ptr(S.tiles), ptr(S.n_tiles), ptr(S.wops), ptr(S.bn5), ptr(S.bn6),
                                              ptr(dc), ptr(s6), ptr(dWs), ptr(dbs), G, V, st),
                   "dva_chain3_score_stats")
 
         def layer(stage, x, zrows, vp_, u, bn_lo, bn_hi, sm, dc_, arg_, dpooled_, da_in, da_out, dW, du, P, stats,
                   name, nbytes):
             with ops._timed(name, nbytes):
-                check(lib.dva_chain3_bwd_layer(stage, ptr(x), ptr(zrows), ptr(vp_), ptr(u), ptr(tiles), ptr(n_tiles),
-                                               ptr(wops), ptr(bn_lo), ptr(bn_hi), ptr(sm), ptr(dc_), ptr(arg_),
+                check(lib.dva_chain3_bwd_layer(stage, ptr(x), ptr(zrows), ptr(vp_), ptr(u), ptr(S.tiles), ptr(S.n_tiles),
+                                               ptr(S.wops), ptr(bn_lo), ptr(bn_hi), ptr(sm), ptr(dc_), ptr(arg_),
                                                ptr(dpooled_), ptr(da_in), ptr(da_out), ptr(dW), ptr(du), ptr(P),
                                                ptr(stats), V, N, st), "dva_chain3_bwd_layer")
 
-        sm6, g6, b6 = consts(s6, bn6)
+        sm6, g6, b6 = consts(s6, S.bn6)
         dW6 = arena.take(D, D)
         s5 = zstats()
         da5 = torch.empty((V, D), dtype=torch.float32, device=dev)
-        layer(6, None, z5, None, None, bn5, bn6, sm6, dc, None, None, None, da5, dW6, None, None, s5,
+        layer(6, None, z5, None, None, S.bn5, S.bn6, sm6, dc, None, None, None, da5, dW6, None, None, s5,
               "chain3_bwd_l6", V * (2 * ROW + 16))
         del z5, dc
-        sm5, g5, b5 = consts(s5, bn5)
+        sm5, g5, b5 = consts(s5, S.bn5)
         dW5 = arena.take(D, 2 * D)
         du = torch.zeros((N, D), dtype=torch.float32, device=dev)
         s2 = zstats()
         da2 = torch.empty((V, D), dtype=torch.float32, device=dev)
-        layer(5, None, z2, vp, t_add, bn2, bn5, sm5, None, None, None, da5, da2, dW5, du, None, s2,
+        layer(5, None, z2, S.vp, S.t_add, S.bn2, S.bn5, sm5, None, None, None, da5, da2, dW5, du, None, s2,
               "chain3_bwd_l5", V * (4 + 3 * ROW) + N * 256)
         del da5
         # ---- per-point set branch
-        dpooled, d_set = _set_branch_backward(ctx.set_saved, du, dW5, training, zstats, arena)
-        consts(s2, bn2, out=False)            # view part; the per-point part below is accumulated in z_hat directly
+        dpooled, d_set = _set_branch_backward(set_saved, du, dW5, training, zstats, arena)
+        consts(s2, S.bn2, out=False)            # view part; the per-point part below is accumulated in z_hat directly
         dpooled_dy = torch.empty((N, D), dtype=torch.float32, device=dev)     # leaky'(y*) dpooled: what stage 2 routes
-        check(lib.dva_chain_route_stats(ptr(zstar), ptr(dpooled), ptr(bn2), ptr(csr_idx), ptr(s2), ptr(dpooled_dy), N,
+        check(lib.dva_chain_route_stats(ptr(S.zstar), ptr(dpooled), ptr(S.bn2), ptr(csr_idx), ptr(s2), ptr(dpooled_dy), N,
                                         st), "dva_chain_route_stats")
-        sm2, g2, b2 = consts(s2, bn2, hat=False)
+        sm2, g2, b2 = consts(s2, S.bn2, hat=False)
         dW2, P = arena.take(D, D), arena.take(D, 20)       # P = sum dy1 [x | 0 | 1]^T
         s1 = zstats()
-        layer(2, x_map, z2, vp, None, bn1, bn2, sm2, None, arg, dpooled_dy, da2, None, dW2, None, P, None,
+        layer(2, x_map, z2, S.vp, None, S.bn1, S.bn2, sm2, None, S.arg, dpooled_dy, da2, None, dW2, None, P, None,
               "chain3_bwd_l2", V * (36 + 2 * ROW) + N * 256)
         del da2, z2
         check(lib.dva_chain_stats1(ptr(P), ptr(W1), 1, ptr(s1), st), "dva_chain_stats1")    # layer 1 is linear in x_map
-        sm1, g1, b1 = consts(s1, bn1)
+        sm1, g1, b1 = consts(s1, S.bn1)
         dW1 = arena.take(D, 8)
-        check(lib.dva_chain_dw1(ptr(P), ptr(mom), ptr(W1), 1, ptr(bn1), ptr(sm1), ptr(dW1), st), "dva_chain_dw1")
-        ctx.set_saved = None
+        check(lib.dva_chain_dw1(ptr(P), ptr(S.mom), ptr(W1), 1, ptr(S.bn1), ptr(sm1), ptr(dW1), st), "dva_chain_dw1")
         grads = [dW1, g1, b1, dW2, g2, b2, dW5, g5, b5, dW6, g6, b6, dWs, dbs, None, None] + d_set
         return (None, None, None) + tuple(grads)
 

@@ -117,7 +117,7 @@ class _DeepSetLinear(torch.autograd.Function):
 
         # ---- elt MLP 1: x_map -> a1 -> a2
         s1 = zstats()
-        if training and act == torch.float32 and V * 32 < (1 << 32) - 16:
+        if training and act == torch.float32 and _lib.fits_buffer(V * 32):
             # z1 = Wa x is linear in x: its statistics from the fp64 moments of x_map (dva_chain_moments, shifted
             # accumulation), as the fp32 chain does -- the fp32 per-lane sums of the pass below lose the variance when
             # |mean| / sd of z1 is large (2.2e-4 relative at |mean| / sd = 300, V = 2^25)

@@ -28,6 +28,7 @@ ops; names and argument meaning follow the reference call site
 
 All ops require tensors on a HIP device and raise otherwise (no CPU fallback).
 """
+import collections
 import os
 
 import threading
@@ -373,8 +374,7 @@ class _ViewAttention(torch.autograd.Function):
                                              ptr(gb) if has_gate else None, ptr(gval), ptr(gcompat),
                                              ptr(gwb), N, V, C, G, scaling, dtype_code(val),
                                              ATTENTION_ALGO, stream_of(val)), "dva_view_attention_bwd")
-        g_w = gwb[:G].reshape(w_shape) if (has_gate and w_shape is not None) else None
-        g_b = gwb[G:].reshape(b_shape) if (has_gate and b_shape is not None) else None
+        g_w, g_b = _gate_grads(gwb, G, has_gate, w_shape, b_shape)
         return gval, gcompat, None, g_w, g_b, None, None
 
 
@@ -655,6 +655,7 @@ def split_plan_serves(dtype, C):
     """Does a consumer of [R, C] value rows of this dtype take its rows gradient over a SplitPlan?  bf16 / fp16: the
     16-byte records of the chain (any C: bucket kernel at C in {32, 64}, the two record passes otherwise); fp32: the 32-byte
     records of the lean attention backward at C in {32, 64} (round 6).  Everything else wants the permutation."""
+    # (a plan builder that knew its consumer's shapes would ask attention_bwd_route which backward runs: DESIGN.md)
     return dtype in (torch.bfloat16, torch.float16) or (dtype == torch.float32 and C in (32, 64))
 
 
@@ -983,7 +984,7 @@ class _GatherSegmentMax(torch.autograd.Function):
                                                      ptr(grows), V, P, R, C, dtype_code(gout), stream_of(gout)),
                       "dva_gather_segment_max_bwd")
             return grows.to(dt), None, None, None
-        perm, row_ptr = ctx.plan if ctx.plan is not None else row_plan(row_idx, R, with_counts=False, split=False)[0]
+        perm, row_ptr = _plan_or_build(ctx.plan, row_idx, R, False)
         voa = csr_expand(atom_ptr, P)
         grows = torch.empty((R, C), dtype=torch.float32, device=gout.device)
         with _timed("gather_segment_max_bwd", P * (16 + C * (es + 2)) + R * (C * 4 + 4)):
@@ -1183,6 +1184,137 @@ def _team_records_ok(C, G, dtype):
 # fp32 rows with four score groups: the lean tile-based attention backward (False: the team kernel; tests A/B)
 LEAN_ATTENTION_BWD = True
 
+AttentionBwdRoute = collections.namedtuple("AttentionBwdRoute", "kernel rows_grad records")
+
+
+def attention_bwd_route(rows_dtype, gout_dtype, out_dtype, C, G, V, R, N, need_rows, aligned16):
+    """Which kernels the backward of ``view_gather_attention`` launches, from plain values (no tensor, no device call;
+    ``LEAN_ATTENTION_BWD``, ``ATTENTION_ALGO`` and ``ROWS_GRAD_ALGO`` are read when it is called).  ``aligned16``: the value
+    rows and ``gout`` both start on 16 bytes.  ``kernel``: "lean_f32" / "lean_16" = the tile kernels of csrc/chain_bwd.hip,
+    "team" = csrc/attention.hip; ``rows_grad``: "none", "plan" (segmented reduction over the row plan) or "atomics";
+    ``records`` ("team" only): the attention backward writes view records for the rows-gradient pass."""
+    use_plan = need_rows and ROWS_GRAD_ALGO == 0
+    if (LEAN_ATTENTION_BWD and use_plan and ATTENTION_ALGO != 1 and rows_dtype == torch.float32
+            and gout_dtype == torch.float32 and G == 4 and C in (32, 64, 128, 256) and V > 0
+            and _lib.fits_buffer(V * 32, max(R, N) * C * 4)):
+        return AttentionBwdRoute("lean_f32", "plan", False)
+    if (LEAN_ATTENTION_BWD and use_plan and ATTENTION_ALGO != 1 and rows_dtype in (torch.bfloat16, torch.float16)
+            and gout_dtype == rows_dtype and out_dtype == rows_dtype and G in (1, 2, 4)
+            and C in (32, 64, 128, 256, 512) and V > 0 and _lib.fits_buffer(V * 16, max(R, N) * C * 2)):
+        return AttentionBwdRoute("lean_16", "plan", False)
+    # (the team kernel takes 16-byte aligned value and gradient rows only: csrc/attention.hip bwd_impl)
+    records = bool(use_plan and ATTENTION_ALGO != 1 and _team_records_ok(C, G, rows_dtype) and aligned16)
+    return AttentionBwdRoute("team", "plan" if use_plan else "atomics" if need_rows else "none", records)
+
+
+def _gate_grads(gwb, G, has_gate, w_shape, b_shape):
+    """(d gate_w, d gate_b) in the parameters' shapes from the fp32 [2 G] accumulator of an attention backward."""
+    g_w = gwb[:G].reshape(w_shape) if (has_gate and w_shape is not None) else None
+    g_b = gwb[G:].reshape(b_shape) if (has_gate and b_shape is not None) else None
+    return g_w, g_b
+
+
+def _plan_or_build(plan, row_idx, n_rows, split):
+    """The caller's row plan, or one built now; ``split=False`` where the consumer unpacks ``(perm, row_ptr)``."""
+    return plan if plan is not None else row_plan(row_idx, n_rows, with_counts=False, split=split)[0]
+
+
+def _rows_grad_perm(gout, att, gate, vp, perm, row_ptr, rec, rs, R, C, G, rows):
+    """fp32 [R, C] rows gradient of ``view_gather_attention``: segmented reduction over the permutation plan, from the
+    view records (``rec`` fp32 [V, rs]) or, without them, from ``vp`` (view -> point) + ``att`` + ``gate``."""
+    lib = _lib.load()
+    V = att.shape[0]
+    grows = torch.empty((R, C), dtype=torch.float32, device=rows.device)
+    # per view: perm + record (or view_point + scores) + grad_out row; per row: fp32 row written
+    per_view = 4 + (rs * 4 if rec is not None else 4 + 2 * G * 4) + C * rows.element_size()
+    with _timed("view_gather_rows_grad", V * per_view + R * (C * 4 + 4)):
+        check(lib.dva_view_gather_rows_grad(
+            ptr(gout), ptr(att), ptr(gate), ptr(vp), ptr(perm), ptr(row_ptr), ptr(rec), rs, ptr(grows), R, V, C, G,
+            dtype_code(rows), stream_of(rows)), "dva_view_gather_rows_grad")
+    return grows
+
+
+# The three attention backwards (attention_bwd_route picks one).  Arguments: the route, the caller's row plan or None, the
+# forward's saved tensors (gw / gb None without gating), grad_out, the score gradients to fill, the gate accumulator or None,
+# scaling, eps.  Each returns (grows, gcompat).
+
+def _attn_bwd_lean_f32(route, plan, rows, row_idx, compat, csr_idx, att, gate, amax, gw, gb, out, gout, gcompat, gwb,
+                       scaling, eps):
+    # fp32 rows, four score groups (the no-autocast headline shape): the tile-based attention backward of the
+    # chain path (csrc/chain_bwd.hip attn_bwd_kernel<float, ...>: scores in, score gradients + 32-byte view
+    # records out) instead of the team kernel: 2.8 -> 2.0 ms at V = 33.5 M
+    from .fused_chain import build_tiles
+    lib = _lib.load()
+    N, V, (R, C), G = csr_idx.shape[0] - 1, row_idx.shape[0], rows.shape, compat.shape[1]
+    tiles, n_tiles = build_tiles(csr_idx, V)
+    vp = csr_expand(csr_idx, V)
+    rec = torch.empty((V, 8), dtype=torch.float32, device=rows.device)
+    with _timed("view_gather_attention_bwd", V * (C * 4 + 16 + 8 + 16 + 32) + N * (C * 4 + 8)):
+        check(lib.dva_chain_attn_bwd_f32(
+            ptr(compat), ptr(vp), ptr(tiles), ptr(n_tiles), ptr(rows), ptr(row_idx), ptr(csr_idx), ptr(gw), ptr(gb),
+            ptr(gout), ptr(out), ptr(gcompat), ptr(rec), ptr(gwb), N, V, R, C, G, scaling, eps, stream_of(rows)),
+            "dva_chain_attn_bwd_f32")
+    plan = _plan_or_build(plan, row_idx, R, split_plan_serves(rows.dtype, C))
+    grows = None
+    if isinstance(plan, SplitPlan) and SPLIT_FUSED:
+        # round 6: the 32-byte records through pass A of the split plan + the fp32 bucket kernel
+        grows = plan.rows_grad_f32(gout, rec, C, G, stream_of(rows))
+    if grows is None:
+        perm, row_ptr = plan
+        grows = _rows_grad_perm(gout, att, gate if gw is not None else None, None, perm, row_ptr, rec, 8, R, C, G, rows)
+    return grows, gcompat
+
+
+def _attn_bwd_lean_16(route, plan, rows, row_idx, compat, csr_idx, att, gate, amax, gw, gb, out, gout, gcompat, gwb,
+                      scaling, eps):
+    # bf16 rows (round 4; QKVBimodalCSRPool on the chain, and every bf16 caller with <= 4 score groups): the
+    # chain path's attention backward (scores [V, 4] in, score gradients + 16-byte view records out) and its
+    # 16-byte-record rows gradient instead of the team kernels: 1.6 + 1.3 -> 0.9 + 1.3 ms at V = 33.5 M
+    from .fused_chain import build_tiles
+    lib = _lib.load()
+    N, V, (R, C), G = csr_idx.shape[0] - 1, row_idx.shape[0], rows.shape, compat.shape[1]
+    tiles, n_tiles = build_tiles(csr_idx, V)
+    vp = csr_expand(csr_idx, V)
+    if G == 4:
+        sc4 = compat
+    else:
+        sc4 = torch.zeros((V, 4), dtype=torch.float32, device=rows.device)
+        sc4[:, :G] = compat
+    dc = torch.empty((V, 4), dtype=torch.float32, device=rows.device)
+    rec = torch.empty((V, 4), dtype=torch.int32, device=rows.device)
+    with _timed("view_gather_attention_bwd", V * (C * 2 + 16 + 8 + 16 + 16) + N * (C * 2 + 8)):
+        check(lib.dva_chain_attn_bwd_dt(
+            ptr(sc4), ptr(vp), ptr(tiles), ptr(n_tiles), ptr(rows), ptr(row_idx), ptr(csr_idx), ptr(gw), ptr(gb),
+            ptr(gout), ptr(out), ptr(dc), ptr(rec), ptr(gwb), N, V, R, C, G, scaling, eps, dtype_code(rows),
+            stream_of(rows)), "dva_chain_attn_bwd_dt")
+    plan = _plan_or_build(plan, row_idx, R, True)
+    # bf16 / fp16: rounded where it is summed
+    grows = rows_grad_rec16(gout, plan, rec, R, C, G, rows.dtype, stream_of(rows))
+    return grows, (dc if G == 4 else dc[:, :G].contiguous())
+
+
+def _attn_bwd_team(route, plan, rows, row_idx, compat, csr_idx, att, gate, amax, gw, gb, out, gout, gcompat, gwb,
+                   scaling, eps):
+    lib = _lib.load()
+    N, V, (R, C), G = csr_idx.shape[0] - 1, row_idx.shape[0], rows.shape, compat.shape[1]
+    es = rows.element_size()
+    grows = torch.zeros((R, C), dtype=torch.float32, device=rows.device) if route.rows_grad == "atomics" else None
+    # per-view records (point id | gate * attention per group) for the rows-gradient pass: one 32-byte
+    # sector per view instead of scattered reads of view_point, att and gate
+    rs = ((G + 1 + 7) // 8) * 8
+    rec = torch.empty((V, rs), dtype=torch.float32, device=rows.device) if route.records else None
+    per_view = C * es + 4 + 2 * G * 4 + (C * 4 * 2 if grows is not None else 0) + (rs * 4 if rec is not None else 0)
+    with _timed("view_gather_attention_bwd", V * per_view + N * (C * es + 8 + 3 * G * 4)):
+        check(lib.dva_view_gather_attention_bwd(
+            ptr(gout), ptr(rows), ptr(row_idx), ptr(compat), ptr(att), ptr(gate), ptr(amax), ptr(csr_idx), ptr(gw), ptr(gb),
+            ptr(grows), ptr(gcompat), ptr(gwb), ptr(rec), rs, N, V, C, G, scaling, dtype_code(rows), ATTENTION_ALGO,
+            stream_of(rows)), "dva_view_gather_attention_bwd")
+    if route.rows_grad == "plan":
+        perm, row_ptr = _plan_or_build(plan, row_idx, R, False)
+        vp = csr_expand(csr_idx, V) if rec is None else None
+        grows = _rows_grad_perm(gout, att, gate if gw is not None else None, vp, perm, row_ptr, rec, rs, R, C, G, rows)
+    return (grows.to(rows.dtype) if grows is not None else None), gcompat
+
 
 class _ViewGatherAttention(torch.autograd.Function):
     @staticmethod
@@ -1219,114 +1351,21 @@ class _ViewGatherAttention(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout, _gatt, _ggate):
-        lib = _lib.load()
         rows, row_idx, compat, csr_idx, att, gate, amax, gw, gb, out = ctx.saved_tensors
         scaling, has_gate, w_shape, b_shape = ctx.meta
+        if not has_gate:
+            gw = gb = None      # (placeholders in saved_tensors)
         gout = gout.contiguous()
         N, V, (R, C), G = csr_idx.shape[0] - 1, row_idx.shape[0], rows.shape, compat.shape[1]
         gcompat = torch.empty_like(compat)             # every view is written (it belongs to a point)
         gwb = torch.zeros(2 * G, dtype=torch.float32, device=rows.device) if has_gate else None
-        es = rows.element_size()
-        need_rows = ctx.needs_input_grad[0]
-        use_plan = need_rows and ROWS_GRAD_ALGO == 0
-        if (LEAN_ATTENTION_BWD and use_plan and ATTENTION_ALGO != 1 and rows.dtype == torch.float32
-                and gout.dtype == torch.float32 and G == 4 and C in (32, 64, 128, 256) and V > 0
-                and V * 32 < (1 << 32) - 16 and max(R, N) * C * 4 < (1 << 32) - 16):
-            # fp32 rows, four score groups (the no-autocast headline shape): the tile-based attention backward of the
-            # chain path (csrc/chain_bwd.hip attn_bwd_kernel<float, ...>: scores in, score gradients + 32-byte view
-            # records out) instead of the team kernel: 2.8 -> 2.0 ms at V = 33.5 M
-            from .fused_chain import build_tiles
-            tiles, n_tiles = build_tiles(csr_idx, V)
-            vp = csr_expand(csr_idx, V)
-            rec = torch.empty((V, 8), dtype=torch.float32, device=rows.device)
-            with _timed("view_gather_attention_bwd", V * (C * 4 + 16 + 8 + 16 + 32) + N * (C * 4 + 8)):
-                check(lib.dva_chain_attn_bwd_f32(
-                    ptr(compat), ptr(vp), ptr(tiles), ptr(n_tiles), ptr(rows), ptr(row_idx), ptr(csr_idx),
-                    ptr(gw) if has_gate else None, ptr(gb) if has_gate else None, ptr(gout), ptr(out), ptr(gcompat),
-                    ptr(rec), ptr(gwb), N, V, R, C, G, scaling, ctx.eps, stream_of(rows)), "dva_chain_attn_bwd_f32")
-            plan = ctx.plan if ctx.plan is not None else row_plan(row_idx, R, with_counts=False,
-                                                                  split=split_plan_serves(rows.dtype, C))[0]
-            grows = None
-            if isinstance(plan, SplitPlan) and SPLIT_FUSED:
-                # round 6: the 32-byte records through pass A of the split plan + the fp32 bucket kernel
-                grows = plan.rows_grad_f32(gout, rec, C, G, stream_of(rows))
-            if grows is None:
-                perm, row_ptr = plan
-                grows = torch.empty((R, C), dtype=torch.float32, device=rows.device)
-                with _timed("view_gather_rows_grad", V * (4 + 32 + C * es) + R * (C * 4 + 4)):
-                    check(lib.dva_view_gather_rows_grad(
-                        ptr(gout), ptr(att), ptr(gate) if has_gate else None, None, ptr(perm), ptr(row_ptr), ptr(rec), 8,
-                        ptr(grows), R, V, C, G, dtype_code(rows), stream_of(rows)), "dva_view_gather_rows_grad")
-            g_w = gwb[:G].reshape(w_shape) if (has_gate and w_shape is not None) else None
-            g_b = gwb[G:].reshape(b_shape) if (has_gate and b_shape is not None) else None
-            return grows, None, gcompat, None, g_w, g_b, None, None, None
-        if (LEAN_ATTENTION_BWD and use_plan and ATTENTION_ALGO != 1 and rows.dtype in (torch.bfloat16, torch.float16)
-                and gout.dtype == rows.dtype and out.dtype == rows.dtype and G in (1, 2, 4)
-                and C in (32, 64, 128, 256, 512) and V > 0 and V * 16 < (1 << 32) - 16
-                and max(R, N) * C * 2 < (1 << 32) - 16):
-            # bf16 rows (round 4; QKVBimodalCSRPool on the chain, and every bf16 caller with <= 4 score groups): the
-            # chain path's attention backward (scores [V, 4] in, score gradients + 16-byte view records out) and its
-            # 16-byte-record rows gradient instead of the team kernels: 1.6 + 1.3 -> 0.9 + 1.3 ms at V = 33.5 M
-            from .fused_chain import build_tiles
-            tiles, n_tiles = build_tiles(csr_idx, V)
-            vp = csr_expand(csr_idx, V)
-            if G == 4:
-                sc4 = compat
-            else:
-                sc4 = torch.zeros((V, 4), dtype=torch.float32, device=rows.device)
-                sc4[:, :G] = compat
-            dc = torch.empty((V, 4), dtype=torch.float32, device=rows.device)
-            rec = torch.empty((V, 4), dtype=torch.int32, device=rows.device)
-            with _timed("view_gather_attention_bwd", V * (C * 2 + 16 + 8 + 16 + 16) + N * (C * 2 + 8)):
-                check(lib.dva_chain_attn_bwd_dt(
-                    ptr(sc4), ptr(vp), ptr(tiles), ptr(n_tiles), ptr(rows), ptr(row_idx), ptr(csr_idx),
-                    ptr(gw) if has_gate else None, ptr(gb) if has_gate else None, ptr(gout), ptr(out), ptr(dc),
-                    ptr(rec), ptr(gwb), N, V, R, C, G, scaling, ctx.eps, dtype_code(rows), stream_of(rows)),
-                      "dva_chain_attn_bwd_dt")
-            plan = ctx.plan if ctx.plan is not None else row_plan(row_idx, R, with_counts=False)[0]
-            # bf16 / fp16: rounded where it is summed
-            grows = rows_grad_rec16(gout, plan, rec, R, C, G, rows.dtype, stream_of(rows))
-            g_w = gwb[:G].reshape(w_shape) if (has_gate and w_shape is not None) else None
-            g_b = gwb[G:].reshape(b_shape) if (has_gate and b_shape is not None) else None
-            gcompat = dc if G == 4 else dc[:, :G].contiguous()
-            return grows, None, gcompat, None, g_w, g_b, None, None, None
-        if need_rows and not use_plan:
-            grows = torch.zeros((R, C), dtype=torch.float32, device=rows.device)
-        else:
-            grows = None
-        # per-view records (point id | gate * attention per group) for the rows-gradient pass: one 32-byte
-        # sector per view instead of scattered reads of view_point, att and gate
-        rs = ((G + 1 + 7) // 8) * 8
-        rec = None
-        # (the team kernel takes 16-byte aligned value and gradient rows only: csrc/attention.hip bwd_impl)
-        if (use_plan and ATTENTION_ALGO != 1 and _team_records_ok(C, G, rows.dtype) and rows.data_ptr() % 16 == 0
-                and gout.data_ptr() % 16 == 0):
-            rec = torch.empty((V, rs), dtype=torch.float32, device=rows.device)
-        with _timed("view_gather_attention_bwd",
-                    V * (C * es + 4 + 2 * G * 4 + (C * 4 * 2 if grows is not None else 0)
-                         + (rs * 4 if rec is not None else 0))
-                    + N * (C * es + 8 + 3 * G * 4)):
-            check(lib.dva_view_gather_attention_bwd(
-                ptr(gout), ptr(rows), ptr(row_idx), ptr(compat), ptr(att), ptr(gate), ptr(amax),
-                ptr(csr_idx), ptr(gw) if has_gate else None, ptr(gb) if has_gate else None, ptr(grows),
-                ptr(gcompat), ptr(gwb), ptr(rec), rs, N, V, C, G, scaling, dtype_code(rows), ATTENTION_ALGO,
-                stream_of(rows)), "dva_view_gather_attention_bwd")
-        if use_plan:
-            plan = ctx.plan if ctx.plan is not None else row_plan(row_idx, R, with_counts=False, split=False)[0]
-            perm, row_ptr = plan
-            vp = csr_expand(csr_idx, V) if rec is None else None
-            grows = torch.empty((R, C), dtype=torch.float32, device=rows.device)
-            # per view: perm + record (or view_point + scores) + grad_out row; per row: fp32 row written
-            with _timed("view_gather_rows_grad", V * (4 + (rs * 4 if rec is not None else 4 + 2 * G * 4) + C * es)
-                        + R * (C * 4 + 4)):
-                check(lib.dva_view_gather_rows_grad(
-                    ptr(gout), ptr(att), ptr(gate) if has_gate else None, ptr(vp), ptr(perm), ptr(row_ptr),
-                    ptr(rec), rs, ptr(grows), R, V, C, G, dtype_code(rows), stream_of(rows)),
-                    "dva_view_gather_rows_grad")
-        g_w = gwb[:G].reshape(w_shape) if (has_gate and w_shape is not None) else None
-        g_b = gwb[G:].reshape(b_shape) if (has_gate and b_shape is not None) else None
-        return (grows.to(rows.dtype) if grows is not None else None), None, gcompat, None, g_w, g_b, \
-            None, None, None
+        route = attention_bwd_route(rows.dtype, gout.dtype, out.dtype, C, G, V, R, N, ctx.needs_input_grad[0],
+                                    rows.data_ptr() % 16 == 0 and gout.data_ptr() % 16 == 0)
+        helper = {"lean_f32": _attn_bwd_lean_f32, "lean_16": _attn_bwd_lean_16, "team": _attn_bwd_team}[route.kernel]
+        grows, gcompat = helper(route, ctx.plan, rows, row_idx, compat, csr_idx, att, gate, amax, gw, gb, out, gout,
+                                gcompat, gwb, scaling, ctx.eps)
+        g_w, g_b = _gate_grads(gwb, G, has_gate, w_shape, b_shape)
+        return grows, None, gcompat, None, g_w, g_b, None, None, None
 
 
 def view_gather_attention(rows, row_idx, compat, csr_idx, gate_w=None, gate_b=None, scaling=False,

@@ -244,6 +244,14 @@ SIGNATURES = {
     "dva_mapping_merge_count": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
     "dva_mapping_merge_fill": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i64, _i64, _i64, _i64, _i64, _i64,
                                               _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "dva_mapping_select_tile_views": (ctypes.c_int, []),
+    "dva_mapping_select_workspace_bytes": (ctypes.c_int64, [_i64, _i64, _i64, _i32]),
+    "dva_mapping_select_count": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp,
+                                                _i64, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "dva_mapping_select_fill": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp,
+                                               _vp, _vp, _i64, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp,
+                                               _vp, _vp, _vp, _i64, _vp]),
+    "dva_mapping_image_stats": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _vp]),
     "dva_lex_workspace_bytes": (ctypes.c_int64, [_i64]),
     "dva_argsort_i64": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "dva_argunique_i64": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp]),

@@ -324,9 +324,19 @@ class PickImagesFromMappingArea(ImageTransform):
         assert images.mappings is not None, "No mappings found in images."
         m = images.mappings
         threshold = images.img_size[0] * images.img_size[1] * self.area_ratio
+        B = images.num_views
+        stats = m.image_stats(B)
+        if stats is not None:
+            # one device op: the exact integer atom counts (equal to the float sum of ones below 2^24 atoms per
+            # image) and the boxes, in the dtypes of the composition below
+            count, lo_x, hi_x, lo_y, hi_y = stats
+            if not self.use_bbox:
+                areas = count.float()
+            else:
+                areas = ((hi_x - lo_x).int() * (hi_y - lo_y).int()).masked_fill(count == 0, 0)
+            return data, images[self._pick(areas, threshold, images.num_views)]
         atom_ptr = m.values[1].pointers
         pixel_idx = m.images.repeat_interleave(atom_ptr[1:] - atom_ptr[:-1])
-        B = images.num_views
         if not self.use_bbox:
             areas = torch.zeros(B, device=pixel_idx.device).index_add_(
                 0, pixel_idx, torch.ones(pixel_idx.shape[0], device=pixel_idx.device))
@@ -339,12 +349,15 @@ class PickImagesFromMappingArea(ImageTransform):
             hi.scatter_reduce_(0, pixel_idx.view(-1, 1).expand(-1, 2), pix, 'amax')
             empty = lo[:, 0] == big                       # torch_scatter leaves 0 for images without pixels
             areas = ((hi[:, 0] - lo[:, 0]) * (hi[:, 1] - lo[:, 1])).masked_fill(empty, 0)
-        n_max = images.num_views if self.n_max is None else self.n_max
+        return data, images[self._pick(areas, threshold, images.num_views)]
+
+    def _pick(self, areas, threshold, num_views):
+        n_max = num_views if self.n_max is None else self.n_max
         idx = areas.argsort().flip(0)
         idx = idx[areas[idx] > threshold][:n_max]
-        if idx.shape[0] == 0 and images.num_views > 0 and self.n_min > 0:
+        if idx.shape[0] == 0 and num_views > 0 and self.n_min > 0:
             idx = idx[:self.n_min]
-        return data, images[idx]
+        return idx
 
 
 class PickMappingsFromMappingFeatures(ImageTransform):
@@ -526,7 +539,11 @@ class CropImageGroups(ImageTransform):
             return data, ImageData([images])
         dev = images.device
         W, H = images.img_size
-        x0, x1, y0, y1 = images.mappings.bounding_boxes
+        stats = images.mappings.image_stats(images.num_views)
+        if stats is None:
+            count, (x0, x1, y0, y1) = None, images.mappings.bounding_boxes
+        else:
+            count, x0, x1, y0, y1 = stats
         x0, y0 = (x0 - self.padding).clamp(min=0), (y0 - self.padding).clamp(min=0)
         x1, y1 = (x1 + self.padding).clamp(0, W), (y1 + self.padding).clamp(0, H)
         bw, bh = x1 - x0, y1 - y0
@@ -542,8 +559,14 @@ class CropImageGroups(ImageTransform):
         fits = torch.stack([(bw <= sw) & (bh <= sh) for sw, sh in ladder[:-1]] +
                            [torch.ones_like(bw, dtype=torch.bool)], dim=1)
         level = fits.int().argmax(dim=1)
+        if count is not None:
+            # bounding_boxes ends at the last image that has atoms, so the images behind it are in no crop family
+            ids = torch.arange(1, count.shape[0] + 1, device=count.device)
+            level = torch.where(ids <= (ids * (count > 0)).max(), level, -1)
         crop_families = {}
         for lv in torch.unique(level).tolist():
+            if lv < 0:
+                continue
             sw, sh = ladder[lv]
             idx = torch.where(level == lv)[0]
             # centre the box in the crop, inside the image borders

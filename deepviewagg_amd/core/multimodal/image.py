@@ -175,6 +175,16 @@ class ImageMapping(CSRData):
         mx = torch.full((n, 2), big.min, dtype=torch.long, device=self.device).scatter_reduce(0, idx, pix, 'amax')
         return mn[:, 0], mx[:, 0], mn[:, 1], mx[:, 1]
 
+    def image_stats(self, num_images):
+        """``(count, w_min, w_max, h_min, h_max)`` per image id below ``num_images``: the atoms of every image and
+        ``bounding_boxes`` for a known image count, in one device op without a host read (``ops.mapping_image_stats``).
+        Unlike ``bounding_boxes``, which ends at the last image that has atoms, every one of the ``num_images`` images
+        has an entry (the sentinels for one without atoms).  None where the op does not apply: a CPU mapping,
+        ``SELECT_ON_DEVICE`` off, pixels other than int16."""
+        if not self._select_on_device() or self.pixels.dtype != torch.int16:
+            return None
+        return ops.mapping_image_stats(self.images, self.values[1].pointers, self.pixels, num_images)
+
     @property
     def feature_map_indexing(self):
         """Index tuple ``X[idx]`` extracts the mapped features from X [B, C, H, W]
@@ -237,10 +247,58 @@ class ImageMapping(CSRData):
         out.pixels = new.long().type(pix.dtype)
         return out
 
+    # test / measurement hook: False sends device mappings through the torch compositions of select_points('pick'),
+    # select_images, select_views and crop as well
+    SELECT_ON_DEVICE = True
+
+    def _select_on_device(self):
+        return self.SELECT_ON_DEVICE and self.pointers.is_cuda
+
+    def _select_device(self, cls, fresh=False, **selection):
+        """``ops.select_mapping`` on this mapping: ``(mapping of class cls, info)``, the mapping None where the kernels
+        do not take the input (the caller then runs its composition).  The nested CSR has the class indexing it
+        gives (a batch loses its batch class); ``fresh``: the containers ``from_dense`` builds."""
+        from ..._lib import DvaError
+        try:
+            out = ops.select_mapping(self.pointers, self.images, self.values[1].pointers, self.pixels, self.features,
+                                     **selection)
+        except DvaError as err:
+            if err.code != -2:      # DVA_ERR_UNSUPPORTED: dtypes / sizes outside the kernels' range
+                raise
+            return None, None
+        info = out[5]
+        assert not info['duplicate_keys'], "Index must not contain duplicates."
+        if info['out_of_range'] and not fresh:
+            raise IndexError("index out of range in a mapping selection")
+        if out[0] is None:
+            return None, info
+        pointers, images, atom_ptr, pixels, features = out[:5]
+        nested = self.values[1]
+        if fresh:
+            values = [images, CSRData(atom_ptr, pixels, dense=False)]
+        else:
+            nested_cls = nested.__csr_type__ if isinstance(nested, CSRBatch) else type(nested)
+            values = [images, nested_cls(atom_ptr, pixels, dense=False, is_index_value=nested.is_index_value)]
+        if features is not None:
+            values.append(features)
+        is_index_value = [True, False, False][:len(values)] if fresh else self.is_index_value
+        return cls(pointers, *values, dense=False, is_index_value=is_index_value), info
+
     def select_images(self, idx):
-        """Keep the mappings to images ``idx`` and renumber them idx[i] -> i
-        (reference image.py:2029-2093)."""
+        """Keep the mappings to images ``idx`` and renumber them idx[i] -> i (reference image.py:2029-2093).  On a
+        device mapping this is one ``ops.select_mapping`` (the images are looked up in the sorted ``idx``, so no bound
+        on the image ids is read back; the "no duplicates" check travels in the op's one readback); CPU mappings, and
+        what the op does not take, go through ``_select_images_composition``."""
         idx = tensor_idx(idx).to(self.device)
+        if self._select_on_device() and self.num_views > 0 and idx.shape[0] > 0 and self.num_groups > 0:
+            keys, order = torch.sort(idx)
+            out, _ = self._select_device(type(self), image_keys=keys, image_map=order)
+            if out is not None:
+                return out
+        return self._select_images_composition(idx)
+
+    def _select_images_composition(self, idx):
+        """The reference's composition in torch: serves CPU mappings and is the yardstick of the device op."""
         assert idx.unique().numel() == idx.shape[0], "Index must not contain duplicates."
         if self.num_items == 0:
             return self.clone()
@@ -265,7 +323,23 @@ class ImageMapping(CSRData):
     def crop(self, crop_size, crop_offsets):
         """Copy of the mapping for images cropped to ``crop_size`` (W, H) at per-image ``crop_offsets``
         [B, 2]: pixel coordinates are shifted, pixels outside the box are dropped (reference
-        image.py:2279-2342, including its early return when no pixel at all is inside the boxes)."""
+        image.py:2279-2342, including its early return when no pixel at all is inside the boxes).  On a device
+        mapping this is one ``ops.select_mapping`` with one readback; the composition runs for CPU mappings, for what
+        the op does not take, and when no pixel is left (the early return)."""
+        if (self._select_on_device() and self.num_views > 0 and self.num_groups > 0 and crop_offsets.dim() == 2
+                and crop_offsets.dtype == torch.int64 and all(isinstance(c, int) for c in crop_size)):
+            out, info = self._select_device(ImageMapping, fresh=True, crop=(crop_size[0], crop_size[1],
+                                                                             crop_offsets.to(self.device)))
+            if info is not None:
+                n_img = info['num_seen']
+                assert crop_offsets.shape == (n_img, 2) and not info['out_of_range'], \
+                    f"Expected crop_offsets to have shape {(n_img, 2)} but got shape {crop_offsets.shape} instead."
+            if out is not None and info['num_atoms'] > 0:
+                return out
+        return self._crop_composition(crop_size, crop_offsets)
+
+    def _crop_composition(self, crop_size, crop_offsets):
+        """The reference's composition in torch: serves CPU mappings and is the yardstick of the device op."""
         n_img = self.images.unique().numel()
         assert crop_offsets.shape == (n_img, 2), \
             f"Expected crop_offsets to have shape {(n_img, 2)} but got shape {crop_offsets.shape} instead."
@@ -284,9 +358,26 @@ class ImageMapping(CSRData):
         return ImageMapping.from_dense(point_ids[inside], image_ids[inside], pixels[inside], features,
                                        num_points=self.num_groups)
 
-    def select_views(self, view_mask):
+    def select_views(self, view_mask, num_images=None):
         """Keep the views selected by a boolean mask; returns (mapping, seen image indices)
-        (reference image.py:2095-2165)."""
+        (reference image.py:2095-2165).  On a device mapping this is one ``ops.select_mapping`` with one readback when
+        the caller gives ``num_images`` (a bound above every image id; ``SameSettingImageData`` knows it from shapes);
+        without it one more device maximum is read back.  CPU mappings, and what the op does not take, go through
+        ``_select_views_composition``."""
+        if self._select_on_device() and self.num_views > 0 and self.num_groups > 0:
+            assert view_mask.dtype == torch.bool and view_mask.shape[0] == self.num_views
+            if num_images is None:
+                num_images = int(self.images.max()) + 1
+            out, info = self._select_device(type(self), view_mask=view_mask.to(self.device), compact=True,
+                                            num_images=num_images)
+            if out is not None:
+                if info['num_views'] == self.num_views:
+                    return self.clone(), None
+                return out, info['seen']
+        return self._select_views_composition(view_mask)
+
+    def _select_views_composition(self, view_mask):
+        """The reference's composition in torch: serves CPU mappings and is the yardstick of the device op."""
         assert view_mask.dtype == torch.bool and view_mask.shape[0] == self.num_items
         if self.num_items == 0 or bool(view_mask.all()):
             return self.clone(), None
@@ -312,24 +403,43 @@ class ImageMapping(CSRData):
         """'pick': keep the points ``idx`` (in that order). 'merge': point i becomes voxel idx[i];
         views of merged points are united, duplicate pixels removed, features of a merged view are
         averaged (reference image.py:2167-2277).  A merge of a device mapping is one device op
-        (``ops.merge_mapping``, a single readback of the output sizes); CPU mappings, and what the op
-        does not take, go through ``_merge_points_composition``."""
+        (``ops.merge_mapping``, a single readback of the output sizes), and so is a pick
+        (``ops.select_mapping``); CPU mappings, and what the ops do not take, go through
+        ``_merge_points_composition`` and the CSR indexing ``self[idx]``."""
         modes = ['pick', 'merge']
         assert mode in modes, f"Unknown mode '{mode}'. Supported modes are {modes}."
         idx = tensor_idx(idx).to(self.device)
         if idx is None or idx.shape[0] == 0 or self.num_groups == 0:
             return self.clone()
-        on_device = mode == 'merge' and self.MERGE_ON_DEVICE and self.pointers.is_cuda
+        on_device = (self.MERGE_ON_DEVICE if mode == 'merge' else self.SELECT_ON_DEVICE) and self.pointers.is_cuda
         # num_views is a shape, num_items a read of the last pointer: the same number, without the host sync
         if (self.num_views if on_device else self.num_items) == 0:
             out = self.clone()
             out.pointers = torch.zeros(idx.shape[0] + 1, dtype=torch.long, device=self.device)
             return out
         if mode == 'pick':
+            if on_device:
+                out, _ = self._select_device(self._picked_class(), point_idx=idx)
+                if out is not None:
+                    return out
             return self[idx]
         if on_device:
             return self._merge_points_device(idx)
         return self._merge_points_composition(idx)
+
+    def _picked_class(self):
+        """Class of ``self[idx]``: indexing a batch gives its plain type."""
+        return self.__csr_type__ if isinstance(self, CSRBatch) else type(self)
+
+    def _pick_points_compact(self, idx, num_images):
+        """``select_points(idx, 'pick')`` followed by the drop and renumbering of the images no picked point sees, in
+        one device op: ``(mapping, seen, seen as a host list)``, or None where the op does not apply."""
+        if not self._select_on_device() or idx.shape[0] == 0 or self.num_groups == 0 or self.num_views == 0:
+            return None
+        out, info = self._select_device(self._picked_class(), point_idx=idx, compact=True, num_images=num_images)
+        if out is None:
+            return None
+        return out, info['seen'], info['seen_host']
 
     def _merge_points_device(self, idx):
         from ..._lib import DvaError
@@ -604,6 +714,16 @@ class SameSettingImageData:
         if len(self) == 0:
             return self.clone()
         if mode == 'pick':
+            picked = self.mappings._pick_points_compact(idx, self.num_views)
+            if picked is not None:
+                # one device op: the pick, the images it sees and their renumbering; the seen images come back with
+                # the op's one readback, so the image attributes are indexed without a second one
+                mappings, seen, seen_host = picked
+                held, self._mappings = self._mappings, None
+                images = self._take_images(seen, np.asarray(seen_host, dtype=np.int64))
+                images.mappings = mappings
+                self._mappings = held
+                return images
             mappings = self.mappings.select_points(idx, mode=mode)
             seen = torch.unique(mappings.images) if mappings.num_items > 0 else []
             held, self._mappings = self._mappings, None
@@ -624,7 +744,7 @@ class SameSettingImageData:
     def select_views(self, view_mask):
         if self.mappings is None or view_mask is None or bool(torch.all(view_mask)) or len(self) == 0:
             return self.clone()
-        mappings, seen = self.mappings.select_views(view_mask)
+        mappings, seen = self.mappings.select_views(view_mask, num_images=self.num_views)
         held, self._mappings = self._mappings, None
         images = self[seen] if seen is not None else self.clone()
         self._mappings = held
@@ -673,9 +793,14 @@ class SameSettingImageData:
 
     def __getitem__(self, idx):
         """Select images (no duplicates); mappings follow (reference image.py:1109-1148)."""
-        idx = tensor_idx(idx).to(self.device)
-        assert idx.unique().numel() == idx.shape[0], "Index must not contain duplicates."
-        idx_np = np.asarray(idx.cpu())
+        return self._take_images(tensor_idx(idx).to(self.device))
+
+    def _take_images(self, idx, idx_np=None):
+        """``self[idx]`` for a LongTensor on the device; ``idx_np``: the same index on the host, known to hold no
+        duplicates (then nothing is read back)."""
+        if idx_np is None:
+            assert idx.unique().numel() == idx.shape[0], "Index must not contain duplicates."
+            idx_np = np.asarray(idx.cpu())
 
         def sel(a):
             return a[idx] if a is not None else None
@@ -896,9 +1021,9 @@ class WindowedSameSettingImageData(SameSettingImageData):
             out._source_roll = roll if device is None else roll.to(device)
         return out
 
-    def __getitem__(self, idx):
-        out = self._without_pixels(SameSettingImageData.__getitem__, idx)
-        return self._follow(out, idx=tensor_idx(idx).to(self.device))
+    def _take_images(self, idx, idx_np=None):
+        out = self._without_pixels(SameSettingImageData._take_images, idx, idx_np)
+        return self._follow(out, idx=idx)
 
     def clone(self):
         return self._follow(self._without_pixels(SameSettingImageData.clone))

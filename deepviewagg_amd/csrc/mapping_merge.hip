@@ -23,6 +23,7 @@
 // Image ids are < 2^31 and pixels are non-negative int16 (the key packing); a view without atoms contributes
 // nothing (the reference drops it when it expands to atom rows).
 #include "dva_common.h"
+#include "scan.h"
 
 namespace dva {
 
@@ -30,12 +31,7 @@ constexpr int MERGE_TILE = 512;      // atoms of a voxel staged in LDS: 2 x 4 Ki
 constexpr int MERGE_GRID = 32768;    // blocks of the per-voxel kernels (grid-stride above)
 constexpr int BIG_THREADS = 1024;
 constexpr int BIG_GRID = 256;
-constexpr int SCAN_THREADS = 256;
-constexpr int SCAN_ITEMS = 4;
-constexpr int SCAN_BLOCK = SCAN_THREADS * SCAN_ITEMS;
 constexpr int MERGE_MAX_F = 1 << 16;
-
-typedef unsigned long long u64;
 
 // counters at the start of the workspace
 enum { C_BAD = 0, C_M = 1, C_NBIG = 2, C_AUSED = 3, C_VUSED = 4, C_COUNT = 8 };
@@ -76,31 +72,9 @@ static inline MergeLayout merge_layout(void* ws, int64_t N, int64_t V, int64_t P
 // wavefront helpers
 // ---------------------------------------------------------------------------------------------------------------
 
-// orders the LDS / global accesses of the lanes of ONE wavefront (the block-wide kernels use __syncthreads)
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-__device__ __forceinline__ u64 lanes_below(int lane) { return lane == 0 ? 0ull : (~0ull >> (64 - lane)); }
-
-__device__ __forceinline__ long long wave_sum(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, DVA_WAVE);
-  return v;
-}
 __device__ __forceinline__ int wave_max(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, DVA_WAVE));
-  return v;
-}
-__device__ __forceinline__ long long wave_incl_scan(long long v, int lane) {
-#pragma unroll
-  for (int o = 1; o < DVA_WAVE; o <<= 1) {
-    const long long t = __shfl_up(v, o, DVA_WAVE);
-    if (lane >= o) v += t;
-  }
   return v;
 }
 
@@ -141,81 +115,7 @@ __global__ __launch_bounds__(256) void merge_scatter_kernel(const int64_t* __res
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// exclusive scan of n int32 (totals < 2^31): out[0 .. n], out[n] = total
-// ---------------------------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ int block_excl_scan(int v, int* total, int* wsum) {
-  const int lane = threadIdx.x & (DVA_WAVE - 1), w = threadIdx.x / DVA_WAVE;
-  const int incl = (int)wave_incl_scan(v, lane);
-  __syncthreads();      // wsum of the previous call has been read
-  if (lane == DVA_WAVE - 1) wsum[w] = incl;
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int k = 0; k < SCAN_THREADS / DVA_WAVE; ++k) {
-    const int s = wsum[k];
-    if (k < w) before += s;
-    all += s;
-  }
-  *total = all;
-  return before + incl - v;
-}
-
-__global__ __launch_bounds__(SCAN_THREADS) void scan_partial_kernel(const int* __restrict__ in, int64_t n,
-                                                                     int* __restrict__ bsum) {
-  __shared__ int wsum[SCAN_THREADS / DVA_WAVE];
-  const int64_t i0 = blockIdx.x * (int64_t)SCAN_BLOCK + threadIdx.x * SCAN_ITEMS;
-  int s = 0;
-#pragma unroll
-  for (int c = 0; c < SCAN_ITEMS; ++c)
-    if (i0 + c < n) s += in[i0 + c];
-  int total;
-  block_excl_scan(s, &total, wsum);
-  if (threadIdx.x == 0) bsum[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(SCAN_THREADS) void scan_spine_kernel(int* __restrict__ bsum, int64_t nb) {
-  __shared__ int wsum[SCAN_THREADS / DVA_WAVE];
-  int carry = 0;
-  for (int64_t c0 = 0; c0 < nb; c0 += SCAN_THREADS) {
-    const int64_t i = c0 + threadIdx.x;
-    const int v = i < nb ? bsum[i] : 0;
-    int total;
-    const int excl = block_excl_scan(v, &total, wsum);
-    if (i < nb) bsum[i] = carry + excl;
-    carry += total;
-  }
-  if (threadIdx.x == 0) bsum[nb] = carry;
-}
-
-__global__ __launch_bounds__(SCAN_THREADS) void scan_apply_kernel(const int* __restrict__ in, int64_t n,
-                                                                   const int* __restrict__ bsum, int64_t nb,
-                                                                   int* __restrict__ out) {
-  __shared__ int wsum[SCAN_THREADS / DVA_WAVE];
-  const int64_t i0 = blockIdx.x * (int64_t)SCAN_BLOCK + threadIdx.x * SCAN_ITEMS;
-  int v[SCAN_ITEMS], s = 0;
-#pragma unroll
-  for (int c = 0; c < SCAN_ITEMS; ++c) {
-    v[c] = i0 + c < n ? in[i0 + c] : 0;
-    s += v[c];
-  }
-  int total;
-  int run = bsum[blockIdx.x] + block_excl_scan(s, &total, wsum);
-#pragma unroll
-  for (int c = 0; c < SCAN_ITEMS; ++c) {
-    if (i0 + c < n) out[i0 + c] = run;
-    run += v[c];
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = bsum[nb];
-}
-
-static inline void launch_scan(const int* in, int64_t n, int* bsum, int64_t nb, int* out, hipStream_t s) {
-  hipLaunchKernelGGL(scan_partial_kernel, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, in, n, bsum);
-  hipLaunchKernelGGL(scan_spine_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, bsum, nb);
-  hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, in, n, (const int*)bsum, nb,
-                     out);
-}
+// the exclusive scans (n int32, totals < 2^31) are launch_scan<int> of scan.h
 
 // ---------------------------------------------------------------------------------------------------------------
 // per-voxel work.  The staging and the passes over the sorted keys are run by ONE wavefront (lane = 0 .. 63); the

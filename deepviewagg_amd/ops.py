@@ -24,6 +24,7 @@ ops; names and argument meaning follow the reference call site
 ``lovasz_softmax_flat``    metrics/lovasz_loss.py:174-215 (``flatten_probas`` + ``lovasz_softmax_flat``)
 ``confusion_counts``       metrics/segmentation_tracker.py:72-83 (mask + ``np.argmax`` + ``np.bincount``)
 ``merge_mapping``          core/multimodal/image.py:2211-2273 (``select_points(mode='merge')`` + ``from_dense``)
+``select_mapping``         core/multimodal/image.py:2029-2210, :2279-2342 (``select_images / _views / _points('pick')``, ``crop``)
 =========================  ==========================================================
 
 All ops require tensors on a HIP device and raise otherwise (no CPU fallback).
@@ -1755,6 +1756,158 @@ def merge_mapping(pointers, images, atom_ptr, pixels, features, idx):
     if out_feat is not None and features.dim() == 1:
         out_feat = out_feat.view(-1)
     return out_ptr, out_img, out_aptr, out_pix, out_feat, True
+
+
+# ---------------------------------------------------------------------------------------------
+# mapping selection: pick, views, images, crop (core/multimodal/image.py:2029-2342, csr.py:235-294)
+# ---------------------------------------------------------------------------------------------
+
+def _select_unsupported(what):
+    return _lib.DvaError(f"ops.select_mapping: {what}: {_lib._ERRORS[-2]}", code=-2)
+
+
+def select_mapping(pointers, images, atom_ptr, pixels, features, *, point_idx=None, view_mask=None, image_map=None,
+                   compact=False, crop=None, num_images=None, image_keys=None):
+    """Filter, compact and renumber a mapping in one device operation: ``(pointers', images', atom_ptr', pixels',
+    features', info)``.  Output point ``m`` is source point ``point_idx[m]`` (int64, any order, duplicates allowed;
+    all points in order without it).  A source view survives if ``view_mask`` (bool [V]) is set for it and, with
+    ``image_map`` (int64 [B]), if ``image_map[image] >= 0``, which is then its new image id; with ``image_keys``
+    (int64 [K], ASCENDING) as well, ``image_map`` has one entry per key and a view survives if its image is a key with
+    a new id ``>= 0`` -- the form that needs no bound on the image ids.  ``compact`` (exclusive with ``image_map``)
+    gives a surviving view the rank of its image among the distinct surviving images, ``info['seen']``; it needs
+    ``num_images``, above every image id.  ``crop = (W, H, offsets [B, 2])`` (exclusive with ``image_map`` and
+    ``compact``; offsets indexed by image id): atom pixels become ``pixel - offset[image]`` in the pixel dtype, atoms
+    outside ``[0, W) x [0, H)`` and views left without atoms are dropped, the surviving views of a point are ordered
+    by ascending image id (stably), and the features of a view are the fp32 mean of ``c`` copies of its source
+    features, ``c`` its surviving atoms, added one after the other.  Features are copied as bits otherwise.
+
+    ``info``: ``seen`` (int64 device tensor: the distinct surviving images with ``compact``, the distinct images of
+    the views that pass the mask with ``crop``, else None), ``seen_host`` (the same as a list), ``num_seen``,
+    ``unsupported`` (a crop that leaves two views of one point with the same image, which ``from_dense`` would unite,
+    or 2^31 or more views or atoms), ``out_of_range`` (a point index or image id outside its range) and
+    ``duplicate_keys``.  With any of the three set the tensors are None.  One host synchronisation: the readback of
+    sizes, flags and ``seen`` in one buffer.  Raises ``DvaError`` with ``code == -2`` for what the kernels do not take
+    (pixels other than int16, indices other than int64, features other than fp32, 2^31 or more views or atoms)."""
+    lib = _lib.load()
+    dev = require_device(pointers, images, atom_ptr, pixels, features, point_idx, view_mask, image_map, image_keys)
+    named = [("pointers", pointers), ("images", images), ("atom_ptr", atom_ptr), ("point_idx", point_idx),
+             ("image_map", image_map), ("image_keys", image_keys)]
+    for name, t in named:
+        if t is None:
+            continue
+        if t.dim() != 1:
+            raise ValueError(f"ops.select_mapping: {name} must be 1-D, got {tuple(t.shape)}")
+        if t.dtype != torch.int64:
+            raise _select_unsupported(f"{name} is {t.dtype}, not int64")
+    if pixels.dim() != 2 or pixels.shape[1] != 2:
+        raise ValueError(f"ops.select_mapping: pixels must be [P, 2], got {tuple(pixels.shape)}")
+    if pixels.dtype != torch.int16:
+        raise _select_unsupported(f"pixels are {pixels.dtype}, not int16")
+    n, v, p = pointers.shape[0] - 1, images.shape[0], pixels.shape[0]
+    if n < 1 or atom_ptr.shape[0] != v + 1:
+        raise ValueError(f"ops.select_mapping: {n} points, {v} views and {atom_ptr.shape[0]} atom pointers")
+    if features is not None and (features.dim() not in (1, 2) or features.shape[0] != v):
+        raise ValueError(f"ops.select_mapping: features must be [{v}, F] or [{v}], got {tuple(features.shape)}")
+    if features is not None and features.dtype != torch.float32:
+        raise _select_unsupported(f"features are {features.dtype}, not float32")
+    if view_mask is not None and (view_mask.dtype != torch.bool or tuple(view_mask.shape) != (v,)):
+        raise ValueError(f"ops.select_mapping: view_mask must be bool [{v}]")
+    if image_map is not None and (compact or crop is not None):
+        raise ValueError("ops.select_mapping: image_map excludes compact and crop")
+    if compact and crop is not None:
+        raise ValueError("ops.select_mapping: compact excludes crop")
+    if image_keys is not None and (image_map is None or image_map.shape != image_keys.shape):
+        raise ValueError("ops.select_mapping: image_keys needs an image_map with one entry per key")
+    m = n if point_idx is None else point_idx.shape[0]
+    if m < 1:
+        raise ValueError("ops.select_mapping: no output point")
+    crop_w = crop_h = 0
+    offsets = None
+    b = 0
+    if crop is not None:
+        crop_w, crop_h, offsets = int(crop[0]), int(crop[1]), crop[2]
+        require_device(pointers, offsets)
+        if offsets.dim() != 2 or offsets.shape[1] != 2:
+            raise ValueError(f"ops.select_mapping: crop offsets must be [B, 2], got {tuple(offsets.shape)}")
+        if offsets.dtype != torch.int64:
+            raise _select_unsupported(f"crop offsets are {offsets.dtype}, not int64")
+        if crop_w < 1 or crop_h < 1:
+            raise ValueError(f"ops.select_mapping: crop size {(crop_w, crop_h)}")
+        offsets = offsets.contiguous()
+        b = offsets.shape[0]
+        if num_images is not None and int(num_images) != b:
+            raise ValueError(f"ops.select_mapping: {b} crop offsets for num_images={num_images}")
+    elif compact:
+        if num_images is None:
+            raise ValueError("ops.select_mapping: compact needs num_images")
+        b = int(num_images)
+    try:
+        ws, nbytes = _lib.workspace("dva_mapping_select_workspace_bytes", dev, m, v, b, int(crop is not None))
+    except _lib.DvaError as e:
+        if e.code != -2:
+            raise
+        raise _select_unsupported(f"{m} points, {v} views, {b} images") from None
+    pointers, images, atom_ptr, pixels = (pointers.contiguous(), images.contiguous(), atom_ptr.contiguous(),
+                                          pixels.contiguous())
+    point_idx, view_mask, image_map, image_keys = (None if t is None else t.contiguous()
+                                                   for t in (point_idx, view_mask, image_map, image_keys))
+    f = 0 if features is None else (1 if features.dim() == 1 else features.shape[1])
+    feat = None if features is None else features.detach().reshape(v, f).contiguous()
+    feat_in = feat if f > 0 else None
+    n_map = 0 if image_map is None else image_map.shape[0]
+    sizes = torch.empty(4 + b, dtype=torch.int64, device=dev)
+    s = stream_of(pointers)
+    sel = (ptr(point_idx), m, ptr(view_mask), ptr(image_keys), ptr(image_map), n_map, int(bool(compact)), b, crop_w,
+           crop_h, ptr(offsets))
+    read = m * 16 + v * (16 + (view_mask is not None)) + (p * 4 if crop is not None else 0)
+    with _timed("mapping_select_count", read + m * 8):
+        check(lib.dva_mapping_select_count(ptr(pointers), ptr(images), ptr(atom_ptr), ptr(pixels), 2, n, v, p, *sel,
+                                           ptr(sizes), ptr(ws), int(nbytes), s), "dva_mapping_select_count")
+    host = sizes.tolist()                                 # host read: sizes, flags and the seen images together
+    v_out, p_out, n_seen, flags = host[:4]
+    tracked = compact or crop is not None
+    info = dict(seen=sizes[4:4 + n_seen] if tracked else None, seen_host=host[4:4 + n_seen] if tracked else None,
+                num_seen=n_seen, unsupported=bool(flags & 1), out_of_range=bool(flags & 2),
+                duplicate_keys=bool(flags & 4), num_views=v_out, num_atoms=p_out)
+    if flags:
+        return None, None, None, None, None, info
+    out_ptr = torch.empty(m + 1, dtype=torch.int64, device=dev)
+    out_img = torch.empty(v_out, dtype=torch.int64, device=dev)
+    out_aptr = torch.empty(v_out + 1, dtype=torch.int64, device=dev)
+    out_pix = torch.empty((p_out, 2), dtype=torch.int16, device=dev)
+    out_feat = None if feat is None else torch.empty((v_out, f), dtype=torch.float32, device=dev)
+    with _timed("mapping_select_fill", read + p * 4 + m * 8 + v_out * (16 + 8 * f) + p_out * 8):
+        check(lib.dva_mapping_select_fill(ptr(pointers), ptr(images), ptr(atom_ptr), ptr(pixels), 2, ptr(feat_in), f,
+                                          n, v, p, *sel, v_out, p_out, ptr(out_ptr), ptr(out_img), ptr(out_aptr),
+                                          ptr(out_pix), ptr(out_feat if f > 0 else None), ptr(ws), int(nbytes), s),
+              "dva_mapping_select_fill")
+    if out_feat is not None:
+        out_feat = out_feat.view((v_out,) + tuple(features.shape[1:]))
+    return out_ptr, out_img, out_aptr, out_pix, out_feat, info
+
+
+def mapping_image_stats(images, atom_ptr, pixels, num_images):
+    """Per image id ``< num_images`` of a mapping: ``(count, x_min, x_max, y_min, y_max)``, int64 [num_images] each --
+    its number of atoms and the bounding box of its pixels, by integer atomics (order-free).  An image without atoms
+    has ``iinfo(int64).max`` / ``.min`` as minima / maxima, the sentinels of ``ImageMapping.bounding_boxes``.  No
+    host synchronisation.  ``DvaError`` with ``code == -2`` for pixels other than int16 or indices other than int64."""
+    lib = _lib.load()
+    dev = require_device(images, atom_ptr, pixels)
+    if images.dtype != torch.int64 or atom_ptr.dtype != torch.int64:
+        raise _lib.DvaError(f"ops.mapping_image_stats: indices are not int64: {_lib._ERRORS[-2]}", code=-2)
+    if pixels.dtype != torch.int16:
+        raise _lib.DvaError(f"ops.mapping_image_stats: pixels are {pixels.dtype}, not int16: {_lib._ERRORS[-2]}",
+                            code=-2)
+    v, p, b = images.shape[0], pixels.shape[0], int(num_images)
+    if images.dim() != 1 or tuple(atom_ptr.shape) != (v + 1,) or pixels.dim() != 2 or pixels.shape[1] != 2 or b < 0:
+        raise ValueError(f"ops.mapping_image_stats: {v} views, {tuple(atom_ptr.shape)} atom pointers, pixels "
+                         f"{tuple(pixels.shape)}, {b} images")
+    images, atom_ptr, pixels = images.contiguous(), atom_ptr.contiguous(), pixels.contiguous()
+    stats = torch.empty((5, b), dtype=torch.int64, device=dev)
+    with _timed("mapping_image_stats", v * 16 + p * 4 + b * 40):
+        check(lib.dva_mapping_image_stats(ptr(images), ptr(atom_ptr), ptr(pixels), 2, v, p, b, ptr(stats),
+                                          stream_of(images)), "dva_mapping_image_stats")
+    return stats[0], stats[1], stats[2], stats[3], stats[4]
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1305,6 +1305,60 @@ int dva_mapping_merge_fill(const int64_t* pointers, const int64_t* images, const
                            int64_t* out_atom_ptr, void* out_pixels, float* out_features, void* workspace,
                            int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------ *
+ * Mapping selection.  Replaces the torch compositions of ImageMapping.select_points(mode='pick'),
+ * select_images, select_views and crop (core/multimodal/image.py:2029-2342, csr.py:235-294): one
+ * filter / compact / renumber of the nested CSR point -> views -> atoms, with one readback.
+ * Mapping as for the merge (pixels int16, pixel_bytes = 2; 1 / 4 / 8 return DVA_ERR_UNSUPPORTED;
+ * features fp32 [n_views, F] nullable).  Output point m is source point point_idx[m] (int64 [n_out],
+ * any order, duplicates allowed; null: all points in order, n_out = n_points).  A source view
+ * survives if view_mask (uint8 [n_views], nullable) is set for it and
+ *   image_map without image_keys: image_map[image] >= 0 (int64 [n_map]; an image >= n_map is dropped),
+ *   image_map with image_keys:    image == image_keys[k] for some k and image_map[k] >= 0 (image_keys
+ *                                 int64 [n_map] ASCENDING; a repeated key sets flag bit 2),
+ * and it gets that new id.  compact (exclusive with image_map): the new id of a surviving view is the
+ * rank of its image among the distinct surviving images, which must be < n_images.  crop_offsets (int64
+ * [n_images, 2], exclusive with image_map and compact): atom pixels become pixel - offset[image] in
+ * int16 arithmetic, atoms outside [0, crop_w) x [0, crop_h) and views left without atoms are dropped,
+ * the surviving views of a point are ordered by ascending image, stably, and the features of a view
+ * are acc = 0; acc += f (c times); acc /= (float)c for its c surviving atoms.  Two surviving views of
+ * one point with the same image set flag bit 0.  n_images is 0 without compact and crop.
+ * dva_mapping_select_count writes sizes (device int64 [4 + n_images]) = {views of the result, atoms of
+ * the result, distinct images, flags, the distinct images ascending ...}: the distinct images are those
+ * of the surviving views with compact, and of the source views that pass view_mask with a crop.
+ * flags: bit 0 unsupported (see above, or 2^31 - 1 or more views or atoms in the result), bit 1 a point
+ * index or image id out of range, bit 2 a repeated image key; with any of them set the fill must not
+ * be called.  The caller reads sizes back (the only host synchronisation), allocates the outputs and
+ * calls dva_mapping_select_fill with the SAME arguments and workspace, untouched in between:
+ * out_pointers int64 [n_out + 1], out_images int64 [V'], out_atom_ptr int64 [V' + 1], out_pixels int16
+ * [P', 2], out_features fp32 [V', F] (null when features is null; an empty output may be null).  Every
+ * output element is written exactly once, without float atomics; features are copied as bits except
+ * under a crop.
+ * dva_mapping_select_tile_views: the views of a point up to which a crop orders them in LDS.
+ * Sizes of 2^31 - 1 or more return DVA_ERR_UNSUPPORTED.
+ * dva_mapping_image_stats: stats int64 [5, n_images] = per image id < n_images the number of atoms,
+ * then min x, max x, min y, max y of its pixels (integer atomics), INT64_MAX / INT64_MIN for the minima /
+ * maxima of an image without atoms; views of other image ids are skipped.
+ * ------------------------------------------------------------------------------------------ */
+int dva_mapping_select_tile_views(void);
+int64_t dva_mapping_select_workspace_bytes(int64_t n_out, int64_t n_views, int64_t n_images, int32_t crop);
+int dva_mapping_select_count(const int64_t* pointers, const int64_t* images, const int64_t* atom_ptr,
+                             const void* pixels, int32_t pixel_bytes, int64_t n_points, int64_t n_views,
+                             int64_t n_atoms, const int64_t* point_idx, int64_t n_out, const uint8_t* view_mask,
+                             const int64_t* image_keys, const int64_t* image_map, int64_t n_map, int32_t compact,
+                             int64_t n_images, int64_t crop_w, int64_t crop_h, const int64_t* crop_offsets,
+                             int64_t* sizes, void* workspace, int64_t workspace_bytes, void* stream);
+int dva_mapping_select_fill(const int64_t* pointers, const int64_t* images, const int64_t* atom_ptr,
+                            const void* pixels, int32_t pixel_bytes, const float* features, int32_t F,
+                            int64_t n_points, int64_t n_views, int64_t n_atoms, const int64_t* point_idx,
+                            int64_t n_out, const uint8_t* view_mask, const int64_t* image_keys,
+                            const int64_t* image_map, int64_t n_map, int32_t compact, int64_t n_images, int64_t crop_w,
+                            int64_t crop_h, const int64_t* crop_offsets, int64_t n_views_out, int64_t n_atoms_out,
+                            int64_t* out_pointers, int64_t* out_images, int64_t* out_atom_ptr, void* out_pixels,
+                            float* out_features, void* workspace, int64_t workspace_bytes, void* stream);
+int dva_mapping_image_stats(const int64_t* images, const int64_t* atom_ptr, const void* pixels, int32_t pixel_bytes,
+                            int64_t n_views, int64_t n_atoms, int64_t n_images, int64_t* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -149,6 +149,8 @@ SIGNATURES = {
     "dva_qkv_compat_bwd": (ctypes.c_int, [_vp] * 7 + [_i64, _i64, _i32, _f32, _vp]),
     "dva_plan_split_table_bytes": (ctypes.c_int64, [_i64, _i64]),
     "dva_plan_split_build": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "dva_mapping_row_index_split": (ctypes.c_int, [_vp, _vp, _i32, ctypes.c_double, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
+                                                   _i64, _vp, _i64, _vp]),
     "dva_plan_split_sort_records": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
     "dva_plan_split_sort_records32": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),
     "dva_plan_split_rows_grad": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp]),

@@ -119,6 +119,20 @@ struct __attribute__((aligned(8))) PackedIdx {
   int16_t y;
 };
 
+// torch.floor_divide on floats (c10::div_floor_floating): floor of the exact quotient a/b.  The pixel rounding of every
+// kernel that maps a pixel onto a feature map (gather.hip, plan_split.hip).
+__device__ __forceinline__ float floordiv_f32(float a, float b) {
+  const float mod = fmodf(a, b);
+  float div = __fdiv_rn(__fsub_rn(a, mod), b);
+  if (mod != 0.f && ((b < 0.f) != (mod < 0.f))) div = __fsub_rn(div, 1.f);
+  if (div != 0.f) {
+    float fl = floorf(div);
+    if (__fsub_rn(div, fl) > 0.5f) fl = __fadd_rn(fl, 1.f);
+    return fl;
+  }
+  return copysignf(0.f, __fdiv_rn(a, b));
+}
+
 static inline int blocks_for(int64_t n, int threads) { return (int)((n + threads - 1) / threads); }
 
 // Launch grid of a grid-stride kernel: ceil(n / per_block) blocks, at most `cap`, at least 1.

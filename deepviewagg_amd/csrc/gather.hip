@@ -10,19 +10,6 @@
 
 namespace dva {
 
-// torch.floor_divide on floats (c10::div_floor_floating): floor of the exact quotient a/b.
-__device__ __forceinline__ float floordiv_f32(float a, float b) {
-  const float mod = fmodf(a, b);
-  float div = __fdiv_rn(__fsub_rn(a, mod), b);
-  if (mod != 0.f && ((b < 0.f) != (mod < 0.f))) div = __fsub_rn(div, 1.f);
-  if (div != 0.f) {
-    float fl = floorf(div);
-    if (__fsub_rn(div, fl) > 0.5f) fl = __fadd_rn(fl, 1.f);
-    return fl;
-  }
-  return copysignf(0.f, __fdiv_rn(a, b));
-}
-
 template <typename PIX>
 __global__ __launch_bounds__(256) void pack_index_kernel(const int64_t* __restrict__ images,
                                                           const int64_t* __restrict__ atom_ptr,

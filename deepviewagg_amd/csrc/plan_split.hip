@@ -6,6 +6,8 @@
 //
 //   build (keys only):  hist_hi -> scan_tiles -> bucket_starts -> scatter<LOWS> (9-bit low digits, bucket order)
 //                       -> hist_lo -> scan_rows  => counts[R], row_ptr[R + 1], offA[bucket][tile], offB[tile][digit]
+//                       (exact mappings, dva_mapping_row_index_split: mapping_row_index_kernel_hist writes the keys and
+//                       is hist_hi in the same pass)
 //   records:            scatter<REC_A> (view order -> bucket order), then either
 //                         bucket_rows_grad (C <= 64): one workgroup per bucket of 512 rows ranks + stages the bucket's
 //                           records in LDS like a second pass and CONSUMES them there (sums in registers), or
@@ -105,6 +107,73 @@ __global__ __launch_bounds__(TILE / IPT) void hist_hi_kernel(const uint32_t* __r
   }
   __syncthreads();
   for (int i = threadIdx.x; i < nb; i += THREADS) offA[(int64_t)i * nt + blockIdx.x] = h[i];
+}
+
+// The first step of the build for an EXACT mapping (one atom per view: atom == view, no atom pointers): the row keys are
+// produced (mapping_row_index_kernel of gather.hip, the same arithmetic) and counted in the pass that writes them, so
+// hist_hi never reads them back -- 12 bytes read (image id + int16 pixel pair) and 4 written per view instead of 28 + 4.
+// The entry pattern of hist_hi_kernel: all of a thread's IPT loads are in flight before its first LDS atomic.
+// One workgroup walks K consecutive tiles, one LDS histogram each (stride BINS + 1: the write-out reads K histograms at
+// one digit), and writes K adjacent ints per bucket -- offA[d][t0 .. t0 + K) -- where one tile per workgroup leaves one
+// dword per bucket at a stride of nt ints.  113 us at 2^25 views (4.9 TB/s) against 154 + 70; issuing a tile's loads one
+// tile ahead (two register sets) measured the same: the LDS atomics, not the load latency, are what is left.
+#ifndef DVA_PLAN_FUSED_K
+#define DVA_PLAN_FUSED_K 16      // (the A/B of csrc/Makefile EXTRA=; chosen by measurement, see build_from_mapping)
+#endif
+constexpr int FUSED_K = DVA_PLAN_FUSED_K;
+
+template <typename PIX>
+struct __attribute__((aligned(2 * sizeof(PIX)))) PixPair {
+  PIX x, y;
+};
+
+template <typename PIX, int TILE, int K>
+__global__ __launch_bounds__(TILE / IPT) void mapping_row_index_kernel_hist(const int64_t* __restrict__ images,
+                                                                            const PixPair<PIX>* __restrict__ pixels,
+                                                                            double ratio, int64_t n, int H, int W, int nb,
+                                                                            int64_t nt, int32_t* __restrict__ row_idx,
+                                                                            int32_t* __restrict__ offA) {
+  constexpr int THREADS = TILE / IPT, HS = BINS + 1;
+  __shared__ int h[K * HS];
+  for (int i = threadIdx.x; i < K * HS; i += THREADS) h[i] = 0;
+  __syncthreads();
+  const int64_t t0 = (int64_t)blockIdx.x * K;
+  const float rf = (float)ratio;
+  for (int j = 0; j < K && t0 + j < nt; ++j) {
+    const int64_t base = (t0 + j) * TILE;
+    int64_t im[IPT];
+    PixPair<PIX> px[IPT];
+#pragma unroll
+    for (int k = 0; k < IPT; ++k) {
+      const int64_t e = base + k * THREADS + threadIdx.x;
+      const int64_t g = e < n ? e : n - 1;
+      im[k] = images[g];
+      px[k] = pixels[g];
+    }
+#pragma unroll
+    for (int k = 0; k < IPT; ++k) {
+      const int64_t e = base + k * THREADS + threadIdx.x;
+      const int32_t img = (int32_t)im[k];
+      int32_t x, y;
+      if (ratio == 1.0) {
+        x = (int32_t)px[k].x;
+        y = (int32_t)px[k].y;
+      } else {
+        x = (int32_t)(int16_t)floordiv_f32((float)px[k].x, rf);
+        y = (int32_t)(int16_t)floordiv_f32((float)px[k].y, rf);
+      }
+      const int32_t key = (img * H + y) * W + x;
+      if (e < n) {
+        row_idx[e] = key;
+        atomicAdd(&h[j * HS + hi_digit((uint32_t)key, nb)], 1);
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nb * K; i += THREADS) {
+    const int d = i / K, j = i % K;
+    if (t0 + j < nt) offA[(int64_t)d * nt + t0 + j] = h[j * HS + d];
+  }
 }
 
 // row d of offA[nb][nt]: counts -> exclusive prefix over the tiles (in place, chunks of 256 tiles); tot[d] = row sum
@@ -636,11 +705,11 @@ static inline Tables tables_of(void* tables, const Layout& L) {
 // grid of a scatter pass: its tiles rounded up to a multiple of 8 for the XCD-aware order (the extra workgroups exit)
 static inline unsigned scatter_grid(int64_t tiles) { return (unsigned)((tiles + 7) / 8 * 8); }
 
-static void build(const uint32_t* keys, int64_t n, int64_t n_rows, int32_t* row_ptr, int32_t* counts, const Layout& L,
-                  const Tables& T, void* scratch, hipStream_t s) {
+// everything of the build after the first histogram (offA holds the per-tile counts of the high digit)
+static void build_tail(const uint32_t* keys, int64_t n, int64_t n_rows, int32_t* row_ptr, int32_t* counts, const Layout& L,
+                       const Tables& T, void* scratch, hipStream_t s) {
   constexpr int TILE = PLAN_TILE, THREADS = TILE / IPT;
   const int nb = (int)L.nb;
-  hipLaunchKernelGGL(hist_hi_kernel<TILE>, dim3((unsigned)L.nt), dim3(THREADS), 0, s, keys, n, nb, L.nt, T.offA);
   hipLaunchKernelGGL(scan_tiles_kernel, dim3(nb), dim3(256), 0, s, T.offA, L.nt, T.tot);
   hipLaunchKernelGGL(bucket_starts_kernel, dim3(1), dim3(BINS), 0, s, T.tot, nb, TILE, T.bstart, T.tstart, T.desc, T.order);
   hipLaunchKernelGGL((scatter_kernel<MODE_LOWS, TILE>), dim3(scatter_grid(L.nt)), dim3(THREADS), 0, s, keys,
@@ -649,6 +718,32 @@ static void build(const uint32_t* keys, int64_t n, int64_t n_rows, int32_t* row_
   hipLaunchKernelGGL(hist_lo_kernel<TILE>, dim3((unsigned)L.ntb), dim3(THREADS), 0, s, (const uint16_t*)scratch, nb,
                      T.tstart, T.desc, T.offB);
   hipLaunchKernelGGL(scan_rows_kernel, dim3(nb), dim3(BINS), 0, s, T.offB, T.bstart, T.tstart, n_rows, n, row_ptr, counts);
+}
+
+static void build(const uint32_t* keys, int64_t n, int64_t n_rows, int32_t* row_ptr, int32_t* counts, const Layout& L,
+                  const Tables& T, void* scratch, hipStream_t s) {
+  constexpr int TILE = PLAN_TILE;
+  hipLaunchKernelGGL(hist_hi_kernel<TILE>, dim3((unsigned)L.nt), dim3(TILE / IPT), 0, s, keys, n, (int)L.nb, L.nt, T.offA);
+  build_tail(keys, n, n_rows, row_ptr, counts, L, T, scratch, s);
+}
+
+// the build of an exact mapping: the keys are written (row_idx) and counted by one kernel, then the same tail
+template <typename PIX>
+static void build_from_mapping(const int64_t* images, const void* pixels, double ratio, int64_t n, int H, int W,
+                               int64_t n_rows, int32_t* row_idx, int32_t* row_ptr, int32_t* counts, const Layout& L,
+                               const Tables& T, void* scratch, hipStream_t s) {
+  constexpr int TILE = PLAN_TILE;
+  // FUSED_K tiles per workgroup only where that still leaves two workgroups for each of 256 CUs (the whole build at 8192
+  // tiles = 2^25 views, 2^18 rows: 0.301 ms at 16 tiles per workgroup, 0.309 at 8 and at 4, 0.315 at 1; 0.403 ms with
+  // mapping_row_index_kernel + hist_hi); a smaller mapping keeps one workgroup per tile, which fills the device sooner
+  if (L.nt >= (int64_t)FUSED_K * 512)
+    hipLaunchKernelGGL((mapping_row_index_kernel_hist<PIX, TILE, FUSED_K>), dim3((unsigned)((L.nt + FUSED_K - 1) / FUSED_K)),
+                       dim3(TILE / IPT), 0, s, images, (const PixPair<PIX>*)pixels, ratio, n, H, W, (int)L.nb, L.nt,
+                       row_idx, T.offA);
+  else
+    hipLaunchKernelGGL((mapping_row_index_kernel_hist<PIX, TILE, 1>), dim3((unsigned)L.nt), dim3(TILE / IPT), 0, s, images,
+                       (const PixPair<PIX>*)pixels, ratio, n, H, W, (int)L.nb, L.nt, row_idx, T.offA);
+  build_tail((const uint32_t*)row_idx, n, n_rows, row_ptr, counts, L, T, scratch, s);
 }
 
 static void sort_records(const uint32_t* keys, const uint4* rec, int64_t n, int64_t n_rows, const int32_t* row_ptr,
@@ -684,6 +779,33 @@ int dva_plan_split_build(const int32_t* row_idx, int64_t n_views, int64_t n_rows
   if ((int64_t)L.total > tables_bytes || scratch_bytes < n_views * 2) return DVA_ERR_INVALID;
   const ps::Tables T = ps::tables_of(tables, L);
   ps::build((const uint32_t*)row_idx, n_views, n_rows, row_ptr, counts, L, T, scratch, (hipStream_t)stream);
+  DVA_CHECK_LAUNCH();
+  return DVA_OK;
+}
+
+// dva_mapping_row_index (atom == view) + dva_plan_split_build in one call: the keys and their first histogram come from
+// one kernel.  Same outputs, byte for byte.
+int dva_mapping_row_index_split(const int64_t* images, const void* pixels, int32_t pix_bytes, double ratio,
+                                int64_t n_views, int32_t B, int32_t H, int32_t W, int32_t* row_idx, int32_t* row_ptr,
+                                int32_t* counts, void* tables, int64_t tables_bytes, void* scratch, int64_t scratch_bytes,
+                                void* stream) {
+  if (n_views < 0 || !(ratio >= 1.0) || B < 0 || H < 0 || W < 0) return DVA_ERR_INVALID;
+  if (pix_bytes != 2 && pix_bytes != 4 && pix_bytes != 8) return DVA_ERR_INVALID;
+  if (H > 32767 || W > 32767) return DVA_ERR_UNSUPPORTED;
+  const int64_t n_rows = (int64_t)B * H * W;
+  if (!ps::eligible(n_views, n_rows)) return DVA_ERR_UNSUPPORTED;
+  if (!images || !pixels || !row_idx || !row_ptr || !tables || !scratch) return DVA_ERR_INVALID;
+  if ((uintptr_t)pixels % (2 * (size_t)pix_bytes)) return DVA_ERR_UNSUPPORTED;      // a pixel pair is one load
+  const ps::Layout L = ps::layout(n_views, n_rows);
+  if ((int64_t)L.total > tables_bytes || scratch_bytes < n_views * 2) return DVA_ERR_INVALID;
+  const ps::Tables T = ps::tables_of(tables, L);
+  hipStream_t s = (hipStream_t)stream;
+  if (pix_bytes == 2)
+    ps::build_from_mapping<int16_t>(images, pixels, ratio, n_views, H, W, n_rows, row_idx, row_ptr, counts, L, T, scratch, s);
+  else if (pix_bytes == 4)
+    ps::build_from_mapping<int32_t>(images, pixels, ratio, n_views, H, W, n_rows, row_idx, row_ptr, counts, L, T, scratch, s);
+  else
+    ps::build_from_mapping<int64_t>(images, pixels, ratio, n_views, H, W, n_rows, row_idx, row_ptr, counts, L, T, scratch, s);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }

@@ -846,9 +846,35 @@ def gather_row_index(packed_idx, B, H, W, row_offset=0, with_counts=True, with_p
     return row_idx, counts
 
 
-def mapping_row_index(images, atom_ptr, pixels, ratio, B, H, W, with_counts=True, with_plan=True, split=True):
+def _mapping_row_index_split(images, pixels, ratio, B, H, W, with_counts):
+    """Row index and split plan of an exact mapping from one call (``dva_mapping_row_index_split``: the keys and the
+    plan's first histogram in one kernel), or None where the split plan does not apply."""
+    lib = _lib.load()
+    V, R, dev = images.shape[0], B * H * W, pixels.device
+    es = pixels.element_size()
+    if not (SPLIT_PLAN and _split_plan_pays(V, R)) or pixels.shape[0] != V or pixels.data_ptr() % (2 * es):
+        return None
+    nbytes = int(lib.dva_plan_split_table_bytes(V, R))
+    if nbytes <= 0:
+        return None
+    row_idx = torch.empty(V, dtype=torch.int32, device=dev)
+    row_ptr = torch.empty(R + 1, dtype=torch.int32, device=dev)
+    counts = torch.empty(R, dtype=torch.int32, device=dev) if with_counts else None
+    tables = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    lows = torch.empty(V, dtype=torch.int16, device=dev)
+    # image id + pixel pair read, key written, read once more (scatter<LOWS>), 2-byte digits written + read
+    with _timed("mapping_row_plan", V * (8 + 2 * es + 4 + 4 + 4)):
+        check(lib.dva_mapping_row_index_split(ptr(images), ptr(pixels), es, float(ratio), V, B, H, W, ptr(row_idx),
+                                              ptr(row_ptr), ptr(counts), ptr(tables), nbytes, ptr(lows), V * 2,
+                                              stream_of(pixels)), "dva_mapping_row_index_split")
+    return row_idx, counts, SplitPlan(row_idx, R, row_ptr, tables)
+
+
+def mapping_row_index(images, atom_ptr, pixels, ratio, B, H, W, with_counts=True, with_plan=True, split=True, exact=False):
     """``gather_row_index(pack_gather_index(images, atom_ptr, pixels, ratio), B, H, W)`` in one pass (no packed index):
-    (row_idx, counts, plan) with the counts taken from the row plan."""
+    (row_idx, counts, plan) with the counts taken from the row plan.  ``exact``: the caller knows that every view owns
+    exactly one atom (``atom_ptr`` = 0 .. V); where the plan is a split plan, the index and the plan then come from one
+    call that does not read ``atom_ptr``."""
     lib = _lib.load()
     require_device(images, atom_ptr, pixels)
     images = images.contiguous()
@@ -856,6 +882,10 @@ def mapping_row_index(images, atom_ptr, pixels, ratio, B, H, W, with_counts=True
     pixels = pixels.contiguous()
     if pixels.dtype not in (torch.int16, torch.int32, torch.int64):
         raise TypeError(f"pixels must be int16/int32/int64, got {pixels.dtype}")
+    if exact and split and with_plan:
+        fused = _mapping_row_index_split(images, pixels, ratio, B, H, W, with_counts)
+        if fused is not None:
+            return fused
     V, P = images.shape[0], pixels.shape[0]
     row_idx = torch.empty(P, dtype=torch.int32, device=pixels.device)
     with _timed("gather_row_index", V * 28 + P * 8):
@@ -944,7 +974,7 @@ def lazy_gather_nearest_mapping(x, images, atom_ptr, pixels, ratio, exact):
     B, C, H, W = x.shape
     rows = x.permute(0, 2, 3, 1).reshape(B * H * W, C)   # view when x is channels_last
     row_idx, counts, plan = mapping_row_index(images, atom_ptr, pixels, ratio, B, H, W,
-                                              split=bool(exact) and split_plan_serves(x.dtype, C))
+                                              split=bool(exact) and split_plan_serves(x.dtype, C), exact=bool(exact))
     return GatheredFeatures(rows, row_idx, counts, exact, plan)
 
 

@@ -235,6 +235,15 @@ int dva_row_plan(const int32_t* row_idx, int64_t n_views, int64_t n_rows, int32_
 int64_t dva_plan_split_table_bytes(int64_t n_views, int64_t n_rows);
 int dva_plan_split_build(const int32_t* row_idx, int64_t n_views, int64_t n_rows, int32_t* row_ptr, int32_t* counts,
                          void* tables, int64_t tables_bytes, void* scratch, int64_t scratch_bytes, void* stream);
+/* dva_mapping_row_index + dva_plan_split_build in one call for an EXACT mapping (one atom per view, so no atom_ptr): one
+ * kernel writes the row keys and counts their high digit, the rest of the build is dva_plan_split_build's.  row_idx int32
+ * [n_views], row_ptr, counts (nullable), tables and scratch as there, n_rows = B * H * W; every output is byte for byte
+ * what the two calls leave.  Refuses what either of them refuses, and a pixels pointer that is not aligned to one (x, y)
+ * pair (DVA_ERR_UNSUPPORTED: the pair is one load). */
+int dva_mapping_row_index_split(const int64_t* images, const void* pixels, int32_t pix_bytes, double ratio,
+                                int64_t n_views, int32_t B, int32_t H, int32_t W, int32_t* row_idx, int32_t* row_ptr,
+                                int32_t* counts, void* tables, int64_t tables_bytes, void* scratch, int64_t scratch_bytes,
+                                void* stream);
 int dva_plan_split_sort_records(const int32_t* row_idx, const void* rec, int64_t n_views, int64_t n_rows,
                                 const int32_t* row_ptr, const void* tables, int64_t tables_bytes, void* buf,
                                 void* rec_sorted, void* stream);

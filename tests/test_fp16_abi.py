@@ -36,4 +36,4 @@ def test_new_entries_validate_without_gpu():
     # entries outside the fp16 list refuse it as unsupported, not as a bad argument
     assert lib.dva_sparse_conv_workspace_bytes(27, 16, 16, _lib.DVA_F16) == -2
     assert lib.dva_concat_cast_fwd(None, None, None, 4, 4, 4, _lib.DVA_F16, None) == -2
-    assert lib.dva_deepset_fwd_layer(None, None, None, None, None, None, None, 0, 0, _lib.DVA_F16, None) == -2
+    assert lib.dva_deepset_fwd_layer(None, None, None, None, None, None, None, 0, _lib.DVA_F16, None) == -2

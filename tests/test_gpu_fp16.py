@@ -550,13 +550,13 @@ def test_fp16_refused_by_entries_outside_the_list():
     assert lib.dva_plan_split_rows_grad(P, P, 2048, 600, P, 1 << 16, P, 64, 4, _lib.DVA_BF16, F16, st) == -2
     assert lib.dva_anchor_rows_sum(P, P, P, P, P, 4, 8, 64, F16, st) == -2
     assert lib.dva_anchor_fixup(P, P, P, P, P, 4, 1, 2, 2, 64, F16, st) == -2
-    assert lib.dva_deepset_fwd_first(P, P, P, P, P, P, 8, 8, 1, 0, F16, st) == -2
+    assert lib.dva_deepset_fwd_first(P, P, P, P, P, P, 8, 8, 1, F16, st) == -2
     assert lib.dva_deepset_segmax(P, P, P, P, P, 4, 8, F16, st) == -2
-    assert lib.dva_deepset_fwd_layer(P, P, P, P, P, P, P, 8, 0, F16, st) == -2
-    assert lib.dva_deepset_fwd_score(P, P, P, P, P, 8, 4, P, P, 0, F16, st) == -2
-    assert lib.dva_deepset_bwd_score(P, P, P, P, P, P, P, P, 8, 4, P, P, 0, F16, st) == -2
-    assert lib.dva_deepset_bwd_layer(*([P] * 15), 8, 0, 0, 0, F16, st) == -2
-    assert lib.dva_deepset_bwd_max(*([P] * 8), 8, 0, F16, st) == -2
+    assert lib.dva_deepset_fwd_layer(P, P, P, P, P, P, P, 8, F16, st) == -2
+    assert lib.dva_deepset_fwd_score(P, P, P, P, P, 8, 4, F16, st) == -2
+    assert lib.dva_deepset_bwd_score(P, P, P, P, P, P, P, P, 8, 4, F16, st) == -2
+    assert lib.dva_deepset_bwd_layer(*([P] * 14), 8, 0, 0, F16, st) == -2
+    assert lib.dva_deepset_bwd_max(*([P] * 8), 8, F16, st) == -2
     assert lib.dva_deepset_bwd_first(*([P] * 6), 8, 0, F16, st) == -2
     assert lib.dva_concat_cast_fwd(P, P, P, 4, 4, 4, F16, st) == -2
     assert lib.dva_concat_cast_bwd(P, P, P, 4, 4, 4, F16, st) == -2

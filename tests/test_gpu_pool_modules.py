@@ -289,9 +289,12 @@ def test_fused_deepset_large_vs_generic(stored_activation_passes):
             close(a, b, rtol=1e-4, atol=1e-5)
 
 
-def test_deepset_mfma_equals_valu_generation(stored_activation_passes):
-    """The fp32-MFMA layer kernels (algo 0) against the first-generation VALU kernels (algo 1): both are
-    exact fp32 fma chains, only the summation order differs."""
+def test_deepset_stored_passes_ragged_train_vs_f64(stored_activation_passes):
+    """The fp32-MFMA layer kernels of the stored-activation path on a ragged train-mode case (20001 points, 0-8 views
+    each, use_num, 4 scores per view): output and every parameter gradient against float64 autograd of the oracle
+    module on the device, at the class gates of tolerances.py; a gate rises at most to 4x the error of the oracle's
+    own fp32 evaluation of the same case."""
+    import copy
     from deepviewagg_amd.modules.multimodal import pooling as P
     from deepviewagg_amd import fused_deepset
     gen = torch.Generator().manual_seed(9)
@@ -299,25 +302,41 @@ def test_deepset_mfma_equals_valu_generation(stored_activation_passes):
     sizes = torch.randint(0, 9, (N,), generator=gen)
     csr = torch.cat([torch.zeros(1, dtype=torch.long), sizes.cumsum(0)]).to(DEV)
     V = int(csr[-1])
-    m = P.GroupBimodalCSRPool(in_map=8, in_mod=C, num_groups=4, use_num=True).to(DEV).train()
+    kwargs = dict(in_map=8, in_mod=C, num_groups=4, use_num=True)
+    m = P.GroupBimodalCSRPool(**kwargs).to(DEV).train()
     with torch.no_grad():
         for p in m.parameters():
             p.copy_(torch.randn(p.shape, generator=gen).to(DEV) * 0.4)
+    ref = O.GroupBimodalCSRPool(**kwargs)
+    ref.load_state_dict({k: v.cpu() for k, v in m.state_dict().items()}, strict=True)
+    ref.train()
     x_mod = torch.randn(V, C, generator=gen).to(DEV)
     x_map = torch.rand(V, 8, generator=gen).to(DEV)
     w = torch.randn(N, C, generator=gen).to(DEV)
+    calls = []
+    real = fused_deepset.deepset_linear
+    fused_deepset.deepset_linear = lambda *a: (calls.append(1), real(*a))[1]
+    try:
+        out = m(None, x_mod, x_map, csr)
+    finally:
+        fused_deepset.deepset_linear = real
+    assert calls, "the stored-activation kernels did not run"
+    names = [k for k, _ in m.named_parameters()]
+    grads = torch.autograd.grad((out * w).sum(), list(m.parameters()))
     res = {}
-    for algo in (0, 1):
-        fused_deepset.ALGO = algo
-        try:
-            out = m(None, x_mod, x_map, csr)
-            res[algo] = (out, torch.autograd.grad((out * w).sum(), list(m.parameters())))
-        finally:
-            fused_deepset.ALGO = 0
-    close(res[0][0], res[1][0], rtol=1e-4, atol=1e-5)
-    for (n, _), a, b in zip(m.named_parameters(), res[0][1], res[1][1]):
-        scale = float(b.abs().max()) + 1e-6
-        assert float((a - b).abs().max()) / scale < 2e-3, (n, float((a - b).abs().max()), scale)
+    for dt in (torch.float64, torch.float32):
+        r = copy.deepcopy(ref).to(DEV).to(dt)
+        o = r(None, x_mod.to(dt), x_map.to(dt), csr)
+        res[dt] = (o.detach(), torch.autograd.grad((o * w.to(dt)).sum(), list(r.parameters())))
+    (o64, g64), (o32, g32) = res[torch.float64], res[torch.float32]
+    case = f"ragged N={N} V={V} train"
+    rep = T.Report("stored-activation DeepSet kernels vs float64")
+    rep.add(case, "out", "out", T.rel_err(out, o64), T.rel_err(o32, o64))
+    gp64 = dict(zip(names, g64))
+    for k, a, b, b32 in zip(names, grads, g64, g32):
+        scale = T.param_scale(k, gp64)
+        rep.add(case, k, "grad_param", T.rel_err(a, b, scale), T.rel_err(b32, b, scale))
+    rep.check()
 
 
 def test_deepset_bf16_activation_storage(stored_activation_passes):
@@ -377,44 +396,6 @@ def test_deepset_bf16_activation_storage(stored_activation_passes):
     with torch.autocast("cuda", dtype=torch.bfloat16):
         assert fused_deepset._act_dtype() == torch.bfloat16
     print("bf16-storage error vs reference-autocast error per parameter:", report)
-
-
-
-def test_deepset_recompute_equals_stored_activations(stored_activation_passes):
-    """bf16 storage with RECOMPUTE (a4 never stored, layer outputs rebuilt from the layer inputs in the
-    backward passes) against the stored-activation variant: same maths, the recomputed values are the fp32
-    ones instead of their bf16 roundings -> relative L2 differences at the 2^-9 level."""
-    from deepviewagg_amd.modules.multimodal import pooling as P
-    from deepviewagg_amd import fused_deepset
-    gen = torch.Generator().manual_seed(21)
-    N, C = 20011, 32
-    sizes = torch.randint(0, 9, (N,), generator=gen)
-    sizes[:40] = 70
-    csr = torch.cat([torch.zeros(1, dtype=torch.long), sizes.cumsum(0)]).to(DEV)
-    V = int(csr[-1])
-    m = P.GroupBimodalCSRPool(in_map=8, in_mod=C, num_groups=4, use_num=True).to(DEV)
-    with torch.no_grad():
-        for p in m.parameters():
-            p.copy_(torch.randn(p.shape, generator=gen).to(DEV) * 0.4)
-    x_mod = torch.randn(V, C, generator=gen).to(DEV)
-    x_map = torch.rand(V, 8, generator=gen).to(DEV)
-    w = torch.randn(N, C, generator=gen).to(DEV)
-    for train in (True, False):
-        m.train(train)
-        res = {}
-        for rc in (False, True):
-            fused_deepset.ACT_DTYPE, fused_deepset.RECOMPUTE = torch.bfloat16, rc
-            try:
-                out = m(None, x_mod, x_map, csr)
-                res[rc] = (out, torch.autograd.grad((out * w).sum(), list(m.parameters())))
-            finally:
-                fused_deepset.ACT_DTYPE, fused_deepset.RECOMPUTE = None, False
-        assert not torch.equal(res[True][0], res[False][0])
-        rel = float((res[True][0].detach() - res[False][0].detach()).norm() / res[False][0].detach().norm())
-        assert rel < 1e-2, rel
-        for (n, _), a, b in zip(m.named_parameters(), res[True][1], res[False][1]):
-            rel = float((a - b).norm() / (b.norm() + 1e-6))
-            assert rel < 1.5e-1, (n, rel)      # two bf16 schemes: each is ~10 % from fp32 on the deepest gradients
 
 
 def test_view_level_pool_with_equal_counts_is_not_the_identity():

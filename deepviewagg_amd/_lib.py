@@ -68,6 +68,21 @@ class DvaCamera(ctypes.Structure):
 _vp, _i64, _i32, _f32, _f64 = (ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_float,
                                ctypes.c_double)
 
+
+class DvaCollateItem(ctypes.Structure):
+    """Mirror of ``struct dva_collate_item`` (include/dva.h): one mapping of a ``dva_mapping_collate`` call."""
+    _fields_ = [
+        ("pointers", _vp),
+        ("images", _vp),
+        ("atom_ptr", _vp),
+        ("pixels", _vp),
+        ("features", _vp),
+        ("n_points", _i64),
+        ("n_views", _i64),
+        ("n_atoms", _i64),
+        ("point_base", _i64),
+    ]
+
 # name -> (restype, argtypes); every symbol include/dva.h declares must be listed here
 SIGNATURES = {
     "dva_version": (ctypes.c_int, []),
@@ -253,6 +268,10 @@ SIGNATURES = {
                                                _vp, _vp, _i64, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp,
                                                _vp, _vp, _vp, _i64, _vp]),
     "dva_mapping_image_stats": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _vp]),
+    "dva_mapping_collate_group_items": (ctypes.c_int, []),
+    "dva_mapping_collate_workspace_bytes": (ctypes.c_int64, [_i64]),
+    "dva_mapping_collate": (ctypes.c_int, [ctypes.POINTER(DvaCollateItem), _i64, _i32, _i32, _i64, _i64, _i64, _vp,
+                                           _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "dva_lex_workspace_bytes": (ctypes.c_int64, [_i64]),
     "dva_argsort_i64": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "dva_argunique_i64": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp]),

@@ -179,8 +179,33 @@ class CSRBatch(CSRData):
         return out
 
     @staticmethod
-    def from_csr_list(csr_list):
+    def from_csr_list(csr_list, group_bases=None, num_groups=None):
+        """Stack the items (reference csr.py:352-420).  With ``group_bases`` (one int per item, ascending, no overlap)
+        item ``i`` becomes the groups ``group_bases[i] ...`` of a batch of ``num_groups`` groups and the groups no item
+        covers are empty: ``from_csr_list`` followed by ``insert_empty_groups``.  Item classes that provide
+        ``_collate_device`` (``ImageMapping``) are stacked by it, in one device operation without a host
+        synchronisation, where it applies; everything else goes through ``_from_csr_list_composition``."""
         assert isinstance(csr_list, list) and len(csr_list) > 0
+        assert isinstance(csr_list[0], CSRData), "All provided items must be CSRData objects."
+        if group_bases is not None:
+            group_bases = [int(b) for b in group_bases]
+            assert len(group_bases) == len(csr_list), "One group base per item is required."
+            if sum(c.num_groups for c in csr_list) == 0:
+                group_bases = num_groups = None           # nothing to place: insert_empty_groups is never reached
+        device_route = getattr(type(csr_list[0]), '_collate_device', None)
+        if device_route is not None:
+            batch = device_route(csr_list, group_bases, num_groups)
+            if batch is not None:
+                return batch
+        batch = CSRBatch._from_csr_list_composition(csr_list)
+        if group_bases is not None:
+            group_idx = torch.cat([torch.arange(b, b + c.num_groups) for b, c in zip(group_bases, csr_list)])
+            batch.insert_empty_groups(group_idx, num_groups=num_groups)
+        return batch
+
+    @staticmethod
+    def _check_csr_list(csr_list):
+        """The reference's checks on the items of a batch; reads no tensor on the device."""
         assert isinstance(csr_list[0], CSRData), "All provided items must be CSRData objects."
         csr_type = type(csr_list[0])
         assert all(isinstance(c, csr_type) for c in csr_list), "All provided items must have the same class."
@@ -196,6 +221,13 @@ class CSRBatch(CSRData):
         for i in range(num_values):
             assert all(type(c.values[i]) == type(csr_list[0].values[i]) for c in csr_list), \
                 "All provided items must have the same value types."
+        return csr_type, device, num_values, is_index_value
+
+    @staticmethod
+    def _from_csr_list_composition(csr_list):
+        """The reference's composition in torch: it reads the device back per item and per level (``num_items``, the
+        image maxima).  Serves CPU items and plain ``CSRData``, and is the yardstick of the device route."""
+        csr_type, device, num_values, is_index_value = CSRBatch._check_csr_list(csr_list)
         # pointers: drop each item's leading 0, offset by the items already stacked
         offsets = torch.cumsum(torch.tensor([0] + [c.num_items for c in csr_list[:-1]], dtype=torch.long), 0)
         pointers = torch.cat([torch.zeros(1, dtype=torch.long, device=device)] + [

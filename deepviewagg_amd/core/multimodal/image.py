@@ -457,6 +457,54 @@ class ImageMapping(CSRData):
             values.append(features)
         return ImageMapping(pointers, *values, dense=False, is_index_value=[True, False, False][:len(values)])
 
+    # test / measurement hook: False sends device mappings through the torch composition of from_csr_list as well
+    COLLATE_ON_DEVICE = True
+
+    @staticmethod
+    def _collate_device(csr_list, group_bases=None, num_groups=None):
+        """``CSRBatch.from_csr_list`` (+ ``insert_empty_groups``) of mappings on one HIP device as one
+        ``ops.collate_mapping``: the batch the composition builds, classes and bookkeeping included, without a host
+        synchronisation.  None where the op does not apply (the caller then runs the composition): CPU items, a layout
+        other than images / atoms / features with the standard ``is_index_value``, dtypes the kernel does not take,
+        ``COLLATE_ON_DEVICE`` off."""
+        from ..._lib import DvaError
+        first = csr_list[0]
+        if not ImageMapping.COLLATE_ON_DEVICE or not isinstance(first, ImageMapping) or not first.pointers.is_cuda:
+            return None
+        csr_type, _, num_values, is_index_value = CSRBatch._check_csr_list(csr_list)
+        if num_values not in (2, 3) or is_index_value.tolist() != [True, False, False][:num_values]:
+            return None
+        nested = [c.values[1] for c in csr_list]
+        nested_type = type(nested[0])
+        CSRBatch._check_csr_list(nested)
+        if nested[0].num_values != 1 or bool(nested[0].is_index_value[0]):
+            return None
+        if not all(torch.is_tensor(c.values[0]) and torch.is_tensor(a.values[0]) for c, a in zip(csr_list, nested)):
+            return None
+        if num_values == 3 and not all(torch.is_tensor(c.values[2]) for c in csr_list):
+            return None
+        if group_bases is not None:
+            assert all(b1 >= b0 + c.num_groups for b0, b1, c in zip(group_bases, group_bases[1:], csr_list)), \
+                "New group indices must be sorted."
+            top = group_bases[-1] + csr_list[-1].num_groups
+            num_groups = top if num_groups is None else max(top, int(num_groups))
+        try:
+            pointers, images, atom_ptr, pixels, features, _ = ops.collate_mapping(
+                [(c.pointers, c.values[0], a.pointers, a.values[0], c.values[2] if num_values == 3 else None)
+                 for c, a in zip(csr_list, nested)], point_bases=group_bases, num_points=num_groups)
+        except DvaError as err:
+            if err.code != -2:      # DVA_ERR_UNSUPPORTED: dtypes / sizes outside the kernel's range
+                raise
+            return None
+        atoms = nested_type.get_batch_type()(atom_ptr, pixels, dense=False, is_index_value=nested[0].is_index_value)
+        atoms.__sizes__ = torch.tensor([a.num_groups for a in nested], dtype=torch.long)
+        atoms.__csr_type__ = nested_type
+        values = [images, atoms] + ([features] if num_values == 3 else [])
+        batch = csr_type.get_batch_type()(pointers, *values, dense=False, is_index_value=is_index_value)
+        batch.__sizes__ = torch.tensor([c.num_groups for c in csr_list], dtype=torch.long)
+        batch.__csr_type__ = csr_type
+        return batch
+
     def _merge_points_composition(self, idx):
         """The reference's composition (image.py:2211-2273) in torch: expansion to atom rows, a four-key
         ``lexargunique`` and ``from_dense``.  Serves CPU mappings and is the yardstick of the device op."""
@@ -1064,7 +1112,10 @@ class SameSettingImageBatch(SameSettingImageData):
         return len(self.__sizes__) if self.__sizes__ is not None else None
 
     @staticmethod
-    def from_data_list(image_data_list):
+    def from_data_list(image_data_list, point_bases=None, num_points=None):
+        """``point_bases`` / ``num_points`` (``ImageBatch.from_data_list``): item ``i``'s points become the points
+        ``point_bases[i] ...`` of a batch of ``num_points`` points, the others have no view -- the mappings are
+        stacked and their empty groups inserted in one pass (``CSRBatch.from_csr_list``)."""
         assert isinstance(image_data_list, list) and len(image_data_list) > 0
         assert all(isinstance(x, SameSettingImageData) for x in image_data_list)
         first = image_data_list[0]
@@ -1079,7 +1130,8 @@ class SameSettingImageBatch(SameSettingImageData):
         xs = [im.x for im in image_data_list]
         batch_dict['x'] = None if any(v is None for v in xs) else torch.cat(xs)
         maps = [im.mappings for im in image_data_list]
-        batch_dict['mappings'] = None if any(m is None for m in maps) else ImageMappingBatch.from_csr_list(maps)
+        batch_dict['mappings'] = None if any(m is None for m in maps) else ImageMappingBatch.from_csr_list(
+            maps, group_bases=point_bases, num_groups=num_points)
         batch = SameSettingImageBatch(**batch_dict)
         batch.__sizes__ = np.array([im.num_views for im in image_data_list])
         return batch
@@ -1230,12 +1282,11 @@ class ImageBatch(ImageData):
                 il_idx_dict[h].append(il_idx)
                 im_idx_dict[h].append(im_idx)
                 groups[h].append(im)
-        batches = [SameSettingImageBatch.from_data_list(groups[h]) for h in hashes]
-        for h, im in zip(hashes, batches):
-            if im.num_points > 0:
-                global_idx = torch.cat([torch.arange(int(cum_pts[i]), int(cum_pts[i + 1]))
-                                        for i in il_idx_dict[h]])
-                im.mappings.insert_empty_groups(global_idx, num_groups=int(cum_pts[-1]))
+        # the points of a setting's items sit at the global indices of the samples that own the setting; the mappings
+        # are stacked and the empty groups of the other samples inserted in the same pass
+        cum = cum_pts.tolist()
+        batches = [SameSettingImageBatch.from_data_list(groups[h], point_bases=[cum[i] for i in il_idx_dict[h]],
+                                                        num_points=cum[-1]) for h in hashes]
         out = ImageBatch(batches)
         out.__il_sizes__ = [len(il) for il in image_data_list]
         out.__hashes__ = hashes

@@ -10,7 +10,7 @@ cylinder samplers (SphereSampling, CylinderSampling, GridSphereSampling, GridCyl
 ``torch_points3d.core.data_transform.transforms``, and both groups on the package
 ``torch_points3d.core.data_transform`` itself (``instantiate_transform`` and ``cT.GridSampling3D`` look them up there),
 and imports the data classes from
-``torch_points3d.core.multimodal.{csr,image}``, and takes ``lovasz_softmax`` and ``ConfusionMatrix`` from
+``torch_points3d.core.multimodal.{csr,image,data}`` (``MMData`` / ``MMBatch`` in the last), and takes ``lovasz_softmax`` and ``ConfusionMatrix`` from
 ``torch_points3d.metrics.{lovasz_loss,confusion_matrix}`` and ``SegmentationVoter`` from
 ``torch_points3d.metrics.segmentation_helpers``; where the reference's ``SegmentationTracker`` can be imported,
 its ``_compute_metrics`` becomes ``deepviewagg_amd.metrics.segmentation_tracker.compute_metrics``.  The image transforms
@@ -37,6 +37,7 @@ _ALIASES = {
     "torch_points3d.core.data_transform.transforms": "deepviewagg_amd.core.data_transform.transforms",
     "torch_points3d.core.multimodal.csr": "deepviewagg_amd.core.multimodal.csr",
     "torch_points3d.core.multimodal.image": "deepviewagg_amd.core.multimodal.image",
+    "torch_points3d.core.multimodal.data": "deepviewagg_amd.core.multimodal.data",
     "torch_points3d.core.multimodal.visibility": "deepviewagg_amd.core.multimodal.visibility",
     "torch_points3d.utils.multimodal": "deepviewagg_amd.utils.multimodal",
     "torch_points3d.modules.SparseConv3d.modules": "deepviewagg_amd.modules.SparseConv3d.modules",

@@ -25,9 +25,8 @@ from torch.utils.checkpoint import checkpoint
 
 from ... import ops
 from ...core.common_modules.base_modules import Identity
+from ...core.multimodal.data import MODALITY_NAMES
 from .dropout import ModalityDropout
-
-MODALITY_NAMES = ['image']      # core/multimodal/data.py:10
 
 
 class SparseVoxels:

@@ -1941,6 +1941,111 @@ def mapping_image_stats(images, atom_ptr, pixels, num_images):
 
 
 # ---------------------------------------------------------------------------------------------
+# mapping collation: CSRBatch.from_csr_list on ImageMappings + insert_empty_groups (core/multimodal/csr.py:352-420)
+# ---------------------------------------------------------------------------------------------
+
+def _collate_unsupported(what):
+    return _lib.DvaError(f"ops.collate_mapping: {what}: {_lib._ERRORS[-2]}", code=-2)
+
+
+def collate_mapping(items, point_bases=None, num_points=None):
+    """Stack mappings into one batch mapping in one device operation: ``(pointers, images, atom_ptr, pixels, features,
+    image_offsets)``.  ``items`` is a list of ``(pointers, images, atom_ptr, pixels, features_or_None)`` device tensors
+    (int64, int64, int64, int16 ``[P, 2]``, fp32 ``[V]`` or ``[V, ...]``; made contiguous where they are not).  Item
+    ``b`` lands at the points ``point_bases[b] ...`` of the result (ascending, no overlap; back to back without
+    ``point_bases``), which has ``num_points`` points (at least the end of the last item); the points no item covers
+    are empty groups, as ``insert_empty_groups`` makes them.  Views, atom pointers and pixels follow in item order;
+    the image ids of item ``b`` are raised by ``image_offsets[b]``, the sum over the items before it of
+    ``max(images) + 1`` (0 for an item without views), int64 on the device.  Pixels and features are copied as bits;
+    the features take the items' trailing shape back.  Items without points (``pointers == [0]``) or views are
+    legal.  No host synchronisation: every size comes from a tensor shape.  Raises ``DvaError`` with ``code == -2``
+    for what the kernel does not take: dtypes other than int64 / int16 / fp32, features on some items only, items
+    whose features differ in their trailing shape, 2^31 - 1 or more points, views or atoms."""
+    lib = _lib.load()
+    if not isinstance(items, (list, tuple)) or len(items) == 0:
+        raise ValueError("ops.collate_mapping: a non-empty list of items")
+    dev = require_device(*[t for item in items for t in item])
+    with_features = [item[4] is not None for item in items]
+    if any(with_features) and not all(with_features):
+        raise _collate_unsupported("features on some items only")
+    trailing = None
+    rows, keep = [], []
+    for b, (pointers, images, atom_ptr, pixels, features) in enumerate(items):
+        for name, t in (("pointers", pointers), ("images", images), ("atom_ptr", atom_ptr)):
+            if t.dim() != 1:
+                raise ValueError(f"ops.collate_mapping: {name} of item {b} must be 1-D, got {tuple(t.shape)}")
+            if t.dtype != torch.int64:
+                raise _collate_unsupported(f"{name} of item {b} is {t.dtype}, not int64")
+        if pixels.dim() != 2 or pixels.shape[1] != 2:
+            raise ValueError(f"ops.collate_mapping: pixels of item {b} must be [P, 2], got {tuple(pixels.shape)}")
+        if pixels.dtype != torch.int16:
+            raise _collate_unsupported(f"pixels of item {b} are {pixels.dtype}, not int16")
+        n, v, p = pointers.shape[0] - 1, images.shape[0], pixels.shape[0]
+        if n < 0 or atom_ptr.shape[0] != v + 1:
+            raise ValueError(f"ops.collate_mapping: item {b} has {n} points, {v} views and {atom_ptr.shape[0]} atom "
+                             f"pointers")
+        if features is not None:
+            if features.dim() < 1 or features.shape[0] != v:
+                raise ValueError(f"ops.collate_mapping: features of item {b} must be [{v}, ...], got "
+                                 f"{tuple(features.shape)}")
+            if features.dtype != torch.float32:
+                raise _collate_unsupported(f"features of item {b} are {features.dtype}, not float32")
+            if trailing is None:
+                trailing = tuple(features.shape[1:])
+            elif tuple(features.shape[1:]) != trailing:
+                raise _collate_unsupported(f"features of item {b} are [V, {tuple(features.shape[1:])}], those of item 0 "
+                                           f"[V, {trailing}]")
+        rows.append((n, v, p))
+    f = 0 if trailing is None else int(np.prod(trailing, dtype=np.int64))
+    if point_bases is None:
+        bases = [0] * len(rows)
+        for b in range(1, len(rows)):
+            bases[b] = bases[b - 1] + rows[b - 1][0]
+    else:
+        bases = [int(x) for x in point_bases]
+        if len(bases) != len(rows):
+            raise ValueError(f"ops.collate_mapping: {len(bases)} point bases for {len(rows)} items")
+    end = bases[-1] + rows[-1][0]
+    n_out = end if num_points is None else int(num_points)
+    v_out, p_out = sum(r[1] for r in rows), sum(r[2] for r in rows)
+    if max(n_out, v_out, p_out) >= 2 ** 31 - 1:
+        raise _collate_unsupported(f"{n_out} points, {v_out} views, {p_out} atoms")
+    descriptors = (_lib.DvaCollateItem * len(rows))()
+    for b, ((pointers, images, atom_ptr, pixels, features), (n, v, p)) in enumerate(zip(items, rows)):
+        # (no aten call for what is contiguous already: a batch is launch-bound, and so is the host in front of it)
+        pointers, images, atom_ptr, pixels = (t if t.is_contiguous() else t.contiguous()
+                                              for t in (pointers, images, atom_ptr, pixels))
+        if pixels.data_ptr() % 4:
+            pixels = pixels.clone()                       # an int16 view that starts on an odd element
+        feat = None
+        if f > 0 and features is not None:
+            feat = features if features.dim() == 2 else features.reshape(v, f)
+            feat = feat if feat.is_contiguous() else feat.contiguous()
+        held = (pointers, images, atom_ptr, pixels, feat)
+        keep.append(held)
+        d = descriptors[b]
+        d.pointers, d.images, d.atom_ptr, d.pixels = (h.data_ptr() if h.numel() else None for h in held[:4])
+        d.features = feat.data_ptr() if feat is not None and feat.numel() else None
+        d.n_points, d.n_views, d.n_atoms, d.point_base = n, v, p, bases[b]
+    ws, nbytes = _lib.workspace("dva_mapping_collate_workspace_bytes", dev, len(rows))
+    out_ptr = torch.empty(n_out + 1, dtype=torch.int64, device=dev)
+    out_img = torch.empty(v_out, dtype=torch.int64, device=dev)
+    out_aptr = torch.empty(v_out + 1, dtype=torch.int64, device=dev)
+    out_pix = torch.empty((p_out, 2), dtype=torch.int16, device=dev)
+    out_feat = None if trailing is None else torch.empty((v_out, f), dtype=torch.float32, device=dev)
+    offsets = torch.empty(len(rows), dtype=torch.int64, device=dev)
+    moved = (n_out + 1) * 8 + sum(r[0] for r in rows) * 8 + v_out * (40 + 8 * f) + p_out * 8
+    with _timed("mapping_collate", moved):
+        check(lib.dva_mapping_collate(descriptors, len(rows), 2, f, n_out, v_out, p_out, ptr(out_ptr), ptr(out_img),
+                                      ptr(out_aptr), ptr(out_pix), ptr(out_feat if f > 0 else None), ptr(offsets),
+                                      ptr(ws), int(nbytes), stream_of(out_ptr)), "dva_mapping_collate")
+    del keep                                              # the launches are queued: the stream orders the frees
+    if out_feat is not None:
+        out_feat = out_feat.view((v_out,) + trailing)
+    return out_ptr, out_img, out_aptr, out_pix, out_feat, offsets
+
+
+# ---------------------------------------------------------------------------------------------
 # sparse 3D convolution on voxel tensors (modules/SparseConv3d over torchsparse 1.1.0 Conv3d)
 # ---------------------------------------------------------------------------------------------
 

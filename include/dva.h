@@ -1356,6 +1356,53 @@ int dva_mapping_select_fill(const int64_t* pointers, const int64_t* images, cons
 int dva_mapping_image_stats(const int64_t* images, const int64_t* atom_ptr, const void* pixels, int32_t pixel_bytes,
                             int64_t n_views, int64_t n_atoms, int64_t n_images, int64_t* stats, void* stream);
 
+/* ------------------------------------------------------------------------------------------ *
+ * Mapping collation.  Replaces the torch composition of CSRBatch.from_csr_list on ImageMappings
+ * followed by insert_empty_groups (core/multimodal/csr.py:352-420, :197-229): n_items mappings
+ * stacked into one, without a host synchronisation.  items is a HOST array, read before the entry
+ * returns and not kept: item b has pointers int64 [n_points + 1], images int64 [n_views], atom_ptr
+ * int64 [n_views + 1], pixels int16 [n_atoms, 2] (pixel_bytes = 2; anything else returns
+ * DVA_ERR_UNSUPPORTED), features fp32 [n_views, F] (null for every item when F = 0), all device
+ * arrays, and its destination point_base: ascending, point_base[b] >= point_base[b-1] +
+ * n_points[b-1], and n_points_out >= the end of the last item.  n_views_out and n_atoms_out are the
+ * sums over the items.  With view_base[b] / atom_base[b] the views / atoms of the items before b:
+ *   out_pointers int64 [n_points_out + 1]: entry 0 is 0, entry point_base[b] + i (1 <= i <=
+ *     n_points[b]) is pointers_b[i] + view_base[b], and every entry no item covers (in front of the
+ *     first item, between two items, behind the last) holds the views stacked so far;
+ *   out_images int64 [n_views_out]: images_b[j] + off[b] at view_base[b] + j, off[b] the sum over
+ *     c < b of max(images_c) + 1 (int64 arithmetic; 0 for an item without views), reduced and
+ *     scanned on the device; out_image_offsets (device int64 [n_items], nullable) receives off;
+ *   out_atom_ptr int64 [n_views_out + 1]: entry 0 is 0, entry view_base[b] + j (1 <= j <= n_views[b])
+ *     is atom_ptr_b[j] + atom_base[b];
+ *   out_pixels int16 [n_atoms_out, 2] and out_features fp32 [n_views_out, F]: copied as bits.
+ * Every output element is written exactly once, without atomics; only the sizes bound the accesses,
+ * never a value read from pointers or atom_ptr.  The item descriptors reach the kernels by value,
+ * dva_mapping_collate_group_items() = 32 per launch: up to 32 items are three launches (maxima,
+ * scan, fill), every further 32 add a maxima and a fill launch.  No allocation and no copy inside
+ * the entry, and no host memory kept after it returns.  Bad arguments (null items or outputs, n_items < 1,
+ * negative sizes, bases that descend or overlap, sums that differ from the totals) return
+ * DVA_ERR_INVALID before any HIP call; totals of 2^31 - 1 or more return DVA_ERR_UNSUPPORTED.
+ * workspace: dva_mapping_collate_workspace_bytes(n_items) bytes, 16-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+struct dva_collate_item {
+  const int64_t* pointers;
+  const int64_t* images;
+  const int64_t* atom_ptr;
+  const void* pixels;
+  const float* features;
+  int64_t n_points;
+  int64_t n_views;
+  int64_t n_atoms;
+  int64_t point_base;
+};
+int dva_mapping_collate_group_items(void);
+int64_t dva_mapping_collate_workspace_bytes(int64_t n_items);
+int dva_mapping_collate(const struct dva_collate_item* items /* HOST array */, int64_t n_items, int32_t pixel_bytes,
+                        int32_t F, int64_t n_points_out, int64_t n_views_out, int64_t n_atoms_out,
+                        int64_t* out_pointers, int64_t* out_images, int64_t* out_atom_ptr, void* out_pixels,
+                        float* out_features, int64_t* out_image_offsets /* device [n_items], nullable */,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

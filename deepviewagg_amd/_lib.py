@@ -244,6 +244,8 @@ SIGNATURES = {
     "dva_image_window_workspace_bytes": (ctypes.c_int64, [_i64]),
     "dva_image_window_u8": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32,
                                            _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "dva_cloud_augment_workspace_bytes": (ctypes.c_int64, [_i64, _i32]),
+    "dva_cloud_augment_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "dva_lovasz_tile": (ctypes.c_int, []),
     "dva_seg_nll_workspace_bytes": (ctypes.c_int64, []),
     "dva_seg_logsoftmax_nll_fwd": (ctypes.c_int, [_vp, _i32, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),

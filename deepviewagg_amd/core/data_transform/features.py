@@ -109,3 +109,15 @@ class EigenFeatures:
 
     def __repr__(self):
         return _repr(self)
+
+
+# The classes of the reference's module that augment.py provides: kept out of the eagerly listed names above and served
+# by name, as grid_transform.py serves ElasticDistortion.
+_LAZY = ("Random3AxisRotation", "XYZFeature", "AddFeatsByKeys", "AddFeatByKey")
+
+
+def __getattr__(name):
+    if name in _LAZY:
+        from . import augment as _augment
+        return getattr(_augment, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

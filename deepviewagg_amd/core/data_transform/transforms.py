@@ -286,3 +286,15 @@ class Select:
         def index(device):
             return indices.to(device) if _torch.is_tensor(indices) else indices
         return _select(data, num_points, index)
+
+
+# The augmentations of the reference's module that augment.py provides: kept out of the eagerly listed names above and
+# served by name, as grid_transform.py serves ElasticDistortion.
+_LAZY = ("RandomNoise", "RandomScaleAnisotropic", "RandomSymmetry", "ShiftVoxels")
+
+
+def __getattr__(name):
+    if name in _LAZY:
+        from . import augment as _augment
+        return getattr(_augment, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -7,7 +7,8 @@ models/base_architectures/unet.py:69-101), ``torch_points3d.core.multimodal.visi
 (PCAComputePointwise, EigenFeatures) in ``torch_points3d.core.data_transform.features``, GridSampling3D,
 SaveOriginalPosId and ElasticDistortion in ``torch_points3d.core.data_transform.grid_transform``, the sphere and
 cylinder samplers (SphereSampling, CylinderSampling, GridSphereSampling, GridCylinderSampling, Select) in
-``torch_points3d.core.data_transform.transforms``, and both groups on the package
+``torch_points3d.core.data_transform.transforms``, the 3D augmentations of ``core/data_transform/augment.py`` in the
+reference's ``transforms`` and ``features`` modules (``RandomRotate`` and ``Center`` on the package alone), and all groups on the package
 ``torch_points3d.core.data_transform`` itself (``instantiate_transform`` and ``cT.GridSampling3D`` look them up there),
 and imports the data classes from
 ``torch_points3d.core.multimodal.{csr,image,data}`` (``MMData`` / ``MMBatch`` in the last), and takes ``lovasz_softmax`` and ``ConfusionMatrix`` from
@@ -56,6 +57,18 @@ _PACKAGE_NAMES = [
      ("ElasticDistortion",)),
     ("torch_points3d.core.data_transform", "deepviewagg_amd.core.data_transform.transforms",
      ("SphereSampling", "CylinderSampling", "GridSphereSampling", "GridCylinderSampling", "Select")),
+    # the 3D augmentations of augment.py, which our transforms / features modules serve through their __getattr__: by
+    # name on a patched reference module and on the package
+    ("torch_points3d.core.data_transform.transforms", "deepviewagg_amd.core.data_transform.transforms",
+     ("RandomNoise", "RandomScaleAnisotropic", "RandomSymmetry", "ShiftVoxels")),
+    ("torch_points3d.core.data_transform", "deepviewagg_amd.core.data_transform.transforms",
+     ("RandomNoise", "RandomScaleAnisotropic", "RandomSymmetry", "ShiftVoxels")),
+    ("torch_points3d.core.data_transform.features", "deepviewagg_amd.core.data_transform.features",
+     ("Random3AxisRotation", "XYZFeature", "AddFeatsByKeys", "AddFeatByKey")),
+    ("torch_points3d.core.data_transform", "deepviewagg_amd.core.data_transform.features",
+     ("Random3AxisRotation", "XYZFeature", "AddFeatsByKeys", "AddFeatByKey")),
+    # torch_geometric's, which the reference re-exports on the package alone
+    ("torch_points3d.core.data_transform", "deepviewagg_amd.core.data_transform.augment", ("RandomRotate", "Center")),
 ]
 
 

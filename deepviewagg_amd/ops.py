@@ -20,6 +20,7 @@ ops; names and argument meaning follow the reference call site
 ``elastic_distortion``     grid_transform.py:218-243 (one level of ElasticDistortion)
 ``image_tail``             core/data_transform/multimodal/image.py:1195-1282 (ColorJitter, flip, ToFloatImage, Normalize)
 ``image_window``           the same tail over deferred windows: core/multimodal/image.py:578-722 (rolls, crops) folded in
+``cloud_augment``          core/data_transform/transforms.py:463-563, features.py:30-81 (noise, rotation, scale, symmetry, centre)
 ``log_softmax_nll``        models/segmentation/sparseconv3d.py:45-51 (``F.log_softmax`` + ``F.nll_loss``)
 ``lovasz_softmax_flat``    metrics/lovasz_loss.py:174-215 (``flatten_probas`` + ``lovasz_softmax_flat``)
 ``confusion_counts``       metrics/segmentation_tracker.py:72-83 (mask + ``np.argmax`` + ``np.bincount``)
@@ -2866,6 +2867,118 @@ def image_window(src, index, rollings=None, offsets=None, size=None, jitter=(), 
                                       factors, len(names), int(bool(flip)), int(bool(to_float)), mean_c, std_c, ptr(out),
                                       ptr(ws), ws_bytes, stream_of(src)), "dva_image_window_u8")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# the positional 3D augmentations (core/data_transform/transforms.py:463-563, features.py:30-81: RandomNoise,
+# Random3AxisRotation, RandomScaleAnisotropic, RandomSymmetry; torch_geometric's RandomRotate and Center;
+# csrc/cloud_augment.hip)
+# ---------------------------------------------------------------------------------------------
+
+CLOUD_STEP_CODE = {"noise": 0, "linear": 1, "scale": 2, "flip": 3, "center": 4}      # DVA_CLOUD_*
+CLOUD_MAX_STEPS = 16                                                                  # DVA_CLOUD_MAX_STEPS
+CLOUD_STEP_PARAMS = 10                                                                # DVA_CLOUD_STEP_PARAMS
+
+
+def _cloud_floats(value, count, what):
+    """``count`` float32 values of a host tensor, array or nested sequence, as Python floats (exact)."""
+    flat = torch.as_tensor(value).detach().cpu().to(torch.float32).reshape(-1).tolist()
+    if len(flat) != count:
+        raise ValueError(f"ops.cloud_augment: {what} takes {count} numbers, got {len(flat)}")
+    return flat
+
+
+def cloud_augment(pos, steps, norm=None, noise=None):
+    """An ordered list of positional augmentation steps in one pass over ``pos`` float32 [N, 3] and, when given, ``norm``
+    float32 [N, 3]; returns ``(pos_out, norm_out, consts)``, new tensors (``norm_out`` is ``norm`` itself when no step
+    touches it, None without ``norm``).  The random draws are the caller's; ``steps`` holds the drawn values, at most
+    16 of:
+
+    ``("noise",)``                 ``p_c = p_c + e_c``, ``e`` the point's row of ``noise`` float32 [N, 3] on the device
+    ``("linear", M, with_norm)``   ``q_i = ((p_0 M_i0 + p_1 M_i1) + p_2 M_i2)``, ``M`` 3 x 3 host values; the same for
+                                   ``norm`` when ``with_norm``.  This is ``pos @ M.T``.
+    ``("scale", s)``               ``p_c = p_c * s_c``, ``s`` 3 host values; with ``norm``: ``n_c = n_c / s_c``,
+                                   ``l = sqrt((n_0 n_0 + n_1 n_1) + n_2 n_2)``, ``n_c = n_c / max(l, 1e-12)``
+    ``("flip", mask)``             on every axis flagged in ``mask`` (3 bools, at least one set): ``p_c = m_c - p_c``,
+                                   ``m_c`` the exact maximum of ``p_c`` over the points at this stage
+    ``("center",)``                ``p_c = p_c - mu_c``, ``mu_c = f32(S_c / N)``, ``S_c`` the float64 sum of the stage's
+                                   float32 values, the division in float64
+
+    float32 throughout, every operation rounded on its own, divisions and square roots correctly rounded.  ``consts``
+    float32 [number of flip and center steps, 3] holds the ``m`` / ``mu`` rows that were used, in step order, 0 on the
+    axes a flip leaves alone.  One apply kernel, and in front of it one reduction launch per flip / center step; no
+    atomics, the same call gives the same bytes; no host synchronisation.  ``N = 0`` launches nothing.  ``3 N >= 2^31``
+    raises ``DvaError`` with code ``DVA_ERR_UNSUPPORTED``.
+
+    Against the torch composition of the reference's lines: noise, scale on ``pos`` and flip are its results bit for
+    bit; linear differs from a BLAS ``matmul`` within ``6 * 2^-24 * sum_j |p_j| |M_ij|`` (each side lies within half of
+    that of the exact value); center subtracts the correctly rounded mean where torch's float32 ``mean`` carries its
+    summation error."""
+    import ctypes
+    if not torch.is_tensor(pos):
+        raise TypeError("ops.cloud_augment: pos must be a tensor")
+    dev = require_device(pos, norm, noise)
+    if pos.dtype != torch.float32 or pos.dim() != 2 or pos.shape[1] != 3:
+        raise TypeError(f"ops.cloud_augment: pos must be float32 [N, 3], got {pos.dtype} {tuple(pos.shape)}")
+    n = int(pos.shape[0])
+    for name, t in (("norm", norm), ("noise", noise)):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (n, 3)):
+            raise TypeError(f"ops.cloud_augment: {name} must be float32 [{n}, 3], got {t.dtype} {tuple(t.shape)}")
+    steps = [tuple(s) for s in steps]
+    if len(steps) > CLOUD_MAX_STEPS:
+        raise ValueError(f"ops.cloud_augment: {len(steps)} steps, the kernel takes at most {CLOUD_MAX_STEPS}")
+    codes = (ctypes.c_int32 * max(len(steps), 1))()
+    params = (ctypes.c_float * (max(len(steps), 1) * CLOUD_STEP_PARAMS))()
+    n_reduce, with_norm, with_noise = 0, False, False
+    for k, step in enumerate(steps):
+        name, args = step[0], step[1:]
+        if name not in CLOUD_STEP_CODE:
+            raise ValueError(f"ops.cloud_augment: unknown step {name!r} (one of {sorted(CLOUD_STEP_CODE)})")
+        codes[k] = CLOUD_STEP_CODE[name]
+        row = [0.0] * CLOUD_STEP_PARAMS
+        if name == "noise":
+            if noise is None:
+                raise ValueError("ops.cloud_augment: a noise step needs the noise tensor")
+            with_noise = True
+        elif name == "linear":
+            row[:9] = _cloud_floats(args[0], 9, "a linear step's matrix")
+            if len(args) > 1 and args[1]:
+                if norm is None:
+                    raise ValueError("ops.cloud_augment: a linear step with_norm needs norm")
+                row[9], with_norm = 1.0, True
+        elif name == "scale":
+            row[:3] = _cloud_floats(args[0], 3, "a scale step")
+            if norm is not None:
+                row[9], with_norm = 1.0, True
+        elif name == "flip":
+            mask = [bool(a) for a in args[0]]
+            if len(mask) != 3 or not any(mask):
+                raise ValueError(f"ops.cloud_augment: a flip step takes three flags, at least one set, got {args[0]}")
+            row[:3] = [float(a) for a in mask]
+            n_reduce += 1
+        else:
+            n_reduce += 1
+        params[k * CLOUD_STEP_PARAMS:(k + 1) * CLOUD_STEP_PARAMS] = row
+    if 3 * n >= 1 << 31:
+        raise _lib.DvaError(f"ops.cloud_augment: {n} points; the kernels take 3 N < 2^31 (DVA_ERR_UNSUPPORTED)", code=-2)
+    out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    norm_out = norm if not with_norm else torch.empty((n, 3), dtype=torch.float32, device=dev)
+    consts = torch.empty((n_reduce, 3), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out, norm_out, consts
+    lib = _lib.load()
+    pos = pos.contiguous()
+    norm_in = norm.contiguous() if with_norm else None
+    noise_in = noise.contiguous() if with_noise else None
+    ws, ws_bytes = None, 0
+    if n_reduce:
+        ws, ws_bytes = _lib.workspace("dva_cloud_augment_workspace_bytes", dev, n, n_reduce)
+    # every launch reads pos (and noise); the apply launch also reads norm and writes pos_out (and norm_out)
+    with _timed("cloud_augment", n * 12 * ((n_reduce + 1) * (1 + bool(with_noise)) + 1 + 2 * bool(with_norm))):
+        check(lib.dva_cloud_augment_f32(ptr(pos), ptr(norm_in), ptr(noise_in), n, codes, params, len(steps), ptr(out),
+                                        ptr(norm_out) if with_norm else None, ptr(consts), ptr(ws), ws_bytes,
+                                        stream_of(pos)), "dva_cloud_augment_f32")
+    return out, norm_out, consts
 
 
 # ---------------------------------------------------------------------------------------------

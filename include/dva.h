@@ -1090,6 +1090,65 @@ int dva_image_window_u8(const uint8_t* src, int64_t N, int64_t H, int64_t W, con
                         void* stream);
 
 /* ------------------------------------------------------------------------------------------ *
+ * The positional 3D augmentations of the per-sample transform chains (cloud_augment.hip): RandomNoise, RandomRotate /
+ * Random3AxisRotation, RandomScaleAnisotropic, RandomSymmetry and Center (core/data_transform/transforms.py:463-563,
+ * features.py:30-81; RandomRotate and Center are torch_geometric's, of which no source or fixture exists here: for
+ * those two the arithmetic below is the contract, parity is UNPINNED).  The host makes every random draw; this entry
+ * applies the drawn values.  All arithmetic is fp32, every operation rounded on its own, no fused multiply-add,
+ * correctly rounded division and square root.
+ *   dva_cloud_augment_f32    pos fp32 [n, 3], norm fp32 [n, 3] (nullable), noise fp32 [n, 3] (nullable), all DEVICE and
+ *                            contiguous.  The n_steps <= DVA_CLOUD_MAX_STEPS steps codes[k] (DVA_CLOUD_*, HOST int32)
+ *                            with the parameters params[k] (HOST fp32 [n_steps, DVA_CLOUD_STEP_PARAMS], passed on by
+ *                            value: q = params + DVA_CLOUD_STEP_PARAMS k) are applied in order to every point p and,
+ *                            where a step says so, to its normal v:
+ *                              NOISE    p_c = p_c + e_c, e = the point's row of noise.  No parameters.
+ *                              LINEAR   p_i = ((p_0 M_i0 + p_1 M_i1) + p_2 M_i2), M row-major in q[0..8]; with q[9]
+ *                                       != 0 (with_norm) the same for v.  Random3AxisRotation passes its matrix M
+ *                                       (pos @ M^T), RandomRotate the transpose of its matrix A (pos @ A).
+ *                              SCALE    p_c = p_c * s_c, s = q[0..2]; with q[9] != 0 (with_norm) v_c = v_c / s_c,
+ *                                       l = sqrt((v_0 v_0 + v_1 v_1) + v_2 v_2), v_c = v_c / max(l, 1e-12f)
+ *                                       (F.normalize).
+ *                              FLIP     on every axis c with q[c] != 0: p_c = m_c - p_c, m_c = the exact maximum of p_c
+ *                                       over the n points in their state at this step.  At least one axis.
+ *                              CENTER   p_c = p_c - mu_c, mu_c = f32(S_c / n), S_c = the fp64 sum of the fp32 values
+ *                                       p_c of the n points in their state at this step, the division in fp64.
+ *                            out fp32 [n, 3] takes p; norm_out fp32 [n, 3] takes v and is written (and required) only
+ *                            when some step has with_norm.  consts fp32 [number of FLIP and CENTER steps, 3] (DEVICE)
+ *                            takes the rows m / mu the entry used, in step order, 0 on the axes a FLIP leaves alone;
+ *                            it is required when such a step exists.
+ *                            Launches: one reduction kernel per FLIP / CENTER step, in step order (it evaluates the
+ *                            steps in front of its step on every point and writes per-block partial maxima or fp64
+ *                            sums), then one apply kernel.  The partials of a reduction are combined by every block of
+ *                            the next launch in a fixed order; no atomics, and the grid of a reduction depends on n
+ *                            alone: the same call gives the same bytes.  Every launch reads each input row once and
+ *                            the apply kernel writes each output element once.  Nothing synchronises.
+ *                            Aliasing: out may be pos (and norm_out norm) only in a list WITHOUT a FLIP or CENTER
+ *                            step, where a point is read and written by its own lane alone; with one, the reductions
+ *                            and the apply pass must read the same input and an alias is DVA_ERR_INVALID.
+ *                            workspace: dva_cloud_augment_workspace_bytes(n, n_steps) (rows of partials for up to
+ *                            n_steps reducing steps), needed with a FLIP / CENTER step only; it need not be cleared.
+ *                            Two deviations from the reference's torch composition are inherent: LINEAR against a BLAS
+ *                            matmul (both lie within 3 * 2^-24 * sum_j |p_j| |M_ij| of the exact value, so within
+ *                            twice that of each other), and CENTER against torch's fp32 mean (mu here is the correctly
+ *                            rounded mean up to the fp64 summation error; torch sums in fp32).  NOISE, SCALE on pos
+ *                            and FLIP are the composition's results bit for bit.  NaN coordinates are not supported.
+ * Argument errors return DVA_ERR_INVALID before any HIP call: a negative size, more than DVA_CLOUD_MAX_STEPS steps, a
+ * null codes / params with steps, an unknown code, NOISE without noise, with_norm without norm, a FLIP of no axis; and,
+ * with n > 0, a null pos / out, a missing norm_out / consts / workspace where the list needs one, a workspace that is
+ * too small.  3 n >= 2^31 is DVA_ERR_UNSUPPORTED.  n = 0 is a no-op that needs no buffer. */
+#define DVA_CLOUD_NOISE 0
+#define DVA_CLOUD_LINEAR 1
+#define DVA_CLOUD_SCALE 2
+#define DVA_CLOUD_FLIP 3
+#define DVA_CLOUD_CENTER 4
+#define DVA_CLOUD_MAX_STEPS 16
+#define DVA_CLOUD_STEP_PARAMS 10
+int64_t dva_cloud_augment_workspace_bytes(int64_t n, int32_t n_steps);
+int dva_cloud_augment_f32(const float* pos, const float* norm, const float* noise, int64_t n, const int32_t* codes,
+                          const float* params, int32_t n_steps, float* out, float* norm_out, float* consts,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------ *
  * The tail of the segmentation step (segloss.hip).  Replaces F.log_softmax + F.nll_loss and lovasz_softmax of
  * models/segmentation/sparseconv3d.py:42-55 (metrics/lovasz_loss.py:155-202) and the argmax + bincount of
  * SegmentationTracker._compute_metrics (metrics/segmentation_tracker.py:71-91).

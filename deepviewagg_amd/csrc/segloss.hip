@@ -506,7 +506,8 @@ int dva_lovasz_softmax(const float* probas, const int64_t* labels, int64_t P, in
   if (P > 0 && (!probas || !labels || !grad || !workspace)) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   if (P == 0) {
-    if (hipMemsetAsync(loss, 0, sizeof(float), s) != hipSuccess) return DVA_ERR_LAUNCH;
+    zero_words(loss, 1, s);
+    DVA_CHECK_LAUNCH();
     return DVA_OK;
   }
   LovaszLayout L;
@@ -516,8 +517,8 @@ int dva_lovasz_softmax(const float* probas, const int64_t* labels, int64_t P, in
   const int64_t N = P * C;
   rocprim::double_buffer<uint64_t> keys(L.k0, L.k1);
   rocprim::double_buffer<uint32_t> vals(L.v0, L.v1);
-  if (hipMemsetAsync(L.cnt, 0, (size_t)(C + 1) * 4, s) != hipSuccess) return DVA_ERR_LAUNCH;
-  if (hipMemsetAsync(grad, 0, (size_t)N * 4, s) != hipSuccess) return DVA_ERR_LAUNCH;
+  zero_words(L.cnt, C + 1, s);          // kernels, not memset nodes: the entry is capturable (dva_common.h)
+  zero_words(grad, N, s);
   hipLaunchKernelGGL(lovasz_keys_kernel, dim3(capped_grid(N, SEG_THREADS, 8192)), dim3(SEG_THREADS), 0, s, probas,
                      labels, ignore_index, (int)use_ignore, class_mask, P, (int)C, keys.current(), vals.current(),
                      L.cnt);

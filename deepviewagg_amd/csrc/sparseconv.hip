@@ -435,7 +435,8 @@ int dva_sparse_conv_wgrad(const void* x, const int32_t* nbr, const void* grad_ou
   if (n_src > 0x7fffffffLL || n_dst > 0x7fffffffLL / K) return DVA_ERR_UNSUPPORTED;
   if (!grad_W) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(grad_W, 0, (size_t)K * Cin * Cout * sizeof(float), s) != hipSuccess) return DVA_ERR_LAUNCH;
+  zero_words(grad_W, (int64_t)K * Cin * Cout, s);        // a kernel, not a memset node: capturable (dva_common.h)
+  DVA_CHECK_LAUNCH();
   if (n_dst == 0 || n_src == 0) return DVA_OK;
   if (!x || !nbr || !grad_out) return DVA_ERR_INVALID;
   if (((uintptr_t)x | (uintptr_t)grad_out) & 15) return DVA_ERR_INVALID;

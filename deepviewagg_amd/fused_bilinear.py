@@ -33,9 +33,9 @@ def position_order(C, device):
     """kappa [C]: channel held by position p of the kernels' row layout (32 b + 16 h + r -> 32 b + chan(r, h))."""
     key = (C, str(device))
     if key not in _POS:
-        p = torch.arange(C)
+        p = torch.arange(C, device=device)       # built on the device: a host-to-device copy would synchronise
         b, h, r = p // 32, (p % 32) // 16, p % 16
-        _POS[key] = (32 * b + (r & 3) + 8 * (r >> 2) + 4 * h).to(device)
+        _POS[key] = 32 * b + (r & 3) + 8 * (r >> 2) + 4 * h
     return _POS[key]
 
 

@@ -342,9 +342,9 @@ def key_position_order(device):
     """kappa [32]: key channel held by position i of a key row (i = 16 h + r -> (r & 3) + 8 (r >> 2) + 4 h)."""
     k = str(device)
     if k not in _KEY_POS:
-        i = torch.arange(D)
+        i = torch.arange(D, device=device)       # built on the device: a host-to-device copy would synchronise
         r, h = i % 16, i // 16
-        _KEY_POS[k] = ((r & 3) + 8 * (r >> 2) + 4 * h).to(device)
+        _KEY_POS[k] = (r & 3) + 8 * (r >> 2) + 4 * h
     return _KEY_POS[k]
 
 

@@ -31,6 +31,14 @@ CLASS_GATES[ROW_MAX] = CLASS_GATES[ROW_P99] = 0.0
 P99_MIN_ROWS = 200
 AUTOCAST_ROW_HEADROOM = 1.5
 
+# A captured step replayed on new contents against its eager twin (tests/graph_replay.py): NO typed-in gate either.  The
+# gate is REPLAY_HEADROOM x the twin's own run-to-run spread on identical contents, measured at test time; a tensor
+# whose spread is exactly 0 is held bit for bit.  (Five runs under-estimate the tail of ordering noise, hence 4 x; the
+# defects aimed at -- a stale constant, an accumulator that keeps growing -- move results by orders of magnitude more.)
+REPLAY = "replay"
+CLASS_GATES[REPLAY] = 0.0
+REPLAY_HEADROOM = 4.0
+
 # parameter gradients that are zero in exact arithmetic when the module has no gate (a bias common to all views of a
 # point) -> the sibling whose max-abs is the scale.  Used when the float64 tensor is below 1e-9 of that sibling.
 STRUCTURAL_ZERO_SIBLING = {

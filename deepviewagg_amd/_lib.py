@@ -274,6 +274,13 @@ SIGNATURES = {
     "dva_mapping_collate_workspace_bytes": (ctypes.c_int64, [_i64]),
     "dva_mapping_collate": (ctypes.c_int, [ctypes.POINTER(DvaCollateItem), _i64, _i32, _i32, _i64, _i64, _i64, _vp,
                                            _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "dva_nearest_seen_workspace_bytes": (ctypes.c_int64, [_i64]),
+    "dva_nearest_seen": (ctypes.c_int, [_vp, _vp, _i64, _vp, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp,
+                                        _i64, _vp]),
+    "dva_view_nll_workspace_bytes": (ctypes.c_int64, []),
+    "dva_view_nll_counts": (ctypes.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp]),
+    "dva_view_nll_fwd": (ctypes.c_int, [_vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "dva_view_nll_bwd": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
     "dva_lex_workspace_bytes": (ctypes.c_int64, [_i64]),
     "dva_argsort_i64": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "dva_argunique_i64": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp]),

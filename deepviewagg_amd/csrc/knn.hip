@@ -17,25 +17,12 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "dva_common.h"
+#include "knn_grid.h"
 
 namespace dva {
 
 constexpr int KNN_TPB = 64;      // one wavefront per block: the candidate lists live in LDS, [slot][thread]
 constexpr int KNN_KMAX = 128;     // k <= 64: 32 KB of candidate lists per block; k <= 128 (BiasuttiVisibility, k = 75): 64 KB
-constexpr int CELL_BITS = 21;
-constexpr int64_t CELL_BIAS = 1 << 20;
-
-__device__ __forceinline__ uint64_t cell_key(int64_t cx, int64_t cy, int64_t cz) {
-  return ((uint64_t)(cx + CELL_BIAS) << (2 * CELL_BITS)) | ((uint64_t)(cy + CELL_BIAS) << CELL_BITS) |
-         (uint64_t)(cz + CELL_BIAS);
-}
-__device__ __forceinline__ uint32_t hash64(uint64_t k) {
-  k ^= k >> 33; k *= 0xff51afd7ed558ccdULL; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ULL; k ^= k >> 33;
-  return (uint32_t)k;
-}
-__device__ __forceinline__ int cell_of(float p, float origin, float inv_cell) {
-  return (int)floorf((p - origin) * inv_cell);
-}
 
 // bbox = min xyz | max xyz (device memory, written by the caller's stream)
 __global__ __launch_bounds__(256) void knn_keys_kernel(const float* __restrict__ xyz, int64_t n,
@@ -69,17 +56,6 @@ __global__ __launch_bounds__(256) void knn_cells_kernel(const float* __restrict_
         h = (h + 1) & mask;
       }
     }
-  }
-}
-
-__device__ __forceinline__ int cell_start(const uint64_t* __restrict__ tkeys, const int32_t* __restrict__ tvals,
-                                          uint32_t mask, uint64_t k) {
-  uint32_t h = hash64(k) & mask;
-  for (;;) {
-    const uint64_t t = tkeys[h];
-    if (t == k) return tvals[h];
-    if (t == ~0ULL) return -1;
-    h = (h + 1) & mask;
   }
 }
 
@@ -131,8 +107,7 @@ __global__ __launch_bounds__(KNN_TPB) void knn_query_kernel(
             if (s < 0) continue;
             for (; s < n && keys_sorted[s] == key; ++s) {
               const float4 p = pts[s];
-              const float ex = q.x - p.x, ey = q.y - p.y, ez = q.z - p.z;
-              const float d = (ex * ex + ey * ey) + ez * ez;
+              const float d = dist2_f32(q.x, q.y, q.z, p.x, p.y, p.z);
               const int j = __float_as_int(p.w);
               if (cnt < k) {
                 s_d[cnt][t] = d;

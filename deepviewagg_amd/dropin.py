@@ -14,7 +14,9 @@ and imports the data classes from
 ``torch_points3d.core.multimodal.{csr,image,data}`` (``MMData`` / ``MMBatch`` in the last), and takes ``lovasz_softmax`` and ``ConfusionMatrix`` from
 ``torch_points3d.metrics.{lovasz_loss,confusion_matrix}`` and ``SegmentationVoter`` from
 ``torch_points3d.metrics.segmentation_helpers``; where the reference's ``SegmentationTracker`` can be imported,
-its ``_compute_metrics`` becomes ``deepviewagg_amd.metrics.segmentation_tracker.compute_metrics``.  The image transforms
+its ``_compute_metrics`` becomes ``deepviewagg_amd.metrics.segmentation_tracker.compute_metrics``; where
+``torch_points3d.models.segmentation.multimodal.no3d`` is loaded or can be imported, ``No3D.forward`` becomes
+``deepviewagg_amd.models.no3d.forward`` (nearest-seen fill and view-level loss on the device).  The image transforms
 of the data configs resolve on ``torch_points3d.core.data_transform.multimodal.image``, which is aliased whole: with
 ``ColorJitter``, ``Normalize`` and ``ToImageData`` every per-sample image transform the shipped chains name is there, next
 to ``FusedImageTail`` and ``fuse_image_tail`` (one pass for the tail of a chain) and to ``DeferImages`` and
@@ -109,6 +111,7 @@ def install(patch_existing=True):
         for k in names:
             setattr(pkg, k, getattr(ours, k))
     _bind_tracker(patch_existing)
+    _bind_no3d(patch_existing)
     return done
 
 
@@ -128,3 +131,20 @@ def _bind_tracker(patch_existing):
     from .metrics.segmentation_tracker import compute_metrics
     cls._compute_metrics = compute_metrics
     tracker.ConfusionMatrix = ConfusionMatrix
+
+
+def _bind_no3d(patch_existing):
+    """The reference's image-only models (models/segmentation/multimodal/no3d.py), when the module is loaded or can be
+    imported, run their tail on the device from now on: nearest-seen fill and view-level loss (models.no3d)."""
+    name = "torch_points3d.models.segmentation.multimodal.no3d"
+    module = sys.modules.get(name)
+    if module is None and patch_existing:
+        try:
+            module = importlib.import_module(name)
+        except Exception:
+            module = None
+    cls = getattr(module, "No3D", None)
+    if cls is None:
+        return
+    from .models.no3d import forward
+    cls.forward = forward

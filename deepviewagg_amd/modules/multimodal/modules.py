@@ -134,6 +134,10 @@ class MultimodalBlockUp(nn.Module):
 
 
 class UnimodalBranch(nn.Module):
+    # True: keep_last_view stores a lazy gather (ops.GatheredFeatures / InterpolatedFeatures) in last_view_x_mod as it
+    # is, for consumers that take it (models.no3d: the view-level loss on the map rows); False: the reference's [V, C]
+    KEEP_LAST_VIEW_LAZY = False
+
     def __init__(self, conv, atomic_pool, view_pool, fusion, drop_3d=0, drop_mod=0, hard_drop=False,
                  keep_last_view=False, checkpointing='', out_channels=None, interpolate=False):
         super().__init__()
@@ -266,7 +270,8 @@ class UnimodalBranch(nn.Module):
             csr_idx = mod_data.view_csr_indexing
         if self.keep_last_view:
             # reference consumers (applications/multimodal/no3d.py:128, view losses) expect the [V, C] tensor
-            mod_data.last_view_x_mod = x_mod.materialize() if isinstance(x_mod, ops.LAZY_TYPES) else x_mod
+            lazy = isinstance(x_mod, ops.LAZY_TYPES) and not self.KEEP_LAST_VIEW_LAZY
+            mod_data.last_view_x_mod = x_mod.materialize() if lazy else x_mod
             mod_data.last_view_x_map = x_map
             mod_data.last_view_csr_idx = csr_idx
         if 'v' in self.checkpointing and isinstance(x_mod, torch.Tensor):
@@ -287,8 +292,13 @@ class UnimodalBranch(nn.Module):
             x_mod = self.drop_mod(x_mod)
             if self.keep_last_view:
                 last = mod_data.last_view_x_mod
-                last = last.materialize() if isinstance(last, ops.LAZY_TYPES) else last
-                mod_data.last_view_x_mod = self.drop_mod(last)
+                # element-wise dropout on [V, C] does not commute with the gather: only nn.Dropout in eval mode, the
+                # identity, leaves a lazy gather (KEEP_LAST_VIEW_LAZY) as it is
+                identity = isinstance(self.drop_mod, nn.Dropout) and not self.training
+                if isinstance(last, ops.LAZY_TYPES) and not identity:
+                    last = last.materialize()
+                if not isinstance(last, ops.LAZY_TYPES):
+                    mod_data.last_view_x_mod = self.drop_mod(last)
         return x_3d, x_mod, mod_data
 
     def extra_repr(self) -> str:

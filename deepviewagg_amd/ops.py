@@ -3070,6 +3070,169 @@ def log_softmax_nll(logits, labels, weight=None, ignore_index=-1):
     return _LogSoftmaxNLL.apply(logits, lab, weight, int(ignore_index))
 
 
+# ---------------------------------------------------------------------------------------------
+# the tail of the image-only models (models/segmentation/multimodal/no3d.py:102-154): csrc/nearest_seen.hip,
+# csrc/view_loss.hip
+# ---------------------------------------------------------------------------------------------
+
+NEAREST_SEEN_LEVELS = 4     # grids of a search, cell x4 each; the last one walks every shell, so any cell is exact
+
+
+def _nearest_seen(what, pos, seen, x, cell):
+    lib = _lib.load()
+    if not torch.is_tensor(pos) or not torch.is_tensor(seen):
+        raise TypeError(f"ops.{what} takes tensors")
+    require_device(pos, seen, x)
+    if pos.dim() != 2 or pos.shape[1] != 3:
+        raise ValueError(f"ops.{what}: pos must be [N, 3], got {tuple(pos.shape)}")
+    n = int(pos.shape[0])
+    if seen.dtype not in (torch.bool, torch.uint8) or seen.dim() != 1 or seen.shape[0] != n:
+        raise ValueError(f"ops.{what}: seen must be bool or uint8 [N] = [{n}], got {seen.dtype} {tuple(seen.shape)}")
+    pos = pos.detach().float().contiguous()
+    seen8 = seen.detach().contiguous().view(torch.uint8)
+    dev = pos.device
+    filled, K, code = None, 0, 0
+    if x is not None:
+        if x.dim() != 2 or x.shape[0] != n or x.shape[1] < 1:
+            raise ValueError(f"ops.{what}: x must be [N, K] = [{n}, K >= 1], got {tuple(x.shape)}")
+        x = x.detach().contiguous()
+        K, code = int(x.shape[1]), dtype_code(x)
+        filled = torch.empty_like(x)
+    src = torch.empty(n, dtype=torch.int32, device=dev)
+    any_seen = torch.zeros(1, dtype=torch.bool, device=dev)
+    if n == 0:
+        return src, any_seen, filled
+    lo, hi = pos.min(0).values, pos.max(0).values
+    bbox = torch.cat([lo, hi]).contiguous()
+    ext = None
+    if cell is None:
+        box = bbox.cpu()                               # the one host read: the extent that sizes the cell
+        ext = float((box[3:] - box[:3]).max())
+        cell = _knn_default_cell(box[:3], box[3:], ext, n, 1) if ext > 0 else 1.0
+    cell = max(float(cell), 1e-12)
+    ws, nbytes = _lib.workspace("dva_nearest_seen_workspace_bytes", dev, n)
+    done = torch.zeros(n, dtype=torch.uint8, device=dev)
+    shells = 2
+    with _timed(what, n * (13 + 4 + 2 * K * (x.element_size() if x is not None else 0))):
+        for level in range(NEAREST_SEEN_LEVELS):
+            last = level == NEAREST_SEEN_LEVELS - 1 or (ext is not None and cell * shells >= ext + cell)
+            check(lib.dva_nearest_seen(ptr(pos), ptr(seen8), n, ptr(bbox), float(cell), shells, int(last), ptr(done),
+                                       ptr(src), ptr(any_seen), ptr(x) if last else None, K, code,
+                                       ptr(filled) if last else None, ptr(ws), int(nbytes), stream_of(pos)),
+                  "dva_nearest_seen")
+            if last:
+                break
+            cell *= 4.0
+    return src, any_seen, filled
+
+
+def nearest_seen(pos, seen, cell=None):
+    """``(src int32 [N], any_seen bool [1])``: ``src[i] = i`` for a seen point, and for an unseen point the index of the
+    seen point with the smallest fp32 squared distance ``((dx*dx + dy*dy) + dz*dz)`` (each operation rounded on its own,
+    ties to the lowest index): the KeOps ``argmin`` of the reference's eval forward
+    (models/segmentation/multimodal/no3d.py:119-122), mapped back to the numbering of ``pos``.  With no seen point
+    ``src[i] = i`` everywhere and ``any_seen`` is False.  ``pos`` fp32 [N, 3], ``seen`` bool or uint8 [N].
+
+    As in the reference the whole batch is ONE cloud: a point may take its neighbour from another sample of the batch.
+    The mask is never compacted and the number of seen points is never read back.  The search is exact for any
+    ``cell`` (it affects time only); with ``cell=None`` the extent of ``pos`` is read once to size it (the only host
+    read), with a ``cell`` there is none.  Bitwise reproducible."""
+    src, any_seen, _ = _nearest_seen("nearest_seen", pos, seen, None, cell)
+    return src, any_seen
+
+
+def fill_unseen(x, pos, seen, cell=None):
+    """``(filled [N, K] in x.dtype, any_seen bool [1])`` with ``filled[i] = x[src[i]]`` for ``src`` of ``nearest_seen``:
+    every unseen point takes the row of its nearest seen point (reference no3d.py:105-125), the rows copied as bits in
+    the launch that finishes the search.  ``x`` [N, K] float32, bfloat16 or float16.  With no seen point ``filled``
+    equals ``x``.  The whole batch is one cloud, as in the reference (no ``batch=``).  NOT differentiable: the
+    reference applies it in eval mode only, ``x`` is detached.  Host reads as for ``nearest_seen``."""
+    if not torch.is_tensor(x):
+        raise TypeError("ops.fill_unseen takes tensors")
+    _, any_seen, filled = _nearest_seen("fill_unseen", pos, seen, x, cell)
+    return filled, any_seen
+
+
+class _ViewNLL(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rows, row_idx, labels, csr_idx, weight, ignore_index):
+        lib = _lib.load()
+        x = rows.detach().contiguous()
+        R, K = x.shape
+        dev = x.device
+        V = R if row_idx is None else int(row_idx.shape[0])
+        N = int(labels.shape[0])
+        cnt = torch.empty((R, K), dtype=torch.int32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        numden = torch.empty(2, dtype=torch.float64, device=dev)
+        ws, nbytes = _lib.workspace("dva_view_nll_workspace_bytes", dev)
+        with _timed("view_nll_fwd", V * 4 + N * 16 + R * K * (8 + x.element_size())):
+            check(lib.dva_view_nll_counts(ptr(row_idx), V, ptr(csr_idx), ptr(labels), N, int(ignore_index), R, K, ptr(cnt),
+                                          stream_of(x)), "dva_view_nll_counts")
+            check(lib.dva_view_nll_fwd(ptr(x), dtype_code(x), ptr(cnt), ptr(weight), R, K, ptr(loss), ptr(numden), ptr(ws),
+                                       nbytes, stream_of(x)), "dva_view_nll_fwd")
+        ctx.save_for_backward(x, cnt, weight, numden)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        x, cnt, weight, numden = ctx.saved_tensors
+        lib = _lib.load()
+        R, K = x.shape
+        g_loss = g_loss.to(torch.float32).reshape(1).contiguous()
+        out = torch.empty_like(x)
+        with _timed("view_nll_bwd", R * K * (4 + 2 * x.element_size())):
+            check(lib.dva_view_nll_bwd(ptr(x), dtype_code(x), ptr(cnt), ptr(weight), ptr(numden), ptr(g_loss), R, K,
+                                       ptr(out), stream_of(x)), "dva_view_nll_bwd")
+        return out, None, None, None, None, None
+
+
+def view_nll(x_view, labels, csr_idx, weight=None, ignore_index=-1):
+    """The view-level loss of the image-only models (reference no3d.py:145-154):
+    ``F.nll_loss(F.log_softmax(x_view, -1), labels.repeat_interleave(csr_idx[1:] - csr_idx[:-1]), weight, ignore_index)``
+    up to summation order, as a float32 scalar, without the [V, K] tensor and without the repeated labels.
+
+    ``x_view`` is a ``GatheredFeatures`` (the lazy gather of an exact mapping, the identity gather that
+    ``gather_segment_max`` returns, or a ``GatheredFeatures.cat``) or a plain [V, K] tensor (rows under the identity
+    index); rows float32, bfloat16 or float16, upcast exactly, 1 <= K <= 64.  ``labels`` integer [N], ``csr_idx`` int64
+    [N + 1].  Every view of a map row has that row's log-softmax, so the loss is a function of the per-row label
+    counts (exact integers): ``sum w[y_v] (-logp_v[y_v]) / sum w[y_v]`` over the views whose point's label is not
+    ``ignore_index``; a label outside [0, K) takes no part; NaN when no view takes part, as torch.  Reduced in float64
+    in a fixed order: bitwise reproducible.  The gradient flows to the rows only, in their dtype.  No host
+    synchronisation."""
+    if isinstance(x_view, GatheredFeatures):
+        rows, row_idx = x_view.rows, x_view.row_idx
+    elif torch.is_tensor(x_view):
+        rows, row_idx = x_view, None
+    else:
+        raise TypeError(f"ops.view_nll takes a GatheredFeatures or a [V, K] tensor, got {type(x_view).__name__}")
+    if not torch.is_tensor(labels) or not torch.is_tensor(csr_idx):
+        raise TypeError("ops.view_nll takes tensors")
+    require_device(rows, row_idx, labels, csr_idx, weight)
+    if rows.dtype not in _SEG_DTYPES:
+        raise TypeError(f"ops.view_nll: rows of dtype {rows.dtype}; supported: {', '.join(str(d) for d in _SEG_DTYPES)}")
+    if rows.dim() != 2:
+        raise ValueError(f"ops.view_nll: the rows must be [R, K], got {tuple(rows.shape)}")
+    R, K = int(rows.shape[0]), int(rows.shape[1])
+    if not 1 <= K <= SEG_MAX_CLASSES:
+        raise ValueError(f"ops.view_nll: K = {K} classes; the kernels take 1 <= K <= {SEG_MAX_CLASSES}")
+    if R * K >= 1 << 31:
+        raise ValueError(f"ops.view_nll: R * K = {R} * {K} elements; the kernels take fewer than 2^31")
+    if labels.dim() != 1 or labels.dtype.is_floating_point or labels.dtype == torch.bool:
+        raise TypeError(f"ops.view_nll: labels must be integers [N], got {labels.dtype} {tuple(labels.shape)}")
+    csr_idx = _check_ptr(csr_idx)
+    if csr_idx.shape[0] != labels.shape[0] + 1:
+        raise ValueError(f"ops.view_nll: csr_idx must be [N + 1] = [{labels.shape[0] + 1}], got {tuple(csr_idx.shape)}")
+    if row_idx is not None:
+        row_idx = row_idx.detach().to(torch.int32).contiguous()
+    if weight is not None:
+        if weight.dim() != 1 or weight.shape[0] != K:
+            raise ValueError(f"ops.view_nll: weight must be [K] = [{K}], got {tuple(weight.shape)}")
+        weight = weight.detach().to(torch.float32).contiguous()
+    return _ViewNLL.apply(rows, row_idx, labels.detach().to(torch.int64).contiguous(), csr_idx, weight,
+                          int(ignore_index))
+
+
 class _LovaszSoftmax(torch.autograd.Function):
     @staticmethod
     def forward(ctx, probas, labels, class_mask, present_only, ignore):

@@ -1462,6 +1462,54 @@ int dva_mapping_collate(const struct dva_collate_item* items /* HOST array */, i
                         float* out_features, int64_t* out_image_offsets /* device [n_items], nullable */,
                         void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------ *
+ * The tail of the image-only models (models/segmentation/multimodal/no3d.py:102-154): nearest-seen
+ * fill in eval mode (csrc/nearest_seen.hip) and the view-level loss (csrc/view_loss.hip).
+ *
+ * dva_nearest_seen   pos fp32 [n, 3], seen uint8 [n] (non-zero = seen), bbox = device fp32[6] (min xyz |
+ *   max xyz of pos).  src int32 [n]: src[i] = i for a seen point; for an unseen point the index, in
+ *   the numbering of pos, of the seen point with the smallest d2 = ((dx*dx + dy*dy) + dz*dz), every
+ *   operation rounded on its own in fp32 (the distance of dva_knn_query), ties to the lowest index.
+ *   With no seen point src[i] = i everywhere and any_seen[0] = 0 (else 1).  The whole array is one
+ *   cloud: a batch is searched across its samples, as the reference does.
+ *   Levels as for dva_knn: a call with last = 0 walks at most max_shell shells of cells around each
+ *   unfinished query (done uint8 [n], zeroed by the caller before the first call) and finishes those
+ *   whose neighbour is provably final; the call with last != 0 walks every shell the box holds, so
+ *   it finishes every query for ANY cell (the cell affects time only; a cell below extent / 2^19, in
+ *   the last call below extent / 16, is raised to that on the device), and writes src of the seen points and any_seen.  With x
+ *   ([n, K] of dtype, K <= 2^20; last call only) the same launch also writes filled[i] = x[src[i]],
+ *   rows copied as bits; filled must not alias x.  No float atomics: two runs give the same bits.
+ *   Nothing is read back to the host and the number of seen points is never needed.
+ *   n < 2^30 (DVA_ERR_UNSUPPORTED beyond); n = 0 is a no-op; bad arguments return before any HIP call.
+ *
+ * dva_view_nll_*   the loss nll_loss(log_softmax(x_view), repeat_interleave(labels, views per point))
+ *   of views that are a gather x_view[v] = rows[row_idx[v]] (row_idx int32 [n_views]; null = the
+ *   identity, n_rows = n_views), without x_view and without the repeated labels.  csr_idx int64
+ *   [n_points + 1] are the view pointers, labels int64 [n_points]; a view counts when its point's
+ *   label is not ignore_index and lies in [0, K); 1 <= K <= 64 and n_rows K < 2^31, n_views < 2^31
+ *   (DVA_ERR_UNSUPPORTED beyond).
+ *     counts  cnt int32 [n_rows, K], zeroed by the call: cnt[r][c] = counted views of row r whose
+ *             point has label c (int32 atomics: exact, so every run gives the same bits).
+ *     fwd     rows [n_rows, K] of dtype, upcast exactly; weight fp32 [K] (nullable: ones).
+ *             loss[0] = num / den, num = sum cnt w_c (-logp_r[c]), den = sum cnt w_c, reduced in fp64
+ *             in a fixed order; numden fp64 [2] keeps both; NaN when no view counts.
+ *     bwd     grad_rows[r][c] = grad_loss[0] / den * ((sum_c' cnt[r][c'] w_c') softmax_r[c] - cnt[r][c] w_c)
+ *             in the rows' dtype; a row without counted views gets zeros.
+ *   Nothing synchronises with the host.
+ * ------------------------------------------------------------------------------------------ */
+int64_t dva_nearest_seen_workspace_bytes(int64_t n);
+int dva_nearest_seen(const float* pos, const uint8_t* seen, int64_t n, const float* bbox, float cell,
+                     int32_t max_shell, int32_t last, uint8_t* done, int32_t* src, uint8_t* any_seen, const void* x,
+                     int32_t K, int32_t dtype, void* filled, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t dva_view_nll_workspace_bytes(void);
+int dva_view_nll_counts(const int32_t* row_idx, int64_t n_views, const int64_t* csr_idx, const int64_t* labels,
+                        int64_t n_points, int64_t ignore_index, int64_t n_rows, int32_t K, int32_t* cnt,
+                        void* stream);
+int dva_view_nll_fwd(const void* rows, int32_t dtype, const int32_t* cnt, const float* weight, int64_t n_rows,
+                     int32_t K, float* loss, double* numden, void* workspace, int64_t workspace_bytes, void* stream);
+int dva_view_nll_bwd(const void* rows, int32_t dtype, const int32_t* cnt, const float* weight, const double* numden,
+                     const float* grad_loss, int64_t n_rows, int32_t K, void* grad_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

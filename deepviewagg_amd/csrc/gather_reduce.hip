@@ -1,0 +1,293 @@
+// Lazy nearest gather fused with the mean / sum / min pool behind it, for gfx950 (reference: x_mod = features[idx],
+// core/multimodal/image.py:1262-1287, followed by BimodalCSRPool(mode) = torch_scatter.segment_csr over the items of each
+// segment, modules/multimodal/pooling.py:14-71; the max pool is csrc/gather.hip's dva_gather_segment_max_*).
+//
+// forward   out[s][c] = reduce over the items a in [seg_ptr[s], seg_ptr[s + 1]) of rows[row_idx[a]][c]
+// backward  grad_rows[r][c] = sum over the items a with row_idx[a] == r of g(a, c)
+//
+// No [P, C] tensor in either direction.  The forward is dva_segment_csr_fwd's arithmetic on the rows it would have been
+// handed (fp32 accumulation from 0 in item order, one division for the mean, one rounding; min: first item on ties, a NaN
+// wins only as the first item), so it equals the materialised composition bit for bit.  The backward is a segmented
+// reduction over the row plan of the items (perm = items sorted by map row, row_ptr): one wavefront per map row, fp32
+// accumulators, every element of grad_rows written once in the rows' storage type -- no float atomics, so two runs agree
+// bit for bit, and one rounding per map row where the materialised route rounds per item and again per row.
+//
+// Bytes: forward P (4 + C s) [map rows, out of the cache hierarchy] + S (8 + C s) (+ 2 S C: min's arg offsets);
+//        backward P (8 + C s) [gradient rows of the segments, cached] (+ 8 P: mean / min read seg_ptr, + 2 P C: min's
+//        arg rows) + R (4 + C s).
+#include "dva_common.h"
+
+namespace dva {
+
+// VEC consecutive channels of one row <-> fp32.  VEC = 16 / sizeof(T): one 16-byte access (C % VEC == 0 and 16-byte
+// aligned bases: the caller decides); VEC = 1: element accesses, any C and any base.
+template <typename T, int VEC>
+struct RowChunk {
+  static __device__ __forceinline__ void ld(const T* p, float* f) {
+    const uint4 r = *reinterpret_cast<const uint4*>(p);
+    if constexpr (sizeof(T) == 4) {
+      f[0] = __uint_as_float(r.x); f[1] = __uint_as_float(r.y);
+      f[2 % VEC] = __uint_as_float(r.z); f[3 % VEC] = __uint_as_float(r.w);
+    } else {
+      unpack_h8<T>(r, f);
+    }
+  }
+  static __device__ __forceinline__ void st(T* p, const float* f) {
+    if constexpr (sizeof(T) == 4)
+      *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2 % VEC], f[3 % VEC]);
+    else
+      *reinterpret_cast<uint4*>(p) = pack_h8<T>(f);
+  }
+  // the uint16 arg offsets of the same channels
+  static __device__ __forceinline__ void ld_arg(const uint16_t* p, uint32_t* k) {
+    if constexpr (VEC == 4) {
+      const uint2 a = *reinterpret_cast<const uint2*>(p);
+      k[0] = a.x & 0xffffu; k[1] = a.x >> 16; k[2 % VEC] = a.y & 0xffffu; k[3 % VEC] = a.y >> 16;
+    } else {
+      const uint4 a = *reinterpret_cast<const uint4*>(p);
+      const uint32_t w[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        k[(2 * e) % VEC] = w[e] & 0xffffu;
+        k[(2 * e + 1) % VEC] = w[e] >> 16;
+      }
+    }
+  }
+  static __device__ __forceinline__ void st_arg(uint16_t* p, const uint32_t* k) {
+    if constexpr (VEC == 4)
+      *reinterpret_cast<uint2*>(p) = make_uint2(k[0] | (k[1] << 16), k[2 % VEC] | (k[3 % VEC] << 16));
+    else
+      *reinterpret_cast<uint4*>(p) = make_uint4(k[0] | (k[1] << 16), k[2 % VEC] | (k[3 % VEC] << 16),
+                                                k[4 % VEC] | (k[5 % VEC] << 16), k[6 % VEC] | (k[7 % VEC] << 16));
+  }
+};
+template <typename T>
+struct RowChunk<T, 1> {
+  static __device__ __forceinline__ void ld(const T* p, float* f) { f[0] = Elt<T>::ld(p, 0); }
+  static __device__ __forceinline__ void st(T* p, const float* f) { Elt<T>::st(p, 0, f[0]); }
+  static __device__ __forceinline__ void ld_arg(const uint16_t* p, uint32_t* k) { k[0] = p[0]; }
+  static __device__ __forceinline__ void st_arg(uint16_t* p, const uint32_t* k) { p[0] = (uint16_t)k[0]; }
+};
+
+// One thread per (segment, VEC-channel chunk) walks the segment's items in order: the loop of segment_csr_fwd_kernel /
+// _vec_kernel (segment.hip) with the row index in between.
+template <typename T, int VEC, int REDUCE>
+__global__ __launch_bounds__(256) void gather_segment_reduce_fwd_kernel(const T* __restrict__ rows,
+                                                                         const int32_t* __restrict__ row_idx,
+                                                                         const int64_t* __restrict__ seg_ptr,
+                                                                         T* __restrict__ out, uint16_t* __restrict__ arg,
+                                                                         int64_t S, int C) {
+  const int cpr = C / VEC;
+  const int64_t total = S * (int64_t)cpr;
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t s = t / cpr;
+    const int c0 = (int)(t - s * cpr) * VEC;
+    const int64_t beg = seg_ptr[s], end = seg_ptr[s + 1];
+    float acc[VEC];
+    uint32_t best[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      acc[k] = 0.f;
+      best[k] = 0xffffu;
+    }
+    for (int64_t a = beg; a < end; ++a) {
+      float f[VEC];
+      RowChunk<T, VEC>::ld(rows + (int64_t)row_idx[a] * C + c0, f);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) {
+        if (REDUCE == DVA_MIN) {
+          if (a == beg || f[k] < acc[k]) {
+            acc[k] = f[k];
+            best[k] = (uint32_t)(a - beg);
+          }
+        } else {
+          acc[k] += f[k];
+        }
+      }
+    }
+    if (REDUCE == DVA_MEAN && end > beg) {
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) acc[k] /= (float)(end - beg);
+    }
+    RowChunk<T, VEC>::st(out + s * C + c0, acc);
+    if (REDUCE == DVA_MIN) RowChunk<T, VEC>::st_arg(arg + s * C + c0, best);
+  }
+}
+
+// One wavefront per map row r: its items perm[row_ptr[r] .. row_ptr[r + 1]) are spread over 64 / lpr slots, lpr lanes (a
+// power of two) own the VEC-channel chunks of a row; rows wider than lpr chunks are walked in column passes of lpr chunks.
+// Item a of segment s = seg_of_item[a] contributes grad_out[s][c] (sum), grad_out[s][c] / count_s (mean, fp32 true
+// division as segment_csr_bwd_kernel) or grad_out[s][c] where arg[s][c] == a - seg_ptr[s] (min).  The slots are summed
+// with wave64 xor shuffles in a fixed order.
+template <typename T, int VEC, int REDUCE>
+__global__ __launch_bounds__(256) void gather_segment_reduce_bwd_kernel(
+    const T* __restrict__ gout, const uint16_t* __restrict__ arg, const int64_t* __restrict__ seg_ptr,
+    const int32_t* __restrict__ perm, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ seg_of_item,
+    T* __restrict__ grows, int64_t R, int C, int lpr) {
+  constexpr int U = 2;
+  const int chunks = C / VEC;
+  const int lane = threadIdx.x & 63;
+  const int lane_r = lane & (lpr - 1), slot = lane / lpr, slots = 64 / lpr;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  for (int64_t r = wave; r < R; r += n_waves) {
+    const int beg = row_ptr[r], end = row_ptr[r + 1];
+    for (int ch0 = 0; ch0 < chunks; ch0 += lpr) {
+      const bool live = ch0 + lane_r < chunks;                 // lanes behind the last chunk of the row carry zeros
+      const int64_t col = (int64_t)(live ? ch0 + lane_r : 0) * VEC;
+      float acc[VEC];
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
+      for (int i0 = beg; i0 < end; i0 += slots * U) {
+        int64_t s[U];
+        uint32_t koff[U];
+        float scale[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int i = i0 + u * slots + slot;
+          const bool ok = i < end && live;
+          const int a = perm[i < end ? i : beg];
+          s[u] = seg_of_item[a];
+          koff[u] = 0xfffeu;                                   // 0xfffe never is a stored offset
+          scale[u] = ok ? 1.f : 0.f;
+          if (REDUCE != DVA_SUM) {
+            const int64_t sb = seg_ptr[s[u]];
+            if (REDUCE == DVA_MEAN) scale[u] = ok ? (float)(seg_ptr[s[u] + 1] - sb) : 0.f;
+            if (REDUCE == DVA_MIN && ok) koff[u] = (uint32_t)((int64_t)a - sb);
+          }
+        }
+        float g[U][VEC];
+        uint32_t ak[U][VEC];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          RowChunk<T, VEC>::ld(gout + s[u] * C + col, g[u]);
+          if (REDUCE == DVA_MIN) RowChunk<T, VEC>::ld_arg(arg + s[u] * C + col, ak[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) {
+            if (REDUCE == DVA_SUM)
+              acc[k] += scale[u] != 0.f ? g[u][k] : 0.f;
+            else if (REDUCE == DVA_MEAN)
+              acc[k] += scale[u] != 0.f ? g[u][k] / scale[u] : 0.f;
+            else
+              acc[k] += ak[u][k] == koff[u] ? g[u][k] : 0.f;
+          }
+        }
+      }
+      for (int off = lpr; off < 64; off <<= 1) {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) acc[k] += __shfl_xor(acc[k], off);
+      }
+      if (slot == 0 && live) RowChunk<T, VEC>::st(grows + r * C + col, acc);
+    }
+  }
+}
+
+constexpr int64_t GSR_GRID_CAP = 256 * 32;      // 256 CUs x 32 blocks, grid-stride beyond
+constexpr int64_t GSR_SIZE_MAX = 0x7fffffffLL;  // int32 row plan, int32 segment of item
+
+template <typename T, int VEC>
+static void launch_fwd(const void* rows, const int32_t* row_idx, const int64_t* seg_ptr, void* out, void* arg, int64_t S,
+                       int C, int reduce, hipStream_t s) {
+  const dim3 grid(capped_grid(S * (int64_t)(C / VEC), 256, GSR_GRID_CAP));
+#define DVA_L(R)                                                                                                   \
+  hipLaunchKernelGGL((gather_segment_reduce_fwd_kernel<T, VEC, R>), grid, dim3(256), 0, s, (const T*)rows, row_idx, \
+                     seg_ptr, (T*)out, (uint16_t*)arg, S, C)
+  if (reduce == DVA_SUM) DVA_L(DVA_SUM);
+  else if (reduce == DVA_MEAN) DVA_L(DVA_MEAN);
+  else DVA_L(DVA_MIN);
+#undef DVA_L
+}
+
+template <typename T, int VEC>
+static void launch_bwd(const void* gout, const void* arg, const int64_t* seg_ptr, const int32_t* perm,
+                       const int32_t* row_ptr, const int32_t* seg_of_item, void* grows, int64_t R, int C, int reduce,
+                       hipStream_t s) {
+  const int chunks = C / VEC;
+  int lpr = 1;
+  while (lpr < chunks && lpr < 64) lpr <<= 1;
+  const dim3 grid(capped_grid(R, 4, GSR_GRID_CAP));      // four wavefronts, four map rows per block
+#define DVA_L(RD)                                                                                                  \
+  hipLaunchKernelGGL((gather_segment_reduce_bwd_kernel<T, VEC, RD>), grid, dim3(256), 0, s, (const T*)gout,         \
+                     (const uint16_t*)arg, seg_ptr, perm, row_ptr, seg_of_item, (T*)grows, R, C, lpr)
+  if (reduce == DVA_SUM) DVA_L(DVA_SUM);
+  else if (reduce == DVA_MEAN) DVA_L(DVA_MEAN);
+  else DVA_L(DVA_MIN);
+#undef DVA_L
+}
+
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+static int check_sizes(int64_t S, int64_t P, int64_t R, int C, int dtype, int reduce) {
+  if (S < 0 || P < 0 || R < 0 || C < 0) return DVA_ERR_INVALID;
+  if (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16) return DVA_ERR_INVALID;
+  if (reduce < DVA_SUM || reduce > DVA_MIN) return DVA_ERR_INVALID;
+  return DVA_OK;
+}
+
+}  // namespace dva
+
+using namespace dva;
+
+extern "C" {
+
+int dva_gather_segment_reduce_fwd(const void* rows, const int32_t* row_idx, const int64_t* seg_ptr, void* out, void* arg,
+                                  int64_t S, int64_t P, int64_t R, int32_t C, int32_t dtype, int32_t reduce,
+                                  void* stream) {
+  int rc = check_sizes(S, P, R, C, dtype, reduce);
+  if (rc) return rc;
+  if (S > 0 && C > 0 && (!seg_ptr || !out || (reduce == DVA_MIN && !arg) || (P > 0 && (!rows || !row_idx))))
+    return DVA_ERR_INVALID;
+  if (reduce == DVA_MAX) return DVA_ERR_UNSUPPORTED;      // dva_gather_segment_max_fwd
+  if (S > GSR_SIZE_MAX || P > GSR_SIZE_MAX || R > GSR_SIZE_MAX) return DVA_ERR_UNSUPPORTED;
+  if (S == 0 || C == 0) return DVA_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const int vec = dtype == DVA_F32 ? 4 : 8;
+  const bool wide = C % vec == 0 && aligned16(rows) && aligned16(out) && aligned16(arg);
+  if (dtype == DVA_F32) {
+    if (wide) launch_fwd<float, 4>(rows, row_idx, seg_ptr, out, arg, S, C, reduce, s);
+    else launch_fwd<float, 1>(rows, row_idx, seg_ptr, out, arg, S, C, reduce, s);
+  } else if (dtype == DVA_F16) {
+    if (wide) launch_fwd<f16_t, 8>(rows, row_idx, seg_ptr, out, arg, S, C, reduce, s);
+    else launch_fwd<f16_t, 1>(rows, row_idx, seg_ptr, out, arg, S, C, reduce, s);
+  } else {
+    if (wide) launch_fwd<bf16_t, 8>(rows, row_idx, seg_ptr, out, arg, S, C, reduce, s);
+    else launch_fwd<bf16_t, 1>(rows, row_idx, seg_ptr, out, arg, S, C, reduce, s);
+  }
+  DVA_CHECK_LAUNCH();
+  return DVA_OK;
+}
+
+int dva_gather_segment_reduce_bwd(const void* grad_out, const void* arg, const int64_t* seg_ptr, const int32_t* perm,
+                                  const int32_t* row_ptr, const int32_t* seg_of_item, void* grad_rows, int64_t S,
+                                  int64_t P, int64_t R, int32_t C, int32_t dtype, int32_t reduce, void* stream) {
+  int rc = check_sizes(S, P, R, C, dtype, reduce);
+  if (rc) return rc;
+  if (S > 0 && C > 0 && R > 0 &&
+      (!grad_rows || !row_ptr ||
+       (P > 0 && (!grad_out || !seg_ptr || !perm || !seg_of_item || (reduce == DVA_MIN && !arg)))))
+    return DVA_ERR_INVALID;
+  if (reduce == DVA_MAX) return DVA_ERR_UNSUPPORTED;      // dva_gather_segment_max_bwd
+  if (S > GSR_SIZE_MAX || P > GSR_SIZE_MAX || R > GSR_SIZE_MAX) return DVA_ERR_UNSUPPORTED;
+  if (R == 0 || C == 0) return DVA_OK;
+  if (!grad_rows || !row_ptr) return DVA_ERR_INVALID;     // S == 0: every row still gets its zeros
+  hipStream_t s = (hipStream_t)stream;
+  const int vec = dtype == DVA_F32 ? 4 : 8;
+  const bool wide = C % vec == 0 && aligned16(grad_out) && aligned16(grad_rows) && aligned16(arg);
+  if (dtype == DVA_F32) {
+    if (wide) launch_bwd<float, 4>(grad_out, arg, seg_ptr, perm, row_ptr, seg_of_item, grad_rows, R, C, reduce, s);
+    else launch_bwd<float, 1>(grad_out, arg, seg_ptr, perm, row_ptr, seg_of_item, grad_rows, R, C, reduce, s);
+  } else if (dtype == DVA_F16) {
+    if (wide) launch_bwd<f16_t, 8>(grad_out, arg, seg_ptr, perm, row_ptr, seg_of_item, grad_rows, R, C, reduce, s);
+    else launch_bwd<f16_t, 1>(grad_out, arg, seg_ptr, perm, row_ptr, seg_of_item, grad_rows, R, C, reduce, s);
+  } else {
+    if (wide) launch_bwd<bf16_t, 8>(grad_out, arg, seg_ptr, perm, row_ptr, seg_of_item, grad_rows, R, C, reduce, s);
+    else launch_bwd<bf16_t, 1>(grad_out, arg, seg_ptr, perm, row_ptr, seg_of_item, grad_rows, R, C, reduce, s);
+  }
+  DVA_CHECK_LAUNCH();
+  return DVA_OK;
+}
+
+}  // extern "C"

@@ -226,6 +226,17 @@ class BimodalCSRPool(nn.Module, _SaveLast):
                     and ops.gather_segment_max_applicable(x_mod, csr_idx)):
                 # VIEW-level max pool of lazily gathered values: the same fused kernel, a plain [N, C] tensor out
                 return ops.gather_segment_max(x_mod, csr_idx).rows
+            if (x_map is None and self._mode != 'max' and not self.save_last
+                    and csr_idx.shape[0] - 1 < x_mod.shape[0]
+                    and ops.gather_segment_reduce_applicable(x_mod, csr_idx, self._mode)):
+                # ATOMIC mean / sum / min pool of a NON-exact mapping: gather and reduction in one kernel, forward and
+                # backward without a [P, C] tensor; the pooled [V, C] rows stay lazy at the VIEW level like the max pool's
+                return ops.gather_segment_reduce(x_mod, csr_idx, self._mode, level='atom')
+            if (x_map is not None and self._mode != 'max' and not self.save_last
+                    and ops.gather_segment_reduce_applicable(x_mod, csr_idx, self._mode)):
+                # VIEW-level mean / sum / min pool of lazily gathered values (the view pooling of the image-only models
+                # and of the mean-pool baselines): the same kernels, a plain [N, C] tensor out
+                return ops.gather_segment_reduce(x_mod, csr_idx, self._mode, level='view')
             x_mod = x_mod.materialize()
         x_pool = segment_csr(x_mod, csr_idx, reduce=self._mode)
         self._save(x_map, x_mod, csr_idx)

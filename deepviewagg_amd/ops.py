@@ -11,6 +11,7 @@ ops; names and argument meaning follow the reference call site
 ``view_attention``         pooling.py:284-300 / :514-530 (softmax + weighted sum + gating)
 ``gather_nearest``         core/multimodal/image.py:1285 (``x[feature_map_indexing]``)
 ``gather_bilinear``        core/multimodal/image.py:105-170 (``sparse_interpolation``)
+``gather_segment_reduce``  pooling.py:14-71 (``BimodalCSRPool`` mean / sum / min) on image.py:1285, without the gather
 ``grid_cluster``           core/data_transform/grid_transform.py:143-148 (grid_cluster / voxel_grid)
 ``grid_mean``              grid_transform.py:81 (``scatter_mean``)
 ``grid_majority``          grid_transform.py:76-79 (one_hot + ``scatter_add`` + argmax)
@@ -1069,6 +1070,93 @@ def gather_segment_max(x_mod, atom_ptr):
     the max --, then the recompute chain).  Reference: modules/multimodal/modules.py:400-407, pooling.py:14-71."""
     atom_ptr = _check_ptr(atom_ptr)
     xv = _GatherSegmentMax.apply(x_mod.rows, x_mod.row_idx.contiguous(), atom_ptr, x_mod.plan)
+    V = xv.shape[0]
+    ident = torch.arange(V + 1, dtype=torch.int32, device=xv.device)
+    return GatheredFeatures(xv, ident[:V], torch.ones(V, dtype=torch.int32, device=xv.device), True, (ident[:V], ident))
+
+
+class _GatherSegmentReduce(torch.autograd.Function):
+    """``segment_csr(rows[row_idx], csr_idx, reduce)`` for mean / sum / min without the [P, C] tensor, forward and backward
+    (csrc/gather_reduce.hip).  ``plan`` = the ``(perm, row_ptr)`` row plan of the items, or None / a split plan: the
+    permutation is then built in backward."""
+
+    @staticmethod
+    def forward(ctx, rows, row_idx, csr_idx, plan, reduce):
+        lib = _lib.load()
+        require_device(rows, row_idx, csr_idx)
+        rows = rows.contiguous()
+        (R, C), S, P = rows.shape, csr_idx.shape[0] - 1, row_idx.shape[0]
+        code = _lib.REDUCE_CODE[reduce]
+        out = torch.empty((S, C), dtype=rows.dtype, device=rows.device)
+        arg = torch.empty((S, C), dtype=torch.int16, device=rows.device) if code == _lib.DVA_MIN else None
+        es = rows.element_size()
+        with _timed("gather_segment_reduce_fwd", P * (4 + C * es) + S * (8 + C * es) + (S * C * 2 if arg is not None else 0)):
+            check(lib.dva_gather_segment_reduce_fwd(ptr(rows), ptr(row_idx), ptr(csr_idx), ptr(out), ptr(arg), S, P, R, C,
+                                                    dtype_code(rows), code, stream_of(rows)),
+                  "dva_gather_segment_reduce_fwd")
+        ctx.save_for_backward(row_idx, csr_idx, arg if arg is not None else csr_idx)
+        ctx.meta = (R, C, rows.dtype, code, arg is not None)
+        ctx.plan = plan
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = _lib.load()
+        row_idx, csr_idx, arg = ctx.saved_tensors
+        R, C, dt, code, has_arg = ctx.meta
+        S, P = csr_idx.shape[0] - 1, row_idx.shape[0]
+        if P == 0 or R == 0 or C == 0:
+            return torch.zeros((R, C), dtype=dt, device=gout.device), None, None, None, None
+        gout = gout.contiguous().to(dt)
+        plan = ctx.plan
+        if plan is None or isinstance(plan, SplitPlan):
+            plan = row_plan(row_idx, R, with_counts=False, split=False)[0]
+        perm, row_ptr = plan
+        soi = csr_expand(csr_idx, P)
+        grows = torch.empty((R, C), dtype=dt, device=gout.device)
+        es = gout.element_size()
+        per_item = 8 + C * es + (0 if code == _lib.DVA_SUM else 8) + (2 * C if has_arg else 0)
+        with _timed("gather_segment_reduce_bwd", P * per_item + R * (4 + C * es)):
+            check(lib.dva_gather_segment_reduce_bwd(ptr(gout), ptr(arg) if has_arg else None, ptr(csr_idx), ptr(perm),
+                                                    ptr(row_ptr), ptr(soi), ptr(grows), S, P, R, C, dtype_code(gout), code,
+                                                    stream_of(gout)), "dva_gather_segment_reduce_bwd")
+        return grows, None, None, None, None
+
+
+# A/B and tests: False sends mean / sum / min pools of lazily gathered features down the materialised route
+# (``x_mod.materialize()`` + ``segment_csr``)
+LAZY_REDUCE = True
+_LAZY_REDUCES = ("mean", "sum", "min")
+
+
+def gather_segment_reduce_applicable(x_mod, csr_idx, reduce):
+    """Does ``gather_segment_reduce`` serve this pool?  Nearest-gathered features on the device in fp32 / bf16 / fp16, any
+    C >= 1 (rows that are not 16-byte aligned or whose C is no multiple of 16 bytes take the kernels' element path;
+    non-contiguous rows are copied by the op); ``min`` keeps uint16 arg offsets, so its segments own <= 65534 items."""
+    if not (LAZY_REDUCE and isinstance(x_mod, GatheredFeatures) and reduce in _LAZY_REDUCES):
+        return False
+    rows = x_mod.rows
+    if not (rows.is_cuda and csr_idx.is_cuda and rows.dim() == 2 and rows.shape[1] >= 1
+            and rows.dtype in (torch.float32, torch.bfloat16, torch.float16)
+            and max(rows.shape[0], x_mod.row_idx.shape[0], csr_idx.shape[0]) < (1 << 31)):
+        return False
+    return reduce != "min" or _atoms_per_view_ok(csr_idx)
+
+
+def gather_segment_reduce(x_mod, csr_idx, reduce, level="view"):
+    """Mean / sum / min pool of lazily gathered features over CSR segments, gather and reduction in one kernel (reference:
+    ``BimodalCSRPool(mode)`` on ``x[idx]``, modules/multimodal/pooling.py:14-71).  ``level='view'``: the plain [N, C]
+    tensor of a view pooling.  ``level='atom'`` (atomic pool of a non-exact mapping, modules.py:400-407): the pooled
+    [V, C] rows as ``GatheredFeatures`` under the identity gather, as ``gather_segment_max`` returns them, so that the
+    view pooling behind it keeps its fused path."""
+    if reduce not in _LAZY_REDUCES:
+        raise ValueError(f"gather_segment_reduce reduces by one of {_LAZY_REDUCES}, got '{reduce}'")
+    if level not in ("view", "atom"):
+        raise ValueError(f"level must be 'view' or 'atom', got '{level}'")
+    csr_idx = _check_ptr(csr_idx)
+    xv = _GatherSegmentReduce.apply(x_mod.rows, x_mod.row_idx.contiguous(), csr_idx, x_mod.plan, reduce)
+    if level == "view":
+        return xv
     V = xv.shape[0]
     ident = torch.arange(V + 1, dtype=torch.int32, device=xv.device)
     return GatheredFeatures(xv, ident[:V], torch.ones(V, dtype=torch.int32, device=xv.device), True, (ident[:V], ident))

@@ -15,7 +15,7 @@
  * of "feature" buffers (void*): fp32, bf16 or fp16; scores / mapping features / statistics are fp32.
  * DVA_F16 (torch.float16, autocast(float16)) is accepted by: dva_segment_csr_fwd / _bwd, dva_gather_csr,
  * dva_gather_nearest_fwd / _bwd, dva_gather_bilinear_fwd / _bwd, dva_gather_rows_sum, dva_gather_segment_max_fwd /
- * _bwd, dva_view_attention_*, dva_view_gather_attention_*, dva_view_gather_rows_grad,
+ * _bwd, dva_gather_segment_reduce_fwd / _bwd, dva_view_attention_*, dva_view_gather_attention_*, dva_view_gather_rows_grad,
  * dva_view_gather_rows_grad_rec16_to, dva_rowbn_*, dva_chain_attn_fwd_dt, dva_chain_attn_bwd_dt and
  * dva_plan_split_rows_grad (dtype = out_dtype = DVA_F16).  Every other entry with a dtype argument returns
  * DVA_ERR_UNSUPPORTED for it before launching anything.
@@ -139,6 +139,28 @@ int dva_gather_segment_max_fwd(const void* rows, const int32_t* row_idx, const i
 int dva_gather_segment_max_bwd(const void* grad_out, const void* arg, const int32_t* row_idx, const int64_t* atom_ptr,
                                const int32_t* perm, const int32_t* row_ptr, const int32_t* view_of_atom, float* grad_rows,
                                int64_t n_views, int64_t n_atoms, int64_t n_rows, int32_t C, int32_t dtype, void* stream);
+
+/* The same nearest gather fused with the MEAN / SUM / MIN pool behind it (BimodalCSRPool(mode), pooling.py:14-71; at the
+ * atomic level of a non-exact mapping through modules.py:400-407, at the view level as the view pooling of the image-only
+ * and the mean-pool baselines): out[s][c] = reduce over the items a in [seg_ptr[s], seg_ptr[s+1]) of rows[row_idx[a]][c]
+ * with dva_segment_csr_fwd's arithmetic (fp32 accumulation from 0 in item order, MEAN divides once by the fp32 count, one
+ * rounding to the storage type, empty segments give 0, MIN: first item on ties) -- bit for bit the materialised
+ * composition, no [P, C] tensor.  Any C >= 1, dtype fp32 / bf16 / fp16: 16-byte accesses when C % (16 / s) == 0 and rows,
+ * out and arg are 16-byte aligned, one thread per (segment, channel) otherwise.  arg (MIN only, else nullable) uint16
+ * [S][C] = offset of the winning item inside its segment (0xffff: none; segments must own <= 65534 items).
+ * _bwd: grad_rows [R][C] in the rows' dtype, WRITTEN (every element once, fp32 accumulation, one rounding) =
+ * sum over the items a on row r of grad_out[s][c] (SUM), grad_out[s][c] / count_s (MEAN, fp32 true division) or
+ * grad_out[s][c] where arg[s][c] == a - seg_ptr[s] (MIN), s = seg_of_item[a] (int32 [P], dva_csr_expand); a segmented
+ * reduction over the row plan of the items (perm int32 [P] = items sorted by map row, row_ptr int32 [R + 1], as
+ * dva_row_plan gives them), one wavefront per map row, no float atomics: deterministic.
+ * reduce = DVA_MAX and sizes of 2^31 or more return DVA_ERR_UNSUPPORTED (the max pool keeps its own entries above). */
+int dva_gather_segment_reduce_fwd(const void* rows, const int32_t* row_idx, const int64_t* seg_ptr, void* out, void* arg,
+                                  int64_t S, int64_t P, int64_t R, int32_t C, int32_t dtype, int32_t reduce,
+                                  void* stream);
+int dva_gather_segment_reduce_bwd(const void* grad_out, const void* arg, const int64_t* seg_ptr, const int32_t* perm,
+                                  const int32_t* row_ptr, const int32_t* seg_of_item, void* grad_rows, int64_t S,
+                                  int64_t P, int64_t R, int32_t C, int32_t dtype, int32_t reduce, void* stream);
+
 /* Bilinear gather with the reference's border-replicate semantics (image.py:105-170):
  * q = coord * (H, W) + 0.5 in the 1-padded map; 4 taps floor(q), floor(q+1); weights |prod(q - opposite)|.
  * coords fp32 [P,2] = (y, x) in [0,1]; the image of atom p comes from packed_idx (its x,y unused). */

@@ -1,0 +1,152 @@
+#!/usr/bin/env python
+"""Time the view-level ``BimodalCSRPool`` (mean by default) on lazily gathered features: the fused route
+(``ops.gather_segment_reduce``, csrc/gather_reduce.hip) against ``ops.LAZY_REDUCE = False`` -- the materialised route
+(``x_mod.materialize()`` + ``ops.segment_csr``) -- on the same build and device.
+
+Scenes are ``bench.make_scene`` at the benchmark's view distribution (S1: 32 views per point over 32 images of 64 x 128
+map rows; S2 with --workload S2), N = 3 x 10^5 and 2^20 points, C = 13 / 64 / 128, bf16 and fp32 maps.  One measurement
+is forward + backward of the pool (the output gradient handed in), timed with device events; the two routes alternate
+in one process after --warmup untimed rounds, and the table holds the median and [min, max] over --reps.  ``launches``
+are the device kernels of one forward + backward as the torch profiler counts them in a separate, untimed pass (None
+where the profiler is not available), ``peak_bytes`` the peak of allocated device memory above the inputs in one more
+untimed pass, ``hbm_share`` the algorithmic bytes of the fused kernels (what the pool has to move: P (4 + C s) +
+S (8 + C s) forward, P (16 + C s) + R (4 + C s) backward for the mean) over the median time, as a fraction of the
+8 TB/s HBM specification -- for both routes, so it is each route's rate on the same bytes.  The outputs of the two
+routes are compared bit for bit, the gradients by their largest difference.  One JSON line on stdout; --out writes it
+(profiles/view_pool_bench.json).
+
+Usage:  python tools/view_pool_bench.py [--reps 7] [--warmup 2] [--mode mean] [--workload S1] [--out FILE]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+POINTS = (300000, 1 << 20)
+CHANNELS = (13, 64, 128)
+DTYPES = (torch.bfloat16, torch.float32)
+VIEWS, IMAGES, H, W = 32, 32, 64, 128
+HBM_SPEC_BYTES_PER_S = 8.0e12
+
+
+def stats(ms):
+    return {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
+
+
+def algorithmic_bytes(P, S, R, C, es, mode):
+    fwd = P * (4 + C * es) + S * (8 + C * es) + (2 * S * C if mode == "min" else 0)
+    bwd = P * (8 + C * es + (0 if mode == "sum" else 8) + (2 * C if mode == "min" else 0)) + R * (4 + C * es)
+    return fwd + bwd
+
+
+def count_launches(fn):
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        fn()
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        return int(sum(e.count for e in prof.key_averages()
+                       if getattr(e, "device_type", None) is not None and "cuda" in str(e.device_type).lower()))
+    except Exception as exc:        # no tracer on this install: not measured
+        print(f"launch count not measured: {exc!r}", file=sys.stderr)
+        return None
+
+
+def peak_bytes(fn):
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    fn()
+    torch.cuda.synchronize()
+    return int(torch.cuda.max_memory_allocated() - base)
+
+
+def run_case(bench, n, C, dtype, mode, workload, reps, warmup):
+    from deepviewagg_amd import ops
+    from deepviewagg_amd.modules.multimodal import pooling as P
+    dev = torch.device("cuda", 0)
+    scene = bench.make_scene(n, VIEWS, IMAGES, C, H, W, dtype, dev, seed=4321, workload=workload)
+    x = scene["x"].requires_grad_()
+    csr, x_map = scene["csr"], scene["x_map"]
+    feats = ops.lazy_gather_nearest_mapping(x, scene["images"], scene["atom_ptr"], scene["pixels"], 1.0, exact=True)
+    V, S, R = feats.shape[0], csr.shape[0] - 1, feats.rows.shape[0]
+    w = torch.randn(S, C, device=dev).to(dtype)
+    pool = P.BimodalCSRPool(mode=mode)
+
+    def step(fused):
+        ops.LAZY_REDUCE = fused
+        try:
+            out = pool(None, feats, x_map, csr)
+            (g,) = torch.autograd.grad(out, x, grad_outputs=w)
+        finally:
+            ops.LAZY_REDUCE = True
+        return out, g
+
+    routes = {"fused": lambda: step(True), "materialised": lambda: step(False)}
+    (out_f, g_f), (out_m, g_m) = routes["fused"](), routes["materialised"]()
+    agree = {"out_equal": bool(torch.equal(out_f, out_m)),
+             "grad_max_abs_diff": float((g_f.float() - g_m.float()).abs().max()),
+             "grad_max_abs": float(g_m.float().abs().max())}
+    del out_f, g_f, out_m, g_m
+    for _ in range(warmup):
+        for fn in routes.values():
+            fn()
+    ms = {k: [] for k in routes}
+    for _ in range(reps):
+        for k, fn in routes.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[k].append(e0.elapsed_time(e1))
+    nbytes = algorithmic_bytes(V, S, R, C, x.element_size(), mode)
+    res = {"N": n, "V": V, "map_rows": R, "C": C, "dtype": str(dtype)[6:], "mode": mode, "workload": workload,
+           "plan": type(feats.plan).__name__, "algorithmic_bytes": nbytes, "agree": agree}
+    for k, fn in routes.items():
+        t = stats(ms[k])
+        res[k] = dict(t, launches=count_launches(fn), peak_bytes=peak_bytes(fn),
+                      hbm_share=round(nbytes / (t["median_ms"] * 1e-3) / HBM_SPEC_BYTES_PER_S, 4))
+    res["speedup"] = round(res["materialised"]["median_ms"] / res["fused"]["median_ms"], 3)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--mode", default="mean", choices=("mean", "sum", "min"))
+    ap.add_argument("--workload", default="S1", choices=("S1", "S2"))
+    ap.add_argument("--points", type=int, nargs="*", default=list(POINTS))
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "view_pool_bench needs a HIP device"
+    import bench
+    from deepviewagg_amd import _lib
+    result = {"tool": "view_pool_bench", "device": torch.cuda.get_device_name(0),
+              "dva_version": _lib.load().dva_version(), "kernel_sources_sha256": _lib.source_sha256(),
+              "reps": args.reps, "warmup": args.warmup,
+              "timing": "device events around forward + backward of BimodalCSRPool on lazily gathered features, the two "
+                        "routes alternating in one process; median and [min, max] over reps",
+              "hbm_spec_bytes_per_s": HBM_SPEC_BYTES_PER_S,
+              "cases": [run_case(bench, n, C, dt, args.mode, args.workload, args.reps, args.warmup)
+                        for n in args.points for C in CHANNELS for dt in DTYPES]}
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -1877,6 +1877,10 @@ int dva_emod_prep(const float* Wb, int32_t C_out, void* ops, void* stream) {
 
 #define DVA_EMOD_CHECK_SIZES()                                                                            \
   if (n_rows * (int64_t)C_out * 2 > 0xfffffff0ll || n_views * 32 > 0xfffffff0ll) return DVA_ERR_UNSUPPORTED
+// a width or a group count that is none at all is a bad argument (as in dva_emod_stats / dva_emod_bwd); a pair of valid
+// ones without kernels is DVA_ERR_UNSUPPORTED at the switch
+#define DVA_EMOD_CHECK_WIDTH()                                                                            \
+  if ((C_out != 32 && C_out != 64 && C_out != 128 && C_out != 256) || (G != 1 && G != 2 && G != 4)) return DVA_ERR_INVALID
 
 int dva_emod_stats(int32_t layer, const void* Y, const int32_t* tap_rows, const float* tap_weights, const void* tiles,
                    const int32_t* n_tiles, const void* eops, const float* bn_a, double* stats, void* z_a,
@@ -1936,6 +1940,7 @@ int dva_emod_attn_fwd(const float* x_map, const int32_t* view_point, const float
                       const void* z_a, int64_t n_points, int64_t n_views, int64_t n_rows, int32_t C_out, int32_t G,
                       int32_t scaling, float eps, void* stream) {
   if (n_views < 0 || n_points < 0) return DVA_ERR_INVALID;
+  DVA_EMOD_CHECK_WIDTH();
   if (n_views == 0) return DVA_OK;
   if (!x_map || !view_point || !u || !tiles || !n_tiles || !ops || !bn1 || !bn2 || !bn5 || !bn6 || !score_bias ||
       !eops || !bn_a || !bn_b || !ptr || !out || ((gate_w == nullptr) != (gate_b == nullptr)))
@@ -1983,6 +1988,7 @@ int dva_emod_attn_bwd(const float* scores, const int32_t* view_point, const void
                       float* grad_gate_wb, double* stats_b, const void* z_a, int64_t n_points, int64_t n_views,
                       int64_t n_rows, int32_t C_out, int32_t G, int32_t scaling, float eps, void* stream) {
   if (n_views < 0 || n_points < 0) return DVA_ERR_INVALID;
+  DVA_EMOD_CHECK_WIDTH();
   if (n_views == 0) return DVA_OK;
   if (!scores || !view_point || !tiles || !n_tiles || !z_a || !eops || !bn_a || !bn_b ||
       !ptr || !grad_out || !out || !grad_scores || !view_rec || !stats_b ||

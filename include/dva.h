@@ -622,6 +622,8 @@ int dva_chain_attn_fwd_dt(const float* x_map, const int32_t* view_point, const f
  * layer's output is under autocast in the reference).  Train mode: written by dva_emod_stats(layer 1), read by every
  * later pass of the step instead of the four taps of Y (those passes ignore Y / tap_rows / tap_weights, which may be
  * NULL).  Eval mode: dva_emod_attn_fwd with z_a = NULL evaluates the taps itself.
+ * A C_out outside {32, 64, 128, 256} or a G outside {1, 2, 4} is DVA_ERR_INVALID; a pair of valid ones without kernels
+ * (C_out = 256 with G != 4) and a stage a width does not have are DVA_ERR_UNSUPPORTED.  Both return before any launch.
  * ------------------------------------------------------------------------------------------ */
 /* eops: 2 * (C_out / 32)^2 * 2 KiB: Linear_b's weight W_b fp32 [C_out][C_out] as bf16 matrix-core operands
  * (forward blocks, then the transposed blocks of the input gradient). */

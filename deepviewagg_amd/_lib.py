@@ -246,6 +246,10 @@ SIGNATURES = {
     "dva_image_window_workspace_bytes": (ctypes.c_int64, [_i64]),
     "dva_image_window_u8": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32,
                                            _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "dva_image_resample_workspace_bytes": (ctypes.c_int64, [_i64, _i64, _i64]),
+    "dva_image_resample_u8": (ctypes.c_int, [_vp] + [_i64] * 7 + [_vp] + [_i64] * 6 + [_i32, _vp, _vp, _i64, _i64, _i32, _vp,
+                                             _vp, _i32, _i32, _i32, _vp]),
+    "dva_image_nonstatic_mask": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
     "dva_cloud_augment_workspace_bytes": (ctypes.c_int64, [_i64, _i32]),
     "dva_cloud_augment_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "dva_lovasz_tile": (ctypes.c_int, []),

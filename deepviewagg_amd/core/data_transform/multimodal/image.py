@@ -633,8 +633,10 @@ class ToFloatImage(ImageTransform):
 # ---- the radiometric tail of the chains (reference :64-68, :1235-1282) -----------------------------------------
 # The reference's ColorJitter and Normalize wrap torchvision.transforms 0.8.2 objects.  torchvision is no dependency
 # here and no fixture of it exists, so parity with it is unpinned: the arithmetic documented at ``ops.image_tail``,
-# restated from torchvision 0.8.2's ColorJitter.forward and functional_tensor, is the contract.  Hue, GaussianBlur
-# (no shipped config uses it), LoadImages and NonStaticMask are not provided.
+# restated from torchvision 0.8.2's ColorJitter.forward and functional_tensor, is the contract.  Hue and GaussianBlur
+# (no shipped config uses it) are not provided.  LoadImages and NonStaticMask (:71-159) decode on the host and do the
+# pixel arithmetic -- Pillow's 8-bit bicubic resample, roll, crop, comparison -- on the device (``ops.read_images_u8``,
+# ``ops.image_nonstatic_mask``), bit for bit.
 
 class ToImageData(ImageTransform):
     """Wrap a ``SameSettingImageData`` into an ``ImageData`` of one setting (:64-68)."""
@@ -642,6 +644,68 @@ class ToImageData(ImageTransform):
     def _process(self, data, images):
         from ...multimodal.image import ImageData
         return data, ImageData([images])
+
+
+class LoadImages(ImageTransform):
+    """Load the images of ``path`` into ``x`` (:71-103).  The resizing and cropping state of the
+    ``SameSettingImageData`` is edited first where an argument is given; the images are then loaded with respect to
+    that state (``SameSettingImageData.load``)."""
+
+    def __init__(self, ref_size=None, crop_size=None, crop_offsets=None, downscale=None, show_progress=False):
+        self.ref_size = ref_size
+        self.crop_size = crop_size
+        self.crop_offsets = crop_offsets
+        self.downscale = downscale
+        self.show_progress = show_progress
+
+    def _process(self, data, images):
+        if self.ref_size is not None:
+            images.ref_size = self.ref_size
+        if self.crop_size is not None:
+            images.crop_size = self.crop_size
+        if self.crop_offsets is not None:
+            images.crop_offsets = self.crop_offsets
+        if self.downscale is not None:
+            images.downscale = self.downscale
+        if self.show_progress:
+            print("    LoadImages...")
+        images.load(show_progress=self.show_progress)
+        return data, images
+
+
+class NonStaticMask(ImageTransform):
+    """Find the mask of the pixels that are not identical across a sample of the images (:106-159) and save it in the
+    ``mask`` of the ``SameSettingImageData``, for ``MapImages`` to use.  The draw is the reference's, on the host
+    default generator: ``torch.multinomial(torch.arange(num_views, dtype=torch.float), n_sample)`` (view 0 has weight 0),
+    the first drawn view the one the others are compared with; fewer than two views to sample give the all-ones mask
+    and draw nothing.  The ``n_sample`` images are read in ONE ``read_images`` call at ``proj_size``; on a GPU the
+    comparison is one launch (``ops.image_nonstatic_mask``), on the host the reference's loop."""
+
+    def __init__(self, ref_size=None, proj_upscale=None, n_sample=5):
+        self.ref_size = tuple(ref_size)
+        self.proj_upscale = proj_upscale
+        self.n_sample = n_sample
+
+    def _process(self, data, images):
+        if self.ref_size is not None:
+            images.ref_size = self.ref_size
+        if self.proj_upscale is not None:
+            images.proj_upscale = self.proj_upscale
+        n_sample = min(self.n_sample, images.num_views)
+        if n_sample < 2:
+            mask = torch.ones(images.proj_size, dtype=torch.bool)
+        else:
+            idx = torch.multinomial(torch.arange(images.num_views, dtype=torch.float), n_sample)
+            views = images.read_images(idx=idx, size=images.proj_size)
+            if views.is_cuda:
+                from .... import ops
+                mask = ops.image_nonstatic_mask(views)
+            else:
+                mask = torch.zeros(images.proj_size, dtype=torch.bool)
+                for other in views[1:]:
+                    mask |= (views[0] != other).all(dim=0).t()
+        images.mask = mask
+        return data, images
 
 
 class ColorJitter(ImageTransform):

@@ -7,9 +7,11 @@ poke (SURVEY.md §8b seam 3): ``pointers``, ``values[0]`` images, ``values[1]`` 
 ``values[2]`` features, ``is_index_value=[True, False, False]``.
 
 Sorting / unique go through the HIP lex kernels (``utils.multimodal``), per-view feature means through
-``ops.segment_csr``; what remains is index arithmetic in torch on the device.  File / PIL loading
-(``load``, ``read_images``) and the interactive visualisation helpers of the reference are outside the hot
-path and not provided.
+``ops.segment_csr``; what remains is index arithmetic in torch on the device.  Loading (``load``,
+``read_images``, :973-1101) decodes the files on the host (``decode_image``) and does the rest -- Pillow's 8-bit
+bicubic resample, roll, crop -- on the device, bit for bit (``ops.read_images_u8``); the reference's PIL composition
+stays as the host route.  The interactive visualisation helpers of the reference are outside the hot path and not
+provided.
 """
 import copy
 from typing import List
@@ -553,6 +555,58 @@ class ImageMappingBatch(ImageMapping, CSRBatch):
 
 
 # ------------------------------------------------------------------------------------------------
+# Decoding image files (the one step of loading that stays on the host)
+# ------------------------------------------------------------------------------------------------
+
+def decode_image(path):
+    """One image file as a uint8 array ``[H, W, 3]``: ``PIL.Image.open(path).convert('RGB')`` (PIL is imported here, when
+    the first file is decoded), or ``numpy.load`` for a path ending in ``.npy``.  ``read_images`` looks this name up in
+    the module at every call, so a replacement decoder is one assignment."""
+    path = str(path)
+    if path.endswith('.npy'):
+        a = np.load(path)
+    else:
+        from PIL import Image
+        with Image.open(path) as im:
+            a = np.asarray(im.convert('RGB'))
+    if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8:
+        raise ValueError(f"decode_image: expected a uint8 [H, W, 3] image at {path}, got {a.dtype} {a.shape}")
+    return a
+
+
+def _read_images_pil(sources, size, rollings, crop_size, crop_offsets, downscale):
+    """The reference's serial PIL loop over decoded images (image.py:1059-1101): resize, roll, crop or box resize,
+    stack.  The host fallback of ``read_images`` and the yardstick of its device route."""
+    from PIL import Image
+    images = [Image.fromarray(np.ascontiguousarray(a)).resize(size) for a in sources]
+
+    def pil_roll(image, delta):
+        xsize, ysize = image.size
+        delta = delta % xsize
+        if delta == 0:
+            return image
+        part1 = image.crop((0, 0, delta, ysize))
+        part2 = image.crop((delta, 0, xsize, ysize))
+        part1.load()
+        part2.load()
+        image.paste(part2, (0, 0, xsize - delta, ysize))
+        image.paste(part1, (xsize - delta, 0, xsize, ysize))
+        return image
+    images = [pil_roll(im, r.item()) for im, r in zip(images, rollings)]
+    w, h = crop_size
+    if downscale is None:
+        images = [im.crop((left, top, left + w, top + h)) for im, (left, top) in zip(images, np.asarray(crop_offsets))]
+    else:
+        end_size = tuple(int(v / downscale) for v in crop_size)
+        images = [im.resize(end_size, box=(left, top, left + w, top + h))
+                  for im, (left, top) in zip(images, np.asarray(crop_offsets))]
+    if not images:
+        end = crop_size if downscale is None else tuple(int(v / downscale) for v in crop_size)
+        return torch.empty((0, 3, end[1], end[0]), dtype=torch.uint8)
+    return torch.from_numpy(np.stack([np.asarray(im) for im in images])).permute(0, 3, 1, 2)
+
+
+# ------------------------------------------------------------------------------------------------
 # SameSettingImageData
 # ------------------------------------------------------------------------------------------------
 
@@ -689,6 +743,19 @@ class SameSettingImageData:
     def crop_size(self):
         return self._crop_size
 
+    @crop_size.setter
+    def crop_size(self, crop_size):
+        """Reference image.py:640-654: only before ``x`` and ``mappings`` exist (``update_cropping`` afterwards)."""
+        crop_size = tuple(crop_size)
+        if self.crop_size == crop_size:
+            return
+        assert self.x is None and self.mappings is None, \
+            "Can't directly edit 'crop_size' if 'x' or 'mappings' are not both None. Consider using 'update_cropping'."
+        assert len(crop_size) == 2, f"Expected len(crop_size)=2 but got {len(crop_size)} instead."
+        assert crop_size[0] <= self.ref_size[0] and crop_size[1] <= self.ref_size[1], \
+            f"Expected size smaller than {self.ref_size} but got {crop_size} instead."
+        self._crop_size = crop_size
+
     @property
     def mapping_size(self):
         return self.crop_size
@@ -696,6 +763,19 @@ class SameSettingImageData:
     @property
     def crop_offsets(self):
         return self._crop_offsets
+
+    @crop_offsets.setter
+    def crop_offsets(self, crop_offsets):
+        """Reference image.py:673-686 (the pinhole intrinsics are left as they are, as by this class's ``ref_size``)."""
+        assert (self.x is None and self.mappings is None) \
+            or bool((self.crop_offsets == crop_offsets.to(self.device)).all()), \
+            "Can't directly edit 'crop_offsets' if 'x' or 'mappings' are not both None. Consider using " \
+            "'update_cropping'."
+        assert crop_offsets.dtype == torch.int64, \
+            f"Expected dtype=torch.int64 but got dtype={crop_offsets.dtype} instead."
+        assert tuple(crop_offsets.shape) == (self.num_views, 2), \
+            f"Expected tensor of shape {(self.num_views, 2)} but got {tuple(crop_offsets.shape)} instead."
+        self._crop_offsets = crop_offsets.to(self.device)
 
     @property
     def downscale(self):
@@ -753,6 +833,103 @@ class SameSettingImageData:
                 f"Expected mask of size {self.proj_size} but got {tuple(mask.shape)} instead."
             mask = mask.to(self.device)
         self._mask = mask
+
+    # -- loading the pixels
+    LOAD_ON_DEVICE = True
+
+    def load(self, show_progress=False):
+        """Load the images of ``path`` into ``x`` (reference image.py:973-989): uint8 ``[N, 3, H, W]`` with
+        ``(W, H) = img_size``, read in the order of ``path``, resized to ``ref_size``, rolled with ``rollings``, cropped
+        with ``crop_size`` / ``crop_offsets`` and subsampled by ``downscale``."""
+        x = self.read_images(size=self.ref_size, rollings=self.rollings, crop_size=self.crop_size,
+                             crop_offsets=self.crop_offsets, downscale=self.downscale, show_progress=show_progress)
+        if getattr(self, 'is_deferred', False):
+            self._end_deferral()
+        self._x = x.to(self.device)               # as the reference: not through the setter, 'downscale' stands
+        return self
+
+    def read_images(self, idx=None, size=None, rollings=None, crop_size=None, crop_offsets=None, downscale=None,
+                    show_progress=False, device=None):
+        """Read images and batch them into a uint8 tensor ``[B, 3, H, W]`` (reference image.py:991-1101): the images
+        ``idx`` of ``path`` are decoded (``decode_image``), resized to ``size`` (default ``img_size``) as
+        ``PIL.Image.resize`` does, rolled with ``rollings``, and cropped with ``crop_size`` / ``crop_offsets`` or, with
+        ``downscale``, resized from that box to ``crop_size / downscale``.
+
+        On a GPU (``device``, default the object's own, with ``LOAD_ON_DEVICE``) only the decode runs on the host:
+        sources of equal size go up as one batch each and ``ops.read_images_u8`` does the pixel arithmetic, bit for
+        bit Pillow's; the result stays on that device.  Otherwise the reference's PIL composition runs on the host
+        and the result is a host tensor, as there."""
+        if idx is None:
+            idx = np.arange(self.num_views)
+        elif isinstance(idx, int):
+            idx = np.array([idx])
+        elif isinstance(idx, torch.Tensor):
+            idx = np.asarray(idx.cpu())
+        elif isinstance(idx, slice):
+            idx = np.arange(self.num_views)[idx]
+        idx = np.asarray(idx)
+        if len(idx.shape) < 1:
+            idx = np.array([idx])
+        n = idx.shape[0]
+        if size is None:
+            size = self.img_size
+        size = tuple(int(v) for v in size)
+        if rollings is not None:
+            assert rollings.dtype == torch.int64, f"Expected dtype=torch.int64 but got dtype={rollings.dtype} instead."
+            assert rollings.shape[0] == n, f"Expected tensor of shape {n} but got {rollings.shape[0]} instead."
+        else:
+            rollings = torch.zeros(n, dtype=torch.int64)
+        assert bool(crop_size) == bool(crop_offsets is not None), \
+            "If either 'crop_size' or 'crop_offsets' is specified, both must be specified."
+        if crop_size is not None:
+            crop_size = tuple(int(v) for v in crop_size)
+            assert len(crop_size) == 2, f"Expected len(crop_size)=2 but got {len(crop_size)} instead."
+            assert all(a <= b for a, b in zip(crop_size, size)), \
+                f"Expected crop_size to be smaller than size but got size={size} and crop_size={crop_size} instead."
+            assert crop_offsets.dtype == torch.int64, \
+                f"Expected dtype=torch.int64 but got dtype={crop_offsets.dtype} instead."
+            assert tuple(crop_offsets.shape) == (n, 2), \
+                f"Expected tensor of shape {(n, 2)} but got {tuple(crop_offsets.shape)} instead."
+        else:
+            crop_size = size
+            crop_offsets = torch.zeros((n, 2), dtype=torch.int64)
+        if downscale is not None:
+            assert downscale >= 1, f"Expected scalar larger than 1 but got {downscale} instead."
+        rollings, crop_offsets = rollings.cpu(), crop_offsets.cpu()
+
+        paths = self.path[idx]
+        if show_progress:
+            try:
+                from tqdm.auto import tqdm
+                paths = tqdm(paths)
+            except ImportError:
+                pass
+        sources = [decode_image(p) for p in paths]
+
+        device = torch.device(device) if device is not None else self.device
+        if device.type == 'cuda' and self.LOAD_ON_DEVICE:
+            return self._read_images_device(sources, device, size, rollings, crop_size, crop_offsets, downscale)
+        return _read_images_pil(sources, size, rollings, crop_size, crop_offsets, downscale)
+
+    @staticmethod
+    def _read_images_device(sources, device, size, rollings, crop_size, crop_offsets, downscale):
+        """One upload and one ``ops.read_images_u8`` per distinct source size, the results placed in ``idx`` order."""
+        groups = {}
+        for i, a in enumerate(sources):
+            groups.setdefault(a.shape, []).append(i)
+        parts = []
+        for members in groups.values():
+            batch = torch.from_numpy(np.stack([sources[i] for i in members])).to(device)
+            parts.append(ops.read_images_u8(batch, size, rollings[members], crop_size, crop_offsets[members], downscale))
+        if len(parts) == 1:
+            return parts[0]
+        if not parts:
+            return ops.read_images_u8(torch.empty((0, 1, 1, 3), dtype=torch.uint8, device=device), size, rollings,
+                                      crop_size, crop_offsets, downscale)
+        out = torch.empty((len(sources),) + tuple(parts[0].shape[1:]), dtype=torch.uint8, device=device)
+        for members, part in zip(groups.values(), parts):
+            out[torch.as_tensor(members, device=device)] = part
+        return out
 
     def select_points(self, idx, mode='pick'):
         """Reference image.py:826-907: 'pick' also drops the images no selected point sees."""
@@ -1203,6 +1380,11 @@ class ImageData:
     def select_views(self, view_mask_list):
         assert isinstance(view_mask_list, list), "Expected a list of view masks."
         return self.__class__([im.select_views(m) for im, m in zip(self, view_mask_list)])
+
+    def load(self):
+        """Load the images of every setting (reference image.py:1502-1504)."""
+        self._list = [im.load() for im in self]
+        return self
 
     def clone(self):
         return self.__class__([im.clone() for im in self])

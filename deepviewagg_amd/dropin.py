@@ -18,7 +18,9 @@ its ``_compute_metrics`` becomes ``deepviewagg_amd.metrics.segmentation_tracker.
 ``torch_points3d.models.segmentation.multimodal.no3d`` is loaded or can be imported, ``No3D.forward`` becomes
 ``deepviewagg_amd.models.no3d.forward`` (nearest-seen fill and view-level loss on the device).  The image transforms
 of the data configs resolve on ``torch_points3d.core.data_transform.multimodal.image``, which is aliased whole: with
-``ColorJitter``, ``Normalize`` and ``ToImageData`` every per-sample image transform the shipped chains name is there, next
+``ColorJitter``, ``Normalize`` and ``ToImageData`` every per-sample image transform the shipped chains name is there, and
+with ``LoadImages`` and ``NonStaticMask`` (decode on the host, Pillow's resample, roll, crop and the mask comparison on
+the device) every image ``pre_transform`` the shipped multimodal data configs name as well; they stand next
 to ``FusedImageTail`` and ``fuse_image_tail`` (one pass for the tail of a chain) and to ``DeferImages`` and
 ``defer_image_windows`` (image selection, roll and crop deferred into that pass; the deferred setting is
 ``WindowedSameSettingImageData`` / ``SameSettingImageData.windowed()`` in ``core.multimodal.image``).  ``install()`` either patches an importable

@@ -21,6 +21,9 @@ ops; names and argument meaning follow the reference call site
 ``elastic_distortion``     grid_transform.py:218-243 (one level of ElasticDistortion)
 ``image_tail``             core/data_transform/multimodal/image.py:1195-1282 (ColorJitter, flip, ToFloatImage, Normalize)
 ``image_window``           the same tail over deferred windows: core/multimodal/image.py:578-722 (rolls, crops) folded in
+``image_resample``         PIL ``Image.resize`` (8-bit BICUBIC) of decoded RGB batches, as core/multimodal/image.py:1061,1093 call it
+``read_images_u8``         core/multimodal/image.py:1059-1099 (resize, roll, crop or box resize) after the decode
+``image_nonstatic_mask``   core/data_transform/multimodal/image.py:139-154 (NonStaticMask's comparison)
 ``cloud_augment``          core/data_transform/transforms.py:463-563, features.py:30-81 (noise, rotation, scale, symmetry, centre)
 ``log_softmax_nll``        models/segmentation/sparseconv3d.py:45-51 (``F.log_softmax`` + ``F.nll_loss``)
 ``lovasz_softmax_flat``    metrics/lovasz_loss.py:174-215 (``flatten_probas`` + ``lovasz_softmax_flat``)
@@ -32,6 +35,7 @@ ops; names and argument meaning follow the reference call site
 All ops require tensors on a HIP device and raise otherwise (no CPU fallback).
 """
 import collections
+import ctypes
 import os
 
 import threading
@@ -2955,6 +2959,288 @@ def image_window(src, index, rollings=None, offsets=None, size=None, jitter=(), 
                                       factors, len(names), int(bool(flip)), int(bool(to_float)), mean_c, std_c, ptr(out),
                                       ptr(ws), ws_bytes, stream_of(src)), "dva_image_window_u8")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# loading images: SameSettingImageData.read_images after the decode (core/multimodal/image.py:1059-1099: PIL resize,
+# roll, crop or box resize) and NonStaticMask's comparison (core/data_transform/multimodal/image.py:130-154);
+# csrc/image_load.hip
+# ---------------------------------------------------------------------------------------------
+
+IMAGE_RESAMPLE_BITS = 22                                                              # Pillow's PRECISION_BITS
+
+
+def image_resample_tables(in_size, in0, in1, out_size):
+    """The coefficient table of one axis of Pillow's 8-bit BICUBIC resample (``Image.resize`` on an RGB image): input
+    length ``in_size``, box ``[in0, in1)``, output length ``out_size``.  Returns ``(coeffs, bounds)``: int32
+    ``[out_size, ksize]`` fixed-point weights (22 fractional bits, zero beyond a row's ``xmax``) and int32
+    ``[out_size, 2]`` rows ``(xmin, xmax)``.  Everything is float64, every operation rounded on its own, in the order of
+    the C source (include/dva.h states the expressions); the weight sum ``ww`` is the sequential one."""
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size < 1 or out_size < 1:
+        raise ValueError(f"image_resample_tables: sizes must be positive, got {in_size} -> {out_size}")
+    in0, in1 = float(in0), float(in1)
+    if not (0 <= in0 < in1 <= in_size):
+        raise ValueError(f"image_resample_tables: the box [{in0}, {in1}) does not lie in [0, {in_size}]")
+    scale = (in1 - in0) / out_size
+    filterscale = scale if scale >= 1.0 else 1.0
+    support = 2.0 * filterscale
+    ksize = int(np.ceil(support)) * 2 + 1
+    ss = 1.0 / filterscale
+    center = in0 + (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum(np.trunc(center - support + 0.5).astype(np.int64), 0)
+    xmax = np.minimum(np.trunc(center + support + 0.5).astype(np.int64), in_size) - xmin
+    x = np.arange(ksize, dtype=np.int64)[None, :]
+    arg = np.abs((((x + xmin[:, None]).astype(np.float64) - center[:, None]) + 0.5) * ss)
+    with np.errstate(invalid='ignore', over='ignore'):
+        near = ((1.5 * arg - 2.5) * arg) * arg + 1
+        far = (((arg - 5) * arg + 8) * arg - 4) * -0.5
+    w = np.where(arg < 1.0, near, np.where(arg < 2.0, far, 0.0))
+    w = np.where(x < xmax[:, None], w, 0.0)
+    ww = np.cumsum(w, axis=1)[:, -1:]                      # x = 0, 1, ... in order; the zeros beyond xmax add nothing
+    w = np.where(ww != 0.0, w / np.where(ww != 0.0, ww, 1.0), w)
+    one = float(1 << IMAGE_RESAMPLE_BITS)
+    coeffs = np.trunc(np.where(w < 0, -0.5 + w * one, 0.5 + w * one)).astype(np.int32)
+    bounds = np.stack([xmin, xmax], axis=1).astype(np.int32)
+    return coeffs, bounds
+
+
+def _image_identity_table(n):
+    """The table of a pass that copies: one tap of weight 1 at the output's own index (``(2^21 + p 2^22) >> 22 = p``)."""
+    coeffs = np.full((n, 1), 1 << IMAGE_RESAMPLE_BITS, dtype=np.int32)
+    bounds = np.stack([np.arange(n), np.ones(n, dtype=np.int64)], axis=1).astype(np.int32)
+    return coeffs, bounds
+
+
+class _ResamplePass:
+    """One launch of ``dva_image_resample_u8``: its axis, its tables (one per distinct box), the output size, and the
+    per-image table index, shifts and periods (``_lib.SIGNATURES`` / include/dva.h)."""
+
+    def __init__(self, axis, tables, table_index, out_hw, B):
+        self.axis = axis
+        self.coeffs = np.stack([t[0] for t in tables])
+        self.bounds = np.stack([t[1] for t in tables])
+        self.table_index = np.asarray(table_index, dtype=np.int32).reshape(B)
+        self.out_hw = (int(out_hw[0]), int(out_hw[1]))
+        self.shifts = np.zeros((B, 3), dtype=np.int32)
+        self.periods = [0, 0, 0]                              # out, src, other
+
+
+def _image_box_pass(axis, in_size, starts, length, out_size, out_hw, B):
+    """The pass along ``axis`` that resamples ``[start, start + length)`` of ``in_size`` pixels to ``out_size``, one
+    table per distinct start (the border clamp and the rounding of the centres differ between them)."""
+    distinct, inverse = np.unique(np.asarray(starts, dtype=np.int64), return_inverse=True)
+    tables = [image_resample_tables(in_size, int(s), int(s) + length, out_size) for s in distinct]
+    return _ResamplePass(axis, tables, inverse, out_hw, B)
+
+
+def _image_run_passes(src, passes, what):
+    """Run the passes over ``src`` uint8 ``[B, Hs, Ws, 3]``: every table, table index and shift goes up in one copy, every
+    pass but the last writes an HWC intermediate, the last writes the planar ``[B, 3, H, W]`` result."""
+    lib = _lib.load()
+    dev = src.device
+    B, h, w = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
+    Ho, Wo = passes[-1].out_hw
+    out = torch.empty((B, 3, Ho, Wo), dtype=torch.uint8, device=dev)
+    if B == 0 or Ho == 0 or Wo == 0:
+        return out
+    parts, offsets, at = [], [], 0
+    for p in passes:
+        mine = []
+        for a in (p.coeffs, p.bounds, p.table_index, p.shifts):
+            mine.append(at)
+            parts.append(np.ascontiguousarray(a, dtype=np.int32).reshape(-1))
+            at += parts[-1].size
+        offsets.append(mine)
+    plan = torch.from_numpy(np.concatenate(parts)).to(dev)
+    base = plan.data_ptr()
+    cur, strides = src, (h * w * 3, w * 3, 3, 1)
+    keep = [plan]
+    for p, (o_coeffs, o_bounds, o_index, o_shifts) in zip(passes, offsets):
+        ho, wo = p.out_hw
+        if p is passes[-1]:
+            dst, dstrides = out, (3 * ho * wo, wo, 1, ho * wo)
+        else:
+            dst, _ = _lib.workspace("dva_image_resample_workspace_bytes", dev, B, ho, wo)
+            dstrides = (ho * wo * 3, wo * 3, 3, 1)
+            keep.append(dst)
+        n_tables, rows, ksize = (int(d) for d in p.coeffs.shape)
+        taps = int(p.bounds[..., 1].max())
+        with _timed("image_resample", B * ho * wo * 3 * (1 + taps)):
+            check(lib.dva_image_resample_u8(
+                ptr(cur), B, h, w, *strides, ptr(dst), ho, wo, *dstrides, p.axis,
+                ctypes.c_void_p(base + 4 * o_coeffs), ctypes.c_void_p(base + 4 * o_bounds), n_tables, rows, ksize,
+                ctypes.c_void_p(base + 4 * o_index), ctypes.c_void_p(base + 4 * o_shifts), *p.periods,
+                stream_of(src)), f"dva_image_resample_u8 ({what})")
+        cur, strides, h, w = dst, dstrides, ho, wo
+    return out
+
+
+def _image_sources(src, what):
+    if not torch.is_tensor(src):
+        raise TypeError(f"{what}: src must be a tensor")
+    dev = require_device(src)
+    if src.dim() != 4 or src.shape[3] != 3:
+        raise ValueError(f"{what}: decoded images must be [N, H, W, 3], got {tuple(src.shape)}")
+    if src.dtype != torch.uint8:
+        raise TypeError(f"{what} takes uint8 images, got {src.dtype}")
+    if src.shape[0] > 0 and (src.shape[1] < 1 or src.shape[2] < 1):
+        raise ValueError(f"{what}: empty images {tuple(src.shape)}")
+    return src.contiguous(), dev
+
+
+def _image_size(size, what, name="size"):
+    size = tuple(int(v) for v in size)
+    if len(size) != 2 or size[0] < 1 or size[1] < 1:
+        raise ValueError(f"{what}: {name} must be a positive (W, H), got {size}")
+    return size
+
+
+def image_resample(src, size, box=None):
+    """``PIL.Image.resize(size, box=box)`` (BICUBIC, Pillow's 8-bit fixed-point resample) of a batch of decoded RGB
+    images, bit for bit: ``src`` uint8 ``[N, Hs, Ws, 3]`` on the device, ``size = (W, H)``, ``box = (left, top, right,
+    bottom)`` in source pixels (``None``: the whole image; fractions allowed, as in Pillow).  Returns uint8
+    ``[N, 3, H, W]``.  A horizontal pass into a uint8 intermediate, then a vertical pass; a pass whose axis keeps its
+    length with the box covering it is skipped, as in Pillow, and with both skipped the one launch is a copy into the
+    planar layout.  The coefficient tables are computed on the host (``image_resample_tables``) and uploaded in one
+    copy; nothing is read back."""
+    what = "ops.image_resample"
+    src, dev = _image_sources(src, what)
+    N, Hs, Ws = (int(d) for d in src.shape[:3])
+    W, H = _image_size(size, what)
+    if N == 0:
+        return torch.empty((0, 3, H, W), dtype=torch.uint8, device=dev)
+    x0, y0, x1, y1 = (0, 0, Ws, Hs) if box is None else (float(v) for v in box)
+    if x0 < 0 or y0 < 0 or x1 > Ws or y1 > Hs:
+        raise ValueError(f"{what}: box can't exceed original image size")
+    if x1 <= x0 or y1 <= y0:
+        raise ValueError(f"{what}: box can't be empty")
+    passes = []
+    if W != Ws or x0 != 0 or x1 != Ws:
+        passes.append(_ResamplePass(0, [image_resample_tables(Ws, x0, x1, W)], np.zeros(N), (Hs, W), N))
+    if H != Hs or y0 != 0 or y1 != Hs:
+        passes.append(_ResamplePass(1, [image_resample_tables(Hs, y0, y1, H)], np.zeros(N), (H, W), N))
+    if not passes:
+        passes.append(_ResamplePass(0, [_image_identity_table(W)], np.zeros(N), (H, W), N))
+    return _image_run_passes(src, passes, what)
+
+
+def _host_int64(value, shape, what, name):
+    """A per-image integer argument as a host int64 array (a device tensor is read back once, before any launch)."""
+    if torch.is_tensor(value):
+        if value.dtype != torch.int64:
+            raise TypeError(f"{what}: {name} must be int64, got {value.dtype}")
+        value = value.detach().cpu().numpy()
+    value = np.asarray(value, dtype=np.int64)
+    if value.shape != shape:
+        raise ValueError(f"{what}: {name} must have shape {shape}, got {value.shape}")
+    return value
+
+
+def read_images_u8(src, size, rollings=None, crop_size=None, crop_offsets=None, downscale=None):
+    """``SameSettingImageData.read_images`` after the decode (reference core/multimodal/image.py:1059-1099), bit for
+    bit over Pillow's BICUBIC: every image of ``src`` (uint8 ``[N, Hs, Ws, 3]`` on the device, the decoded files) is
+    resized to ``size = (W, H)``, rolled along the width (``new[x] = old[(x + rollings[i] mod W) mod W]``), and then,
+    with ``downscale`` ``None``, cropped to ``crop_size = (w, h)`` at ``crop_offsets[i] = (left, top)``, otherwise
+    resized to ``(int(w / downscale), int(h / downscale))`` from that box.  ``crop_size`` and ``crop_offsets`` come
+    together or not at all (the whole image).  Returns uint8 ``[N, 3, H', W']``.
+
+    One to four launches of the resample pass (``dva_image_resample_u8``): the passes Pillow would run, skipped under
+    Pillow's rule, with the roll and the crop folded into them as per-image shifts -- into the passes of the second
+    resize, or into the last pass of the first one when no second resize happens (then an unchanged size is one copy
+    pass).  No rolled or cropped image is written.  ``rollings`` and ``crop_offsets`` are HOST values (int64 tensors,
+    arrays or sequences): a box resize needs one coefficient table per distinct offset, computed on the host; a device
+    tensor is read back once before the first launch.  Nothing else synchronises."""
+    what = "ops.read_images_u8"
+    src, dev = _image_sources(src, what)
+    N, Hs, Ws = (int(d) for d in src.shape[:3])
+    passes, (end_h, end_w) = _read_images_plan(N, Hs, Ws, size, rollings, crop_size, crop_offsets, downscale, what)
+    if N == 0:
+        return torch.empty((0, 3, end_h, end_w), dtype=torch.uint8, device=dev)
+    return _image_run_passes(src, passes, what)
+
+
+def _read_images_plan(N, Hs, Ws, size, rollings, crop_size, crop_offsets, downscale, what="ops.read_images_u8"):
+    """The passes of ``read_images_u8`` over ``N`` sources of ``Hs x Ws`` pixels and the ``(H, W)`` of its result: host
+    work only (argument checks, tables, shifts)."""
+    W1, H1 = _image_size(size, what)
+    if bool(crop_size) != bool(crop_offsets is not None):
+        raise ValueError(f"{what}: if either 'crop_size' or 'crop_offsets' is specified, both must be specified")
+    roll = np.zeros(N, dtype=np.int64) if rollings is None else _host_int64(rollings, (N,), what, "rollings")
+    roll = roll % W1                                             # non-negative, as Python's and the reference's
+    if crop_size is not None:
+        w, h = _image_size(crop_size, what, "crop_size")
+        if w > W1 or h > H1:
+            raise ValueError(f"{what}: expected crop_size to be smaller than size but got size={(W1, H1)} and "
+                             f"crop_size={(w, h)} instead")
+        offs = _host_int64(crop_offsets, (N, 2), what, "crop_offsets")
+        if N and (offs.min() < 0 or (offs[:, 0] + w).max() > W1 or (offs[:, 1] + h).max() > H1):
+            raise ValueError(f"{what}: a crop box leaves the resized image {(W1, H1)}")
+    else:
+        w, h = W1, H1
+        offs = np.zeros((N, 2), dtype=np.int64)
+    if downscale is not None:
+        if not downscale >= 1:
+            raise ValueError(f"{what}: expected scalar larger than 1 but got {downscale} instead")
+        end_w, end_h = int(w / downscale), int(h / downscale)
+        if end_w < 1 or end_h < 1:
+            raise ValueError(f"{what}: height and width must be > 0, got {(end_w, end_h)}")
+    else:
+        end_w, end_h = w, h
+    if N == 0:
+        return [], (end_h, end_w)
+    left, top = offs[:, 0], offs[:, 1]
+
+    passes = []
+    if Ws != W1:
+        passes.append(_ResamplePass(0, [image_resample_tables(Ws, 0, Ws, W1)], np.zeros(N), (Hs, W1), N))
+    if Hs != H1:
+        passes.append(_ResamplePass(1, [image_resample_tables(Hs, 0, Hs, H1)], np.zeros(N), (H1, W1), N))
+    second_h = downscale is not None and (end_w != W1 or w != W1)     # w == W1 leaves left = 0 only
+    second_v = downscale is not None and (end_h != H1 or h != H1)
+    if second_h:
+        p = _image_box_pass(0, W1, left, w, end_w, (H1, end_w), N)
+        p.shifts[:, 1], p.periods[1] = roll, W1                      # its taps read the rolled image
+        passes.append(p)
+    if second_v:
+        p = _image_box_pass(1, H1, top, h, end_h, (end_h, end_w), N)
+        if not second_h:
+            p.shifts[:, 2], p.periods[2] = roll, W1                  # the roll runs across this pass
+        passes.append(p)
+    if not (second_h or second_v):
+        # no second resize: the window (roll, then crop) of the first one's result, read by its last pass
+        if not passes:
+            passes.append(_ResamplePass(0, [_image_identity_table(W1)], np.zeros(N), (H1, W1), N))
+        p = passes[-1]
+        if p.axis == 0:
+            p.shifts[:, 0], p.periods[0] = left + roll, W1
+            p.shifts[:, 2] = top
+        else:
+            p.shifts[:, 0] = top
+            p.shifts[:, 2], p.periods[2] = left + roll, W1
+        p.out_hw = (h, w)
+    return passes, (end_h, end_w)
+
+
+def image_nonstatic_mask(images):
+    """NonStaticMask's comparison (reference core/data_transform/multimodal/image.py:139-154) in one launch:
+    ``images`` uint8 ``[n, 3, H, W]``, image 0 the reference view; returns bool ``[W, H]`` (the reference's transposed
+    ``proj_size`` orientation) with ``mask[x, y] = any_{i >= 1} all_c images[0, c, y, x] != images[i, c, y, x]``."""
+    what = "ops.image_nonstatic_mask"
+    if not torch.is_tensor(images):
+        raise TypeError(f"{what}: images must be a tensor")
+    dev = require_device(images)
+    if images.dim() != 4 or images.shape[1] != 3 or images.shape[0] < 1:
+        raise ValueError(f"{what}: images must be [n >= 1, 3, H, W], got {tuple(images.shape)}")
+    if images.dtype != torch.uint8:
+        raise TypeError(f"{what} takes uint8 images, got {images.dtype}")
+    images = images.contiguous()
+    n, _, H, W = (int(d) for d in images.shape)
+    mask = torch.empty((W, H), dtype=torch.bool, device=dev)
+    with _timed("image_nonstatic_mask", n * 3 * H * W + H * W):
+        check(_lib.load().dva_image_nonstatic_mask(ptr(images), n, H, W, ptr(mask), stream_of(images)),
+              "dva_image_nonstatic_mask")
+    return mask
 
 
 # ---------------------------------------------------------------------------------------------

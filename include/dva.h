@@ -1114,6 +1114,57 @@ int dva_image_window_u8(const uint8_t* src, int64_t N, int64_t H, int64_t W, con
                         void* stream);
 
 /* ------------------------------------------------------------------------------------------ *
+ * Loading images (image_load.hip): the pixel arithmetic of SameSettingImageData.read_images
+ * (core/multimodal/image.py:1059-1099) and NonStaticMask (core/data_transform/multimodal/image.py:130-154) once the
+ * files are decoded.  The reference resizes with PIL.Image.resize, for RGB images Pillow's 8-bit BICUBIC resample.
+ * That arithmetic is the contract, bit for bit.  Per axis (input length inSize, box [in0, in1), output length out), in
+ * C double, every operation rounded on its own, no fused multiply-add -- computed by the HOST (ops.image_resample_tables):
+ *   scale = filterscale = (in1 - in0) / out, filterscale = max(filterscale, 1); support = 2.0 filterscale;
+ *   ksize = (int)ceil(support) * 2 + 1; for output xx: center = in0 + (xx + 0.5) scale, ss = 1.0 / filterscale,
+ *   xmin = max((int)(center - support + 0.5), 0), xmax = min((int)(center + support + 0.5), inSize) - xmin,
+ *   w[x] = bicubic((x + xmin - center + 0.5) ss) for x < xmax, divided by their sum ww (taken in that order) if ww != 0;
+ *   bicubic(x), a = -0.5, x = |x|: ((a + 2) x - (a + 3)) x x + 1 for x < 1, (((x - 5) x + 8) x - 4) a for x < 2, else 0;
+ *   k[x] = (int)(w[x] < 0 ? -0.5 + w[x] 2^22 : 0.5 + w[x] 2^22), the cast truncating toward zero.
+ * A pixel and channel, on the DEVICE: int32 s = 2^21 + sum_x in[xmin + x] k[x], out = clamp(s >> 22, 0, 255), the
+ * shift arithmetic.  A resize is a horizontal pass into a uint8 intermediate (a rounding point), then a vertical pass; a
+ * pass whose axis keeps its length with the box covering it is skipped.
+ *   dva_image_resample_u8    ONE pass along x (axis 0) or y (axis 1) over B images of 3 channels.  src and dst are
+ *                            described by BYTE strides (image, row, column, channel) and their (h, w): HWC bytes are
+ *                            (h w 3, w 3, 3, 1), a planar [B, 3, h, w] batch is (3 h w, w, 1, h w).  coeffs int32
+ *                            [n_tables, table_rows, ksize] and bounds int32 [n_tables, table_rows, 2] = (xmin, xmax),
+ *                            table_index int32 [B] (nullable: table 0) and shifts int32 [B, 3] (nullable: zeros) are
+ *                            DEVICE arrays.  With i the output index along the axis and j along the other axis:
+ *                              r      = i + shifts[b, 0]                 (mod out_period when out_period > 0)
+ *                              a(x)   = xmin[r] + x + shifts[b, 1]       (mod src_period when src_period > 0)
+ *                              o      = j + shifts[b, 2]                 (mod other_period when other_period > 0)
+ *                              dst[b, i, j, c] = clamp((2^21 + sum_{x < xmax[r]} src[b, a(x), o, c] k[r, x]) >> 22)
+ *                            with row r of table table_index[b]; every mod is non-negative.  These shifts fold the
+ *                            roll and the crop of read_images into a pass: no rolled or cropped image is written.  A
+ *                            non-zero src_period / other_period must equal the source length of its axis and
+ *                            out_period may not exceed table_rows (DVA_ERR_INVALID).  Any ksize is served (the tap loop
+ *                            runs to xmax[r]).  The device arrays cannot be validated without a synchronisation, so
+ *                            the kernel clamps the table, its row, the tap range and every source index into range:
+ *                            no access leaves src or the tables, values outside are the caller's error.  dst may not
+ *                            overlap src.  One kernel, no workspace, nothing synchronises.
+ *   dva_image_resample_workspace_bytes   the bytes of the HWC intermediate [B, H, W, 3] between two passes, padded as
+ *                            every workspace region is.
+ *   dva_image_nonstatic_mask images uint8 [n, 3, H, W] contiguous, n >= 1; mask uint8 (bool) [W, H], TRANSPOSED:
+ *                              mask[x, y] = OR_{1 <= i < n} AND_c (images[0, c, y, x] != images[i, c, y, x])
+ *                            (all zero for n = 1).  One kernel, a tiled transpose through LDS.
+ * Argument errors (null pointer, negative size, axis other than 0 / 1, no table, a stride < 1) return DVA_ERR_INVALID
+ * before any HIP call; sizes beyond int32 per axis return DVA_ERR_UNSUPPORTED; B = 0 or an empty destination is a
+ * no-op. */
+int64_t dva_image_resample_workspace_bytes(int64_t B, int64_t H, int64_t W);
+int dva_image_resample_u8(const uint8_t* src, int64_t B, int64_t src_h, int64_t src_w, int64_t src_stride_b,
+                          int64_t src_stride_y, int64_t src_stride_x, int64_t src_stride_c, uint8_t* dst, int64_t dst_h,
+                          int64_t dst_w, int64_t dst_stride_b, int64_t dst_stride_y, int64_t dst_stride_x,
+                          int64_t dst_stride_c, int32_t axis, const int32_t* coeffs, const int32_t* bounds,
+                          int64_t n_tables, int64_t table_rows, int32_t ksize, const int32_t* table_index,
+                          const int32_t* shifts, int32_t out_period, int32_t src_period, int32_t other_period,
+                          void* stream);
+int dva_image_nonstatic_mask(const uint8_t* images, int64_t n, int64_t H, int64_t W, uint8_t* mask, void* stream);
+
+/* ------------------------------------------------------------------------------------------ *
  * The positional 3D augmentations of the per-sample transform chains (cloud_augment.hip): RandomNoise, RandomRotate /
  * Random3AxisRotation, RandomScaleAnisotropic, RandomSymmetry and Center (core/data_transform/transforms.py:463-563,
  * features.py:30-81; RandomRotate and Center are torch_geometric's, of which no source or fixture exists here: for

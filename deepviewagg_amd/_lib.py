@@ -83,6 +83,18 @@ class DvaCollateItem(ctypes.Structure):
         ("point_base", _i64),
     ]
 
+
+class DvaCoverageItem(ctypes.Structure):
+    """Mirror of ``struct dva_coverage_item`` (include/dva.h): one mapping of a ``dva_mapping_coverage_step`` call."""
+    _fields_ = [
+        ("pointers", _vp),
+        ("images", _vp),
+        ("n_points", _i64),
+        ("n_views", _i64),
+        ("n_images", _i64),
+        ("image_base", _i64),
+    ]
+
 # name -> (restype, argtypes); every symbol include/dva.h declares must be listed here
 SIGNATURES = {
     "dva_version": (ctypes.c_int, []),
@@ -276,6 +288,14 @@ SIGNATURES = {
                                                _vp, _vp, _i64, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp,
                                                _vp, _vp, _vp, _i64, _vp]),
     "dva_mapping_image_stats": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _vp]),
+    "dva_mapping_center_workspace_bytes": (ctypes.c_int64, [_i64]),
+    "dva_mapping_center_rollings": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _i64,
+                                                   _vp]),
+    "dva_mapping_roll_pixels": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i64, _i64, _vp, _i64, _i64, _vp]),
+    "dva_mapping_coverage_group_items": (ctypes.c_int, []),
+    "dva_mapping_coverage_hist_images": (ctypes.c_int, []),
+    "dva_mapping_coverage_step": (ctypes.c_int, [ctypes.POINTER(DvaCoverageItem), _i64, _i64, _i64, _i64, _vp, _vp, _vp,
+                                                 _vp]),
     "dva_mapping_collate_group_items": (ctypes.c_int, []),
     "dva_mapping_collate_workspace_bytes": (ctypes.c_int64, [_i64]),
     "dva_mapping_collate": (ctypes.c_int, [ctypes.POINTER(DvaCollateItem), _i64, _i32, _i32, _i64, _i64, _i64, _vp,

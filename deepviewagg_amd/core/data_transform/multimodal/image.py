@@ -416,6 +416,8 @@ class PickImagesFromMemoryCredit(ImageTransform):
     """Cherry-pick images of an ``ImageData`` under a pixel-memory credit, optionally favouring images that
     see yet-unseen points (:765-874).  Same sequential sampling (``np.random.choice``) as the reference."""
     _PROCESS_IMAGE_DATA = True
+    # device mappings take ``ops.MappingCoverage`` for the coverage counts; False: the composition below
+    ON_DEVICE = True
 
     def __init__(self, credit=None, img_size=[], k_coverage=0, n_img=0):
         if credit is not None:
@@ -427,7 +429,72 @@ class PickImagesFromMemoryCredit(ImageTransform):
         self.use_coverage = k_coverage > 0
         self.k_coverage = k_coverage
 
+    def _coverage(self, data, images):
+        """The device coverage counts of ``images``, or None where they do not apply: the switch off, no coverage
+        weight, a host mapping, or anything the op declines."""
+        from .... import ops
+        if not (self.ON_DEVICE and self.use_coverage) or _num_nodes(data) < 1:
+            return None
+        items = []
+        for im in images:
+            mp = im.mappings
+            if mp is None or not mp.pointers.is_cuda or mp.num_groups > _num_nodes(data):
+                return None
+            items.append((mp.pointers, mp.images, im.num_views))
+        try:
+            return ops.MappingCoverage(items, _num_nodes(data))
+        except DvaError as e:
+            if e.code != -2:
+                raise
+            return None
+
     def _process(self, data, images):
+        """Same host loop, float64 weights and ``np.random.choice`` draws as the composition; the coverage counts come
+        from ``ops.MappingCoverage`` -- one launch and one read-back of ``B`` integers per picked image, the pick of
+        the iteration before as its argument -- so no ``[B, N]`` matrix exists on either side, and the final
+        selection hands its host index to ``_take_images``."""
+        import numpy as np
+        from ...multimodal.image import ImageData
+        if images.num_views == 0:
+            return data, images
+        coverage = self._coverage(data, images)
+        if coverage is None:
+            return self._process_composition(data, images)
+        # flat table of candidate images: (setting, index in setting, pixel area)
+        setting = np.concatenate([np.full(im.num_views, i) for i, im in enumerate(images)])
+        local = np.concatenate([np.arange(im.num_views) for im in images])
+        area = np.array([images[int(i)].img_size[0] * images[int(i)].img_size[1] for i in setting], dtype=np.float64)
+        credit = self.credit
+        assert credit > 0 and credit >= area.min(), \
+            f"Insufficient credit={credit} to pick any of the provided images with min_size={int(area.min())}."
+        alive = np.ones(len(setting), dtype=bool)
+        chosen = []
+        last_pick = -1                                      # the pick the next coverage step has to take in
+        while credit > 0 and alive.any():
+            alive &= area <= credit                         # images that no longer fit the remaining credit
+            cand = np.flatnonzero(alive)
+            if cand.size == 0:
+                break
+            # a step is launched here only: when this iteration really draws
+            cover = coverage.step(last_pick).cpu().numpy()[cand]      # host read: B integers
+            w_cov = self.k_coverage * cover / (cover.max() + 1)
+            weights = area[cand] / area[cand].max() + w_cov      # size weight + coverage weight (:836-850)
+            pick = cand[np.random.choice(cand.size, p=weights / weights.sum())]
+            chosen.append(pick)
+            alive[pick] = False
+            credit -= area[pick]
+            last_pick = int(pick)
+        groups = []
+        for i, im in enumerate(images):
+            mine = np.array([int(local[c]) for c in chosen if setting[c] == i], dtype=np.int64)
+            if mine.size:
+                # the index is duplicate-free by construction (``alive``): nothing to check or read back; pinned, so
+                # that its upload does not wait for the device
+                idx = torch.from_numpy(mine).pin_memory().to(im.device, non_blocking=True)
+                groups.append(im._take_images(idx, idx_np=mine))
+        return data, ImageData(groups)
+
+    def _process_composition(self, data, images):
         import numpy as np
         from ...multimodal.image import ImageData
         if images.num_views == 0:
@@ -482,12 +549,46 @@ class CenterRoll(ImageTransform):
     centre as possible (reference :962-1037): per image, the roll offset (among ``angular_res`` candidates)
     minimising span + centring distance of the mapped columns, evaluated in 8-bit angular coordinates."""
 
+    # device mappings with int16 pixels take ``ops.mapping_center_rollings`` / ``ops.roll_mapping_pixels``; False:
+    # the composition below
+    ON_DEVICE = True
+
     def __init__(self, angular_res=16):
         assert isinstance(angular_res, int)
         assert angular_res <= 256
         self.angular_res = angular_res
 
     def _process(self, data, images):
+        """One device op for the offsets, one read-back (the reference's assertion), one op for the mapped columns;
+        the pixels roll as before (a gather, or the deferred ``source_roll``)."""
+        from .... import ops
+        m = images.mappings
+        if (not self.ON_DEVICE or m is None or not m.pointers.is_cuda or m.pixels.dtype != torch.int16
+                or m.images.shape[0] == 0 or not 1 <= self.angular_res <= 256):
+            return self._process_composition(data, images)
+        name = self.__class__.__name__
+        assert images.ref_size[0] == images.img_size[0], \
+            f"{name} cannot operate if images and mappings underwent prior cropping or resizing."
+        assert images.crop_size is None or images.crop_size[0] == images.ref_size[0], \
+            f"{name} cannot operate if images and mappings underwent prior cropping or resizing."
+        assert images.downscale is None or images.downscale == 1, \
+            f"{name} cannot operate if images and mappings underwent prior cropping or resizing."
+        try:
+            rollings, info = ops.mapping_center_rollings(m.images, m.values[1].pointers, m.pixels, images.num_views,
+                                                         images.ref_size[0], self.angular_res)
+        except DvaError as e:
+            if e.code != -2:
+                raise
+            return self._process_composition(data, images)
+        empty, flags = info.tolist()                       # host read: the only one
+        if flags:
+            # image ids or columns outside their range: what the integer restatement does not cover
+            return self._process_composition(data, images)
+        assert empty == 0, "Image indices discrepancy in the rollings."
+        images.update_rollings(rollings, on_device=True)
+        return data, images
+
+    def _process_composition(self, data, images):
         from ....utils.multimodal import lexunique
         assert images.mappings is not None, "No mappings found in images."
         name = self.__class__.__name__

@@ -976,9 +976,11 @@ class SameSettingImageData:
         images.mappings = mappings
         return images
 
-    def update_rollings(self, rollings):
+    def update_rollings(self, rollings, on_device=False):
         """Roll spherical images and their mappings along the width, with respect to the reference state
-        (reference image.py:578-628).  No prior cropping along the width or resizing."""
+        (reference image.py:578-628).  No prior cropping along the width or resizing.  ``on_device``: the mapping half
+        as one in-place device op (``ops.roll_mapping_pixels``) where it applies -- a device mapping with contiguous
+        int16 pixels -- and the expression below otherwise."""
         assert self.ref_size[0] == self.img_size[0], \
             "CenterRoll cannot operate if images and mappings underwent prior cropping or resizing."
         assert self.crop_size is None or tuple(self.crop_size) == tuple(self.ref_size), \
@@ -991,11 +993,27 @@ class SameSettingImageData:
             W = self.x.shape[-1]
             src = (torch.arange(W, device=self.device).view(1, -1) - self.rollings.view(-1, 1)) % W
             self.x = torch.gather(self.x, 3, src.view(-1, 1, 1, W).expand_as(self.x))
-        if self.mappings is not None:
+        if self.mappings is not None and not (on_device and self._roll_mapping_device()):
             pix_roll = self.rollings[self.mappings.images].repeat_interleave(self.mappings._atom_sizes())
             w_pix = (self.mappings.pixels[:, 0].long() + pix_roll) % self.ref_size[0]
             self.mappings.pixels[:, 0] = w_pix.to(self.mappings.pixels.dtype)
         return self
+
+    def _roll_mapping_device(self):
+        """``update_rollings``' mapping half through ``ops.roll_mapping_pixels``; False where the op does not apply."""
+        from ..._lib import DvaError
+        m = self.mappings
+        pix = m.pixels
+        if not (pix.is_cuda and pix.dtype == torch.int16 and pix.is_contiguous() and pix.data_ptr() % 4 == 0
+                and self.ref_size[0] <= 32767):
+            return False
+        try:
+            ops.roll_mapping_pixels(m.images, m.values[1].pointers, pix, self.rollings, self.ref_size[0])
+        except DvaError as e:
+            if e.code != -2:
+                raise
+            return False
+        return True
 
     def update_cropping(self, crop_size, crop_offsets):
         """Crop ``x`` and the mappings with respect to the CURRENT ``img_size``; the stored crop state is
@@ -1256,9 +1274,9 @@ class WindowedSameSettingImageData(SameSettingImageData):
     def to(self, device):
         return self._follow(self._without_pixels(SameSettingImageData.to, device), device=device)
 
-    def update_rollings(self, rollings):
+    def update_rollings(self, rollings, on_device=False):
         deferred = self.is_deferred
-        self._without_pixels(SameSettingImageData.update_rollings, rollings)
+        self._without_pixels(SameSettingImageData.update_rollings, rollings, on_device=on_device)
         if deferred:
             self._source_roll = (self._source_roll + self.rollings) % self._source.shape[3]
         return self

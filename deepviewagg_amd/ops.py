@@ -2034,6 +2034,154 @@ def mapping_image_stats(images, atom_ptr, pixels, num_images):
 
 
 # ---------------------------------------------------------------------------------------------
+# the image picks: CenterRoll and the coverage counts of PickImagesFromMemoryCredit
+# (core/data_transform/multimodal/image.py:962-1037, :765-874)
+# ---------------------------------------------------------------------------------------------
+
+def _pick_mapping_arguments(name, images, atom_ptr, pixels):
+    if images.dtype != torch.int64 or atom_ptr.dtype != torch.int64:
+        raise _lib.DvaError(f"ops.{name}: indices are not int64: {_lib._ERRORS[-2]}", code=-2)
+    if pixels.dtype != torch.int16:
+        raise _lib.DvaError(f"ops.{name}: pixels are {pixels.dtype}, not int16: {_lib._ERRORS[-2]}", code=-2)
+    dev = require_device(images, atom_ptr, pixels)
+    v, p = images.shape[0], pixels.shape[0]
+    if images.dim() != 1 or tuple(atom_ptr.shape) != (v + 1,) or pixels.dim() != 2 or pixels.shape[1] != 2:
+        raise ValueError(f"ops.{name}: {v} views, {tuple(atom_ptr.shape)} atom pointers, pixels {tuple(pixels.shape)}")
+    return dev, v, p
+
+
+def mapping_center_rollings(images, atom_ptr, pixels, num_images, width, angular_res=16):
+    """CenterRoll's offsets (reference :999-1029) in one device operation: ``(rollings, info)``.  ``rollings`` int64
+    ``[num_images]``: per image the roll ``long(float(r) / 256 * width)`` of the first candidate ``r`` in
+    ``arange(0, 256, int(256 / angular_res))`` that minimises span + centring distance of the image's atom columns in
+    8-bit angular coordinates; 0 for an image without atoms.  ``info`` int32 ``[2]`` on the device: the number of images
+    without atoms, and flags -- bit 0 a view whose image is outside ``[0, num_images)``, bit 1 an atom column outside
+    ``[0, width)``; with a flag set the offsets leave those views / atoms out and the caller takes the composition.
+    Integer arithmetic, exactly the reference's float expressions for ``width <= 32767``; integer OR atomics only, so
+    two runs give the same bits.  No host synchronisation.  ``angular_res`` is an int in 1..256 (``ValueError``);
+    ``DvaError`` with ``code == -2`` for pixels other than int16, indices other than int64 or ``width > 32767``."""
+    lib = _lib.load()
+    if not isinstance(angular_res, int) or isinstance(angular_res, bool) or not 1 <= angular_res <= 256:
+        raise ValueError(f"ops.mapping_center_rollings: angular_res must be an int in 1..256, got {angular_res!r}")
+    dev, v, p = _pick_mapping_arguments("mapping_center_rollings", images, atom_ptr, pixels)
+    b, w = int(num_images), int(width)
+    if b < 0 or w < 1:
+        raise ValueError(f"ops.mapping_center_rollings: {b} images of width {w}")
+    if w > 32767:
+        raise _lib.DvaError(f"ops.mapping_center_rollings: width {w} above 32767: {_lib._ERRORS[-2]}", code=-2)
+    images, atom_ptr, pixels = images.contiguous(), atom_ptr.contiguous(), pixels.contiguous()
+    ws, nbytes = _lib.workspace("dva_mapping_center_workspace_bytes", dev, b)
+    rollings = torch.empty(b, dtype=torch.int64, device=dev)
+    info = torch.empty(2, dtype=torch.int32, device=dev)
+    with _timed("mapping_center_rollings", v * 16 + p * 4 + b * 72):
+        check(lib.dva_mapping_center_rollings(ptr(images), ptr(atom_ptr), ptr(pixels), 2, v, p, b, w, angular_res,
+                                              ptr(rollings), ptr(info), ptr(ws), int(nbytes), stream_of(images)),
+              "dva_mapping_center_rollings")
+    return rollings, info
+
+
+def roll_mapping_pixels(images, atom_ptr, pixels, rollings, width):
+    """The mapping half of ``update_rollings`` (reference :610-621) in one device operation, IN PLACE:
+    ``pixels[a, 0] = (pixels[a, 0] + rollings[image of a]) % width`` for every atom ``a``.  ``pixels`` is int16
+    ``[P, 2]`` and contiguous (it is written where it is, so a copy would be wrong: ``ValueError``), ``rollings`` int64
+    ``[B]``.  Returns ``pixels``.  No host synchronisation.  ``DvaError`` with ``code == -2`` for pixels other than
+    int16, indices other than int64 or ``width > 32767``."""
+    lib = _lib.load()
+    dev, v, p = _pick_mapping_arguments("roll_mapping_pixels", images, atom_ptr, pixels)
+    require_device(images, rollings)
+    if rollings.dtype != torch.int64:
+        raise _lib.DvaError(f"ops.roll_mapping_pixels: rollings are {rollings.dtype}, not int64: {_lib._ERRORS[-2]}",
+                            code=-2)
+    w = int(width)
+    if rollings.dim() != 1 or w < 1:
+        raise ValueError(f"ops.roll_mapping_pixels: rollings {tuple(rollings.shape)}, width {w}")
+    if w > 32767:
+        raise _lib.DvaError(f"ops.roll_mapping_pixels: width {w} above 32767: {_lib._ERRORS[-2]}", code=-2)
+    if not pixels.is_contiguous() or pixels.data_ptr() % 4:
+        raise ValueError("ops.roll_mapping_pixels: pixels must be contiguous and 4-byte aligned to be rolled in place")
+    images, atom_ptr, rollings = images.contiguous(), atom_ptr.contiguous(), rollings.contiguous()
+    with _timed("roll_mapping_pixels", v * 16 + p * 8):
+        check(lib.dva_mapping_roll_pixels(ptr(images), ptr(atom_ptr), ptr(pixels), 2, v, p, ptr(rollings),
+                                          rollings.shape[0], w, stream_of(images)), "dva_mapping_roll_pixels")
+    return pixels
+
+
+class MappingCoverage:
+    """The coverage counts of ``PickImagesFromMemoryCredit`` (reference :803-868) without its dense ``[B, N]``
+    matrix.  ``items`` is a list of ``(pointers, images, num_images)``, one per setting: int64 device tensors of
+    mappings over the SAME ``num_points`` points (a mapping may cover fewer).  Image ``j`` of item ``b`` has the global
+    id ``bases[b] + j``, ``bases`` the running sum of ``num_images``.
+
+    ``step(pick)`` marks the points that global image ``pick`` sees as covered (``pick = -1``: none) and returns
+    ``counts`` int64 ``[total images]`` on the device, ``counts[i] = |{p : image i sees p, no picked image sees p}|``:
+    the row sums of the reference's ``unseen`` after ``unseen &= ~unseen[pick]`` for every pick so far.  One launch per
+    32 items, which also clears the row of the next step; integer atomics only (an LDS histogram per workgroup up to
+    ``hist_images()`` images in all, global atomics above), so the counts are exact and order-free.  No host
+    synchronisation; the tensor a step returns is valid until the step after the next.
+
+    PRECONDITION: a view is a distinct (point, image) pair, as in every ``ImageMapping`` the library builds
+    (``from_dense`` unites repeated pairs); a repeated pair would count twice.
+
+    State: ``covered`` uint8 ``[num_points]`` and two count rows -- ``num_points + 16 * total`` bytes."""
+
+    @staticmethod
+    def hist_images():
+        return int(_lib.load().dva_mapping_coverage_hist_images())
+
+    def __init__(self, items, num_points):
+        lib = _lib.load()
+        if not isinstance(items, (list, tuple)) or len(items) == 0:
+            raise ValueError("ops.MappingCoverage: a non-empty list of items")
+        self.device = require_device(*[t for item in items for t in item[:2]])
+        self.num_points = int(num_points)
+        if self.num_points < 1:
+            raise ValueError(f"ops.MappingCoverage: {self.num_points} points")
+        self._keep = []
+        self._descriptors = (_lib.DvaCoverageItem * len(items))()
+        base = 0
+        for b, (pointers, images, num_images) in enumerate(items):
+            for name, t in (("pointers", pointers), ("images", images)):
+                if t.dim() != 1:
+                    raise ValueError(f"ops.MappingCoverage: {name} of item {b} must be 1-D, got {tuple(t.shape)}")
+                if t.dtype != torch.int64:
+                    raise _lib.DvaError(f"ops.MappingCoverage: {name} of item {b} is {t.dtype}, not int64: "
+                                        f"{_lib._ERRORS[-2]}", code=-2)
+            n, v, k = pointers.shape[0] - 1, images.shape[0], int(num_images)
+            if n < 0 or n > self.num_points or k < 0:
+                raise ValueError(f"ops.MappingCoverage: item {b} has {n} points of {self.num_points} and {k} images")
+            pointers, images = pointers.contiguous(), images.contiguous()
+            self._keep.append((pointers, images))
+            d = self._descriptors[b]
+            d.pointers = pointers.data_ptr() if n > 0 else None
+            d.images = images.data_ptr() if v > 0 else None
+            d.n_points, d.n_views, d.n_images, d.image_base = n, v, k, base
+            base += k
+        self.num_images = base
+        if self.num_images < 1:
+            raise ValueError("ops.MappingCoverage: no image")
+        if max(self.num_points, self.num_images) >= 2 ** 31 - 1:
+            raise _lib.DvaError(f"ops.MappingCoverage: {self.num_points} points, {self.num_images} images: "
+                                f"{_lib._ERRORS[-2]}", code=-2)
+        self._lib = lib
+        self.covered = torch.zeros(self.num_points, dtype=torch.uint8, device=self.device)
+        self._counts = torch.zeros((2, self.num_images), dtype=torch.int64, device=self.device)
+        self._row = 0
+
+    def step(self, pick=-1):
+        pick = int(pick)
+        if not -1 <= pick < self.num_images:
+            raise ValueError(f"ops.MappingCoverage.step: pick {pick} outside [-1, {self.num_images})")
+        counts, clear = self._counts[self._row], self._counts[1 - self._row]
+        views = sum(d.n_views for d in self._descriptors)
+        with _timed("mapping_coverage_step", self.num_points * 18 + views * 8 + self.num_images * 16):
+            check(self._lib.dva_mapping_coverage_step(self._descriptors, len(self._descriptors), self.num_points,
+                                                      self.num_images, pick, ptr(self.covered), ptr(counts), ptr(clear),
+                                                      stream_of(self.covered)), "dva_mapping_coverage_step")
+        self._row = 1 - self._row
+        return counts
+
+
+# ---------------------------------------------------------------------------------------------
 # mapping collation: CSRBatch.from_csr_list on ImageMappings + insert_empty_groups (core/multimodal/csr.py:352-420)
 # ---------------------------------------------------------------------------------------------
 

@@ -1491,6 +1491,59 @@ int dva_mapping_image_stats(const int64_t* images, const int64_t* atom_ptr, cons
                             int64_t n_views, int64_t n_atoms, int64_t n_images, int64_t* stats, void* stream);
 
 /* ------------------------------------------------------------------------------------------ *
+ * The image picks (csrc/mapping_pick.hip): CenterRoll and the coverage counts of
+ * PickImagesFromMemoryCredit (core/data_transform/multimodal/image.py:962-1037, :765-874).  Mapping
+ * arrays as for the selection (pixels int16, pixel_bytes = 2; 1 / 4 / 8 return DVA_ERR_UNSUPPORTED).
+ *
+ * dva_mapping_center_rollings: rollings int64 [n_images] = per image the roll r * width >> 8 of the
+ *   first candidate r in {0, step, 2 step, ... < 256}, step = 256 / angular_res (integer division,
+ *   angular_res in 1..256), that minimises (hi - lo) + (|hi + lo - 256| >> 1), lo / hi the minimum /
+ *   maximum of (c + r) mod 256 over the distinct c = x * 256 / width of the image's atom columns x:
+ *   for 0 <= x < width <= 32767 the reference's float expressions (:999-1029) exactly.  An image
+ *   without atoms gets 0.  info int32 [2] = {images without atoms, flags}; flag bit 0: a view whose image
+ *   is outside [0, n_images), bit 1: an atom column outside [0, width); such views / atoms are left out
+ *   and the caller decides.  Integer OR atomics into a 256-bit occupancy bitmap per image: the result
+ *   does not depend on their order.  workspace: dva_mapping_center_workspace_bytes(n_images) bytes,
+ *   4-byte aligned.  width > 32767 returns DVA_ERR_UNSUPPORTED.
+ * dva_mapping_roll_pixels: x = (x + rollings[image]) mod width (the sign of width) IN PLACE in the
+ *   column of every atom; views whose image is outside [0, n_images) are left alone.
+ * dva_mapping_coverage_step: one step of the coverage counts over n_items mappings of the SAME
+ *   n_points points (items is a HOST array, read before the entry returns; item b has n_points <= the
+ *   total, its images are the global ids image_base .. image_base + n_images - 1, bases ascending
+ *   without overlap inside n_images).  covered uint8 [n_points] is the state, zero before the first
+ *   step.  With pick a global image id (or -1): covered[p] is set for every point p that pick sees;
+ *   then counts[i] += 1 for every view (p, i) of a point still uncovered, so that on a counts row that
+ *   was zero counts[i] = |{p : image i sees p, no picked image sees p}|, the row sums of the
+ *   reference's dense matrix (:803-868).  PRECONDITION: a view is a distinct (point, image) pair, as in
+ *   every mapping from_dense builds; a repeated pair counts twice.  counts int64 [n_images] must be zero
+ *   on entry; clear (int64 [n_images], nullable, not counts) is zeroed by the same launch: the row of
+ *   the next step.  Up to dva_mapping_coverage_hist_images() images in all a workgroup counts in an LDS
+ *   histogram and flushes one integer atomic per non-zero bin; above, global integer atomics.  No float
+ *   atomics.  dva_mapping_coverage_group_items() = 32 items per launch, by value.
+ * ------------------------------------------------------------------------------------------ */
+struct dva_coverage_item {
+  const int64_t* pointers;
+  const int64_t* images;
+  int64_t n_points;
+  int64_t n_views;
+  int64_t n_images;
+  int64_t image_base;
+};
+int64_t dva_mapping_center_workspace_bytes(int64_t n_images);
+int dva_mapping_center_rollings(const int64_t* images, const int64_t* atom_ptr, const void* pixels, int32_t pixel_bytes,
+                                int64_t n_views, int64_t n_atoms, int64_t n_images, int64_t width, int32_t angular_res,
+                                int64_t* rollings, int32_t* info, void* workspace, int64_t workspace_bytes,
+                                void* stream);
+int dva_mapping_roll_pixels(const int64_t* images, const int64_t* atom_ptr, void* pixels, int32_t pixel_bytes,
+                            int64_t n_views, int64_t n_atoms, const int64_t* rollings, int64_t n_images,
+                            int64_t width, void* stream);
+int dva_mapping_coverage_group_items(void);
+int dva_mapping_coverage_hist_images(void);
+int dva_mapping_coverage_step(const struct dva_coverage_item* items /* HOST array */, int64_t n_items,
+                              int64_t n_points, int64_t n_images, int64_t pick, uint8_t* covered, int64_t* counts,
+                              int64_t* clear, void* stream);
+
+/* ------------------------------------------------------------------------------------------ *
  * Mapping collation.  Replaces the torch composition of CSRBatch.from_csr_list on ImageMappings
  * followed by insert_empty_groups (core/multimodal/csr.py:352-420, :197-229): n_items mappings
  * stacked into one, without a host synchronisation.  items is a HOST array, read before the entry

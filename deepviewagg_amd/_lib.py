@@ -28,6 +28,7 @@ _ERRORS = {
     -3: "DVA_ERR_LAUNCH (HIP runtime error)",
     -4: "DVA_ERR_OVERFLOW (composite key does not fit int64)",
 }
+DVA_ERR_UNSUPPORTED = -2    # dtypes / sizes outside a kernel's range: the callers take their composition
 
 
 class DvaError(RuntimeError):
@@ -36,6 +37,17 @@ class DvaError(RuntimeError):
     def __init__(self, message, code=None):
         super().__init__(message)
         self.code = code
+
+
+def unless_unsupported(fn, *args, **kwargs):
+    """``fn(*args, **kwargs)``, or None where it raises ``DvaError`` with ``code == DVA_ERR_UNSUPPORTED`` (the caller then
+    takes its composition); every other exception propagates."""
+    try:
+        return fn(*args, **kwargs)
+    except DvaError as err:
+        if err.code != DVA_ERR_UNSUPPORTED:
+            raise
+    return None
 
 
 class DvaCamera(ctypes.Structure):

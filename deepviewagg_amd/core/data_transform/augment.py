@@ -132,12 +132,9 @@ def _device_steps(pos, norm, steps):
     if len(noises) > 1:
         raise ValueError("one pass takes one noise tensor: fuse_cloud_augment splits a run in front of a second RandomNoise")
     noise = noises[0].to(pos.device) if noises else None
-    try:
-        return ops.cloud_augment(pos, [s[:1] if s[0] == "noise" else s for s in steps], norm=norm, noise=noise)[:2]
-    except _lib.DvaError as err:
-        if err.code != -2:                            # DVA_ERR_UNSUPPORTED: the composition takes over
-            raise
-    return None
+    out = _lib.unless_unsupported(ops.cloud_augment, pos, [s[:1] if s[0] == "noise" else s for s in steps], norm=norm,
+                                  noise=noise)
+    return None if out is None else out[:2]               # None: the composition takes over
 
 
 def _run(data, steps):

@@ -13,7 +13,7 @@ cloud's own order (one admissible KD-tree order; tie-breaks depend on it, see vi
 """
 import torch
 
-from ...._lib import DvaError
+from ...._lib import DvaError, unless_unsupported
 from ....utils.multimodal import MAPPING_KEY, lexargunique
 from ...multimodal import visibility as visibility_module
 from ...multimodal.image import ImageMapping, SameSettingImageData
@@ -441,12 +441,7 @@ class PickImagesFromMemoryCredit(ImageTransform):
             if mp is None or not mp.pointers.is_cuda or mp.num_groups > _num_nodes(data):
                 return None
             items.append((mp.pointers, mp.images, im.num_views))
-        try:
-            return ops.MappingCoverage(items, _num_nodes(data))
-        except DvaError as e:
-            if e.code != -2:
-                raise
-            return None
+        return unless_unsupported(ops.MappingCoverage, items, _num_nodes(data))
 
     def _process(self, data, images):
         """Same host loop, float64 weights and ``np.random.choice`` draws as the composition; the coverage counts come
@@ -573,13 +568,11 @@ class CenterRoll(ImageTransform):
             f"{name} cannot operate if images and mappings underwent prior cropping or resizing."
         assert images.downscale is None or images.downscale == 1, \
             f"{name} cannot operate if images and mappings underwent prior cropping or resizing."
-        try:
-            rollings, info = ops.mapping_center_rollings(m.images, m.values[1].pointers, m.pixels, images.num_views,
-                                                         images.ref_size[0], self.angular_res)
-        except DvaError as e:
-            if e.code != -2:
-                raise
+        out = unless_unsupported(ops.mapping_center_rollings, m.images, m.values[1].pointers, m.pixels, images.num_views,
+                                 images.ref_size[0], self.angular_res)
+        if out is None:
             return self._process_composition(data, images)
+        rollings, info = out
         empty, flags = info.tolist()                       # host read: the only one
         if flags:
             # image ids or columns outside their range: what the integer restatement does not cover

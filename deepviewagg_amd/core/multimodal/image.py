@@ -260,13 +260,10 @@ class ImageMapping(CSRData):
         """``ops.select_mapping`` on this mapping: ``(mapping of class cls, info)``, the mapping None where the kernels
         do not take the input (the caller then runs its composition).  The nested CSR has the class indexing it
         gives (a batch loses its batch class); ``fresh``: the containers ``from_dense`` builds."""
-        from ..._lib import DvaError
-        try:
-            out = ops.select_mapping(self.pointers, self.images, self.values[1].pointers, self.pixels, self.features,
-                                     **selection)
-        except DvaError as err:
-            if err.code != -2:      # DVA_ERR_UNSUPPORTED: dtypes / sizes outside the kernels' range
-                raise
+        from ..._lib import unless_unsupported
+        out = unless_unsupported(ops.select_mapping, self.pointers, self.images, self.values[1].pointers, self.pixels,
+                                 self.features, **selection)
+        if out is None:             # dtypes / sizes outside the kernels' range
             return None, None
         info = out[5]
         assert not info['duplicate_keys'], "Index must not contain duplicates."
@@ -444,14 +441,12 @@ class ImageMapping(CSRData):
         return out, info['seen'], info['seen_host']
 
     def _merge_points_device(self, idx):
-        from ..._lib import DvaError
-        try:
-            pointers, images, atom_ptr, pixels, features, ok = ops.merge_mapping(
-                self.pointers, self.images, self.values[1].pointers, self.pixels, self.features, idx)
-        except DvaError as err:
-            if err.code != -2:      # DVA_ERR_UNSUPPORTED: dtypes / sizes outside the kernels' range
-                raise
+        from ..._lib import unless_unsupported
+        out = unless_unsupported(ops.merge_mapping, self.pointers, self.images, self.values[1].pointers, self.pixels,
+                                 self.features, idx)
+        if out is None:             # dtypes / sizes outside the kernels' range
             return self._merge_points_composition(idx)
+        pointers, images, atom_ptr, pixels, features, ok = out
         if not ok:
             return self.clone()
         values = [images, CSRData(atom_ptr, pixels, dense=False)]
@@ -469,7 +464,7 @@ class ImageMapping(CSRData):
         synchronisation.  None where the op does not apply (the caller then runs the composition): CPU items, a layout
         other than images / atoms / features with the standard ``is_index_value``, dtypes the kernel does not take,
         ``COLLATE_ON_DEVICE`` off."""
-        from ..._lib import DvaError
+        from ..._lib import unless_unsupported
         first = csr_list[0]
         if not ImageMapping.COLLATE_ON_DEVICE or not isinstance(first, ImageMapping) or not first.pointers.is_cuda:
             return None
@@ -490,14 +485,13 @@ class ImageMapping(CSRData):
                 "New group indices must be sorted."
             top = group_bases[-1] + csr_list[-1].num_groups
             num_groups = top if num_groups is None else max(top, int(num_groups))
-        try:
-            pointers, images, atom_ptr, pixels, features, _ = ops.collate_mapping(
-                [(c.pointers, c.values[0], a.pointers, a.values[0], c.values[2] if num_values == 3 else None)
-                 for c, a in zip(csr_list, nested)], point_bases=group_bases, num_points=num_groups)
-        except DvaError as err:
-            if err.code != -2:      # DVA_ERR_UNSUPPORTED: dtypes / sizes outside the kernel's range
-                raise
+        out = unless_unsupported(
+            ops.collate_mapping,
+            [(c.pointers, c.values[0], a.pointers, a.values[0], c.values[2] if num_values == 3 else None)
+             for c, a in zip(csr_list, nested)], point_bases=group_bases, num_points=num_groups)
+        if out is None:             # dtypes / sizes outside the kernel's range
             return None
+        pointers, images, atom_ptr, pixels, features, _ = out
         atoms = nested_type.get_batch_type()(atom_ptr, pixels, dense=False, is_index_value=nested[0].is_index_value)
         atoms.__sizes__ = torch.tensor([a.num_groups for a in nested], dtype=torch.long)
         atoms.__csr_type__ = nested_type
@@ -1001,19 +995,14 @@ class SameSettingImageData:
 
     def _roll_mapping_device(self):
         """``update_rollings``' mapping half through ``ops.roll_mapping_pixels``; False where the op does not apply."""
-        from ..._lib import DvaError
+        from ..._lib import unless_unsupported
         m = self.mappings
         pix = m.pixels
         if not (pix.is_cuda and pix.dtype == torch.int16 and pix.is_contiguous() and pix.data_ptr() % 4 == 0
                 and self.ref_size[0] <= 32767):
             return False
-        try:
-            ops.roll_mapping_pixels(m.images, m.values[1].pointers, pix, self.rollings, self.ref_size[0])
-        except DvaError as e:
-            if e.code != -2:
-                raise
-            return False
-        return True
+        return unless_unsupported(ops.roll_mapping_pixels, m.images, m.values[1].pointers, pix, self.rollings,
+                                  self.ref_size[0]) is not None
 
     def update_cropping(self, crop_size, crop_offsets):
         """Crop ``x`` and the mappings with respect to the CURRENT ``img_size``; the stored crop state is

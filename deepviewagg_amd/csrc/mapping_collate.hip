@@ -20,6 +20,7 @@
 //      is ever used as an address.
 // Item descriptors travel by value as kernel arguments, COLLATE_GROUP items per launch (5 pointers + 8 int64 each,
 // 3.3 KB): a larger batch takes more launches of 1 and 3, and the entry holds no host memory after it returns.
+#include "mapping_args.h"
 #include "scan.h"
 
 namespace dva {
@@ -191,7 +192,7 @@ int dva_mapping_collate_group_items(void) { return COLLATE_GROUP; }
 
 int64_t dva_mapping_collate_workspace_bytes(int64_t n_items) {
   if (n_items < 1) return DVA_ERR_INVALID;
-  if (n_items >= 0x7fffffffLL / COLLATE_PARTIALS) return DVA_ERR_UNSUPPORTED;
+  if (n_items >= I31_LIMIT / COLLATE_PARTIALS) return DVA_ERR_UNSUPPORTED;
   return collate_layout(nullptr, n_items).total;
 }
 
@@ -201,7 +202,7 @@ int dva_mapping_collate(const struct dva_collate_item* items, int64_t n_items, i
                         int64_t* out_image_offsets, void* workspace, int64_t workspace_bytes, void* stream) {
   // every check comes before the first HIP call
   if (!items || n_items < 1 || !out_pointers || !out_atom_ptr || !workspace) return DVA_ERR_INVALID;
-  if (n_points_out < 0 || n_views_out < 0 || n_atoms_out < 0 || F < 0) return DVA_ERR_INVALID;
+  if (any_negative({n_points_out, n_views_out, n_atoms_out, F})) return DVA_ERR_INVALID;
   if ((n_views_out > 0 && !out_images) || (n_atoms_out > 0 && !out_pixels)) return DVA_ERR_INVALID;
   if ((F > 0 && n_views_out > 0 && !out_features) || (F == 0 && out_features)) return DVA_ERR_INVALID;
   if (((uintptr_t)out_pixels & 3) || ((uintptr_t)out_features & 3) || ((uintptr_t)workspace & 15))
@@ -209,11 +210,11 @@ int dva_mapping_collate(const struct dva_collate_item* items, int64_t n_items, i
   int64_t end = 0, views = 0, atoms = 0, v_max = 0, work = 0;
   for (int64_t b = 0; b < n_items; ++b) {
     const struct dva_collate_item& it = items[b];
-    if (it.n_points < 0 || it.n_views < 0 || it.n_atoms < 0) return DVA_ERR_INVALID;
-    if (!it.pointers || !it.atom_ptr || (it.n_views > 0 && !it.images) || (it.n_atoms > 0 && !it.pixels))
+    if (any_negative({it.n_points, it.n_views, it.n_atoms})) return DVA_ERR_INVALID;
+    if (!it.pointers || !mapping_arrays_ok(it.images, it.atom_ptr, it.pixels, it.n_views, it.n_atoms))
       return DVA_ERR_INVALID;
     if ((F > 0 && it.n_views > 0 && !it.features) || (F == 0 && it.features)) return DVA_ERR_INVALID;
-    if (((uintptr_t)it.pixels & 3) || ((uintptr_t)it.features & 3)) return DVA_ERR_INVALID;
+    if ((uintptr_t)it.features & 3) return DVA_ERR_INVALID;
     if (it.point_base < end) return DVA_ERR_INVALID;      // not ascending, or inside the item before
     if (it.n_points > n_points_out - it.point_base) return DVA_ERR_INVALID;
     end = it.point_base + it.n_points;
@@ -224,8 +225,7 @@ int dva_mapping_collate(const struct dva_collate_item* items, int64_t n_items, i
   }
   if (views != n_views_out || atoms != n_atoms_out) return DVA_ERR_INVALID;
   if (pixel_bytes != 2 || F > COLLATE_MAX_F) return DVA_ERR_UNSUPPORTED;
-  if (n_points_out >= 0x7fffffffLL || n_views_out >= 0x7fffffffLL || n_atoms_out >= 0x7fffffffLL ||
-      n_items >= 0x7fffffffLL / COLLATE_PARTIALS)
+  if (fits_i31({n_points_out, n_views_out, n_atoms_out}) != DVA_OK || n_items >= I31_LIMIT / COLLATE_PARTIALS)
     return DVA_ERR_UNSUPPORTED;
   const CollateLayout L = collate_layout(workspace, n_items);
   if (workspace_bytes < L.total) return DVA_ERR_INVALID;

@@ -23,6 +23,7 @@
 // Image ids are < 2^31 and pixels are non-negative int16 (the key packing); a view without atoms contributes
 // nothing (the reference drops it when it expands to atom rows).
 #include "dva_common.h"
+#include "mapping_args.h"
 #include "scan.h"
 
 namespace dva {
@@ -500,9 +501,8 @@ __global__ __launch_bounds__(BIG_THREADS) void merge_fill_big_kernel(const u64* 
 }
 
 static inline int merge_check_sizes(int64_t N, int64_t V, int64_t P) {
-  if (N < 1 || V < 0 || P < 0) return DVA_ERR_INVALID;
-  if (N >= 0x7fffffffLL || V >= 0x7fffffffLL || P >= 0x7fffffffLL) return DVA_ERR_UNSUPPORTED;
-  return DVA_OK;
+  if (N < 1 || any_negative({V, P})) return DVA_ERR_INVALID;
+  return fits_i31({N, V, P});
 }
 
 }  // namespace dva
@@ -523,13 +523,11 @@ int dva_mapping_merge_count(const int64_t* pointers, const int64_t* images, cons
                             const void* pixels, int32_t pixel_bytes, const int64_t* idx, int64_t n_points,
                             int64_t n_views, int64_t n_atoms, int64_t* sizes, void* workspace,
                             int64_t workspace_bytes, void* stream) {
-  const int rc = merge_check_sizes(n_points, n_views, n_atoms);
+  int rc = merge_check_sizes(n_points, n_views, n_atoms);
   if (rc != DVA_OK) return rc;
-  if (pixel_bytes != 2) return pixel_bytes == 1 || pixel_bytes == 4 || pixel_bytes == 8 ? DVA_ERR_UNSUPPORTED
-                                                                                         : DVA_ERR_INVALID;
-  if (!pointers || !atom_ptr || !idx || !sizes || !workspace) return DVA_ERR_INVALID;
-  if ((n_views > 0 && !images) || (n_atoms > 0 && !pixels)) return DVA_ERR_INVALID;
-  if (((uintptr_t)pixels & 3) || ((uintptr_t)workspace & 15)) return DVA_ERR_INVALID;
+  if ((rc = pixel_bytes_code(pixel_bytes)) != DVA_OK) return rc;
+  if (!pointers || !idx || !sizes || !workspace || ((uintptr_t)workspace & 15)) return DVA_ERR_INVALID;
+  if (!mapping_arrays_ok(images, atom_ptr, pixels, n_views, n_atoms)) return DVA_ERR_INVALID;
   const MergeLayout L = merge_layout(workspace, n_points, n_views, n_atoms);
   if (workspace_bytes < L.total) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
@@ -559,19 +557,18 @@ int dva_mapping_merge_fill(const int64_t* pointers, const int64_t* images, const
                            int64_t n_views_out, int64_t n_atoms_out, int64_t* out_pointers, int64_t* out_images,
                            int64_t* out_atom_ptr, void* out_pixels, float* out_features, void* workspace,
                            int64_t workspace_bytes, void* stream) {
-  const int rc = merge_check_sizes(n_points, n_views, n_atoms);
+  int rc = merge_check_sizes(n_points, n_views, n_atoms);
   if (rc != DVA_OK) return rc;
-  if (pixel_bytes != 2) return pixel_bytes == 1 || pixel_bytes == 4 || pixel_bytes == 8 ? DVA_ERR_UNSUPPORTED
-                                                                                         : DVA_ERR_INVALID;
+  if ((rc = pixel_bytes_code(pixel_bytes)) != DVA_OK) return rc;
   if (n_voxels < 1 || n_voxels > n_points || n_views_out < 0 || n_views_out > n_views || n_atoms_out < 0 ||
       n_atoms_out > n_atoms || F < 0)
     return DVA_ERR_INVALID;
   if (F > MERGE_MAX_F) return DVA_ERR_UNSUPPORTED;
-  if (!pointers || !atom_ptr || !workspace || !out_pointers || !out_atom_ptr) return DVA_ERR_INVALID;
-  if ((n_views > 0 && !images) || (n_atoms > 0 && !pixels)) return DVA_ERR_INVALID;
+  if (!pointers || !workspace || !out_pointers || !out_atom_ptr) return DVA_ERR_INVALID;
+  if (!mapping_arrays_ok(images, atom_ptr, pixels, n_views, n_atoms)) return DVA_ERR_INVALID;
   if ((n_views_out > 0 && !out_images) || (n_atoms_out > 0 && !out_pixels)) return DVA_ERR_INVALID;
   if ((features != nullptr) != (out_features != nullptr) || (features && F < 1)) return DVA_ERR_INVALID;
-  if (((uintptr_t)pixels & 3) || ((uintptr_t)out_pixels & 3) || ((uintptr_t)workspace & 15)) return DVA_ERR_INVALID;
+  if (((uintptr_t)out_pixels & 3) || ((uintptr_t)workspace & 15)) return DVA_ERR_INVALID;
   const MergeLayout L = merge_layout(workspace, n_points, n_views, n_atoms);
   if (workspace_bytes < L.total) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;

@@ -29,6 +29,8 @@
 // (point, image) pair in every mapping the library builds (from_dense unites repeated pairs); a repeated pair would
 // count twice.  Item descriptors travel by value, COVER_GROUP per launch, the item of the pick with every launch.
 #include "dva_common.h"
+#include "mapping_args.h"
+#include "scan.h"
 
 namespace dva {
 
@@ -40,9 +42,6 @@ constexpr int COVER_GRID = 1024;
 constexpr int COVER_HIST = 1024;      // images in all up to which a workgroup counts in LDS: 4 KiB
 
 enum { CI_EMPTY = 0, CI_FLAGS = 1, CI_COUNT = 2 };
-typedef unsigned long long cover_u64;
-
-__device__ __forceinline__ int64_t pick_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // CenterRoll
@@ -73,7 +72,8 @@ __global__ __launch_bounds__(CENTER_THREADS) void center_bits_kernel(const int64
       atomicOr(&info[CI_FLAGS], 1);
       continue;
     }
-    const int64_t a0 = pick_clamp(atom_ptr[v], 0, P), a1 = pick_clamp(atom_ptr[v + 1], a0, P);
+    int64_t a0, a1;
+    csr_range(atom_ptr, v, P, &a0, &a1);
     int cur = -1;
     uint32_t bits = 0u;
     bool outside = false;
@@ -158,7 +158,8 @@ __global__ __launch_bounds__(CENTER_THREADS) void roll_pixels_kernel(const int64
     const int64_t img = images[v];
     if (img < 0 || img >= B) continue;
     const int64_t roll = rollings[img];
-    const int64_t a0 = pick_clamp(atom_ptr[v], 0, P), a1 = pick_clamp(atom_ptr[v + 1], a0, P);
+    int64_t a0, a1;
+    csr_range(atom_ptr, v, P, &a0, &a1);
     for (int64_t a = a0; a < a1; ++a) {
       const uint32_t px = pixels[a];
       // the remainder takes the sign of W > 0, as the int64 tensors compute it
@@ -188,7 +189,7 @@ __global__ __launch_bounds__(COVER_THREADS) void coverage_step_kernel(CoverGroup
                                                                        int64_t pick_local, int64_t n_points,
                                                                        int64_t n_images,
                                                                        uint8_t* __restrict__ covered,
-                                                                       cover_u64* __restrict__ counts,
+                                                                       u64* __restrict__ counts,
                                                                        int64_t* __restrict__ clear) {
   __shared__ int hist[HIST ? COVER_HIST : 1];
   if (HIST) {
@@ -201,8 +202,8 @@ __global__ __launch_bounds__(COVER_THREADS) void coverage_step_kernel(CoverGroup
        p += (int64_t)gridDim.x * COVER_THREADS) {
     bool c = covered[p] != 0;
     if (!c && pick_local >= 0 && p < picked.n) {
-      const int64_t v0 = pick_clamp(picked.pointers[p], 0, picked.v);
-      const int64_t v1 = pick_clamp(picked.pointers[p + 1], v0, picked.v);
+      int64_t v0, v1;
+      csr_range(picked.pointers, p, picked.v, &v0, &v1);
       for (int64_t v = v0; v < v1 && !c; ++v) c = picked.images[v] == pick_local;
       if (c) covered[p] = 1;      // p has one owner
     }
@@ -210,14 +211,15 @@ __global__ __launch_bounds__(COVER_THREADS) void coverage_step_kernel(CoverGroup
     for (int k = 0; k < count; ++k) {
       const CoverItem& it = g.item[k];
       if (p >= it.n) continue;
-      const int64_t v0 = pick_clamp(it.pointers[p], 0, it.v), v1 = pick_clamp(it.pointers[p + 1], v0, it.v);
+      int64_t v0, v1;
+      csr_range(it.pointers, p, it.v, &v0, &v1);
       for (int64_t v = v0; v < v1; ++v) {
         const int64_t img = it.images[v];
         if (img < 0 || img >= it.b) continue;      // base + b <= n_images: checked by the entry
         if (HIST)
           atomicAdd(&hist[it.base + img], 1);
         else
-          atomicAdd(&counts[it.base + img], (cover_u64)1);
+          atomicAdd(&counts[it.base + img], (u64)1);
       }
     }
   }
@@ -225,7 +227,7 @@ __global__ __launch_bounds__(COVER_THREADS) void coverage_step_kernel(CoverGroup
     __syncthreads();
     for (int i = threadIdx.x; i < (int)n_images; i += COVER_THREADS) {
       const int h = hist[i];
-      if (h != 0) atomicAdd(&counts[i], (cover_u64)h);
+      if (h != 0) atomicAdd(&counts[i], (u64)h);
     }
   }
 }
@@ -238,7 +240,7 @@ extern "C" {
 
 int64_t dva_mapping_center_workspace_bytes(int64_t n_images) {
   if (n_images < 0) return DVA_ERR_INVALID;
-  if (n_images >= 0x7fffffffLL / 8) return DVA_ERR_UNSUPPORTED;
+  if (n_images >= I31_LIMIT / 8) return DVA_ERR_UNSUPPORTED;
   return (int64_t)align_up((size_t)(n_images > 0 ? n_images : 1) * 8 * sizeof(uint32_t), 16);
 }
 
@@ -246,16 +248,13 @@ int dva_mapping_center_rollings(const int64_t* images, const int64_t* atom_ptr, 
                                 int64_t n_views, int64_t n_atoms, int64_t n_images, int64_t width, int32_t angular_res,
                                 int64_t* rollings, int32_t* info, void* workspace, int64_t workspace_bytes,
                                 void* stream) {
-  if (n_views < 0 || n_atoms < 0 || n_images < 0 || width < 1 || angular_res < 1 || angular_res > 256)
+  if (any_negative({n_views, n_atoms, n_images}) || width < 1 || angular_res < 1 || angular_res > 256)
     return DVA_ERR_INVALID;
-  if (pixel_bytes != 2) return pixel_bytes == 1 || pixel_bytes == 4 || pixel_bytes == 8 ? DVA_ERR_UNSUPPORTED
-                                                                                         : DVA_ERR_INVALID;
-  if (n_views >= 0x7fffffffLL || n_atoms >= 0x7fffffffLL || n_images >= 0x7fffffffLL / 8 || width > 32767)
-    return DVA_ERR_UNSUPPORTED;
-  if (!info || !atom_ptr || !workspace || (n_images > 0 && !rollings) || (n_views > 0 && !images) ||
-      (n_atoms > 0 && !pixels))
-    return DVA_ERR_INVALID;
-  if (((uintptr_t)pixels & 3) || ((uintptr_t)workspace & 3)) return DVA_ERR_INVALID;
+  const int rc = pixel_bytes_code(pixel_bytes);
+  if (rc != DVA_OK) return rc;
+  if (fits_i31({n_views, n_atoms}) != DVA_OK || n_images >= I31_LIMIT / 8 || width > 32767) return DVA_ERR_UNSUPPORTED;
+  if (!info || !workspace || ((uintptr_t)workspace & 3) || (n_images > 0 && !rollings)) return DVA_ERR_INVALID;
+  if (!mapping_arrays_ok(images, atom_ptr, pixels, n_views, n_atoms)) return DVA_ERR_INVALID;
   if (workspace_bytes < dva_mapping_center_workspace_bytes(n_images)) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   uint32_t* bitmap = (uint32_t*)workspace;
@@ -277,14 +276,12 @@ int dva_mapping_center_rollings(const int64_t* images, const int64_t* atom_ptr, 
 int dva_mapping_roll_pixels(const int64_t* images, const int64_t* atom_ptr, void* pixels, int32_t pixel_bytes,
                             int64_t n_views, int64_t n_atoms, const int64_t* rollings, int64_t n_images,
                             int64_t width, void* stream) {
-  if (n_views < 0 || n_atoms < 0 || n_images < 0 || width < 1) return DVA_ERR_INVALID;
-  if (pixel_bytes != 2) return pixel_bytes == 1 || pixel_bytes == 4 || pixel_bytes == 8 ? DVA_ERR_UNSUPPORTED
-                                                                                         : DVA_ERR_INVALID;
-  if (n_views >= 0x7fffffffLL || n_atoms >= 0x7fffffffLL || n_images >= 0x7fffffffLL || width > 32767)
-    return DVA_ERR_UNSUPPORTED;
-  if (!atom_ptr || (n_images > 0 && !rollings) || (n_views > 0 && !images) || (n_atoms > 0 && !pixels))
+  if (any_negative({n_views, n_atoms, n_images}) || width < 1) return DVA_ERR_INVALID;
+  const int rc = pixel_bytes_code(pixel_bytes);
+  if (rc != DVA_OK) return rc;
+  if (fits_i31({n_views, n_atoms, n_images}) != DVA_OK || width > 32767) return DVA_ERR_UNSUPPORTED;
+  if ((n_images > 0 && !rollings) || !mapping_arrays_ok(images, atom_ptr, pixels, n_views, n_atoms))
     return DVA_ERR_INVALID;
-  if ((uintptr_t)pixels & 3) return DVA_ERR_INVALID;
   if (n_views == 0 || n_atoms == 0 || n_images == 0) return DVA_OK;
   hipLaunchKernelGGL(roll_pixels_kernel, dim3(capped_grid(n_views, CENTER_THREADS, CENTER_GRID)),
                      dim3(CENTER_THREADS), 0, (hipStream_t)stream, images, atom_ptr, (uint32_t*)pixels, n_views,
@@ -304,12 +301,12 @@ int dva_mapping_coverage_step(const struct dva_coverage_item* items, int64_t n_i
   if (!items || n_items < 1 || n_points < 1 || n_images < 1 || !covered || !counts || counts == clear)
     return DVA_ERR_INVALID;
   if (pick < -1 || pick >= n_images) return DVA_ERR_INVALID;
-  if (n_points >= 0x7fffffffLL || n_images >= 0x7fffffffLL) return DVA_ERR_UNSUPPORTED;
+  if (fits_i31({n_points, n_images}) != DVA_OK) return DVA_ERR_UNSUPPORTED;
   int64_t end = 0, pick_item = -1;
   for (int64_t b = 0; b < n_items; ++b) {
     const struct dva_coverage_item& it = items[b];
-    if (it.n_points < 0 || it.n_views < 0 || it.n_images < 0 || it.n_points > n_points) return DVA_ERR_INVALID;
-    if (it.n_views >= 0x7fffffffLL) return DVA_ERR_UNSUPPORTED;
+    if (any_negative({it.n_points, it.n_views, it.n_images}) || it.n_points > n_points) return DVA_ERR_INVALID;
+    if (fits_i31({it.n_views}) != DVA_OK) return DVA_ERR_UNSUPPORTED;
     if ((it.n_points > 0 && !it.pointers) || (it.n_views > 0 && !it.images)) return DVA_ERR_INVALID;
     if (it.image_base < end || it.n_images > n_images - it.image_base) return DVA_ERR_INVALID;      // ascending, no overlap
     end = it.image_base + it.n_images;
@@ -338,10 +335,10 @@ int dva_mapping_coverage_step(const struct dva_coverage_item* items, int64_t n_i
     int64_t* clr = gi == 0 ? clear : nullptr;
     if (hist)
       hipLaunchKernelGGL(coverage_step_kernel<true>, grid, dim3(COVER_THREADS), 0, s, g, count, picked, pick_local,
-                         n_points, n_images, covered, (cover_u64*)counts, clr);
+                         n_points, n_images, covered, (u64*)counts, clr);
     else
       hipLaunchKernelGGL(coverage_step_kernel<false>, grid, dim3(COVER_THREADS), 0, s, g, count, picked, pick_local,
-                         n_points, n_images, covered, (cover_u64*)counts, clr);
+                         n_points, n_images, covered, (u64*)counts, clr);
   }
   DVA_CHECK_LAUNCH();
   return DVA_OK;

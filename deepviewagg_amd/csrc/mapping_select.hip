@@ -23,6 +23,7 @@
 // source arrays and the vcnt workspace above that.  Two surviving views of one point with the same image are what
 // from_dense would unite: the count pass raises the `unsupported` flag and the caller takes the composition.
 #include "dva_common.h"
+#include "mapping_args.h"
 #include "scan.h"
 
 namespace dva {
@@ -78,16 +79,12 @@ struct SelectOut {
   uint32_t* features;
 };
 
-__device__ __forceinline__ int64_t clampi(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // the views [v0, v1) of source point p, inside [0, V] whatever the pointers hold
 __device__ __forceinline__ void point_views(const SelectIn& in, int64_t p, int64_t* v0, int64_t* v1) {
-  *v0 = clampi(in.pointers[p], 0, in.V);
-  *v1 = clampi(in.pointers[p + 1], *v0, in.V);
+  csr_range(in.pointers, p, in.V, v0, v1);
 }
 __device__ __forceinline__ void view_atoms(const SelectIn& in, int64_t v, int64_t* a0, int64_t* a1) {
-  *a0 = clampi(in.atom_ptr[v], 0, in.P);
-  *a1 = clampi(in.atom_ptr[v + 1], *a0, in.P);
+  csr_range(in.atom_ptr, v, in.P, a0, a1);
 }
 
 // Does view v survive the mask and the image selection?  *id = its new image id (its own image with compact, which
@@ -285,7 +282,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void select_sizes_kernel(const int* _
   if (threadIdx.x == 0) {
     const int64_t Vp = view_base[M], Pp = atom_base[M];
     int64_t f = 0;
-    if (flags[SF_UNSUPPORTED] || Vp >= 0x7fffffffLL || Pp >= 0x7fffffffLL) f |= 1;
+    if (flags[SF_UNSUPPORTED] || Vp >= I31_LIMIT || Pp >= I31_LIMIT) f |= 1;
     if (flags[SF_RANGE]) f |= 2;
     if (repeated) f |= 4;
     sizes[0] = Vp;
@@ -403,7 +400,8 @@ __global__ __launch_bounds__(256) void image_stats_kernel(const int64_t* __restr
   for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v < V; v += (int64_t)gridDim.x * blockDim.x) {
     const int64_t img = images[v];
     if (img < 0 || img >= B) continue;
-    const int64_t a0 = clampi(atom_ptr[v], 0, P), a1 = clampi(atom_ptr[v + 1], a0, P);
+    int64_t a0, a1;
+    csr_range(atom_ptr, v, P, &a0, &a1);
     if (a1 == a0) continue;
     long long x0 = 32767, x1 = -32768, y0 = 32767, y1 = -32768;
     for (int64_t a = a0; a < a1; ++a) {
@@ -428,15 +426,8 @@ __global__ __launch_bounds__(256) void image_stats_kernel(const int64_t* __restr
 // ---------------------------------------------------------------------------------------------------------------
 
 static inline int select_check_sizes(int64_t N, int64_t V, int64_t P, int64_t M, int64_t B) {
-  if (N < 1 || V < 0 || P < 0 || M < 1 || B < 0) return DVA_ERR_INVALID;
-  if (N >= 0x7fffffffLL || V >= 0x7fffffffLL || P >= 0x7fffffffLL || M >= 0x7fffffffLL || B >= 0x7fffffffLL)
-    return DVA_ERR_UNSUPPORTED;
-  return DVA_OK;
-}
-
-static inline int pixel_bytes_code(int32_t pixel_bytes) {
-  if (pixel_bytes == 2) return DVA_OK;
-  return pixel_bytes == 1 || pixel_bytes == 4 || pixel_bytes == 8 ? DVA_ERR_UNSUPPORTED : DVA_ERR_INVALID;
+  if (N < 1 || M < 1 || any_negative({V, P, B})) return DVA_ERR_INVALID;
+  return fits_i31({N, V, P, M, B});
 }
 
 // the checks the two entries share; fills `in`
@@ -449,14 +440,13 @@ static int select_arguments(const int64_t* pointers, const int64_t* images, cons
   int rc = select_check_sizes(n_points, n_views, n_atoms, n_out, n_images);
   if (rc != DVA_OK) return rc;
   if ((rc = pixel_bytes_code(pixel_bytes)) != DVA_OK) return rc;
-  if (!pointers || !atom_ptr || !workspace) return DVA_ERR_INVALID;
-  if ((n_views > 0 && !images) || (n_atoms > 0 && !pixels)) return DVA_ERR_INVALID;
+  if (!pointers || !workspace || ((uintptr_t)workspace & 15)) return DVA_ERR_INVALID;
+  if (!mapping_arrays_ok(images, atom_ptr, pixels, n_views, n_atoms)) return DVA_ERR_INVALID;
   if (!point_idx && n_out != n_points) return DVA_ERR_INVALID;
   if (n_map < 0 || (image_keys && !image_map) || (image_map && compact) || (!image_map && n_map != 0))
     return DVA_ERR_INVALID;
   if (crop_offsets && (compact || image_map || crop_w < 1 || crop_h < 1)) return DVA_ERR_INVALID;
   if (!compact && !crop_offsets && n_images != 0) return DVA_ERR_INVALID;
-  if (((uintptr_t)pixels & 3) || ((uintptr_t)workspace & 15)) return DVA_ERR_INVALID;
   *in = SelectIn{pointers, images, atom_ptr, (const uint32_t*)pixels, point_idx, view_mask, image_keys, image_map,
                  crop_offsets, n_points, n_views, n_atoms, n_out, n_map, n_images, crop_w, crop_h, compact ? 1 : 0,
                  crop_offsets ? 1 : 0};
@@ -526,8 +516,8 @@ int dva_mapping_select_fill(const int64_t* pointers, const int64_t* images, cons
                                   point_idx, n_out, view_mask, image_keys, image_map, n_map, compact, n_images, crop_w,
                                   crop_h, crop_offsets, workspace, &in);
   if (rc != DVA_OK) return rc;
-  if (n_views_out < 0 || n_atoms_out < 0 || F < 0) return DVA_ERR_INVALID;
-  if (n_views_out >= 0x7fffffffLL || n_atoms_out >= 0x7fffffffLL || F > SELECT_MAX_F) return DVA_ERR_UNSUPPORTED;
+  if (any_negative({n_views_out, n_atoms_out, F})) return DVA_ERR_INVALID;
+  if (fits_i31({n_views_out, n_atoms_out}) != DVA_OK || F > SELECT_MAX_F) return DVA_ERR_UNSUPPORTED;
   if (!out_pointers || !out_atom_ptr) return DVA_ERR_INVALID;
   if ((n_views_out > 0 && !out_images) || (n_atoms_out > 0 && !out_pixels)) return DVA_ERR_INVALID;
   if ((!features && out_features) || (features && (F < 1 || (n_views_out > 0 && !out_features)))) return DVA_ERR_INVALID;
@@ -551,13 +541,12 @@ int dva_mapping_select_fill(const int64_t* pointers, const int64_t* images, cons
 
 int dva_mapping_image_stats(const int64_t* images, const int64_t* atom_ptr, const void* pixels, int32_t pixel_bytes,
                             int64_t n_views, int64_t n_atoms, int64_t n_images, int64_t* stats, void* stream) {
-  if (n_views < 0 || n_atoms < 0 || n_images < 0) return DVA_ERR_INVALID;
-  if (n_views >= 0x7fffffffLL || n_atoms >= 0x7fffffffLL || n_images >= 0x7fffffffLL) return DVA_ERR_UNSUPPORTED;
-  const int rc = pixel_bytes_code(pixel_bytes);
+  if (any_negative({n_views, n_atoms, n_images})) return DVA_ERR_INVALID;
+  int rc = fits_i31({n_views, n_atoms, n_images});
+  if (rc == DVA_OK) rc = pixel_bytes_code(pixel_bytes);
   if (rc != DVA_OK) return rc;
   if (n_images == 0) return DVA_OK;
-  if (!stats || !atom_ptr || (n_views > 0 && !images) || (n_atoms > 0 && !pixels)) return DVA_ERR_INVALID;
-  if ((uintptr_t)pixels & 3) return DVA_ERR_INVALID;
+  if (!stats || !mapping_arrays_ok(images, atom_ptr, pixels, n_views, n_atoms)) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(image_stats_init_kernel, dim3(capped_grid(5 * n_images, 256, 4096)), dim3(256), 0, s,
                      (long long*)stats, n_images);

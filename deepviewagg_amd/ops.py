@@ -1813,8 +1813,64 @@ def voxel_parent_index(in_coords, out_coords, stride_out, batch_col=3):
 MERGE_TILE_ATOMS = 512      # atoms of a voxel merged in LDS (dva_mapping_merge_tile_atoms); larger voxels sort in the workspace
 
 
-def _merge_unsupported(what):
-    return _lib.DvaError(f"ops.merge_mapping: {what}: {_lib._ERRORS[-2]}", code=-2)
+def _unsupported(op, what):
+    """The ``DvaError`` with ``code == DVA_ERR_UNSUPPORTED`` of ``ops.<op>``: the callers take their composition."""
+    code = _lib.DVA_ERR_UNSUPPORTED
+    return _lib.DvaError(f"ops.{op}: {what}: {_lib._ERRORS[code]}", code=code)
+
+
+def _mapping_arguments(op, pointers, images, atom_ptr=None, pixels=None, features=None, *, features_dtype=torch.float32,
+                       item=None, dev=None, **index_vectors):
+    """The argument checks of the ops on the nested mapping CSR ``pointers`` -> ``images`` / ``atom_ptr`` -> ``pixels``
+    (+ ``features``): ``(device, points, views, atoms)``, ``points`` / ``atoms`` None without ``pointers`` / ``pixels``.
+    One order for every op: shapes (``ValueError``), then what the kernels do not take -- index tensors (the extra
+    ``index_vectors`` by name as well) other than int64, pixels other than int16, features other than
+    ``features_dtype`` (None: any), 2^31 - 1 or more points, views or atoms -- (``DvaError`` with code -2), then the
+    device (``DvaError`` without a code; ``dev``: the device of the items before).  Reads shapes, dtypes and devices
+    only; ``op`` and ``item`` go into the messages and nowhere else."""
+    of = "" if item is None else f" of item {item}"
+    index = dict(pointers=pointers, images=images, atom_ptr=atom_ptr, **index_vectors)
+    for name, t in index.items():
+        if t is not None and t.dim() != 1:
+            raise ValueError(f"ops.{op}: {name}{of} must be 1-D, got {tuple(t.shape)}")
+    if pixels is not None and (pixels.dim() != 2 or pixels.shape[1] != 2):
+        raise ValueError(f"ops.{op}: pixels{of} must be [P, 2], got {tuple(pixels.shape)}")
+    n = None if pointers is None else pointers.shape[0] - 1
+    v = images.shape[0]
+    p = None if pixels is None else pixels.shape[0]
+    if atom_ptr is not None and atom_ptr.shape[0] != v + 1:
+        raise ValueError(f"ops.{op}: atom_ptr{of} must have {v + 1} entries for {v} views, got {atom_ptr.shape[0]}")
+    if features is not None and (features.dim() < 1 or features.shape[0] != v):
+        raise ValueError(f"ops.{op}: features{of} must be [{v}, ...], got {tuple(features.shape)}")
+    for name, t in index.items():
+        if t is not None and t.dtype != torch.int64:
+            raise _unsupported(op, f"{name}{of} is {t.dtype}, not int64")
+    if pixels is not None and pixels.dtype != torch.int16:
+        raise _unsupported(op, f"pixels{of} are {pixels.dtype}, not int16")
+    if features is not None and features_dtype is not None and features.dtype != features_dtype:
+        raise _unsupported(op, f"features{of} are {features.dtype}, not {features_dtype}")
+    if max(n or 0, v, p or 0) >= 2 ** 31 - 1:
+        raise _unsupported(op, f"{n} points, {v} views, {p} atoms{of}")
+    device = require_device(*index.values(), pixels, features)
+    if dev is not None and device != dev:
+        raise _lib.DvaError(f"tensors on different devices: {dev} vs {device}")
+    return device, n, v, p
+
+
+def _mapping_outputs(dev, n, v, p, f):
+    """The five tensors of a mapping of ``n`` points, ``v`` views and ``p`` atoms: ``(pointers, images, atom_ptr,
+    pixels, features)``, the features fp32 ``[v, f]`` (``f`` may be 0), None for ``f`` None."""
+    return (torch.empty(n + 1, dtype=torch.int64, device=dev), torch.empty(v, dtype=torch.int64, device=dev),
+            torch.empty(v + 1, dtype=torch.int64, device=dev), torch.empty((p, 2), dtype=torch.int16, device=dev),
+            None if f is None else torch.empty((v, f), dtype=torch.float32, device=dev))
+
+
+def _mapping_workspace(op, query, dev, what, *args):
+    """``_lib.workspace(query, dev, *args)``; sizes the query refuses are what ``ops.<op>`` does not take."""
+    ws = _lib.unless_unsupported(_lib.workspace, query, dev, *args)
+    if ws is None:
+        raise _unsupported(op, what)
+    return ws
 
 
 def merge_mapping(pointers, images, atom_ptr, pixels, features, idx):
@@ -1827,29 +1883,16 @@ def merge_mapping(pointers, images, atom_ptr, pixels, features, idx):
     ``code == -2`` for what the kernels do not take (pixels other than int16, indices other than int64, 2^31 or more
     views or atoms)."""
     lib = _lib.load()
-    dev = require_device(pointers, images, atom_ptr, pixels, features, idx)
-    for name, t in (("pointers", pointers), ("images", images), ("atom_ptr", atom_ptr), ("idx", idx)):
-        if t.dim() != 1:
-            raise ValueError(f"ops.merge_mapping: {name} must be 1-D, got {tuple(t.shape)}")
-        if t.dtype != torch.int64:
-            raise _merge_unsupported(f"{name} is {t.dtype}, not int64")
-    if pixels.dim() != 2 or pixels.shape[1] != 2:
-        raise ValueError(f"ops.merge_mapping: pixels must be [P, 2], got {tuple(pixels.shape)}")
-    if pixels.dtype != torch.int16:
-        raise _merge_unsupported(f"pixels are {pixels.dtype}, not int16")
-    n, v, p = pointers.shape[0] - 1, images.shape[0], pixels.shape[0]
-    if n < 1 or atom_ptr.shape[0] != v + 1:
-        raise ValueError(f"ops.merge_mapping: {n} points, {v} views and {atom_ptr.shape[0]} atom pointers")
-    if features is not None and (features.dim() not in (1, 2) or features.shape[0] != v):
+    dev, n, v, p = _mapping_arguments("merge_mapping", pointers, images, atom_ptr, pixels, features,
+                                      features_dtype=None, idx=idx)
+    if n < 1:
+        raise ValueError(f"ops.merge_mapping: pointers of {n} points")
+    if features is not None and features.dim() > 2:
         raise ValueError(f"ops.merge_mapping: features must be [{v}, F] or [{v}], got {tuple(features.shape)}")
     if idx.shape[0] != n:
         return pointers, images, atom_ptr, pixels, features, False
-    try:
-        ws, nbytes = _lib.workspace("dva_mapping_merge_workspace_bytes", dev, n, v, p)
-    except _lib.DvaError as e:
-        if e.code != -2:
-            raise
-        raise _merge_unsupported(f"{n} points, {v} views, {p} atoms") from None
+    ws, nbytes = _mapping_workspace("merge_mapping", "dva_mapping_merge_workspace_bytes", dev,
+                                    f"{n} points, {v} views, {p} atoms", n, v, p)
     pointers, images, atom_ptr = pointers.contiguous(), images.contiguous(), atom_ptr.contiguous()
     pixels, idx = pixels.contiguous(), idx.contiguous()
     feat = None
@@ -1866,11 +1909,7 @@ def merge_mapping(pointers, images, atom_ptr, pixels, features, idx):
     m, v_out, p_out, ok = sizes.tolist()                  # host read: the sizes of the outputs
     if not ok:
         return pointers, images, atom_ptr, pixels, features, False
-    out_ptr = torch.empty(m + 1, dtype=torch.int64, device=dev)
-    out_img = torch.empty(v_out, dtype=torch.int64, device=dev)
-    out_aptr = torch.empty(v_out + 1, dtype=torch.int64, device=dev)
-    out_pix = torch.empty((p_out, 2), dtype=torch.int16, device=dev)
-    out_feat = None if feat is None else torch.empty((v_out, f), dtype=torch.float32, device=dev)
+    out_ptr, out_img, out_aptr, out_pix, out_feat = _mapping_outputs(dev, m, v_out, p_out, None if feat is None else f)
     with _timed("mapping_merge_fill", read + v * f * 4 + m * 8 + v_out * 16 + p_out * 4 + v_out * f * 4):
         check(lib.dva_mapping_merge_fill(ptr(pointers), ptr(images), ptr(atom_ptr), ptr(pixels), 2, ptr(feat_in), f,
                                          n, v, p, m, v_out, p_out, ptr(out_ptr), ptr(out_img), ptr(out_aptr),
@@ -1884,10 +1923,6 @@ def merge_mapping(pointers, images, atom_ptr, pixels, features, idx):
 # ---------------------------------------------------------------------------------------------
 # mapping selection: pick, views, images, crop (core/multimodal/image.py:2029-2342, csr.py:235-294)
 # ---------------------------------------------------------------------------------------------
-
-def _select_unsupported(what):
-    return _lib.DvaError(f"ops.select_mapping: {what}: {_lib._ERRORS[-2]}", code=-2)
-
 
 def select_mapping(pointers, images, atom_ptr, pixels, features, *, point_idx=None, view_mask=None, image_map=None,
                    compact=False, crop=None, num_images=None, image_keys=None):
@@ -1912,27 +1947,13 @@ def select_mapping(pointers, images, atom_ptr, pixels, features, *, point_idx=No
     sizes, flags and ``seen`` in one buffer.  Raises ``DvaError`` with ``code == -2`` for what the kernels do not take
     (pixels other than int16, indices other than int64, features other than fp32, 2^31 or more views or atoms)."""
     lib = _lib.load()
-    dev = require_device(pointers, images, atom_ptr, pixels, features, point_idx, view_mask, image_map, image_keys)
-    named = [("pointers", pointers), ("images", images), ("atom_ptr", atom_ptr), ("point_idx", point_idx),
-             ("image_map", image_map), ("image_keys", image_keys)]
-    for name, t in named:
-        if t is None:
-            continue
-        if t.dim() != 1:
-            raise ValueError(f"ops.select_mapping: {name} must be 1-D, got {tuple(t.shape)}")
-        if t.dtype != torch.int64:
-            raise _select_unsupported(f"{name} is {t.dtype}, not int64")
-    if pixels.dim() != 2 or pixels.shape[1] != 2:
-        raise ValueError(f"ops.select_mapping: pixels must be [P, 2], got {tuple(pixels.shape)}")
-    if pixels.dtype != torch.int16:
-        raise _select_unsupported(f"pixels are {pixels.dtype}, not int16")
-    n, v, p = pointers.shape[0] - 1, images.shape[0], pixels.shape[0]
-    if n < 1 or atom_ptr.shape[0] != v + 1:
-        raise ValueError(f"ops.select_mapping: {n} points, {v} views and {atom_ptr.shape[0]} atom pointers")
-    if features is not None and (features.dim() not in (1, 2) or features.shape[0] != v):
+    dev, n, v, p = _mapping_arguments("select_mapping", pointers, images, atom_ptr, pixels, features,
+                                      point_idx=point_idx, image_map=image_map, image_keys=image_keys)
+    require_device(pointers, view_mask)
+    if n < 1:
+        raise ValueError(f"ops.select_mapping: pointers of {n} points")
+    if features is not None and features.dim() > 2:
         raise ValueError(f"ops.select_mapping: features must be [{v}, F] or [{v}], got {tuple(features.shape)}")
-    if features is not None and features.dtype != torch.float32:
-        raise _select_unsupported(f"features are {features.dtype}, not float32")
     if view_mask is not None and (view_mask.dtype != torch.bool or tuple(view_mask.shape) != (v,)):
         raise ValueError(f"ops.select_mapping: view_mask must be bool [{v}]")
     if image_map is not None and (compact or crop is not None):
@@ -1953,7 +1974,7 @@ def select_mapping(pointers, images, atom_ptr, pixels, features, *, point_idx=No
         if offsets.dim() != 2 or offsets.shape[1] != 2:
             raise ValueError(f"ops.select_mapping: crop offsets must be [B, 2], got {tuple(offsets.shape)}")
         if offsets.dtype != torch.int64:
-            raise _select_unsupported(f"crop offsets are {offsets.dtype}, not int64")
+            raise _unsupported("select_mapping", f"crop offsets are {offsets.dtype}, not int64")
         if crop_w < 1 or crop_h < 1:
             raise ValueError(f"ops.select_mapping: crop size {(crop_w, crop_h)}")
         offsets = offsets.contiguous()
@@ -1964,12 +1985,8 @@ def select_mapping(pointers, images, atom_ptr, pixels, features, *, point_idx=No
         if num_images is None:
             raise ValueError("ops.select_mapping: compact needs num_images")
         b = int(num_images)
-    try:
-        ws, nbytes = _lib.workspace("dva_mapping_select_workspace_bytes", dev, m, v, b, int(crop is not None))
-    except _lib.DvaError as e:
-        if e.code != -2:
-            raise
-        raise _select_unsupported(f"{m} points, {v} views, {b} images") from None
+    ws, nbytes = _mapping_workspace("select_mapping", "dva_mapping_select_workspace_bytes", dev,
+                                    f"{m} points, {v} views, {b} images", m, v, b, int(crop is not None))
     pointers, images, atom_ptr, pixels = (pointers.contiguous(), images.contiguous(), atom_ptr.contiguous(),
                                           pixels.contiguous())
     point_idx, view_mask, image_map, image_keys = (None if t is None else t.contiguous()
@@ -1994,11 +2011,7 @@ def select_mapping(pointers, images, atom_ptr, pixels, features, *, point_idx=No
                 duplicate_keys=bool(flags & 4), num_views=v_out, num_atoms=p_out)
     if flags:
         return None, None, None, None, None, info
-    out_ptr = torch.empty(m + 1, dtype=torch.int64, device=dev)
-    out_img = torch.empty(v_out, dtype=torch.int64, device=dev)
-    out_aptr = torch.empty(v_out + 1, dtype=torch.int64, device=dev)
-    out_pix = torch.empty((p_out, 2), dtype=torch.int16, device=dev)
-    out_feat = None if feat is None else torch.empty((v_out, f), dtype=torch.float32, device=dev)
+    out_ptr, out_img, out_aptr, out_pix, out_feat = _mapping_outputs(dev, m, v_out, p_out, None if feat is None else f)
     with _timed("mapping_select_fill", read + p * 4 + m * 8 + v_out * (16 + 8 * f) + p_out * 8):
         check(lib.dva_mapping_select_fill(ptr(pointers), ptr(images), ptr(atom_ptr), ptr(pixels), 2, ptr(feat_in), f,
                                           n, v, p, *sel, v_out, p_out, ptr(out_ptr), ptr(out_img), ptr(out_aptr),
@@ -2015,16 +2028,10 @@ def mapping_image_stats(images, atom_ptr, pixels, num_images):
     has ``iinfo(int64).max`` / ``.min`` as minima / maxima, the sentinels of ``ImageMapping.bounding_boxes``.  No
     host synchronisation.  ``DvaError`` with ``code == -2`` for pixels other than int16 or indices other than int64."""
     lib = _lib.load()
-    dev = require_device(images, atom_ptr, pixels)
-    if images.dtype != torch.int64 or atom_ptr.dtype != torch.int64:
-        raise _lib.DvaError(f"ops.mapping_image_stats: indices are not int64: {_lib._ERRORS[-2]}", code=-2)
-    if pixels.dtype != torch.int16:
-        raise _lib.DvaError(f"ops.mapping_image_stats: pixels are {pixels.dtype}, not int16: {_lib._ERRORS[-2]}",
-                            code=-2)
-    v, p, b = images.shape[0], pixels.shape[0], int(num_images)
-    if images.dim() != 1 or tuple(atom_ptr.shape) != (v + 1,) or pixels.dim() != 2 or pixels.shape[1] != 2 or b < 0:
-        raise ValueError(f"ops.mapping_image_stats: {v} views, {tuple(atom_ptr.shape)} atom pointers, pixels "
-                         f"{tuple(pixels.shape)}, {b} images")
+    dev, _, v, p = _mapping_arguments("mapping_image_stats", None, images, atom_ptr, pixels)
+    b = int(num_images)
+    if b < 0:
+        raise ValueError(f"ops.mapping_image_stats: {b} images")
     images, atom_ptr, pixels = images.contiguous(), atom_ptr.contiguous(), pixels.contiguous()
     stats = torch.empty((5, b), dtype=torch.int64, device=dev)
     with _timed("mapping_image_stats", v * 16 + p * 4 + b * 40):
@@ -2037,18 +2044,6 @@ def mapping_image_stats(images, atom_ptr, pixels, num_images):
 # the image picks: CenterRoll and the coverage counts of PickImagesFromMemoryCredit
 # (core/data_transform/multimodal/image.py:962-1037, :765-874)
 # ---------------------------------------------------------------------------------------------
-
-def _pick_mapping_arguments(name, images, atom_ptr, pixels):
-    if images.dtype != torch.int64 or atom_ptr.dtype != torch.int64:
-        raise _lib.DvaError(f"ops.{name}: indices are not int64: {_lib._ERRORS[-2]}", code=-2)
-    if pixels.dtype != torch.int16:
-        raise _lib.DvaError(f"ops.{name}: pixels are {pixels.dtype}, not int16: {_lib._ERRORS[-2]}", code=-2)
-    dev = require_device(images, atom_ptr, pixels)
-    v, p = images.shape[0], pixels.shape[0]
-    if images.dim() != 1 or tuple(atom_ptr.shape) != (v + 1,) or pixels.dim() != 2 or pixels.shape[1] != 2:
-        raise ValueError(f"ops.{name}: {v} views, {tuple(atom_ptr.shape)} atom pointers, pixels {tuple(pixels.shape)}")
-    return dev, v, p
-
 
 def mapping_center_rollings(images, atom_ptr, pixels, num_images, width, angular_res=16):
     """CenterRoll's offsets (reference :999-1029) in one device operation: ``(rollings, info)``.  ``rollings`` int64
@@ -2063,12 +2058,12 @@ def mapping_center_rollings(images, atom_ptr, pixels, num_images, width, angular
     lib = _lib.load()
     if not isinstance(angular_res, int) or isinstance(angular_res, bool) or not 1 <= angular_res <= 256:
         raise ValueError(f"ops.mapping_center_rollings: angular_res must be an int in 1..256, got {angular_res!r}")
-    dev, v, p = _pick_mapping_arguments("mapping_center_rollings", images, atom_ptr, pixels)
+    dev, _, v, p = _mapping_arguments("mapping_center_rollings", None, images, atom_ptr, pixels)
     b, w = int(num_images), int(width)
     if b < 0 or w < 1:
         raise ValueError(f"ops.mapping_center_rollings: {b} images of width {w}")
     if w > 32767:
-        raise _lib.DvaError(f"ops.mapping_center_rollings: width {w} above 32767: {_lib._ERRORS[-2]}", code=-2)
+        raise _unsupported("mapping_center_rollings", f"width {w} above 32767")
     images, atom_ptr, pixels = images.contiguous(), atom_ptr.contiguous(), pixels.contiguous()
     ws, nbytes = _lib.workspace("dva_mapping_center_workspace_bytes", dev, b)
     rollings = torch.empty(b, dtype=torch.int64, device=dev)
@@ -2087,16 +2082,12 @@ def roll_mapping_pixels(images, atom_ptr, pixels, rollings, width):
     ``[B]``.  Returns ``pixels``.  No host synchronisation.  ``DvaError`` with ``code == -2`` for pixels other than
     int16, indices other than int64 or ``width > 32767``."""
     lib = _lib.load()
-    dev, v, p = _pick_mapping_arguments("roll_mapping_pixels", images, atom_ptr, pixels)
-    require_device(images, rollings)
-    if rollings.dtype != torch.int64:
-        raise _lib.DvaError(f"ops.roll_mapping_pixels: rollings are {rollings.dtype}, not int64: {_lib._ERRORS[-2]}",
-                            code=-2)
+    _, _, v, p = _mapping_arguments("roll_mapping_pixels", None, images, atom_ptr, pixels, rollings=rollings)
     w = int(width)
-    if rollings.dim() != 1 or w < 1:
-        raise ValueError(f"ops.roll_mapping_pixels: rollings {tuple(rollings.shape)}, width {w}")
+    if w < 1:
+        raise ValueError(f"ops.roll_mapping_pixels: width {w}")
     if w > 32767:
-        raise _lib.DvaError(f"ops.roll_mapping_pixels: width {w} above 32767: {_lib._ERRORS[-2]}", code=-2)
+        raise _unsupported("roll_mapping_pixels", f"width {w} above 32767")
     if not pixels.is_contiguous() or pixels.data_ptr() % 4:
         raise ValueError("ops.roll_mapping_pixels: pixels must be contiguous and 4-byte aligned to be rolled in place")
     images, atom_ptr, rollings = images.contiguous(), atom_ptr.contiguous(), rollings.contiguous()
@@ -2132,21 +2123,15 @@ class MappingCoverage:
         lib = _lib.load()
         if not isinstance(items, (list, tuple)) or len(items) == 0:
             raise ValueError("ops.MappingCoverage: a non-empty list of items")
-        self.device = require_device(*[t for item in items for t in item[:2]])
         self.num_points = int(num_points)
         if self.num_points < 1:
             raise ValueError(f"ops.MappingCoverage: {self.num_points} points")
         self._keep = []
         self._descriptors = (_lib.DvaCoverageItem * len(items))()
-        base = 0
+        base, self.device = 0, None
         for b, (pointers, images, num_images) in enumerate(items):
-            for name, t in (("pointers", pointers), ("images", images)):
-                if t.dim() != 1:
-                    raise ValueError(f"ops.MappingCoverage: {name} of item {b} must be 1-D, got {tuple(t.shape)}")
-                if t.dtype != torch.int64:
-                    raise _lib.DvaError(f"ops.MappingCoverage: {name} of item {b} is {t.dtype}, not int64: "
-                                        f"{_lib._ERRORS[-2]}", code=-2)
-            n, v, k = pointers.shape[0] - 1, images.shape[0], int(num_images)
+            self.device, n, v, _ = _mapping_arguments("MappingCoverage", pointers, images, item=b, dev=self.device)
+            k = int(num_images)
             if n < 0 or n > self.num_points or k < 0:
                 raise ValueError(f"ops.MappingCoverage: item {b} has {n} points of {self.num_points} and {k} images")
             pointers, images = pointers.contiguous(), images.contiguous()
@@ -2160,8 +2145,7 @@ class MappingCoverage:
         if self.num_images < 1:
             raise ValueError("ops.MappingCoverage: no image")
         if max(self.num_points, self.num_images) >= 2 ** 31 - 1:
-            raise _lib.DvaError(f"ops.MappingCoverage: {self.num_points} points, {self.num_images} images: "
-                                f"{_lib._ERRORS[-2]}", code=-2)
+            raise _unsupported("MappingCoverage", f"{self.num_points} points, {self.num_images} images")
         self._lib = lib
         self.covered = torch.zeros(self.num_points, dtype=torch.uint8, device=self.device)
         self._counts = torch.zeros((2, self.num_images), dtype=torch.int64, device=self.device)
@@ -2185,10 +2169,6 @@ class MappingCoverage:
 # mapping collation: CSRBatch.from_csr_list on ImageMappings + insert_empty_groups (core/multimodal/csr.py:352-420)
 # ---------------------------------------------------------------------------------------------
 
-def _collate_unsupported(what):
-    return _lib.DvaError(f"ops.collate_mapping: {what}: {_lib._ERRORS[-2]}", code=-2)
-
-
 def collate_mapping(items, point_bases=None, num_points=None):
     """Stack mappings into one batch mapping in one device operation: ``(pointers, images, atom_ptr, pixels, features,
     image_offsets)``.  ``items`` is a list of ``(pointers, images, atom_ptr, pixels, features_or_None)`` device tensors
@@ -2205,37 +2185,22 @@ def collate_mapping(items, point_bases=None, num_points=None):
     lib = _lib.load()
     if not isinstance(items, (list, tuple)) or len(items) == 0:
         raise ValueError("ops.collate_mapping: a non-empty list of items")
-    dev = require_device(*[t for item in items for t in item])
     with_features = [item[4] is not None for item in items]
     if any(with_features) and not all(with_features):
-        raise _collate_unsupported("features on some items only")
-    trailing = None
+        raise _unsupported("collate_mapping", "features on some items only")
+    trailing = dev = None
     rows, keep = [], []
-    for b, (pointers, images, atom_ptr, pixels, features) in enumerate(items):
-        for name, t in (("pointers", pointers), ("images", images), ("atom_ptr", atom_ptr)):
-            if t.dim() != 1:
-                raise ValueError(f"ops.collate_mapping: {name} of item {b} must be 1-D, got {tuple(t.shape)}")
-            if t.dtype != torch.int64:
-                raise _collate_unsupported(f"{name} of item {b} is {t.dtype}, not int64")
-        if pixels.dim() != 2 or pixels.shape[1] != 2:
-            raise ValueError(f"ops.collate_mapping: pixels of item {b} must be [P, 2], got {tuple(pixels.shape)}")
-        if pixels.dtype != torch.int16:
-            raise _collate_unsupported(f"pixels of item {b} are {pixels.dtype}, not int16")
-        n, v, p = pointers.shape[0] - 1, images.shape[0], pixels.shape[0]
-        if n < 0 or atom_ptr.shape[0] != v + 1:
-            raise ValueError(f"ops.collate_mapping: item {b} has {n} points, {v} views and {atom_ptr.shape[0]} atom "
-                             f"pointers")
+    for b, item in enumerate(items):
+        dev, n, v, p = _mapping_arguments("collate_mapping", *item, item=b, dev=dev)
+        if n < 0:
+            raise ValueError(f"ops.collate_mapping: pointers of item {b} are empty")
+        features = item[4]
         if features is not None:
-            if features.dim() < 1 or features.shape[0] != v:
-                raise ValueError(f"ops.collate_mapping: features of item {b} must be [{v}, ...], got "
-                                 f"{tuple(features.shape)}")
-            if features.dtype != torch.float32:
-                raise _collate_unsupported(f"features of item {b} are {features.dtype}, not float32")
             if trailing is None:
                 trailing = tuple(features.shape[1:])
             elif tuple(features.shape[1:]) != trailing:
-                raise _collate_unsupported(f"features of item {b} are [V, {tuple(features.shape[1:])}], those of item 0 "
-                                           f"[V, {trailing}]")
+                raise _unsupported("collate_mapping", f"features of item {b} are [V, {tuple(features.shape[1:])}], "
+                                                      f"those of item 0 [V, {trailing}]")
         rows.append((n, v, p))
     f = 0 if trailing is None else int(np.prod(trailing, dtype=np.int64))
     if point_bases is None:
@@ -2250,7 +2215,7 @@ def collate_mapping(items, point_bases=None, num_points=None):
     n_out = end if num_points is None else int(num_points)
     v_out, p_out = sum(r[1] for r in rows), sum(r[2] for r in rows)
     if max(n_out, v_out, p_out) >= 2 ** 31 - 1:
-        raise _collate_unsupported(f"{n_out} points, {v_out} views, {p_out} atoms")
+        raise _unsupported("collate_mapping", f"{n_out} points, {v_out} views, {p_out} atoms")
     descriptors = (_lib.DvaCollateItem * len(rows))()
     for b, ((pointers, images, atom_ptr, pixels, features), (n, v, p)) in enumerate(zip(items, rows)):
         # (no aten call for what is contiguous already: a batch is launch-bound, and so is the host in front of it)
@@ -2269,11 +2234,8 @@ def collate_mapping(items, point_bases=None, num_points=None):
         d.features = feat.data_ptr() if feat is not None and feat.numel() else None
         d.n_points, d.n_views, d.n_atoms, d.point_base = n, v, p, bases[b]
     ws, nbytes = _lib.workspace("dva_mapping_collate_workspace_bytes", dev, len(rows))
-    out_ptr = torch.empty(n_out + 1, dtype=torch.int64, device=dev)
-    out_img = torch.empty(v_out, dtype=torch.int64, device=dev)
-    out_aptr = torch.empty(v_out + 1, dtype=torch.int64, device=dev)
-    out_pix = torch.empty((p_out, 2), dtype=torch.int16, device=dev)
-    out_feat = None if trailing is None else torch.empty((v_out, f), dtype=torch.float32, device=dev)
+    out_ptr, out_img, out_aptr, out_pix, out_feat = _mapping_outputs(dev, n_out, v_out, p_out,
+                                                                     None if trailing is None else f)
     offsets = torch.empty(len(rows), dtype=torch.int64, device=dev)
     moved = (n_out + 1) * 8 + sum(r[0] for r in rows) * 8 + v_out * (40 + 8 * f) + p_out * 8
     with _timed("mapping_collate", moved):
@@ -3482,7 +3444,7 @@ def cloud_augment(pos, steps, norm=None, noise=None):
             n_reduce += 1
         params[k * CLOUD_STEP_PARAMS:(k + 1) * CLOUD_STEP_PARAMS] = row
     if 3 * n >= 1 << 31:
-        raise _lib.DvaError(f"ops.cloud_augment: {n} points; the kernels take 3 N < 2^31 (DVA_ERR_UNSUPPORTED)", code=-2)
+        raise _unsupported("cloud_augment", f"{n} points; the kernels take 3 N < 2^31")
     out = torch.empty((n, 3), dtype=torch.float32, device=dev)
     norm_out = norm if not with_norm else torch.empty((n, 3), dtype=torch.float32, device=dev)
     consts = torch.empty((n_reduce, 3), dtype=torch.float32, device=dev)

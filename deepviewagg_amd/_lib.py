@@ -180,6 +180,10 @@ SIGNATURES = {
     "dva_gather_segment_max_bwd": (ctypes.c_int, [_vp] * 8 + [_i64, _i64, _i64, _i32, _i32, _vp]),
     "dva_gather_segment_reduce_fwd": (ctypes.c_int, [_vp] * 5 + [_i64, _i64, _i64, _i32, _i32, _i32, _vp]),
     "dva_gather_segment_reduce_bwd": (ctypes.c_int, [_vp] * 7 + [_i64, _i64, _i64, _i32, _i32, _i32, _vp]),
+    "dva_interp_segment_reduce_fwd": (ctypes.c_int, [_vp] * 6 + [_i64, _i64, _i64, _i32, _i32, _i32, _vp]),
+    "dva_interp_segment_reduce_bwd": (ctypes.c_int, [_vp] * 8 + [_i64, _i64, _i64, _i32, _i32, _i32, _vp]),
+    "dva_interp_anchor_rows_sum": (ctypes.c_int, [_vp] * 8 + [_i64, _i64, _i32, _i32, _i32, _vp]),
+    "dva_interp_anchor_fixup": (ctypes.c_int, [_vp] * 9 + [_i64, _i64, _i32, _i32, _i32, _vp]),
     "dva_chain_keys_compat": (ctypes.c_int, [_vp] * 14 + [_i32, _f32, _i64, _i64, _vp]),
     "dva_chain_attn_fwd_keys": (ctypes.c_int, [_vp] * 12 + [_f32] + [_vp] * 8 + [_i64, _i64, _i64, _i32, _i32, _i32, _f32, _vp]),
     "dva_qkv_dquery": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _i64, _i64, _i32, _f32, _vp]),

@@ -237,6 +237,11 @@ class BimodalCSRPool(nn.Module, _SaveLast):
                 # VIEW-level mean / sum / min pool of lazily gathered values (the view pooling of the image-only models
                 # and of the mean-pool baselines): the same kernels, a plain [N, C] tensor out
                 return ops.gather_segment_reduce(x_mod, csr_idx, self._mode, level='view')
+            if not self.save_last and ops.interp_segment_reduce_applicable(x_mod, csr_idx, self._mode):
+                # BILINEAR lazy gather under any of the four modes, at the view level or at the atomic level of a non-exact
+                # mapping: interpolation and reduction in one kernel, forward and backward without a [P, C] tensor.  The
+                # plain pooled tensor comes out at both levels -- what the materialised route hands on
+                return ops.interp_segment_reduce(x_mod, csr_idx, self._mode, level='view')
             x_mod = x_mod.materialize()
         x_pool = segment_csr(x_mod, csr_idx, reduce=self._mode)
         self._save(x_map, x_mod, csr_idx)
@@ -276,6 +281,19 @@ class HeuristicBimodalCSRPool(nn.Module, _SaveLast):
             x_pool = ops.gather_rows(x_mod.rows, sel.to(torch.int32)) if x_mod.row_idx.shape[0] else \
                 x_mod.rows.new_zeros((arg_idx.shape[0], x_mod.rows.shape[1]))
             # unseen points: exact zeros whatever the (unrelated) gathered row holds -- 0 * Inf would be NaN
+            return torch.where(seen.unsqueeze(1), x_pool, torch.zeros((), dtype=x_pool.dtype, device=x_pool.device))
+        if (isinstance(x_mod, ops.InterpolatedFeatures) and x_mod.parts is None and x_mod.rows.is_cuda
+                and not self.save_last):
+            # bilinear lazy gather of one setting: only the SELECTED view of every point is interpolated -- N
+            # interpolations instead of V (several settings keep materialising: the selection crosses their maps)
+            _, arg_idx = ops.segment_csr_arg(x_map[:, self._feat].float(), csr_idx, reduce=self._mode)
+            arg_idx = arg_idx.reshape(-1).long()
+            seen = arg_idx >= 0
+            if x_mod.shape[0] == 0:
+                return x_mod.rows.new_zeros((arg_idx.shape[0], x_mod.rows.shape[1]))
+            sel = arg_idx.clamp(min=0)
+            x_pool = ops.gather_bilinear(x_mod.x, x_mod.packed_idx[sel], x_mod.coords[sel])
+            # unseen points: exact zeros whatever the (unrelated) interpolated row holds -- 0 * Inf would be NaN
             return torch.where(seen.unsqueeze(1), x_pool, torch.zeros((), dtype=x_pool.dtype, device=x_pool.device))
         x_mod = _materialize(x_mod)
         # arg of the per-group extremum of the heuristic feature (first row on ties, -1 if unseen)

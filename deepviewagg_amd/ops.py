@@ -12,6 +12,7 @@ ops; names and argument meaning follow the reference call site
 ``gather_nearest``         core/multimodal/image.py:1285 (``x[feature_map_indexing]``)
 ``gather_bilinear``        core/multimodal/image.py:105-170 (``sparse_interpolation``)
 ``gather_segment_reduce``  pooling.py:14-71 (``BimodalCSRPool`` mean / sum / min) on image.py:1285, without the gather
+``interp_segment_reduce``  pooling.py:14-71 (``BimodalCSRPool`` max / mean / sum / min) on image.py:105-170, without the gather
 ``grid_cluster``           core/data_transform/grid_transform.py:143-148 (grid_cluster / voxel_grid)
 ``grid_mean``              grid_transform.py:81 (``scatter_mean``)
 ``grid_majority``          grid_transform.py:76-79 (one_hot + ``scatter_add`` + argmax)
@@ -1268,6 +1269,147 @@ def lazy_gather_bilinear(x, packed_idx, coords, exact):
         check(lib.dva_gather_bilinear_taps_anchor(ptr(packed_idx), ptr(coords), P, B, H, W, ptr(rows4), ptr(w4),
                                                   ptr(anchors), stream_of(x)), "dva_gather_bilinear_taps_anchor")
     return InterpolatedFeatures(x, packed_idx, coords, rows4, w4, anchors, exact)
+
+
+class _InterpSegmentReduce(torch.autograd.Function):
+    """``segment_csr(x_mod.materialize(), csr_idx, reduce)`` of a bilinear lazy gather for max / mean / sum / min without
+    the [P, C] tensor, forward and backward (csrc/interp_reduce.hip).  The gradient goes to the stacked map rows; the plan
+    (over the P anchors where ``_anchor_ok`` serves the shape and ``anchors`` / ``geometry`` are given, over the 4 P taps
+    elsewhere) and the segment of every item are built in backward and not kept."""
+
+    @staticmethod
+    def forward(ctx, rows, tap_rows, tap_weights, csr_idx, reduce, anchors=None, geometry=None):
+        lib = _lib.load()
+        require_device(rows, tap_rows, tap_weights, csr_idx)
+        rows = rows.contiguous()
+        (R, C), S, P = rows.shape, csr_idx.shape[0] - 1, tap_rows.shape[0]
+        code = _lib.REDUCE_CODE[reduce]
+        has_arg = code in (_lib.DVA_MAX, _lib.DVA_MIN)
+        out = torch.empty((S, C), dtype=rows.dtype, device=rows.device)
+        arg = torch.empty((S, C), dtype=torch.int16, device=rows.device) if has_arg else None
+        es = rows.element_size()
+        with _timed("interp_segment_reduce_fwd", P * (32 + 4 * C * es) + S * (8 + C * es) + (S * C * 2 if has_arg else 0)):
+            check(lib.dva_interp_segment_reduce_fwd(ptr(rows), ptr(tap_rows), ptr(tap_weights), ptr(csr_idx), ptr(out),
+                                                    ptr(arg), S, P, R, C, dtype_code(rows), code, stream_of(rows)),
+                  "dva_interp_segment_reduce_fwd")
+        ctx.save_for_backward(tap_rows, tap_weights, csr_idx, arg if has_arg else csr_idx,
+                              anchors if anchors is not None else csr_idx)
+        ctx.meta = (R, C, rows.dtype, code, has_arg, geometry if anchors is not None else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = _lib.load()
+        tap_rows, tap_weights, csr_idx, arg, anchors = ctx.saved_tensors
+        R, C, dt, code, has_arg, geometry = ctx.meta
+        S, P = csr_idx.shape[0] - 1, tap_rows.shape[0]
+        none = (None,) * 6
+        if P == 0 or R == 0 or C == 0:
+            return (torch.zeros((R, C), dtype=dt, device=gout.device),) + none
+        gout = gout.contiguous().to(dt)
+        soi = csr_expand(csr_idx, P)
+        if INTERP_REDUCE_ANCHOR and geometry is not None and _anchor_ok(C, dt):
+            return (_interp_anchor_backward(gout, arg if has_arg else None, csr_idx, tap_rows, tap_weights, anchors, soi,
+                                            geometry, R, C, code).to(dt),) + none
+        perm, row_ptr = row_plan(tap_rows.view(-1), R, with_counts=False, split=False)[0]
+        grows = torch.empty((R, C), dtype=dt, device=gout.device)
+        es = gout.element_size()
+        per_tap = 12 + C * es + (0 if code == _lib.DVA_SUM else 8) + (2 * C if has_arg else 0)
+        with _timed("interp_segment_reduce_bwd", 4 * P * per_tap + R * (4 + C * es)):
+            check(lib.dva_interp_segment_reduce_bwd(ptr(gout), ptr(arg) if has_arg else None, ptr(csr_idx), ptr(perm),
+                                                    ptr(row_ptr), ptr(tap_weights), ptr(soi), ptr(grows), S, P, R, C,
+                                                    dtype_code(gout), code, stream_of(gout)),
+                  "dva_interp_segment_reduce_bwd")
+        return (grows,) + none
+
+
+def _interp_anchor_backward(gout, arg, csr_idx, tap_rows, tap_weights, anchors, soi, geometry, R, C, code):
+    """fp32 [R, C] gradient of ``_InterpSegmentReduce`` over the ANCHOR plan of the items, as ``bilinear_scatter`` forms it
+    for a materialised gradient, the [P, C] gradient being evaluated on the fly from ``gout`` [S, C]: per-anchor sums
+    (``dva_interp_anchor_rows_sum``, images in chunks within the workspace budget), the 2 x 2 stencil
+    (``dva_anchor_combine``), then the items of the dummy anchor tap by tap (``dva_interp_anchor_fixup``)."""
+    lib = _lib.load()
+    P, dev, st, es = tap_rows.shape[0], gout.device, stream_of(gout), gout.element_size()
+    dummy = n_anchors(geometry)
+    perm, row_ptr = anchor_plan(anchors, geometry)
+    out = torch.empty((R, C), dtype=torch.float32, device=dev)
+    chunks = [_anchor_chunk_images(b, (h + 1) * (w + 1) * 4 * C * 4, dev) for b, h, w in geometry]
+    S = torch.empty((max(min(i, b) * (h + 1) * (w + 1) for i, (b, h, w) in zip(chunks, geometry)) + 1, 4, C),
+                    dtype=torch.float32, device=dev)
+    per_item = 24 + C * es + (0 if code == _lib.DVA_SUM else 16) + (2 * C if arg is not None else 0)
+    a_off = r_off = 0
+    for imgs, (Bs, Hs, Ws) in zip(chunks, geometry):
+        per_image = (Hs + 1) * (Ws + 1)
+        for b0 in range(0, Bs, imgs):
+            nb = min(imgs, Bs - b0)
+            a0, na = a_off + b0 * per_image, nb * per_image
+            with _timed("interp_anchor_sum", P * per_item * na // max(dummy, 1) + na * 4 * C * 4):
+                check(lib.dva_interp_anchor_rows_sum(ptr(gout), ptr(arg), ptr(csr_idx), ptr(perm),
+                                                     ptr(row_ptr[a0:a0 + na + 1]), ptr(tap_weights), ptr(soi), ptr(S), na,
+                                                     P, C, dtype_code(gout), code, st), "dva_interp_anchor_rows_sum")
+            with _timed("bilinear_anchor_combine", na * 4 * C * 4 + nb * Hs * Ws * C * 4):
+                check(lib.dva_anchor_combine(ptr(S), ptr(out[r_off + b0 * Hs * Ws:]), nb, Hs, Ws, C, st),
+                      "dva_anchor_combine")
+        a_off += Bs * per_image
+        r_off += Bs * Hs * Ws
+    check(lib.dva_interp_anchor_fixup(ptr(gout), ptr(arg), ptr(csr_idx), ptr(perm), ptr(row_ptr), ptr(tap_rows),
+                                      ptr(tap_weights), ptr(soi), ptr(out), dummy, P, C, dtype_code(gout), code, st),
+          "dva_interp_anchor_fixup")
+    return out
+
+
+# A/B and tests: False sends max / mean / sum / min pools of a bilinear lazy gather down the materialised route
+# (``x_mod.materialize()`` + ``segment_csr``)
+LAZY_INTERP_REDUCE = True
+# A/B and tests: False keeps the backward of ``interp_segment_reduce`` on the plan over the 4 P taps where the anchor plan
+# (P keys, ``_anchor_ok`` shapes) would serve it
+INTERP_REDUCE_ANCHOR = True
+_INTERP_REDUCES = ("max", "mean", "sum", "min")
+
+
+def interp_segment_reduce_applicable(x_mod, csr_idx, reduce):
+    """Does ``interp_segment_reduce`` serve this pool?  A bilinear lazy gather (one setting or a ``cat`` of several) on the
+    device with fp32 / bf16 / fp16 map rows, any C >= 1; 4 P taps, R map rows and S segments below 2^31 (int32 tap plan);
+    ``max`` and ``min`` keep uint16 arg offsets, so their segments own <= 65534 items.  Not gated on C: on shapes whose
+    backward runs over the tap plan (``_anchor_ok`` false) the route measured 0.74 to 1.07 x the materialised one at C = 13
+    (profiles/view_pool_bilinear_bench.json) and is kept there for its 1.75 to 2.1 x lower peak memory."""
+    if not (LAZY_INTERP_REDUCE and isinstance(x_mod, InterpolatedFeatures) and reduce in _INTERP_REDUCES):
+        return False
+    rows, taps = x_mod.rows, x_mod.tap_rows
+    if not (rows.is_cuda and csr_idx.is_cuda and taps.is_cuda and rows.dim() == 2 and rows.shape[1] >= 1
+            and rows.dtype in (torch.float32, torch.bfloat16, torch.float16)
+            and max(rows.shape[0], 4 * taps.shape[0], csr_idx.shape[0]) < (1 << 31)):
+        return False
+    return reduce in ("mean", "sum") or _atoms_per_view_ok(csr_idx)
+
+
+def _taps16(t):
+    """The [P, 4] tap tensor as the kernels read it: contiguous 16-byte records."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def interp_segment_reduce(x_mod, csr_idx, reduce, level="view"):
+    """Max / mean / sum / min pool of bilinearly gathered features over CSR segments, interpolation and reduction in one
+    kernel (reference: ``BimodalCSRPool(mode)`` on ``sparse_interpolation(x, coords, batch)``, modules/multimodal/
+    pooling.py:14-71 on core/multimodal/image.py:105-170).  ``level='view'``: the plain [S, C] tensor.  ``level='atom'``
+    (atomic pool of a non-exact mapping, modules.py:400-407): the pooled [V, C] rows as ``GatheredFeatures`` under the
+    identity gather, as ``gather_segment_reduce`` and ``gather_segment_max`` return them."""
+    if reduce not in _INTERP_REDUCES:
+        raise ValueError(f"interp_segment_reduce reduces by one of {_INTERP_REDUCES}, got '{reduce}'")
+    if level not in ("view", "atom"):
+        raise ValueError(f"level must be 'view' or 'atom', got '{level}'")
+    if not isinstance(x_mod, InterpolatedFeatures):
+        raise TypeError(f"interp_segment_reduce pools InterpolatedFeatures, got {type(x_mod).__name__}")
+    csr_idx = _check_ptr(csr_idx)
+    anchors = getattr(x_mod, "anchors", None)
+    xv = _InterpSegmentReduce.apply(x_mod.rows, _taps16(x_mod.tap_rows), _taps16(x_mod.tap_weights), csr_idx, reduce,
+                                    anchors.contiguous() if anchors is not None else None, _geometry(x_mod.geometry))
+    if level == "view":
+        return xv
+    V = xv.shape[0]
+    ident = torch.arange(V + 1, dtype=torch.int32, device=xv.device)
+    return GatheredFeatures(xv, ident[:V], torch.ones(V, dtype=torch.int32, device=xv.device), True, (ident[:V], ident))
 
 
 LAZY_TYPES = (GatheredFeatures, InterpolatedFeatures)     # what .materialize() turns into the reference's [P, C] tensor

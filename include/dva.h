@@ -15,8 +15,8 @@
  * of "feature" buffers (void*): fp32, bf16 or fp16; scores / mapping features / statistics are fp32.
  * DVA_F16 (torch.float16, autocast(float16)) is accepted by: dva_segment_csr_fwd / _bwd, dva_gather_csr,
  * dva_gather_nearest_fwd / _bwd, dva_gather_bilinear_fwd / _bwd, dva_gather_rows_sum, dva_gather_segment_max_fwd /
- * _bwd, dva_gather_segment_reduce_fwd / _bwd, dva_view_attention_*, dva_view_gather_attention_*, dva_view_gather_rows_grad,
- * dva_view_gather_rows_grad_rec16_to, dva_rowbn_*, dva_chain_attn_fwd_dt, dva_chain_attn_bwd_dt and
+ * _bwd, dva_gather_segment_reduce_fwd / _bwd, dva_interp_segment_reduce_fwd / _bwd, dva_view_attention_*,
+ * dva_view_gather_attention_*, dva_view_gather_rows_grad, dva_view_gather_rows_grad_rec16_to, dva_rowbn_*, dva_chain_attn_fwd_dt, dva_chain_attn_bwd_dt and
  * dva_plan_split_rows_grad (dtype = out_dtype = DVA_F16).  Every other entry with a dtype argument returns
  * DVA_ERR_UNSUPPORTED for it before launching anything.
  */
@@ -160,6 +160,50 @@ int dva_gather_segment_reduce_fwd(const void* rows, const int32_t* row_idx, cons
 int dva_gather_segment_reduce_bwd(const void* grad_out, const void* arg, const int64_t* seg_ptr, const int32_t* perm,
                                   const int32_t* row_ptr, const int32_t* seg_of_item, void* grad_rows, int64_t S,
                                   int64_t P, int64_t R, int32_t C, int32_t dtype, int32_t reduce, void* stream);
+
+/* The BILINEAR gather (sparse_interpolation, image.py:105-170) fused with the MAX / MEAN / SUM / MIN pool behind it
+ * (BimodalCSRPool(mode), pooling.py:14-71): out[s][c] = reduce over the items p in [seg_ptr[s], seg_ptr[s+1]) of v(p, c),
+ * v(p, c) = ((w0 x0 + w1 x1) + w2 x2) + w3 x3 with x_k = rows[tap_rows[p][k]][c] and w_k = tap_weights[p][k] -- the
+ * arithmetic of dva_gather_bilinear_fwd (products and sums rounded one by one, no fma), rounded once to the storage type as
+ * the [P, C] tensor would have held it -- and on those values dva_segment_csr_fwd's arithmetic (fp32 accumulation from 0
+ * in item order, MEAN divides once by the fp32 count, one rounding, empty segments give 0, MAX / MIN: first item on ties,
+ * NaN as that entry treats it): bit for bit the materialised composition, no [P, C] tensor.  rows [R][C] fp32 / bf16 /
+ * fp16 = the stacked map rows (several settings: the numbering of the concatenation), tap_rows int32 [P][4] and
+ * tap_weights fp32 [P][4] in the tap order of dva_gather_bilinear_taps_anchor, both 16-byte aligned (else
+ * DVA_ERR_UNSUPPORTED).  Any C >= 1: 16-byte row accesses when C % (16 / s) == 0 and rows, out and arg are 16-byte
+ * aligned, element accesses otherwise; one wavefront per segment.  arg (MAX / MIN, else nullable) uint16 [S][C] = offset
+ * of the winning item inside its segment (0xffff: none; segments must own <= 65534 items).
+ * _bwd: grad_rows [R][C] in the rows' dtype, WRITTEN (every element once, fp32 accumulation, one rounding; a map row
+ * without taps gets 0) = sum over the taps (p, k) with tap_rows[p][k] == r of tap_weights[p][k] * g(p, c), g(p, c) =
+ * grad_out[s][c] (SUM), grad_out[s][c] / count_s (MEAN, fp32 true division) or grad_out[s][c] where arg[s][c] == p -
+ * seg_ptr[s], else 0 (MAX / MIN), s = seg_of_item[p] (int32 [P], dva_csr_expand); a segmented reduction over the row plan
+ * of the 4 P taps (perm int32 [4 P] = taps 4 p + k sorted by map row, row_ptr int32 [R + 1], as dva_row_plan gives them for
+ * the flat tap_rows), one wavefront per map row, no float atomics: deterministic.  No [P, C] gradient exists.
+ * 4 P, R or S of 2^31 or more return DVA_ERR_UNSUPPORTED. */
+int dva_interp_segment_reduce_fwd(const void* rows, const int32_t* tap_rows, const float* tap_weights,
+                                  const int64_t* seg_ptr, void* out, void* arg, int64_t S, int64_t P, int64_t R, int32_t C,
+                                  int32_t dtype, int32_t reduce, void* stream);
+int dva_interp_segment_reduce_bwd(const void* grad_out, const void* arg, const int64_t* seg_ptr, const int32_t* perm,
+                                  const int32_t* row_ptr, const float* tap_weights, const int32_t* seg_of_item,
+                                  void* grad_rows, int64_t S, int64_t P, int64_t R, int32_t C, int32_t dtype,
+                                  int32_t reduce, void* stream);
+
+/* The same backward over the ANCHOR plan of the items (anchors of dva_gather_bilinear_taps_anchor; perm int32 [P] = items
+ * sorted by anchor, row_ptr int32 [n_anchors + 1], as dva_row_plan gives them): S fp32 [n_anchors][4][C], WRITTEN, =
+ * sum over the items p of anchor a of tap_weights[p][k] * g(p, c) -- dva_anchor_rows_sum with g evaluated on the fly, P keys
+ * instead of 4 P and every gradient row of a segment read once per item; dva_anchor_combine turns S into the fp32 map
+ * gradient.  fp32 / bf16 with C / (16 / s) a power of two <= 64 and 16-byte aligned grad_out, arg, tap_weights and S;
+ * anything else (fp16 among it) returns DVA_ERR_UNSUPPORTED: the caller takes dva_interp_segment_reduce_bwd.  row_ptr may
+ * point into the plan (a range of images).
+ * _fixup: the items of the dummy anchor (row_ptr[dummy] .. row_ptr[dummy + 1] of the whole plan), tap by tap in plan order
+ * into grad_rows fp32 [R][C] after dva_anchor_combine; one block, no atomics: deterministic. */
+int dva_interp_anchor_rows_sum(const void* grad_out, const void* arg, const int64_t* seg_ptr, const int32_t* perm,
+                               const int32_t* row_ptr, const float* tap_weights, const int32_t* seg_of_item, float* S,
+                               int64_t n_anchors, int64_t P, int32_t C, int32_t dtype, int32_t reduce, void* stream);
+int dva_interp_anchor_fixup(const void* grad_out, const void* arg, const int64_t* seg_ptr, const int32_t* perm,
+                            const int32_t* row_ptr, const int32_t* tap_rows, const float* tap_weights,
+                            const int32_t* seg_of_item, float* grad_rows, int64_t dummy, int64_t P, int32_t C,
+                            int32_t dtype, int32_t reduce, void* stream);
 
 /* Bilinear gather with the reference's border-replicate semantics (image.py:105-170):
  * q = coord * (H, W) + 0.5 in the 1-padded map; 4 taps floor(q), floor(q+1); weights |prod(q - opposite)|.

@@ -176,8 +176,6 @@ SIGNATURES = {
     "dva_chain_attn_fwd_dt": (ctypes.c_int, [_vp] * 18 + [_i64, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _vp]),
     "dva_chain_attn_bwd_dt": (ctypes.c_int, [_vp] * 14 + [_i64, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _vp]),
     "dva_chain_attn_bwd_f32": (ctypes.c_int, [_vp] * 14 + [_i64, _i64, _i64, _i32, _i32, _i32, _f32, _vp]),
-    "dva_gather_segment_max_fwd": (ctypes.c_int, [_vp] * 5 + [_i64, _i64, _i64, _i32, _i32, _vp]),
-    "dva_gather_segment_max_bwd": (ctypes.c_int, [_vp] * 8 + [_i64, _i64, _i64, _i32, _i32, _vp]),
     "dva_gather_segment_reduce_fwd": (ctypes.c_int, [_vp] * 5 + [_i64, _i64, _i64, _i32, _i32, _i32, _vp]),
     "dva_gather_segment_reduce_bwd": (ctypes.c_int, [_vp] * 7 + [_i64, _i64, _i64, _i32, _i32, _i32, _vp]),
     "dva_interp_segment_reduce_fwd": (ctypes.c_int, [_vp] * 6 + [_i64, _i64, _i64, _i32, _i32, _i32, _vp]),

@@ -1073,7 +1073,7 @@ __global__ __launch_bounds__(256) void rows_grad_team_kernel(
   }
 }
 
-// Sparse row plans (at most ~2 views per row: the identity gather of a view-level tensor, ops.gather_segment_max): one
+// Sparse row plans (at most ~2 views per row: the identity gather of a view-level tensor, an atomic ops.gather_segment_reduce): one
 // lane team per ROW instead of one wavefront per row -- 64 / lpr rows per wavefront, no cross-slot reduction.
 template <typename T, typename TO = float>
 __global__ __launch_bounds__(256) void rows_grad_short_rec16_kernel(const T* __restrict__ gout,

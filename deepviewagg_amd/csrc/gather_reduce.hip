@@ -1,20 +1,20 @@
-// Lazy nearest gather fused with the mean / sum / min pool behind it, for gfx950 (reference: x_mod = features[idx],
+// Lazy nearest gather fused with the max / mean / sum / min pool behind it, for gfx950 (reference: x_mod = features[idx],
 // core/multimodal/image.py:1262-1287, followed by BimodalCSRPool(mode) = torch_scatter.segment_csr over the items of each
-// segment, modules/multimodal/pooling.py:14-71; the max pool is csrc/gather.hip's dva_gather_segment_max_*).
+// segment, modules/multimodal/pooling.py:14-71).
 //
 // forward   out[s][c] = reduce over the items a in [seg_ptr[s], seg_ptr[s + 1]) of rows[row_idx[a]][c]
 // backward  grad_rows[r][c] = sum over the items a with row_idx[a] == r of g(a, c)
 //
 // No [P, C] tensor in either direction.  The forward is dva_segment_csr_fwd's arithmetic on the rows it would have been
-// handed (fp32 accumulation from 0 in item order, one division for the mean, one rounding; min: first item on ties, a NaN
-// wins only as the first item), so it equals the materialised composition bit for bit.  The backward is a segmented
+// handed (fp32 accumulation from 0 in item order, one division for the mean, one rounding; max / min: first item on ties,
+// a NaN wins only as the first item), so it equals the materialised composition bit for bit.  The backward is a segmented
 // reduction over the row plan of the items (perm = items sorted by map row, row_ptr): one wavefront per map row, fp32
 // accumulators, every element of grad_rows written once in the rows' storage type -- no float atomics, so two runs agree
 // bit for bit, and one rounding per map row where the materialised route rounds per item and again per row.
 //
-// Bytes: forward P (4 + C s) [map rows, out of the cache hierarchy] + S (8 + C s) (+ 2 S C: min's arg offsets);
-//        backward P (8 + C s) [gradient rows of the segments, cached] (+ 8 P: mean / min read seg_ptr, + 2 P C: min's
-//        arg rows) + R (4 + C s).
+// Bytes: forward P (4 + C s) [map rows, out of the cache hierarchy] + S (8 + C s) (+ 2 S C: the arg offsets of max / min);
+//        backward P (8 + C s) [gradient rows of the segments, cached] (+ 8 P: mean / max / min read seg_ptr, + 2 P C: the
+//        arg rows of max / min) + R (4 + C s).
 #include "dva_common.h"
 #include "row_chunk.h"
 
@@ -45,31 +45,21 @@ __global__ __launch_bounds__(256) void gather_segment_reduce_fwd_kernel(const T*
       float f[VEC];
       RowChunk<T, VEC>::ld(rows + (int64_t)row_idx[a] * C + c0, f);
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) {
-        if (REDUCE == DVA_MIN) {
-          if (a == beg || f[k] < acc[k]) {
-            acc[k] = f[k];
-            best[k] = (uint32_t)(a - beg);
-          }
-        } else {
-          acc[k] += f[k];
-        }
-      }
+      for (int k = 0; k < VEC; ++k) pool_step<REDUCE>(acc[k], best[k], f[k], a == beg, (uint32_t)(a - beg));
     }
     if (REDUCE == DVA_MEAN && end > beg) {
 #pragma unroll
       for (int k = 0; k < VEC; ++k) acc[k] /= (float)(end - beg);
     }
     RowChunk<T, VEC>::st(out + s * C + c0, acc);
-    if (REDUCE == DVA_MIN) RowChunk<T, VEC>::st_arg(arg + s * C + c0, best);
+    if (keeps_arg(REDUCE)) RowChunk<T, VEC>::st_arg(arg + s * C + c0, best);
   }
 }
 
 // One wavefront per map row r: its items perm[row_ptr[r] .. row_ptr[r + 1]) are spread over 64 / lpr slots, lpr lanes (a
 // power of two) own the VEC-channel chunks of a row; rows wider than lpr chunks are walked in column passes of lpr chunks.
-// Item a of segment s = seg_of_item[a] contributes grad_out[s][c] (sum), grad_out[s][c] / count_s (mean, fp32 true
-// division as segment_csr_bwd_kernel) or grad_out[s][c] where arg[s][c] == a - seg_ptr[s] (min).  The slots are summed
-// with wave64 xor shuffles in a fixed order.
+// Item a of segment s = seg_of_item[a] contributes pool_term of grad_out[s][c].  The slots are summed with wave64 xor
+// shuffles in a fixed order.
 template <typename T, int VEC, int REDUCE>
 __global__ __launch_bounds__(256) void gather_segment_reduce_bwd_kernel(
     const T* __restrict__ gout, const uint16_t* __restrict__ arg, const int64_t* __restrict__ seg_ptr,
@@ -92,7 +82,7 @@ __global__ __launch_bounds__(256) void gather_segment_reduce_bwd_kernel(
       for (int i0 = beg; i0 < end; i0 += slots * U) {
         int64_t s[U];
         uint32_t koff[U];
-        float scale[U];
+        float count[U];                                        // items of the segment; 0: no item in this slot
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const int i = i0 + u * slots + slot;
@@ -100,30 +90,26 @@ __global__ __launch_bounds__(256) void gather_segment_reduce_bwd_kernel(
           const int a = perm[i < end ? i : beg];
           s[u] = seg_of_item[a];
           koff[u] = 0xfffeu;                                   // 0xfffe never is a stored offset
-          scale[u] = ok ? 1.f : 0.f;
+          count[u] = ok ? 1.f : 0.f;
           if (REDUCE != DVA_SUM) {
             const int64_t sb = seg_ptr[s[u]];
-            if (REDUCE == DVA_MEAN) scale[u] = ok ? (float)(seg_ptr[s[u] + 1] - sb) : 0.f;
-            if (REDUCE == DVA_MIN && ok) koff[u] = (uint32_t)((int64_t)a - sb);
+            if (REDUCE == DVA_MEAN) count[u] = ok ? (float)(seg_ptr[s[u] + 1] - sb) : 0.f;
+            if (keeps_arg(REDUCE) && ok) koff[u] = (uint32_t)((int64_t)a - sb);
           }
         }
         float g[U][VEC];
-        uint32_t ak[U][VEC];
+        uint32_t ak[U][VEC] = {};
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           RowChunk<T, VEC>::ld(gout + s[u] * C + col, g[u]);
-          if (REDUCE == DVA_MIN) RowChunk<T, VEC>::ld_arg(arg + s[u] * C + col, ak[u]);
+          if (keeps_arg(REDUCE)) RowChunk<T, VEC>::ld_arg(arg + s[u] * C + col, ak[u]);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
 #pragma unroll
           for (int k = 0; k < VEC; ++k) {
-            if (REDUCE == DVA_SUM)
-              acc[k] += scale[u] != 0.f ? g[u][k] : 0.f;
-            else if (REDUCE == DVA_MEAN)
-              acc[k] += scale[u] != 0.f ? g[u][k] / scale[u] : 0.f;
-            else
-              acc[k] += ak[u][k] == koff[u] ? g[u][k] : 0.f;
+            const float term = pool_term<REDUCE>(g[u][k], 1.f, count[u], ak[u][k], koff[u]);
+            acc[k] += count[u] != 0.f ? term : 0.f;
           }
         }
       }
@@ -134,46 +120,6 @@ __global__ __launch_bounds__(256) void gather_segment_reduce_bwd_kernel(
       if (slot == 0 && live) RowChunk<T, VEC>::st(grows + r * C + col, acc);
     }
   }
-}
-
-constexpr int64_t GSR_GRID_CAP = 256 * 32;      // 256 CUs x 32 blocks, grid-stride beyond
-constexpr int64_t GSR_SIZE_MAX = 0x7fffffffLL;  // int32 row plan, int32 segment of item
-
-template <typename T, int VEC>
-static void launch_fwd(const void* rows, const int32_t* row_idx, const int64_t* seg_ptr, void* out, void* arg, int64_t S,
-                       int C, int reduce, hipStream_t s) {
-  const dim3 grid(capped_grid(S * (int64_t)(C / VEC), 256, GSR_GRID_CAP));
-#define DVA_L(R)                                                                                                   \
-  hipLaunchKernelGGL((gather_segment_reduce_fwd_kernel<T, VEC, R>), grid, dim3(256), 0, s, (const T*)rows, row_idx, \
-                     seg_ptr, (T*)out, (uint16_t*)arg, S, C)
-  if (reduce == DVA_SUM) DVA_L(DVA_SUM);
-  else if (reduce == DVA_MEAN) DVA_L(DVA_MEAN);
-  else DVA_L(DVA_MIN);
-#undef DVA_L
-}
-
-template <typename T, int VEC>
-static void launch_bwd(const void* gout, const void* arg, const int64_t* seg_ptr, const int32_t* perm,
-                       const int32_t* row_ptr, const int32_t* seg_of_item, void* grows, int64_t R, int C, int reduce,
-                       hipStream_t s) {
-  const int chunks = C / VEC;
-  int lpr = 1;
-  while (lpr < chunks && lpr < 64) lpr <<= 1;
-  const dim3 grid(capped_grid(R, 4, GSR_GRID_CAP));      // four wavefronts, four map rows per block
-#define DVA_L(RD)                                                                                                  \
-  hipLaunchKernelGGL((gather_segment_reduce_bwd_kernel<T, VEC, RD>), grid, dim3(256), 0, s, (const T*)gout,         \
-                     (const uint16_t*)arg, seg_ptr, perm, row_ptr, seg_of_item, (T*)grows, R, C, lpr)
-  if (reduce == DVA_SUM) DVA_L(DVA_SUM);
-  else if (reduce == DVA_MEAN) DVA_L(DVA_MEAN);
-  else DVA_L(DVA_MIN);
-#undef DVA_L
-}
-
-static int check_sizes(int64_t S, int64_t P, int64_t R, int C, int dtype, int reduce) {
-  if (S < 0 || P < 0 || R < 0 || C < 0) return DVA_ERR_INVALID;
-  if (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16) return DVA_ERR_INVALID;
-  if (reduce < DVA_SUM || reduce > DVA_MIN) return DVA_ERR_INVALID;
-  return DVA_OK;
 }
 
 }  // namespace dva
@@ -187,24 +133,21 @@ int dva_gather_segment_reduce_fwd(const void* rows, const int32_t* row_idx, cons
                                   void* stream) {
   int rc = check_sizes(S, P, R, C, dtype, reduce);
   if (rc) return rc;
-  if (S > 0 && C > 0 && (!seg_ptr || !out || (reduce == DVA_MIN && !arg) || (P > 0 && (!rows || !row_idx))))
+  if (S > 0 && C > 0 && (!seg_ptr || !out || (keeps_arg(reduce) && !arg) || (P > 0 && (!rows || !row_idx))))
     return DVA_ERR_INVALID;
-  if (reduce == DVA_MAX) return DVA_ERR_UNSUPPORTED;      // dva_gather_segment_max_fwd
-  if (S > GSR_SIZE_MAX || P > GSR_SIZE_MAX || R > GSR_SIZE_MAX) return DVA_ERR_UNSUPPORTED;
+  if (S > POOL_SIZE_MAX || P > POOL_SIZE_MAX || R > POOL_SIZE_MAX) return DVA_ERR_UNSUPPORTED;
   if (S == 0 || C == 0) return DVA_OK;
   hipStream_t s = (hipStream_t)stream;
-  const int vec = dtype == DVA_F32 ? 4 : 8;
-  const bool wide = C % vec == 0 && aligned16(rows) && aligned16(out) && aligned16(arg);
-  if (dtype == DVA_F32) {
-    if (wide) launch_fwd<float, 4>(rows, row_idx, seg_ptr, out, arg, S, C, reduce, s);
-    else launch_fwd<float, 1>(rows, row_idx, seg_ptr, out, arg, S, C, reduce, s);
-  } else if (dtype == DVA_F16) {
-    if (wide) launch_fwd<f16_t, 8>(rows, row_idx, seg_ptr, out, arg, S, C, reduce, s);
-    else launch_fwd<f16_t, 1>(rows, row_idx, seg_ptr, out, arg, S, C, reduce, s);
-  } else {
-    if (wide) launch_fwd<bf16_t, 8>(rows, row_idx, seg_ptr, out, arg, S, C, reduce, s);
-    else launch_fwd<bf16_t, 1>(rows, row_idx, seg_ptr, out, arg, S, C, reduce, s);
-  }
+  const bool wide = C % row_vec(dtype) == 0 && aligned16(rows) && aligned16(out) && aligned16(arg);
+  with_row_type(dtype, wide, [&](auto row) {
+    using T = typename decltype(row)::T;
+    constexpr int VEC = decltype(row)::VEC;
+    const dim3 grid(capped_grid(S * (int64_t)(C / VEC), 256, POOL_GRID_CAP));
+    with_reduce(reduce, [&](auto rd) {
+      hipLaunchKernelGGL((gather_segment_reduce_fwd_kernel<T, VEC, decltype(rd)::value>), grid, dim3(256), 0, s,
+                         (const T*)rows, row_idx, seg_ptr, (T*)out, (uint16_t*)arg, S, (int)C);
+    });
+  });
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -216,25 +159,23 @@ int dva_gather_segment_reduce_bwd(const void* grad_out, const void* arg, const i
   if (rc) return rc;
   if (S > 0 && C > 0 && R > 0 &&
       (!grad_rows || !row_ptr ||
-       (P > 0 && (!grad_out || !seg_ptr || !perm || !seg_of_item || (reduce == DVA_MIN && !arg)))))
+       (P > 0 && (!grad_out || !seg_ptr || !perm || !seg_of_item || (keeps_arg(reduce) && !arg)))))
     return DVA_ERR_INVALID;
-  if (reduce == DVA_MAX) return DVA_ERR_UNSUPPORTED;      // dva_gather_segment_max_bwd
-  if (S > GSR_SIZE_MAX || P > GSR_SIZE_MAX || R > GSR_SIZE_MAX) return DVA_ERR_UNSUPPORTED;
+  if (S > POOL_SIZE_MAX || P > POOL_SIZE_MAX || R > POOL_SIZE_MAX) return DVA_ERR_UNSUPPORTED;
   if (R == 0 || C == 0) return DVA_OK;
   if (!grad_rows || !row_ptr) return DVA_ERR_INVALID;     // S == 0: every row still gets its zeros
   hipStream_t s = (hipStream_t)stream;
-  const int vec = dtype == DVA_F32 ? 4 : 8;
-  const bool wide = C % vec == 0 && aligned16(grad_out) && aligned16(grad_rows) && aligned16(arg);
-  if (dtype == DVA_F32) {
-    if (wide) launch_bwd<float, 4>(grad_out, arg, seg_ptr, perm, row_ptr, seg_of_item, grad_rows, R, C, reduce, s);
-    else launch_bwd<float, 1>(grad_out, arg, seg_ptr, perm, row_ptr, seg_of_item, grad_rows, R, C, reduce, s);
-  } else if (dtype == DVA_F16) {
-    if (wide) launch_bwd<f16_t, 8>(grad_out, arg, seg_ptr, perm, row_ptr, seg_of_item, grad_rows, R, C, reduce, s);
-    else launch_bwd<f16_t, 1>(grad_out, arg, seg_ptr, perm, row_ptr, seg_of_item, grad_rows, R, C, reduce, s);
-  } else {
-    if (wide) launch_bwd<bf16_t, 8>(grad_out, arg, seg_ptr, perm, row_ptr, seg_of_item, grad_rows, R, C, reduce, s);
-    else launch_bwd<bf16_t, 1>(grad_out, arg, seg_ptr, perm, row_ptr, seg_of_item, grad_rows, R, C, reduce, s);
-  }
+  const bool wide = C % row_vec(dtype) == 0 && aligned16(grad_out) && aligned16(grad_rows) && aligned16(arg);
+  const dim3 grid(capped_grid(R, 4, POOL_GRID_CAP));      // four wavefronts, four map rows per block
+  with_row_type(dtype, wide, [&](auto row) {
+    using T = typename decltype(row)::T;
+    constexpr int VEC = decltype(row)::VEC;
+    with_reduce(reduce, [&](auto rd) {
+      hipLaunchKernelGGL((gather_segment_reduce_bwd_kernel<T, VEC, decltype(rd)::value>), grid, dim3(256), 0, s,
+                         (const T*)grad_out, (const uint16_t*)arg, seg_ptr, perm, row_ptr, seg_of_item, (T*)grad_rows, R,
+                         (int)C, lanes_per_row(C / VEC));
+    });
+  });
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }

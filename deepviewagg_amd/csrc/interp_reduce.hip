@@ -45,7 +45,6 @@ template <typename T, int VEC, int REDUCE>
 __global__ __launch_bounds__(256) void interp_segment_reduce_fwd_kernel(
     const T* __restrict__ rows, const int4* __restrict__ tap_rows, const float4* __restrict__ tap_weights,
     const int64_t* __restrict__ seg_ptr, T* __restrict__ out, uint16_t* __restrict__ arg, int64_t S, int C, int lpr) {
-  constexpr bool EXTREMUM = REDUCE == DVA_MAX || REDUCE == DVA_MIN;
   const int chunks = C / VEC;
   const int lane = threadIdx.x & 63;
   const int lane_r = lane & (lpr - 1), slot = lane / lpr, slots = 64 / lpr;
@@ -83,17 +82,8 @@ __global__ __launch_bounds__(256) void interp_segment_reduce_fwd_kernel(
         for (int j = 0; j < n; ++j) {
           const int src = j * lpr + lane_r;
 #pragma unroll
-          for (int k = 0; k < VEC; ++k) {
-            const float f = __shfl(v[k], src);
-            if (EXTREMUM) {
-              if ((i0 + j == beg) || (REDUCE == DVA_MAX ? f > acc[k] : f < acc[k])) {
-                acc[k] = f;
-                best[k] = (uint32_t)(i0 + j - beg);
-              }
-            } else {
-              acc[k] = __fadd_rn(acc[k], f);
-            }
-          }
+          for (int k = 0; k < VEC; ++k)
+            pool_step<REDUCE>(acc[k], best[k], __shfl(v[k], src), i0 + j == beg, (uint32_t)(i0 + j - beg));
         }
       }
       if (REDUCE == DVA_MEAN && end > beg) {
@@ -102,7 +92,7 @@ __global__ __launch_bounds__(256) void interp_segment_reduce_fwd_kernel(
       }
       if (slot == 0 && live) {
         RowChunk<T, VEC>::st(out + s * C + col, acc);
-        if (EXTREMUM) RowChunk<T, VEC>::st_arg(arg + s * C + col, best);
+        if (keeps_arg(REDUCE)) RowChunk<T, VEC>::st_arg(arg + s * C + col, best);
       }
     }
   }
@@ -118,7 +108,6 @@ __global__ __launch_bounds__(256) void interp_segment_reduce_bwd_kernel(
     const T* __restrict__ gout, const uint16_t* __restrict__ arg, const int64_t* __restrict__ seg_ptr,
     const int32_t* __restrict__ perm, const int32_t* __restrict__ row_ptr, const float* __restrict__ tap_weights,
     const int32_t* __restrict__ seg_of_item, T* __restrict__ grows, int64_t R, int C, int lpr) {
-  constexpr bool EXTREMUM = REDUCE == DVA_MAX || REDUCE == DVA_MIN;
   constexpr int U = 2;
   const int chunks = C / VEC;
   const int lane = threadIdx.x & 63;
@@ -151,24 +140,21 @@ __global__ __launch_bounds__(256) void interp_segment_reduce_bwd_kernel(
           if (REDUCE != DVA_SUM) {
             const int64_t sb = seg_ptr[s[u]];
             if (REDUCE == DVA_MEAN) count[u] = (float)(seg_ptr[s[u] + 1] - sb);
-            if (EXTREMUM) koff[u] = (uint32_t)((int64_t)p - sb);
+            if (keeps_arg(REDUCE)) koff[u] = (uint32_t)((int64_t)p - sb);
           }
         }
         float g[U][VEC];
-        uint32_t ak[U][VEC];
+        uint32_t ak[U][VEC] = {};
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           RowChunk<T, VEC>::ld(gout + s[u] * C + col, g[u]);
-          if (EXTREMUM) RowChunk<T, VEC>::ld_arg(arg + s[u] * C + col, ak[u]);
+          if (keeps_arg(REDUCE)) RowChunk<T, VEC>::ld_arg(arg + s[u] * C + col, ak[u]);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
 #pragma unroll
           for (int k = 0; k < VEC; ++k) {
-            float term;
-            if (REDUCE == DVA_SUM) term = w[u] * g[u][k];
-            else if (REDUCE == DVA_MEAN) term = w[u] * (g[u][k] / count[u]);
-            else term = ak[u][k] == koff[u] ? w[u] * g[u][k] : 0.f;
+            const float term = pool_term<REDUCE>(g[u][k], w[u], count[u], ak[u][k], koff[u]);
             acc[k] += ok[u] ? term : 0.f;
           }
         }
@@ -192,7 +178,6 @@ __global__ __launch_bounds__(256) void interp_anchor_sum_kernel(
     const T* __restrict__ gout, const uint16_t* __restrict__ arg, const int64_t* __restrict__ seg_ptr,
     const int32_t* __restrict__ perm, const int32_t* __restrict__ row_ptr, const float4* __restrict__ tap_weights,
     const int32_t* __restrict__ seg_of_item, float* __restrict__ S, int64_t A, int C, int lpr) {
-  constexpr bool EXTREMUM = REDUCE == DVA_MAX || REDUCE == DVA_MIN;
   constexpr int U = 2;
   const int lane = threadIdx.x & 63;
   const int lane_r = lane & (lpr - 1), slot = lane / lpr, slots = 64 / lpr;
@@ -225,25 +210,22 @@ __global__ __launch_bounds__(256) void interp_anchor_sum_kernel(
         if (REDUCE != DVA_SUM) {
           const int64_t sb = seg_ptr[s[u]];
           if (REDUCE == DVA_MEAN) count[u] = (float)(seg_ptr[s[u] + 1] - sb);
-          if (EXTREMUM) koff[u] = (uint32_t)((int64_t)p - sb);
+          if (keeps_arg(REDUCE)) koff[u] = (uint32_t)((int64_t)p - sb);
         }
       }
       float g[U][VEC];
-      uint32_t ak[U][VEC];
+      uint32_t ak[U][VEC] = {};
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         RowChunk<T, VEC>::ld(gout + s[u] * C + col, g[u]);
-        if (EXTREMUM) RowChunk<T, VEC>::ld_arg(arg + s[u] * C + col, ak[u]);
+        if (keeps_arg(REDUCE)) RowChunk<T, VEC>::ld_arg(arg + s[u] * C + col, ak[u]);
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const float ww[4] = {w[u].x, w[u].y, w[u].z, w[u].w};
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
-          float term;
-          if (REDUCE == DVA_SUM) term = g[u][e];
-          else if (REDUCE == DVA_MEAN) term = g[u][e] / count[u];
-          else term = ak[u][e] == koff[u] ? g[u][e] : 0.f;
+          const float term = pool_term<REDUCE>(g[u][e], 1.f, count[u], ak[u][e], koff[u]);
 #pragma unroll
           for (int k = 0; k < 4; ++k) acc[k][e] += ok[u] ? ww[k] * term : 0.f;
         }
@@ -282,92 +264,13 @@ __global__ __launch_bounds__(256) void interp_anchor_fixup_kernel(
     for (int i = beg; i < end; ++i) {
       const int64_t p = perm[i];
       const int64_t s = seg_of_item[p];
-      float g = Elt<T>::ld(gout, s * C + c);
-      if (REDUCE == DVA_MEAN) g /= (float)(seg_ptr[s + 1] - seg_ptr[s]);
-      if (REDUCE == DVA_MAX || REDUCE == DVA_MIN) g = arg[s * C + c] == (uint16_t)(p - seg_ptr[s]) ? g : 0.f;
+      const float count = REDUCE == DVA_MEAN ? (float)(seg_ptr[s + 1] - seg_ptr[s]) : 1.f;
+      const uint32_t ak = keeps_arg(REDUCE) ? arg[s * C + c] : 0u, koff = (uint16_t)(p - seg_ptr[s]);
+      const float g = pool_term<REDUCE>(Elt<T>::ld(gout, s * C + c), 1.f, count, ak, koff);
       for (int k = 0; k < 4; ++k) dY[(int64_t)tap_rows[4 * p + k] * C + c] += tap_weights[4 * p + k] * g;
     }
   }
 }
-
-constexpr int64_t ISR_GRID_CAP = 256 * 32;      // 256 CUs x 32 blocks, grid-stride beyond
-constexpr int64_t ISR_SIZE_MAX = 0x7fffffffLL;  // int32 tap plan over 4 P taps, int32 segment of item
-
-static inline int lanes_per_row(int chunks) {
-  int lpr = 1;
-  while (lpr < chunks && lpr < 64) lpr <<= 1;
-  return lpr;
-}
-
-template <typename T, int VEC>
-static void launch_fwd(const void* rows, const int32_t* tap_rows, const float* tap_weights, const int64_t* seg_ptr,
-                       void* out, void* arg, int64_t S, int C, int reduce, hipStream_t s) {
-  const int lpr = lanes_per_row(C / VEC);
-  const dim3 grid(capped_grid(S, 4, ISR_GRID_CAP));      // four wavefronts, four segments per block
-#define DVA_L(RD)                                                                                                    \
-  hipLaunchKernelGGL((interp_segment_reduce_fwd_kernel<T, VEC, RD>), grid, dim3(256), 0, s, (const T*)rows,           \
-                     (const int4*)tap_rows, (const float4*)tap_weights, seg_ptr, (T*)out, (uint16_t*)arg, S, C, lpr)
-  if (reduce == DVA_SUM) DVA_L(DVA_SUM);
-  else if (reduce == DVA_MEAN) DVA_L(DVA_MEAN);
-  else if (reduce == DVA_MAX) DVA_L(DVA_MAX);
-  else DVA_L(DVA_MIN);
-#undef DVA_L
-}
-
-template <typename T, int VEC>
-static void launch_bwd(const void* gout, const void* arg, const int64_t* seg_ptr, const int32_t* perm,
-                       const int32_t* row_ptr, const float* tap_weights, const int32_t* seg_of_item, void* grows,
-                       int64_t R, int C, int reduce, hipStream_t s) {
-  const int lpr = lanes_per_row(C / VEC);
-  const dim3 grid(capped_grid(R, 4, ISR_GRID_CAP));      // four wavefronts, four map rows per block
-#define DVA_L(RD)                                                                                                    \
-  hipLaunchKernelGGL((interp_segment_reduce_bwd_kernel<T, VEC, RD>), grid, dim3(256), 0, s, (const T*)gout,           \
-                     (const uint16_t*)arg, seg_ptr, perm, row_ptr, tap_weights, seg_of_item, (T*)grows, R, C, lpr)
-  if (reduce == DVA_SUM) DVA_L(DVA_SUM);
-  else if (reduce == DVA_MEAN) DVA_L(DVA_MEAN);
-  else if (reduce == DVA_MAX) DVA_L(DVA_MAX);
-  else DVA_L(DVA_MIN);
-#undef DVA_L
-}
-
-template <typename T, int VEC>
-static void launch_anchor(const void* gout, const void* arg, const int64_t* seg_ptr, const int32_t* perm,
-                          const int32_t* row_ptr, const float* tap_weights, const int32_t* seg_of_item, float* S, int64_t A,
-                          int C, int reduce, hipStream_t s) {
-  const int lpr = C / VEC;
-  const dim3 grid(capped_grid(A, 4, ISR_GRID_CAP));
-#define DVA_L(RD)                                                                                                    \
-  hipLaunchKernelGGL((interp_anchor_sum_kernel<T, VEC, RD>), grid, dim3(256), 0, s, (const T*)gout,                   \
-                     (const uint16_t*)arg, seg_ptr, perm, row_ptr, (const float4*)tap_weights, seg_of_item, S, A, C, lpr)
-  if (reduce == DVA_SUM) DVA_L(DVA_SUM);
-  else if (reduce == DVA_MEAN) DVA_L(DVA_MEAN);
-  else if (reduce == DVA_MAX) DVA_L(DVA_MAX);
-  else DVA_L(DVA_MIN);
-#undef DVA_L
-}
-
-template <typename T>
-static void launch_fixup(const void* gout, const void* arg, const int64_t* seg_ptr, const int32_t* perm,
-                         const int32_t* row_ptr, const int32_t* tap_rows, const float* tap_weights,
-                         const int32_t* seg_of_item, float* dY, int64_t dummy, int C, int reduce, hipStream_t s) {
-#define DVA_L(RD)                                                                                                    \
-  hipLaunchKernelGGL((interp_anchor_fixup_kernel<T, RD>), dim3(1), dim3(256), 0, s, (const T*)gout,                   \
-                     (const uint16_t*)arg, seg_ptr, perm, row_ptr, tap_rows, tap_weights, seg_of_item, dY, dummy, C)
-  if (reduce == DVA_SUM) DVA_L(DVA_SUM);
-  else if (reduce == DVA_MEAN) DVA_L(DVA_MEAN);
-  else if (reduce == DVA_MAX) DVA_L(DVA_MAX);
-  else DVA_L(DVA_MIN);
-#undef DVA_L
-}
-
-static int check_sizes(int64_t S, int64_t P, int64_t R, int C, int dtype, int reduce) {
-  if (S < 0 || P < 0 || R < 0 || C < 0) return DVA_ERR_INVALID;
-  if (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16) return DVA_ERR_INVALID;
-  if (reduce < DVA_SUM || reduce > DVA_MIN) return DVA_ERR_INVALID;
-  return DVA_OK;
-}
-
-static inline bool keeps_arg(int reduce) { return reduce == DVA_MAX || reduce == DVA_MIN; }
 
 }  // namespace dva
 
@@ -383,23 +286,22 @@ int dva_interp_segment_reduce_fwd(const void* rows, const int32_t* tap_rows, con
   if (S > 0 && C > 0 &&
       (!seg_ptr || !out || (keeps_arg(reduce) && !arg) || (P > 0 && (!rows || !tap_rows || !tap_weights))))
     return DVA_ERR_INVALID;
-  if (S > ISR_SIZE_MAX || P > ISR_SIZE_MAX / 4 || R > ISR_SIZE_MAX) return DVA_ERR_UNSUPPORTED;
+  if (S > POOL_SIZE_MAX || P > POOL_SIZE_MAX / 4 || R > POOL_SIZE_MAX) return DVA_ERR_UNSUPPORTED;
   if (S == 0 || C == 0) return DVA_OK;
   hipStream_t s = (hipStream_t)stream;
-  const int vec = dtype == DVA_F32 ? 4 : 8;
   // the taps are read as 16-byte records on both paths: [P, 4] tensors of 4-byte elements
   if (P > 0 && (!aligned16(tap_rows) || !aligned16(tap_weights))) return DVA_ERR_UNSUPPORTED;
-  const bool wide = C % vec == 0 && aligned16(rows) && aligned16(out) && aligned16(arg);
-  if (dtype == DVA_F32) {
-    if (wide) launch_fwd<float, 4>(rows, tap_rows, tap_weights, seg_ptr, out, arg, S, C, reduce, s);
-    else launch_fwd<float, 1>(rows, tap_rows, tap_weights, seg_ptr, out, arg, S, C, reduce, s);
-  } else if (dtype == DVA_F16) {
-    if (wide) launch_fwd<f16_t, 8>(rows, tap_rows, tap_weights, seg_ptr, out, arg, S, C, reduce, s);
-    else launch_fwd<f16_t, 1>(rows, tap_rows, tap_weights, seg_ptr, out, arg, S, C, reduce, s);
-  } else {
-    if (wide) launch_fwd<bf16_t, 8>(rows, tap_rows, tap_weights, seg_ptr, out, arg, S, C, reduce, s);
-    else launch_fwd<bf16_t, 1>(rows, tap_rows, tap_weights, seg_ptr, out, arg, S, C, reduce, s);
-  }
+  const bool wide = C % row_vec(dtype) == 0 && aligned16(rows) && aligned16(out) && aligned16(arg);
+  const dim3 grid(capped_grid(S, 4, POOL_GRID_CAP));      // four wavefronts, four segments per block
+  with_row_type(dtype, wide, [&](auto row) {
+    using T = typename decltype(row)::T;
+    constexpr int VEC = decltype(row)::VEC;
+    with_reduce(reduce, [&](auto rd) {
+      hipLaunchKernelGGL((interp_segment_reduce_fwd_kernel<T, VEC, decltype(rd)::value>), grid, dim3(256), 0, s,
+                         (const T*)rows, (const int4*)tap_rows, (const float4*)tap_weights, seg_ptr, (T*)out,
+                         (uint16_t*)arg, S, (int)C, lanes_per_row(C / VEC));
+    });
+  });
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -414,22 +316,21 @@ int dva_interp_segment_reduce_bwd(const void* grad_out, const void* arg, const i
       (!grad_rows || !row_ptr ||
        (P > 0 && (!grad_out || !seg_ptr || !perm || !tap_weights || !seg_of_item || (keeps_arg(reduce) && !arg)))))
     return DVA_ERR_INVALID;
-  if (S > ISR_SIZE_MAX || P > ISR_SIZE_MAX / 4 || R > ISR_SIZE_MAX) return DVA_ERR_UNSUPPORTED;
+  if (S > POOL_SIZE_MAX || P > POOL_SIZE_MAX / 4 || R > POOL_SIZE_MAX) return DVA_ERR_UNSUPPORTED;
   if (R == 0 || C == 0) return DVA_OK;
   if (!grad_rows || !row_ptr) return DVA_ERR_INVALID;     // S == 0: every row still gets its zeros
   hipStream_t s = (hipStream_t)stream;
-  const int vec = dtype == DVA_F32 ? 4 : 8;
-  const bool wide = C % vec == 0 && aligned16(grad_out) && aligned16(grad_rows) && aligned16(arg);
-  if (dtype == DVA_F32) {
-    if (wide) launch_bwd<float, 4>(grad_out, arg, seg_ptr, perm, row_ptr, tap_weights, seg_of_item, grad_rows, R, C, reduce, s);
-    else launch_bwd<float, 1>(grad_out, arg, seg_ptr, perm, row_ptr, tap_weights, seg_of_item, grad_rows, R, C, reduce, s);
-  } else if (dtype == DVA_F16) {
-    if (wide) launch_bwd<f16_t, 8>(grad_out, arg, seg_ptr, perm, row_ptr, tap_weights, seg_of_item, grad_rows, R, C, reduce, s);
-    else launch_bwd<f16_t, 1>(grad_out, arg, seg_ptr, perm, row_ptr, tap_weights, seg_of_item, grad_rows, R, C, reduce, s);
-  } else {
-    if (wide) launch_bwd<bf16_t, 8>(grad_out, arg, seg_ptr, perm, row_ptr, tap_weights, seg_of_item, grad_rows, R, C, reduce, s);
-    else launch_bwd<bf16_t, 1>(grad_out, arg, seg_ptr, perm, row_ptr, tap_weights, seg_of_item, grad_rows, R, C, reduce, s);
-  }
+  const bool wide = C % row_vec(dtype) == 0 && aligned16(grad_out) && aligned16(grad_rows) && aligned16(arg);
+  const dim3 grid(capped_grid(R, 4, POOL_GRID_CAP));      // four wavefronts, four map rows per block
+  with_row_type(dtype, wide, [&](auto row) {
+    using T = typename decltype(row)::T;
+    constexpr int VEC = decltype(row)::VEC;
+    with_reduce(reduce, [&](auto rd) {
+      hipLaunchKernelGGL((interp_segment_reduce_bwd_kernel<T, VEC, decltype(rd)::value>), grid, dim3(256), 0, s,
+                         (const T*)grad_out, (const uint16_t*)arg, seg_ptr, perm, row_ptr, tap_weights, seg_of_item,
+                         (T*)grad_rows, R, (int)C, lanes_per_row(C / VEC));
+    });
+  });
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -443,17 +344,25 @@ int dva_interp_anchor_rows_sum(const void* grad_out, const void* arg, const int6
       (!row_ptr || !S ||
        (P > 0 && (!grad_out || !seg_ptr || !perm || !tap_weights || !seg_of_item || (keeps_arg(reduce) && !arg)))))
     return DVA_ERR_INVALID;
-  if (dtype == DVA_F16 || n_anchors > ISR_SIZE_MAX || P > ISR_SIZE_MAX) return DVA_ERR_UNSUPPORTED;
+  if (dtype == DVA_F16 || n_anchors > POOL_SIZE_MAX || P > POOL_SIZE_MAX) return DVA_ERR_UNSUPPORTED;
   if (n_anchors == 0 || C == 0) return DVA_OK;
-  const int vec = dtype == DVA_F32 ? 4 : 8, lpr = C / vec;
+  const int vec = row_vec(dtype), lpr = C / vec;
   if (C % vec || (lpr & (lpr - 1)) || lpr > 64 || !aligned16(grad_out) || !aligned16(S) || !aligned16(arg) ||
       !aligned16(tap_weights))
     return DVA_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == DVA_F32)
-    launch_anchor<float, 4>(grad_out, arg, seg_ptr, perm, row_ptr, tap_weights, seg_of_item, S, n_anchors, C, reduce, s);
-  else
-    launch_anchor<bf16_t, 8>(grad_out, arg, seg_ptr, perm, row_ptr, tap_weights, seg_of_item, S, n_anchors, C, reduce, s);
+  const dim3 grid(capped_grid(n_anchors, 4, POOL_GRID_CAP));
+  auto launch = [&](auto row) {
+    using T = typename decltype(row)::T;
+    constexpr int VEC = decltype(row)::VEC;
+    with_reduce(reduce, [&](auto rd) {
+      hipLaunchKernelGGL((interp_anchor_sum_kernel<T, VEC, decltype(rd)::value>), grid, dim3(256), 0, s,
+                         (const T*)grad_out, (const uint16_t*)arg, seg_ptr, perm, row_ptr, (const float4*)tap_weights,
+                         seg_of_item, S, n_anchors, (int)C, lpr);
+    });
+  };
+  if (dtype == DVA_F32) launch(RowType<float, 4>{});
+  else launch(RowType<bf16_t, 8>{});
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -464,18 +373,22 @@ int dva_interp_anchor_fixup(const void* grad_out, const void* arg, const int64_t
                             int32_t dtype, int32_t reduce, void* stream) {
   int rc = check_sizes(dummy, P, 0, C, dtype, reduce);
   if (rc) return rc;
-  if (dtype == DVA_F16 || dummy >= ISR_SIZE_MAX || P > ISR_SIZE_MAX) return DVA_ERR_UNSUPPORTED;
+  if (dtype == DVA_F16 || dummy >= POOL_SIZE_MAX || P > POOL_SIZE_MAX) return DVA_ERR_UNSUPPORTED;
   if (P == 0 || C == 0) return DVA_OK;
   if (!grad_out || !seg_ptr || !perm || !row_ptr || !tap_rows || !tap_weights || !seg_of_item || !grad_rows ||
       (keeps_arg(reduce) && !arg))
     return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == DVA_F32)
-    launch_fixup<float>(grad_out, arg, seg_ptr, perm, row_ptr, tap_rows, tap_weights, seg_of_item, grad_rows, dummy, C,
-                        reduce, s);
-  else
-    launch_fixup<bf16_t>(grad_out, arg, seg_ptr, perm, row_ptr, tap_rows, tap_weights, seg_of_item, grad_rows, dummy, C,
-                         reduce, s);
+  auto launch = [&](auto row) {
+    using T = typename decltype(row)::T;
+    with_reduce(reduce, [&](auto rd) {
+      hipLaunchKernelGGL((interp_anchor_fixup_kernel<T, decltype(rd)::value>), dim3(1), dim3(256), 0, s,
+                         (const T*)grad_out, (const uint16_t*)arg, seg_ptr, perm, row_ptr, tap_rows, tap_weights,
+                         seg_of_item, grad_rows, dummy, (int)C);
+    });
+  };
+  if (dtype == DVA_F32) launch(RowType<float, 1>{});
+  else launch(RowType<bf16_t, 1>{});
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }

@@ -1,6 +1,9 @@
-// 16-byte and element accesses to VEC consecutive channels of one row, shared by the fused gather + pool kernels
-// (gather_reduce.hip, interp_reduce.hip).
+// What the fused gather + pool kernels (gather_reduce.hip: nearest gather, interp_reduce.hip: bilinear gather) share: 16-byte
+// and element accesses to VEC consecutive channels of one row, the pooling step and its gradient term, the argument checks
+// and the choice of a kernel instantiation from (dtype, wide) and reduce.  The two files differ where the gathers differ.
 #pragma once
+#include <type_traits>
+
 #include "dva_common.h"
 
 namespace dva {
@@ -56,5 +59,72 @@ struct RowChunk<T, 1> {
 };
 
 static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+constexpr int64_t POOL_GRID_CAP = 256 * 32;      // 256 CUs x 32 blocks, grid-stride beyond
+constexpr int64_t POOL_SIZE_MAX = 0x7fffffffLL;  // int32 row / tap plan, int32 segment of item
+
+constexpr bool keeps_arg(int reduce) { return reduce == DVA_MAX || reduce == DVA_MIN; }
+
+// lanes of a wavefront that own the chunks of one row: the power of two that covers them, at most 64 (wider rows are
+// walked in column passes)
+static inline int lanes_per_row(int chunks) {
+  int lpr = 1;
+  while (lpr < chunks && lpr < 64) lpr <<= 1;
+  return lpr;
+}
+
+static inline int check_sizes(int64_t S, int64_t P, int64_t R, int C, int dtype, int reduce) {
+  if (S < 0 || P < 0 || R < 0 || C < 0) return DVA_ERR_INVALID;
+  if (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16) return DVA_ERR_INVALID;
+  if (reduce < DVA_SUM || reduce > DVA_MIN) return DVA_ERR_INVALID;
+  return DVA_OK;
+}
+
+// One item joins the pool of a channel, as dva_segment_csr_fwd has it: fp32 sum from 0 in item order (sum, mean), or the
+// extremum with the offset of its item -- the first item on ties, a NaN wins only as the first item.
+template <int REDUCE>
+__device__ __forceinline__ void pool_step(float& acc, uint32_t& best, float f, bool first, uint32_t off) {
+  if constexpr (REDUCE == DVA_MAX || REDUCE == DVA_MIN) {
+    if (first || (REDUCE == DVA_MAX ? f > acc : f < acc)) {
+      acc = f;
+      best = off;
+    }
+  } else {
+    acc = __fadd_rn(acc, f);
+  }
+}
+
+// What an item of a segment of `count` items at offset koff hands on of the segment's gradient g, times the weight w of the
+// tap it goes to (1 under a nearest gather): w g (sum), w (g / count) (mean, fp32 true division as segment_csr_bwd_kernel)
+// or w g where the stored arg offset ak is the item's (max / min).
+template <int REDUCE>
+__device__ __forceinline__ float pool_term(float g, float w, float count, uint32_t ak, uint32_t koff) {
+  if constexpr (REDUCE == DVA_SUM) return w * g;
+  else if constexpr (REDUCE == DVA_MEAN) return w * (g / count);
+  else return ak == koff ? w * g : 0.f;
+}
+
+// f(std::integral_constant<int, REDUCE>) for the run-time reduce (checked by check_sizes)
+template <typename F>
+static inline void with_reduce(int reduce, F&& f) {
+  if (reduce == DVA_SUM) f(std::integral_constant<int, DVA_SUM>{});
+  else if (reduce == DVA_MEAN) f(std::integral_constant<int, DVA_MEAN>{});
+  else if (reduce == DVA_MAX) f(std::integral_constant<int, DVA_MAX>{});
+  else f(std::integral_constant<int, DVA_MIN>{});
+}
+
+// f(RowType<T, VEC>) for the run-time dtype (checked by check_sizes): 16-byte chunks when wide, elements otherwise
+template <typename T_, int VEC_>
+struct RowType {
+  using T = T_;
+  static constexpr int VEC = VEC_;
+};
+static inline int row_vec(int dtype) { return dtype == DVA_F32 ? 4 : 8; }
+template <typename F>
+static inline void with_row_type(int dtype, bool wide, F&& f) {
+  if (dtype == DVA_F32) wide ? f(RowType<float, 4>{}) : f(RowType<float, 1>{});
+  else if (dtype == DVA_F16) wide ? f(RowType<f16_t, 8>{}) : f(RowType<f16_t, 1>{});
+  else wide ? f(RowType<bf16_t, 8>{}) : f(RowType<bf16_t, 1>{});
+}
 
 }  // namespace dva

@@ -329,7 +329,7 @@ using namespace dva;
 
 extern "C" {
 
-int dva_version(void) { return 330; }
+int dva_version(void) { return 331; }
 
 int dva_device_count(void) {
   int n = 0;

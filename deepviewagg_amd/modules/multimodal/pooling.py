@@ -216,32 +216,9 @@ class BimodalCSRPool(nn.Module, _SaveLast):
                 # not imply one view per point (csr = [0, 2, 2, 3]): always reduce there.
                 self._save(x_map, x_mod, csr_idx)
                 return x_mod
-            if (x_map is None and self._mode == 'max' and not self.save_last
-                    and csr_idx.shape[0] - 1 < x_mod.shape[0] and ops.gather_segment_max_applicable(x_mod, csr_idx)):
-                # ATOMIC max pool of a NON-exact mapping (several pixels per view, round 4): gather and max in one kernel,
-                # no [P, C] tensor; the result stays lazy at the VIEW level (identity gather over the pooled [V, C] rows) so
-                # that the view pooling keeps its fused path
-                return ops.gather_segment_max(x_mod, csr_idx)
-            if (x_map is not None and self._mode == 'max' and not self.save_last
-                    and ops.gather_segment_max_applicable(x_mod, csr_idx)):
-                # VIEW-level max pool of lazily gathered values: the same fused kernel, a plain [N, C] tensor out
-                return ops.gather_segment_max(x_mod, csr_idx).rows
-            if (x_map is None and self._mode != 'max' and not self.save_last
-                    and csr_idx.shape[0] - 1 < x_mod.shape[0]
-                    and ops.gather_segment_reduce_applicable(x_mod, csr_idx, self._mode)):
-                # ATOMIC mean / sum / min pool of a NON-exact mapping: gather and reduction in one kernel, forward and
-                # backward without a [P, C] tensor; the pooled [V, C] rows stay lazy at the VIEW level like the max pool's
-                return ops.gather_segment_reduce(x_mod, csr_idx, self._mode, level='atom')
-            if (x_map is not None and self._mode != 'max' and not self.save_last
-                    and ops.gather_segment_reduce_applicable(x_mod, csr_idx, self._mode)):
-                # VIEW-level mean / sum / min pool of lazily gathered values (the view pooling of the image-only models
-                # and of the mean-pool baselines): the same kernels, a plain [N, C] tensor out
-                return ops.gather_segment_reduce(x_mod, csr_idx, self._mode, level='view')
-            if not self.save_last and ops.interp_segment_reduce_applicable(x_mod, csr_idx, self._mode):
-                # BILINEAR lazy gather under any of the four modes, at the view level or at the atomic level of a non-exact
-                # mapping: interpolation and reduction in one kernel, forward and backward without a [P, C] tensor.  The
-                # plain pooled tensor comes out at both levels -- what the materialised route hands on
-                return ops.interp_segment_reduce(x_mod, csr_idx, self._mode, level='view')
+            if not self.save_last and ops.lazy_pool_applicable(x_mod, csr_idx, self._mode, atomic=x_map is None):
+                # gather and reduction in one kernel, forward and backward without a [P, C] tensor (ops.lazy_pool)
+                return ops.lazy_pool(x_mod, csr_idx, self._mode, atomic=x_map is None)
             x_mod = x_mod.materialize()
         x_pool = segment_csr(x_mod, csr_idx, reduce=self._mode)
         self._save(x_map, x_mod, csr_idx)

@@ -712,7 +712,9 @@ class SplitPlan:
                               "than asking row_plan(..., split=False) up front); counted in ops.SplitPlan.LAZY_PERMS",
                               RuntimeWarning, stacklevel=3)
             SplitPlan.LAZY_PERMS += 1
-            self._perm = _legacy_row_plan(self.row_idx, self.n_rows, False)[0][0]
+            self._perm, row_ptr = _legacy_row_plan(self.row_idx, self.n_rows, False)[0]
+            if self.row_ptr is None:        # a plan made of the row index alone
+                self.row_ptr = row_ptr
         return self._perm
 
     def __iter__(self):
@@ -985,57 +987,6 @@ def lazy_gather_nearest_mapping(x, images, atom_ptr, pixels, ratio, exact):
     return GatheredFeatures(rows, row_idx, counts, exact, plan)
 
 
-class _GatherSegmentMax(torch.autograd.Function):
-    """``segment_csr(rows[row_idx], atom_ptr, 'max')`` without the [P, C] tensor (csrc/gather.hip).  ``plan`` = the row plan
-    of the atoms (``row_plan(row_idx, R)[0]``) or None: built in backward."""
-
-    @staticmethod
-    def forward(ctx, rows, row_idx, atom_ptr, plan):
-        lib = _lib.load()
-        require_device(rows, row_idx, atom_ptr)
-        rows = rows.contiguous()
-        (R, C), V, P = rows.shape, atom_ptr.shape[0] - 1, row_idx.shape[0]
-        out = torch.empty((V, C), dtype=rows.dtype, device=rows.device)
-        arg = torch.empty((V, C), dtype=torch.int16, device=rows.device)
-        es = rows.element_size()
-        with _timed("gather_segment_max_fwd", P * (4 + C * es) + V * (8 + C * (es + 2))):
-            check(lib.dva_gather_segment_max_fwd(ptr(rows), ptr(row_idx), ptr(atom_ptr), ptr(out), ptr(arg), V, P, R, C,
-                                                 dtype_code(rows), stream_of(rows)), "dva_gather_segment_max_fwd")
-        ctx.save_for_backward(row_idx, atom_ptr, arg)
-        ctx.meta = (R, C, rows.dtype)
-        ctx.plan = plan
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        lib = _lib.load()
-        row_idx, atom_ptr, arg = ctx.saved_tensors
-        R, C, dt = ctx.meta
-        gout = gout.contiguous().to(dt)
-        V, P = atom_ptr.shape[0] - 1, row_idx.shape[0]
-        es = gout.element_size()
-        groups = C // (16 // es)
-        if SEGMENT_MAX_ATOMICS or groups & (groups - 1) or groups > 64 or P > 0x7fffffff:
-            grows = torch.zeros((R, C), dtype=torch.float32, device=gout.device)
-            with _timed("gather_segment_max_bwd", V * (8 + C * (es + 2 + 4)) + R * C * 4):
-                check(lib.dva_gather_segment_max_bwd(ptr(gout), ptr(arg), ptr(row_idx), ptr(atom_ptr), None, None, None,
-                                                     ptr(grows), V, P, R, C, dtype_code(gout), stream_of(gout)),
-                      "dva_gather_segment_max_bwd")
-            return grows.to(dt), None, None, None
-        perm, row_ptr = _plan_or_build(ctx.plan, row_idx, R, False)
-        voa = csr_expand(atom_ptr, P)
-        grows = torch.empty((R, C), dtype=torch.float32, device=gout.device)
-        with _timed("gather_segment_max_bwd", P * (16 + C * (es + 2)) + R * (C * 4 + 4)):
-            check(lib.dva_gather_segment_max_bwd(ptr(gout), ptr(arg), ptr(row_idx), ptr(atom_ptr), ptr(perm), ptr(row_ptr),
-                                                 ptr(voa), ptr(grows), V, P, R, C, dtype_code(gout), stream_of(gout)),
-                  "dva_gather_segment_max_bwd")
-        return grows.to(dt), None, None, None
-
-
-# A/B: fp32 atomics instead of the segmented reduction over the atoms' row plan (tests)
-SEGMENT_MAX_ATOMICS = False
-
-
 def _atoms_per_view_ok(atom_ptr):
     """True when no view owns more than 65534 atoms (the uint16 arg offsets of the fused max pool).  One device
     synchronisation per mapping tensor; the verdict is remembered ON the tensor object together with its version
@@ -1053,37 +1004,19 @@ def _atoms_per_view_ok(atom_ptr):
     return ok
 
 
-LAZY_NONEXACT = os.environ.get("DVA_LAZY_NONEXACT", "1") == "1"
-
-
-def gather_segment_max_applicable(x_mod, atom_ptr):
-    if not (LAZY_NONEXACT and isinstance(x_mod, GatheredFeatures)):
-        return False
-    C, es = x_mod.rows.shape[1], x_mod.rows.element_size()
-    # 16-byte alignment of the row base: a contiguous slice of a feature map with a storage offset that is not a
-    # multiple of 16 bytes takes the materialised route instead of DVA_ERR_UNSUPPORTED; non-contiguous
-    # rows are copied by the op (fresh, aligned allocation)
-    return (x_mod.rows.dtype in (torch.float32, torch.bfloat16, torch.float16) and C % (16 // es) == 0 and C > 0
-            and x_mod.rows.is_cuda and (not x_mod.rows.is_contiguous() or x_mod.rows.data_ptr() % 16 == 0)
-            and _atoms_per_view_ok(atom_ptr))
-
-
-def gather_segment_max(x_mod, atom_ptr):
-    """Atomic max pool of a lazily gathered NON-exact mapping (several pixels per view): ``GatheredFeatures`` at the atom
-    level -> ``GatheredFeatures`` at the VIEW level whose rows are the pooled [V, C] features (identity gather, one view
-    per row), so that the view-level pooling stays on its fused path (E_mod on the [V, C] rows -- it does not commute with
-    the max --, then the recompute chain).  Reference: modules/multimodal/modules.py:400-407, pooling.py:14-71."""
-    atom_ptr = _check_ptr(atom_ptr)
-    xv = _GatherSegmentMax.apply(x_mod.rows, x_mod.row_idx.contiguous(), atom_ptr, x_mod.plan)
+def _identity_gather(xv):
+    """Pooled [V, C] rows as ``GatheredFeatures`` under the identity gather (one view per row, exact, with the identity
+    row plan): what an atomic pool hands to the view pooling, so that it keeps its fused path (E_mod on the [V, C] rows --
+    it does not commute with the pool --, then the recompute chain)."""
     V = xv.shape[0]
     ident = torch.arange(V + 1, dtype=torch.int32, device=xv.device)
     return GatheredFeatures(xv, ident[:V], torch.ones(V, dtype=torch.int32, device=xv.device), True, (ident[:V], ident))
 
 
 class _GatherSegmentReduce(torch.autograd.Function):
-    """``segment_csr(rows[row_idx], csr_idx, reduce)`` for mean / sum / min without the [P, C] tensor, forward and backward
-    (csrc/gather_reduce.hip).  ``plan`` = the ``(perm, row_ptr)`` row plan of the items, or None / a split plan: the
-    permutation is then built in backward."""
+    """``segment_csr(rows[row_idx], csr_idx, reduce)`` for max / mean / sum / min without the [P, C] tensor, forward and backward
+    (csrc/gather_reduce.hip).  ``plan`` = the row plan of the items (a split plan hands out its permutation on first
+    use and keeps it), or None: built in backward."""
 
     @staticmethod
     def forward(ctx, rows, row_idx, csr_idx, plan, reduce):
@@ -1093,7 +1026,7 @@ class _GatherSegmentReduce(torch.autograd.Function):
         (R, C), S, P = rows.shape, csr_idx.shape[0] - 1, row_idx.shape[0]
         code = _lib.REDUCE_CODE[reduce]
         out = torch.empty((S, C), dtype=rows.dtype, device=rows.device)
-        arg = torch.empty((S, C), dtype=torch.int16, device=rows.device) if code == _lib.DVA_MIN else None
+        arg = torch.empty((S, C), dtype=torch.int16, device=rows.device) if code in (_lib.DVA_MAX, _lib.DVA_MIN) else None
         es = rows.element_size()
         with _timed("gather_segment_reduce_fwd", P * (4 + C * es) + S * (8 + C * es) + (S * C * 2 if arg is not None else 0)):
             check(lib.dva_gather_segment_reduce_fwd(ptr(rows), ptr(row_idx), ptr(csr_idx), ptr(out), ptr(arg), S, P, R, C,
@@ -1113,10 +1046,7 @@ class _GatherSegmentReduce(torch.autograd.Function):
         if P == 0 or R == 0 or C == 0:
             return torch.zeros((R, C), dtype=dt, device=gout.device), None, None, None, None
         gout = gout.contiguous().to(dt)
-        plan = ctx.plan
-        if plan is None or isinstance(plan, SplitPlan):
-            plan = row_plan(row_idx, R, with_counts=False, split=False)[0]
-        perm, row_ptr = plan
+        perm, row_ptr = _plan_or_build(ctx.plan, row_idx, R, False)      # a split plan builds its permutation once
         soi = csr_expand(csr_idx, P)
         grows = torch.empty((R, C), dtype=dt, device=gout.device)
         es = gout.element_size()
@@ -1128,43 +1058,47 @@ class _GatherSegmentReduce(torch.autograd.Function):
         return grows, None, None, None, None
 
 
-# A/B and tests: False sends mean / sum / min pools of lazily gathered features down the materialised route
-# (``x_mod.materialize()`` + ``segment_csr``)
+# A/B and tests: False sends the pools of nearest-gathered features down the materialised route
+# (``x_mod.materialize()`` + ``segment_csr``): LAZY_NONEXACT the max pool, LAZY_REDUCE the mean / sum / min pools
+LAZY_NONEXACT = True
 LAZY_REDUCE = True
-_LAZY_REDUCES = ("mean", "sum", "min")
+_LAZY_REDUCES = ("max", "mean", "sum", "min")
 
 
 def gather_segment_reduce_applicable(x_mod, csr_idx, reduce):
-    """Does ``gather_segment_reduce`` serve this pool?  Nearest-gathered features on the device in fp32 / bf16 / fp16, any
-    C >= 1 (rows that are not 16-byte aligned or whose C is no multiple of 16 bytes take the kernels' element path;
-    non-contiguous rows are copied by the op); ``min`` keeps uint16 arg offsets, so its segments own <= 65534 items."""
-    if not (LAZY_REDUCE and isinstance(x_mod, GatheredFeatures) and reduce in _LAZY_REDUCES):
+    """Does a module send this pool to ``gather_segment_reduce``?  Nearest-gathered features on the device in fp32 / bf16 /
+    fp16 with S, P and R below 2^31; ``max`` and ``min`` keep uint16 arg offsets, so their segments own <= 65534 items.
+    Mean / sum / min: any C >= 1 (rows that are not 16-byte aligned or whose C is no multiple of 16 bytes take the kernels'
+    element path; non-contiguous rows are copied by the op).  Max: rows of whole 16-byte chunks only, and a contiguous
+    slice whose base is not 16-byte aligned takes the materialised route -- the op itself serves those too, the gate is
+    the one the max pool was measured with."""
+    if not (isinstance(x_mod, GatheredFeatures) and reduce in _LAZY_REDUCES
+            and (LAZY_NONEXACT if reduce == "max" else LAZY_REDUCE)):
         return False
     rows = x_mod.rows
     if not (rows.is_cuda and csr_idx.is_cuda and rows.dim() == 2 and rows.shape[1] >= 1
             and rows.dtype in (torch.float32, torch.bfloat16, torch.float16)
             and max(rows.shape[0], x_mod.row_idx.shape[0], csr_idx.shape[0]) < (1 << 31)):
         return False
-    return reduce != "min" or _atoms_per_view_ok(csr_idx)
+    if reduce == "max" and not (rows.shape[1] * rows.element_size() % 16 == 0
+                                and (not rows.is_contiguous() or rows.data_ptr() % 16 == 0)):
+        return False
+    return reduce in ("mean", "sum") or _atoms_per_view_ok(csr_idx)
 
 
 def gather_segment_reduce(x_mod, csr_idx, reduce, level="view"):
-    """Mean / sum / min pool of lazily gathered features over CSR segments, gather and reduction in one kernel (reference:
-    ``BimodalCSRPool(mode)`` on ``x[idx]``, modules/multimodal/pooling.py:14-71).  ``level='view'``: the plain [N, C]
-    tensor of a view pooling.  ``level='atom'`` (atomic pool of a non-exact mapping, modules.py:400-407): the pooled
-    [V, C] rows as ``GatheredFeatures`` under the identity gather, as ``gather_segment_max`` returns them, so that the
-    view pooling behind it keeps its fused path."""
+    """Max / mean / sum / min pool of lazily gathered features over CSR segments, gather and reduction in one kernel
+    (reference: ``BimodalCSRPool(mode)`` on ``x[idx]``, modules/multimodal/pooling.py:14-71).  ``level='view'``: the plain
+    [N, C] tensor of a view pooling.  ``level='atom'`` (atomic pool of a non-exact mapping, several pixels per view,
+    modules.py:400-407): the pooled [V, C] rows as ``GatheredFeatures`` under the identity gather, so that the view
+    pooling behind it keeps its fused path."""
     if reduce not in _LAZY_REDUCES:
         raise ValueError(f"gather_segment_reduce reduces by one of {_LAZY_REDUCES}, got '{reduce}'")
     if level not in ("view", "atom"):
         raise ValueError(f"level must be 'view' or 'atom', got '{level}'")
     csr_idx = _check_ptr(csr_idx)
     xv = _GatherSegmentReduce.apply(x_mod.rows, x_mod.row_idx.contiguous(), csr_idx, x_mod.plan, reduce)
-    if level == "view":
-        return xv
-    V = xv.shape[0]
-    ident = torch.arange(V + 1, dtype=torch.int32, device=xv.device)
-    return GatheredFeatures(xv, ident[:V], torch.ones(V, dtype=torch.int32, device=xv.device), True, (ident[:V], ident))
+    return xv if level == "view" else _identity_gather(xv)
 
 
 class InterpolatedFeatures:
@@ -1394,7 +1328,7 @@ def interp_segment_reduce(x_mod, csr_idx, reduce, level="view"):
     kernel (reference: ``BimodalCSRPool(mode)`` on ``sparse_interpolation(x, coords, batch)``, modules/multimodal/
     pooling.py:14-71 on core/multimodal/image.py:105-170).  ``level='view'``: the plain [S, C] tensor.  ``level='atom'``
     (atomic pool of a non-exact mapping, modules.py:400-407): the pooled [V, C] rows as ``GatheredFeatures`` under the
-    identity gather, as ``gather_segment_reduce`` and ``gather_segment_max`` return them."""
+    identity gather, as ``gather_segment_reduce`` returns them."""
     if reduce not in _INTERP_REDUCES:
         raise ValueError(f"interp_segment_reduce reduces by one of {_INTERP_REDUCES}, got '{reduce}'")
     if level not in ("view", "atom"):
@@ -1405,14 +1339,30 @@ def interp_segment_reduce(x_mod, csr_idx, reduce, level="view"):
     anchors = getattr(x_mod, "anchors", None)
     xv = _InterpSegmentReduce.apply(x_mod.rows, _taps16(x_mod.tap_rows), _taps16(x_mod.tap_weights), csr_idx, reduce,
                                     anchors.contiguous() if anchors is not None else None, _geometry(x_mod.geometry))
-    if level == "view":
-        return xv
-    V = xv.shape[0]
-    ident = torch.arange(V + 1, dtype=torch.int32, device=xv.device)
-    return GatheredFeatures(xv, ident[:V], torch.ones(V, dtype=torch.int32, device=xv.device), True, (ident[:V], ident))
+    return xv if level == "view" else _identity_gather(xv)
 
 
 LAZY_TYPES = (GatheredFeatures, InterpolatedFeatures)     # what .materialize() turns into the reference's [P, C] tensor
+
+
+def lazy_pool_applicable(x_mod, csr_idx, reduce, atomic):
+    """Does ``lazy_pool`` serve ``BimodalCSRPool(reduce)`` on the lazy gather ``x_mod``?  ``atomic``: the pool of the atoms
+    of every view (``x_map is None``), else the pool of the views of every point.  A nearest gather at the atomic level is
+    pooled only where that shrinks it (S < P)."""
+    if isinstance(x_mod, GatheredFeatures):
+        return ((not atomic or csr_idx.shape[0] - 1 < x_mod.shape[0])
+                and gather_segment_reduce_applicable(x_mod, csr_idx, reduce))
+    return interp_segment_reduce_applicable(x_mod, csr_idx, reduce)
+
+
+def lazy_pool(x_mod, csr_idx, reduce, atomic):
+    """``segment_csr(x_mod.materialize(), csr_idx, reduce)`` in one kernel, forward and backward without a [P, C] tensor.
+    Nearest gather: a plain [N, C] tensor at the view level; at the atomic level the pooled [V, C] rows stay lazy under the
+    identity gather, so that the view pooling keeps its fused path.  Bilinear gather: the plain pooled tensor at both
+    levels -- what the materialised route hands on."""
+    if isinstance(x_mod, GatheredFeatures):
+        return gather_segment_reduce(x_mod, csr_idx, reduce, level="atom" if atomic else "view")
+    return interp_segment_reduce(x_mod, csr_idx, reduce, level="view")
 
 
 class _GatherRows(torch.autograd.Function):
@@ -3819,7 +3769,7 @@ def view_nll(x_view, labels, csr_idx, weight=None, ignore_index=-1):
     up to summation order, as a float32 scalar, without the [V, K] tensor and without the repeated labels.
 
     ``x_view`` is a ``GatheredFeatures`` (the lazy gather of an exact mapping, the identity gather that
-    ``gather_segment_max`` returns, or a ``GatheredFeatures.cat``) or a plain [V, K] tensor (rows under the identity
+    an atomic ``gather_segment_reduce`` returns, or a ``GatheredFeatures.cat``) or a plain [V, K] tensor (rows under the identity
     index); rows float32, bfloat16 or float16, upcast exactly, 1 <= K <= 64.  ``labels`` integer [N], ``csr_idx`` int64
     [N + 1].  Every view of a map row has that row's log-softmax, so the loss is a function of the per-row label
     counts (exact integers): ``sum w[y_v] (-logp_v[y_v]) / sum w[y_v]`` over the views whose point's label is not

@@ -14,8 +14,8 @@
  * CSR pointers are int64 (reference: torch.LongTensor). dtype codes below select the element type
  * of "feature" buffers (void*): fp32, bf16 or fp16; scores / mapping features / statistics are fp32.
  * DVA_F16 (torch.float16, autocast(float16)) is accepted by: dva_segment_csr_fwd / _bwd, dva_gather_csr,
- * dva_gather_nearest_fwd / _bwd, dva_gather_bilinear_fwd / _bwd, dva_gather_rows_sum, dva_gather_segment_max_fwd /
- * _bwd, dva_gather_segment_reduce_fwd / _bwd, dva_interp_segment_reduce_fwd / _bwd, dva_view_attention_*,
+ * dva_gather_nearest_fwd / _bwd, dva_gather_bilinear_fwd / _bwd, dva_gather_rows_sum,
+ * dva_gather_segment_reduce_fwd / _bwd, dva_interp_segment_reduce_fwd / _bwd, dva_view_attention_*,
  * dva_view_gather_attention_*, dva_view_gather_rows_grad, dva_view_gather_rows_grad_rec16_to, dva_rowbn_*, dva_chain_attn_fwd_dt, dva_chain_attn_bwd_dt and
  * dva_plan_split_rows_grad (dtype = out_dtype = DVA_F16).  Every other entry with a dtype argument returns
  * DVA_ERR_UNSUPPORTED for it before launching anything.
@@ -124,36 +124,20 @@ int dva_gather_nearest_bwd(const void* grad_out, const void* packed_idx, float* 
                            int64_t n_atoms, int32_t B, int32_t H, int32_t W, int32_t C,
                            int32_t dtype, void* stream);
 
-/* Nearest gather fused with the atomic MAX pool of a non-exact mapping (several pixels per view; reference
- * core/multimodal/image.py:1262-1287 followed by BimodalCSRPool('max'), modules/multimodal/pooling.py:14-71 through
- * modules.py:400-407): out[v][c] = max over the atoms a in [atom_ptr[v], atom_ptr[v+1]) of rows[row_idx[a]][c], 0 for a view
- * without atoms, ties -> first atom; no [P, C] tensor.  rows fp32 / bf16 [n_rows][C] (16-byte aligned, C % 4 resp. % 8 == 0),
- * arg uint16 [V][C] = offset of the winning atom inside its view (0xffff: none; views must own <= 65534 atoms).
- * _bwd: grad_rows fp32 [n_rows][C] = sum of grad_out[v][c] over the (view, channel) pairs whose winning atom lies on the row.
- * With the row plan of the atoms (perm int32 [P] = atoms sorted by map row, row_ptr int32 [n_rows + 1], as dva_row_plan gives
- * them) and view_of_atom int32 [P]: a deterministic segmented reduction, grad_rows written (C / vec a power of two <= 64);
- * with perm = row_ptr = view_of_atom = NULL: fp32 atomics into the caller-zeroed grad_rows (23 ms against 2 ms at
- * V = 8.4 M, C = 64 -- kept as the A/B). */
-int dva_gather_segment_max_fwd(const void* rows, const int32_t* row_idx, const int64_t* atom_ptr, void* out, void* arg,
-                               int64_t n_views, int64_t n_atoms, int64_t n_rows, int32_t C, int32_t dtype, void* stream);
-int dva_gather_segment_max_bwd(const void* grad_out, const void* arg, const int32_t* row_idx, const int64_t* atom_ptr,
-                               const int32_t* perm, const int32_t* row_ptr, const int32_t* view_of_atom, float* grad_rows,
-                               int64_t n_views, int64_t n_atoms, int64_t n_rows, int32_t C, int32_t dtype, void* stream);
-
-/* The same nearest gather fused with the MEAN / SUM / MIN pool behind it (BimodalCSRPool(mode), pooling.py:14-71; at the
- * atomic level of a non-exact mapping through modules.py:400-407, at the view level as the view pooling of the image-only
- * and the mean-pool baselines): out[s][c] = reduce over the items a in [seg_ptr[s], seg_ptr[s+1]) of rows[row_idx[a]][c]
+/* The nearest gather (core/multimodal/image.py:1262-1287) fused with the MAX / MEAN / SUM / MIN pool behind it
+ * (BimodalCSRPool(mode), pooling.py:14-71; at the atomic level of a non-exact mapping -- several pixels per view -- through
+ * modules.py:400-407, at the view level as the view pooling of the image-only and the mean-pool baselines): out[s][c] = reduce over the items a in [seg_ptr[s], seg_ptr[s+1]) of rows[row_idx[a]][c]
  * with dva_segment_csr_fwd's arithmetic (fp32 accumulation from 0 in item order, MEAN divides once by the fp32 count, one
- * rounding to the storage type, empty segments give 0, MIN: first item on ties) -- bit for bit the materialised
+ * rounding to the storage type, empty segments give 0, MAX / MIN: first item on ties) -- bit for bit the materialised
  * composition, no [P, C] tensor.  Any C >= 1, dtype fp32 / bf16 / fp16: 16-byte accesses when C % (16 / s) == 0 and rows,
- * out and arg are 16-byte aligned, one thread per (segment, channel) otherwise.  arg (MIN only, else nullable) uint16
+ * out and arg are 16-byte aligned, one thread per (segment, channel) otherwise.  arg (MAX / MIN, else nullable) uint16
  * [S][C] = offset of the winning item inside its segment (0xffff: none; segments must own <= 65534 items).
  * _bwd: grad_rows [R][C] in the rows' dtype, WRITTEN (every element once, fp32 accumulation, one rounding) =
  * sum over the items a on row r of grad_out[s][c] (SUM), grad_out[s][c] / count_s (MEAN, fp32 true division) or
- * grad_out[s][c] where arg[s][c] == a - seg_ptr[s] (MIN), s = seg_of_item[a] (int32 [P], dva_csr_expand); a segmented
+ * grad_out[s][c] where arg[s][c] == a - seg_ptr[s] (MAX / MIN), s = seg_of_item[a] (int32 [P], dva_csr_expand); a segmented
  * reduction over the row plan of the items (perm int32 [P] = items sorted by map row, row_ptr int32 [R + 1], as
  * dva_row_plan gives them), one wavefront per map row, no float atomics: deterministic.
- * reduce = DVA_MAX and sizes of 2^31 or more return DVA_ERR_UNSUPPORTED (the max pool keeps its own entries above). */
+ * Sizes of 2^31 or more return DVA_ERR_UNSUPPORTED. */
 int dva_gather_segment_reduce_fwd(const void* rows, const int32_t* row_idx, const int64_t* seg_ptr, void* out, void* arg,
                                   int64_t S, int64_t P, int64_t R, int32_t C, int32_t dtype, int32_t reduce,
                                   void* stream);

@@ -1,11 +1,11 @@
-"""References and the shared case generator of the fused gather + mean / sum / min pool (csrc/gather_reduce.hip).
+"""References and the shared case generator of the fused gather + max / mean / sum / min pool (csrc/gather_reduce.hip).
 Plain Python, imported by name like ``tolerances.py`` and ``primitives_ref.py``.
 
 * ``forward_ref``: a numpy restatement of the kernel contract, written from include/dva.h and the reference's
   expressions (``segment_csr(x[idx], ptr, mode)``, pooling.py:14-71 on image.py:1285) and not from the kernels: fp32
   accumulation from 0 in item order, the mean divides once by the fp32 count, one rounding to the storage type, empty
-  segments give 0, min takes the first item on ties (a NaN wins only as the first item) and keeps the uint16 offset of
-  the winner, 0xffff for none.
+  segments give 0, max and min take the first item on ties (a NaN wins only as the first item) and keep the uint16
+  offset of the winner, 0xffff for none.
 * ``forward_f64`` / ``backward_f64``: the same pool and its gradient w.r.t. the map rows in float64.
 * ``make_case``: the segment sizes and row indices every test of this feature shares (see its docstring).
 """
@@ -16,6 +16,7 @@ R_ROWS = 96                       # map rows of every generated case
 HOT_ROW, HOT_HITS = 5, 320        # one map row gathered by >= 300 items
 COLD_ROWS = (0, 17, 95)           # map rows no item gathers
 NP_DTYPE = {torch.float32: np.float32, torch.float16: np.float16}
+EXTREMA = ("max", "min")          # the modes that keep the offset of the winning item
 
 
 def round_to(x32, dtype):
@@ -46,14 +47,14 @@ def forward_ref(rows, row_idx, ptr, reduce, dtype):
     rows = np.asarray(rows, dtype=np.float32)
     S, C = len(ptr) - 1, rows.shape[1]
     out = np.zeros((S, C), dtype=np.float32)
-    arg = np.full((S, C), 0xffff, dtype=np.uint16) if reduce == "min" else None
+    arg = np.full((S, C), 0xffff, dtype=np.uint16) if reduce in EXTREMA else None
     for s in range(S):
         beg, end = int(ptr[s]), int(ptr[s + 1])
         acc = np.zeros(C, dtype=np.float32)
         for a in range(beg, end):
             v = rows[int(row_idx[a])]
-            if reduce == "min":
-                better = (v < acc) if a > beg else np.ones(C, dtype=bool)
+            if reduce in EXTREMA:
+                better = (v > acc if reduce == "max" else v < acc) if a > beg else np.ones(C, dtype=bool)
                 acc = np.where(better, v, acc)
                 arg[s] = np.where(better, np.uint16(a - beg), arg[s])
             else:
@@ -69,7 +70,7 @@ def forward_f64(rows, row_idx, ptr, reduce):
     x = np.asarray(rows, dtype=np.float64)[np.asarray(row_idx, dtype=np.int64)]
     S, C = len(ptr) - 1, x.shape[1]
     out = np.zeros((S, C), dtype=np.float64)
-    arg = np.full((S, C), -1, dtype=np.int64) if reduce == "min" else None
+    arg = np.full((S, C), -1, dtype=np.int64) if reduce in EXTREMA else None
     for s in range(S):
         beg, end = int(ptr[s]), int(ptr[s + 1])
         if end <= beg:
@@ -80,7 +81,7 @@ def forward_f64(rows, row_idx, ptr, reduce):
         elif reduce == "mean":
             out[s] = seg.sum(0) / (end - beg)
         else:
-            k = seg.argmin(0)                      # numpy: the first occurrence
+            k = seg.argmax(0) if reduce == "max" else seg.argmin(0)      # numpy: the first occurrence
             arg[s] = beg + k
             out[s] = seg[k, np.arange(C)]
     return out, arg
@@ -88,7 +89,7 @@ def forward_f64(rows, row_idx, ptr, reduce):
 
 def backward_f64(gout, row_idx, ptr, reduce, arg, n_rows):
     """float64 [R, C]: gradient of ``(forward(rows) * gout).sum()`` w.r.t. the map rows; ``arg`` = winning items of the
-    forward that is being differentiated (min)."""
+    forward that is being differentiated (max / min)."""
     g = np.asarray(gout, dtype=np.float64)
     row_idx = np.asarray(row_idx, dtype=np.int64)
     S, C = g.shape
@@ -97,7 +98,7 @@ def backward_f64(gout, row_idx, ptr, reduce, arg, n_rows):
         beg, end = int(ptr[s]), int(ptr[s + 1])
         if end <= beg:
             continue
-        if reduce == "min":
+        if reduce in EXTREMA:
             np.add.at(grows, (row_idx[arg[s]], np.arange(C)), g[s])
         else:
             np.add.at(grows, row_idx[beg:end], g[s] / (end - beg) if reduce == "mean" else g[s])
@@ -117,7 +118,7 @@ def segment_sizes(seed):
 
 def make_case(C, dtype, seed=0):
     """CPU tensors of one case: rows [R_ROWS, C] in ``dtype`` (values on a coarse grid, so that duplicates -- ties of the
-    min -- occur in every segment of a few items), row_idx int32 [P] with HOT_ROW gathered by HOT_HITS items spread over
+    max and the min -- occur in every segment of a few items), row_idx int32 [P] with HOT_ROW gathered by HOT_HITS items spread over
     the segments and COLD_ROWS by none, ptr int64 [S + 1], and an output gradient [S, C] in ``dtype``."""
     gen = torch.Generator().manual_seed(1000 * seed + C)
     sizes = segment_sizes(seed)

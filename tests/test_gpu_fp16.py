@@ -125,7 +125,7 @@ def test_chain_rows_gradient_rounds_once_to_nearest_even(plan_kind, chain_calls)
 
 
 def test_segment_max_and_bilinear_gather_fp16_match_their_fp32_upcast():
-    """The non-exact gather + atomic max pool (dva_gather_segment_max_*) and the bilinear gather (dva_gather_bilinear_*,
+    """The non-exact gather + atomic max pool (dva_gather_segment_reduce_*) and the bilinear gather (dva_gather_bilinear_*,
     backward through dva_gather_rows_sum) on an fp16 map against the same ops on its fp32 upcast."""
     from deepviewagg_amd import ops
     from deepviewagg_amd.modules.multimodal import pooling as P

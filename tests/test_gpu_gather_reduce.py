@@ -1,4 +1,4 @@
-"""-m gpu: the fused gather + mean / sum / min pool (csrc/gather_reduce.hip, ``ops.gather_segment_reduce``) against the
+"""-m gpu: the fused gather + max / mean / sum / min pool (csrc/gather_reduce.hip, ``ops.gather_segment_reduce``) against the
 materialised composition ``ops.segment_csr(x_mod.materialize(), ptr, reduce)`` -- forward bit for bit, backward against
 float64 with the materialised route's own error as the yardstick -- and through ``BimodalCSRPool``.
 
@@ -18,7 +18,7 @@ import tolerances as T
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-REDUCES = ["mean", "sum", "min"]
+REDUCES = ["max", "mean", "sum", "min"]
 DTYPES = [torch.float32, torch.bfloat16, torch.float16]
 CHANNELS = [1, 13, 16, 24, 64, 200]
 
@@ -79,10 +79,36 @@ def test_fused_pool_against_the_materialised_composition(C, dtype):
         assert err <= bound, (reduce, err, err_m, bound)
         for r in GR.COLD_ROWS:
             assert float(g[r].float().abs().max()) == 0.0, "a map row no item gathers keeps a zero gradient"
-        # determinism, and the plan handed in / a split plan (rebuilt as a permutation) give the same bits
+        # determinism, and the plan handed in / a split plan (its permutation built on first use) give the same bits
         for p in (None, plan, ops.SplitPlan(row_idx, case["R"], None, None)):
             _, g2 = one_route(ops, True, rows, row_idx, ptr, gout, reduce, plan=p)
             assert torch.equal(g2, g), (reduce, type(p))
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "bf16", "f16"])
+def test_max_pool_of_rows_whose_chunks_are_no_power_of_two(dtype):
+    """C = 136: 17 chunks on 32 lanes in bf16 / fp16, 34 chunks on 64 lanes in fp32 -- the rows whose max gradient went
+    through fp32 atomics before the plan reduction walked column passes.  Forward bit for bit, backward at the gates of
+    ``test_fused_pool_against_the_materialised_composition``, and two runs give equal bits."""
+    from deepviewagg_amd import ops
+    C = 136
+    case, dev = device_case(C, dtype)
+    rows, row_idx, ptr, gout = dev["rows"], dev["row_idx"], dev["ptr"], dev["gout"]
+    (out, g), (out_m, g_m) = both_routes(ops, rows, row_idx, ptr, gout, "max")
+    assert torch.equal(out, out_m)
+    want, _ = GR.forward_ref(GR.stored(case["rows"]), case["row_idx"].numpy(), case["ptr"].numpy(), "max", dtype)
+    assert np.array_equal(GR.stored(out), want)
+    _, arg64 = GR.forward_f64(GR.stored(case["rows"]), case["row_idx"].numpy(), case["ptr"].numpy(), "max")
+    g64 = torch.from_numpy(GR.backward_f64(GR.stored(case["gout"]), case["row_idx"].numpy(), case["ptr"].numpy(), "max",
+                                           arg64, case["R"]))
+    err, err_m = T.rel_err(g, g64), T.rel_err(g_m, g64)
+    bound = T.gate("grad_in", err_m) if dtype == torch.float32 else T.AUTOCAST_ROW_HEADROOM * err_m
+    print(f"gather_segment_reduce bwd C={C} {str(dtype)[6:]} max: fused {err:.3e} materialised {err_m:.3e} bound {bound:.3e}")
+    assert err <= bound, (err, err_m, bound)
+    for r in GR.COLD_ROWS:
+        assert float(g[r].float().abs().max()) == 0.0
+    _, g2 = one_route(ops, True, rows, row_idx, ptr, gout, "max")
+    assert torch.equal(g2, g), "two runs of the max gradient differ"
 
 
 @pytest.mark.parametrize("reduce", REDUCES)
@@ -97,7 +123,7 @@ def test_min_ties_go_to_the_first_item(reduce):
     gout = torch.randn(5, C, device=DEV)
     (out, g), (out_m, g_m) = both_routes(ops, rows, row_idx, ptr, gout, reduce)
     assert torch.equal(out, out_m)
-    if reduce == "min":
+    if reduce in GR.EXTREMA:
         assert torch.equal(g, g_m)          # every gradient element is a copy or a sum of two terms
         assert torch.equal(g[1], gout[0]) and torch.equal(g[2], gout[1] + gout[4])
     else:
@@ -106,8 +132,8 @@ def test_min_ties_go_to_the_first_item(reduce):
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "bf16", "f16"])
 def test_nan_and_inf_are_treated_as_segment_csr_treats_them(dtype):
-    """A NaN wins the min only as the first item of its segment (``v < acc`` is false for it afterwards), sums and means
-    carry it; infinities order as usual.  Same bits as the materialised composition, NaN payloads included."""
+    """A NaN wins the max and the min only as the first item of its segment (``v > acc`` and ``v < acc`` are false for it
+    afterwards), sums and means carry it; infinities order as usual.  Same bits as the materialised composition, NaN payloads included."""
     from deepviewagg_amd import ops
     C = 16
     rows = torch.randn(6, C, device=DEV)
@@ -122,8 +148,9 @@ def test_nan_and_inf_are_treated_as_segment_csr_treats_them(dtype):
         out = ops.gather_segment_reduce(lazy_of(ops, rows, row_idx), ptr, reduce)
         want = ops.segment_csr(rows[row_idx.long()], ptr, reduce=reduce)
         assert torch.equal(bits(out), bits(want)), reduce
-    out = ops.gather_segment_reduce(lazy_of(ops, rows, row_idx), ptr, "min").float()
-    assert bool(torch.isnan(out[0, ::2]).all()) and not bool(torch.isnan(out[1]).any())
+    for reduce in GR.EXTREMA:
+        out = ops.gather_segment_reduce(lazy_of(ops, rows, row_idx), ptr, reduce).float()
+        assert bool(torch.isnan(out[0, ::2]).all()) and not bool(torch.isnan(out[1]).any())
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "bf16", "f16"])
@@ -153,7 +180,8 @@ def test_empty_inputs(dtype):
 @pytest.mark.parametrize("layout", ["offset", "strided"])
 def test_rows_off_the_16_byte_grid_and_non_contiguous_rows(layout, dtype):
     """``offset``: a contiguous slice whose storage offset is one element (C = 16 would take the 16-byte path, the base
-    address sends it down the element path); ``strided``: every second column of a wider map (the op copies)."""
+    address sends it down the element path); ``strided``: every second column of a wider map (the op copies).  The op
+    serves both under every mode; a module sends the max pool of the ``offset`` rows down the materialised route."""
     from deepviewagg_amd import ops
     case, dev = device_case(16, dtype, seed=2)
     R, C = case["R"], 16
@@ -168,7 +196,8 @@ def test_rows_off_the_16_byte_grid_and_non_contiguous_rows(layout, dtype):
         rows = wide[:, ::2]
         assert not rows.is_contiguous()
     for reduce in REDUCES:
-        assert ops.gather_segment_reduce_applicable(lazy_of(ops, rows, dev["row_idx"]), dev["ptr"], reduce)
+        assert ops.gather_segment_reduce_applicable(lazy_of(ops, rows, dev["row_idx"]), dev["ptr"], reduce) \
+            == (reduce != "max" or layout == "strided")
         leaf = rows.detach().requires_grad_()
         assert leaf.data_ptr() == rows.data_ptr()
         out = ops.gather_segment_reduce(lazy_of(ops, leaf, dev["row_idx"]), dev["ptr"], reduce)
@@ -286,6 +315,7 @@ def test_non_exact_mapping_stays_lazy_through_the_atomic_mean_pool(monkeypatch):
 
 
 def test_min_pool_of_a_65535_item_segment_takes_the_materialised_route(monkeypatch):
+    """Max and min keep uint16 arg offsets: a segment of 65535 items materialises, one of 65534 does not."""
     from deepviewagg_amd import ops
     from deepviewagg_amd.modules.multimodal import pooling as P
     C, R = 4, 50
@@ -297,17 +327,19 @@ def test_min_pool_of_a_65535_item_segment_takes_the_materialised_route(monkeypat
     row_idx = torch.randint(0, R, (Pn,), generator=gen).to(torch.int32).to(DEV)
     x_map = torch.rand(Pn, 8, device=DEV)
     feats = lazy_of(ops, rows, row_idx)
-    assert not ops.gather_segment_reduce_applicable(feats, ptr, "min")
-    assert ops.gather_segment_reduce_applicable(feats, ptr, "mean")           # only min keeps uint16 offsets
-    counter = Counter(ops, monkeypatch)
-    out = P.BimodalCSRPool(mode='min')(None, feats, x_map, ptr)
-    assert counter.calls == 1
-    assert torch.equal(out, ops.segment_csr(rows[row_idx.long()], ptr, reduce='min'))
+    assert ops.gather_segment_reduce_applicable(feats, ptr, "mean")           # only max and min keep uint16 offsets
     short = torch.cat([torch.zeros(1, dtype=torch.long), torch.tensor([3, 65534, 0, 3]).cumsum(0)]).to(DEV)
-    assert ops.gather_segment_reduce_applicable(feats, short, "min")
-    assert torch.equal(P.BimodalCSRPool(mode='min')(None, feats, x_map, short),
-                       ops.segment_csr(rows[row_idx.long()], short, reduce='min'))
-    assert counter.calls == 1
+    counter = Counter(ops, monkeypatch)
+    for mode in GR.EXTREMA:
+        before = counter.calls
+        assert not ops.gather_segment_reduce_applicable(feats, ptr, mode)
+        out = P.BimodalCSRPool(mode=mode)(None, feats, x_map, ptr)
+        assert counter.calls == before + 1
+        assert torch.equal(out, ops.segment_csr(rows[row_idx.long()], ptr, reduce=mode))
+        assert ops.gather_segment_reduce_applicable(feats, short, mode)
+        assert torch.equal(P.BimodalCSRPool(mode=mode)(None, feats, x_map, short),
+                           ops.segment_csr(rows[row_idx.long()], short, reduce=mode))
+        assert counter.calls == before + 1
 
 
 def test_no3d_tail_with_a_mean_view_pool_on_lazy_features(monkeypatch):

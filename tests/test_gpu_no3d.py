@@ -166,7 +166,7 @@ def view_inputs(case, kind, dtype):
         cat = ops.GatheredFeatures.cat([a, b], order=order)
         assert cat.row_idx.shape[0] == V
         return cat, rows, lambda r: r[case["row_idx"].long()]
-    if kind == "identity":     # what gather_segment_max returns: the pooled [V, K] rows under the identity index
+    if kind == "identity":     # what an atomic gather_segment_reduce returns: the pooled [V, K] rows under the identity index
         xv = case["rows"][case["row_idx"].long()].to(dtype).to(DEV).requires_grad_()
         V = xv.shape[0]
         ident = torch.arange(V + 1, dtype=torch.int32, device=DEV)

@@ -227,8 +227,8 @@ def test_gather_segment_max_golden():
     ptr_ = t(g["atom_pointers"], DEV)
     packed = ops.pack_gather_index(t(g["images"], DEV), ptr_, t(g["pixels"], DEV), ratio=float(g["downscale"]))
     lazy = ops.lazy_gather_nearest(x, packed, exact=False)
-    assert ops.gather_segment_max_applicable(lazy, ptr_)
-    pooled = ops.gather_segment_max(lazy, ptr_)
+    assert ops.gather_segment_reduce_applicable(lazy, ptr_, "max")
+    pooled = ops.gather_segment_reduce(lazy, ptr_, "max", level="atom")
     assert isinstance(pooled, ops.GatheredFeatures) and pooled.exact
     assert torch.equal(pooled.materialize().cpu(), t(g["out_atomic_max"]))
 
@@ -253,23 +253,15 @@ def test_gather_segment_max_against_oracle(dtype, C):
     ref = O.segment_csr(r0[row_idx.long()], ptr_, 'max')
     (gr0,) = torch.autograd.grad((ref * w.float()).sum(), r0)
     grads = []
-    for atomics in (False, True):            # the deterministic plan reduction (C / vec a power of two) and the atomics A/B
-        ops.SEGMENT_MAX_ATOMICS = atomics
-        try:
-            r = rows.to(DEV).requires_grad_()
-            out = ops._GatherSegmentMax.apply(r, row_idx.to(DEV), ptr_.to(DEV), None)
-            assert torch.equal(out.float().cpu(), ref.detach())
-            (gr,) = torch.autograd.grad((out.float() * w.to(DEV).float()).sum(), r)
-        finally:
-            ops.SEGMENT_MAX_ATOMICS = False
+    for _ in range(2):        # the plan reduction serves every C (136: 17 resp. 34 chunks a row) and is bit-reproducible
+        r = rows.to(DEV).requires_grad_()
+        out = ops.gather_segment_reduce(ops.GatheredFeatures(r, row_idx.to(DEV), None, False), ptr_.to(DEV), "max")
+        assert torch.equal(out.float().cpu(), ref.detach())
+        (gr,) = torch.autograd.grad((out.float() * w.to(DEV).float()).sum(), r)
         torch.testing.assert_close(gr.float().cpu(), gr0, rtol=2e-2 if dtype == torch.bfloat16 else 1e-5,
                                    atol=2e-2 if dtype == torch.bfloat16 else 1e-5)
         grads.append(gr)
-    if C != 136:       # 17 column groups: no power-of-two lane team, both runs took the atomics
-        r = rows.to(DEV).requires_grad_()
-        out = ops._GatherSegmentMax.apply(r, row_idx.to(DEV), ptr_.to(DEV), None)
-        (gr2,) = torch.autograd.grad((out.float() * w.to(DEV).float()).sum(), r)
-        assert torch.equal(gr2, grads[0])          # the plan reduction is bit-reproducible
+    assert torch.equal(grads[1], grads[0])
 
 
 def test_gather_bilinear_golden():

@@ -433,7 +433,7 @@ def test_view_level_pool_with_equal_counts_is_not_the_identity():
 def test_non_exact_mapping_stays_lazy_through_the_atomic_max_pool():
     """VERDICT r3 missing 3: a mapping with several pixels per view (exact=False) through BimodalCSRPool('max') at the atomic
     level + GroupBimodalCSRPool at the view level: the fused gather + max pool (no [P, C] tensor, lazily gathered [V, C] rows
-    handed to the recompute chain) against the materialised route (DVA_LAZY_NONEXACT off) under autocast, and the pooled
+    handed to the recompute chain) against the materialised route (``ops.LAZY_NONEXACT`` off) under autocast, and the pooled
     rows bit-exact against segment_csr of the materialised gather."""
     from deepviewagg_amd.modules.multimodal import pooling as P
     from deepviewagg_amd import ops

@@ -247,7 +247,7 @@ def test_switch_and_what_the_op_serves(monkeypatch):
     assert not ops.interp_segment_reduce_applicable(ops.GatheredFeatures(dev(torch.float32, (63, 16)),
                                                                          dev(torch.int32, (40,)), None, False), ptr_, "mean")
     assert not ops.gather_segment_reduce_applicable(feats, ptr_, "mean")        # the nearest ops answer for their own type
-    assert not ops.gather_segment_max_applicable(feats, ptr_)
+    assert not ops.gather_segment_reduce_applicable(feats, ptr_, "max")
     # the limits: 4 P, R, S below 2^31
     assert ops.interp_segment_reduce_applicable(feats_of(torch.float32, 63, 16, (1 << 29) - 1), ptr_, "sum")
     assert not ops.interp_segment_reduce_applicable(feats_of(torch.float32, 63, 16, 1 << 29), ptr_, "sum")

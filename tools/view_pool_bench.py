@@ -2,8 +2,8 @@
 """Time the view-level ``BimodalCSRPool`` (mean by default) on lazily gathered features: the fused route against the
 materialised route (``x_mod.materialize()`` + ``ops.segment_csr``) on the same build and device.
 
---gather nearest: ``ops.gather_segment_reduce`` (csrc/gather_reduce.hip; max: ``ops.gather_segment_max``) against
-``ops.LAZY_REDUCE = False`` (max: ``ops.LAZY_NONEXACT = False``).  --gather bilinear: ``ops.interp_segment_reduce``
+--gather nearest: ``ops.gather_segment_reduce`` (csrc/gather_reduce.hip, all four modes) against
+``ops.LAZY_REDUCE = False`` (max: ``ops.LAZY_NONEXACT = False``, the switch of the max pool).  --gather bilinear: ``ops.interp_segment_reduce``
 (csrc/interp_reduce.hip) against ``ops.LAZY_INTERP_REDUCE = False`` on the same scenes, the views' coordinates being their
 pixels over the mapping size as ``bench.py`` forms them.
 

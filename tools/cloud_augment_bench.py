@@ -29,17 +29,18 @@ One JSON line on stdout; --out writes it (profiles/cloud_augment_bench.json).
 Usage:  python tools/cloud_augment_bench.py [--reps 7] [--window 0.2] [--out FILE]
 """
 import argparse
-import json
 import os
 import random
-import statistics
 import sys
 from types import SimpleNamespace
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import torch  # noqa: E402
+
+import measure  # noqa: E402
 
 SIZES = (100_000, 300_000, 1 << 20)
 
@@ -52,16 +53,6 @@ def chains():
         "scannet": ([A.Random3AxisRotation(rot_x=2, rot_y=2, rot_z=180), A.RandomSymmetry([True, True, False]),
                      A.RandomScaleAnisotropic([0.9, 1.1])], True),
     }
-
-
-def window(fn, inner):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(inner):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / inner
 
 
 def seed_with_every_symmetry(members, data):
@@ -159,20 +150,11 @@ def run_case(name, n, reps, seconds, gen):
     reducing = sum(type(m) in (A.RandomSymmetry, A.Center) for m in members)
     launches = {"fused": 1 + reducing, "eager": len(members) + reducing,
                 "torch": profiled_kernels(variants["torch"], seed)}
-    inner = {}
-    for key, fn in variants.items():
-        for _ in range(3):
-            fn()
-        torch.cuda.synchronize()
-        inner[key] = max(1, int(seconds * 1e3 / max(window(fn, 3), 1e-3)))
-    ms = {key: [] for key in variants}
-    for _ in range(reps):
-        for key, fn in variants.items():
-            ms[key].append(window(fn, inner[key]))
+    ms, inner = measure.alternate(variants, reps, measure.event_window, warmup=3, seconds=seconds, probe_inner=3)
     rows = {}
     for key in variants:
-        med = statistics.median(ms[key])
-        rows[key] = {"ms": round(med, 4), "min_ms": round(min(ms[key]), 4), "max_ms": round(max(ms[key]), 4),
+        t = measure.summarise(ms[key], 4)
+        rows[key] = {"ms": t["median"], "min_ms": t["min"], "max_ms": t["max"],
                      "applications_per_window": inner[key]}
         if key in launches:
             rows[key]["launches"] = launches[key]
@@ -182,24 +164,17 @@ def run_case(name, n, reps, seconds, gen):
             "checks": checks, "variants": rows}
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--window", type=float, default=0.2, help="seconds of work per timed window")
     ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    from deepviewagg_amd import _lib
+    args = ap.parse_args(argv)
     gen = torch.Generator().manual_seed(0)
-    result = {"tool": "cloud_augment_bench", "device": torch.cuda.get_device_name(0),
-              "dva_version": _lib.load().dva_version(), "source_sha256": _lib.source_sha256(), "reps": args.reps,
-              "window_s": args.window, "host_cpu_threads": torch.get_num_threads(),
-              "cases": [run_case(name, n, args.reps, args.window, gen) for n in SIZES for name in ("s3dis", "scannet")]}
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    result = measure.header(
+        "cloud_augment_bench", reps=args.reps, window_s=args.window, host_cpu_threads=torch.get_num_threads(),
+        cases=[run_case(name, n, args.reps, args.window, gen) for n in SIZES for name in ("s3dis", "scannet")])
+    measure.emit(result, args.out)
 
 
 if __name__ == "__main__":

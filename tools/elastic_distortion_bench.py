@@ -16,7 +16,6 @@ One JSON line on stdout; --out writes it (profiles/elastic_distortion_bench.json
 Usage:  python tools/elastic_distortion_bench.py [--reps 7] [--warmup 2] [--out FILE]
 """
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -24,9 +23,12 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+
+import measure  # noqa: E402
 
 GRANULARITY, MAGNITUDE = [0.2, 0.8], [0.4, 1.6]
 CLOUDS = (("scannet_scene", 150000, (8.0, 6.0, 3.0)), ("area_2^22", 1 << 22, (30.0, 20.0, 5.0)))
@@ -133,25 +135,18 @@ def run_cloud(name, n, extent, reps, warmup, gen):
     return out
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    from deepviewagg_amd import _lib
+    args = ap.parse_args(argv)
     gen = torch.Generator().manual_seed(0)
     np.random.seed(0)
-    result = {"tool": "elastic_distortion_bench", "device": torch.cuda.get_device_name(0),
-              "dva_version": _lib.load().dva_version(), "host_cpu_threads": torch.get_num_threads(),
-              "granularity": GRANULARITY, "magnitude": MAGNITUDE,
-              "clouds": [run_cloud(name, n, extent, args.reps, args.warmup, gen) for name, n, extent in CLOUDS]}
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    result = measure.header(
+        "elastic_distortion_bench", host_cpu_threads=torch.get_num_threads(), granularity=GRANULARITY,
+        magnitude=MAGNITUDE, clouds=[run_cloud(name, n, extent, args.reps, args.warmup, gen) for name, n, extent in CLOUDS])
+    measure.emit(result, args.out)
 
 
 if __name__ == "__main__":

@@ -23,7 +23,6 @@ the comparison of the results at the sizes timed; ``peak_mib`` the peak device m
 Usage:  python tools/full_res_vote_bench.py [--reps 5] [--warmup 1] [--host-reps 1] [--sizes 22,24] [--out FILE]
 """
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -31,9 +30,12 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+
+import measure  # noqa: E402
 
 BATCH = 300000
 VOTED = 0.3
@@ -160,35 +162,29 @@ def run_size(N, C, reps, warmup, host_reps, gen):
     return out
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--host-reps", type=int, default=1)
     ap.add_argument("--sizes", default="22,24", help="log2 of the raw cloud sizes")
     ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "full_res_vote_bench needs a HIP device"
-    from deepviewagg_amd import _lib
     gen = torch.Generator().manual_seed(0)
     sizes = [(1 << int(s), C) for s in args.sizes.split(",") for C in CLASSES]
     rows = []
     for N, C in sizes:
         rows.append(run_size(N, C, args.reps, args.warmup, args.host_reps, gen))
         print(f"done N={N} C={C}", file=sys.stderr, flush=True)
-    result = {"tool": "full_res_vote_bench", "device": torch.cuda.get_device_name(0),
-              "dva_version": _lib.load().dva_version(), "kernel_sources_sha256": _lib.source_sha256(),
-              "reps": args.reps, "warmup": args.warmup, "host_reps": args.host_reps,
-              "host_cpu_threads": torch.get_num_threads(),
-              "timing": "median ms; accumulate new / torch: device events around all batches; every other arm: host "
-                        "clock around a synchronised call; the arms of a part alternate in one process",
-              "sizes": rows}
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    result = measure.header(
+        "full_res_vote_bench", reps=args.reps, warmup=args.warmup, host_reps=args.host_reps,
+        host_cpu_threads=torch.get_num_threads(),
+        timing="median ms; accumulate new / torch: device events around all batches; every other arm: host "
+               "clock around a synchronised call; the arms of a part alternate in one process",
+        sizes=rows)
+    result["kernel_sources_sha256"] = result["source_sha256"]               # the name earlier records carry
+    measure.emit(result, args.out)
 
 
 if __name__ == "__main__":

@@ -14,17 +14,17 @@ unique, index_add / bincount), timed once with the host clock.  One JSON line on
 Usage:  python tools/grid_sampling_bench.py [--reps 5] [--warmup 2] [--out FILE]
 """
 import argparse
-import json
 import os
-import statistics
 import sys
-import time
 from types import SimpleNamespace
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import torch  # noqa: E402
+
+import measure  # noqa: E402
 
 
 def street(n, gen):
@@ -52,23 +52,12 @@ def room(n, gen):
 
 
 def timed(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return {"median_ms": round(statistics.median(ms), 3), "min_ms": round(min(ms), 3), "reps": reps}
+    t = measure.summarise(measure.repeated(fn, reps, measure.event_window, warmup), 3)
+    return {"median_ms": t["median"], "min_ms": t["min"], "reps": reps}
 
 
 def host_restatement(pos, size, attrs, labels, mode):
     """The same step on the host CPU in torch: quantise, unique, then per-voxel gather / means / majority."""
-    t0 = time.perf_counter()
     coords = torch.round(pos / size).long()
     _, cluster = torch.unique(coords, dim=0, return_inverse=True)
     m = int(cluster.max()) + 1
@@ -84,7 +73,6 @@ def host_restatement(pos, size, attrs, labels, mode):
         lab = labels - labels.min()
         nl = int(lab.max()) + 1
         _ = torch.bincount(cluster * nl + lab, minlength=m * nl).view(m, nl).argmax(1)
-    return round((time.perf_counter() - t0) * 1e3, 1)
 
 
 def run_case(name, n, size, mode, reps, warmup, gen):
@@ -109,12 +97,8 @@ def run_case(name, n, size, mode, reps, warmup, gen):
     out = transform()
     res = {"n": n, "size": size, "mode": mode, "n_voxels": int(out.pos.shape[0]),
            "transform": timed(transform, reps, warmup)}
-    ms = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        torch.randperm(n)
-        ms.append((time.perf_counter() - t0) * 1e3)
-    res["cpu_randperm_ms"] = round(statistics.median(ms), 3)
+    ms = measure.repeated(lambda: torch.randperm(n), reps, measure.host_window, warmup=0)
+    res["cpu_randperm_ms"] = measure.summarise(ms, 3)["median"]
     rank = torch.randperm(n).to(dev) if mode == "last" else None
     res["grid_cluster"] = timed(lambda: ops.grid_cluster(pos_d, size, rank=rank), reps, warmup)
     cl = ops.grid_cluster(pos_d, size, rank=rank)
@@ -129,30 +113,23 @@ def run_case(name, n, size, mode, reps, warmup, gen):
     floats = [v for v in attrs.values() if v.is_floating_point()]
     if mode == "last":
         floats = floats + [attrs["mapping_index"]]
-    res["host_cpu_restatement_ms"] = host_restatement(pos, size, floats + ([pos] if mode == "mean" else []),
-                                                      attrs["y"], mode)
+    host = lambda: host_restatement(pos, size, floats + ([pos] if mode == "mean" else []), attrs["y"], mode)
+    res["host_cpu_restatement_ms"] = round(measure.host_window(host), 1)
     res["host_cpu_threads"] = torch.get_num_threads()
     return res
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    from deepviewagg_amd import _lib
+    args = ap.parse_args(argv)
     gen = torch.Generator().manual_seed(0)
-    result = {"tool": "grid_sampling_bench", "device": torch.cuda.get_device_name(0),
-              "dva_version": _lib.load().dva_version(),
-              "last": run_case("last", 1 << 20, 0.05, "last", args.reps, args.warmup, gen),
-              "mean": run_case("mean", 1 << 24, 0.02, "mean", args.reps, args.warmup, gen)}
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    result = measure.header("grid_sampling_bench")
+    result["last"] = run_case("last", 1 << 20, 0.05, "last", args.reps, args.warmup, gen)
+    result["mean"] = run_case("mean", 1 << 24, 0.02, "mean", args.reps, args.warmup, gen)
+    measure.emit(result, args.out)
 
 
 if __name__ == "__main__":

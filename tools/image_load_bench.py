@@ -24,36 +24,24 @@ One JSON line on stdout; --out writes it (profiles/image_load_bench.json).
 Usage:  python tools/image_load_bench.py [--reps 5] [--window 0.5] [--out FILE]
 """
 import argparse
-import json
 import os
-import statistics
 import sys
 import tempfile
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+
+import measure  # noqa: E402
 
 HBM_PEAK = 8.0e12
 # name, views, source (W, H), ref_size, proj_upscale, file type
 CASES = (("s3dis", 8, (4096, 2048), (1024, 512), 2, "png"),
          ("scannet", 16, (1296, 968), (320, 240), 1, "jpg"),
          ("kitti360", 16, (1408, 376), (1408, 376), 1, "png"))
-
-
-class CountLaunches:
-    """ops.TIMER stand-in: records the calls into the HIP library."""
-
-    def __init__(self):
-        self.names = []
-
-    def launch(self, name, nbytes):
-        from deepviewagg_amd import ops
-        self.names.append(name)
-        return ops._NO_TIMER
 
 
 def scene_image(W, H, seed):
@@ -79,35 +67,12 @@ def algorithmic_bytes(N, Hs, Ws, size):
 
 
 def windows(variants, window_fn, reps, seconds):
-    inner = {}
-    for key, fn in variants.items():
-        fn()
-        inner[key] = max(1, int(seconds * 1e3 / max(window_fn(fn, 1), 1e-3)))
-    ms = {key: [] for key in variants}
-    for _ in range(reps):
-        for key, fn in variants.items():                    # the variants alternate
-            ms[key].append(window_fn(fn, inner[key]))
-    return {key: {"ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4),
-                  "calls_per_window": inner[key]} for key, v in ms.items()}
-
-
-def host_window(fn, inner):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(inner):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / inner
-
-
-def event_window(fn, inner):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(inner):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / inner
+    ms, inner = measure.alternate(variants, reps, window_fn, warmup=1, seconds=seconds)
+    rows = {}
+    for key in variants:
+        s = measure.summarise(ms[key], 4)
+        rows[key] = {"ms": s["median"], "min_ms": s["min"], "max_ms": s["max"], "calls_per_window": inner[key]}
+    return rows
 
 
 def run_case(name, N, src_size, ref_size, upscale, ext, reps, seconds, tmp):
@@ -137,18 +102,14 @@ def run_case(name, N, src_size, ref_size, upscale, ext, reps, seconds, tmp):
     def upload_op():
         return ops.read_images_u8(torch.from_numpy(np.stack(decoded)).to(dev), ref_size, downscale=1)
     assert torch.equal(op(), pil()) and torch.equal(upload_op(), pil()), f"{name}: the device op and PIL differ"
-    counter = CountLaunches()
-    ops.TIMER = counter
-    try:
+    with measure.launch_counter() as counter:
         op()
-    finally:
-        ops.TIMER = None
     nbytes = algorithmic_bytes(N, Hs, Ws, ref_size)
-    kernel = windows({"op": op}, event_window, reps, seconds)["op"]
+    kernel = windows({"op": op}, measure.event_window, reps, seconds)["op"]
     kernel.update(launches=counter.names, algorithmic_bytes=nbytes,
                   tb_per_s=round(nbytes / (kernel["ms"] * 1e-3) / 1e12, 4),
                   share_of_8tb_s=round(nbytes / (kernel["ms"] * 1e-3) / HBM_PEAK, 4))
-    decoded_rows = windows({"device_upload_and_op": upload_op, "pil_and_upload": pil}, host_window, reps, seconds)
+    decoded_rows = windows({"device_upload_and_op": upload_op, "pil_and_upload": pil}, measure.host_window, reps, seconds)
     decoded_rows["op_on_resident_sources"] = kernel
 
     def setting(on_device):
@@ -160,11 +121,8 @@ def run_case(name, N, src_size, ref_size, upscale, ext, reps, seconds, tmp):
     def load(on_device):
         return lambda: setting(on_device).load().x
     assert torch.equal(load(True)(), load(False)()), f"{name}: load() differs between the routes"
-    t0 = time.perf_counter()
-    for p in paths:
-        I.decode_image(p)
-    decode_ms = (time.perf_counter() - t0) * 1e3
-    load_rows = windows({"device": load(True), "host": load(False)}, host_window, reps, seconds)
+    decode_ms = measure.host_window(lambda: [I.decode_image(p) for p in paths])
+    load_rows = windows({"device": load(True), "host": load(False)}, measure.host_window, reps, seconds)
     load_rows["decode_alone_ms"] = round(decode_ms, 3)
 
     tr = NonStaticMask(ref_size=ref_size, proj_upscale=upscale, n_sample=5)
@@ -175,7 +133,7 @@ def run_case(name, N, src_size, ref_size, upscale, ext, reps, seconds, tmp):
             return tr(None, setting(on_device))[1].mask
         return fn
     assert torch.equal(mask(True)(), mask(False)()), f"{name}: NonStaticMask differs between the routes"
-    mask_rows = windows({"device": mask(True), "host": mask(False)}, host_window, reps, seconds)
+    mask_rows = windows({"device": mask(True), "host": mask(False)}, measure.host_window, reps, seconds)
     for rows in (decoded_rows, load_rows, mask_rows):
         if "device" in rows:
             rows["device"]["speedup_vs_host"] = round(rows["host"]["ms"] / rows["device"]["ms"], 2)
@@ -185,27 +143,19 @@ def run_case(name, N, src_size, ref_size, upscale, ext, reps, seconds, tmp):
             "checks": {"device_equals_pil": True}, "decoded": decoded_rows, "load": load_rows, "nonstatic_mask": mask_rows}
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.5, help="seconds of work per timed window")
     ap.add_argument("--cases", default=",".join(c[0] for c in CASES))
     ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "image_load_bench measures on a HIP device"
     import PIL
-    from deepviewagg_amd import _lib
     with tempfile.TemporaryDirectory() as tmp:
         cases = [run_case(*c, args.reps, args.window, tmp) for c in CASES if c[0] in args.cases.split(",")]
-    result = {"tool": "image_load_bench", "device": torch.cuda.get_device_name(0), "dva_version": _lib.load().dva_version(),
-              "source_sha256": _lib.source_sha256(), "pillow": PIL.__version__, "host_cpu_threads": torch.get_num_threads(),
-              "reps": args.reps, "window_s": args.window, "cases": cases}
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    measure.emit(measure.header("image_load_bench", pillow=PIL.__version__, host_cpu_threads=torch.get_num_threads(),
+                                reps=args.reps, window_s=args.window, cases=cases), args.out)
 
 
 if __name__ == "__main__":

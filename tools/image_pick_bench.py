@@ -23,11 +23,8 @@ One JSON line on stdout; --out writes it (profiles/image_pick_bench.json).
 Usage:  python tools/image_pick_bench.py [--reps 15] [--out FILE]
 """
 import argparse
-import json
 import os
-import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -36,8 +33,10 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from image_window_bench import CASES, CountDeviceOps, CountLaunches, Data, make_chain, make_scene, seed_all  # noqa: E402
-from mapping_select_bench import count_syncs  # noqa: E402
+import measure  # noqa: E402
+from bench_scenes import CASES, Data, make_chain, make_scene, run_chain, seed_all  # noqa: E402
+
+ARMS = {"device": True, "composition": False}
 
 
 def set_switch(on):
@@ -47,7 +46,7 @@ def set_switch(on):
 
 def big_scene(B, H, W, n_points, gen, dev, pixels=True):
     """B images of W x H over ``n_points`` points: image i sees random points through one random box (the scene of
-    tools/image_window_bench.py at another point count)."""
+    tools/bench_scenes.py at another point count)."""
     from deepviewagg_amd.core.multimodal.image import ImageMapping, SameSettingImageData
     pts, imgs, pix = [], [], []
     for i in range(B):
@@ -67,49 +66,29 @@ def big_scene(B, H, W, n_points, gen, dev, pixels=True):
     return images
 
 
-def profile_once(fn, prepare):
-    from deepviewagg_amd import ops
-    args = prepare(0)
-    torch.cuda.synchronize()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    counter = CountLaunches()
-    ops.TIMER = counter
-    try:
-        with CountDeviceOps() as mode:
-            fn(args)
-    finally:
-        ops.TIMER = None
-    torch.cuda.synchronize()
-    peak = int(torch.cuda.max_memory_allocated() - base)
-    args = prepare(0)
-    return {"torch_ops": mode.n, "dva_launches": counter.n, "syncs": count_syncs(lambda: fn(args)), "peak_bytes": peak}
-
-
 def time_both(fn, prepare, reps):
     """``fn(prepare(rep))`` with the switches on ('device') and off ('composition'), alternating inside every
     repetition; ``prepare`` (fresh inputs, seeds) is outside the timed region."""
-    ms = {"device": [], "composition": []}
-    extra = {}
-    for key, on in (("device", True), ("composition", False)):
-        set_switch(on)
+    args = []
+
+    def before(key, rep):
+        set_switch(ARMS[key])
+        args[:] = [prepare(rep or 0)]
+
+    call = lambda: fn(args[0])
+    profile = {}
+    for key in ARMS:                                    # warm up, then what one call does, before any timed window
         for _ in range(3):
-            fn(prepare(0))
-        extra[key] = profile_once(fn, prepare)
-    for rep in range(reps):
-        for key, on in (("device", True), ("composition", False)):
-            set_switch(on)
-            args = prepare(rep)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            fn(args)
-            torch.cuda.synchronize()
-            ms[key].append((time.perf_counter() - t0) * 1e3)
-    set_switch(True)
+            before(key, None)
+            call()
+        before(key, None)
+        profile[key] = measure.profile_once(call)
+    ms, _ = measure.alternate(dict.fromkeys(ARMS, call), reps, measure.host_window, warmup=0, before=before)
     rows = {}
-    for key in ms:
-        rows[key] = {"ms": round(statistics.median(ms[key]), 4), "min_ms": round(min(ms[key]), 4),
-                     "max_ms": round(max(ms[key]), 4), "reps": reps, **extra[key]}
+    for key in ARMS:
+        s = measure.summarise(ms[key], 4)
+        rows[key] = {"ms": s["median"], "min_ms": s["min"], "max_ms": s["max"], "reps": reps, **profile[key]}
+    set_switch(True)
     rows["device"]["speedup_vs_composition"] = round(rows["composition"]["ms"] / rows["device"]["ms"], 2)
     rows["device"]["range_below_composition"] = rows["device"]["max_ms"] < rows["composition"]["min_ms"]
     return rows
@@ -189,23 +168,18 @@ def crop_groups(B, H, W, kind, n_points, gen, dev):
     return out
 
 
-def run_chain(name, B, H, W, kind, reps, gen, dev):
+def run_chain_case(name, B, H, W, kind, reps, gen, dev):
     from deepviewagg_amd.core.data_transform.multimodal import image as T
     images, keep = make_scene(B, H, W, gen, dev)
     transforms = T.defer_image_windows(make_chain(kind, H, W))
 
     def prepare(rep):
         seed_all(3 + rep)
-        return None
 
     def fn(args):
-        data = Data(pos=torch.zeros(keep.shape[0], 3, device=dev), mapping_index=keep, num_nodes=keep.shape[0])
-        out = images
-        for tr in transforms:
-            data, out = tr(data, out)
-        return out
+        return run_chain(transforms, images, keep)
     outs, after = {}, {}
-    for key, on in (("device", True), ("composition", False)):
+    for key, on in ARMS.items():
         set_switch(on)
         seed_all(1)
         outs[key] = list(fn(None))
@@ -219,19 +193,17 @@ def run_chain(name, B, H, W, kind, reps, gen, dev):
             "variants": time_both(fn, prepare, reps)}
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--out", default=None)
     ap.add_argument("--skip-chains", action="store_true")
-    args = ap.parse_args()
-    from deepviewagg_amd import _lib
+    args = ap.parse_args(argv)
     from deepviewagg_amd.core.multimodal.image import ImageData
     dev = torch.device("cuda", 0)
     gen = torch.Generator().manual_seed(0)
-    result = {"tool": "image_pick_bench", "device": torch.cuda.get_device_name(0), "reps": args.reps,
-              "dva_version": _lib.load().dva_version(), "source_sha256": _lib.source_sha256(),
-              "composition": "the parent commit's method bodies (ON_DEVICE = False)", "rows": [], "chains": []}
+    result = measure.header("image_pick_bench", reps=args.reps,
+                            composition="the parent commit's method bodies (ON_DEVICE = False)", rows=[], chains=[])
     n = 300000
     for B in (32, 64):
         result["rows"].append(run_center_roll(f"center_roll_{B}", B, 512, 1024, n, args.reps, gen, dev))
@@ -249,12 +221,8 @@ def main():
         for name, B, H, W, kind in CASES:
             if name == "s3dis_64":
                 continue
-            result["chains"].append(run_chain(name, B, H, W, kind, args.reps, gen, dev))
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as fh:
-            fh.write(line + "\n")
+            result["chains"].append(run_chain_case(name, B, H, W, kind, args.reps, gen, dev))
+    measure.emit(result, args.out)
 
 
 if __name__ == "__main__":

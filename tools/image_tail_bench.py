@@ -25,17 +25,18 @@ One JSON line on stdout; --out writes it (profiles/image_tail_bench.json).
 Usage:  python tools/image_tail_bench.py [--reps 5] [--window 0.25] [--out FILE]
 """
 import argparse
-import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+
+import measure  # noqa: E402
 
 SHAPES = (("s3dis_equirect", (32, 3, 512, 1024)), ("crop_group", (16, 3, 256, 512)), ("scannet", (64, 3, 240, 320)),
           ("kitti360", (32, 3, 376, 1408)))
@@ -55,16 +56,6 @@ def make_setting(x, gen):
                                 num_points=n_points)
     return SameSettingImageData(path=np.array([f"img_{i}" for i in range(B)]), pos=torch.zeros(B, 3, device=dev),
                                 opk=torch.zeros(B, 3, device=dev), ref_size=(W, H), proj_upscale=1, mappings=m, x=x)
-
-
-def window(fn, inner):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(inner):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / inner
 
 
 def run_shape(name, shape, reps, seconds, gen):
@@ -105,22 +96,14 @@ def run_shape(name, shape, reps, seconds, gen):
                        "torch_max_abs_diff": float((outs["torch"] - outs["fused"]).abs().max())}
         del outs
     # warm-up of every variant, and the number of applications that fills a window
-    inner = {}
-    for key, fn in variants.items():
-        for _ in range(3):
-            fn()
-        torch.cuda.synchronize()
-        inner[key] = max(1, int(seconds * 1e3 / max(window(fn, 3), 1e-3)))
-    ms = {key: [] for key in variants}
-    for _ in range(reps):
-        for key, fn in variants.items():
-            ms[key].append(window(fn, inner[key]))
+    ms, inner = measure.alternate(variants, reps, measure.event_window, warmup=3, seconds=seconds, probe_inner=3)
     pixels = shape[0] * shape[2] * shape[3]
     rows = {}
     for key in variants:
         nbytes = pixels * (3 + (3 if key.endswith("train") else 0) + 12)
-        med = statistics.median(ms[key])
-        rows[key] = {"ms": round(med, 4), "min_ms": round(min(ms[key]), 4), "max_ms": round(max(ms[key]), 4),
+        t = measure.summarise(ms[key], 4)
+        med = t["median"]
+        rows[key] = {"ms": med, "min_ms": t["min"], "max_ms": t["max"],
                      "applications_per_window": inner[key], "bytes": nbytes,
                      "tb_per_s": round(nbytes / (med * 1e-3) / 1e12, 3),
                      "share_of_8tb_s": round(nbytes / (med * 1e-3) / HBM_PEAK, 3)}
@@ -130,25 +113,17 @@ def run_shape(name, shape, reps, seconds, gen):
     return {"shape": name, "x": list(shape), "checks": checks, "variants": rows}
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.25, help="seconds of work per timed window")
     ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    from deepviewagg_amd import _lib
+    args = ap.parse_args(argv)
     gen = torch.Generator().manual_seed(0)
-    result = {"tool": "image_tail_bench", "device": torch.cuda.get_device_name(0),
-              "dva_version": _lib.load().dva_version(), "source_sha256": _lib.source_sha256(), "reps": args.reps,
-              "window_s": args.window, "jitter": list(JITTER), "flip_p": 1.0,
-              "bytes_per_pixel": {"read": 3, "read_contrast": 3, "written": 12},
-              "shapes": [run_shape(name, shape, args.reps, args.window, gen) for name, shape in SHAPES]}
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    result = measure.header("image_tail_bench", reps=args.reps, window_s=args.window, jitter=list(JITTER), flip_p=1.0,
+                            bytes_per_pixel={"read": 3, "read_contrast": 3, "written": 12},
+                            shapes=[run_shape(name, shape, args.reps, args.window, gen) for name, shape in SHAPES])
+    measure.emit(result, args.out)
 
 
 if __name__ == "__main__":

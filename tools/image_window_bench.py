@@ -33,136 +33,36 @@ One JSON line on stdout; --out writes it (profiles/image_window_bench.json).
 Usage:  python tools/image_window_bench.py [--reps 5] [--window 0.25] [--out FILE]
 """
 import argparse
-import json
 import os
-import random
-import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
-from torch.utils._python_dispatch import TorchDispatchMode  # noqa: E402
 
-JITTER = (0.6, 0.6, 0.7)
+import measure  # noqa: E402
+from bench_scenes import CASES, JITTER, make_chain, make_scene, run_chain, seed_all  # noqa: E402
+
 HBM_PEAK = 8.0e12
-N_POINTS = 20000
-CASES = (("s3dis_32", 32, 512, 1024, "s3dis"), ("s3dis_64", 64, 512, 1024, "s3dis"),
-         ("kitti360_32", 32, 376, 1408, "kitti360"), ("crop_group_16", 16, 512, 1024, "crop"))
-
-
-class Data:
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
-
-
-class CountDeviceOps(TorchDispatchMode):
-    """Counts the aten operator calls that take or return a device tensor."""
-
-    def __init__(self):
-        super().__init__()
-        self.n = 0
-
-    def __torch_dispatch__(self, func, types, args=(), kwargs=None):
-        out = func(*args, **(kwargs or {}))
-        flat = list(args) + list((kwargs or {}).values()) + (list(out) if isinstance(out, (tuple, list)) else [out])
-        if any(torch.is_tensor(a) and a.is_cuda for a in flat):
-            self.n += 1
-        return out
-
-
-class CountLaunches:
-    """ops.TIMER stand-in: counts the calls into the HIP library, no events."""
-
-    def __init__(self):
-        self.n = 0
-
-    def launch(self, name, nbytes):
-        from deepviewagg_amd import ops
-        self.n += 1
-        return ops._NO_TIMER
-
-
-def make_scene(B, H, W, gen, dev):
-    """B uint8 images of W x H and a mapping in which image i sees random points through one random box."""
-    from deepviewagg_amd.core.multimodal.image import ImageMapping, SameSettingImageData
-    x = torch.randint(0, 256, (B, 3, H, W), dtype=torch.uint8, generator=gen).to(dev)
-    pts, imgs, pix = [], [], []
-    for i in range(B):
-        bw, bh = int(torch.randint(40, W // 2, (1,), generator=gen)), int(torch.randint(40, H // 2, (1,), generator=gen))
-        x0, y0 = int(torch.randint(0, W - bw, (1,), generator=gen)), int(torch.randint(0, H - bh, (1,), generator=gen))
-        n = int(torch.randint(bw * bh // 2, bw * bh, (1,), generator=gen))
-        pts.append(torch.randint(0, N_POINTS, (n,), generator=gen))
-        imgs.append(torch.full((n,), i))
-        pix.append(torch.stack([x0 + torch.randint(0, bw, (n,), generator=gen),
-                                y0 + torch.randint(0, bh, (n,), generator=gen)], 1).short())
-    pts, imgs, pix = torch.cat(pts), torch.cat(imgs), torch.cat(pix)
-    m = ImageMapping.from_dense(pts.to(dev), imgs.to(dev), pix.to(dev), torch.rand(pts.shape[0], 2, generator=gen).to(dev),
-                                num_points=N_POINTS)
-    images = SameSettingImageData(path=np.array([f"img_{i}" for i in range(B)]), pos=torch.zeros(B, 3, device=dev),
-                                  opk=torch.zeros(B, 3, device=dev), ref_size=(W, H), proj_upscale=1, mappings=m, x=x)
-    keep = torch.randperm(N_POINTS, generator=gen)[:N_POINTS // 2].to(dev)
-    return images, keep
-
-
-def make_chain(kind, H, W):
-    from deepviewagg_amd.core.data_transform.multimodal import image as T
-    tail = [T.ColorJitter(*JITTER), T.RandomHorizontalFlip(), T.ToFloatImage(), T.Normalize()]
-    if kind == "crop":
-        return [T.CropImageGroups(padding=8, min_size=64)] + tail
-    head = [T.SelectMappingFromPointId()] + ([T.CenterRoll()] if kind == "s3dis" else [])
-    return head + [T.PickImagesFromMappingArea(use_bbox=False), T.CropImageGroups(padding=8, min_size=64),
-                   T.PickImagesFromMemoryCredit(img_size=[W, H], n_img=4, k_coverage=2),
-                   T.JitterMappingFeatures(sigma=0.02, clip=0.03)] + tail
-
-
-def seed_all(seed):
-    torch.manual_seed(seed)
-    np.random.seed(seed)
-    random.seed(seed)
 
 
 def run_case(name, B, H, W, kind, reps, seconds, gen):
-    from deepviewagg_amd import ops
     from deepviewagg_amd.core.data_transform.multimodal import image as T
     dev = torch.device("cuda", 0)
     images, keep = make_scene(B, H, W, gen, dev)
     chain = make_chain(kind, H, W)
     chains = {"eager": T.fuse_image_tail(chain), "deferred": T.defer_image_windows(chain)}
-
-    def through(transforms):
-        def fn():
-            # the chain's first transform builds new settings and leaves `images` as it is; `data` is rewritten
-            data = Data(pos=torch.zeros(keep.shape[0], 3, device=dev), mapping_index=keep, num_nodes=keep.shape[0])
-            out = images
-            for tr in transforms:
-                data, out = tr(data, out)
-            return out
-        return fn
-
-    variants = {k: through(v) for k, v in chains.items()}
+    variants = {k: (lambda v=v: run_chain(v, images, keep)) for k, v in chains.items()}
     # equal results from equal seeds, and what one application launches and allocates
     outs, extra, after = {}, {}, {}
     for key, fn in variants.items():
         fn()
-        torch.cuda.synchronize()
-        base = torch.cuda.memory_allocated()
-        torch.cuda.reset_peak_memory_stats()
         seed_all(1)
-        counter = CountLaunches()
-        ops.TIMER = counter
-        try:
-            with CountDeviceOps() as mode:
-                outs[key] = fn()
-        finally:
-            ops.TIMER = None
-        torch.cuda.synchronize()
+        extra[key] = counters(lambda: outs.update({key: fn()}))
         after[key] = (torch.rand(1), np.random.rand())
-        extra[key] = {"torch_ops": mode.n, "dva_launches": counter.n,
-                      "peak_bytes": int(torch.cuda.max_memory_allocated() - base)}
     a, b = list(outs["eager"]), list(outs["deferred"])
     assert len(a) == len(b) and after["eager"] == after["deferred"], f"{name}: the variants drew differently"
     for u, v in zip(a, b):
@@ -170,38 +70,25 @@ def run_case(name, B, H, W, kind, reps, seconds, gen):
     windows = [[im.num_views, 3, int(im.x.shape[2]), int(im.x.shape[3])] for im in a]
     nbytes = sum(n * h * w for n, _, h, w in windows) * (3 + 3 + 12)
     del outs, a, b
-
-    def host_window(fn, inner):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(inner):
-            fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e3 / inner
-
-    rows = measure(variants, host_window, reps, seconds, nbytes, extra)
+    rows = measure_variants(variants, measure.host_window, reps, seconds, nbytes, extra)
     rows["deferred"]["speedup_vs_eager"] = round(rows["eager"]["ms"] / rows["deferred"]["ms"], 2)
     return {"case": name, "source": [B, 3, H, W], "chain": [type(tr).__name__ for tr in chain], "windows": windows,
             "checks": {"deferred_equals_eager": True}, "variants": rows}
 
 
-def measure(variants, window, reps, seconds, nbytes, extra):
-    inner = {}
-    for key, fn in variants.items():
-        for _ in range(3):
-            seed_all(2)
-            fn()
-        torch.cuda.synchronize()
-        inner[key] = max(1, int(seconds * 1e3 / max(window(fn, 3), 1e-3)))
-    ms = {key: [] for key in variants}
-    for rep in range(reps):
-        for key, fn in variants.items():
-            seed_all(3 + rep)
-            ms[key].append(window(fn, inner[key]))
+def counters(fn):
+    profile = measure.profile_once(fn)
+    return {k: profile[k] for k in ("torch_ops", "dva_launches", "peak_bytes")}
+
+
+def measure_variants(variants, window, reps, seconds, nbytes, extra):
+    ms, inner = measure.alternate(variants, reps, window, warmup=3, seconds=seconds, probe_inner=3,
+                                  before=lambda key, rep: seed_all(2 if rep is None else 3 + rep))
     rows = {}
     for key in variants:
-        med = statistics.median(ms[key])
-        rows[key] = {"ms": round(med, 4), "min_ms": round(min(ms[key]), 4), "max_ms": round(max(ms[key]), 4),
+        s = measure.summarise(ms[key], 4)
+        med = s["median"]
+        rows[key] = {"ms": med, "min_ms": s["min"], "max_ms": s["max"],
                      "applications_per_window": inner[key], "bytes": nbytes,
                      "tb_per_s": round(nbytes / (med * 1e-3) / 1e12, 4),
                      "share_of_8tb_s": round(nbytes / (med * 1e-3) / HBM_PEAK, 4), **extra.get(key, {})}
@@ -234,58 +121,28 @@ def run_kernel_case(name, B, H, W, Wc, Hc, reps, seconds, gen):
 
     variants = {"eager": eager, "window": windowed}
     assert torch.equal(eager(), windowed()), f"{name}: ops.image_window and the eager composition differ"
-    extra = {}
-    for key, fn in variants.items():
-        torch.cuda.synchronize()
-        base = torch.cuda.memory_allocated()
-        torch.cuda.reset_peak_memory_stats()
-        counter = CountLaunches()
-        ops.TIMER = counter
-        try:
-            with CountDeviceOps() as mode:
-                fn()
-        finally:
-            ops.TIMER = None
-        torch.cuda.synchronize()
-        extra[key] = {"torch_ops": mode.n, "dva_launches": counter.n,
-                      "peak_bytes": int(torch.cuda.max_memory_allocated() - base)}
-
-    def event_window(fn, inner):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(inner):
-            fn()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) / inner
-
+    extra = {key: counters(fn) for key, fn in variants.items()}
     nbytes = B * Hc * Wc * (3 + 3 + 12)
-    rows = measure(variants, event_window, reps, seconds, nbytes, extra)
+    rows = measure_variants(variants, measure.event_window, reps, seconds, nbytes, extra)
     rows["window"]["speedup_vs_eager"] = round(rows["eager"]["ms"] / rows["window"]["ms"], 2)
     return {"case": name, "source": [2 * B, 3, H, W], "windows": [[B, 3, Hc, Wc]],
             "checks": {"window_equals_eager": True}, "variants": rows}
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.25, help="seconds of work per timed window")
     ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    from deepviewagg_amd import _lib
+    args = ap.parse_args(argv)
     gen = torch.Generator().manual_seed(0)
-    result = {"tool": "image_window_bench", "device": torch.cuda.get_device_name(0),
-              "dva_version": _lib.load().dva_version(), "source_sha256": _lib.source_sha256(), "reps": args.reps,
-              "window_s": args.window, "jitter": list(JITTER), "bytes_per_pixel": {"read": 3, "read_contrast": 3, "written": 12},
-              "chains": [run_case(*case, args.reps, args.window, gen) for case in CASES],
-              "kernels": [run_kernel_case("window_256", 16, 512, 1024, 256, 256, args.reps, args.window, gen),
-                          run_kernel_case("window_full", 8, 512, 1024, 1024, 512, args.reps, args.window, gen)]}
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    result = measure.header(
+        "image_window_bench", reps=args.reps, window_s=args.window, jitter=list(JITTER),
+        bytes_per_pixel={"read": 3, "read_contrast": 3, "written": 12},
+        chains=[run_case(*case, args.reps, args.window, gen) for case in CASES],
+        kernels=[run_kernel_case("window_256", 16, 512, 1024, 256, 256, args.reps, args.window, gen),
+                 run_kernel_case("window_full", 8, 512, 1024, 1024, 512, args.reps, args.window, gen)])
+    measure.emit(result, args.out)
 
 
 if __name__ == "__main__":

@@ -22,12 +22,8 @@ One JSON line on stdout; --out writes it (profiles/mapping_collate_bench.json).
 Usage:  python tools/mapping_collate_bench.py [--reps 20] [--out FILE]
 """
 import argparse
-import json
 import os
-import statistics
 import sys
-import time
-import warnings
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -36,26 +32,13 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from image_window_bench import CountDeviceOps, CountLaunches  # noqa: E402
+import measure  # noqa: E402
+from bench_scenes import make_collate_mapping  # noqa: E402
 
 HBM_PEAK = 8.0e12
 N_IMAGES, N_FEAT = 10, 8
 BATCHES = (("batch_3e5", 300000, (2, 4, 8, 16)), ("batch_2^20", 1 << 20, (8,)))
-
-
-def make_mapping(n, gen, dev):
-    """n points with 0 .. 5 views each, one pixel per view."""
-    from deepviewagg_amd.core.multimodal.csr import CSRData
-    from deepviewagg_amd.core.multimodal.image import ImageMapping
-    sizes = torch.randint(0, 6, (n,), generator=gen)
-    pointers = torch.cat([torch.zeros(1, dtype=torch.long), sizes.cumsum(0)])
-    v = int(pointers[-1])
-    images = torch.randint(0, N_IMAGES, (v,), generator=gen)
-    images[:N_IMAGES] = torch.arange(N_IMAGES)
-    pixels = torch.stack([torch.randint(0, 1024, (v,), generator=gen), torch.randint(0, 512, (v,), generator=gen)], 1)
-    nested = CSRData(torch.arange(v + 1).to(dev), pixels.short().to(dev), dense=False)
-    return ImageMapping(pointers.to(dev), images.to(dev), nested, torch.rand(v, N_FEAT, generator=gen).to(dev),
-                        dense=False, is_index_value=[True, False, False])
+ARMS = {"device": True, "composition": False}
 
 
 def make_setting(mapping, ref_size, dev):
@@ -65,70 +48,32 @@ def make_setting(mapping, ref_size, dev):
                                 mappings=mapping)
 
 
-def count_syncs(fn):
-    torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode("warn")
-    try:
-        with warnings.catch_warnings(record=True) as w:
-            warnings.simplefilter("always")
-            fn()
-    finally:
-        torch.cuda.set_sync_debug_mode("default")
-    return sum("synchroniz" in str(x.message).lower() for x in w)
-
-
 def set_switch(on):
     from deepviewagg_amd.core.multimodal.image import ImageMapping
     ImageMapping.COLLATE_ON_DEVICE = on
 
 
-def profile_once(fn):
-    """What one call launches and synchronises."""
-    from deepviewagg_amd import ops
-    torch.cuda.synchronize()
-    counter = CountLaunches()
-    ops.TIMER = counter
-    try:
-        with CountDeviceOps() as mode:
-            fn()
-    finally:
-        ops.TIMER = None
-    torch.cuda.synchronize()
-    return {"torch_ops": mode.n, "dva_calls": counter.n, "syncs": count_syncs(fn)}
-
-
 def time_both(fn, reps):
     """fn with the switch on ('device') and off ('composition'), alternating inside every repetition."""
-    ms = {"device": [], "composition": []}
-    dev_ms = {"device": [], "composition": []}
-    extra = {}
-    for key, on in (("device", True), ("composition", False)):
-        set_switch(on)
+    before = lambda key, rep: set_switch(ARMS[key])
+    profiles = {}
+    for key in ARMS:                                    # warm up, then what one call does, before any timed window
+        before(key, None)
         for _ in range(3):
             fn()
-        extra[key] = profile_once(fn)
-    for _ in range(reps):
-        for key, on in (("device", True), ("composition", False)):
-            set_switch(on)
-            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            start.record()
-            fn()
-            stop.record()
-            torch.cuda.synchronize()
-            ms[key].append((time.perf_counter() - t0) * 1e3)
-            dev_ms[key].append(start.elapsed_time(stop))
-    set_switch(True)
+        profiles[key] = measure.profile_once(fn)
+    both, _ = measure.alternate(dict.fromkeys(ARMS, fn), reps, measure.both_window, warmup=0, before=before)
     rows = {}
-    for key in ms:
-        rows[key] = {"ms": round(statistics.median(ms[key]), 4), "min_ms": round(min(ms[key]), 4),
-                     "max_ms": round(max(ms[key]), 4), "device_ms": round(statistics.median(dev_ms[key]), 4),
-                     "device_min_ms": round(min(dev_ms[key]), 4), "device_max_ms": round(max(dev_ms[key]), 4),
-                     "reps": reps, **extra[key]}
+    for key in ARMS:
+        host, dev = (measure.summarise(ms, 4) for ms in zip(*both[key]))
+        profile = profiles[key]
+        rows[key] = {"ms": host["median"], "min_ms": host["min"], "max_ms": host["max"], "device_ms": dev["median"],
+                     "device_min_ms": dev["min"], "device_max_ms": dev["max"], "reps": reps,
+                     "torch_ops": profile["torch_ops"], "dva_calls": profile["dva_launches"], "syncs": profile["syncs"]}
+    set_switch(True)
     rows["device"]["speedup_vs_composition"] = round(rows["composition"]["ms"] / rows["device"]["ms"], 2)
-    rows["device"]["ranges_overlap"] = not (rows["device"]["min_ms"] > rows["composition"]["max_ms"]
-                                            or rows["composition"]["min_ms"] > rows["device"]["max_ms"])
+    rows["device"]["ranges_overlap"] = measure.ranges_overlap(
+        *((rows[key]["min_ms"], rows[key]["max_ms"]) for key in ARMS))
     return rows
 
 
@@ -167,8 +112,8 @@ def finish(rows, nbytes, n_items):
 def run_batch(name, n_points, n_samples, reps, gen, dev):
     from deepviewagg_amd.core.multimodal.image import ImageBatch, ImageData, ImageMappingBatch
     per = [n_points // n_samples + (1 if i < n_points % n_samples else 0) for i in range(n_samples)]
-    first = [make_mapping(n, gen, dev) for n in per]
-    second = [make_mapping(n, gen, dev) if i % 2 == 0 else None for i, n in enumerate(per)]
+    first = [make_collate_mapping(n, N_IMAGES, N_FEAT, gen, dev) for n in per]
+    second = [make_collate_mapping(n, N_IMAGES, N_FEAT, gen, dev) if i % 2 == 0 else None for i, n in enumerate(per)]
     one = [ImageData([make_setting(m, (1024, 512), dev)]) for m in first]
     two = [ImageData([make_setting(m, (1024, 512), dev)] + ([make_setting(s, (512, 256), dev)] if s is not None else []))
            for m, s in zip(first, second)]
@@ -194,24 +139,18 @@ def run_batch(name, n_points, n_samples, reps, gen, dev):
     return out
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    from deepviewagg_amd import _lib
+    args = ap.parse_args(argv)
     dev = torch.device("cuda", 0)
     gen = torch.Generator().manual_seed(0)
-    result = {"tool": "mapping_collate_bench", "device": torch.cuda.get_device_name(0), "reps": args.reps,
-              "dva_version": _lib.load().dva_version(), "source_sha256": _lib.source_sha256(),
-              "composition": "the parent commit's from_csr_list + insert_empty_groups "
-                             "(ImageMapping.COLLATE_ON_DEVICE = False)",
-              "batches": [run_batch(name, n, k, args.reps, gen, dev) for name, n, sizes in BATCHES for k in sizes]}
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as fh:
-            fh.write(line + "\n")
+    result = measure.header(
+        "mapping_collate_bench", reps=args.reps,
+        composition="the parent commit's from_csr_list + insert_empty_groups (ImageMapping.COLLATE_ON_DEVICE = False)",
+        batches=[run_batch(name, n, k, args.reps, gen, dev) for name, n, sizes in BATCHES for k in sizes])
+    measure.emit(result, args.out)
 
 
 if __name__ == "__main__":

@@ -11,18 +11,17 @@ the spread (max - min) of the repetitions, the HIP-event times of the two entrie
 device op on the algorithmic count  read N*8 + V*16 + P*4 + V*F*4, write (M+1)*8 + V'*16 + P'*4 + V'*F*4.
 """
 import argparse
-import json
 import os
-import statistics
 import sys
-import time
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-from deepviewagg_amd import _lib, ops                                   # noqa: E402
+import measure                                                           # noqa: E402
+from deepviewagg_amd import ops                                          # noqa: E402
 from deepviewagg_amd.core.multimodal.csr import CSRData                  # noqa: E402
 from deepviewagg_amd.core.multimodal.image import ImageMapping           # noqa: E402
 
@@ -66,15 +65,7 @@ def scene(name, gen):
     return exact_mapping(sizes, 32, gen), parents(n, 100, gen)
 
 
-def timed(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3, out
-
-
-def measure(name, reps):
+def run_shape(name, reps):
     gen = torch.Generator(device=DEV).manual_seed(1234)
     m, idx = scene(name, gen)
 
@@ -91,10 +82,8 @@ def measure(name, reps):
                                               (out.values[1].pointers, ref.values[1].pointers),
                                               (out.pixels, ref.pixels)))
     err = float((out.features - ref.features).abs().max())
-    ms = {True: [], False: []}
-    for _ in range(reps):
-        for route in (True, False):
-            ms[route].append(timed(lambda: run(route))[0])
+    ms, _ = measure.alternate({True: lambda: run(True), False: lambda: run(False)}, reps, measure.host_window,
+                              warmup=0)                                  # both routes are warm from the parity check
     ops.TIMER = ops.KernelTimer(only=("mapping_merge_count", "mapping_merge_fill"))
     run(True)
     kernels = {k: round(v["ms"], 4) for k, v in ops.TIMER.summary().items()}
@@ -102,33 +91,27 @@ def measure(name, reps):
     n, v, p = m.num_groups, m.num_views, m.num_atoms
     mm, v2, p2 = out.num_groups, out.num_views, out.num_atoms
     nbytes = n * 8 + v * 16 + p * 4 + v * F * 4 + (mm + 1) * 8 + v2 * 16 + p2 * 4 + v2 * F * 4
-    med = {r: statistics.median(x) for r, x in ms.items()}
-    spread = {r: max(x) - min(x) for r, x in ms.items()}
+    dev_ms, comp_ms = (measure.summarise(ms[r], 4) for r in (True, False))
+    runs = lambda x: [round(t, 4) for t in x]
     return {
         "shape": name, "points": n, "views": v, "atoms": p, "voxels": mm, "views_out": v2, "atoms_out": p2, "F": F,
         "indices_equal": bool(same), "features_max_abs_diff": err,
-        "device_op_ms": {"median": round(med[True], 4), "spread": round(spread[True], 4),
-                         "runs": [round(x, 4) for x in ms[True]], "entries_event_ms": kernels},
-        "composition_ms": {"median": round(med[False], 4), "spread": round(spread[False], 4),
-                           "runs": [round(x, 4) for x in ms[False]]},
-        "algorithmic_bytes": nbytes, "device_op_GBps": round(nbytes / med[True] / 1e6, 2),
-        "speedup": round(med[False] / med[True], 2),
-        "device_op_wins": bool(med[False] - med[True] > max(spread.values())),
+        "device_op_ms": {"median": dev_ms["median"], "spread": dev_ms["spread"], "runs": runs(ms[True]),
+                         "entries_event_ms": kernels},
+        "composition_ms": {"median": comp_ms["median"], "spread": comp_ms["spread"], "runs": runs(ms[False])},
+        "algorithmic_bytes": nbytes, "device_op_GBps": round(nbytes / dev_ms["median"] / 1e6, 2),
+        "speedup": round(comp_ms["median"] / dev_ms["median"], 2),
+        "device_op_wins": bool(comp_ms["median"] - dev_ms["median"] > max(dev_ms["spread"], comp_ms["spread"])),
     }
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mapping_merge_bench.json"))
-    args = ap.parse_args()
-    res = {"device": torch.cuda.get_device_name(0), "dva_version": _lib.load().dva_version(),
-           "tile_atoms": ops.MERGE_TILE_ATOMS, "reps": args.reps,
-           "shapes": [measure(s, args.reps) for s in ("headline", "batch")]}
-    with open(args.out, "w") as fh:
-        json.dump(res, fh, indent=1)
-        fh.write("\n")
-    print(json.dumps(res))
+    args = ap.parse_args(argv)
+    measure.emit(measure.header("mapping_merge_bench", tile_atoms=ops.MERGE_TILE_ATOMS, reps=args.reps,
+                                shapes=[run_shape(s, args.reps) for s in ("headline", "batch")]), args.out)
 
 
 if __name__ == "__main__":

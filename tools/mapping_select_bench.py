@@ -25,12 +25,8 @@ One JSON line on stdout; --out writes it (profiles/mapping_select_bench.json).
 Usage:  python tools/mapping_select_bench.py [--reps 20] [--out FILE]
 """
 import argparse
-import json
 import os
-import statistics
 import sys
-import time
-import warnings
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -39,40 +35,13 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from image_window_bench import CASES, CountDeviceOps, CountLaunches, Data, make_chain, make_scene, seed_all  # noqa: E402
+import measure  # noqa: E402
+from bench_scenes import CASES, make_chain, make_scene, make_select_mapping, run_chain, seed_all  # noqa: E402
 
 HBM_PEAK = 8.0e12
 N_IMAGES, N_FEAT = 300, 8
 SIZES = (("area_2^20", 1 << 20, 100000), ("batch_3e5", 300000, 30000))
-
-
-def make_mapping(n, gen, dev):
-    """n points with 0 .. 16 views each of distinct images, one pixel per view."""
-    from deepviewagg_amd.core.multimodal.csr import CSRData
-    from deepviewagg_amd.core.multimodal.image import ImageMapping
-    sizes = torch.randint(0, 17, (n,), generator=gen)
-    pointers = torch.cat([torch.zeros(1, dtype=torch.long), sizes.cumsum(0)])
-    v = int(pointers[-1])
-    point = torch.arange(n).repeat_interleave(sizes)
-    within = torch.arange(v) - pointers[:-1].repeat_interleave(sizes)
-    images = (torch.randint(0, N_IMAGES, (n,), generator=gen)[point] + within) % N_IMAGES
-    pixels = torch.stack([torch.randint(0, 1024, (v,), generator=gen), torch.randint(0, 512, (v,), generator=gen)], 1)
-    feats = torch.rand(v, N_FEAT, generator=gen)
-    nested = CSRData(torch.arange(v + 1).to(dev), pixels.short().to(dev), dense=False)
-    return ImageMapping(pointers.to(dev), images.to(dev), nested, feats.to(dev), dense=False,
-                        is_index_value=[True, False, False])
-
-
-def count_syncs(fn):
-    torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode("warn")
-    try:
-        with warnings.catch_warnings(record=True) as w:
-            warnings.simplefilter("always")
-            fn()
-    finally:
-        torch.cuda.set_sync_debug_mode("default")
-    return sum("synchroniz" in str(x.message).lower() for x in w)
+ARMS = {"device": True, "composition": False}
 
 
 def set_switch(on):
@@ -80,62 +49,31 @@ def set_switch(on):
     ImageMapping.SELECT_ON_DEVICE = on
 
 
-def profile_once(fn):
-    """What one call launches, synchronises and allocates."""
-    from deepviewagg_amd import ops
-    torch.cuda.synchronize()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    counter = CountLaunches()
-    ops.TIMER = counter
-    try:
-        with CountDeviceOps() as mode:
-            fn()
-    finally:
-        ops.TIMER = None
-    torch.cuda.synchronize()
-    peak = int(torch.cuda.max_memory_allocated() - base)
-    return {"torch_ops": mode.n, "dva_launches": counter.n, "syncs": count_syncs(fn), "peak_bytes": peak}
+def time_both(fn, reps, seed=False):
+    """fn with the switch on ('device') and off ('composition'), alternating inside every repetition; with ``seed``
+    every call starts from the seeds of its repetition."""
+    def before(key, rep):
+        set_switch(ARMS[key])
+        if seed:
+            seed_all(3 + (rep or 0))
 
-
-def time_both(fn, reps, before=None):
-    """fn with the switch on ('device') and off ('composition'), alternating inside every repetition."""
-    ms = {"device": [], "composition": []}
-    dev_ms = {"device": [], "composition": []}
-    extra = {}
-    for key, on in (("device", True), ("composition", False)):
-        set_switch(on)
+    profile = {}
+    for key in ARMS:                                    # warm up, then what one call does, before any timed window
         for _ in range(3):
-            if before:
-                before()
+            before(key, None)
             fn()
-        if before:
-            before()
-        extra[key] = profile_once(fn)
-    for rep in range(reps):
-        for key, on in (("device", True), ("composition", False)):
-            set_switch(on)
-            if before:
-                before(rep)
-            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            start.record()
-            fn()
-            stop.record()
-            torch.cuda.synchronize()
-            ms[key].append((time.perf_counter() - t0) * 1e3)
-            dev_ms[key].append(start.elapsed_time(stop))
-    set_switch(True)
+        before(key, None)
+        profile[key] = measure.profile_once(fn)
+    both, _ = measure.alternate(dict.fromkeys(ARMS, fn), reps, measure.both_window, warmup=0, before=before)
     rows = {}
-    for key in ms:
-        rows[key] = {"ms": round(statistics.median(ms[key]), 4), "min_ms": round(min(ms[key]), 4),
-                     "max_ms": round(max(ms[key]), 4), "device_ms": round(statistics.median(dev_ms[key]), 4),
-                     "device_min_ms": round(min(dev_ms[key]), 4), "device_max_ms": round(max(dev_ms[key]), 4),
-                     "reps": reps, **extra[key]}
+    for key in ARMS:
+        host, dev = (measure.summarise(ms, 4) for ms in zip(*both[key]))
+        rows[key] = {"ms": host["median"], "min_ms": host["min"], "max_ms": host["max"], "device_ms": dev["median"],
+                     "device_min_ms": dev["min"], "device_max_ms": dev["max"], "reps": reps, **profile[key]}
+    set_switch(True)
     rows["device"]["speedup_vs_composition"] = round(rows["composition"]["ms"] / rows["device"]["ms"], 2)
-    rows["device"]["ranges_overlap"] = not (rows["device"]["min_ms"] > rows["composition"]["max_ms"]
-                                            or rows["composition"]["min_ms"] > rows["device"]["max_ms"])
+    rows["device"]["ranges_overlap"] = measure.ranges_overlap(
+        *((rows[key]["min_ms"], rows[key]["max_ms"]) for key in ARMS))
     return rows
 
 
@@ -148,7 +86,7 @@ def mapping_bytes(m, rows_read):
 
 
 def run_methods(name, n, n_pick, reps, gen, dev):
-    m = make_mapping(n, gen, dev)
+    m = make_select_mapping(n, N_IMAGES, N_FEAT, gen, dev)
     pick = torch.randperm(n, generator=gen)[:n_pick].to(dev)
     idx = torch.randperm(N_IMAGES, generator=gen)[:256].to(dev)
     mask = (torch.rand(m.num_views, generator=gen) < 0.3).to(dev)
@@ -184,23 +122,13 @@ def run_methods(name, n, n_pick, reps, gen, dev):
     return out
 
 
-def run_chain(name, B, H, W, kind, reps, gen, dev):
+def run_chain_case(name, B, H, W, kind, reps, gen, dev):
     from deepviewagg_amd.core.data_transform.multimodal import image as T
     images, keep = make_scene(B, H, W, gen, dev)
     transforms = T.defer_image_windows(make_chain(kind, H, W))
-
-    def fn():
-        data = Data(pos=torch.zeros(keep.shape[0], 3, device=dev), mapping_index=keep, num_nodes=keep.shape[0])
-        out = images
-        for tr in transforms:
-            data, out = tr(data, out)
-        return out
-
-    def before(rep=0):
-        seed_all(3 + rep)
-
+    fn = lambda: run_chain(transforms, images, keep)
     outs, after = {}, {}
-    for key, on in (("device", True), ("composition", False)):
+    for key, on in ARMS.items():
         set_switch(on)
         seed_all(1)
         outs[key] = list(fn())
@@ -212,32 +140,26 @@ def run_chain(name, B, H, W, kind, reps, gen, dev):
         assert torch.equal(u.mappings.pointers, v.mappings.pointers) and torch.equal(u.mappings.images, v.mappings.images)
     del outs
     return {"case": name, "source": [B, 3, H, W], "chain": [type(tr).__name__ for tr in transforms],
-            "variants": time_both(fn, reps, before)}
+            "variants": time_both(fn, reps, seed=True)}
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--skip-chains", action="store_true")
-    args = ap.parse_args()
-    from deepviewagg_amd import _lib
+    args = ap.parse_args(argv)
     dev = torch.device("cuda", 0)
     gen = torch.Generator().manual_seed(0)
-    result = {"tool": "mapping_select_bench", "device": torch.cuda.get_device_name(0), "reps": args.reps,
-              "source_sha256": _lib.source_sha256(),
-              "composition": "the parent commit's method bodies (ImageMapping.SELECT_ON_DEVICE = False)",
-              "methods": [run_methods(name, n, k, args.reps, gen, dev) for name, n, k in SIZES], "chains": []}
+    result = measure.header("mapping_select_bench", reps=args.reps,
+                            composition="the parent commit's method bodies (ImageMapping.SELECT_ON_DEVICE = False)",
+                            methods=[run_methods(name, n, k, args.reps, gen, dev) for name, n, k in SIZES], chains=[])
     if not args.skip_chains:
         for name, B, H, W, kind in CASES:
             if name == "s3dis_64":
                 continue
-            result["chains"].append(run_chain(name, B, H, W, kind, args.reps, gen, dev))
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as fh:
-            fh.write(line + "\n")
+            result["chains"].append(run_chain_case(name, B, H, W, kind, args.reps, gen, dev))
+    measure.emit(result, args.out)
 
 
 if __name__ == "__main__":

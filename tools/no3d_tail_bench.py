@@ -17,17 +17,16 @@ it (profiles/no3d_tail_bench.json).
 Usage:  python tools/no3d_tail_bench.py [--reps 7] [--warmup 2] [--out FILE]
 """
 import argparse
-import json
 import os
-import statistics
 import sys
-import time
-import warnings
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import torch  # noqa: E402
+
+import measure  # noqa: E402
 
 POINTS = (300000, 1 << 20)
 FRACTIONS = (0.9, 0.5, 0.01)
@@ -37,45 +36,16 @@ MAP_ROWS = 1 << 18
 IGNORE = -1
 
 
-def stats(ms):
-    return {"median_ms": round(statistics.median(ms), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3)}
-
-
 def alternate(ours, theirs, reps, warmup):
-    for _ in range(warmup):
-        ours()
-        theirs()
-    ms = ([], [])
-    for _ in range(reps):
-        for k, fn in enumerate((ours, theirs)):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            fn()
-            torch.cuda.synchronize()
-            ms[k].append((time.perf_counter() - t0) * 1e3)
-    return stats(ms[0]), stats(ms[1])
-
-
-def observe(fn):
-    """(host synchronisations that torch reports, peak MiB allocated above what is resident) of one call."""
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.set_sync_debug_mode("warn")
-    try:
-        with warnings.catch_warnings(record=True) as seen:
-            warnings.simplefilter("always")
-            fn()
-    finally:
-        torch.cuda.set_sync_debug_mode("default")
-    torch.cuda.synchronize()
-    syncs = sum("synchroniz" in str(w.message).lower() and "prototype" not in str(w.message).lower() for w in seen)
-    return syncs, round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
-
-
-def side(timing, fn):
-    syncs, peak = observe(fn)
-    return dict(timing, host_syncs=syncs, peak_mib=peak)
+    """[timing and counters of ours, of theirs]: host clock around a synchronised call, the two alternating."""
+    arms = {"ours": ours, "theirs": theirs}
+    ms, _ = measure.alternate(arms, reps, measure.host_window, warmup=warmup)
+    sides = []
+    for key, fn in arms.items():
+        s, profile = measure.summarise(ms[key], 3), measure.profile_once(fn)
+        sides.append({"median_ms": s["median"], "min_ms": s["min"], "max_ms": s["max"], "host_syncs": profile["syncs"],
+                      "peak_mib": round(profile["peak_bytes"] / 2 ** 20, 1)})
+    return sides
 
 
 def run_fill(n, frac, K, reps, warmup, gen):
@@ -97,7 +67,7 @@ def run_fill(n, frac, K, reps, warmup, gen):
 
     equal = bool(torch.equal(ours(), composition()))
     a, b = alternate(ours, composition, reps, warmup)
-    return {"N": n, "seen_fraction": frac, "K": K, "fill_unseen": side(a, ours), "composition": side(b, composition),
+    return {"N": n, "seen_fraction": frac, "K": K, "fill_unseen": a, "composition": b,
             "speedup": round(b["median_ms"] / a["median_ms"], 2), "agree": {"rows_equal": equal}}
 
 
@@ -130,33 +100,27 @@ def run_view(n, views, K, reps, warmup, gen):
     lb = composition(); gb = rows.grad.clone()
     rel = lambda p, q: float((p.double() - q.double()).abs().max() / q.double().abs().max().clamp_min(1e-300))
     a, b = alternate(ours, composition, reps, warmup)
-    return {"N": n, "views_per_point": views, "V": V, "K": K, "map_rows": MAP_ROWS, "view_nll": side(a, ours),
-            "composition": side(b, composition), "speedup": round(b["median_ms"] / a["median_ms"], 2),
+    return {"N": n, "views_per_point": views, "V": V, "K": K, "map_rows": MAP_ROWS, "view_nll": a,
+            "composition": b, "speedup": round(b["median_ms"] / a["median_ms"], 2),
             "agree": {"loss": rel(la.detach(), lb.detach()), "grad": rel(ga, gb)}}
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "no3d_tail_bench needs a HIP device"
-    from deepviewagg_amd import _lib
     gen = torch.Generator().manual_seed(0)
-    result = {"tool": "no3d_tail_bench", "device": torch.cuda.get_device_name(0),
-              "dva_version": _lib.load().dva_version(), "kernel_sources_sha256": _lib.source_sha256(),
-              "reps": args.reps, "warmup": args.warmup, "host_cpu_threads": torch.get_num_threads(),
-              "timing": "host clock around a synchronised call, both sides alternating in one process; median and "
-                        "[min, max] over reps; view_nll is forward + backward",
-              "fill": [run_fill(n, f, K, args.reps, args.warmup, gen) for n in POINTS for f in FRACTIONS for K in CLASSES],
-              "view_nll": [run_view(n, v, K, args.reps, args.warmup, gen) for n in POINTS for v in VIEWS for K in CLASSES]}
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    result = measure.header(
+        "no3d_tail_bench", reps=args.reps, warmup=args.warmup, host_cpu_threads=torch.get_num_threads(),
+        timing="host clock around a synchronised call, both sides alternating in one process; median and "
+               "[min, max] over reps; view_nll is forward + backward")
+    result["kernel_sources_sha256"] = result["source_sha256"]               # the name earlier records carry
+    result["fill"] = [run_fill(n, f, K, args.reps, args.warmup, gen) for n in POINTS for f in FRACTIONS for K in CLASSES]
+    result["view_nll"] = [run_view(n, v, K, args.reps, args.warmup, gen) for n in POINTS for v in VIEWS for K in CLASSES]
+    measure.emit(result, args.out)
 
 
 if __name__ == "__main__":

@@ -17,14 +17,15 @@ Usage:  python tools/pointwise_pca_bench.py [--reps 5] [--warmup 2] [--out FILE]
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import torch  # noqa: E402
+
+import measure  # noqa: E402
 
 
 def room(n, gen):
@@ -63,29 +64,19 @@ def street(n, gen):
 
 
 def timed(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    ms = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return {"median_ms": round(statistics.median(ms), 3), "min_ms": round(min(ms), 3), "reps": reps}
+    t = measure.summarise(measure.repeated(fn, reps, measure.event_window, warmup), 3)
+    return {"median_ms": t["median"], "min_ms": t["min"], "reps": reps}
 
 
 def reference_cpu(search, nbr, chunk=1_000_000):
     """features.py:455-470 on the CPU: batch_pca per chunk, fp32, eigh for symeig."""
-    t0 = time.perf_counter()
     evals = []
     for i in range(0, nbr.shape[0], chunk):
         x = search[nbr[i:i + chunk].long()]
         c = x - x.mean(dim=1).unsqueeze(1)
         w, _ = torch.linalg.eigh(c.transpose(1, 2).bmm(c) / c.shape[1], UPLO='U')
         evals.append(w.clamp(min=0))
-    return torch.cat(evals), (time.perf_counter() - t0) * 1e3
+    return torch.cat(evals)
 
 
 def case(name, query, search, k, reps, warmup, with_self_knn):
@@ -99,7 +90,9 @@ def case(name, query, search, k, reps, warmup, with_self_knn):
     nbr, _ = ops.knn_query(q, s, k)
     out["pointwise_pca"] = timed(lambda: ops.pointwise_pca(s, nbr), reps, warmup)
     evals, _ = ops.pointwise_pca(s, nbr)
-    ref, cpu_ms = reference_cpu(search, nbr.cpu())
+    nbr_cpu, ref = nbr.cpu(), []
+    cpu_ms = measure.host_window(lambda: ref.append(reference_cpu(search, nbr_cpu)))
+    ref = ref[0]
     lmax = ref[:, 2:].clamp(min=1e-30)
     out["reference_cpu_batch_pca"] = {"ms": round(cpu_ms, 1), "threads": torch.get_num_threads(),
                                       "max_eigenvalue_diff_over_lmax": float(((evals.cpu() - ref).abs() / lmax).max())}
@@ -107,29 +100,22 @@ def case(name, query, search, k, reps, warmup, with_self_knn):
     return out
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "pointwise_pca_bench measures the HIP device"
-    from deepviewagg_amd import _lib
     gen = torch.Generator().manual_seed(0)
-    res = {"tool": "pointwise_pca_bench", "device": torch.cuda.get_device_name(),
-           "dva_version": _lib.load().dva_version()}
+    res = measure.header("pointwise_pca_bench")
     cloud = room(1_000_000, gen)
     res["self"] = case("self", cloud, cloud, 50, args.reps, args.warmup, True)
     full = street(5_000_000, gen)
     sub = full[torch.randperm(full.shape[0], generator=gen)[:1_000_000]]
     sub = sub + torch.randn(sub.shape, generator=gen) * 0.02
     res["full_pos"] = case("full_pos", sub, full, 50, args.reps, args.warmup, False)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    measure.emit(res, args.out)
 
 
 if __name__ == "__main__":

@@ -14,17 +14,17 @@ and how many centres were timed.  Timed once with the host clock.  One JSON line
 Usage:  python tools/radius_sampling_bench.py [--reps 5] [--warmup 2] [--host-centres 256] [--out FILE]
 """
 import argparse
-import json
 import os
-import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+
+import measure  # noqa: E402
 
 RADIUS = 2.0
 
@@ -35,18 +35,8 @@ def area(n, gen):
 
 
 def timed(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return {"median_ms": round(statistics.median(ms), 3), "min_ms": round(min(ms), 3), "reps": reps}
+    t = measure.summarise(measure.repeated(fn, reps, measure.event_window, warmup), 3)
+    return {"median_ms": t["median"], "min_ms": t["min"], "reps": reps}
 
 
 def host_times(pos, centres_by_b, dims, host_centres):
@@ -59,23 +49,24 @@ def host_times(pos, centres_by_b, dims, host_centres):
         KDTree = None
     if KDTree is not None:
         res["method"] = "sklearn KDTree(leaf_size=50).query_radius, one centre at a time"
-        t0 = time.perf_counter()
-        tree = KDTree(p, leaf_size=50)
-        res["build_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
+        built = []
+        res["build_ms"] = round(measure.host_window(lambda: built.append(KDTree(p, leaf_size=50))), 1)
+        tree = built[0]
     else:
         res["method"] = "numpy float64 brute force, one centre at a time"
         p64 = p.astype(np.float64)
         host_centres = min(host_centres, 16)
     for B, centres in centres_by_b.items():
         c = centres.numpy()[:host_centres]
-        t0 = time.perf_counter()
-        for row in c:
-            if KDTree is not None:
-                tree.query_radius(row[np.newaxis], r=RADIUS)
-            else:
-                d = ((p64 - row) ** 2).sum(1)
-                np.nonzero(d <= RADIUS * RADIUS)
-        res["query_ms"][str(B)] = round((time.perf_counter() - t0) * 1e3, 1)
+
+        def queries():
+            for row in c:
+                if KDTree is not None:
+                    tree.query_radius(row[np.newaxis], r=RADIUS)
+                else:
+                    d = ((p64 - row) ** 2).sum(1)
+                    np.nonzero(d <= RADIUS * RADIUS)
+        res["query_ms"][str(B)] = round(measure.host_window(queries), 1)
         res["centres_timed"][str(B)] = int(c.shape[0])
     return res
 
@@ -103,25 +94,18 @@ def run_cloud(n, centre_counts, reps, warmup, host_centres, gen):
     return out
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--host-centres", type=int, default=256)
     ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    from deepviewagg_amd import _lib
+    args = ap.parse_args(argv)
     gen = torch.Generator().manual_seed(0)
-    result = {"tool": "radius_sampling_bench", "device": torch.cuda.get_device_name(0),
-              "dva_version": _lib.load().dva_version(), "host_cpu_threads": torch.get_num_threads(),
-              "clouds": [run_cloud(n, (4, 256, 2048), args.reps, args.warmup, args.host_centres, gen)
-                         for n in (1 << 20, 1 << 24)]}
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    result = measure.header("radius_sampling_bench", host_cpu_threads=torch.get_num_threads(),
+                            clouds=[run_cloud(n, (4, 256, 2048), args.reps, args.warmup, args.host_centres, gen)
+                                    for n in (1 << 20, 1 << 24)])
+    measure.emit(result, args.out)
 
 
 if __name__ == "__main__":

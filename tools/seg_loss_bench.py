@@ -18,11 +18,8 @@ stdout; --out writes it (profiles/seg_loss_bench.json).
 Usage:  python tools/seg_loss_bench.py [--reps 9] [--warmup 3] [--out FILE]
 """
 import argparse
-import json
 import os
-import statistics
 import sys
-import time
 import types
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,6 +31,7 @@ import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
 import gen_golden_seg_loss as GEN  # noqa: E402
+import measure  # noqa: E402
 
 SIZES = [(300000, 13), (300000, 20), (1 << 20, 13), (1 << 20, 20)]
 IGNORE = -1
@@ -41,27 +39,9 @@ IGNORE = -1
 
 def alternate(ours, theirs, reps, warmup, host_clock=False):
     """median ms of ``ours()`` and of ``theirs()``, run alternately."""
-    for _ in range(warmup):
-        ours()
-        theirs()
-    torch.cuda.synchronize()
-    ms = ([], [])
-    for _ in range(reps):
-        for k, fn in enumerate((ours, theirs)):
-            if host_clock:
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                fn()
-                torch.cuda.synchronize()
-                ms[k].append((time.perf_counter() - t0) * 1e3)
-            else:
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                fn()
-                b.record()
-                b.synchronize()
-                ms[k].append(a.elapsed_time(b))
-    return round(statistics.median(ms[0]), 3), round(statistics.median(ms[1]), 3)
+    ms, _ = measure.alternate({"ours": ours, "theirs": theirs}, reps,
+                              measure.host_window if host_clock else measure.event_window, warmup=warmup)
+    return [measure.summarise(m, 3)["median"] for m in ms.values()]
 
 
 def rel(a, b):
@@ -152,27 +132,21 @@ def run_size(P, C, reps, warmup, gen):
     return out
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "seg_loss_bench needs a HIP device"
-    from deepviewagg_amd import _lib
     gen = torch.Generator().manual_seed(0)
-    result = {"tool": "seg_loss_bench", "device": torch.cuda.get_device_name(0),
-              "dva_version": _lib.load().dva_version(), "kernel_sources_sha256": _lib.source_sha256(),
-              "reps": args.reps, "warmup": args.warmup, "host_cpu_threads": torch.get_num_threads(),
-              "timing": "median ms of forward + backward, device events (tracker: host clock around a synchronised "
-                        "call), both sides alternating in one process",
-              "sizes": [run_size(P, C, args.reps, args.warmup, gen) for P, C in SIZES]}
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    result = measure.header(
+        "seg_loss_bench", reps=args.reps, warmup=args.warmup, host_cpu_threads=torch.get_num_threads(),
+        timing="median ms of forward + backward, device events (tracker: host clock around a synchronised "
+               "call), both sides alternating in one process",
+        sizes=[run_size(P, C, args.reps, args.warmup, gen) for P, C in SIZES])
+    result["kernel_sources_sha256"] = result["source_sha256"]               # the name earlier records carry
+    measure.emit(result, args.out)
 
 
 if __name__ == "__main__":

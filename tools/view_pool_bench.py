@@ -35,25 +35,22 @@ Usage:  python tools/view_pool_bench.py [--gather nearest] [--reps 7] [--warmup 
                                         [--out FILE]
 """
 import argparse
-import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import torch  # noqa: E402
+
+import measure  # noqa: E402
 
 POINTS = (300000, 1 << 20)
 CHANNELS = (13, 64, 128)
 DTYPES = (torch.bfloat16, torch.float32)
 VIEWS, IMAGES, H, W = 32, 32, 64, 128
 HBM_SPEC_BYTES_PER_S = 8.0e12
-
-
-def stats(ms):
-    return {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
 
 
 def algorithmic_bytes(P, S, R, C, es, mode, gather="nearest", anchors=None):
@@ -69,30 +66,6 @@ def algorithmic_bytes(P, S, R, C, es, mode, gather="nearest", anchors=None):
     fwd = P * (4 + C * es) + S * (8 + C * es) + (2 * S * C if arg else 0)
     bwd = P * (8 + C * es + (0 if mode == "sum" else 8) + (2 * C if arg else 0)) + R * (4 + C * es)
     return fwd + bwd
-
-
-def count_launches(fn):
-    try:
-        from torch.profiler import ProfilerActivity, profile
-        fn()
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        return int(sum(e.count for e in prof.key_averages()
-                       if getattr(e, "device_type", None) is not None and "cuda" in str(e.device_type).lower()))
-    except Exception as exc:        # no tracer on this install: not measured
-        print(f"launch count not measured: {exc!r}", file=sys.stderr)
-        return None
-
-
-def peak_bytes(fn):
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    fn()
-    torch.cuda.synchronize()
-    return int(torch.cuda.max_memory_allocated() - base)
 
 
 def run_case(bench, n, C, dtype, mode, workload, reps, warmup, gather="nearest"):
@@ -139,19 +112,9 @@ def run_case(bench, n, C, dtype, mode, workload, reps, warmup, gather="nearest")
              "grad_max_abs_diff": float((g_f.float() - g_m.float()).abs().max()),
              "grad_max_abs": float(g_m.float().abs().max())}
     del out_f, g_f, out_m, g_m
-    for _ in range(warmup):
-        for fn in routes.values():
-            fn()
-    ms = {k: [] for k in routes}
-    for _ in range(reps):
-        for k, fn in routes.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            fn()
-            e1.record()
-            torch.cuda.synchronize()
-            ms[k].append(e0.elapsed_time(e1))
+    # every window starts on an idle device
+    ms, _ = measure.alternate(routes, reps, measure.event_window, warmup=warmup,
+                              before=lambda key, rep: torch.cuda.synchronize())
     nbytes = algorithmic_bytes(V, S, R, C, x.element_size(), mode, gather,
                                ops.n_anchors(feats.geometry) + 1 if anchored else None)
     tap_bytes = algorithmic_bytes(V, S, R, C, x.element_size(), mode, gather)
@@ -159,9 +122,10 @@ def run_case(bench, n, C, dtype, mode, workload, reps, warmup, gather="nearest")
            "gather": gather, "plan": type(getattr(feats, "plan", None)).__name__, "algorithmic_bytes": nbytes,
            "backward_plan": ("anchor" if anchored else "tap") if gather == "bilinear" else "row", "agree": agree}
     for k, fn in routes.items():
-        t = stats(ms[k])
+        t = measure.summarise(ms[k], 4)
+        t = {"median_ms": t["median"], "min_ms": t["min"], "max_ms": t["max"]}
         share_of = tap_bytes if k == "fused_tap_plan" else nbytes
-        res[k] = dict(t, launches=count_launches(fn), peak_bytes=peak_bytes(fn),
+        res[k] = dict(t, launches=measure.profiler_kernel_count(fn), peak_bytes=measure.peak_bytes(fn),
                       hbm_share=round(share_of / (t["median_ms"] * 1e-3) / HBM_SPEC_BYTES_PER_S, 4))
     res["speedup"] = round(res["materialised"]["median_ms"] / res["fused"]["median_ms"], 3)
     if anchored:
@@ -169,7 +133,7 @@ def run_case(bench, n, C, dtype, mode, workload, reps, warmup, gather="nearest")
     return res
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
@@ -179,24 +143,18 @@ def main():
     ap.add_argument("--points", type=int, nargs="*", default=list(POINTS))
     ap.add_argument("--channels", type=int, nargs="*", default=list(CHANNELS))
     ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "view_pool_bench needs a HIP device"
     import bench
-    from deepviewagg_amd import _lib
-    result = {"tool": "view_pool_bench", "device": torch.cuda.get_device_name(0),
-              "dva_version": _lib.load().dva_version(), "kernel_sources_sha256": _lib.source_sha256(),
-              "gather": args.gather, "reps": args.reps, "warmup": args.warmup,
-              "timing": "device events around forward + backward of BimodalCSRPool on lazily gathered features, the two "
-                        "routes alternating in one process; median and [min, max] over reps",
-              "hbm_spec_bytes_per_s": HBM_SPEC_BYTES_PER_S,
-              "cases": [run_case(bench, n, C, dt, mode, args.workload, args.reps, args.warmup, args.gather)
-                        for mode in args.mode for n in args.points for C in args.channels for dt in DTYPES]}
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    result = measure.header(
+        "view_pool_bench", gather=args.gather, reps=args.reps, warmup=args.warmup,
+        timing="device events around forward + backward of BimodalCSRPool on lazily gathered features, the two "
+               "routes alternating in one process; median and [min, max] over reps",
+        hbm_spec_bytes_per_s=HBM_SPEC_BYTES_PER_S,
+        cases=[run_case(bench, n, C, dt, mode, args.workload, args.reps, args.warmup, args.gather)
+               for mode in args.mode for n in args.points for C in args.channels for dt in DTYPES])
+    result["kernel_sources_sha256"] = result["source_sha256"]               # the name earlier records carry
+    measure.emit(result, args.out)
 
 
 if __name__ == "__main__":

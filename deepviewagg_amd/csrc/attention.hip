@@ -176,45 +176,6 @@ __global__ __launch_bounds__(256) void att_bwd_val_kernel(const T* __restrict__ 
 // fused team path
 // ------------------------------------------------------------------------------------------------
 
-template <typename T>
-struct Vec16;
-template <>
-struct Vec16<float> {
-  static constexpr int N = 4;
-  typedef float4 raw;
-  static __device__ __forceinline__ void unpack(const raw& r, float* f) {
-    f[0] = r.x; f[1] = r.y; f[2] = r.z; f[3] = r.w;
-  }
-  static __device__ __forceinline__ raw pack(const float* f) { return make_float4(f[0], f[1], f[2], f[3]); }
-};
-template <>
-struct Vec16<bf16_t> {
-  static constexpr int N = 8;
-  typedef uint4 raw;
-  static __device__ __forceinline__ void unpack(const raw& r, float* f) {
-    f[0] = __uint_as_float(r.x << 16); f[1] = __uint_as_float(r.x & 0xffff0000u);
-    f[2] = __uint_as_float(r.y << 16); f[3] = __uint_as_float(r.y & 0xffff0000u);
-    f[4] = __uint_as_float(r.z << 16); f[5] = __uint_as_float(r.z & 0xffff0000u);
-    f[6] = __uint_as_float(r.w << 16); f[7] = __uint_as_float(r.w & 0xffff0000u);
-  }
-  static __device__ __forceinline__ raw pack(const float* f) {
-    uint4 r;
-    r.x = pack_bf16x2(f[0], f[1]);
-    r.y = pack_bf16x2(f[2], f[3]);
-    r.z = pack_bf16x2(f[4], f[5]);
-    r.w = pack_bf16x2(f[6], f[7]);
-    return r;
-  }
-};
-
-template <>
-struct Vec16<f16_t> {
-  static constexpr int N = 8;
-  typedef uint4 raw;
-  static __device__ __forceinline__ void unpack(const raw& r, float* f) { unpack_h8<f16_t>(r, f); }
-  static __device__ __forceinline__ raw pack(const float* f) { return pack_h8<f16_t>(f); }
-};
-
 struct TeamGeom {
   int lpr;      // lanes per view row (power of two, <= 64)
   int rows;     // view rows in flight per team (power of two)
@@ -291,12 +252,12 @@ __global__ __launch_bounds__(256) void att_fwd_team_kernel(
     const float* __restrict__ gw, const float* __restrict__ gb, T* __restrict__ out,
     float* __restrict__ att, float* __restrict__ gate, int32_t* __restrict__ amax, int64_t N, int C,
     int G, int scaling, float eps, TeamGeom tg) {
-  constexpr int VEC = Vec16<T>::N;
+  constexpr int VEC = Chunk16<T>::N;
   // team geometry: constants in the specialised instances (divisions become shifts, the reduction loops unroll,
   // the shuffle offsets are immediates), taken from `tg` in the generic one
   const int tg_lpr = LPR > 0 ? LPR : tg.lpr, tg_rows = LPR > 0 ? ROWS : tg.rows;
   const int tg_ts = tg_lpr * tg_rows, tg_lpg = tg_lpr / G;
-  typedef typename Vec16<T>::raw raw_t;
+  typedef typename Chunk16<T>::raw raw_t;
   const int lane = threadIdx.x & 63;
   const int li = lane & (tg_ts - 1);        // lane in team
   const int team_base = lane - li;          // first lane of the team inside the wave
@@ -455,7 +416,7 @@ __global__ __launch_bounds__(256) void att_fwd_team_kernel(
             att[rr[u] * G + g_lane] = a;
         }
         float f[VEC];
-        Vec16<T>::unpack(x[u], f);
+        Chunk16<T>::unpack(x[u], f);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) acc[k] = fmaf(a, f[k], acc[k]);
       }
@@ -471,7 +432,7 @@ __global__ __launch_bounds__(256) void att_fwd_team_kernel(
       if (row_slot == 0) {
 #pragma unroll
         for (int k = 0; k < VEC; ++k) acc[k] *= gt;
-        *reinterpret_cast<raw_t*>(out + p * C + col) = Vec16<T>::pack(acc);
+        *reinterpret_cast<raw_t*>(out + p * C + col) = Chunk16<T>::pack(acc);
       }
       continue;
     }
@@ -540,7 +501,7 @@ __global__ __launch_bounds__(256) void att_fwd_team_kernel(
         const float a = ok[u] ? __expf((cg[u] - m_l) * inv_dn) * inv_s_l : 0.f;
         if (ok[u] && g_first) att[rr[u] * G + g_lane] = a;
         float f[VEC];
-        Vec16<T>::unpack(x[u], f);
+        Chunk16<T>::unpack(x[u], f);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) acc[k] = fmaf(a, f[k], acc[k]);
       }
@@ -552,7 +513,7 @@ __global__ __launch_bounds__(256) void att_fwd_team_kernel(
     if (row_slot == 0) {
 #pragma unroll
       for (int k = 0; k < VEC; ++k) acc[k] *= gt_l;
-      *reinterpret_cast<raw_t*>(out + p * C + col) = Vec16<T>::pack(acc);
+      *reinterpret_cast<raw_t*>(out + p * C + col) = Chunk16<T>::pack(acc);
     }
   }
 }
@@ -570,12 +531,12 @@ __global__ __launch_bounds__(256, (LPR == 16 && ROWS == 4 && sizeof(T) == 4) ? 2
     const int64_t* __restrict__ ptr, const float* __restrict__ gw, T* __restrict__ gval,
     float* __restrict__ gcompat, float* __restrict__ gwb, float* __restrict__ rec, int rs, int64_t N,
     int C, int G, int scaling, TeamGeom tg) {
-  constexpr int VEC = Vec16<T>::N;
+  constexpr int VEC = Chunk16<T>::N;
   // team geometry: constants in the specialised instances (divisions become shifts, the reduction loops unroll,
   // the shuffle offsets are immediates), taken from `tg` in the generic one
   const int tg_lpr = LPR > 0 ? LPR : tg.lpr, tg_rows = LPR > 0 ? ROWS : tg.rows;
   const int tg_ts = tg_lpr * tg_rows, tg_lpg = tg_lpr / G;
-  typedef typename Vec16<T>::raw raw_t;
+  typedef typename Chunk16<T>::raw raw_t;
   __shared__ float s_wb[64];  // [2*G], G <= 32
   // long segments of the fused-gather form: d[v, g] of a point is parked in LDS between the two passes
   // (DBUF floats per wavefront, shared by its teams) instead of making a round trip through grad_compat
@@ -613,7 +574,7 @@ __global__ __launch_bounds__(256, (LPR == 16 && ROWS == 4 && sizeof(T) == 4) ? 2
   struct StageB {
     int32_t ri[U];
     float av[U];
-    typename Vec16<T>::raw go;
+    typename Chunk16<T>::raw go;
     float gt;
   };
   auto load_a = [&](int64_t p, int64_t& beg, int& n) {
@@ -676,7 +637,7 @@ __global__ __launch_bounds__(256, (LPR == 16 && ROWS == 4 && sizeof(T) == 4) ? 2
     load_a(p + 2 * pstep, beg2, n2);
     const int64_t col = (int64_t)lane_r * VEC;
     float go[VEC];
-    Vec16<T>::unpack(sb.go, go);
+    Chunk16<T>::unpack(sb.go, go);
     const float gt = sb.gt;
 
     // ---- pass 1: d[v,g] = sum_{c in g} go[c]*val[v,c];  sum_ad[g] = sum_v att[v,g]*d[v,g]
@@ -705,7 +666,7 @@ __global__ __launch_bounds__(256, (LPR == 16 && ROWS == 4 && sizeof(T) == 4) ? 2
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         float f[VEC];
-        Vec16<T>::unpack(x[u], f);
+        Chunk16<T>::unpack(x[u], f);
         float d = 0.f;
 #pragma unroll
         for (int k = 0; k < VEC; ++k) d = fmaf(go[k], f[k], d);
@@ -736,7 +697,7 @@ __global__ __launch_bounds__(256, (LPR == 16 && ROWS == 4 && sizeof(T) == 4) ? 2
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           float f[VEC];
-          Vec16<T>::unpack(x[u], f);
+          Chunk16<T>::unpack(x[u], f);
           float d = 0.f;
 #pragma unroll
           for (int k = 0; k < VEC; ++k) d = fmaf(go[k], f[k], d);
@@ -799,7 +760,7 @@ __global__ __launch_bounds__(256, (LPR == 16 && ROWS == 4 && sizeof(T) == 4) ? 2
         float f[VEC];
 #pragma unroll
         for (int k = 0; k < VEC; ++k) f[k] = go[k] * a;
-        *reinterpret_cast<raw_t*>(gval + r * C + col) = Vec16<T>::pack(f);
+        *reinterpret_cast<raw_t*>(gval + r * C + col) = Chunk16<T>::pack(f);
       }
     };
     if (small) {
@@ -880,7 +841,7 @@ static inline bool is_pow2(int x) { return x > 0 && (x & (x - 1)) == 0; }
 // Decide whether the fused team path applies and with which geometry.
 template <typename T>
 static bool team_geometry(int C, int G, int64_t N, int64_t V, TeamGeom* tg) {
-  constexpr int VEC = Vec16<T>::N;
+  constexpr int VEC = Chunk16<T>::N;
   if (C % VEC) return false;
   const int lpr = C / VEC;
   if (!is_pow2(lpr) || lpr > 64) return false;
@@ -904,9 +865,7 @@ static bool team_geometry(int C, int G, int64_t N, int64_t V, TeamGeom* tg) {
 static inline int grid_cap(int64_t blocks) { return capped_grid(blocks, 1, 256 * 16); }
 
 // the team kernels move whole 16-byte vectors: a base pointer that is no multiple of 16 takes the generic kernels
-// (a NULL pointer -- a tensor the form does not have -- passes)
-static inline bool aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
-
+// (a NULL pointer -- a tensor the form does not have -- passes aligned16)
 template <typename T>
 static int fwd_impl(const void* val, const int32_t* row_idx, const float* compat, const int64_t* ptr,
                     const float* gw,
@@ -989,9 +948,9 @@ __global__ __launch_bounds__(256) void rows_grad_team_kernel(
     TO* __restrict__ grows, int64_t R, int C, int G, int lpr, int lpg, int c0 = 0) {
   // C = row stride in elements; a launch covers the channels [c0, c0 + lpr * VEC) of every row.  Every caller passes
   // c0 = 0, lpr * VEC = C: whole rows (channel slabs, one launch each, lost: 7.01 ms against 7.14 - 10.37, HISTORY.md)
-  constexpr int VEC = Vec16<T>::N;
+  constexpr int VEC = Chunk16<T>::N;
   constexpr int U = 4;
-  typedef typename Vec16<T>::raw raw_t;
+  typedef typename Chunk16<T>::raw raw_t;
   const int lane = threadIdx.x & 63;
   const int lane_r = lane & (lpr - 1);
   const int slot = lane / lpr;
@@ -1051,7 +1010,7 @@ __global__ __launch_bounds__(256) void rows_grad_team_kernel(
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         float f[VEC];
-        Vec16<T>::unpack(raw[u], f);
+        Chunk16<T>::unpack(raw[u], f);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) acc[k] = fmaf(f[k], sc[u], acc[k]);
       }
@@ -1067,7 +1026,7 @@ __global__ __launch_bounds__(256) void rows_grad_team_kernel(
         for (int k = 0; k < VEC; k += 4)
           *reinterpret_cast<float4*>(dst + k) = make_float4(acc[k], acc[k + 1], acc[k + 2], acc[k + 3]);
       } else {
-        *reinterpret_cast<raw_t*>(reinterpret_cast<T*>(grows) + r * C + col) = Vec16<T>::pack(acc);
+        *reinterpret_cast<raw_t*>(reinterpret_cast<T*>(grows) + r * C + col) = Chunk16<T>::pack(acc);
       }
     }
   }
@@ -1082,8 +1041,8 @@ __global__ __launch_bounds__(256) void rows_grad_short_rec16_kernel(const T* __r
                                                                      const uint32_t* __restrict__ rec,
                                                                      TO* __restrict__ grows, int64_t R, int C, int lpr,
                                                                      int lpg) {
-  constexpr int VEC = Vec16<T>::N;
-  typedef typename Vec16<T>::raw raw_t;
+  constexpr int VEC = Chunk16<T>::N;
+  typedef typename Chunk16<T>::raw raw_t;
   const int lane = threadIdx.x & 63;
   const int lane_r = lane & (lpr - 1), slot = lane / lpr, slots = 64 / lpr;
   const int g_lane = lane_r / lpg;
@@ -1102,7 +1061,7 @@ __global__ __launch_bounds__(256) void rows_grad_short_rec16_kernel(const T* __r
       const uint32_t w2 = rv[1 + (g_lane >> 1)];
       const float sc = __uint_as_float((g_lane & 1) ? (w2 & 0xffff0000u) : (w2 << 16));
       float f[VEC];
-      Vec16<T>::unpack(*reinterpret_cast<const raw_t*>(gout + p * C + col), f);
+      Chunk16<T>::unpack(*reinterpret_cast<const raw_t*>(gout + p * C + col), f);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) acc[k] = fmaf(f[k], sc, acc[k]);
     }
@@ -1112,7 +1071,7 @@ __global__ __launch_bounds__(256) void rows_grad_short_rec16_kernel(const T* __r
       for (int k = 0; k < VEC; k += 4)
         *reinterpret_cast<float4*>(dst + k) = make_float4(acc[k], acc[k + 1], acc[k + 2], acc[k + 3]);
     } else {
-      *reinterpret_cast<raw_t*>(reinterpret_cast<T*>(grows) + r * C + col) = Vec16<T>::pack(acc);
+      *reinterpret_cast<raw_t*>(reinterpret_cast<T*>(grows) + r * C + col) = Chunk16<T>::pack(acc);
     }
   }
 }
@@ -1152,9 +1111,9 @@ __global__ __launch_bounds__(256) void rows_sum_team_kernel(const T* __restrict_
                                                              const float* __restrict__ weights, int shift,
                                                              float* __restrict__ grows, int64_t R, int C,
                                                              int lpr) {
-  constexpr int VEC = Vec16<T>::N;
+  constexpr int VEC = Chunk16<T>::N;
   constexpr int U = 4;
-  typedef typename Vec16<T>::raw raw_t;
+  typedef typename Chunk16<T>::raw raw_t;
   const int lane = threadIdx.x & 63;
   const int lane_r = lane & (lpr - 1), slot = lane / lpr, slots = 64 / lpr;
   const int64_t col = (int64_t)lane_r * VEC;
@@ -1184,7 +1143,7 @@ __global__ __launch_bounds__(256) void rows_sum_team_kernel(const T* __restrict_
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         float f[VEC];
-        Vec16<T>::unpack(raw[u], f);
+        Chunk16<T>::unpack(raw[u], f);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) acc[k] = fmaf(wu[u], f[k], acc[k]);
       }
@@ -1230,9 +1189,9 @@ __global__ __launch_bounds__(256) void anchor_rows_sum_kernel(const T* __restric
                                                                const float* __restrict__ sm,
                                                                const int4* __restrict__ tap_rows,
                                                                const T* __restrict__ Y) {
-  constexpr int VEC = Vec16<T>::N;
+  constexpr int VEC = Chunk16<T>::N;
   constexpr int U = 2;
-  typedef typename Vec16<T>::raw raw_t;
+  typedef typename Chunk16<T>::raw raw_t;
   const int lane = threadIdx.x & 63;
   const int lane_r = lane & (lpr - 1), slot = lane / lpr, slots = 64 / lpr;
   const int64_t col = (int64_t)lane_r * VEC;
@@ -1297,10 +1256,10 @@ __global__ __launch_bounds__(256) void anchor_rows_sum_kernel(const T* __restric
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         float f[VEC];
-        Vec16<T>::unpack(raw[u], f);
+        Chunk16<T>::unpack(raw[u], f);
         if (AFF == 1) {
           float zf[VEC];
-          Vec16<T>::unpack(zraw[u], zf);
+          Chunk16<T>::unpack(zraw[u], zf);
 #pragma unroll
           for (int e = 0; e < VEC; ++e) f[e] = fmaf(-ck2[e], zf[e], fmaf(cg[e], f[e], -ck1[e]));
         }
@@ -1352,7 +1311,7 @@ __global__ __launch_bounds__(256) void anchor_rows_sum_kernel(const T* __restric
 #pragma unroll
         for (int k2 = 0; k2 < 4; ++k2) {       // one row of Y at a time: 8 registers instead of 32
           float y[VEC];
-          Vec16<T>::unpack(*reinterpret_cast<const raw_t*>(Y + (int64_t)rr[k2] * C + col), y);
+          Chunk16<T>::unpack(*reinterpret_cast<const raw_t*>(Y + (int64_t)rr[k2] * C + col), y);
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
 #pragma unroll
@@ -1392,29 +1351,27 @@ __global__ __launch_bounds__(256) void rows_sum_generic_kernel(const T* __restri
 }
 
 template <typename T>
-static int rows_sum_impl(const void* gout, const int32_t* perm, const int32_t* row_ptr, const float* weights,
+static void rows_sum_impl(const void* gout, const int32_t* perm, const int32_t* row_ptr, const float* weights,
                          int shift, float* grows, int64_t R, int C, hipStream_t s) {
-  constexpr int VEC = Vec16<T>::N;
+  constexpr int VEC = Chunk16<T>::N;
   const int lpr = C / VEC;
-  const bool team_ok = (C % VEC) == 0 && is_pow2(lpr) && lpr <= 64 && ((uintptr_t)gout % 16 == 0) &&
-                       ((uintptr_t)grows % 16 == 0);
+  const bool team_ok = (C % VEC) == 0 && is_pow2(lpr) && lpr <= 64 && aligned16(gout) && aligned16(grows);
   if (team_ok)
     hipLaunchKernelGGL((rows_sum_team_kernel<T>), dim3(grid_cap((R + 3) / 4)), dim3(256), 0, s, (const T*)gout,
                        perm, row_ptr, weights, shift, grows, R, C, lpr);
   else
     hipLaunchKernelGGL((rows_sum_generic_kernel<T>), dim3(grid_cap((R * C + 255) / 256)), dim3(256), 0, s,
                        (const T*)gout, perm, row_ptr, weights, shift, grows, R, C);
-  return DVA_OK;
 }
 
 template <typename T>
-static int rows_grad_impl(const void* gout, const float* att, const float* gate, const int32_t* vp,
+static void rows_grad_impl(const void* gout, const float* att, const float* gate, const int32_t* vp,
                           const int32_t* perm, const int32_t* row_ptr, const float* rec, int rs,
                           float* grows, int64_t R, int C, int G, hipStream_t s) {
-  constexpr int VEC = Vec16<T>::N;
+  constexpr int VEC = Chunk16<T>::N;
   const int lpr = C / VEC;
   const bool team_ok = (C % VEC) == 0 && is_pow2(lpr) && lpr <= 64 && is_pow2(G) && C % G == 0 &&
-                       (C / G) % VEC == 0 && ((uintptr_t)gout % 16 == 0) && ((uintptr_t)grows % 16 == 0);
+                       (C / G) % VEC == 0 && aligned16(gout) && aligned16(grows);
   if (team_ok) {
     hipLaunchKernelGGL((rows_grad_team_kernel<T>), dim3(grid_cap((R + 3) / 4)), dim3(256), 0, s,
                        (const T*)gout, att, gate, vp, perm, row_ptr, rec, rs, grows, R, C, G, lpr, lpr / G);
@@ -1422,7 +1379,6 @@ static int rows_grad_impl(const void* gout, const float* att, const float* gate,
     hipLaunchKernelGGL((rows_grad_generic_kernel<T>), dim3(grid_cap((R * C + 255) / 256)), dim3(256),
                        0, s, (const T*)gout, att, gate, vp, perm, row_ptr, rec, rs, grows, R, C, G);
   }
-  return DVA_OK;
 }
 
 }  // namespace dva
@@ -1471,18 +1427,13 @@ static int attention_fwd_entry(const void* val, const int32_t* row_idx, const fl
   if (!out || !att || !gate || !amax) return DVA_ERR_INVALID;
   if (algo < 0 || algo > 2) return DVA_ERR_INVALID;
   if (n_points == 0) return DVA_OK;
-  int rc;
-  if (dtype == DVA_F32)
-    rc = fwd_impl<float>(val, row_idx, compat, ptr, gate_w, gate_b, out, att, gate, amax, n_points,
-                         n_views, C, G, scaling, eps, algo, (hipStream_t)stream);
-  else if (dtype == DVA_BF16)
-    rc = fwd_impl<bf16_t>(val, row_idx, compat, ptr, gate_w, gate_b, out, att, gate, amax, n_points,
-                          n_views, C, G, scaling, eps, algo, (hipStream_t)stream);
-  else if (dtype == DVA_F16)
-    rc = fwd_impl<f16_t>(val, row_idx, compat, ptr, gate_w, gate_b, out, att, gate, amax, n_points,
-                          n_views, C, G, scaling, eps, algo, (hipStream_t)stream);
-  else
-    return DVA_ERR_INVALID;
+  int rc = DVA_OK;
+  const bool known = with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    rc = fwd_impl<T>(val, row_idx, compat, ptr, gate_w, gate_b, out, att, gate, amax, n_points, n_views, C, G, scaling,
+                     eps, algo, (hipStream_t)stream);
+  });
+  if (!known) return DVA_ERR_INVALID;
   if (rc) return rc;
   DVA_CHECK_LAUNCH();
   return DVA_OK;
@@ -1503,21 +1454,13 @@ static int attention_bwd_entry(const void* grad_out, const void* val, const int3
   if (gate_w && !grad_gate_wb) return DVA_ERR_INVALID;
   if (algo < 0 || algo > 2) return DVA_ERR_INVALID;
   if (n_points == 0) return DVA_OK;
-  int rc;
-  if (dtype == DVA_F32)
-    rc = bwd_impl<float>(grad_out, val, row_idx, grad_rows, compat, att, gate, amax, ptr, gate_w,
-                         grad_val, grad_compat, grad_gate_wb, view_rec, rec_stride, n_points, n_views, C, G,
-                         scaling, algo, (hipStream_t)stream);
-  else if (dtype == DVA_BF16)
-    rc = bwd_impl<bf16_t>(grad_out, val, row_idx, grad_rows, compat, att, gate, amax, ptr, gate_w,
-                          grad_val, grad_compat, grad_gate_wb, view_rec, rec_stride, n_points, n_views, C, G,
-                          scaling, algo, (hipStream_t)stream);
-  else if (dtype == DVA_F16)
-    rc = bwd_impl<f16_t>(grad_out, val, row_idx, grad_rows, compat, att, gate, amax, ptr, gate_w,
-                          grad_val, grad_compat, grad_gate_wb, view_rec, rec_stride, n_points, n_views, C, G,
-                          scaling, algo, (hipStream_t)stream);
-  else
-    return DVA_ERR_INVALID;
+  int rc = DVA_OK;
+  const bool known = with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    rc = bwd_impl<T>(grad_out, val, row_idx, grad_rows, compat, att, gate, amax, ptr, gate_w, grad_val, grad_compat,
+                     grad_gate_wb, view_rec, rec_stride, n_points, n_views, C, G, scaling, algo, (hipStream_t)stream);
+  });
+  if (!known) return DVA_ERR_INVALID;
   if (rc) return rc;
   DVA_CHECK_LAUNCH();
   return DVA_OK;
@@ -1571,11 +1514,11 @@ int dva_view_attention_geometry(int32_t C, int32_t G, int64_t n_points, int64_t 
                                 int32_t* rows) {
   if (C <= 0 || G <= 0 || G > C || n_points < 0 || n_views < 0 || !lpr || !rows) return DVA_ERR_INVALID;
   TeamGeom tg = {0, 0, 0, 0};
-  bool team;
-  if (dtype == DVA_F32) team = team_geometry<float>(C, G, n_points, n_views, &tg);
-  else if (dtype == DVA_BF16) team = team_geometry<bf16_t>(C, G, n_points, n_views, &tg);
-  else if (dtype == DVA_F16) team = team_geometry<f16_t>(C, G, n_points, n_views, &tg);
-  else return DVA_ERR_INVALID;
+  bool team = false;
+  const bool known = with_dtype(dtype, [&](auto tag) {
+    team = team_geometry<typename decltype(tag)::T>(C, G, n_points, n_views, &tg);
+  });
+  if (!known) return DVA_ERR_INVALID;
   *lpr = team ? tg.lpr : 0;
   *rows = team ? tg.rows : 0;
   return team ? 1 : 0;
@@ -1585,23 +1528,22 @@ int dva_view_gather_rows_grad_rec16_to(const void* grad_out, const int32_t* perm
                                        const void* view_rec16, void* grad_rows, int32_t out_dtype, int64_t n_rows,
                                        int64_t n_views, int32_t C, int32_t G, int32_t dtype, void* stream) {
   if (n_rows < 0 || n_views < 0 || C <= 0 || G <= 0 || G > 4 || (G & (G - 1))) return DVA_ERR_INVALID;
-  if (out_dtype != DVA_F32 && out_dtype != DVA_BF16 && out_dtype != DVA_F16) return DVA_ERR_INVALID;
+  if (!dtype_ok(out_dtype)) return DVA_ERR_INVALID;
   if (n_views > 0x7fffffffLL) return DVA_ERR_UNSUPPORTED;
   if (n_rows == 0) return DVA_OK;
   if (!row_ptr || !grad_rows) return DVA_ERR_INVALID;
   if (n_views > 0 && (!grad_out || !view_rec16)) return DVA_ERR_INVALID;     // perm NULL: records in plan order
   if ((dtype != DVA_BF16 && dtype != DVA_F16) || (out_dtype != DVA_F32 && out_dtype != dtype)) return DVA_ERR_UNSUPPORTED;
   const int lpr = C / 8;
-  if ((C % 8) || !is_pow2(lpr) || lpr > 64 || (C % G) || ((C / G) % 8) || ((uintptr_t)grad_out % 16) ||
-      ((uintptr_t)grad_rows % 16))
+  if ((C % 8) || !is_pow2(lpr) || lpr > 64 || (C % G) || ((C / G) % 8) || !aligned16(grad_out) || !aligned16(grad_rows))
     return DVA_ERR_UNSUPPORTED;
   const bool to_16 = out_dtype != DVA_F32;
-  if (dtype == DVA_F16)
-    rows_grad_rec16_launch<f16_t>(grad_out, perm, row_ptr, view_rec16, grad_rows, to_16, n_rows, n_views, C, G,
-                                  (hipStream_t)stream);
-  else
-    rows_grad_rec16_launch<bf16_t>(grad_out, perm, row_ptr, view_rec16, grad_rows, to_16, n_rows, n_views, C, G,
-                                   (hipStream_t)stream);
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    if constexpr (sizeof(T) == 2)      // the records go with 2-byte rows: fp32 was answered above
+      rows_grad_rec16_launch<T>(grad_out, perm, row_ptr, view_rec16, grad_rows, to_16, n_rows, n_views, C, G,
+                                (hipStream_t)stream);
+  });
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -1618,19 +1560,12 @@ int dva_view_gather_rows_grad(const void* grad_out, const float* att, const floa
   if (view_rec && rec_stride < G + 1) return DVA_ERR_INVALID;
   if (n_views > 0 && (!grad_out || !perm)) return DVA_ERR_INVALID;
   if (n_views > 0 && !view_rec && (!att || !view_point)) return DVA_ERR_INVALID;
-  int rc;
-  if (dtype == DVA_F32)
-    rc = rows_grad_impl<float>(grad_out, att, gate, view_point, perm, row_ptr, view_rec, rec_stride,
-                               grad_rows, n_rows, C, G, (hipStream_t)stream);
-  else if (dtype == DVA_BF16)
-    rc = rows_grad_impl<bf16_t>(grad_out, att, gate, view_point, perm, row_ptr, view_rec, rec_stride,
-                                grad_rows, n_rows, C, G, (hipStream_t)stream);
-  else if (dtype == DVA_F16)
-    rc = rows_grad_impl<f16_t>(grad_out, att, gate, view_point, perm, row_ptr, view_rec, rec_stride,
-                                grad_rows, n_rows, C, G, (hipStream_t)stream);
-  else
-    return DVA_ERR_INVALID;
-  if (rc) return rc;
+  const bool known = with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    rows_grad_impl<T>(grad_out, att, gate, view_point, perm, row_ptr, view_rec, rec_stride, grad_rows, n_rows, C, G,
+                      (hipStream_t)stream);
+  });
+  if (!known) return DVA_ERR_INVALID;
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -1642,23 +1577,22 @@ int dva_anchor_rows_sum(const void* grad_out, const int32_t* perm, const int32_t
   if (n_anchors == 0) return DVA_OK;
   if (!row_ptr || !S || (n_views > 0 && (!grad_out || !perm || !weights))) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == DVA_BF16) {
-    const int lpr = C / 8;
-    if ((C % 8) || !is_pow2(lpr) || lpr > 64 || ((uintptr_t)grad_out % 16) || ((uintptr_t)S % 16)) return DVA_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((anchor_rows_sum_kernel<bf16_t, 0>), dim3(grid_cap((n_anchors + 3) / 4)), dim3(256), 0, s,
-                       (const bf16_t*)grad_out, perm, row_ptr, (const float4*)weights, S, n_anchors, (int)C, lpr,
-                       (const bf16_t*)nullptr, (const float*)nullptr, (const float*)nullptr, (const int4*)nullptr,
-                       (const bf16_t*)nullptr);
-  } else if (dtype == DVA_F32) {
-    const int lpr = C / 4;
-    if ((C % 4) || !is_pow2(lpr) || lpr > 64 || ((uintptr_t)grad_out % 16) || ((uintptr_t)S % 16)) return DVA_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((anchor_rows_sum_kernel<float, 0>), dim3(grid_cap((n_anchors + 3) / 4)), dim3(256), 0, s,
-                       (const float*)grad_out, perm, row_ptr, (const float4*)weights, S, n_anchors, (int)C, lpr,
-                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const int4*)nullptr,
-                       (const float*)nullptr);
-  } else {
-    return DVA_ERR_INVALID;
-  }
+  int rc = DVA_OK;
+  const bool known = with_f32_bf16(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    constexpr int VEC = Chunk16<T>::N;
+    const int lpr = C / VEC;
+    if ((C % VEC) || !is_pow2(lpr) || lpr > 64 || !aligned16(grad_out) || !aligned16(S)) {
+      rc = DVA_ERR_UNSUPPORTED;
+      return;
+    }
+    hipLaunchKernelGGL((anchor_rows_sum_kernel<T, 0>), dim3(grid_cap((n_anchors + 3) / 4)), dim3(256), 0, s,
+                       (const T*)grad_out, perm, row_ptr, (const float4*)weights, S, n_anchors, (int)C, lpr,
+                       (const T*)nullptr, (const float*)nullptr, (const float*)nullptr, (const int4*)nullptr,
+                       (const T*)nullptr);
+  });
+  if (!known) return DVA_ERR_INVALID;
+  if (rc) return rc;
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -1671,8 +1605,8 @@ int dva_anchor_rows_sum_bn(const void* dy_a, const void* z_a, const float* bn_a,
   if (!row_ptr || !S || !bn_a || !sm_a || (n_views > 0 && (!dy_a || !perm || !weights))) return DVA_ERR_INVALID;
   if ((z_a == nullptr) == (Y == nullptr) || (Y && !tap_rows)) return DVA_ERR_INVALID;      // exactly one of the two forms
   const int lpr = C / 8;
-  if ((C % 32) || C > 512 || !is_pow2(lpr) || lpr > 64 || ((uintptr_t)dy_a % 16) || ((uintptr_t)z_a % 16) || ((uintptr_t)Y % 16) ||
-      ((uintptr_t)S % 16) || ((uintptr_t)tap_rows % 16))
+  if ((C % 32) || C > 512 || !is_pow2(lpr) || lpr > 64 || !aligned16(dy_a) || !aligned16(z_a) || !aligned16(Y) ||
+      !aligned16(S) || !aligned16(tap_rows))
     return DVA_ERR_UNSUPPORTED;
   const dim3 grid(grid_cap((n_anchors + 3) / 4)), block(256);
   if (Y)
@@ -1695,16 +1629,11 @@ int dva_gather_rows_sum(const void* grad_out, const int32_t* perm, const int32_t
   if (n_rows == 0) return DVA_OK;
   if (!row_ptr || !grad_rows) return DVA_ERR_INVALID;
   if (n_atoms > 0 && (!grad_out || !perm)) return DVA_ERR_INVALID;
-  int rc;
-  if (dtype == DVA_F32)
-    rc = rows_sum_impl<float>(grad_out, perm, row_ptr, weights, atom_shift, grad_rows, n_rows, C, (hipStream_t)stream);
-  else if (dtype == DVA_BF16)
-    rc = rows_sum_impl<bf16_t>(grad_out, perm, row_ptr, weights, atom_shift, grad_rows, n_rows, C, (hipStream_t)stream);
-  else if (dtype == DVA_F16)
-    rc = rows_sum_impl<f16_t>(grad_out, perm, row_ptr, weights, atom_shift, grad_rows, n_rows, C, (hipStream_t)stream);
-  else
-    return DVA_ERR_INVALID;
-  if (rc) return rc;
+  const bool known = with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    rows_sum_impl<T>(grad_out, perm, row_ptr, weights, atom_shift, grad_rows, n_rows, C, (hipStream_t)stream);
+  });
+  if (!known) return DVA_ERR_INVALID;
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }

@@ -74,28 +74,6 @@ __device__ __forceinline__ float dot_row(const float* __restrict__ row, const fl
 // One half-wave per point: every lane reads 16 bytes (VEC channels) of a row, 32/LPR rows are in flight
 // per half-wave and four row loads per lane are issued before the first is used; the row slots are then
 // merged with xor-shuffles (value, row) -- larger value wins, smaller row on ties.
-template <typename AT>
-struct SegVec;
-template <>
-struct SegVec<float> {
-  static constexpr int VEC = 4;
-  typedef float4 raw;
-  static __device__ __forceinline__ void unpack(const raw& r, float* f) { f[0] = r.x; f[1] = r.y; f[2] = r.z; f[3] = r.w; }
-};
-template <>
-struct SegVec<bf16_t> {
-  static constexpr int VEC = 8;
-  typedef uint4 raw;
-  static __device__ __forceinline__ void unpack(const raw& r, float* f) {
-    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      f[2 * e] = __uint_as_float(w[e] << 16);
-      f[2 * e + 1] = __uint_as_float(w[e] & 0xffff0000u);
-    }
-  }
-};
-
 // LPP lanes per point (32, 16 or 8; at least LPR): the host picks it from the average segment length so that
 // short ragged segments (a handful of views per point) do not leave most row slots idle.
 template <typename AT, int LPP>
@@ -104,9 +82,9 @@ __global__ __launch_bounds__(256) void dsf_segmax_kernel(const AT* __restrict__ 
                                                           const int64_t* __restrict__ ptr,
                                                           float* __restrict__ pooled,
                                                           int32_t* __restrict__ arg, int64_t N) {
-  constexpr int VEC = SegVec<AT>::VEC, LPR = D / VEC, SLOTS = LPP / LPR, U = 4, PPW = 64 / LPP;
+  constexpr int VEC = Chunk16<AT>::N, LPR = D / VEC, SLOTS = LPP / LPR, U = 4, PPW = 64 / LPP;
   static_assert(LPP >= LPR && SLOTS >= 1, "a point needs at least one row of lanes");
-  typedef typename SegVec<AT>::raw raw_t;
+  typedef typename Chunk16<AT>::raw raw_t;
   const int lane = threadIdx.x & 63, hl = lane & (LPP - 1), h = lane / LPP;
   const int cl = hl % LPR, slot = hl / LPR, c0 = cl * VEC;
   BNc b[VEC];
@@ -144,7 +122,7 @@ __global__ __launch_bounds__(256) void dsf_segmax_kernel(const AT* __restrict__ 
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         float f[VEC];
-        SegVec<AT>::unpack(raw[u], f);
+        Chunk16<AT>::unpack(raw[u], f);
         const int i = i0 + u * SLOTS + slot;
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {

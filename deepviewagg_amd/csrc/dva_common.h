@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/dva.h"
 
 #define DVA_WAVE 64
@@ -76,6 +78,22 @@ __device__ __forceinline__ uint4 pack_h8(const float* f) {
                     Pair16<T>::pack(f[6], f[7]));
 }
 
+// The 16 bytes of N consecutive elements of a row, as one load / store, <-> fp32
+template <typename T>
+struct Chunk16 {
+  static constexpr int N = 8;
+  typedef uint4 raw;
+  static __device__ __forceinline__ void unpack(const raw& r, float* f) { unpack_h8<T>(r, f); }
+  static __device__ __forceinline__ raw pack(const float* f) { return pack_h8<T>(f); }
+};
+template <>
+struct Chunk16<float> {
+  static constexpr int N = 4;
+  typedef float4 raw;
+  static __device__ __forceinline__ void unpack(const raw& r, float* f) { f[0] = r.x; f[1] = r.y; f[2] = r.z; f[3] = r.w; }
+  static __device__ __forceinline__ raw pack(const float* f) { return make_float4(f[0], f[1], f[2], f[3]); }
+};
+
 template <typename T>
 struct Elt;
 template <>
@@ -141,6 +159,41 @@ static inline int capped_grid(int64_t n, int64_t per_block, int64_t cap) {
   if (b > cap) b = cap;
   if (b < 1) b = 1;
   return (int)b;
+}
+
+constexpr int64_t GRID_CAP = 256 * 32;  // 256 CUs x 32 blocks, grid-stride beyond
+
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+static inline bool dtype_ok(int dtype) { return dtype == DVA_F32 || dtype == DVA_BF16 || dtype == DVA_F16; }
+
+// f(DType<T>) for the run-time storage code; false, and f not called, for any other code.  with_f32_bf16 is for the
+// entries that have no fp16 kernels: they answer DVA_F16 with DVA_ERR_UNSUPPORTED before they get here.
+template <typename T_>
+struct DType {
+  using T = T_;
+};
+template <typename F>
+static inline bool with_f32_bf16(int dtype, F&& f) {
+  if (dtype == DVA_F32) f(DType<float>{});
+  else if (dtype == DVA_BF16) f(DType<bf16_t>{});
+  else return false;
+  return true;
+}
+template <typename F>
+static inline bool with_dtype(int dtype, F&& f) {
+  if (dtype != DVA_F16) return with_f32_bf16(dtype, f);
+  f(DType<f16_t>{});
+  return true;
+}
+
+// f(std::integral_constant<int, REDUCE>) for the run-time reduce (DVA_SUM .. DVA_MIN, checked by the caller)
+template <typename F>
+static inline void with_reduce(int reduce, F&& f) {
+  if (reduce == DVA_SUM) f(std::integral_constant<int, DVA_SUM>{});
+  else if (reduce == DVA_MEAN) f(std::integral_constant<int, DVA_MEAN>{});
+  else if (reduce == DVA_MAX) f(std::integral_constant<int, DVA_MAX>{});
+  else f(std::integral_constant<int, DVA_MIN>{});
 }
 
 // Zero fill of `words` 32-bit words at a 4-byte-aligned address, as a kernel.  The entries that promise to be capturable

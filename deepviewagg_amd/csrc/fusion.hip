@@ -66,16 +66,12 @@ static int concat_cast(float* a, void* b, float* cat, int64_t N, int Ca, int Cb,
   if (N == 0 || Ca + Cb == 0) return DVA_OK;
   if ((Ca && !a) || (Cb && !b) || !cat) return DVA_ERR_INVALID;
   if (dtype == DVA_BF16 && ((uintptr_t)b & 7)) return DVA_ERR_UNSUPPORTED;     // 8-byte moves of the bf16 groups
-  const int64_t groups = N * ((Ca + Cb) >> 2);
-  int64_t blocks = (groups + 255) / 256;
-  if (blocks > 256 * 32) blocks = 256 * 32;
-  const dim3 block(256), grid((int)blocks);
-  if (dtype == DVA_F32)
-    hipLaunchKernelGGL((concat_cast_kernel<float, BWD>), grid, block, 0, s, a, (float*)b, cat, N, Ca, Cb);
-  else if (dtype == DVA_BF16)
-    hipLaunchKernelGGL((concat_cast_kernel<bf16_t, BWD>), grid, block, 0, s, a, (bf16_t*)b, cat, N, Ca, Cb);
-  else
-    return DVA_ERR_INVALID;
+  const dim3 block(256), grid(capped_grid(N * ((Ca + Cb) >> 2), 256, GRID_CAP));
+  const bool known = with_f32_bf16(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    hipLaunchKernelGGL((concat_cast_kernel<T, BWD>), grid, block, 0, s, a, (T*)b, cat, N, Ca, Cb);
+  });
+  if (!known) return DVA_ERR_INVALID;
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }

@@ -176,48 +176,11 @@ __global__ __launch_bounds__(256) void gather_bilinear_fwd_kernel(
 // operation order, no fma: bit-identical output).  The scalar kernel moved 2.8 TB/s at C = 256 (bf16): 2-byte loads,
 // a 64-bit division and the tap arithmetic per element.
 template <typename T>
-struct GVec;
-template <>
-struct GVec<float> {
-  static constexpr int N = 4;
-  typedef float4 raw;
-  static __device__ __forceinline__ void unpack(const raw& r, float* f) { f[0] = r.x; f[1] = r.y; f[2] = r.z; f[3] = r.w; }
-  static __device__ __forceinline__ raw pack(const float* f) { return make_float4(f[0], f[1], f[2], f[3]); }
-};
-template <>
-struct GVec<bf16_t> {
-  static constexpr int N = 8;
-  typedef uint4 raw;
-  static __device__ __forceinline__ void unpack(const raw& r, float* f) {
-    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      f[2 * i] = __uint_as_float(w[i] << 16);
-      f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-  }
-  static __device__ __forceinline__ raw pack(const float* f) {
-    uint4 r;
-    r.x = (uint32_t)f2bf(f[0]) | ((uint32_t)f2bf(f[1]) << 16);
-    r.y = (uint32_t)f2bf(f[2]) | ((uint32_t)f2bf(f[3]) << 16);
-    r.z = (uint32_t)f2bf(f[4]) | ((uint32_t)f2bf(f[5]) << 16);
-    r.w = (uint32_t)f2bf(f[6]) | ((uint32_t)f2bf(f[7]) << 16);
-    return r;
-  }
-};
-template <>
-struct GVec<f16_t> {
-  static constexpr int N = 8;
-  typedef uint4 raw;
-  static __device__ __forceinline__ void unpack(const raw& r, float* f) { unpack_h8<f16_t>(r, f); }
-  static __device__ __forceinline__ raw pack(const float* f) { return pack_h8<f16_t>(f); }
-};
-template <typename T>
 __global__ __launch_bounds__(256) void gather_bilinear_fwd_vec_kernel(
     const T* __restrict__ x, const PackedIdx* __restrict__ idx, const float* __restrict__ coords,
     T* __restrict__ out, int64_t n_atoms, int H, int W, int C, int lpr) {
-  constexpr int VEC = GVec<T>::N;
-  typedef typename GVec<T>::raw raw_t;
+  constexpr int VEC = Chunk16<T>::N;
+  typedef typename Chunk16<T>::raw raw_t;
   const int lane = threadIdx.x & 63, lane_r = lane & (lpr - 1), slot = lane / lpr, slots = 64 / lpr;
   const int64_t col = (int64_t)lane_r * VEC;
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -231,10 +194,10 @@ __global__ __launch_bounds__(256) void gather_bilinear_fwd_vec_kernel(
     const raw_t r2 = *reinterpret_cast<const raw_t*>(x + tp.bl * C + col);
     const raw_t r3 = *reinterpret_cast<const raw_t*>(x + tp.br * C + col);
     float a[VEC], b[VEC], c[VEC], d[VEC], o[VEC];
-    GVec<T>::unpack(r0, a);
-    GVec<T>::unpack(r1, b);
-    GVec<T>::unpack(r2, c);
-    GVec<T>::unpack(r3, d);
+    Chunk16<T>::unpack(r0, a);
+    Chunk16<T>::unpack(r1, b);
+    Chunk16<T>::unpack(r2, c);
+    Chunk16<T>::unpack(r3, d);
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
       float acc = __fmul_rn(tp.w_tl, a[e]);
@@ -242,7 +205,7 @@ __global__ __launch_bounds__(256) void gather_bilinear_fwd_vec_kernel(
       acc = __fadd_rn(acc, __fmul_rn(tp.w_bl, c[e]));
       o[e] = __fadd_rn(acc, __fmul_rn(tp.w_br, d[e]));
     }
-    *reinterpret_cast<raw_t*>(out + p * C + col) = GVec<T>::pack(o);
+    *reinterpret_cast<raw_t*>(out + p * C + col) = Chunk16<T>::pack(o);
   }
 }
 
@@ -386,7 +349,7 @@ int dva_pack_gather_index(const int64_t* images, const int64_t* atom_ptr, const 
   if (n_views < 0 || n_atoms < 0 || !(ratio >= 1.0)) return DVA_ERR_INVALID;
   if (n_views == 0 || n_atoms == 0) return DVA_OK;
   if (!images || !atom_ptr || !pixels || !packed_idx) return DVA_ERR_INVALID;
-  const int grid = capped_grid(n_views, 256, 256 * 32);
+  const int grid = capped_grid(n_views, 256, GRID_CAP);
   hipStream_t s = (hipStream_t)stream;
   PackedIdx* out = (PackedIdx*)packed_idx;
   switch (pix_bytes) {
@@ -416,7 +379,7 @@ int dva_mapping_row_index(const int64_t* images, const int64_t* atom_ptr, const 
   if ((int64_t)B * H * W > 0x7fffffffLL || H > 32767 || W > 32767) return DVA_ERR_UNSUPPORTED;
   if (n_views == 0 || n_atoms == 0) return DVA_OK;
   if (!images || !atom_ptr || !pixels || !row_idx) return DVA_ERR_INVALID;
-  const int grid = capped_grid(n_views, 256, 256 * 32);
+  const int grid = capped_grid(n_views, 256, GRID_CAP);
   hipStream_t s = (hipStream_t)stream;
   switch (pix_bytes) {
     case 2:
@@ -444,7 +407,7 @@ int dva_gather_row_index(const void* packed_idx, int64_t n_atoms, int32_t B, int
   if ((int64_t)B * H * W + row_offset > 0x7fffffffLL) return DVA_ERR_UNSUPPORTED;
   if (n_atoms == 0) return DVA_OK;
   if (!packed_idx || !row_idx) return DVA_ERR_INVALID;
-  hipLaunchKernelGGL(row_index_kernel, dim3(capped_grid(n_atoms, 256, 256 * 32)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(row_index_kernel, dim3(capped_grid(n_atoms, 256, GRID_CAP)), dim3(256), 0, (hipStream_t)stream,
                      (const PackedIdx*)packed_idx, n_atoms, H, W, row_offset, row_idx, counts);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
@@ -452,7 +415,7 @@ int dva_gather_row_index(const void* packed_idx, int64_t n_atoms, int32_t B, int
 
 static int check_map(int64_t n_atoms, int B, int H, int W, int C, int dtype) {
   if (n_atoms < 0 || B < 0 || H < 0 || W < 0 || C < 0) return DVA_ERR_INVALID;
-  if (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16) return DVA_ERR_INVALID;
+  if (!dtype_ok(dtype)) return DVA_ERR_INVALID;
   if (H > 32767 || W > 32767) return DVA_ERR_UNSUPPORTED;
   return DVA_OK;
 }
@@ -466,18 +429,17 @@ int dva_gather_nearest_fwd(const void* x, const void* packed_idx, void* out, int
   const int64_t row_bytes = (int64_t)C * (dtype == DVA_F32 ? 4 : 2);
   hipStream_t s = (hipStream_t)stream;
   const PackedIdx* idx = (const PackedIdx*)packed_idx;
-  const bool al16 = ((uintptr_t)x % 16 == 0) && ((uintptr_t)out % 16 == 0);
-  if (row_bytes % 16 == 0 && al16) {
+  if (row_bytes % 16 == 0 && aligned16(x) && aligned16(out)) {
     const int u = (int)(row_bytes / 16);
-    hipLaunchKernelGGL((gather_nearest_fwd_kernel<uint4>), dim3(capped_grid(n_atoms * u, 256, 256 * 32)), dim3(256), 0,
+    hipLaunchKernelGGL((gather_nearest_fwd_kernel<uint4>), dim3(capped_grid(n_atoms * u, 256, GRID_CAP)), dim3(256), 0,
                        s, (const uint4*)x, idx, (uint4*)out, n_atoms, H, W, u);
   } else if (row_bytes % 4 == 0) {
     const int u = (int)(row_bytes / 4);
-    hipLaunchKernelGGL((gather_nearest_fwd_kernel<uint32_t>), dim3(capped_grid(n_atoms * u, 256, 256 * 32)), dim3(256),
+    hipLaunchKernelGGL((gather_nearest_fwd_kernel<uint32_t>), dim3(capped_grid(n_atoms * u, 256, GRID_CAP)), dim3(256),
                        0, s, (const uint32_t*)x, idx, (uint32_t*)out, n_atoms, H, W, u);
   } else {
     const int u = (int)(row_bytes / 2);
-    hipLaunchKernelGGL((gather_nearest_fwd_kernel<uint16_t>), dim3(capped_grid(n_atoms * u, 256, 256 * 32)), dim3(256),
+    hipLaunchKernelGGL((gather_nearest_fwd_kernel<uint16_t>), dim3(capped_grid(n_atoms * u, 256, GRID_CAP)), dim3(256),
                        0, s, (const uint16_t*)x, idx, (uint16_t*)out, n_atoms, H, W, u);
   }
   DVA_CHECK_LAUNCH();
@@ -493,16 +455,13 @@ int dva_gather_nearest_bwd(const void* grad_out, const void* packed_idx, float* 
   if (!grad_out || !packed_idx || !grad_x) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   const PackedIdx* idx = (const PackedIdx*)packed_idx;
-  const int grid = capped_grid(n_atoms * (int64_t)C, 256, 256 * 32);
-  if (dtype == DVA_F32)
-    hipLaunchKernelGGL((gather_nearest_bwd_kernel<float>), dim3(grid), dim3(256), 0, s,
-                       (const float*)grad_out, idx, grad_x, n_atoms, H, W, C);
-  else if (dtype == DVA_F16)
-    hipLaunchKernelGGL((gather_nearest_bwd_kernel<f16_t>), dim3(grid), dim3(256), 0, s,
-                       (const f16_t*)grad_out, idx, grad_x, n_atoms, H, W, C);
-  else
-    hipLaunchKernelGGL((gather_nearest_bwd_kernel<bf16_t>), dim3(grid), dim3(256), 0, s,
-                       (const bf16_t*)grad_out, idx, grad_x, n_atoms, H, W, C);
+  const int grid = capped_grid(n_atoms * (int64_t)C, 256, GRID_CAP);
+  const bool known = with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    hipLaunchKernelGGL((gather_nearest_bwd_kernel<T>), dim3(grid), dim3(256), 0, s, (const T*)grad_out, idx, grad_x,
+                       n_atoms, H, W, C);
+  });
+  if (!known) return DVA_ERR_INVALID;
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -516,34 +475,22 @@ int dva_gather_bilinear_fwd(const void* x, const void* packed_idx, const float* 
   if (!x || !packed_idx || !coords || !out) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   const PackedIdx* idx = (const PackedIdx*)packed_idx;
-  const int vec = dtype == DVA_F32 ? 4 : 8, lpr = C / vec;
-  const bool vec_ok = (C % vec) == 0 && lpr >= 1 && lpr <= 64 && (lpr & (lpr - 1)) == 0 &&
-                      ((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0;
-  if (vec_ok) {
-    const int slots = 64 / lpr;
-    const int gridv = capped_grid(((n_atoms + slots - 1) / slots) * 64, 256, 256 * 32);
-    if (dtype == DVA_F32)
-      hipLaunchKernelGGL((gather_bilinear_fwd_vec_kernel<float>), dim3(gridv), dim3(256), 0, s, (const float*)x, idx,
-                         coords, (float*)out, n_atoms, H, W, C, lpr);
-    else if (dtype == DVA_F16)
-      hipLaunchKernelGGL((gather_bilinear_fwd_vec_kernel<f16_t>), dim3(gridv), dim3(256), 0, s, (const f16_t*)x, idx,
-                         coords, (f16_t*)out, n_atoms, H, W, C, lpr);
-    else
-      hipLaunchKernelGGL((gather_bilinear_fwd_vec_kernel<bf16_t>), dim3(gridv), dim3(256), 0, s, (const bf16_t*)x, idx,
-                         coords, (bf16_t*)out, n_atoms, H, W, C, lpr);
-    DVA_CHECK_LAUNCH();
-    return DVA_OK;
-  }
-  const int grid = capped_grid(n_atoms * (int64_t)C, 256, 256 * 32);
-  if (dtype == DVA_F32)
-    hipLaunchKernelGGL((gather_bilinear_fwd_kernel<float>), dim3(grid), dim3(256), 0, s,
-                       (const float*)x, idx, coords, (float*)out, n_atoms, H, W, C);
-  else if (dtype == DVA_F16)
-    hipLaunchKernelGGL((gather_bilinear_fwd_kernel<f16_t>), dim3(grid), dim3(256), 0, s,
-                       (const f16_t*)x, idx, coords, (f16_t*)out, n_atoms, H, W, C);
-  else
-    hipLaunchKernelGGL((gather_bilinear_fwd_kernel<bf16_t>), dim3(grid), dim3(256), 0, s,
-                       (const bf16_t*)x, idx, coords, (bf16_t*)out, n_atoms, H, W, C);
+  const bool known = with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    constexpr int vec = Chunk16<T>::N;
+    const int lpr = C / vec;
+    if ((C % vec) == 0 && lpr >= 1 && lpr <= 64 && (lpr & (lpr - 1)) == 0 && aligned16(x) && aligned16(out)) {
+      const int slots = 64 / lpr;
+      const int gridv = capped_grid(((n_atoms + slots - 1) / slots) * 64, 256, GRID_CAP);
+      hipLaunchKernelGGL((gather_bilinear_fwd_vec_kernel<T>), dim3(gridv), dim3(256), 0, s, (const T*)x, idx, coords,
+                         (T*)out, n_atoms, H, W, C, lpr);
+    } else {
+      const int grid = capped_grid(n_atoms * (int64_t)C, 256, GRID_CAP);
+      hipLaunchKernelGGL((gather_bilinear_fwd_kernel<T>), dim3(grid), dim3(256), 0, s, (const T*)x, idx, coords,
+                         (T*)out, n_atoms, H, W, C);
+    }
+  });
+  if (!known) return DVA_ERR_INVALID;
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -557,16 +504,13 @@ int dva_gather_bilinear_bwd(const void* grad_out, const void* packed_idx, const 
   if (!grad_out || !packed_idx || !coords || !grad_x) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   const PackedIdx* idx = (const PackedIdx*)packed_idx;
-  const int grid = capped_grid(n_atoms * (int64_t)C, 256, 256 * 32);
-  if (dtype == DVA_F32)
-    hipLaunchKernelGGL((gather_bilinear_bwd_kernel<float>), dim3(grid), dim3(256), 0, s,
-                       (const float*)grad_out, idx, coords, grad_x, n_atoms, H, W, C);
-  else if (dtype == DVA_F16)
-    hipLaunchKernelGGL((gather_bilinear_bwd_kernel<f16_t>), dim3(grid), dim3(256), 0, s,
-                       (const f16_t*)grad_out, idx, coords, grad_x, n_atoms, H, W, C);
-  else
-    hipLaunchKernelGGL((gather_bilinear_bwd_kernel<bf16_t>), dim3(grid), dim3(256), 0, s,
-                       (const bf16_t*)grad_out, idx, coords, grad_x, n_atoms, H, W, C);
+  const int grid = capped_grid(n_atoms * (int64_t)C, 256, GRID_CAP);
+  const bool known = with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    hipLaunchKernelGGL((gather_bilinear_bwd_kernel<T>), dim3(grid), dim3(256), 0, s, (const T*)grad_out, idx, coords,
+                       grad_x, n_atoms, H, W, C);
+  });
+  if (!known) return DVA_ERR_INVALID;
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -583,7 +527,7 @@ int dva_gather_bilinear_taps_anchor(const void* packed_idx, const float* coords,
   if ((int64_t)B * (H + 1) * (W + 1) >= 0x7fffffffLL || n_atoms > 0x1fffffffLL) return DVA_ERR_UNSUPPORTED;
   if (n_atoms == 0) return DVA_OK;
   if (!packed_idx || !coords || !rows || !weights) return DVA_ERR_INVALID;
-  hipLaunchKernelGGL(bilinear_taps_kernel, dim3(capped_grid(n_atoms, 256, 256 * 32)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(bilinear_taps_kernel, dim3(capped_grid(n_atoms, 256, GRID_CAP)), dim3(256), 0, (hipStream_t)stream,
                      (const PackedIdx*)packed_idx, coords, n_atoms, H, W, rows, weights, anchors,
                      (int32_t)((int64_t)B * (H + 1) * (W + 1)));
   DVA_CHECK_LAUNCH();
@@ -618,7 +562,7 @@ int dva_bilinear_taps_cat(int32_t n_settings, const void* const* tap_rows, const
   if (!rows_out || !weights_out || !anchors_out) return DVA_ERR_INVALID;
   a.n = n_settings;
   a.dummy = (int32_t)an;
-  hipLaunchKernelGGL(taps_cat_kernel, dim3(capped_grid(n_views_total, 256, 256 * 32)), dim3(256), 0,
+  hipLaunchKernelGGL(taps_cat_kernel, dim3(capped_grid(n_views_total, 256, GRID_CAP)), dim3(256), 0,
                      (hipStream_t)stream, a, order, n_views_total, (int4*)rows_out, (float4*)weights_out, anchors_out);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
@@ -628,7 +572,7 @@ int dva_anchor_combine(const float* S, float* grad_rows, int32_t B, int32_t H, i
   if (B < 0 || H <= 0 || W <= 0 || C <= 0 || (C % 4)) return DVA_ERR_INVALID;
   if (B == 0) return DVA_OK;
   if (!S || !grad_rows) return DVA_ERR_INVALID;
-  hipLaunchKernelGGL(anchor_combine_kernel, dim3(capped_grid((int64_t)B * H * W * (C / 4), 256, 256 * 32)), dim3(256),
+  hipLaunchKernelGGL(anchor_combine_kernel, dim3(capped_grid((int64_t)B * H * W * (C / 4), 256, GRID_CAP)), dim3(256),
                      0, (hipStream_t)stream, S, grad_rows, (int)B, (int)H, (int)W, (int)C);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
@@ -637,20 +581,19 @@ int dva_anchor_combine(const float* S, float* grad_rows, int32_t B, int32_t H, i
 int dva_anchor_fixup(const void* grad, const int32_t* rows, const float* weights, const int32_t* anchors,
                      float* grad_rows, int64_t n_atoms, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype,
                      void* stream) {
-  if (n_atoms < 0 || C <= 0 || (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16)) return DVA_ERR_INVALID;
+  if (n_atoms < 0 || C <= 0 || !dtype_ok(dtype)) return DVA_ERR_INVALID;
   if (dtype == DVA_F16) return DVA_ERR_UNSUPPORTED;
   if (n_atoms == 0) return DVA_OK;
   if (!grad || !rows || !weights || !anchors || !grad_rows) return DVA_ERR_INVALID;
   const int32_t dummy = (int32_t)((int64_t)B * (H + 1) * (W + 1));
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == DVA_F32)
-    hipLaunchKernelGGL((anchor_fixup_kernel<float>), dim3(capped_grid(n_atoms, 256, 256 * 32)), dim3(256), 0, s,
-                       (const float*)grad, rows, weights, anchors, dummy, grad_rows, n_atoms, (int)C,
-                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
-  else
-    hipLaunchKernelGGL((anchor_fixup_kernel<bf16_t>), dim3(capped_grid(n_atoms, 256, 256 * 32)), dim3(256), 0, s,
-                       (const bf16_t*)grad, rows, weights, anchors, dummy, grad_rows, n_atoms, (int)C,
-                       (const bf16_t*)nullptr, (const float*)nullptr, (const float*)nullptr);
+  const bool known = with_f32_bf16(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    hipLaunchKernelGGL((anchor_fixup_kernel<T>), dim3(capped_grid(n_atoms, 256, GRID_CAP)), dim3(256), 0, s,
+                       (const T*)grad, rows, weights, anchors, dummy, grad_rows, n_atoms, (int)C, (const T*)nullptr,
+                       (const float*)nullptr, (const float*)nullptr);
+  });
+  if (!known) return DVA_ERR_INVALID;
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -662,7 +605,7 @@ int dva_anchor_fixup_bn(const void* dy_a, const void* z_a, const float* bn_a, co
   if (n_atoms == 0) return DVA_OK;
   if (!dy_a || !z_a || !bn_a || !sm_a || !rows || !weights || !anchors || !grad_rows) return DVA_ERR_INVALID;
   const int32_t dummy = (int32_t)((int64_t)B * (H + 1) * (W + 1));
-  hipLaunchKernelGGL((anchor_fixup_kernel<bf16_t>), dim3(capped_grid(n_atoms, 256, 256 * 32)), dim3(256), 0,
+  hipLaunchKernelGGL((anchor_fixup_kernel<bf16_t>), dim3(capped_grid(n_atoms, 256, GRID_CAP)), dim3(256), 0,
                      (hipStream_t)stream, (const bf16_t*)dy_a, rows, weights, anchors, dummy, grad_rows, n_atoms,
                      (int)C, (const bf16_t*)z_a, bn_a, sm_a);
   DVA_CHECK_LAUNCH();

@@ -142,7 +142,7 @@ int dva_gather_segment_reduce_fwd(const void* rows, const int32_t* row_idx, cons
   with_row_type(dtype, wide, [&](auto row) {
     using T = typename decltype(row)::T;
     constexpr int VEC = decltype(row)::VEC;
-    const dim3 grid(capped_grid(S * (int64_t)(C / VEC), 256, POOL_GRID_CAP));
+    const dim3 grid(capped_grid(S * (int64_t)(C / VEC), 256, GRID_CAP));
     with_reduce(reduce, [&](auto rd) {
       hipLaunchKernelGGL((gather_segment_reduce_fwd_kernel<T, VEC, decltype(rd)::value>), grid, dim3(256), 0, s,
                          (const T*)rows, row_idx, seg_ptr, (T*)out, (uint16_t*)arg, S, (int)C);
@@ -166,7 +166,7 @@ int dva_gather_segment_reduce_bwd(const void* grad_out, const void* arg, const i
   if (!grad_rows || !row_ptr) return DVA_ERR_INVALID;     // S == 0: every row still gets its zeros
   hipStream_t s = (hipStream_t)stream;
   const bool wide = C % row_vec(dtype) == 0 && aligned16(grad_out) && aligned16(grad_rows) && aligned16(arg);
-  const dim3 grid(capped_grid(R, 4, POOL_GRID_CAP));      // four wavefronts, four map rows per block
+  const dim3 grid(capped_grid(R, 4, GRID_CAP));      // four wavefronts, four map rows per block
   with_row_type(dtype, wide, [&](auto row) {
     using T = typename decltype(row)::T;
     constexpr int VEC = decltype(row)::VEC;

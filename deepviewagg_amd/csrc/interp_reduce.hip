@@ -292,7 +292,7 @@ int dva_interp_segment_reduce_fwd(const void* rows, const int32_t* tap_rows, con
   // the taps are read as 16-byte records on both paths: [P, 4] tensors of 4-byte elements
   if (P > 0 && (!aligned16(tap_rows) || !aligned16(tap_weights))) return DVA_ERR_UNSUPPORTED;
   const bool wide = C % row_vec(dtype) == 0 && aligned16(rows) && aligned16(out) && aligned16(arg);
-  const dim3 grid(capped_grid(S, 4, POOL_GRID_CAP));      // four wavefronts, four segments per block
+  const dim3 grid(capped_grid(S, 4, GRID_CAP));      // four wavefronts, four segments per block
   with_row_type(dtype, wide, [&](auto row) {
     using T = typename decltype(row)::T;
     constexpr int VEC = decltype(row)::VEC;
@@ -321,7 +321,7 @@ int dva_interp_segment_reduce_bwd(const void* grad_out, const void* arg, const i
   if (!grad_rows || !row_ptr) return DVA_ERR_INVALID;     // S == 0: every row still gets its zeros
   hipStream_t s = (hipStream_t)stream;
   const bool wide = C % row_vec(dtype) == 0 && aligned16(grad_out) && aligned16(grad_rows) && aligned16(arg);
-  const dim3 grid(capped_grid(R, 4, POOL_GRID_CAP));      // four wavefronts, four map rows per block
+  const dim3 grid(capped_grid(R, 4, GRID_CAP));      // four wavefronts, four map rows per block
   with_row_type(dtype, wide, [&](auto row) {
     using T = typename decltype(row)::T;
     constexpr int VEC = decltype(row)::VEC;
@@ -351,7 +351,7 @@ int dva_interp_anchor_rows_sum(const void* grad_out, const void* arg, const int6
       !aligned16(tap_weights))
     return DVA_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(capped_grid(n_anchors, 4, POOL_GRID_CAP));
+  const dim3 grid(capped_grid(n_anchors, 4, GRID_CAP));
   auto launch = [&](auto row) {
     using T = typename decltype(row)::T;
     constexpr int VEC = decltype(row)::VEC;

@@ -207,7 +207,7 @@ int dva_nearest_seen(const float* pos, const uint8_t* seen, int64_t n, const flo
   if (x) {
     if (!last || K < 1 || x == filled) return DVA_ERR_INVALID;
     if (K > (1 << 20)) return DVA_ERR_UNSUPPORTED;
-    if (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16) return DVA_ERR_INVALID;
+    if (!dtype_ok(dtype)) return DVA_ERR_INVALID;
   }
   if (n > 0x3fffffffLL) return DVA_ERR_UNSUPPORTED;
   if (n == 0) return DVA_OK;
@@ -225,7 +225,7 @@ int dva_nearest_seen(const float* pos, const uint8_t* seen, int64_t n, const flo
   if (hipMemsetAsync(L.tkeys, 0xff, L.cap * 8, s) != hipSuccess) return DVA_ERR_LAUNCH;
   hipLaunchKernelGGL(ns_cells_kernel, dim3(capped_grid(n, 256, 8192)), dim3(256), 0, s, pos, L.keys_sorted, L.perm, n,
                      L.pts, L.tkeys, L.tvals, (uint32_t)(L.cap - 1));
-  const dim3 grid(capped_grid(n, NS_TPB, 256 * 32)), block(NS_TPB);
+  const dim3 grid(capped_grid(n, NS_TPB, GRID_CAP)), block(NS_TPB);
   const uint32_t mask = (uint32_t)(L.cap - 1);
   if (x && dtype == DVA_F32)
     hipLaunchKernelGGL(ns_query_kernel<uint32_t>, grid, block, 0, s, L.pts, L.keys_sorted, n, bbox, cell, L.tkeys,

@@ -2,8 +2,6 @@
 // and element accesses to VEC consecutive channels of one row, the pooling step and its gradient term, the argument checks
 // and the choice of a kernel instantiation from (dtype, wide) and reduce.  The two files differ where the gathers differ.
 #pragma once
-#include <type_traits>
-
 #include "dva_common.h"
 
 namespace dva {
@@ -13,19 +11,10 @@ namespace dva {
 template <typename T, int VEC>
 struct RowChunk {
   static __device__ __forceinline__ void ld(const T* p, float* f) {
-    const uint4 r = *reinterpret_cast<const uint4*>(p);
-    if constexpr (sizeof(T) == 4) {
-      f[0] = __uint_as_float(r.x); f[1] = __uint_as_float(r.y);
-      f[2 % VEC] = __uint_as_float(r.z); f[3 % VEC] = __uint_as_float(r.w);
-    } else {
-      unpack_h8<T>(r, f);
-    }
+    Chunk16<T>::unpack(*reinterpret_cast<const typename Chunk16<T>::raw*>(p), f);
   }
   static __device__ __forceinline__ void st(T* p, const float* f) {
-    if constexpr (sizeof(T) == 4)
-      *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2 % VEC], f[3 % VEC]);
-    else
-      *reinterpret_cast<uint4*>(p) = pack_h8<T>(f);
+    *reinterpret_cast<typename Chunk16<T>::raw*>(p) = Chunk16<T>::pack(f);
   }
   // the uint16 arg offsets of the same channels
   static __device__ __forceinline__ void ld_arg(const uint16_t* p, uint32_t* k) {
@@ -58,9 +47,6 @@ struct RowChunk<T, 1> {
   static __device__ __forceinline__ void st_arg(uint16_t* p, const uint32_t* k) { p[0] = (uint16_t)k[0]; }
 };
 
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-constexpr int64_t POOL_GRID_CAP = 256 * 32;      // 256 CUs x 32 blocks, grid-stride beyond
 constexpr int64_t POOL_SIZE_MAX = 0x7fffffffLL;  // int32 row / tap plan, int32 segment of item
 
 constexpr bool keeps_arg(int reduce) { return reduce == DVA_MAX || reduce == DVA_MIN; }
@@ -75,7 +61,7 @@ static inline int lanes_per_row(int chunks) {
 
 static inline int check_sizes(int64_t S, int64_t P, int64_t R, int C, int dtype, int reduce) {
   if (S < 0 || P < 0 || R < 0 || C < 0) return DVA_ERR_INVALID;
-  if (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16) return DVA_ERR_INVALID;
+  if (!dtype_ok(dtype)) return DVA_ERR_INVALID;
   if (reduce < DVA_SUM || reduce > DVA_MIN) return DVA_ERR_INVALID;
   return DVA_OK;
 }
@@ -104,15 +90,6 @@ __device__ __forceinline__ float pool_term(float g, float w, float count, uint32
   else return ak == koff ? w * g : 0.f;
 }
 
-// f(std::integral_constant<int, REDUCE>) for the run-time reduce (checked by check_sizes)
-template <typename F>
-static inline void with_reduce(int reduce, F&& f) {
-  if (reduce == DVA_SUM) f(std::integral_constant<int, DVA_SUM>{});
-  else if (reduce == DVA_MEAN) f(std::integral_constant<int, DVA_MEAN>{});
-  else if (reduce == DVA_MAX) f(std::integral_constant<int, DVA_MAX>{});
-  else f(std::integral_constant<int, DVA_MIN>{});
-}
-
 // f(RowType<T, VEC>) for the run-time dtype (checked by check_sizes): 16-byte chunks when wide, elements otherwise
 template <typename T_, int VEC_>
 struct RowType {
@@ -122,9 +99,10 @@ struct RowType {
 static inline int row_vec(int dtype) { return dtype == DVA_F32 ? 4 : 8; }
 template <typename F>
 static inline void with_row_type(int dtype, bool wide, F&& f) {
-  if (dtype == DVA_F32) wide ? f(RowType<float, 4>{}) : f(RowType<float, 1>{});
-  else if (dtype == DVA_F16) wide ? f(RowType<f16_t, 8>{}) : f(RowType<f16_t, 1>{});
-  else wide ? f(RowType<bf16_t, 8>{}) : f(RowType<bf16_t, 1>{});
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    wide ? f(RowType<T, Chunk16<T>::N>{}) : f(RowType<T, 1>{});
+  });
 }
 
 }  // namespace dva

@@ -13,8 +13,6 @@
 // Four row-streaming passes (statistics / apply, forward and backward): lanes over channels (coalesced
 // rows), fp64 sums per thread (the bf16 vector statistics: fp32 over four rows, then fp64), LDS per block, fp64
 // atomics per block.
-#include <type_traits>
-
 #include "dva_common.h"
 #include "rowbn_math.h"
 
@@ -116,36 +114,6 @@ __global__ __launch_bounds__(256) void rowbn_bwd_apply_kernel(
 // rows): a thread owns VEC consecutive channels, one load / store instruction per 16 bytes.  Used for the
 // V-sized calls (E_mod on materialised views), where the scalar kernels ran at 2-3 TB/s.
 // ------------------------------------------------------------------------------------------------
-template <typename T> struct RVec;
-template <> struct RVec<float> {
-  static constexpr int N = 4;
-  typedef float4 raw;
-  static __device__ __forceinline__ void unpack(const raw& r, float* f) { f[0] = r.x; f[1] = r.y; f[2] = r.z; f[3] = r.w; }
-  static __device__ __forceinline__ raw pack(const float* f) { return make_float4(f[0], f[1], f[2], f[3]); }
-};
-template <> struct RVec<bf16_t> {
-  static constexpr int N = 8;
-  typedef uint4 raw;
-  static __device__ __forceinline__ void unpack(const raw& r, float* f) {
-    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      f[2 * e] = __uint_as_float(w[e] << 16);
-      f[2 * e + 1] = __uint_as_float(w[e] & 0xffff0000u);
-    }
-  }
-  static __device__ __forceinline__ raw pack(const float* f) {
-    return make_uint4(pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]),
-                      pack_bf16x2(f[6], f[7]));
-  }
-};
-template <> struct RVec<f16_t> {
-  static constexpr int N = 8;
-  typedef uint4 raw;
-  static __device__ __forceinline__ void unpack(const raw& r, float* f) { unpack_h8<f16_t>(r, f); }
-  static __device__ __forceinline__ raw pack(const float* f) { return pack_h8<f16_t>(f); }
-};
-
 // MODE 0: forward statistics (w y | w y^2); MODE 1: backward statistics (dz | dz a)
 template <typename T, int MODE>
 __global__ __launch_bounds__(256) void rowbn_sums_vec_kernel(const T* __restrict__ y, const T* __restrict__ gout,
@@ -153,8 +121,8 @@ __global__ __launch_bounds__(256) void rowbn_sums_vec_kernel(const T* __restrict
                                                               const float* __restrict__ bn,
                                                               double* __restrict__ sums, int64_t R, int C,
                                                               float slope) {
-  constexpr int VEC = RVec<T>::N;
-  typedef typename RVec<T>::raw raw_t;
+  constexpr int VEC = Chunk16<T>::N;
+  typedef typename Chunk16<T>::raw raw_t;
   extern __shared__ double s_red[];
   for (int i = threadIdx.x; i < 2 * C; i += 256) s_red[i] = 0.0;
   __syncthreads();
@@ -197,7 +165,7 @@ __global__ __launch_bounds__(256) void rowbn_sums_vec_kernel(const T* __restrict
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       float v[VEC];
-      RVec<T>::unpack(yr[u], v);
+      Chunk16<T>::unpack(yr[u], v);
       if (EXACT) {
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
@@ -214,7 +182,7 @@ __global__ __launch_bounds__(256) void rowbn_sums_vec_kernel(const T* __restrict
         }
       } else {
         float g[VEC];
-        RVec<T>::unpack(gr[u], g);
+        Chunk16<T>::unpack(gr[u], g);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
           const float a = rowbn::norm(v[k], mu[k], is[k]);
@@ -269,8 +237,8 @@ __global__ __launch_bounds__(256) void rowbn_apply_vec_kernel(const T* __restric
                                                                const float* __restrict__ bn,
                                                                const float* __restrict__ sm, T* __restrict__ out,
                                                                int64_t R, int C, float slope) {
-  constexpr int VEC = RVec<T>::N;
-  typedef typename RVec<T>::raw raw_t;
+  constexpr int VEC = Chunk16<T>::N;
+  typedef typename Chunk16<T>::raw raw_t;
   // the grid stride is a multiple of C / VEC (a power of two <= 256): a thread keeps its channels, so the
   // per-channel constants are loaded once
   const int cpr = C / VEC, sh = __ffs(cpr) - 1, c0 = (threadIdx.x & (cpr - 1)) * VEC;
@@ -289,7 +257,7 @@ __global__ __launch_bounds__(256) void rowbn_apply_vec_kernel(const T* __restric
        t += (int64_t)gridDim.x * blockDim.x) {
     const int64_t r = t >> sh;
     float v[VEC], o[VEC];
-    RVec<T>::unpack(*reinterpret_cast<const raw_t*>(y + r * C + c0), v);
+    Chunk16<T>::unpack(*reinterpret_cast<const raw_t*>(y + r * C + c0), v);
     if (MODE == 0) {
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
@@ -298,7 +266,7 @@ __global__ __launch_bounds__(256) void rowbn_apply_vec_kernel(const T* __restric
       }
     } else {
       float g[VEC];
-      RVec<T>::unpack(*reinterpret_cast<const raw_t*>(gout + r * C + c0), g);
+      Chunk16<T>::unpack(*reinterpret_cast<const raw_t*>(gout + r * C + c0), g);
       const float w = counts ? (float)counts[r] : 1.f;
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
@@ -308,15 +276,28 @@ __global__ __launch_bounds__(256) void rowbn_apply_vec_kernel(const T* __restric
         o[k] = rowbn::grad_y(dz, a, w, ga[k], is[k], s0[k], s1[k]);
       }
     }
-    *reinterpret_cast<raw_t*>(out + r * C + c0) = RVec<T>::pack(o);
+    *reinterpret_cast<raw_t*>(out + r * C + c0) = Chunk16<T>::pack(o);
   }
 }
 
 template <typename T>
 static inline bool rv_ok(int C, const void* a, const void* b, const void* c) {
-  const int cpr = C / RVec<T>::N;
-  return C % RVec<T>::N == 0 && cpr >= 1 && cpr <= 256 && (cpr & (cpr - 1)) == 0 &&
-         (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) % 16 == 0);
+  const int cpr = C / Chunk16<T>::N;
+  return C % Chunk16<T>::N == 0 && cpr >= 1 && cpr <= 256 && (cpr & (cpr - 1)) == 0 && aligned16(a) && aligned16(b) &&
+         aligned16(c);
+}
+
+// grid of rowbn_sums_vec_kernel: 256 / cpr rows per block, four rows per thread and iteration
+template <typename T>
+static inline dim3 sums_vec_grid(int64_t R, int C) {
+  const int rpb = 256 / (C / Chunk16<T>::N);
+  int64_t b = (R + 4 * rpb - 1) / (4 * rpb);
+  if (b > 256 * 2) b = 256 * 2;      // every block ends with 2 C fp64 atomics: more blocks measured slower
+  return dim3((int)b);
+}
+template <typename T>
+static inline dim3 apply_vec_grid(int64_t R, int C) {
+  return dim3(capped_grid(R * (C / Chunk16<T>::N), 256, 256 * 16));
 }
 
 }  // namespace dva
@@ -328,36 +309,21 @@ extern "C" {
 int dva_rowbn_stats(const void* y, const int32_t* counts, double* sums, int64_t R, int32_t C,
                     int32_t dtype, void* stream) {
   if (R < 0 || C <= 0 || C > 4096 || !sums) return DVA_ERR_INVALID;
-  if (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16) return DVA_ERR_INVALID;
+  if (!dtype_ok(dtype)) return DVA_ERR_INVALID;
   if (R == 0) return DVA_OK;
   if (!y) return DVA_ERR_INVALID;
-  const dim3 block(64, 4);
+  hipStream_t s = (hipStream_t)stream;
   const size_t lds = 2 * (size_t)C * sizeof(double);
-  if (dtype == DVA_F32 ? rv_ok<float>(C, y, y, y) : rv_ok<bf16_t>(C, y, y, y)) {
-    const int rpb = 256 / (C / (dtype == DVA_F32 ? 4 : 8));
-    int64_t b = (R + 4 * rpb - 1) / (4 * rpb);      // four rows per thread and iteration
-    if (b > 256 * 2) b = 256 * 2;      // every block ends with 2 C fp64 atomics: more blocks measured slower
-    if (dtype == DVA_F32)
-      hipLaunchKernelGGL((rowbn_sums_vec_kernel<float, 0>), dim3((int)b), dim3(256), lds, (hipStream_t)stream,
-                         (const float*)y, (const float*)nullptr, counts, (const float*)nullptr, sums, R, C, 0.f);
-    else if (dtype == DVA_F16)
-      hipLaunchKernelGGL((rowbn_sums_vec_kernel<f16_t, 0>), dim3((int)b), dim3(256), lds, (hipStream_t)stream,
-                         (const f16_t*)y, (const f16_t*)nullptr, counts, (const float*)nullptr, sums, R, C, 0.f);
+  const bool known = with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    if (rv_ok<T>(C, y, y, y))
+      hipLaunchKernelGGL((rowbn_sums_vec_kernel<T, 0>), sums_vec_grid<T>(R, C), dim3(256), lds, s, (const T*)y,
+                         (const T*)nullptr, counts, (const float*)nullptr, sums, R, C, 0.f);
     else
-      hipLaunchKernelGGL((rowbn_sums_vec_kernel<bf16_t, 0>), dim3((int)b), dim3(256), lds, (hipStream_t)stream,
-                         (const bf16_t*)y, (const bf16_t*)nullptr, counts, (const float*)nullptr, sums, R, C, 0.f);
-    DVA_CHECK_LAUNCH();
-    return DVA_OK;
-  }
-  if (dtype == DVA_F32)
-    hipLaunchKernelGGL((rowbn_stats_kernel<float>), dim3(capped_grid(R, RB_ROWS, 256 * 8)), block, lds,
-                       (hipStream_t)stream, (const float*)y, counts, sums, R, C);
-  else if (dtype == DVA_F16)
-    hipLaunchKernelGGL((rowbn_stats_kernel<f16_t>), dim3(capped_grid(R, RB_ROWS, 256 * 8)), block, lds,
-                       (hipStream_t)stream, (const f16_t*)y, counts, sums, R, C);
-  else
-    hipLaunchKernelGGL((rowbn_stats_kernel<bf16_t>), dim3(capped_grid(R, RB_ROWS, 256 * 8)), block, lds,
-                       (hipStream_t)stream, (const bf16_t*)y, counts, sums, R, C);
+      hipLaunchKernelGGL((rowbn_stats_kernel<T>), dim3(capped_grid(R, RB_ROWS, 256 * 8)), dim3(64, 4), lds, s,
+                         (const T*)y, counts, sums, R, C);
+  });
+  if (!known) return DVA_ERR_INVALID;
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -365,36 +331,20 @@ int dva_rowbn_stats(const void* y, const int32_t* counts, double* sums, int64_t 
 int dva_rowbn_apply(const void* y, const float* bn, void* out, int64_t R, int32_t C, float slope,
                     int32_t dtype, void* stream) {
   if (R < 0 || C <= 0) return DVA_ERR_INVALID;
-  if (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16) return DVA_ERR_INVALID;
+  if (!dtype_ok(dtype)) return DVA_ERR_INVALID;
   if (R == 0) return DVA_OK;
   if (!y || !bn || !out) return DVA_ERR_INVALID;
-  if (dtype == DVA_F32 ? rv_ok<float>(C, y, out, out) : rv_ok<bf16_t>(C, y, out, out)) {
-    const dim3 vg(capped_grid(R * (C / (dtype == DVA_F32 ? 4 : 8)), 256, 256 * 16));
-    if (dtype == DVA_F32)
-      hipLaunchKernelGGL((rowbn_apply_vec_kernel<float, 0>), vg, dim3(256), 0, (hipStream_t)stream, (const float*)y,
-                         (const float*)nullptr, (const int32_t*)nullptr, bn, (const float*)nullptr, (float*)out, R,
-                         C, slope);
-    else if (dtype == DVA_F16)
-      hipLaunchKernelGGL((rowbn_apply_vec_kernel<f16_t, 0>), vg, dim3(256), 0, (hipStream_t)stream,
-                         (const f16_t*)y, (const f16_t*)nullptr, (const int32_t*)nullptr, bn,
-                         (const float*)nullptr, (f16_t*)out, R, C, slope);
+  hipStream_t s = (hipStream_t)stream;
+  const bool known = with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    if (rv_ok<T>(C, y, out, out))
+      hipLaunchKernelGGL((rowbn_apply_vec_kernel<T, 0>), apply_vec_grid<T>(R, C), dim3(256), 0, s, (const T*)y,
+                         (const T*)nullptr, (const int32_t*)nullptr, bn, (const float*)nullptr, (T*)out, R, C, slope);
     else
-      hipLaunchKernelGGL((rowbn_apply_vec_kernel<bf16_t, 0>), vg, dim3(256), 0, (hipStream_t)stream,
-                         (const bf16_t*)y, (const bf16_t*)nullptr, (const int32_t*)nullptr, bn,
-                         (const float*)nullptr, (bf16_t*)out, R, C, slope);
-    DVA_CHECK_LAUNCH();
-    return DVA_OK;
-  }
-  const dim3 grid(capped_grid(R * C, 256, 256 * 16));
-  if (dtype == DVA_F32)
-    hipLaunchKernelGGL((rowbn_apply_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream,
-                       (const float*)y, bn, (float*)out, R, C, slope);
-  else if (dtype == DVA_F16)
-    hipLaunchKernelGGL((rowbn_apply_kernel<f16_t>), grid, dim3(256), 0, (hipStream_t)stream,
-                       (const f16_t*)y, bn, (f16_t*)out, R, C, slope);
-  else
-    hipLaunchKernelGGL((rowbn_apply_kernel<bf16_t>), grid, dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)y, bn, (bf16_t*)out, R, C, slope);
+      hipLaunchKernelGGL((rowbn_apply_kernel<T>), dim3(capped_grid(R * C, 256, 256 * 16)), dim3(256), 0, s,
+                         (const T*)y, bn, (T*)out, R, C, slope);
+  });
+  if (!known) return DVA_ERR_INVALID;
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -402,36 +352,21 @@ int dva_rowbn_apply(const void* y, const float* bn, void* out, int64_t R, int32_
 int dva_rowbn_bwd_stats(const void* grad_out, const void* y, const float* bn, double* sums, int64_t R,
                         int32_t C, float slope, int32_t dtype, void* stream) {
   if (R < 0 || C <= 0 || C > 4096 || !sums) return DVA_ERR_INVALID;
-  if (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16) return DVA_ERR_INVALID;
+  if (!dtype_ok(dtype)) return DVA_ERR_INVALID;
   if (R == 0) return DVA_OK;
   if (!grad_out || !y || !bn) return DVA_ERR_INVALID;
-  const dim3 block(64, 4);
+  hipStream_t s = (hipStream_t)stream;
   const size_t lds = 2 * (size_t)C * sizeof(double);
-  if (dtype == DVA_F32 ? rv_ok<float>(C, y, grad_out, y) : rv_ok<bf16_t>(C, y, grad_out, y)) {
-    const int rpb = 256 / (C / (dtype == DVA_F32 ? 4 : 8));
-    int64_t b = (R + 4 * rpb - 1) / (4 * rpb);      // four rows per thread and iteration
-    if (b > 256 * 2) b = 256 * 2;      // every block ends with 2 C fp64 atomics: more blocks measured slower
-    if (dtype == DVA_F32)
-      hipLaunchKernelGGL((rowbn_sums_vec_kernel<float, 1>), dim3((int)b), dim3(256), lds, (hipStream_t)stream,
-                         (const float*)y, (const float*)grad_out, (const int32_t*)nullptr, bn, sums, R, C, slope);
-    else if (dtype == DVA_F16)
-      hipLaunchKernelGGL((rowbn_sums_vec_kernel<f16_t, 1>), dim3((int)b), dim3(256), lds, (hipStream_t)stream,
-                         (const f16_t*)y, (const f16_t*)grad_out, (const int32_t*)nullptr, bn, sums, R, C, slope);
+  const bool known = with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    if (rv_ok<T>(C, y, grad_out, y))
+      hipLaunchKernelGGL((rowbn_sums_vec_kernel<T, 1>), sums_vec_grid<T>(R, C), dim3(256), lds, s, (const T*)y,
+                         (const T*)grad_out, (const int32_t*)nullptr, bn, sums, R, C, slope);
     else
-      hipLaunchKernelGGL((rowbn_sums_vec_kernel<bf16_t, 1>), dim3((int)b), dim3(256), lds, (hipStream_t)stream,
-                         (const bf16_t*)y, (const bf16_t*)grad_out, (const int32_t*)nullptr, bn, sums, R, C, slope);
-    DVA_CHECK_LAUNCH();
-    return DVA_OK;
-  }
-  if (dtype == DVA_F32)
-    hipLaunchKernelGGL((rowbn_bwd_stats_kernel<float>), dim3(capped_grid(R, RB_ROWS, 256 * 8)), block, lds,
-                       (hipStream_t)stream, (const float*)grad_out, (const float*)y, bn, sums, R, C, slope);
-  else if (dtype == DVA_F16)
-    hipLaunchKernelGGL((rowbn_bwd_stats_kernel<f16_t>), dim3(capped_grid(R, RB_ROWS, 256 * 8)), block, lds,
-                       (hipStream_t)stream, (const f16_t*)grad_out, (const f16_t*)y, bn, sums, R, C, slope);
-  else
-    hipLaunchKernelGGL((rowbn_bwd_stats_kernel<bf16_t>), dim3(capped_grid(R, RB_ROWS, 256 * 8)), block, lds,
-                       (hipStream_t)stream, (const bf16_t*)grad_out, (const bf16_t*)y, bn, sums, R, C, slope);
+      hipLaunchKernelGGL((rowbn_bwd_stats_kernel<T>), dim3(capped_grid(R, RB_ROWS, 256 * 8)), dim3(64, 4), lds, s,
+                         (const T*)grad_out, (const T*)y, bn, sums, R, C, slope);
+  });
+  if (!known) return DVA_ERR_INVALID;
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -440,35 +375,20 @@ int dva_rowbn_bwd_apply(const void* grad_out, const void* y, const int32_t* coun
                         const float* sm, void* grad_y, int64_t R, int32_t C, float slope, int32_t dtype,
                         void* stream) {
   if (R < 0 || C <= 0) return DVA_ERR_INVALID;
-  if (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16) return DVA_ERR_INVALID;
+  if (!dtype_ok(dtype)) return DVA_ERR_INVALID;
   if (R == 0) return DVA_OK;
   if (!grad_out || !y || !bn || !sm || !grad_y) return DVA_ERR_INVALID;
-  if (dtype == DVA_F32 ? rv_ok<float>(C, y, grad_out, grad_y) : rv_ok<bf16_t>(C, y, grad_out, grad_y)) {
-    const dim3 vg(capped_grid(R * (C / (dtype == DVA_F32 ? 4 : 8)), 256, 256 * 16));
-    if (dtype == DVA_F32)
-      hipLaunchKernelGGL((rowbn_apply_vec_kernel<float, 1>), vg, dim3(256), 0, (hipStream_t)stream, (const float*)y,
-                         (const float*)grad_out, counts, bn, sm, (float*)grad_y, R, C, slope);
-    else if (dtype == DVA_F16)
-      hipLaunchKernelGGL((rowbn_apply_vec_kernel<f16_t, 1>), vg, dim3(256), 0, (hipStream_t)stream,
-                         (const f16_t*)y, (const f16_t*)grad_out, counts, bn, sm, (f16_t*)grad_y, R, C, slope);
+  hipStream_t s = (hipStream_t)stream;
+  const bool known = with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    if (rv_ok<T>(C, y, grad_out, grad_y))
+      hipLaunchKernelGGL((rowbn_apply_vec_kernel<T, 1>), apply_vec_grid<T>(R, C), dim3(256), 0, s, (const T*)y,
+                         (const T*)grad_out, counts, bn, sm, (T*)grad_y, R, C, slope);
     else
-      hipLaunchKernelGGL((rowbn_apply_vec_kernel<bf16_t, 1>), vg, dim3(256), 0, (hipStream_t)stream,
-                         (const bf16_t*)y, (const bf16_t*)grad_out, counts, bn, sm, (bf16_t*)grad_y, R, C, slope);
-    DVA_CHECK_LAUNCH();
-    return DVA_OK;
-  }
-  const dim3 grid(capped_grid(R * C, 256, 256 * 16));
-  if (dtype == DVA_F32)
-    hipLaunchKernelGGL((rowbn_bwd_apply_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream,
-                       (const float*)grad_out, (const float*)y, counts, bn, sm, (float*)grad_y, R, C, slope);
-  else if (dtype == DVA_F16)
-    hipLaunchKernelGGL((rowbn_bwd_apply_kernel<f16_t>), grid, dim3(256), 0, (hipStream_t)stream,
-                       (const f16_t*)grad_out, (const f16_t*)y, counts, bn, sm, (f16_t*)grad_y, R, C,
-                       slope);
-  else
-    hipLaunchKernelGGL((rowbn_bwd_apply_kernel<bf16_t>), grid, dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)grad_out, (const bf16_t*)y, counts, bn, sm, (bf16_t*)grad_y, R, C,
-                       slope);
+      hipLaunchKernelGGL((rowbn_bwd_apply_kernel<T>), dim3(capped_grid(R * C, 256, 256 * 16)), dim3(256), 0, s,
+                         (const T*)grad_out, (const T*)y, counts, bn, sm, (T*)grad_y, R, C, slope);
+  });
+  if (!known) return DVA_ERR_INVALID;
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }

@@ -419,21 +419,18 @@ int dva_seg_logsoftmax_nll_fwd(const void* logits, int32_t dtype, const int64_t*
                                double* numden, void* workspace, int64_t workspace_bytes, void* stream) {
   int rc = seg_shape(P, C);
   if (rc) return rc;
-  if (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16) return DVA_ERR_INVALID;
+  if (!dtype_ok(dtype)) return DVA_ERR_INVALID;
   if (!loss || !numden || !workspace || workspace_bytes < dva_seg_nll_workspace_bytes()) return DVA_ERR_INVALID;
   if (P > 0 && (!logits || !labels || !log_probs)) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   double* partial = (double*)workspace;
   const int grid = capped_grid(P, SEG_THREADS, SEG_MAX_BLOCKS);
-  if (dtype == DVA_F32)
-    hipLaunchKernelGGL(seg_nll_fwd_kernel<float>, dim3(grid), dim3(SEG_THREADS), 0, s, (const float*)logits, labels,
-                       weight, ignore_index, P, (int)C, log_probs, partial);
-  else if (dtype == DVA_BF16)
-    hipLaunchKernelGGL(seg_nll_fwd_kernel<bf16_t>, dim3(grid), dim3(SEG_THREADS), 0, s, (const bf16_t*)logits, labels,
-                       weight, ignore_index, P, (int)C, log_probs, partial);
-  else
-    hipLaunchKernelGGL(seg_nll_fwd_kernel<f16_t>, dim3(grid), dim3(SEG_THREADS), 0, s, (const f16_t*)logits, labels,
-                       weight, ignore_index, P, (int)C, log_probs, partial);
+  const bool known = with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    hipLaunchKernelGGL(seg_nll_fwd_kernel<T>, dim3(grid), dim3(SEG_THREADS), 0, s, (const T*)logits, labels, weight,
+                       ignore_index, P, (int)C, log_probs, partial);
+  });
+  if (!known) return DVA_ERR_INVALID;
   hipLaunchKernelGGL(seg_nll_finish_kernel, dim3(1), dim3(SEG_THREADS), 0, s, partial, grid, numden, loss);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
@@ -445,21 +442,18 @@ int dva_seg_logsoftmax_nll_bwd(const float* log_probs, const int64_t* labels, co
                                void* stream) {
   int rc = seg_shape(P, C);
   if (rc) return rc;
-  if (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16) return DVA_ERR_INVALID;
+  if (!dtype_ok(dtype)) return DVA_ERR_INVALID;
   if (!numden) return DVA_ERR_INVALID;
   if (P == 0) return DVA_OK;
   if (!log_probs || !labels || !grad_logits) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   const int grid = capped_grid(P, SEG_THREADS, 1 << 16);
-  if (dtype == DVA_F32)
-    hipLaunchKernelGGL(seg_nll_bwd_kernel<float>, dim3(grid), dim3(SEG_THREADS), 0, s, log_probs, labels, weight, numden,
-                       grad_loss, grad_log_probs, ignore_index, P, (int)C, (float*)grad_logits);
-  else if (dtype == DVA_BF16)
-    hipLaunchKernelGGL(seg_nll_bwd_kernel<bf16_t>, dim3(grid), dim3(SEG_THREADS), 0, s, log_probs, labels, weight, numden,
-                       grad_loss, grad_log_probs, ignore_index, P, (int)C, (bf16_t*)grad_logits);
-  else
-    hipLaunchKernelGGL(seg_nll_bwd_kernel<f16_t>, dim3(grid), dim3(SEG_THREADS), 0, s, log_probs, labels, weight, numden,
-                       grad_loss, grad_log_probs, ignore_index, P, (int)C, (f16_t*)grad_logits);
+  const bool known = with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    hipLaunchKernelGGL(seg_nll_bwd_kernel<T>, dim3(grid), dim3(SEG_THREADS), 0, s, log_probs, labels, weight, numden,
+                       grad_loss, grad_log_probs, ignore_index, P, (int)C, (T*)grad_logits);
+  });
+  if (!known) return DVA_ERR_INVALID;
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -468,21 +462,18 @@ int dva_confusion_counts(const void* outputs, int32_t dtype, const int64_t* labe
                          int32_t C, int64_t* counts, int64_t* n_bad, void* stream) {
   int rc = seg_shape(P, C);
   if (rc) return rc;
-  if (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16) return DVA_ERR_INVALID;
+  if (!dtype_ok(dtype)) return DVA_ERR_INVALID;
   if (!counts || !n_bad) return DVA_ERR_INVALID;
   if (P == 0) return DVA_OK;
   if (!outputs || !labels) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   const int grid = capped_grid(P, SEG_THREADS, 2048);
-  if (dtype == DVA_F32)
-    hipLaunchKernelGGL(confusion_kernel<float>, dim3(grid), dim3(SEG_THREADS), 0, s, (const float*)outputs, labels,
-                       ignore_index, P, (int)C, (long long*)counts, (long long*)n_bad);
-  else if (dtype == DVA_BF16)
-    hipLaunchKernelGGL(confusion_kernel<bf16_t>, dim3(grid), dim3(SEG_THREADS), 0, s, (const bf16_t*)outputs, labels,
-                       ignore_index, P, (int)C, (long long*)counts, (long long*)n_bad);
-  else
-    hipLaunchKernelGGL(confusion_kernel<f16_t>, dim3(grid), dim3(SEG_THREADS), 0, s, (const f16_t*)outputs, labels,
-                       ignore_index, P, (int)C, (long long*)counts, (long long*)n_bad);
+  const bool known = with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    hipLaunchKernelGGL(confusion_kernel<T>, dim3(grid), dim3(SEG_THREADS), 0, s, (const T*)outputs, labels, ignore_index,
+                       P, (int)C, (long long*)counts, (long long*)n_bad);
+  });
+  if (!known) return DVA_ERR_INVALID;
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }

@@ -152,44 +152,14 @@ __global__ __launch_bounds__(256) void segment_softmax_bwd_kernel(const float* _
 // consecutive channels of a group, so a row costs one load / store instruction per thread instead of VEC.
 // Same arithmetic and tie rule (first row) as the scalar kernels.
 // ------------------------------------------------------------------------------------------------
-template <typename T> struct SVec;
-template <> struct SVec<float> {
-  static constexpr int N = 4;
-  typedef float4 raw;
-  static __device__ __forceinline__ void unpack(const raw& r, float* f) { f[0] = r.x; f[1] = r.y; f[2] = r.z; f[3] = r.w; }
-  static __device__ __forceinline__ raw pack(const float* f) { return make_float4(f[0], f[1], f[2], f[3]); }
-};
-template <> struct SVec<bf16_t> {
-  static constexpr int N = 8;
-  typedef uint4 raw;
-  static __device__ __forceinline__ void unpack(const raw& r, float* f) {
-    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      f[2 * e] = __uint_as_float(w[e] << 16);
-      f[2 * e + 1] = __uint_as_float(w[e] & 0xffff0000u);
-    }
-  }
-  static __device__ __forceinline__ raw pack(const float* f) {
-    return make_uint4(pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]),
-                      pack_bf16x2(f[6], f[7]));
-  }
-};
-template <> struct SVec<f16_t> {
-  static constexpr int N = 8;
-  typedef uint4 raw;
-  static __device__ __forceinline__ void unpack(const raw& r, float* f) { unpack_h8<f16_t>(r, f); }
-  static __device__ __forceinline__ raw pack(const float* f) { return pack_h8<f16_t>(f); }
-};
-
 template <typename T, int REDUCE>
 __global__ __launch_bounds__(256) void segment_csr_fwd_vec_kernel(const T* __restrict__ src,
                                                                    const int64_t* __restrict__ ptr,
                                                                    T* __restrict__ out,
                                                                    int32_t* __restrict__ arg,
                                                                    int64_t n_groups, int C) {
-  constexpr int VEC = SVec<T>::N;
-  typedef typename SVec<T>::raw raw_t;
+  constexpr int VEC = Chunk16<T>::N;
+  typedef typename Chunk16<T>::raw raw_t;
   const int cpr = C / VEC;
   const int64_t total = n_groups * (int64_t)cpr;
   for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total;
@@ -206,7 +176,7 @@ __global__ __launch_bounds__(256) void segment_csr_fwd_vec_kernel(const T* __res
     }
     for (int64_t r = beg; r < end; ++r) {
       float f[VEC];
-      SVec<T>::unpack(*reinterpret_cast<const raw_t*>(src + r * C + c0), f);
+      Chunk16<T>::unpack(*reinterpret_cast<const raw_t*>(src + r * C + c0), f);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
         if (REDUCE == DVA_SUM || REDUCE == DVA_MEAN) {
@@ -221,7 +191,7 @@ __global__ __launch_bounds__(256) void segment_csr_fwd_vec_kernel(const T* __res
 #pragma unroll
       for (int k = 0; k < VEC; ++k) acc[k] /= (float)(end - beg);
     }
-    *reinterpret_cast<raw_t*>(out + g * C + c0) = SVec<T>::pack(acc);
+    *reinterpret_cast<raw_t*>(out + g * C + c0) = Chunk16<T>::pack(acc);
     if ((REDUCE == DVA_MAX || REDUCE == DVA_MIN) && arg) {
 #pragma unroll
       for (int k = 0; k < VEC; ++k) arg[g * C + c0 + k] = best[k];
@@ -235,8 +205,8 @@ __global__ __launch_bounds__(256) void segment_csr_bwd_vec_kernel(const T* __res
                                                                    const int32_t* __restrict__ arg,
                                                                    T* __restrict__ gsrc,
                                                                    int64_t n_groups, int C) {
-  constexpr int VEC = SVec<T>::N;
-  typedef typename SVec<T>::raw raw_t;
+  constexpr int VEC = Chunk16<T>::N;
+  typedef typename Chunk16<T>::raw raw_t;
   const int cpr = C / VEC;
   const int64_t total = n_groups * (int64_t)cpr;
   for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total;
@@ -246,7 +216,7 @@ __global__ __launch_bounds__(256) void segment_csr_bwd_vec_kernel(const T* __res
     const int64_t beg = ptr[g], end = ptr[g + 1];
     if (end <= beg) continue;
     float go[VEC];
-    SVec<T>::unpack(*reinterpret_cast<const raw_t*>(gout + g * C + c0), go);
+    Chunk16<T>::unpack(*reinterpret_cast<const raw_t*>(gout + g * C + c0), go);
     if (REDUCE == DVA_MEAN) {
 #pragma unroll
       for (int k = 0; k < VEC; ++k) go[k] /= (float)(end - beg);
@@ -261,66 +231,19 @@ __global__ __launch_bounds__(256) void segment_csr_bwd_vec_kernel(const T* __res
 #pragma unroll
       for (int k = 0; k < VEC; ++k)
         f[k] = (REDUCE == DVA_SUM || REDUCE == DVA_MEAN) ? go[k] : ((int64_t)a[k] == r ? go[k] : 0.f);
-      *reinterpret_cast<raw_t*>(gsrc + r * C + c0) = SVec<T>::pack(f);
+      *reinterpret_cast<raw_t*>(gsrc + r * C + c0) = Chunk16<T>::pack(f);
     }
   }
 }
 
+// 16-byte chunks or elements, and the launch grid that goes with the choice
 template <typename T>
 static inline bool vec_ok(const void* a, const void* b, int C) {
-  return C % SVec<T>::N == 0 && ((uintptr_t)a % 16 == 0) && ((uintptr_t)b % 16 == 0);
+  return C % Chunk16<T>::N == 0 && aligned16(a) && aligned16(b);
 }
-
-constexpr int64_t CSR_GRID_CAP = 256 * 32;  // 256 CUs x 32 blocks, grid-stride beyond
-
 template <typename T>
-static int launch_segment_fwd(const void* src, const int64_t* ptr, void* out, int32_t* arg,
-                              int64_t n, int C, int reduce, hipStream_t s) {
-  const bool vec = vec_ok<T>(src, out, C);
-  const int grid = capped_grid(n * (int64_t)(vec ? C / SVec<T>::N : C), 256, CSR_GRID_CAP);
-#define DVA_L(R)                                                                                        \
-  do {                                                                                                  \
-    if (vec)                                                                                            \
-      hipLaunchKernelGGL((segment_csr_fwd_vec_kernel<T, R>), dim3(grid), dim3(256), 0, s, (const T*)src, \
-                         ptr, (T*)out, arg, n, C);                                                      \
-    else                                                                                                \
-      hipLaunchKernelGGL((segment_csr_fwd_kernel<T, R>), dim3(grid), dim3(256), 0, s, (const T*)src,    \
-                         ptr, (T*)out, arg, n, C);                                                      \
-  } while (0)
-  switch (reduce) {
-    case DVA_SUM: DVA_L(DVA_SUM); break;
-    case DVA_MEAN: DVA_L(DVA_MEAN); break;
-    case DVA_MAX: DVA_L(DVA_MAX); break;
-    case DVA_MIN: DVA_L(DVA_MIN); break;
-    default: return DVA_ERR_INVALID;
-  }
-#undef DVA_L
-  return DVA_OK;
-}
-
-template <typename T>
-static int launch_segment_bwd(const void* gout, const int64_t* ptr, const int32_t* arg, void* gsrc,
-                              int64_t n, int C, int reduce, hipStream_t s) {
-  const bool vec = vec_ok<T>(gout, gsrc, C);
-  const int grid = capped_grid(n * (int64_t)(vec ? C / SVec<T>::N : C), 256, CSR_GRID_CAP);
-#define DVA_L(R)                                                                                         \
-  do {                                                                                                   \
-    if (vec)                                                                                             \
-      hipLaunchKernelGGL((segment_csr_bwd_vec_kernel<T, R>), dim3(grid), dim3(256), 0, s, (const T*)gout, \
-                         ptr, arg, (T*)gsrc, n, C);                                                      \
-    else                                                                                                 \
-      hipLaunchKernelGGL((segment_csr_bwd_kernel<T, R>), dim3(grid), dim3(256), 0, s, (const T*)gout,    \
-                         ptr, arg, (T*)gsrc, n, C);                                                      \
-  } while (0)
-  switch (reduce) {
-    case DVA_SUM: DVA_L(DVA_SUM); break;
-    case DVA_MEAN: DVA_L(DVA_MEAN); break;
-    case DVA_MAX: DVA_L(DVA_MAX); break;
-    case DVA_MIN: DVA_L(DVA_MIN); break;
-    default: return DVA_ERR_INVALID;
-  }
-#undef DVA_L
-  return DVA_OK;
+static inline int segment_grid(int64_t n, int C, bool vec) {
+  return capped_grid(n * (int64_t)(vec ? C / Chunk16<T>::N : C), 256, GRID_CAP);
 }
 
 }  // namespace dva
@@ -345,16 +268,22 @@ int dva_segment_csr_fwd(const void* src, const int64_t* ptr, void* out, int32_t*
   if (reduce < DVA_SUM || reduce > DVA_MIN) return DVA_ERR_INVALID;
   if (n_groups == 0 || C == 0) return DVA_OK;
   if (!out) return DVA_ERR_INVALID;
-  int rc;
-  if (dtype == DVA_F32)
-    rc = launch_segment_fwd<float>(src, ptr, out, arg, n_groups, C, reduce, (hipStream_t)stream);
-  else if (dtype == DVA_BF16)
-    rc = launch_segment_fwd<bf16_t>(src, ptr, out, arg, n_groups, C, reduce, (hipStream_t)stream);
-  else if (dtype == DVA_F16)
-    rc = launch_segment_fwd<f16_t>(src, ptr, out, arg, n_groups, C, reduce, (hipStream_t)stream);
-  else
-    return DVA_ERR_INVALID;
-  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const bool known = with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    const bool vec = vec_ok<T>(src, out, C);
+    const dim3 grid(segment_grid<T>(n_groups, C, vec));
+    with_reduce(reduce, [&](auto red) {
+      constexpr int R = decltype(red)::value;
+      if (vec)
+        hipLaunchKernelGGL((segment_csr_fwd_vec_kernel<T, R>), grid, dim3(256), 0, s, (const T*)src, ptr, (T*)out, arg,
+                           n_groups, C);
+      else
+        hipLaunchKernelGGL((segment_csr_fwd_kernel<T, R>), grid, dim3(256), 0, s, (const T*)src, ptr, (T*)out, arg,
+                           n_groups, C);
+    });
+  });
+  if (!known) return DVA_ERR_INVALID;
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -367,19 +296,22 @@ int dva_segment_csr_bwd(const void* grad_out, const int64_t* ptr, const int32_t*
   if ((reduce == DVA_MAX || reduce == DVA_MIN) && !arg && n_groups > 0 && C > 0)
     return DVA_ERR_INVALID;
   if (n_groups == 0 || C == 0) return DVA_OK;
-  int rc;
-  if (dtype == DVA_F32)
-    rc = launch_segment_bwd<float>(grad_out, ptr, arg, grad_src, n_groups, C, reduce,
-                                   (hipStream_t)stream);
-  else if (dtype == DVA_BF16)
-    rc = launch_segment_bwd<bf16_t>(grad_out, ptr, arg, grad_src, n_groups, C, reduce,
-                                    (hipStream_t)stream);
-  else if (dtype == DVA_F16)
-    rc = launch_segment_bwd<f16_t>(grad_out, ptr, arg, grad_src, n_groups, C, reduce,
-                                    (hipStream_t)stream);
-  else
-    return DVA_ERR_INVALID;
-  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const bool known = with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    const bool vec = vec_ok<T>(grad_out, grad_src, C);
+    const dim3 grid(segment_grid<T>(n_groups, C, vec));
+    with_reduce(reduce, [&](auto red) {
+      constexpr int R = decltype(red)::value;
+      if (vec)
+        hipLaunchKernelGGL((segment_csr_bwd_vec_kernel<T, R>), grid, dim3(256), 0, s, (const T*)grad_out, ptr, arg,
+                           (T*)grad_src, n_groups, C);
+      else
+        hipLaunchKernelGGL((segment_csr_bwd_kernel<T, R>), grid, dim3(256), 0, s, (const T*)grad_out, ptr, arg,
+                           (T*)grad_src, n_groups, C);
+    });
+  });
+  if (!known) return DVA_ERR_INVALID;
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }
@@ -389,17 +321,18 @@ int dva_gather_csr(const void* src, const int64_t* ptr, void* out, int64_t n_gro
   if (n_groups < 0 || C < 0 || !ptr) return DVA_ERR_INVALID;
   if (n_groups == 0 || C == 0) return DVA_OK;
   // pure byte movement: with 16-byte aligned rows every thread copies 16 bytes of a group's row
-  const int64_t row_bytes = (int64_t)C * (dtype == DVA_F32 ? 4 : 2);
-  if (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16) return DVA_ERR_INVALID;
-  if (row_bytes % 16 == 0 && ((uintptr_t)src % 16 == 0) && ((uintptr_t)out % 16 == 0)) {
+  const int elt_bytes = dtype == DVA_F32 ? 4 : 2;
+  const int64_t row_bytes = (int64_t)C * elt_bytes;
+  if (!dtype_ok(dtype)) return DVA_ERR_INVALID;
+  if (row_bytes % 16 == 0 && aligned16(src) && aligned16(out)) {
     const int u = (int)(row_bytes / 16);
-    hipLaunchKernelGGL((gather_csr_kernel<uint4>), dim3(capped_grid(n_groups * (int64_t)u, 256, CSR_GRID_CAP)),
+    hipLaunchKernelGGL((gather_csr_kernel<uint4>), dim3(capped_grid(n_groups * (int64_t)u, 256, GRID_CAP)),
                        dim3(256), 0, (hipStream_t)stream, (const uint4*)src, ptr, (uint4*)out, n_groups, u);
     DVA_CHECK_LAUNCH();
     return DVA_OK;
   }
-  const int grid = capped_grid(n_groups * (int64_t)C, 256, CSR_GRID_CAP);
-  if (dtype == DVA_F32)
+  const int grid = capped_grid(n_groups * (int64_t)C, 256, GRID_CAP);
+  if (elt_bytes == 4)
     hipLaunchKernelGGL((gather_csr_kernel<float>), dim3(grid), dim3(256), 0, (hipStream_t)stream,
                        (const float*)src, ptr, (float*)out, n_groups, C);
   else
@@ -414,7 +347,7 @@ int dva_segment_softmax_csr_fwd(const float* src, const int64_t* ptr, float* out
                                 void* stream) {
   if (n_groups < 0 || G < 0 || !ptr) return DVA_ERR_INVALID;
   if (n_groups == 0 || G == 0) return DVA_OK;
-  const int grid = capped_grid(n_groups * (int64_t)G, 256, CSR_GRID_CAP);
+  const int grid = capped_grid(n_groups * (int64_t)G, 256, GRID_CAP);
   hipLaunchKernelGGL(segment_softmax_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, src,
                      ptr, out, n_groups, G, scaling, eps);
   DVA_CHECK_LAUNCH();
@@ -426,7 +359,7 @@ int dva_segment_softmax_csr_bwd(const float* grad_out, const float* out, const i
                                 void* stream) {
   if (n_groups < 0 || G < 0 || !ptr) return DVA_ERR_INVALID;
   if (n_groups == 0 || G == 0) return DVA_OK;
-  const int grid = capped_grid(n_groups * (int64_t)G, 256, CSR_GRID_CAP);
+  const int grid = capped_grid(n_groups * (int64_t)G, 256, GRID_CAP);
   hipLaunchKernelGGL(segment_softmax_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream,
                      grad_out, out, ptr, grad_src, n_groups, G, scaling);
   DVA_CHECK_LAUNCH();

@@ -137,8 +137,6 @@ __global__ __launch_bounds__(VL_THREADS) void view_nll_bwd_kernel(const T* __res
   }
 }
 
-static bool vl_dtype_ok(int dtype) { return dtype == DVA_F32 || dtype == DVA_BF16 || dtype == DVA_F16; }
-
 }  // namespace dva
 
 using namespace dva;
@@ -165,22 +163,19 @@ int dva_view_nll_counts(const int32_t* row_idx, int64_t n_views, const int64_t* 
 
 int dva_view_nll_fwd(const void* rows, int32_t dtype, const int32_t* cnt, const float* weight, int64_t n_rows,
                      int32_t K, float* loss, double* numden, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (n_rows < 0 || K < 1 || !vl_dtype_ok(dtype)) return DVA_ERR_INVALID;
+  if (n_rows < 0 || K < 1 || !dtype_ok(dtype)) return DVA_ERR_INVALID;
   if (K > VL_MAX_K || n_rows * (int64_t)K >= (1LL << 31)) return DVA_ERR_UNSUPPORTED;
   if (!loss || !numden || !workspace || (n_rows > 0 && (!rows || !cnt))) return DVA_ERR_INVALID;
   if (workspace_bytes < dva_view_nll_workspace_bytes()) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   double* partial = (double*)workspace;
   const int blocks = capped_grid(n_rows, VL_THREADS, VL_MAX_BLOCKS);
-  if (dtype == DVA_F32)
-    hipLaunchKernelGGL(view_nll_fwd_kernel<float>, dim3(blocks), dim3(VL_THREADS), 0, s, (const float*)rows, cnt, weight,
-                       n_rows, K, partial);
-  else if (dtype == DVA_BF16)
-    hipLaunchKernelGGL(view_nll_fwd_kernel<bf16_t>, dim3(blocks), dim3(VL_THREADS), 0, s, (const bf16_t*)rows, cnt,
-                       weight, n_rows, K, partial);
-  else
-    hipLaunchKernelGGL(view_nll_fwd_kernel<f16_t>, dim3(blocks), dim3(VL_THREADS), 0, s, (const f16_t*)rows, cnt, weight,
-                       n_rows, K, partial);
+  const bool known = with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    hipLaunchKernelGGL(view_nll_fwd_kernel<T>, dim3(blocks), dim3(VL_THREADS), 0, s, (const T*)rows, cnt, weight, n_rows,
+                       K, partial);
+  });
+  if (!known) return DVA_ERR_INVALID;
   hipLaunchKernelGGL(view_nll_finish_kernel, dim3(1), dim3(VL_THREADS), 0, s, partial, blocks, numden, loss);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
@@ -188,21 +183,18 @@ int dva_view_nll_fwd(const void* rows, int32_t dtype, const int32_t* cnt, const 
 
 int dva_view_nll_bwd(const void* rows, int32_t dtype, const int32_t* cnt, const float* weight, const double* numden,
                      const float* grad_loss, int64_t n_rows, int32_t K, void* grad_rows, void* stream) {
-  if (n_rows < 0 || K < 1 || !vl_dtype_ok(dtype)) return DVA_ERR_INVALID;
+  if (n_rows < 0 || K < 1 || !dtype_ok(dtype)) return DVA_ERR_INVALID;
   if (K > VL_MAX_K || n_rows * (int64_t)K >= (1LL << 31)) return DVA_ERR_UNSUPPORTED;
   if (n_rows == 0) return DVA_OK;
   if (!rows || !cnt || !numden || !grad_loss || !grad_rows) return DVA_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   const int blocks = capped_grid(n_rows, VL_THREADS, 8192);
-  if (dtype == DVA_F32)
-    hipLaunchKernelGGL(view_nll_bwd_kernel<float>, dim3(blocks), dim3(VL_THREADS), 0, s, (const float*)rows, cnt, weight,
-                       numden, grad_loss, n_rows, K, (float*)grad_rows);
-  else if (dtype == DVA_BF16)
-    hipLaunchKernelGGL(view_nll_bwd_kernel<bf16_t>, dim3(blocks), dim3(VL_THREADS), 0, s, (const bf16_t*)rows, cnt,
-                       weight, numden, grad_loss, n_rows, K, (bf16_t*)grad_rows);
-  else
-    hipLaunchKernelGGL(view_nll_bwd_kernel<f16_t>, dim3(blocks), dim3(VL_THREADS), 0, s, (const f16_t*)rows, cnt, weight,
-                       numden, grad_loss, n_rows, K, (f16_t*)grad_rows);
+  const bool known = with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    hipLaunchKernelGGL(view_nll_bwd_kernel<T>, dim3(blocks), dim3(VL_THREADS), 0, s, (const T*)rows, cnt, weight, numden,
+                       grad_loss, n_rows, K, (T*)grad_rows);
+  });
+  if (!known) return DVA_ERR_INVALID;
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }

@@ -197,7 +197,7 @@ int64_t dva_vote_workspace_bytes(int64_t N) {
 int dva_vote_add(float* votes, int32_t* counts, int64_t N, int32_t C, const int64_t* ids, const void* outputs,
                  int32_t dtype, int64_t P, int32_t* slots, int64_t slots_bytes, int64_t* n_bad, void* stream) {
   if (N < 0 || P < 0 || C < 1) return DVA_ERR_INVALID;
-  if (dtype != DVA_F32 && dtype != DVA_BF16 && dtype != DVA_F16) return DVA_ERR_INVALID;
+  if (!dtype_ok(dtype)) return DVA_ERR_INVALID;
   if (C > VOTE_MAX_C || N > 0x7fffffffLL || P > 0x7fffffffLL) return DVA_ERR_UNSUPPORTED;   // a row position is int32
   if (!slots || !n_bad || slots_bytes < dva_vote_workspace_bytes(N)) return DVA_ERR_INVALID;
   if (N > 0 && (!votes || !counts)) return DVA_ERR_INVALID;
@@ -208,15 +208,12 @@ int dva_vote_add(float* votes, int32_t* counts, int64_t N, int32_t C, const int6
   const int elts_grid = capped_grid(P * C, VOTE_THREADS, 1 << 16);
   hipLaunchKernelGGL(vote_claim_kernel, dim3(rows_grid), dim3(VOTE_THREADS), 0, s, ids, P, N, slots,
                      (long long*)n_bad);
-  if (dtype == DVA_F32)
-    hipLaunchKernelGGL(vote_apply_kernel<float>, dim3(elts_grid), dim3(VOTE_THREADS), 0, s, ids, (const float*)outputs,
-                       P, (int)C, N, slots, votes, counts);
-  else if (dtype == DVA_BF16)
-    hipLaunchKernelGGL(vote_apply_kernel<bf16_t>, dim3(elts_grid), dim3(VOTE_THREADS), 0, s, ids,
-                       (const bf16_t*)outputs, P, (int)C, N, slots, votes, counts);
-  else
-    hipLaunchKernelGGL(vote_apply_kernel<f16_t>, dim3(elts_grid), dim3(VOTE_THREADS), 0, s, ids, (const f16_t*)outputs,
-                       P, (int)C, N, slots, votes, counts);
+  const bool known = with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    hipLaunchKernelGGL(vote_apply_kernel<T>, dim3(elts_grid), dim3(VOTE_THREADS), 0, s, ids, (const T*)outputs, P, (int)C,
+                       N, slots, votes, counts);
+  });
+  if (!known) return DVA_ERR_INVALID;
   hipLaunchKernelGGL(vote_release_kernel, dim3(rows_grid), dim3(VOTE_THREADS), 0, s, ids, P, N, slots);
   DVA_CHECK_LAUNCH();
   return DVA_OK;

@@ -897,6 +897,31 @@ def test_gather_bilinear_forward_is_bitwise_the_reference_expression(dtype, C):
     assert torch.equal(out, acc.to(dtype))
 
 
+@pytest.mark.parametrize("C", [8, 64])
+def test_gather_bilinear_bf16_vector_kernel_equals_the_scalar_kernel_bitwise(C):
+    """dva_gather_bilinear_fwd on bf16 rows: 16-byte aligned rows of C = 8 (one lane a row) and C = 64 (eight lanes a row)
+    take the vector kernel, the same rows one element further on in memory take the scalar kernel.  The vector kernel
+    rounds its eight results to bf16 in pairs (Chunk16::pack), the scalar kernel one by one: both to nearest even, so the
+    outputs are the same bits."""
+    from deepviewagg_amd import ops
+    gen = torch.Generator().manual_seed(C)
+    B, H, W, P = 2, 5, 7, 37
+    x = torch.randn(B, H, W, C, generator=gen).bfloat16().to(DEV)
+    images = torch.randint(0, B, (P,), generator=gen)
+    coords = torch.rand(P, 2, generator=gen)
+    coords[:3] = torch.tensor([0.0, 1.0])
+    coords[3:5] = torch.tensor([1.0, 0.0])
+    packed = ops.pack_gather_index(images.to(DEV), torch.arange(P + 1, device=DEV),
+                                   torch.zeros(P, 2, dtype=torch.int16, device=DEV))
+    shifted = torch.empty(x.numel() + 1, dtype=x.dtype, device=DEV)[1:].view_as(x)
+    shifted.copy_(x)
+    assert x.data_ptr() % 16 == 0 and shifted.data_ptr() % 16 == 2
+    out_vec = ops.gather_bilinear(x.permute(0, 3, 1, 2), packed, coords.to(DEV))
+    out_scalar = ops.gather_bilinear(shifted.permute(0, 3, 1, 2), packed, coords.to(DEV))
+    assert out_vec.isfinite().all() and out_vec.float().abs().sum() > 0
+    assert torch.equal(out_vec, out_scalar)
+
+
 @pytest.mark.parametrize("V,R,C,G,how", [(9000, 600, 64, 4, "uniform"), (300000, 5000, 32, 2, "uniform"),
                                          (2000000, 1 << 18, 64, 4, "uniform"), (500000, 70000, 64, 1, "skewed"),
                                          (100000, 2000, 32, 4, "one_row")])

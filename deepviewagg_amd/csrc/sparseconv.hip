@@ -102,22 +102,36 @@ template <> struct OutStore<float> {
   static __device__ __forceinline__ void st4(float* p, float a, float b, float c, float d) {
     *reinterpret_cast<float4*>(p) = make_float4(a, b, c, d);
   }
+  static __device__ __forceinline__ void ld4(const float* p, float (&r)[4]) {
+    const float4 q = *reinterpret_cast<const float4*>(p);
+    r[0] = q.x, r[1] = q.y, r[2] = q.z, r[3] = q.w;
+  }
 };
 template <> struct OutStore<bf16_t> {
   static __device__ __forceinline__ void st4(bf16_t* p, float a, float b, float c, float d) {
     *reinterpret_cast<uint2*>(p) = make_uint2(pack_bf16x2(a, b), pack_bf16x2(c, d));
   }
+  static __device__ __forceinline__ void ld4(const bf16_t* p, float (&r)[4]) {
+    const uint2 q = *reinterpret_cast<const uint2*>(p);
+    r[0] = __uint_as_float(q.x << 16), r[1] = __uint_as_float(q.x & 0xffff0000u);
+    r[2] = __uint_as_float(q.y << 16), r[3] = __uint_as_float(q.y & 0xffff0000u);
+  }
 };
 
 // NT = 32-channel output blocks per wavefront (2: 64 output channels per workgroup, 4: 128 -- wide layers
 // gather each input row once per 128 output channels instead of once per 64)
-template <typename T, int NT>
+// FUSED (inference with constant weights, dva_sparse_conv_apply_packed): the epilogue applies the activation and
+// the residual sum before the one rounding to T,
+//   v = acc + bias;  v = v >= 0 ? v : slope * v;  v = v + float(residual[j, n]);  out = T(v)
+// each a separately rounded fp32 operation (the intrinsics hold that under any contraction flag); `residual`
+// ([n_dst, Cout] of T, nullable) is read in the 4-element groups the store writes and must not alias `out`.
+template <typename T, int NT, bool FUSED>
 __global__ __launch_bounds__(256, NT == 4 ? 2 : 1) void sconv_apply_kernel(const T* __restrict__ x, const int32_t* __restrict__ nbr,
                                                            const bf16_t* __restrict__ w_hi,
                                                            const bf16_t* __restrict__ w_lo,
                                                            const float* __restrict__ bias, T* __restrict__ out,
                                                            int64_t n_dst, int K, int Cin, int Cout, int Cin_p,
-                                                           int Cout_p) {
+                                                           int Cout_p, const T* __restrict__ residual, float slope) {
   constexpr bool SPLIT = sizeof(T) == 4;
   constexpr int NB = SPLIT ? 2 : 1;
   constexpr int NROWS = 32 * NT;                                 // output channels of this workgroup
@@ -212,6 +226,16 @@ __global__ __launch_bounds__(256, NT == 4 ? 2 : 1) void sconv_apply_kernel(const
           float v[4];
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = acc[u][t][4 * q + e] + (bias ? bias[n + e] : 0.f);
+          if constexpr (FUSED) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = v[e] >= 0.f ? v[e] : __fmul_rn(slope, v[e]);
+            if (residual) {
+              float r[4];
+              OutStore<T>::ld4(residual + j * Cout + n, r);
+#pragma unroll
+              for (int e = 0; e < 4; ++e) v[e] = __fadd_rn(v[e], r[e]);
+            }
+          }
           OutStore<T>::st4(out + j * Cout + n, v[0], v[1], v[2], v[3]);
         }
       }
@@ -368,30 +392,47 @@ static inline int pad_tile(int c) { return (c + SC_TILE - 1) / SC_TILE * SC_TILE
 // output channels of the re-packed weights: one 64-wide tile, or multiples of the 128-wide tile of wide layers
 static inline int pad_out(int c) { return c <= SC_TILE ? SC_TILE : (c + 127) / 128 * 128; }
 
-template <typename T>
-static int sconv_apply_impl(const void* x, const int32_t* nbr, const float* W, const float* bias, void* out,
-                            int64_t n_dst, int K, int Cin, int Cout, int mode, void* ws, hipStream_t s) {
-  constexpr bool SPLIT = sizeof(T) == 4;
+// the re-packed weights of one layer: w_hi [K][Cout_p][Cin_p] bf16, then w_lo for fp32 features
+static void sconv_pack(const float* W, int K, int Cin, int Cout, int mode, bool split, void* packed, hipStream_t s) {
   const int Cin_p = pad_tile(Cin), Cout_p = pad_out(Cout);
   const int64_t elems = (int64_t)K * Cin_p * Cout_p;
-  bf16_t* w_hi = (bf16_t*)ws;
-  bf16_t* w_lo = SPLIT ? w_hi + elems : nullptr;
+  bf16_t* w_hi = (bf16_t*)packed;
+  bf16_t* w_lo = split ? w_hi + elems : nullptr;
   int64_t pb = (elems + 255) / 256;
   if (pb > 4096) pb = 4096;
   hipLaunchKernelGGL(sconv_prep_weights_kernel, dim3((int)pb), dim3(256), 0, s, W, K, Cin, Cout, Cin_p, Cout_p,
                      mode, w_hi, w_lo);
+}
+
+template <typename T, bool FUSED>
+static int sconv_launch(const void* x, const int32_t* nbr, const void* packed, const float* bias,
+                        const void* residual, float slope, void* out, int64_t n_dst, int K, int Cin, int Cout,
+                        hipStream_t s) {
+  constexpr bool SPLIT = sizeof(T) == 4;
+  const int Cin_p = pad_tile(Cin), Cout_p = pad_out(Cout);
+  const bf16_t* w_hi = (const bf16_t*)packed;
+  const bf16_t* w_lo = SPLIT ? w_hi + (int64_t)K * Cin_p * Cout_p : nullptr;
   const int64_t gx = (n_dst + 255) / 256;
   if (Cout_p >= 128) {
     const size_t lds = (size_t)2 * (SPLIT ? 2 : 1) * 128 * SC_WS * sizeof(bf16_t);
-    hipLaunchKernelGGL((sconv_apply_kernel<T, 4>), dim3((unsigned)gx, Cout_p / 128), dim3(256), lds, s,
-                       (const T*)x, nbr, w_hi, w_lo, bias, (T*)out, n_dst, K, Cin, Cout, Cin_p, Cout_p);
+    hipLaunchKernelGGL((sconv_apply_kernel<T, 4, FUSED>), dim3((unsigned)gx, Cout_p / 128), dim3(256), lds, s,
+                       (const T*)x, nbr, w_hi, w_lo, bias, (T*)out, n_dst, K, Cin, Cout, Cin_p, Cout_p,
+                       (const T*)residual, slope);
   } else {
     const size_t lds = (size_t)2 * (SPLIT ? 2 : 1) * SC_TILE * SC_WS * sizeof(bf16_t);
-    hipLaunchKernelGGL((sconv_apply_kernel<T, 2>), dim3((unsigned)gx, Cout_p / SC_TILE), dim3(256), lds, s,
-                       (const T*)x, nbr, w_hi, w_lo, bias, (T*)out, n_dst, K, Cin, Cout, Cin_p, Cout_p);
+    hipLaunchKernelGGL((sconv_apply_kernel<T, 2, FUSED>), dim3((unsigned)gx, Cout_p / SC_TILE), dim3(256), lds, s,
+                       (const T*)x, nbr, w_hi, w_lo, bias, (T*)out, n_dst, K, Cin, Cout, Cin_p, Cout_p,
+                       (const T*)residual, slope);
   }
   DVA_CHECK_LAUNCH();
   return DVA_OK;
+}
+
+template <typename T>
+static int sconv_apply_impl(const void* x, const int32_t* nbr, const float* W, const float* bias, void* out,
+                            int64_t n_dst, int K, int Cin, int Cout, int mode, void* ws, hipStream_t s) {
+  sconv_pack(W, K, Cin, Cout, mode, sizeof(T) == 4, ws, s);
+  return sconv_launch<T, false>(x, nbr, ws, bias, nullptr, 1.f, out, n_dst, K, Cin, Cout, s);
 }
 
 }  // namespace dva
@@ -424,6 +465,38 @@ int dva_sparse_conv_apply(const void* x, const int32_t* nbr, const float* W, con
   return dtype == DVA_F32
              ? sconv_apply_impl<float>(x, nbr, W, bias, out, n_dst, K, Cin, Cout, mode, workspace, s)
              : sconv_apply_impl<bf16_t>(x, nbr, W, bias, out, n_dst, K, Cin, Cout, mode, workspace, s);
+}
+
+int dva_sparse_conv_pack_weights(const float* W, int32_t K, int32_t Cin, int32_t Cout, int32_t mode, int32_t dtype,
+                                 void* packed, int64_t packed_bytes, void* stream) {
+  if (K <= 0 || Cin <= 0 || Cout <= 0 || (mode != 0 && mode != 1)) return DVA_ERR_INVALID;
+  if (dtype == DVA_F16) return DVA_ERR_UNSUPPORTED;
+  if (dtype != DVA_F32 && dtype != DVA_BF16) return DVA_ERR_INVALID;
+  if (Cin % 16 != 0 || Cout % 16 != 0) return DVA_ERR_UNSUPPORTED;  // the host pads the channel counts
+  if (!W || !packed || ((uintptr_t)packed & 15)) return DVA_ERR_INVALID;
+  if (packed_bytes < dva_sparse_conv_workspace_bytes(K, Cin, Cout, dtype)) return DVA_ERR_INVALID;
+  sconv_pack(W, K, Cin, Cout, mode, dtype == DVA_F32, packed, (hipStream_t)stream);
+  DVA_CHECK_LAUNCH();
+  return DVA_OK;
+}
+
+int dva_sparse_conv_apply_packed(const void* x, const int32_t* nbr, const void* packed, int64_t packed_bytes,
+                                 const float* bias, const void* residual, float slope, void* out, int64_t n_src,
+                                 int64_t n_dst, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* stream) {
+  if (n_src < 0 || n_dst < 0 || K <= 0 || Cin <= 0 || Cout <= 0 || !(slope - slope == 0.f)) return DVA_ERR_INVALID;
+  if (dtype == DVA_F16) return DVA_ERR_UNSUPPORTED;
+  if (dtype != DVA_F32 && dtype != DVA_BF16) return DVA_ERR_INVALID;
+  if (Cin % 16 != 0 || Cout % 16 != 0) return DVA_ERR_UNSUPPORTED;  // the host pads the channel counts
+  if (n_src > 0x7fffffffLL || n_dst > 0x7fffffffLL / K) return DVA_ERR_UNSUPPORTED;
+  if (n_dst == 0) return DVA_OK;
+  if (!nbr || !packed || !out || (n_src > 0 && !x) || residual == out) return DVA_ERR_INVALID;
+  if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)packed | (uintptr_t)residual) & 15) return DVA_ERR_INVALID;
+  if (packed_bytes < dva_sparse_conv_workspace_bytes(K, Cin, Cout, dtype)) return DVA_ERR_INVALID;
+  if (n_src == 0) return DVA_ERR_INVALID;  // missing neighbours read the (masked) row 0: it must exist
+  hipStream_t s = (hipStream_t)stream;
+  return dtype == DVA_F32
+             ? sconv_launch<float, true>(x, nbr, packed, bias, residual, slope, out, n_dst, K, Cin, Cout, s)
+             : sconv_launch<bf16_t, true>(x, nbr, packed, bias, residual, slope, out, n_dst, K, Cin, Cout, s);
 }
 
 int dva_sparse_conv_wgrad(const void* x, const int32_t* nbr, const void* grad_out, float* grad_W, int64_t n_src,

@@ -2452,6 +2452,93 @@ def sparse_conv(x, W, bias, nbr, nbr_t):
     return _SparseConv.apply(x, W, bias, nbr, nbr_t)
 
 
+def sparse_conv_feature_dtype(x):
+    """The dtype ``sparse_conv`` and ``sparse_conv_fused`` take the features ``x`` in: the autocast rule above."""
+    if torch.is_autocast_enabled() and x.is_cuda:
+        return torch.bfloat16 if torch.get_autocast_dtype('cuda') == torch.bfloat16 else torch.float32
+    return x.dtype
+
+
+class PackedSparseConvWeights:
+    """The constant weights of one sparse convolution as ``sconv_apply_kernel`` reads them (bf16 ``w_hi | w_lo``
+    tiles): ``buf`` uint8, with ``K``, ``cin``, ``cout``, the widths padded to 16 ``cin_p`` / ``cout_p`` and the
+    feature ``dtype`` the layout was made for."""
+    __slots__ = ("buf", "K", "cin", "cout", "cin_p", "cout_p", "dtype")
+
+    def __init__(self, buf, K, cin, cout, cin_p, cout_p, dtype):
+        self.buf, self.K, self.cin, self.cout, self.cin_p, self.cout_p, self.dtype = buf, K, cin, cout, cin_p, cout_p, dtype
+
+
+def sparse_conv_pack(W, dtype):
+    """Pack W fp32 [K, Cin, Cout] once for ``sparse_conv_fused`` on features of ``dtype`` (fp32 or bf16)."""
+    lib = _lib.load()
+    require_device(W)
+    if W.dim() != 3:
+        raise ValueError(f"ops.sparse_conv_pack: W must be [K, Cin, Cout], got {tuple(W.shape)}")
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"ops.sparse_conv_pack: the kernels take fp32 or bf16 features, not {dtype}")
+    K, cin, cout = W.shape
+    cin_p, cout_p = _pad16(cin), _pad16(cout)
+    Wf = W.detach().float()
+    if cin_p != cin or cout_p != cout:
+        Wf = torch.nn.functional.pad(Wf, (0, cout_p - cout, 0, cin_p - cin))
+    Wf = Wf.contiguous()
+    code = _lib.DVA_F32 if dtype == torch.float32 else _lib.DVA_BF16
+    buf, nbytes = _lib.workspace("dva_sparse_conv_workspace_bytes", W.device, K, cin_p, cout_p, code)
+    with _timed("sparse_conv_pack", K * cin_p * cout_p * 4 + nbytes):
+        check(lib.dva_sparse_conv_pack_weights(ptr(Wf), K, cin_p, cout_p, 0, code, ptr(buf), nbytes, stream_of(Wf)),
+              "dva_sparse_conv_pack_weights")
+    return PackedSparseConvWeights(buf, K, cin, cout, cin_p, cout_p, dtype)
+
+
+def sparse_conv_fused(x, packed, bias, nbr, residual=None, slope=1.0):
+    """Inference form of ``sparse_conv`` over packed constant weights (``sparse_conv_pack``), with the activation and
+    the residual sum in the kernel's epilogue: ``out = T(leaky(conv(x) + bias, slope) + residual)``, fp32 steps, one
+    rounding.  x [n_src, Cin], bias fp32 [Cout] or None, nbr int32 [K, n_dst], residual [n_dst, Cout] or None ->
+    [n_dst, Cout].  No autograd.  The autocast rule of ``sparse_conv`` holds; ``packed`` must be of that dtype."""
+    lib = _lib.load()
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, bias, residual)):
+        raise RuntimeError("ops.sparse_conv_fused has no backward: call it under torch.no_grad() or on detached "
+                           "inputs (ops.sparse_conv is the differentiable form)")
+    require_device(x, packed.buf, nbr, bias, residual)
+    assert nbr.dtype == torch.int32 and nbr.dim() == 2, "nbr is the int32 [K, n_dst] map of voxel_kernel_map"
+    nbr = nbr.contiguous()
+    x = x.detach().to(sparse_conv_feature_dtype(x))
+    if x.dtype != packed.dtype:
+        raise TypeError(f"ops.sparse_conv_fused: weights packed for {packed.dtype} features, got {x.dtype}")
+    K, n_dst = nbr.shape
+    assert K == packed.K, f"the kernel map has {K} offsets, the packed weights {packed.K}"
+    assert x.shape[1] == packed.cin, f"features have {x.shape[1]} channels, the kernel expects {packed.cin}"
+    slope = float(slope)
+    cout, cin_p, cout_p = packed.cout, packed.cin_p, packed.cout_p
+    if residual is not None:
+        assert residual.shape == (n_dst, cout), f"residual {tuple(residual.shape)} for an output {(n_dst, cout)}"
+        residual = residual.detach().to(x.dtype)
+    bias = None if bias is None else bias.detach().float()
+    if x.shape[0] == 0 or n_dst == 0:
+        v = torch.zeros((n_dst, cout), dtype=torch.float32, device=x.device)
+        if bias is not None:
+            v = v + bias
+        v = torch.where(v >= 0, v, slope * v)
+        return (v if residual is None else v + residual.float()).to(x.dtype)
+    if cin_p != packed.cin:
+        x = torch.nn.functional.pad(x, (0, cin_p - packed.cin))
+    if cout_p != cout:
+        bias = None if bias is None else torch.nn.functional.pad(bias, (0, cout_p - cout))
+        residual = None if residual is None else torch.nn.functional.pad(residual, (0, cout_p - cout))
+    x = x.contiguous()
+    bias = None if bias is None else bias.contiguous()
+    residual = None if residual is None else residual.contiguous()
+    out = torch.empty((n_dst, cout_p), dtype=x.dtype, device=x.device)
+    s = x.element_size()
+    with _timed(f"sparse_conv_fused{SPARSE_CONV_TIMER_SHAPES and f'[{K}x{cin_p}->{cout_p}@{n_dst}]' or ''}",
+                n_dst * (K * 4 + cout_p * s * (1 if residual is None else 2)) + x.shape[0] * cin_p * s):
+        check(lib.dva_sparse_conv_apply_packed(ptr(x), ptr(nbr), ptr(packed.buf), packed.buf.numel(), ptr(bias),
+                                               ptr(residual), slope, ptr(out), x.shape[0], n_dst, K, cin_p, cout_p,
+                                               dtype_code(x), stream_of(x)), "dva_sparse_conv_apply_packed")
+    return out if cout_p == cout else out[:, :cout].contiguous()
+
+
 # ---------------------------------------------------------------------------------------------
 # neighbourhood-based mapping features (data_transform/multimodal/image.py:431-612)
 # ---------------------------------------------------------------------------------------------

@@ -920,6 +920,18 @@ int dva_voxel_parent_index(const int32_t* in_coords, int64_t n_in, const int32_t
  *
  * dva_sparse_conv_wgrad: grad_W[k][a][b] = sum_j x[nbr[k][j]][a] * grad_out[j][b], fp32 [K, Cin, Cout],
  * zeroed by the call, accumulated with fp32 atomics (summation order not fixed).
+ *
+ * Inference with constant weights (since dva_version 332):
+ * dva_sparse_conv_pack_weights: the re-pack dva_sparse_conv_apply runs on every call, once, into the caller's
+ * buffer `packed` (16-byte aligned, packed_bytes >= dva_sparse_conv_workspace_bytes(K, Cin, Cout, dtype); the
+ * layout depends on `dtype`, the feature type of the later calls).  W and mode as above.
+ * dva_sparse_conv_apply_packed: the mode 0 convolution from that buffer, no workspace and no re-pack launch,
+ * with the activation and the residual sum folded into the store.  Per output element, in fp32, every step
+ * rounded on its own (no fused multiply-add), then ONE rounding to `dtype`:
+ *   v = acc + bias[n];   v = v >= 0 ? v : slope * v;   v = v + residual[j][n];   out[j][n] = dtype(v)
+ * slope finite (1: no activation, 0: ReLU); residual [n_dst, Cout] in `dtype`, 16-byte aligned, nullable, must
+ * not alias out.  A destination without any neighbour gets act(bias) + residual.  Deterministic, no atomics.
+ * Both validate as dva_sparse_conv_apply does, in its order, before any HIP call.
  * ------------------------------------------------------------------------------------------ */
 int dva_voxel_kernel_map(const int32_t* src_coords, int64_t n_src, const int32_t* dst_coords, int64_t n_dst,
                          const int32_t* offsets, int32_t K, int32_t* nbr, void* workspace,
@@ -930,6 +942,11 @@ int dva_sparse_conv_apply(const void* x, const int32_t* nbr, const float* W, con
                           int32_t dtype, void* workspace, int64_t workspace_bytes, void* stream);
 int dva_sparse_conv_wgrad(const void* x, const int32_t* nbr, const void* grad_out, float* grad_W, int64_t n_src,
                           int64_t n_dst, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* stream);
+int dva_sparse_conv_pack_weights(const float* W, int32_t K, int32_t Cin, int32_t Cout, int32_t mode, int32_t dtype,
+                                 void* packed, int64_t packed_bytes, void* stream);
+int dva_sparse_conv_apply_packed(const void* x, const int32_t* nbr, const void* packed, int64_t packed_bytes,
+                                 const float* bias, const void* residual, float slope, void* out, int64_t n_src,
+                                 int64_t n_dst, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------ *
  * Neighbourhood-based mapping features (core/data_transform/multimodal/image.py:431-612): exact k nearest

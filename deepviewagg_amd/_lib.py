@@ -249,6 +249,12 @@ SIGNATURES = {
     "dva_sparse_conv_pack_weights": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     "dva_sparse_conv_apply_packed": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _f32, _vp, _i64, _i64, _i32, _i32,
                                                     _i32, _i32, _vp]),
+    # parts, widths: host arrays (ctypes arrays of c_void_p / c_int32)
+    "dva_sparse_conv_apply_parts": (ctypes.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32,
+                                                   _vp, _i64, _vp]),
+    "dva_sparse_conv_apply_packed_parts": (ctypes.c_int, [_vp, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _f32, _vp, _i64,
+                                                          _i64, _i32, _i32, _i32, _vp]),
+    "dva_sparse_conv_wgrad_parts": (ctypes.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     "dva_knn_workspace_bytes": (ctypes.c_int64, [_i64]),
     "dva_knn": (ctypes.c_int, [_vp, _i64, _vp, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "dva_view_occlusion": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),

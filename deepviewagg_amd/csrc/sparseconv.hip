@@ -118,6 +118,33 @@ template <> struct OutStore<bf16_t> {
   }
 };
 
+// The features as up to SC_MAX_PARTS tensors on the same voxels, read as their channel concatenation without
+// writing it: part p is [n_src, width[p]] of T (width a multiple of 16) and owns the concatenated channels
+// start[p] .. start[p] + width[p] - 1.  The table travels in the kernel arguments (no device-side copy); unused
+// slots have start = INT_MAX.  A 16-channel piece that begins at a multiple of 16 lies inside one part.
+constexpr int SC_MAX_PARTS = 4;
+template <typename T> struct ScParts {
+  const T* base[SC_MAX_PARTS];
+  int32_t width[SC_MAX_PARTS];
+  int32_t start[SC_MAX_PARTS];
+  // address of concatenated channel c (a multiple of 16) of row `row`: selects, no indexed access to the table
+  __device__ __forceinline__ const T* at(int row, int c) const {
+    const T* b = base[0];
+    int w = width[0], s = 0;
+#pragma unroll
+    for (int p = 1; p < SC_MAX_PARTS; ++p) {
+      const bool in = c >= start[p];
+      b = in ? base[p] : b;
+      w = in ? width[p] : w;
+      s = in ? start[p] : s;
+    }
+    return b + (int64_t)row * w + (c - s);
+  }
+};
+// what a kernel takes as its features: one tensor (the forms of the single-source entries), or the parts
+template <typename T, bool PARTS> struct ScSrc { typedef const T* __restrict__ type; };
+template <typename T> struct ScSrc<T, true> { typedef ScParts<T> type; };
+
 // NT = 32-channel output blocks per wavefront (2: 64 output channels per workgroup, 4: 128 -- wide layers
 // gather each input row once per 128 output channels instead of once per 64)
 // FUSED (inference with constant weights, dva_sparse_conv_apply_packed): the epilogue applies the activation and
@@ -125,8 +152,12 @@ template <> struct OutStore<bf16_t> {
 //   v = acc + bias;  v = v >= 0 ? v : slope * v;  v = v + float(residual[j, n]);  out = T(v)
 // each a separately rounded fp32 operation (the intrinsics hold that under any contraction flag); `residual`
 // ([n_dst, Cout] of T, nullable) is read in the 4-element groups the store writes and must not alias `out`.
-template <typename T, int NT, bool FUSED>
-__global__ __launch_bounds__(256, NT == 4 ? 2 : 1) void sconv_apply_kernel(const T* __restrict__ x, const int32_t* __restrict__ nbr,
+// PARTS (dva_sparse_conv_apply_parts / _packed_parts): x is an ScParts table and Cin the summed width.  The
+// 16-channel steps run in concatenation order, so the accumulation order is that of the materialised tensor;
+// a 64-channel chunk may straddle two parts, a step never does, and c0 + 16 m is wave-uniform: the part of a
+// step is picked with scalar selects.
+template <typename T, int NT, bool FUSED, bool PARTS = false>
+__global__ __launch_bounds__(256, NT == 4 ? 2 : 1) void sconv_apply_kernel(typename ScSrc<T, PARTS>::type x, const int32_t* __restrict__ nbr,
                                                            const bf16_t* __restrict__ w_hi,
                                                            const bf16_t* __restrict__ w_lo,
                                                            const float* __restrict__ bias, T* __restrict__ out,
@@ -183,8 +214,12 @@ __global__ __launch_bounds__(256, NT == 4 ? 2 : 1) void sconv_apply_kernel(const
     for (int m = 0; m < 4; ++m)
       if (m < msteps) {
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
-          xf[t][m].load(x + (int64_t)max(idx[t], 0) * Cin + c0 + 16 * m + 8 * h);
+        for (int t = 0; t < 2; ++t) {
+          if constexpr (PARTS)
+            xf[t][m].load(x.at(max(idx[t], 0), c0 + 16 * m) + 8 * h);
+          else
+            xf[t][m].load(x + (int64_t)max(idx[t], 0) * Cin + c0 + 16 * m + 8 * h);
+        }
       }
     const bf16_t* wb = s_w + (size_t)((it & 1) * NB) * NROWS * SC_WS;
 #pragma unroll
@@ -299,8 +334,10 @@ __device__ __forceinline__ void sc_wave_sync() {
   __builtin_amdgcn_wave_barrier();
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void sconv_wgrad_kernel(const T* __restrict__ x, const int32_t* __restrict__ nbr,
+// PARTS: x is an ScParts table, Cin the summed width and dW [K, Cin, Cout] in concatenation order; the 16
+// channels a lane loads begin at a multiple of 16, so they lie in one part (picked per lane: h differs).
+template <typename T, bool PARTS = false>
+__global__ __launch_bounds__(256) void sconv_wgrad_kernel(typename ScSrc<T, PARTS>::type x, const int32_t* __restrict__ nbr,
                                                            const T* __restrict__ dout, float* __restrict__ dW,
                                                            int64_t n_dst, int Cin, int Cout, int cout_tiles) {
   constexpr bool SPLIT = sizeof(T) == 4;
@@ -336,7 +373,11 @@ __global__ __launch_bounds__(256) void sconv_wgrad_kernel(const T* __restrict__ 
     Row16<T> xr[2], dr[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-      if (16 * h < xa[u]) xr[u].load(x + (int64_t)max(idx, 0) * Cin + a0 + 32 * u + 16 * h);
+      if constexpr (PARTS) {
+        if (16 * h < xa[u]) xr[u].load(x.at(max(idx, 0), a0 + 32 * u + 16 * h));
+      } else {
+        if (16 * h < xa[u]) xr[u].load(x + (int64_t)max(idx, 0) * Cin + a0 + 32 * u + 16 * h);
+      }
       if (16 * h < ob[u]) dr[u].load(dout + (ok ? j : 0) * Cout + b0 + 32 * u + 16 * h);
     }
 #pragma unroll
@@ -435,6 +476,74 @@ static int sconv_apply_impl(const void* x, const int32_t* nbr, const float* W, c
   return sconv_launch<T, false>(x, nbr, ws, bias, nullptr, 1.f, out, n_dst, K, Cin, Cout, s);
 }
 
+// ---- the multi-part entries ---------------------------------------------------------------------
+template <typename T>
+static ScParts<T> sconv_parts_table(const void* const* parts, const int32_t* widths, int P) {
+  ScParts<T> t;
+  int start = 0;
+  for (int p = 0; p < SC_MAX_PARTS; ++p) {
+    t.base[p] = p < P ? (const T*)parts[p] : nullptr;
+    t.width[p] = p < P ? widths[p] : 0;
+    t.start[p] = p < P ? start : 0x7fffffff;
+    if (p < P) start += widths[p];
+  }
+  return t;
+}
+
+template <typename T, bool FUSED>
+static int sconv_launch_parts(const void* const* parts, const int32_t* widths, int P, const int32_t* nbr,
+                              const void* packed, const float* bias, const void* residual, float slope, void* out,
+                              int64_t n_dst, int K, int Cin, int Cout, hipStream_t s) {
+  constexpr bool SPLIT = sizeof(T) == 4;
+  const ScParts<T> x = sconv_parts_table<T>(parts, widths, P);
+  const int Cin_p = pad_tile(Cin), Cout_p = pad_out(Cout);
+  const bf16_t* w_hi = (const bf16_t*)packed;
+  const bf16_t* w_lo = SPLIT ? w_hi + (int64_t)K * Cin_p * Cout_p : nullptr;
+  const int64_t gx = (n_dst + 255) / 256;
+  if (Cout_p >= 128) {
+    const size_t lds = (size_t)2 * (SPLIT ? 2 : 1) * 128 * SC_WS * sizeof(bf16_t);
+    hipLaunchKernelGGL((sconv_apply_kernel<T, 4, FUSED, true>), dim3((unsigned)gx, Cout_p / 128), dim3(256), lds, s,
+                       x, nbr, w_hi, w_lo, bias, (T*)out, n_dst, K, Cin, Cout, Cin_p, Cout_p, (const T*)residual,
+                       slope);
+  } else {
+    const size_t lds = (size_t)2 * (SPLIT ? 2 : 1) * SC_TILE * SC_WS * sizeof(bf16_t);
+    hipLaunchKernelGGL((sconv_apply_kernel<T, 2, FUSED, true>), dim3((unsigned)gx, Cout_p / SC_TILE), dim3(256), lds,
+                       s, x, nbr, w_hi, w_lo, bias, (T*)out, n_dst, K, Cin, Cout, Cin_p, Cout_p, (const T*)residual,
+                       slope);
+  }
+  DVA_CHECK_LAUNCH();
+  return DVA_OK;
+}
+
+// The checks the three multi-part entries share, up to the first pointer: the scalars, the dtype, the number of
+// parts and their widths (a host array, read here), then the 2^31 rules.  *Cin = the summed width.
+static int sconv_parts_check(const int32_t* widths, int32_t P, int64_t n_src, int64_t n_dst, int32_t K, int32_t Cout,
+                             int32_t dtype, int* Cin) {
+  if (n_src < 0 || n_dst < 0 || K <= 0 || Cout <= 0 || P <= 0 || !widths) return DVA_ERR_INVALID;
+  if (dtype == DVA_F16) return DVA_ERR_UNSUPPORTED;  // fp32 / bf16 sparse convolution only
+  if (dtype != DVA_F32 && dtype != DVA_BF16) return DVA_ERR_INVALID;
+  if (P > SC_MAX_PARTS) return DVA_ERR_UNSUPPORTED;
+  int64_t sum = 0;
+  for (int p = 0; p < P; ++p) {
+    if (widths[p] <= 0) return DVA_ERR_INVALID;
+    sum += widths[p];
+  }
+  for (int p = 0; p < P; ++p)
+    if (widths[p] % 16 != 0) return DVA_ERR_UNSUPPORTED;  // the host pads a narrow part, alone
+  if (Cout % 16 != 0 || sum > 0x7fffffffLL - SC_TILE) return DVA_ERR_UNSUPPORTED;
+  if (n_src > 0x7fffffffLL || n_dst > 0x7fffffffLL / K) return DVA_ERR_UNSUPPORTED;
+  *Cin = (int)sum;
+  return DVA_OK;
+}
+
+// null (a part may only be null when there are no source rows) or not 16-byte aligned
+static bool sconv_parts_bad(const void* const* parts, int P, int64_t n_src) {
+  if (!parts) return true;
+  for (int p = 0; p < P; ++p)
+    if ((n_src > 0 && !parts[p]) || ((uintptr_t)parts[p] & 15)) return true;
+  return false;
+}
+
 }  // namespace dva
 
 using namespace dva;
@@ -526,6 +635,79 @@ int dva_sparse_conv_wgrad(const void* x, const int32_t* nbr, const void* grad_ou
   else
     hipLaunchKernelGGL((sconv_wgrad_kernel<bf16_t>), grid, dim3(256), lds, s, (const bf16_t*)x, nbr,
                        (const bf16_t*)grad_out, grad_W, n_dst, Cin, Cout, cout_tiles);
+  DVA_CHECK_LAUNCH();
+  return DVA_OK;
+}
+
+int dva_sparse_conv_apply_parts(const void* const* parts, const int32_t* widths, int32_t P, const int32_t* nbr,
+                                const float* W, const float* bias, void* out, int64_t n_src, int64_t n_dst,
+                                int32_t K, int32_t Cout, int32_t dtype, void* workspace, int64_t workspace_bytes,
+                                void* stream) {
+  int Cin = 0;
+  const int rc = sconv_parts_check(widths, P, n_src, n_dst, K, Cout, dtype, &Cin);
+  if (rc != DVA_OK) return rc;
+  if (n_dst == 0) return DVA_OK;
+  if (!nbr || !W || !out || !workspace || sconv_parts_bad(parts, P, n_src)) return DVA_ERR_INVALID;
+  if (workspace_bytes < dva_sparse_conv_workspace_bytes(K, Cin, Cout, dtype)) return DVA_ERR_INVALID;
+  if (((uintptr_t)out | (uintptr_t)workspace) & 15) return DVA_ERR_INVALID;
+  if (n_src == 0) return DVA_ERR_INVALID;  // missing neighbours read the (masked) row 0: it must exist
+  hipStream_t s = (hipStream_t)stream;
+  sconv_pack(W, K, Cin, Cout, 0, dtype == DVA_F32, workspace, s);
+  return dtype == DVA_F32 ? sconv_launch_parts<float, false>(parts, widths, P, nbr, workspace, bias, nullptr, 1.f,
+                                                              out, n_dst, K, Cin, Cout, s)
+                          : sconv_launch_parts<bf16_t, false>(parts, widths, P, nbr, workspace, bias, nullptr, 1.f,
+                                                               out, n_dst, K, Cin, Cout, s);
+}
+
+int dva_sparse_conv_apply_packed_parts(const void* const* parts, const int32_t* widths, int32_t P,
+                                       const int32_t* nbr, const void* packed, int64_t packed_bytes,
+                                       const float* bias, const void* residual, float slope, void* out,
+                                       int64_t n_src, int64_t n_dst, int32_t K, int32_t Cout, int32_t dtype,
+                                       void* stream) {
+  if (!(slope - slope == 0.f)) return DVA_ERR_INVALID;
+  int Cin = 0;
+  const int rc = sconv_parts_check(widths, P, n_src, n_dst, K, Cout, dtype, &Cin);
+  if (rc != DVA_OK) return rc;
+  if (n_dst == 0) return DVA_OK;
+  if (!nbr || !packed || !out || sconv_parts_bad(parts, P, n_src) || residual == out) return DVA_ERR_INVALID;
+  if (((uintptr_t)out | (uintptr_t)packed | (uintptr_t)residual) & 15) return DVA_ERR_INVALID;
+  if (packed_bytes < dva_sparse_conv_workspace_bytes(K, Cin, Cout, dtype)) return DVA_ERR_INVALID;
+  if (n_src == 0) return DVA_ERR_INVALID;  // missing neighbours read the (masked) row 0: it must exist
+  hipStream_t s = (hipStream_t)stream;
+  return dtype == DVA_F32 ? sconv_launch_parts<float, true>(parts, widths, P, nbr, packed, bias, residual, slope, out,
+                                                             n_dst, K, Cin, Cout, s)
+                          : sconv_launch_parts<bf16_t, true>(parts, widths, P, nbr, packed, bias, residual, slope,
+                                                              out, n_dst, K, Cin, Cout, s);
+}
+
+int dva_sparse_conv_wgrad_parts(const void* const* parts, const int32_t* widths, int32_t P, const int32_t* nbr,
+                                const void* grad_out, float* grad_W, int64_t n_src, int64_t n_dst, int32_t K,
+                                int32_t Cout, int32_t dtype, void* stream) {
+  int Cin = 0;
+  const int rc = sconv_parts_check(widths, P, n_src, n_dst, K, Cout, dtype, &Cin);
+  if (rc != DVA_OK) return rc;
+  if (!grad_W) return DVA_ERR_INVALID;
+  hipStream_t s = (hipStream_t)stream;
+  zero_words(grad_W, (int64_t)K * Cin * Cout, s);
+  DVA_CHECK_LAUNCH();
+  if (n_dst == 0 || n_src == 0) return DVA_OK;
+  if (!nbr || !grad_out || sconv_parts_bad(parts, P, n_src)) return DVA_ERR_INVALID;
+  if ((uintptr_t)grad_out & 15) return DVA_ERR_INVALID;
+  const int cin_tiles = pad_tile(Cin) / SC_TILE, cout_tiles = pad_tile(Cout) / SC_TILE;
+  const int64_t tiles = (n_dst + 31) / 32;
+  int64_t gx = (tiles + 4 * 16 - 1) / (4 * 16);  // as dva_sparse_conv_wgrad
+  if (gx > 64) gx = 64;
+  if (gx < 1) gx = 1;
+  const dim3 grid((unsigned)gx, (unsigned)K, (unsigned)(cin_tiles * cout_tiles));
+  const size_t lds = (size_t)4 * 4 * (dtype == DVA_F32 ? 2 : 1) * 32 * SC_TSB * sizeof(bf16_t);
+  if (dtype == DVA_F32)
+    hipLaunchKernelGGL((sconv_wgrad_kernel<float, true>), grid, dim3(256), lds, s,
+                       sconv_parts_table<float>(parts, widths, P), nbr, (const float*)grad_out, grad_W, n_dst, Cin,
+                       Cout, cout_tiles);
+  else
+    hipLaunchKernelGGL((sconv_wgrad_kernel<bf16_t, true>), grid, dim3(256), lds, s,
+                       sconv_parts_table<bf16_t>(parts, widths, P), nbr, (const bf16_t*)grad_out, grad_W, n_dst, Cin,
+                       Cout, cout_tiles);
   DVA_CHECK_LAUNCH();
   return DVA_OK;
 }

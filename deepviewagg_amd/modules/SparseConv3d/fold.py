@@ -58,7 +58,8 @@ class _Frozen(nn.Module):
 class FoldedConv(_Frozen):
     """``Conv3d`` / ``Conv3dTranspose`` -> ``BatchNorm`` [-> ``ReLU``] as one launch:
     ``out = leaky(conv(x; W') + b', slope) [+ residual]``.  ``weight`` [K, Cin, Cout] and ``bias`` [Cout] are buffers;
-    the packed operand of the kernel is built on the first forward on a device and kept per (device, feature dtype).
+    the packed operand of the kernel is built on the first forward on a device and kept per (device, feature dtype,
+    part widths of a lazy concatenation or None).
     A 1x1x1 stride-1 layer runs the same kernel with K = 1 over the identity map, cached in ``x.kernel_maps`` under the
     key such a convolution has."""
 
@@ -88,10 +89,10 @@ class FoldedConv(_Frozen):
         self._packed = {}
         return super()._load_from_state_dict(*args, **kwargs)
 
-    def _operand(self, dtype):
-        key = (self.weight.device, dtype)
+    def _operand(self, dtype, widths=None):
+        key = (self.weight.device, dtype, widths)
         if key not in self._packed:
-            self._packed[key] = ops.sparse_conv_pack(self.weight, dtype)
+            self._packed[key] = ops.sparse_conv_pack(self.weight, dtype, parts=widths)
         return self._packed[key]
 
     def forward(self, x, residual=None):
@@ -103,8 +104,15 @@ class FoldedConv(_Frozen):
             nbr, out_coords, out_stride = x.kernel_maps[key][0], x.C, x.s
         else:
             nbr, _, out_coords, out_stride = self._maps(x)
-        f = ops.sparse_conv_fused(x.F, self._operand(ops.sparse_conv_feature_dtype(x.F)), self.bias, nbr,
-                                  residual=residual, slope=self.slope)
+        parts = snn.feature_parts(x)     # a lazy concatenation (snn.cat(..., lazy=True)): the kernel reads the parts
+        if parts is None:
+            f = ops.sparse_conv_fused(x.F, self._operand(ops.sparse_conv_feature_dtype(x.F)), self.bias, nbr,
+                                      residual=residual, slope=self.slope)
+        else:
+            dtype = ops.sparse_conv_parts_dtype(parts)
+            widths = tuple(p.shape[1] for p in parts)
+            f = ops.sparse_conv_fused(list(parts), self._operand(dtype, widths), self.bias, nbr, residual=residual,
+                                      slope=self.slope)
         return snn.SparseVoxelTensor(f, out_coords, out_stride, x.coord_maps, x.kernel_maps)
 
 

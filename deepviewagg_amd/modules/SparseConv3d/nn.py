@@ -18,6 +18,7 @@ consumer re-joins coordinates through ``coord_maps`` / ``dva_voxel_parent_index`
 
 The convolution itself is ``csrc/sparseconv.hip`` (output-stationary gather-MFMA, no scatter pass).
 """
+import functools
 import math
 
 import numpy as np
@@ -27,7 +28,7 @@ from torch import nn
 from ... import ops
 from ..multimodal.pooling import batchnorm_act_rows
 
-__all__ = ["cat", "Conv3d", "Conv3dTranspose", "ReLU", "SparseTensor", "BatchNorm"]
+__all__ = ["cat", "Conv3d", "Conv3dTranspose", "ReLU", "SparseTensor", "BatchNorm", "LazyCatTensor"]
 
 # modules/SparseConv3d/nn/__init__.py:28-60: the reference switches between two sparse libraries; here there
 # is one backend, which carries the torchsparse field names (F, C, s, coord_maps) the multimodal blocks read.
@@ -79,9 +80,75 @@ def SparseTensor(feats, coordinates, batch, device=torch.device("cpu")):
     return SparseVoxelTensor(feats, coords).to(device)
 
 
-def cat(*args, dim=1):
-    """Channel concatenation of tensors on the same voxels (nn/torchsparse.py:57-58)."""
+class LazyCatTensor(SparseVoxelTensor):
+    """A channel concatenation that is not written: ``parts`` holds the feature tensors, which ``Conv3d`` /
+    ``Conv3dTranspose`` and their folded twins hand to the convolution kernel as they are
+    (``ops.sparse_conv`` on a list).  ``F`` is a property: the first read runs ``torch.cat(parts, 1)`` and keeps it, so
+    every other consumer sees the tensor ``cat`` returns today, bit for bit; assigning ``F`` drops the parts."""
+
+    def __init__(self, parts, coords, stride=1, coord_maps=None, kernel_maps=None):
+        parts = tuple(parts)
+        assert parts and all(p.dim() == 2 and p.shape[0] == parts[0].shape[0] for p in parts)
+        self._parts, self._feats = parts, None
+        self.C, self.s = coords, stride
+        self.coord_maps = coord_maps if coord_maps is not None else {}
+        self.kernel_maps = kernel_maps if kernel_maps is not None else {}
+        self.coord_maps.setdefault(stride, coords)
+
+    @property
+    def parts(self):
+        """The feature tensors in concatenation order, or None once ``F`` has been assigned."""
+        return self._parts
+
+    @property
+    def num_channels(self):
+        return self._feats.shape[1] if self._parts is None else sum(p.shape[1] for p in self._parts)
+
+    @property
+    def F(self):
+        if self._feats is None:
+            self._feats = torch.cat(self._parts, dim=1)
+        return self._feats
+
+    @F.setter
+    def F(self, feats):
+        self._parts, self._feats = None, feats
+
+    def to(self, device):
+        if self._parts is not None:
+            self._parts = tuple(p.to(device) for p in self._parts)
+        if self._feats is not None:
+            self._feats = self._feats.to(device)
+        self.C = self.C.to(device)
+        self.coord_maps = {k: v.to(device) for k, v in self.coord_maps.items()}
+        return self
+
+
+MAX_PARTS = ops.SPARSE_CONV_MAX_PARTS   # what one convolution launch takes
+
+
+def feature_parts(x):
+    """The list ``ops.sparse_conv`` takes for tensor ``x``: its parts when it is a lazy concatenation of more than one
+    tensor and of at most ``MAX_PARTS``, else None (read ``x.F``)."""
+    parts = getattr(x, "parts", None)
+    if parts is None or not 1 < len(parts) <= MAX_PARTS:
+        return None
+    return parts
+
+
+LAZY_CAT = False    # cat(..., lazy=None): keep the parts (LazyCatTensor) instead of writing the concatenation
+
+
+def cat(*args, dim=1, lazy=None):
+    """Channel concatenation of tensors on the same voxels (nn/torchsparse.py:57-58).  ``lazy`` (default: the module
+    switch ``LAZY_CAT``): return a ``LazyCatTensor`` over the feature tensors; the convolutions read them in place."""
     assert dim == 1
+    if LAZY_CAT if lazy is None else lazy:
+        parts = []
+        for a in args:
+            own = feature_parts(a)
+            parts.extend(own if own is not None else [a.F])
+        return LazyCatTensor(parts, args[0].C, args[0].s, args[0].coord_maps, args[0].kernel_maps)
     return args[0].like(torch.cat([a.F for a in args], dim=1))
 
 
@@ -114,6 +181,45 @@ def downsample_coords(coords, ratio):
     z = (uq // (sx * sy)) % sz
     b = uq // (sx * sy * sz)
     return (torch.stack([x, y, z, b], 1) + lo).int().contiguous()
+
+
+class _PartsLinear(torch.autograd.Function):
+    """``torch.cat(parts, 1) @ kernel`` without the concatenation: one GEMM per part over the matching rows of
+    ``kernel``, the sum in the epilogue of the later ones (``addmm``).  The parts are taken in the autocast dtype, else in
+    torch's promotion over them (what ``torch.cat`` gives).  Backward: one GEMM per part for its gradient; the rows of the
+    weight gradient are reductions over all voxels, run as split-K products (``ops.xty_tall``: a plain GEMM call does such
+    a reduction in one workgroup per 64 x 64 tile)."""
+
+    @staticmethod
+    def forward(ctx, kernel, *parts):
+        dt = ops.sparse_conv_parts_dtype(parts) if parts[0].is_cuda else functools.reduce(
+            torch.promote_types, [p.dtype for p in parts])
+        if dt == torch.float32 and torch.is_autocast_enabled() and parts[0].is_cuda:
+            dt = torch.get_autocast_dtype('cuda')                # autocast(float16): a GEMM, unlike the convolution
+        ps, w = [p.to(dt) for p in parts], kernel.to(dt)
+        ctx.save_for_backward(w, *ps)
+        ctx.meta = (kernel.dtype, [p.dtype for p in parts])
+        f, a = None, 0
+        for p in ps:
+            wp = w[a:a + p.shape[1]]
+            f = p @ wp if f is None else torch.addmm(f, p, wp)
+            a += p.shape[1]
+        return f
+
+    @staticmethod
+    def backward(ctx, g):
+        w, *ps = ctx.saved_tensors
+        k_dt, p_dts = ctx.meta
+        g = g.contiguous().to(w.dtype)
+        gparts, rows, a = [], [], 0
+        for i, p in enumerate(ps):
+            c = p.shape[1]
+            gparts.append((g @ w[a:a + c].t()).to(p_dts[i]) if ctx.needs_input_grad[1 + i] else None)
+            if ctx.needs_input_grad[0]:
+                rows.append(ops.xty_tall(p, g))
+            a += c
+        gk = torch.cat(rows, 0).to(k_dt) if ctx.needs_input_grad[0] else None
+        return (gk, *gparts)
 
 
 class Conv3d(nn.Module):
@@ -180,12 +286,16 @@ class Conv3d(nn.Module):
         return nbr_t, nbr, x.coord_maps[out_stride], out_stride
 
     def forward(self, x):
+        parts = feature_parts(x)
         if self.kernel_volume == 1 and self.stride == 1:
-            f = x.F @ self.kernel.to(x.F.dtype)
+            if parts is None:
+                f = x.F @ self.kernel.to(x.F.dtype)
+            else:
+                f = _PartsLinear.apply(self.kernel, *parts)
             return x.like(f if self.bias is None else f + self.bias.to(f.dtype))
         nbr, nbr_t, out_coords, out_stride = self._maps(x)
         W = self.kernel if self.kernel.dim() == 3 else self.kernel.unsqueeze(0)   # strided 1x1x1: K = 1
-        f = ops.sparse_conv(x.F, W, self.bias, nbr, nbr_t)
+        f = ops.sparse_conv(x.F if parts is None else list(parts), W, self.bias, nbr, nbr_t)
         return SparseVoxelTensor(f, out_coords, out_stride, x.coord_maps, x.kernel_maps)
 
 

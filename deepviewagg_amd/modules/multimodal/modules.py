@@ -214,10 +214,18 @@ class UnimodalBranch(nn.Module):
         x_mod, mod_data, csr_idx = self.forward_view_pool(x_3d, x_mod, mod_data)
         x_seen = csr_idx[1:] > csr_idx[:-1]
         x_3d, x_mod, mod_data = self.forward_dropout(x_3d, x_mod, mod_data)
-        x_3d = self.forward_fusion(x_3d, x_mod)
-        if self._out_channels is None:
-            self._out_channels = x_3d.shape[1]
-        put_x3d(x_3d)
+        if self._lazy_concatenation(mm_data_dict['x_3d'], x_3d, x_mod):
+            # snn.LAZY_CAT: the fused tensor is not written; the first 3D convolution reads (x_3d, x_mod) in place
+            from ..SparseConv3d import nn as snn
+            x3 = mm_data_dict['x_3d']
+            mm_data_dict['x_3d'] = snn.LazyCatTensor((x_3d, x_mod), x3.C, x3.s, x3.coord_maps, x3.kernel_maps)
+            if self._out_channels is None:
+                self._out_channels = x_3d.shape[1] + x_mod.shape[1]
+        else:
+            x_3d = self.forward_fusion(x_3d, x_mod)
+            if self._out_channels is None:
+                self._out_channels = x_3d.shape[1]
+            put_x3d(x_3d)
         mm_data_dict['modalities'][modality] = mod_data
         if mm_data_dict['x_seen'] is None:
             mm_data_dict['x_seen'] = x_seen
@@ -279,6 +287,18 @@ class UnimodalBranch(nn.Module):
         else:
             x_mod = self.view_pool(x_3d, x_mod, x_map, csr_idx)
         return x_mod, mod_data, csr_idx
+
+    def _lazy_concatenation(self, x3, x_3d, x_mod):
+        """Is this fusion a concatenation onto a voxel tensor of the sparse backend that ``snn.LAZY_CAT`` leaves
+        unwritten?  (Its ``F`` is then ``torch.cat((x_3d, x_mod), 1)`` on first read: the values of ``BimodalFusion``.)"""
+        from ..SparseConv3d import nn as snn
+        from .fusion import BimodalFusion
+        return (snn.LAZY_CAT and isinstance(x3, snn.SparseVoxelTensor) and isinstance(self.fusion, BimodalFusion)
+                and self.fusion.mode == 'concatenation' and 'f' not in self.checkpointing
+                and torch.is_tensor(x_3d) and torch.is_tensor(x_mod) and x_3d.dim() == 2 and x_mod.dim() == 2
+                and x_3d.shape[0] == x_mod.shape[0] and x_3d.shape[1] > 0 and x_mod.shape[1] > 0
+                and x_3d.is_cuda and x_mod.is_cuda
+                and all(t.dtype in (torch.float32, torch.bfloat16) for t in (x_3d, x_mod)))
 
     def forward_fusion(self, x_3d, x_mod):
         if 'f' in self.checkpointing:

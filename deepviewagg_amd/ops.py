@@ -1610,6 +1610,18 @@ def _xty_splitk(a, b, splits=64):
     return part.sum(0, dtype=torch.float32)        # one reduction kernel (fp32 accumulation), no fp32 copy of `part`
 
 
+def xty_tall(a, b, splits=64):
+    """``_xty_splitk`` for any number of rows: the split-K product over the largest multiple of ``splits`` rows and a
+    plain product over the rest (fewer than ``splits`` rows).  [R, O], [R, I] -> fp32 [O, I]."""
+    R = a.shape[0]
+    main = R - R % splits
+    if main < 8192:
+        return a.float().t() @ b.float()
+    a, b = a.contiguous(), b.contiguous()
+    out = _xty_splitk(a[:main], b[:main], splits)
+    return out if main == R else out.addmm_(a[main:].float().t(), b[main:].float())
+
+
 class _TallLinear(torch.autograd.Function):
     """``F.linear`` whose weight gradient is a split-K product (same forward, same autocast rule)."""
 
@@ -2442,11 +2454,161 @@ class _SparseConv(torch.autograd.Function):
         return gx, gW, gb, None, None
 
 
+SPARSE_CONV_MAX_PARTS = 4          # SC_MAX_PARTS of csrc/sparseconv.hip
+
+
+def _parts_widths(parts):
+    return tuple(int(p.shape[1]) for p in parts)
+
+
+def _parts_common(parts, what):
+    """The parts of a features list, each brought on its own to the dtype the call on ``torch.cat(parts, 1)`` would
+    run in: the autocast rule of ``sparse_conv``, else torch's promotion over the parts."""
+    parts = list(parts)
+    if not parts or not all(torch.is_tensor(p) and p.dim() == 2 for p in parts):
+        raise ValueError(f"{what}: the features are a tensor [n, C] or a non-empty list of such tensors")
+    if len(parts) > SPARSE_CONV_MAX_PARTS:
+        raise ValueError(f"{what}: at most {SPARSE_CONV_MAX_PARTS} parts, got {len(parts)} (concatenate some of them)")
+    n = parts[0].shape[0]
+    if any(p.shape[0] != n for p in parts):
+        raise ValueError(f"{what}: the parts have {[p.shape[0] for p in parts]} rows; they must sit on the same voxels")
+    if any(p.shape[1] == 0 for p in parts):
+        raise ValueError(f"{what}: a part without channels")
+    require_device(*parts)
+    dtype = sparse_conv_parts_dtype(parts)
+    return [p.to(dtype) for p in parts]
+
+
+def _parts_padded(parts):
+    """Every part contiguous and at a multiple of 16 channels: a narrow part is padded alone, the others are not copied."""
+    return [(p if p.shape[1] % 16 == 0 else torch.nn.functional.pad(p, (0, _pad16(p.shape[1]) - p.shape[1]))).contiguous()
+            for p in parts]
+
+
+def _parts_table(parts):
+    """The host arrays of the ``*_parts`` entries: device pointers and widths."""
+    P = len(parts)
+    return ((ctypes.c_void_p * P)(*[p.data_ptr() for p in parts]),
+            (ctypes.c_int32 * P)(*[p.shape[1] for p in parts]), P)
+
+
+def _parts_weights(W, widths, cout_p):
+    """W fp32 [K, sum widths, Cout] -> [K, sum pad16(widths), cout_p]: every part's zero rows in place."""
+    Wf = W.detach().float()
+    cout = Wf.shape[2]
+    if cout_p == cout and all(w % 16 == 0 for w in widths):
+        return Wf.contiguous()
+    pieces, a = [], 0
+    for w in widths:
+        pieces.append(torch.nn.functional.pad(Wf[:, a:a + w], (0, cout_p - cout, 0, _pad16(w) - w)))
+        a += w
+    return torch.cat(pieces, 1).contiguous()
+
+
+def _sparse_conv_apply_parts(parts, nbr, W, bias, n_dst):
+    """``_sparse_conv_apply`` in mode 0 on the channel concatenation of ``parts`` (one dtype), which is not written."""
+    lib = _lib.load()
+    K, cout = nbr.shape[0], W.shape[2]
+    widths = _parts_widths(parts)
+    assert sum(widths) == W.shape[1], f"the parts have {sum(widths)} channels, the kernel expects {W.shape[1]}"
+    x0 = parts[0]
+    if x0.shape[0] == 0 or n_dst == 0:
+        out = torch.zeros((n_dst, cout), dtype=x0.dtype, device=x0.device)
+        return out if bias is None else out + bias.to(x0.dtype)
+    cout_p = _pad16(cout)
+    Wf = _parts_weights(W, widths, cout_p)
+    cin_p = Wf.shape[1]
+    bias = None if bias is None else bias.detach().float()
+    if bias is not None and cout_p != cout:
+        bias = torch.nn.functional.pad(bias, (0, cout_p - cout))
+    bias = None if bias is None else bias.contiguous()
+    parts = _parts_padded(parts)
+    out = torch.empty((n_dst, cout_p), dtype=x0.dtype, device=x0.device)
+    code = dtype_code(x0)
+    ws, nbytes = _lib.workspace("dva_sparse_conv_workspace_bytes", x0.device, K, cin_p, cout_p, code)
+    s = x0.element_size()
+    ptrs, wid, P = _parts_table(parts)
+    with _timed(f"sparse_conv_apply_parts{SPARSE_CONV_TIMER_SHAPES and f'[{K}x{cin_p}->{cout_p}@{n_dst}]' or ''}",
+                n_dst * (K * 4 + cout_p * s) + x0.shape[0] * cin_p * s):
+        check(lib.dva_sparse_conv_apply_parts(ptrs, wid, P, ptr(nbr), ptr(Wf), ptr(bias), ptr(out), x0.shape[0], n_dst,
+                                              K, cout_p, code, ptr(ws), nbytes, stream_of(x0)),
+              "dva_sparse_conv_apply_parts")
+    return out if cout_p == cout else out[:, :cout].contiguous()
+
+
+def _sparse_conv_wgrad_parts(parts, nbr, gout, cout):
+    """``_sparse_conv_wgrad`` on the parts: fp32 [K, sum widths, Cout], the padding rows of a narrow part cut."""
+    lib = _lib.load()
+    K, n_dst = nbr.shape
+    widths = _parts_widths(parts)
+    cout_p = _pad16(cout)
+    if cout_p != cout:
+        gout = torch.nn.functional.pad(gout, (0, cout_p - cout))
+    gout = gout.contiguous()
+    parts = _parts_padded(parts)
+    cin_p = sum(p.shape[1] for p in parts)
+    x0 = parts[0]
+    gW = torch.empty((K, cin_p, cout_p), dtype=torch.float32, device=x0.device)
+    s = x0.element_size()
+    ptrs, wid, P = _parts_table(parts)
+    with _timed(f"sparse_conv_wgrad_parts{SPARSE_CONV_TIMER_SHAPES and f'[{K}x{cin_p}->{cout_p}@{n_dst}]' or ''}",
+                n_dst * (K * 4 + cout_p * s) + x0.shape[0] * cin_p * s):
+        check(lib.dva_sparse_conv_wgrad_parts(ptrs, wid, P, ptr(nbr), ptr(gout), ptr(gW), x0.shape[0], n_dst, K, cout_p,
+                                              dtype_code(x0), stream_of(x0)), "dva_sparse_conv_wgrad_parts")
+    if cin_p == sum(widths) and cout_p == cout:
+        return gW
+    pieces, a = [], 0
+    for w in widths:
+        pieces.append(gW[:, a:a + w, :cout])
+        a += _pad16(w)
+    return torch.cat(pieces, 1)
+
+
+class _SparseConvParts(torch.autograd.Function):
+    """``_SparseConv`` on features given in parts (one dtype): the concatenation is never written in the forward pass
+    or for the weight gradient; the input gradient is one [n_src, sum C_p] buffer and each part gets its columns."""
+
+    @staticmethod
+    def forward(ctx, W, bias, nbr, nbr_t, *parts):
+        require_device(W, nbr, nbr_t, *parts)
+        ctx.save_for_backward(W, nbr, nbr_t, *parts)
+        ctx.has_bias = bias is not None
+        return _sparse_conv_apply_parts(parts, nbr, W, bias, nbr.shape[1])
+
+    @staticmethod
+    def backward(ctx, gout):
+        W, nbr, nbr_t, *parts = ctx.saved_tensors
+        gout = gout.contiguous().to(parts[0].dtype)
+        gW = gb = None
+        gparts = [None] * len(parts)
+        if any(ctx.needs_input_grad[4:]):
+            gx = _sparse_conv_apply(gout, nbr_t, W, None, parts[0].shape[0], 1)
+            a = 0
+            for i, p in enumerate(parts):
+                if ctx.needs_input_grad[4 + i]:
+                    gparts[i] = gx[:, a:a + p.shape[1]]
+                a += p.shape[1]
+        if ctx.needs_input_grad[0]:
+            gW = _sparse_conv_wgrad_parts(parts, nbr, gout, W.shape[2]).to(W.dtype)
+        if ctx.has_bias and ctx.needs_input_grad[1]:
+            gb = gout.float().sum(0)
+        return (gW, gb, None, None, *gparts)
+
+
 def sparse_conv(x, W, bias, nbr, nbr_t):
     """Sparse convolution over a kernel map pair (see ``voxel_kernel_map``): x [n_src, Cin] (fp32 or bf16),
     W fp32 [K, Cin, Cout], bias [Cout] or None -> [n_dst, Cout].  Under ``torch.autocast`` the features are
     taken in the autocast dtype (the weights stay fp32 masters, rounded to bf16 inside the kernel); the kernels have no fp16
-    form, so under autocast(float16) the 3D branch stays fp32 (the fusion concat already promotes to it)."""
+    form, so under autocast(float16) the 3D branch stays fp32 (the fusion concat already promotes to it).
+
+    ``x`` may be a tuple or list of up to 4 tensors on the same voxels: the result is that of the call on
+    ``torch.cat(x, 1)`` (bit for bit when every width is a multiple of 16), without that tensor being written.  Parts
+    may differ in dtype; each is cast on its own (a bf16 part under autocast(bfloat16) is used as it is)."""
+    if isinstance(x, (tuple, list)):
+        parts = _parts_common(x, "ops.sparse_conv")
+        if len(parts) == 1:
+            return _SparseConv.apply(parts[0], W, bias, nbr, nbr_t)
+        return _SparseConvParts.apply(W, bias, nbr, nbr_t, *parts)
     if torch.is_autocast_enabled() and x.is_cuda:
         x = x.to(torch.bfloat16 if torch.get_autocast_dtype('cuda') == torch.bfloat16 else torch.float32)
     return _SparseConv.apply(x, W, bias, nbr, nbr_t)
@@ -2459,18 +2621,32 @@ def sparse_conv_feature_dtype(x):
     return x.dtype
 
 
+def sparse_conv_parts_dtype(parts):
+    """``sparse_conv_feature_dtype`` for features given in parts: the dtype the call on their concatenation runs in."""
+    if torch.is_autocast_enabled() and parts[0].is_cuda:
+        return torch.bfloat16 if torch.get_autocast_dtype('cuda') == torch.bfloat16 else torch.float32
+    dtype = parts[0].dtype
+    for p in parts[1:]:
+        dtype = torch.promote_types(dtype, p.dtype)
+    return dtype
+
+
 class PackedSparseConvWeights:
     """The constant weights of one sparse convolution as ``sconv_apply_kernel`` reads them (bf16 ``w_hi | w_lo``
     tiles): ``buf`` uint8, with ``K``, ``cin``, ``cout``, the widths padded to 16 ``cin_p`` / ``cout_p`` and the
-    feature ``dtype`` the layout was made for."""
-    __slots__ = ("buf", "K", "cin", "cout", "cin_p", "cout_p", "dtype")
+    feature ``dtype`` the layout was made for.  ``parts``: the widths of the feature parts the input-channel axis was
+    packed for (each padded to 16 in place, ``cin_p`` their sum), or None for one tensor."""
+    __slots__ = ("buf", "K", "cin", "cout", "cin_p", "cout_p", "dtype", "parts")
 
-    def __init__(self, buf, K, cin, cout, cin_p, cout_p, dtype):
+    def __init__(self, buf, K, cin, cout, cin_p, cout_p, dtype, parts=None):
         self.buf, self.K, self.cin, self.cout, self.cin_p, self.cout_p, self.dtype = buf, K, cin, cout, cin_p, cout_p, dtype
+        self.parts = parts
 
 
-def sparse_conv_pack(W, dtype):
-    """Pack W fp32 [K, Cin, Cout] once for ``sparse_conv_fused`` on features of ``dtype`` (fp32 or bf16)."""
+def sparse_conv_pack(W, dtype, parts=None):
+    """Pack W fp32 [K, Cin, Cout] once for ``sparse_conv_fused`` on features of ``dtype`` (fp32 or bf16).  ``parts``:
+    the widths of the tensors the features will be given in (they sum to Cin); the input-channel axis is then packed
+    with each part's padding to 16 in place."""
     lib = _lib.load()
     require_device(W)
     if W.dim() != 3:
@@ -2478,37 +2654,72 @@ def sparse_conv_pack(W, dtype):
     if dtype not in (torch.float32, torch.bfloat16):
         raise TypeError(f"ops.sparse_conv_pack: the kernels take fp32 or bf16 features, not {dtype}")
     K, cin, cout = W.shape
-    cin_p, cout_p = _pad16(cin), _pad16(cout)
-    Wf = W.detach().float()
-    if cin_p != cin or cout_p != cout:
-        Wf = torch.nn.functional.pad(Wf, (0, cout_p - cout, 0, cin_p - cin))
-    Wf = Wf.contiguous()
+    if parts is not None:
+        parts = tuple(int(w) for w in parts)
+        if not 1 <= len(parts) <= SPARSE_CONV_MAX_PARTS or any(w <= 0 for w in parts) or sum(parts) != cin:
+            raise ValueError(f"ops.sparse_conv_pack: parts {parts} are not 1 to {SPARSE_CONV_MAX_PARTS} positive widths "
+                             f"that sum to Cin = {cin}")
+        if len(parts) == 1:
+            parts = None
+    cout_p = _pad16(cout)
+    if parts is None:
+        cin_p = _pad16(cin)
+        Wf = W.detach().float()
+        if cin_p != cin or cout_p != cout:
+            Wf = torch.nn.functional.pad(Wf, (0, cout_p - cout, 0, cin_p - cin))
+        Wf = Wf.contiguous()
+    else:
+        Wf = _parts_weights(W, parts, cout_p)
+        cin_p = Wf.shape[1]
     code = _lib.DVA_F32 if dtype == torch.float32 else _lib.DVA_BF16
     buf, nbytes = _lib.workspace("dva_sparse_conv_workspace_bytes", W.device, K, cin_p, cout_p, code)
     with _timed("sparse_conv_pack", K * cin_p * cout_p * 4 + nbytes):
         check(lib.dva_sparse_conv_pack_weights(ptr(Wf), K, cin_p, cout_p, 0, code, ptr(buf), nbytes, stream_of(Wf)),
               "dva_sparse_conv_pack_weights")
-    return PackedSparseConvWeights(buf, K, cin, cout, cin_p, cout_p, dtype)
+    return PackedSparseConvWeights(buf, K, cin, cout, cin_p, cout_p, dtype, parts)
 
 
 def sparse_conv_fused(x, packed, bias, nbr, residual=None, slope=1.0):
     """Inference form of ``sparse_conv`` over packed constant weights (``sparse_conv_pack``), with the activation and
     the residual sum in the kernel's epilogue: ``out = T(leaky(conv(x) + bias, slope) + residual)``, fp32 steps, one
     rounding.  x [n_src, Cin], bias fp32 [Cout] or None, nbr int32 [K, n_dst], residual [n_dst, Cout] or None ->
-    [n_dst, Cout].  No autograd.  The autocast rule of ``sparse_conv`` holds; ``packed`` must be of that dtype."""
+    [n_dst, Cout].  No autograd.  The autocast rule of ``sparse_conv`` holds; ``packed`` must be of that dtype.
+
+    ``x`` may be a tuple or list of tensors as in ``sparse_conv``; ``packed`` must then have been made with their
+    widths (``sparse_conv_pack(W, dtype, parts=widths)``), else ValueError."""
     lib = _lib.load()
+    parts = None
+    if isinstance(x, (tuple, list)):
+        parts = [p.detach() for p in _parts_common(x, "ops.sparse_conv_fused")]
+        if torch.is_grad_enabled() and any(p.requires_grad for p in x):
+            raise RuntimeError("ops.sparse_conv_fused has no backward: call it under torch.no_grad() or on detached "
+                               "inputs (ops.sparse_conv is the differentiable form)")
+        if len(parts) == 1:
+            x, parts = parts[0], None
+        else:
+            x = parts[0]
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, bias, residual)):
         raise RuntimeError("ops.sparse_conv_fused has no backward: call it under torch.no_grad() or on detached "
                            "inputs (ops.sparse_conv is the differentiable form)")
     require_device(x, packed.buf, nbr, bias, residual)
     assert nbr.dtype == torch.int32 and nbr.dim() == 2, "nbr is the int32 [K, n_dst] map of voxel_kernel_map"
     nbr = nbr.contiguous()
-    x = x.detach().to(sparse_conv_feature_dtype(x))
+    if parts is None:
+        x = x.detach().to(sparse_conv_feature_dtype(x))
     if x.dtype != packed.dtype:
         raise TypeError(f"ops.sparse_conv_fused: weights packed for {packed.dtype} features, got {x.dtype}")
     K, n_dst = nbr.shape
     assert K == packed.K, f"the kernel map has {K} offsets, the packed weights {packed.K}"
-    assert x.shape[1] == packed.cin, f"features have {x.shape[1]} channels, the kernel expects {packed.cin}"
+    if parts is not None:
+        if packed.parts != _parts_widths(parts):
+            raise ValueError(f"ops.sparse_conv_fused: the features come in parts of widths {_parts_widths(parts)}, the "
+                             f"weights were packed for {packed.parts or (packed.cin,)} "
+                             "(ops.sparse_conv_pack(W, dtype, parts=widths))")
+    else:
+        assert x.shape[1] == packed.cin, f"features have {x.shape[1]} channels, the kernel expects {packed.cin}"
+        if packed.parts is not None and any(w % 16 for w in packed.parts):
+            raise ValueError(f"ops.sparse_conv_fused: the weights were packed for parts of widths {packed.parts}, the "
+                             "features are one tensor")
     slope = float(slope)
     cout, cin_p, cout_p = packed.cout, packed.cin_p, packed.cout_p
     if residual is not None:
@@ -2521,7 +2732,9 @@ def sparse_conv_fused(x, packed, bias, nbr, residual=None, slope=1.0):
             v = v + bias
         v = torch.where(v >= 0, v, slope * v)
         return (v if residual is None else v + residual.float()).to(x.dtype)
-    if cin_p != packed.cin:
+    if parts is not None:
+        parts = _parts_padded(parts)
+    elif cin_p != packed.cin:
         x = torch.nn.functional.pad(x, (0, cin_p - packed.cin))
     if cout_p != cout:
         bias = None if bias is None else torch.nn.functional.pad(bias, (0, cout_p - cout))
@@ -2531,11 +2744,19 @@ def sparse_conv_fused(x, packed, bias, nbr, residual=None, slope=1.0):
     residual = None if residual is None else residual.contiguous()
     out = torch.empty((n_dst, cout_p), dtype=x.dtype, device=x.device)
     s = x.element_size()
-    with _timed(f"sparse_conv_fused{SPARSE_CONV_TIMER_SHAPES and f'[{K}x{cin_p}->{cout_p}@{n_dst}]' or ''}",
+    tag = "sparse_conv_fused" if parts is None else "sparse_conv_fused_parts"
+    with _timed(f"{tag}{SPARSE_CONV_TIMER_SHAPES and f'[{K}x{cin_p}->{cout_p}@{n_dst}]' or ''}",
                 n_dst * (K * 4 + cout_p * s * (1 if residual is None else 2)) + x.shape[0] * cin_p * s):
-        check(lib.dva_sparse_conv_apply_packed(ptr(x), ptr(nbr), ptr(packed.buf), packed.buf.numel(), ptr(bias),
-                                               ptr(residual), slope, ptr(out), x.shape[0], n_dst, K, cin_p, cout_p,
-                                               dtype_code(x), stream_of(x)), "dva_sparse_conv_apply_packed")
+        if parts is None:
+            check(lib.dva_sparse_conv_apply_packed(ptr(x), ptr(nbr), ptr(packed.buf), packed.buf.numel(), ptr(bias),
+                                                   ptr(residual), slope, ptr(out), x.shape[0], n_dst, K, cin_p, cout_p,
+                                                   dtype_code(x), stream_of(x)), "dva_sparse_conv_apply_packed")
+        else:
+            ptrs, wid, P = _parts_table(parts)
+            check(lib.dva_sparse_conv_apply_packed_parts(ptrs, wid, P, ptr(nbr), ptr(packed.buf), packed.buf.numel(),
+                                                         ptr(bias), ptr(residual), slope, ptr(out), x.shape[0], n_dst,
+                                                         K, cout_p, dtype_code(x), stream_of(x)),
+                  "dva_sparse_conv_apply_packed_parts")
     return out if cout_p == cout else out[:, :cout].contiguous()
 
 

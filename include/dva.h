@@ -932,6 +932,20 @@ int dva_voxel_parent_index(const int32_t* in_coords, int64_t n_in, const int32_t
  * slope finite (1: no activation, 0: ReLU); residual [n_dst, Cout] in `dtype`, 16-byte aligned, nullable, must
  * not alias out.  A destination without any neighbour gets act(bias) + residual.  Deterministic, no atomics.
  * Both validate as dva_sparse_conv_apply does, in its order, before any HIP call.
+ *
+ * Features in parts (since dva_version 333): the convolution of the channel concatenation of P tensors on the
+ * same voxels, without that concatenation in memory.  `parts` and `widths` are HOST arrays of P device pointers
+ * and P channel counts (copied into the kernel arguments: no device table, no copy, no synchronisation); part p
+ * is [n_src, widths[p]] in `dtype`, 16-byte aligned, widths[p] a multiple of 16 (the host pads a narrow part,
+ * alone), 1 <= P <= 4.  Cin = sum of the widths; W, the packed buffer and grad_W are those of the single-tensor
+ * entries for that Cin, the input channels in concatenation order (a padded part's zero rows in place).
+ * dva_sparse_conv_apply_parts is dva_sparse_conv_apply in mode 0, dva_sparse_conv_apply_packed_parts is
+ * dva_sparse_conv_apply_packed, dva_sparse_conv_wgrad_parts is dva_sparse_conv_wgrad.  The 16-channel steps run
+ * in concatenation order, so apply gives the bits of the single-tensor entry on the concatenated tensor.
+ * Validation, in this order: scalars (P <= 0 or widths == NULL: DVA_ERR_INVALID), DVA_F16 (DVA_ERR_UNSUPPORTED),
+ * P > 4 (DVA_ERR_UNSUPPORTED), a width <= 0 (DVA_ERR_INVALID) or not a multiple of 16 (DVA_ERR_UNSUPPORTED), then
+ * as the single-tensor entry: n_dst == 0 is DVA_OK before any device pointer is looked at; a null or misaligned
+ * part is DVA_ERR_INVALID.
  * ------------------------------------------------------------------------------------------ */
 int dva_voxel_kernel_map(const int32_t* src_coords, int64_t n_src, const int32_t* dst_coords, int64_t n_dst,
                          const int32_t* offsets, int32_t K, int32_t* nbr, void* workspace,
@@ -947,6 +961,18 @@ int dva_sparse_conv_pack_weights(const float* W, int32_t K, int32_t Cin, int32_t
 int dva_sparse_conv_apply_packed(const void* x, const int32_t* nbr, const void* packed, int64_t packed_bytes,
                                  const float* bias, const void* residual, float slope, void* out, int64_t n_src,
                                  int64_t n_dst, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* stream);
+int dva_sparse_conv_apply_parts(const void* const* parts, const int32_t* widths, int32_t P, const int32_t* nbr,
+                                const float* W, const float* bias, void* out, int64_t n_src, int64_t n_dst,
+                                int32_t K, int32_t Cout, int32_t dtype, void* workspace, int64_t workspace_bytes,
+                                void* stream);
+int dva_sparse_conv_apply_packed_parts(const void* const* parts, const int32_t* widths, int32_t P,
+                                       const int32_t* nbr, const void* packed, int64_t packed_bytes,
+                                       const float* bias, const void* residual, float slope, void* out,
+                                       int64_t n_src, int64_t n_dst, int32_t K, int32_t Cout, int32_t dtype,
+                                       void* stream);
+int dva_sparse_conv_wgrad_parts(const void* const* parts, const int32_t* widths, int32_t P, const int32_t* nbr,
+                                const void* grad_out, float* grad_W, int64_t n_src, int64_t n_dst, int32_t K,
+                                int32_t Cout, int32_t dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------ *
  * Neighbourhood-based mapping features (core/data_transform/multimodal/image.py:431-612): exact k nearest

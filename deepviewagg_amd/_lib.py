@@ -242,6 +242,11 @@ SIGNATURES = {
     "dva_voxel_parent_workspace_bytes": (ctypes.c_int64, [_i64]),
     "dva_voxel_parent_index": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),
     "dva_voxel_kernel_map": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _vp]),
+    "dva_voxel_level_workspace_bytes": (ctypes.c_int64, [_i64]),
+    "dva_voxel_bounds": (ctypes.c_int, [_vp, _i64, _vp, _vp, _i64, _vp]),
+    # bounds: a host array (ctypes array of 8 c_int64)
+    "dva_voxel_level": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "dva_voxel_level_maps": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     "dva_sparse_conv_workspace_bytes": (ctypes.c_int64, [_i32, _i32, _i32, _i32]),
     "dva_sparse_conv_apply": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp,
                                              _i64, _vp]),

@@ -252,7 +252,7 @@ using namespace dva;
 
 extern "C" {
 
-int dva_version(void) { return 333; }
+int dva_version(void) { return 334; }
 
 int dva_device_count(void) {
   int n = 0;

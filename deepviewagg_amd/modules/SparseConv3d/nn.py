@@ -28,7 +28,7 @@ from torch import nn
 from ... import ops
 from ..multimodal.pooling import batchnorm_act_rows
 
-__all__ = ["cat", "Conv3d", "Conv3dTranspose", "ReLU", "SparseTensor", "BatchNorm", "LazyCatTensor"]
+__all__ = ["cat", "Conv3d", "Conv3dTranspose", "ReLU", "SparseTensor", "BatchNorm", "LazyCatTensor", "CoordMaps"]
 
 # modules/SparseConv3d/nn/__init__.py:28-60: the reference switches between two sparse libraries; here there
 # is one backend, which carries the torchsparse field names (F, C, s, coord_maps) the multimodal blocks read.
@@ -47,12 +47,41 @@ def set_backend(_backend):
     assert backend_valid(_backend)
 
 
+class CoordMaps(dict):
+    """The coordinate cache of a pyramid, tensor stride -> coordinates, which every tensor derived from one input
+    shares.  It also carries what the one sort of a strided level leaves behind (``Conv3d._build``), outside the keys:
+    ``parents`` {(stride_in, stride_out): int64 [n_in]}, the row of ``self[stride_out]`` that holds each voxel of
+    ``self[stride_in]`` (what ``MultimodalBlockDown`` re-indexes the mappings with), and ``bounds`` = (stride, lo, hi):
+    ``ops.voxel_bounds`` of ``self[stride]``, read once and floored on the host for every coarser level."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.parents, self.bounds = {}, None
+
+    def to(self, device):
+        out = CoordMaps({k: v.to(device) for k, v in self.items()})
+        out.parents = {k: v.to(device) for k, v in self.parents.items()}
+        out.bounds = self.bounds
+        return out
+
+
+def _move_coords(x, device):
+    """``x.C`` and ``x.coord_maps`` to ``device``; the cache keeps its class, and the tensor's own entry stays ``x.C``
+    itself where it was (what is cached per row of ``x.C`` is told by that to belong to the entry)."""
+    found = x.coord_maps
+    own = found.get(x.s) is x.C
+    x.C = x.C.to(device)
+    x.coord_maps = found.to(device) if isinstance(found, CoordMaps) else {k: v.to(device) for k, v in found.items()}
+    if own:
+        x.coord_maps[x.s] = x.C
+
+
 class SparseVoxelTensor:
     """``F`` features, ``C`` int32 [n, 4] (x, y, z, batch), ``s`` tensor stride, shared caches."""
 
     def __init__(self, feats, coords, stride=1, coord_maps=None, kernel_maps=None):
         self.F, self.C, self.s = feats, coords, stride
-        self.coord_maps = coord_maps if coord_maps is not None else {}
+        self.coord_maps = coord_maps if coord_maps is not None else CoordMaps()
         self.kernel_maps = kernel_maps if kernel_maps is not None else {}
         self.coord_maps.setdefault(stride, coords)
 
@@ -61,8 +90,8 @@ class SparseVoxelTensor:
         return SparseVoxelTensor(feats, self.C, self.s, self.coord_maps, self.kernel_maps)
 
     def to(self, device):
-        self.F, self.C = self.F.to(device), self.C.to(device)
-        self.coord_maps = {k: v.to(device) for k, v in self.coord_maps.items()}
+        self.F = self.F.to(device)
+        _move_coords(self, device)
         return self
 
     def __add__(self, other):
@@ -91,7 +120,7 @@ class LazyCatTensor(SparseVoxelTensor):
         assert parts and all(p.dim() == 2 and p.shape[0] == parts[0].shape[0] for p in parts)
         self._parts, self._feats = parts, None
         self.C, self.s = coords, stride
-        self.coord_maps = coord_maps if coord_maps is not None else {}
+        self.coord_maps = coord_maps if coord_maps is not None else CoordMaps()
         self.kernel_maps = kernel_maps if kernel_maps is not None else {}
         self.coord_maps.setdefault(stride, coords)
 
@@ -119,8 +148,7 @@ class LazyCatTensor(SparseVoxelTensor):
             self._parts = tuple(p.to(device) for p in self._parts)
         if self._feats is not None:
             self._feats = self._feats.to(device)
-        self.C = self.C.to(device)
-        self.coord_maps = {k: v.to(device) for k, v in self.coord_maps.items()}
+        _move_coords(self, device)
         return self
 
 
@@ -135,6 +163,8 @@ def feature_parts(x):
         return None
     return parts
 
+
+LEVEL_ON_DEVICE = True   # Conv3d._build of a strided convolution: ops.voxel_level instead of the torch composition
 
 LAZY_CAT = False    # cat(..., lazy=None): keep the parts (LazyCatTensor) instead of writing the concatenation
 
@@ -249,7 +279,52 @@ class Conv3d(nn.Module):
 
     @staticmethod
     def _build(x, key, out_stride):
-        """Kernel map pair of a (non-transposed) convolution with parameters ``key`` on the voxels of ``x``."""
+        """Kernel map pair of a (non-transposed) convolution with parameters ``key`` on the voxels of ``x``: a strided
+        one on the device from one sort (``LEVEL_ON_DEVICE``), else, and wherever that route declines, the composition."""
+        if key[2] != 1 and LEVEL_ON_DEVICE and x.C.is_cuda and Conv3d._build_level(x, key, out_stride):
+            return
+        Conv3d._build_composition(x, key, out_stride)
+
+    @staticmethod
+    def _level_bounds(x):
+        """``ops.voxel_bounds`` of ``x.C``, or the ones the pyramid's cache holds of a finer tensor: one host read per
+        input tensor, not per level."""
+        cached = getattr(x.coord_maps, "bounds", None)
+        if cached is not None and x.s % cached[0] == 0:
+            return cached[1], cached[2]
+        bounds = ops.voxel_bounds(x.C)
+        if bounds is not None and isinstance(x.coord_maps, CoordMaps):
+            x.coord_maps.bounds = (x.s, *bounds)
+        return bounds
+
+    @staticmethod
+    def _build_level(x, key, out_stride):
+        """``_build`` of a strided convolution through ``ops.voxel_level``: output coordinates and parents from one
+        sort, and for kernel_size 2 / stride 2 / dilation 1 both maps with them; any other strided kernel takes its maps
+        from ``ops.voxel_kernel_map``.  Bit for bit what ``_build_composition`` + ``ops.voxel_parent_index`` give.
+        False where the op declines (the key does not pack, stale cached bounds): nothing has been cached then."""
+        _, kernel_size, stride, dilation = key
+        direct = kernel_size == 2 and stride == 2 and dilation == 1
+        level = ops.voxel_level(x.C, out_stride, x.s, maps=direct, bounds=Conv3d._level_bounds(x))
+        if level.out_coords is None:
+            if isinstance(x.coord_maps, CoordMaps):
+                x.coord_maps.bounds = None
+            return False
+        nbr, nbr_t = level.nbr, level.nbr_t
+        if not level.direct:
+            offs = kernel_offsets(kernel_size, x.s, dilation)
+            nbr = ops.voxel_kernel_map(x.C, level.out_coords, offs)
+            nbr_t = ops.voxel_kernel_map(level.out_coords, x.C, -offs)
+        x.kernel_maps[key] = (nbr, nbr_t)
+        kept = x.coord_maps.setdefault(out_stride, level.out_coords)
+        if kept is level.out_coords and isinstance(x.coord_maps, CoordMaps) and x.coord_maps.get(x.s) is x.C:
+            x.coord_maps.parents[(x.s, out_stride)] = level.parent     # rows of coord_maps[out_stride], nothing else
+        return True
+
+    @staticmethod
+    def _build_composition(x, key, out_stride):
+        """``_build`` in torch operators and hash queries: the route of CPU tensors, the fallback of ``_build_level``
+        and the yardstick it is held to."""
         _, kernel_size, stride, dilation = key
         out_coords = x.C if stride == 1 else downsample_coords(x.C, out_stride)
         offs = kernel_offsets(kernel_size, x.s, dilation)

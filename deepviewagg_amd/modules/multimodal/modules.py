@@ -17,7 +17,8 @@ sparse convolutions MERGE the mappings of the input voxels onto their parent vox
 convolution itself (torchsparse / MinkowskiEngine) is not part of this package: any block that maps a
 voxel tensor exposing ``C`` (int32 [N, 4] coordinates, batch index in the last column), ``s`` (stride) and
 ``coord_maps`` (stride -> coordinates), i.e. the torchsparse 1.1 SparseTensor interface, can be plugged in;
-the parent index is a HIP hash query (``ops.voxel_parent_index``).
+the parent index is the one a strided ``snn.Conv3d`` leaves in ``coord_maps.parents`` (``ops.voxel_level``), else a HIP
+hash query (``ops.voxel_parent_index``).
 """
 import torch
 import torch.nn as nn
@@ -110,8 +111,12 @@ class MultimodalBlockDown(nn.Module):
                     f"Sparse coordinates are expected to have shape (N x 4), with batch indices in the last " \
                     f"column and 3D spatial coordinates in the first ones. Yet, received coordinates tensor " \
                     f"with shape {x_3d.C.shape} instead."
-                idx = ops.voxel_parent_index(x_3d.coord_maps[stride_in], x_3d.coord_maps[stride_out],
-                                             int(stride_out), batch_col=3)
+                # the strided convolution's own sort has left the parents in the pyramid's cache (snn.CoordMaps);
+                # any other voxel tensor (a plain dict of coordinates) is joined by the hash query
+                idx = getattr(x_3d.coord_maps, 'parents', {}).get((stride_in, stride_out))
+                if idx is None:
+                    idx = ops.voxel_parent_index(x_3d.coord_maps[stride_in], x_3d.coord_maps[stride_out],
+                                                 int(stride_out), batch_col=3)
         else:
             raise NotImplementedError(
                 f"Unsupported format for x_3d: {type(x_3d)}. Expected a dense feature tensor or a voxel tensor "

@@ -31,6 +31,7 @@ ops; names and argument meaning follow the reference call site
 ``confusion_counts``       metrics/segmentation_tracker.py:72-83 (mask + ``np.argmax`` + ``np.bincount``)
 ``merge_mapping``          core/multimodal/image.py:2211-2273 (``select_points(mode='merge')`` + ``from_dense``)
 ``select_mapping``         core/multimodal/image.py:2029-2210, :2279-2342 (``select_images / _views / _points('pick')``, ``crop``)
+``voxel_level``            a strided torchsparse ``Conv3d``'s coordinates and maps + modules/multimodal/modules.py:176-198, one sort
 =========================  ==========================================================
 
 All ops require tensors on a HIP device and raise otherwise (no CPU fallback).
@@ -2374,7 +2375,83 @@ def voxel_kernel_map(src_coords, dst_coords, offsets):
     return nbr
 
 
-SPARSE_CONV_TIMER_SHAPES = False   # bench tools: label the KernelTimer entries with the layer shape
+# flags of dva_voxel_level's record (include/dva.h)
+VOXEL_LEVEL_FLAG_STRIDE, VOXEL_LEVEL_FLAG_KEY, VOXEL_LEVEL_FLAG_BOUNDS = 1, 2, 4
+
+VoxelLevel = collections.namedtuple("VoxelLevel", "out_coords parent nbr nbr_t direct")
+
+
+def voxel_bounds(coords):
+    """``((min x, y, z, batch), (max x, y, z, batch))`` of int32 [n, 4] coordinates as Python ints, None for n = 0:
+    one launch pair and one host read.  Floored to a coarser stride on the host, these are the exact bounds of every
+    coarser level of the same pyramid (floor is monotone), which is how ``voxel_level`` takes them."""
+    lib = _lib.load()
+    require_device(coords)
+    assert coords.dim() == 2 and coords.shape[1] == 4
+    c = coords.to(torch.int32).contiguous()
+    n = c.shape[0]
+    if n == 0:
+        return None
+    out = torch.empty(8, dtype=torch.int64, device=c.device)
+    ws, nbytes = _lib.workspace("dva_voxel_level_workspace_bytes", c.device, n)
+    with _timed("voxel_bounds", n * 16):
+        check(lib.dva_voxel_bounds(ptr(c), n, ptr(out), ptr(ws), int(nbytes), stream_of(c)), "dva_voxel_bounds")
+    b = out.tolist()                                      # host read: the sort's bit count
+    return tuple(b[:4]), tuple(b[4:])
+
+
+def voxel_level(coords, ratio, in_stride, maps=True, bounds=None):
+    """One strided level of a voxel pyramid from one sort: ``VoxelLevel(out_coords, parent, nbr, nbr_t, direct)``.
+
+    ``coords`` int32 [n, 4] = (x, y, z, batch) at tensor stride ``in_stride``; ``ratio`` the output tensor stride.
+    ``out_coords`` int32 [n_out, 4]: the unique rows of ``(floor(xyz / ratio) * ratio, batch)``, ascending (batch, z,
+    y, x) -- ``snn.downsample_coords``; ``parent`` int64 [n]: ``voxel_parent_index(coords, out_coords, ratio)``.
+    With ``maps`` and ``ratio == 2 * in_stride`` on coordinates that are multiples of ``in_stride``, ``direct`` is True
+    and ``nbr`` int32 [8, n_out], ``nbr_t`` int32 [8, n] are the kernel map pair of a kernel_size 2 / stride 2 /
+    dilation 1 convolution (``voxel_kernel_map(coords, out_coords, offs)`` and ``(out_coords, coords, -offs)``);
+    otherwise both are None and the caller builds them with ``voxel_kernel_map``.
+
+    ``bounds``: ``voxel_bounds`` of ``coords`` or of any finer tensor of the same pyramid (None: computed here, one more
+    host read).  One host read of its own: ``n_out`` and the flags together.  Where the key (batch, z, y, x) does not fit
+    ``downsample_coords``' 62 bits, or a row lies outside ``bounds``, every field is None (``direct`` False): the caller
+    takes the composition."""
+    lib = _lib.load()
+    require_device(coords)
+    assert coords.dim() == 2 and coords.shape[1] == 4
+    ratio, in_stride = int(ratio), int(in_stride)
+    if ratio <= 0 or in_stride <= 0:
+        raise ValueError(f"ops.voxel_level: ratio and in_stride must be positive, got {ratio} and {in_stride}")
+    c = coords.to(torch.int32).contiguous()
+    n, dev = c.shape[0], c.device
+    want_maps = bool(maps) and ratio == 2 * in_stride
+    if n == 0:
+        empty = (lambda: torch.empty((8, 0), dtype=torch.int32, device=dev)) if want_maps else (lambda: None)
+        return VoxelLevel(torch.empty((0, 4), dtype=torch.int32, device=dev),
+                          torch.empty(0, dtype=torch.int64, device=dev), empty(), empty(), want_maps)
+    lo, hi = bounds if bounds is not None else voxel_bounds(c)
+    floored = [v // ratio * ratio for v in lo[:3]] + [lo[3]] + [v // ratio * ratio for v in hi[:3]] + [hi[3]]
+    out_coords = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    parent = torch.empty(n, dtype=torch.int64, device=dev)
+    record = torch.empty(2, dtype=torch.int64, device=dev)
+    ws, nbytes = _lib.workspace("dva_voxel_level_workspace_bytes", dev, n)
+    with _timed("voxel_level", n * 24):                   # compulsory: rows in, parents out (+ 16 n_out, not known yet)
+        check(lib.dva_voxel_level(ptr(c), n, ratio, in_stride, (ctypes.c_int64 * 8)(*floored), ptr(out_coords),
+                                  ptr(parent), ptr(record), ptr(ws), int(nbytes), stream_of(c)), "dva_voxel_level")
+    n_out, flags = record.tolist()                        # host read: the output shapes and the flags, together
+    if flags & (VOXEL_LEVEL_FLAG_KEY | VOXEL_LEVEL_FLAG_BOUNDS):
+        return VoxelLevel(None, None, None, None, False)
+    out_coords = out_coords[:n_out].clone()               # release the capacity
+    if not want_maps or flags & VOXEL_LEVEL_FLAG_STRIDE:
+        return VoxelLevel(out_coords, parent, None, None, False)
+    nbr = torch.empty((8, n_out), dtype=torch.int32, device=dev)
+    nbr_t = torch.empty((8, n), dtype=torch.int32, device=dev)
+    with _timed("voxel_level_maps", n * 56 + n_out * 32):  # rows and parents in, both maps out
+        check(lib.dva_voxel_level_maps(ptr(c), ptr(parent), n, n_out, ratio, in_stride, ptr(nbr), ptr(nbr_t),
+                                       stream_of(c)), "dva_voxel_level_maps")
+    return VoxelLevel(out_coords, parent, nbr, nbr_t, True)
+
+
+SPARSE_CONV_TIMER_SHAPES = False  # bench tools: label the KernelTimer entries with the layer shape
 
 
 def _pad16(c):

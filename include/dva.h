@@ -1021,6 +1021,45 @@ int dva_view_occlusion(const int32_t* view_point, const int64_t* images, int64_t
                        int32_t n_k, uint64_t* bits, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------ *
+ * One strided level of the voxel pyramid (since dva_version 334; csrc/voxel_level.hip): what a strided sparse
+ * convolution needs before it can run -- output coordinates, the parent of every input voxel and, for
+ * kernel_size 2 / stride 2 / dilation 1, both kernel maps -- from one sort instead of a torch composition and three
+ * hash tables.  Coordinates int32 [n, 4] = (x, y, z, batch), 16-byte aligned; ratio = the output tensor stride,
+ * in_stride = the input's.  0 <= n < 2^30 (DVA_ERR_UNSUPPORTED beyond); n == 0 is DVA_OK before any pointer is read.
+ *   dva_voxel_bounds      bounds int64 [8] (device) = min x, y, z, batch, max x, y, z, batch of coords.
+ *   dva_voxel_level       bounds: HOST int64 [8], lo and hi of the rows with x, y, z floored to a multiple of ratio
+ *                         (floor towards -inf).  Floor is monotone, so the floored bounds of any finer tensor of the
+ *                         same pyramid are exact.  out_coords int32 [capacity n, 4] = the unique floored rows, ascending
+ *                         (batch, z, y, x); parent int64 [n] = the row of out_coords holding the floored input row;
+ *                         record int64 [2] (device) = n_out, flags:
+ *                           DVA_VOXEL_LEVEL_FLAG_STRIDE  some x, y or z is not a multiple of in_stride (the results are
+ *                                                        valid; dva_voxel_level_maps does not apply)
+ *                           DVA_VOXEL_LEVEL_FLAG_KEY     prod(hi - lo + 1) >= 2^62: nothing else is written
+ *                           DVA_VOXEL_LEVEL_FLAG_BOUNDS  a floored row lies outside bounds: out_coords, parent and n_out
+ *                                                        are unspecified (every access stays inside the buffers)
+ *                         Workspace: dva_voxel_level_workspace_bytes(n) (also that of dva_voxel_bounds).
+ *   dva_voxel_level_maps  after the caller has read the record, for ratio == 2 * in_stride (else DVA_ERR_INVALID):
+ *                         nbr int32 [8, n_out], nbr_t int32 [8, n] as dva_voxel_kernel_map(in, out, offsets) and
+ *                         (out, in, -offsets) give them for the offsets {0, in_stride}^3, z fastest: with d = (c -
+ *                         floor(c)) / in_stride and k = (d_x * 2 + d_y) * 2 + d_z, nbr_t[k][i] = parent[i] and
+ *                         nbr[k][parent[i]] = i (duplicate input rows: the smallest i), -1 elsewhere.  Requires input
+ *                         coordinates that are multiples of in_stride (no STRIDE flag).  A parent outside [0, n_out)
+ *                         writes -1.  No workspace.
+ * Deterministic: integer atomics only (or of flags, min of row ids).
+ * ------------------------------------------------------------------------------------------ */
+#define DVA_VOXEL_LEVEL_FLAG_STRIDE 1
+#define DVA_VOXEL_LEVEL_FLAG_KEY 2
+#define DVA_VOXEL_LEVEL_FLAG_BOUNDS 4
+int64_t dva_voxel_level_workspace_bytes(int64_t n);
+int dva_voxel_bounds(const int32_t* coords, int64_t n, int64_t* bounds, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+int dva_voxel_level(const int32_t* in_coords, int64_t n, int32_t ratio, int32_t in_stride, const int64_t* bounds,
+                    int32_t* out_coords, int64_t* parent, int64_t* record, void* workspace, int64_t workspace_bytes,
+                    void* stream);
+int dva_voxel_level_maps(const int32_t* in_coords, const int64_t* parent, int64_t n, int64_t n_out, int32_t ratio,
+                         int32_t in_stride, int32_t* nbr, int32_t* nbr_t, void* stream);
+
+/* ------------------------------------------------------------------------------------------ *
  * Voxel-grid subsampling.  Replaces GridSampling3D (core/data_transform/grid_transform.py:24-191: torch_cluster
  * grid_cluster, torch_geometric voxel_grid + consecutive_cluster, torch_scatter scatter_add / scatter_mean).
  *   dva_grid_quantize  pos [n, 3] (DVA_GRID_F32 or _F64) -> coords int32 [n, 3] = rint(pos / size), the division
